@@ -5,8 +5,14 @@ A "step" is one pass of the hot path over one batch that is already resident in 
 shard across ranks with no data-path collective, the per-clip result rows are all-gathered once per step (RCCL) when
 N > 1.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the steps, writes the last step's outputs (--dump-outputs) and prints the headline
+line.  Everything else it can measure or check runs only with --full, after the timed region: the PCM-inclusive pass, the
+one-stream pass of the DSP stages (their rooflines), the per-config lines, the CPU baseline and the parity against oracle/.
+
     python bench.py                                   # e2e: MSHDS + openSMILE-style + Wav2Vec2 -> CNN-LSTM, 1 000 clips
-    python bench.py --config C2|C3|C4                 # BASELINE configs 2-4 on their own (own roofline object)
+    python bench.py --full                            # ... plus every measurement and check beyond the headline figure
+    python bench.py --dump-outputs DIR                # ... plus the last timed step's result columns as DIR/<name>.npy
+    python bench.py --config C2|C3|C4                 # BASELINE configs 2-4 on their own (own roofline object; C2: --full)
     python bench.py --total-clips 10000 --gpus 8      # BASELINE config C5 (strong scaling: 1 250 clips per rank)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -28,6 +34,10 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 MFMA_F32_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense fp32 matrix peak
 F64_VECTOR_PEAK_TFLOPS = 78.6  # MI355X_MICROARCH.md: fp64 vector (= fp64 MFMA issue) peak
+DSP_FAMILY_PREFIXES = ("mshds", "praat", "smile")   # kernel families of the stages the one-stream pass re-times
+# figures of the result line that only --full produces (the plain line stays short enough to be read from an output tail)
+FULL_ONLY_KEYS = ("other_rooflines", "c2_level_roofline", "per_config", "inclusive_of_pcie_and_decode", "kernel_time_note",
+                  "kernels", "kernels_one_stream_pass", "family_time_sums")
 
 
 def parse_args():
@@ -44,8 +54,13 @@ def parse_args():
     ap.add_argument("--seconds", type=float, default=30.0)
     ap.add_argument("--pool", type=int, default=64, help="distinct synthetic clips; global clip g plays member g mod pool")
     ap.add_argument("--stages", type=str, default=None, help="override the config's stage list (comma separated)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-inclusive", action="store_true", help="skip the PCM -> H2D -> ... -> D2H pass after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the PCM-inclusive pass, the one-stream pass of the DSP stages, the "
+                         "per-config lines, the CPU baseline and the parity against oracle/, and print every figure they give")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the result columns of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the parity leg")
+    ap.add_argument("--no-inclusive", action="store_true", help="--full without the PCM -> H2D -> ... -> D2H pass")
     ap.add_argument("--cpu-sample-clips", type=int, default=0, help="0 = auto")
     ap.add_argument("--w2v2-chunks-per-call", type=int, default=2048,
                     help="Wav2Vec2 windows per sub-batch (workspace 118 GiB of the 288 GB at 2048)")
@@ -53,7 +68,7 @@ def parse_args():
                     help="run the MSHDS stage on a second HIP stream beside Wav2Vec2 (per-kernel event times then include "
                          "time-sharing, so the roofline object is only clean without it)")
     ap.add_argument("--no-per-config", action="store_true",
-                    help="skip the short BASELINE config C2 / C3 / C4 measurements that the e2e line carries in `per_config`")
+                    help="--full without the short BASELINE config C2 / C3 / C4 measurements that the e2e line carries in `per_config`")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="no GPU work and NOT a measurement: every rank fabricates its shard's rows on the CPU (gloo), the ranks "
                          "run the sharding plan, the all-gather, the barriers and the MAX-over-ranks timing of the real run; "
@@ -131,6 +146,59 @@ def launcher_selftest(args) -> None:
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+# ---- inputs and outputs of the timed path ------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _synth_worker(job):
+    k, seconds = job
+    from robust_speech_analysis_framework_amd import synth
+    return synth.synth_clip(k, seconds)
+
+
+def synth_clips(ids, seconds, workers):
+    """{k: synth.synth_clip(k, seconds)} for the distinct pool members, on ``workers`` processes (the same samples as
+    in-process: every clip is a pure function of its id)."""
+    if workers <= 1 or len(ids) <= 1:
+        from robust_speech_analysis_framework_amd import synth
+        return {k: synth.synth_clip(k, seconds) for k in ids}
+    import concurrent.futures as cf
+    import multiprocessing as mp
+    with cf.ProcessPoolExecutor(max_workers=min(workers, len(ids)), mp_context=mp.get_context("spawn")) as ex:
+        return dict(zip(ids, ex.map(_synth_worker, [(k, seconds) for k in ids])))
+
+
+def output_columns(stages):
+    """(name, width) of the column blocks of a result row, in row order (pipeline.Pipeline.run; C4: the logits alone)."""
+    if stages == ["cnnlstm_only"]:
+        return [("cnnlstm_logits", 2)]
+    blocks = (("mshds", "mshds_features", 25), ("smile", "smile_functionals", 912), ("cnnlstm", "cnnlstm_logits", 2),
+              ("w2v2", "w2v2_frames", 1))
+    return [(name, width) for stage, name, width in blocks if stage in stages]
+
+
+def dump_outputs(path, rows, stages):
+    """The result rows of the last timed step [clips, width], split into their column blocks: DIR/<block>.npy, float32,
+    rows in global clip order.  Above 64 MB in all, a fixed sample of rows (seed 0, ascending) is written instead and its
+    row numbers go to DIR/sample_rows.npy (float64)."""
+    import numpy as np
+    rows = rows.float().cpu().numpy()
+    cols = output_columns(stages)
+    assert sum(w for _, w in cols) == rows.shape[1], f"result row width {rows.shape[1]} != column blocks {cols}"
+    os.makedirs(path, exist_ok=True)
+    n = rows.shape[0]
+    keep = min(n, DUMP_LIMIT_BYTES // (4 * rows.shape[1] + 8))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(path, "sample_rows.npy"), idx.astype(np.float64))
+    c = 0
+    for name, w in cols:
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(rows[:, c:c + w]))
+        c += w
+    log(f"outputs of the last timed step: {', '.join(f'{name} {rows.shape[0]} x {w}' for name, w in cols)} -> {path}")
 
 
 # ---- CPU baseline leg (the only place outside tests/ and smoke() that touches oracle/) -------------------------------
@@ -378,7 +446,7 @@ def main():
         audio_s_per_step = n_total * frames_seconds
     else:
         uniq = sorted(set(members))
-        base = {m: synth.synth_clip(m, args.seconds) for m in uniq}
+        base = synth_clips(uniq, args.seconds, max(1, benchlib.usable_cpus() // world))
         host = np.stack([base[m] for m in members]) if n_local else np.zeros((0, int(args.seconds * 16000)), np.float32)
         wav = torch.from_numpy(host).to(dev)
         pipe = pipeline.Pipeline(stages, device=dev, seconds=args.seconds,
@@ -430,11 +498,13 @@ def main():
     assert m_cols == 0 or (torch.isfinite(local[:, :m_cols]).sum(dim=1) >= 20).all(), "MSHDS rows mostly NaN"
     dup_ok = benchlib.duplicates_bit_identical(local, members)
     assert dup_ok, "rows of duplicated clips differ: results depend on batch position"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, stages)
 
     # inclusive pass (outside the timed region): 16-bit PCM in pinned host memory -> H2D -> decode on the device -> hot
     # path -> D2H of the result rows; reported beside the resident-in-HBM number, never as `value`
     inclusive = None
-    if rank == 0 and not c4 and not args.no_inclusive and n_local:
+    if args.full and rank == 0 and not c4 and not args.no_inclusive and n_local:
         import ctypes as C
         pcm = torch.from_numpy(np.round(host * 32768.0).astype(np.int16)).pin_memory()
         lib = _lib.load()
@@ -461,7 +531,7 @@ def main():
     # (one stream anyway) from the timed region itself.
     prof_one, one_wall = None, None
     dsp = tuple(st for st in ("mshds", "smile") if st in stages)
-    if rank == 0 and world == 1 and pipe is not None and dsp and n_local:
+    if args.full and rank == 0 and world == 1 and pipe is not None and dsp and n_local:
         keep_streams = pipe.mshds.n_streams if pipe.mshds is not None else None
         if pipe.mshds is not None:
             pipe.mshds.n_streams = 1
@@ -482,7 +552,7 @@ def main():
     # BASELINE configs C2 / C3 / C4 on their own, same process, after the timed region (N = 1, e2e only): the same code
     # paths as `--config C2|C3|C4`, 1 warm-up + 2 timed steps each, so that the per-config table is driver-visible
     per_config = None
-    if rank == 0 and world == 1 and args.config == "e2e" and not args.stages and not args.no_per_config and n_local:
+    if args.full and rank == 0 and world == 1 and args.config == "e2e" and not args.stages and not args.no_per_config and n_local:
         per_config = {}
 
         def timed(fn, audio_s):
@@ -558,7 +628,12 @@ def main():
     if rank == 0:
         value = audio_s_per_step * args.steps / dt
         frames = {"mshds_pitch_path": 6000.0 * args.seconds / 30.0, "smile_viterbi": 2998.0 * args.seconds / 30.0}
-        main_prof = {k: v for k, v in prof.items() if prof_one is None or k not in prof_one}
+        if prof_one is not None:
+            main_prof = {k: v for k, v in prof.items() if k not in prof_one}
+        elif dsp and not args.full:      # DSP brackets overlap here: their rooflines come from the one-stream pass (--full)
+            main_prof = {k: v for k, v in prof.items() if not k.startswith(DSP_FAMILY_PREFIXES)}
+        else:
+            main_prof = prof
         roofs = pipeline.rooflines(main_prof, stages, n_local, args.seconds, args.steps, HBM_PEAK_GBS, MFMA_F32_PEAK_TFLOPS,
                                    F64_VECTOR_PEAK_TFLOPS, wall_ms=1e3 * dt, frames_per_launch=frames)
         c2_level = None
@@ -598,8 +673,8 @@ def main():
             "inclusive_of_pcie_and_decode": inclusive,
             "checks": {"finite": True, "duplicate_clips_bit_identical": dup_ok, "gathered": gathered,
                        "rccl_all_gather_executed": bool(world > 1 or force_collective),
-                       "note": "parity vs the CPU oracle is asserted by tests/ (-m gpu) and smoke(); parity_vs_oracle below reports it "
-                               "for the cpu_baseline sample, outside the timed run"},
+                       "note": "parity vs the CPU oracle is asserted by tests/ (-m gpu) and smoke(); with --full, parity_vs_oracle "
+                               "reports it for the cpu_baseline sample, outside the timed run"},
             "kernel_time_note": "per-family HIP-event brackets on the launch stream.  `kernels` = the timed region: Wav2Vec2 / "
                                 "CNN-LSTM families run on one stream (bracket = kernel time); the MSHDS analyses run on three "
                                 "streams beside each other there, so THOSE brackets include waiting and are flagged multi_stream; "
@@ -617,7 +692,10 @@ def main():
                                  "single_stream_families_ms": round(sum(v["ms"] for k, v in prof.items()
                                                                         if not k.startswith(("mshds", "praat"))), 3)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:
+            for k in FULL_ONLY_KEYS:
+                del line[k]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             ref, line["cpu_baseline"] = cpu_baseline(args.config, stages, args.seconds, args.cpu_sample_clips)
             line["parity_vs_oracle"] = parity_vs_oracle(pipe, ref, stages, dev, model)
         print(json.dumps(line), flush=True)
