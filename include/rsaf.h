@@ -255,6 +255,36 @@ int rsaf_w2v2_forward_ragged(const float* wav, const int64_t* chunk_start, const
                              int intermediate, int pos_kernel, int pos_groups, float layer_norm_eps,
                              const float* weights, void* workspace, int64_t workspace_bytes, float* out,
                              const int64_t* out_row_start, rsaf_stream_t stream);
+/* Forward variants of the large Wav2Vec2 checkpoints (wav2vec2-large-lv60, -large-robust, XLSR-53, XLS-R 300M): the _ex entry
+ * points take `flags`, an OR of the bits below; with flags == 0 they are the entry points above (same weight layout, same
+ * workspace, same output bits).  The HF config switch behind each bit:
+ *   RSAF_W2V2_LAYER_FEAT_NORM  feat_extract_norm="layer": every conv layer is conv -> LayerNorm over the C channels of each
+ *                              frame (eps 1e-5, nn.LayerNorm's default, not layer_norm_eps) -> GELU; no GroupNorm
+ *   RSAF_W2V2_CONV_BIAS        conv_bias=True: the 7 feature-encoder convolutions add a bias
+ *   RSAF_W2V2_PRE_LN           do_stable_layer_norm=True: h = x + pos_conv(x) without a LayerNorm; per layer
+ *                              h += attn(LN1(h)); h += FFN(LN2(h)) (LN1 = layers.l.layer_norm, LN2 = final_layer_norm);
+ *                              encoder.layer_norm once after the last layer
+ *   RSAF_W2V2_NO_INPUT_NORM    preprocessor do_normalize=False: the windows go into conv0 without zero-mean / unit variance
+ * Weight segments appended after the last layer (rsaf_w2v2_weight_offsets_ex lists one offset per C-float row of them):
+ *   CONV_BIAS:        cbias[7][C] (conv layer i's bias)
+ *   LAYER_FEAT_NORM:  cln[7][2][C] ({gamma, beta} of conv layer i's LayerNorm; layer 0's lives here, the GroupNorm slots
+ *                     gn_gamma / gn_beta are unused)
+ * Weight floats, offsets and workspace bytes depend on the flags: size every buffer with the _ex calls.                */
+#define RSAF_W2V2_LAYER_FEAT_NORM 1
+#define RSAF_W2V2_CONV_BIAS 2
+#define RSAF_W2V2_PRE_LN 4
+#define RSAF_W2V2_NO_INPUT_NORM 8
+int64_t rsaf_w2v2_weight_floats_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                   int pos_groups, int flags);
+int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                int pos_groups, int flags, int64_t* offsets_host, int cap, int* n_host);
+int64_t rsaf_w2v2_workspace_bytes_ragged_ex(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers,
+                                            int heads, int intermediate, int pos_kernel, int pos_groups, int flags);
+int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, const int* chunk_len,
+                                const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
+                                int intermediate, int pos_kernel, int pos_groups, float layer_norm_eps, int flags,
+                                const float* weights, void* workspace, int64_t workspace_bytes, float* out,
+                                const int64_t* out_row_start, rsaf_stream_t stream);
 
 /* ---- Praat-style analyses behind the MSHDS features (float64) ---------------------------------------
  * Replace the parselmouth/Praat calls of src/mshds_extractor.py: To Intensity (:41,198), To Pitch

@@ -96,6 +96,10 @@ SIGNATURES = {
     "rsaf_w2v2_forward": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _L, _P, _P, _P]),
     "rsaf_w2v2_workspace_bytes_ragged": (_L, [C.POINTER(_I), _I] + [_I] * 7),
     "rsaf_w2v2_forward_ragged": (_I, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _L, _P, _P, _P]),
+    "rsaf_w2v2_weight_floats_ex": (_L, [_I] * 8),
+    "rsaf_w2v2_weight_offsets_ex": (_I, [_I] * 8 + [C.POINTER(_L), _I, C.POINTER(_I)]),
+    "rsaf_w2v2_workspace_bytes_ragged_ex": (_L, [C.POINTER(_I), _I] + [_I] * 8),
+    "rsaf_w2v2_forward_ragged_ex": (_I, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _L, _P, _P, _P]),
 }
 
 _lib = None

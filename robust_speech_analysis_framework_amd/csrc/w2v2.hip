@@ -24,9 +24,13 @@
 namespace rsaf {
 namespace w2v2 {
 
+// flags: the forward variants of the _ex entry points (include/rsaf.h)
+constexpr int F_LAYER_FEAT_NORM = 1, F_CONV_BIAS = 2, F_PRE_LN = 4, F_NO_INPUT_NORM = 8, F_ALL = 15;
+
 struct Cfg {
     int C, Hd, L, NH, I, PK, PG;
     float eps;
+    int flags = 0;
 };
 
 static inline int64_t pad4(int64_t n) { return (n + 3) & ~int64_t(3); }
@@ -40,6 +44,7 @@ struct LayerOff {
 struct Layout {
     int64_t conv0, gng, gnb, conv[6], fplg, fplb, fpw, fpb, posw, posb, elng, elnb;
     std::vector<LayerOff> layers;
+    int64_t cb = -1, cln = -1;       // appended segments: conv biases [7][C] (CONV_BIAS), conv LayerNorms [7][2][C] (LAYER_FEAT_NORM)
     int64_t total;
 };
 
@@ -63,6 +68,8 @@ static Layout make_layout(const Cfg& c) {
         lo.ln2g = take(c.Hd); lo.ln2b = take(c.Hd);
         L.layers.push_back(lo);
     }
+    if (c.flags & F_CONV_BIAS) L.cb = take((int64_t)7 * c.C);
+    if (c.flags & F_LAYER_FEAT_NORM) L.cln = take((int64_t)14 * c.C);
     L.total = o;
     return L;
 }
@@ -76,6 +83,7 @@ static int check_cfg(const Cfg& c) {
     RSAF_CHECK_ARG(c.NH >= 1 && c.Hd % c.NH == 0 && (c.Hd / c.NH) % 4 == 0, "head_dim must be a multiple of 4");
     RSAF_CHECK_ARG(c.PG >= 1 && c.Hd % c.PG == 0 && (c.Hd / c.PG) % 4 == 0 && c.PK >= 2 && c.PK % 2 == 0,
                    "positional conv: channels/group multiple of 4, even kernel");
+    RSAF_CHECK_ARG((c.flags & ~F_ALL) == 0, "unknown RSAF_W2V2_* flag bits");
     return RSAF_OK;
 }
 
@@ -100,6 +108,7 @@ struct Workspace {
     // scales of the activations: per window of the current conv group (conv_scale[7][G], conv_amax[7][G]), per window of
     // the call (pos_scale, fp_amax, win_norm; wlen: the length table of an equal-window call) and per frame (ln / ffn / qkv scales)
     int64_t conv_scale, conv_amax, pos_scale, fp_amax, wlen, win_norm, s_lnfp, s_x, s_ffn, s_att, s_qkv;
+    int64_t cb_max;                                      // CONV_BIAS: max |bias| of conv1..5 (appended after the tables)
     int64_t t_Tw, t_row0, t_ztab, t_rowwin;              // window tables (int32 / int64 views of the float workspace)
     int slabs, Tp, G;
 };
@@ -193,6 +202,7 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     // {rows, output offset} of conv1..6 and of the positional conv), rowwin[rows] window of every encoder row
     w.t_Tw = take((int64_t)7 * n); w.t_row0 = take(2 * ((int64_t)n + 1)); w.t_ztab = take((int64_t)7 * n * 2 * 2);
     w.t_rowwin = take(rows);
+    w.cb_max = (c.flags & F_CONV_BIAS) ? take(8) : -1;
     w.total = o;
     return w;
 }
@@ -231,6 +241,8 @@ __global__ __launch_bounds__(256) void fill_i32_kernel(int* __restrict__ p, int 
 }
 
 // ---- per-chunk zero-mean / unit-variance normalisation -------------------------------------------
+// NORM = false (RSAF_W2V2_NO_INPUT_NORM, HF do_normalize=False): the window's samples go to conv0 as they are
+template <bool NORM>
 __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict__ wav,
                                                         const int64_t* __restrict__ starts, const int* __restrict__ wlen,
                                                         int maxlen, float* __restrict__ xn) {
@@ -239,6 +251,10 @@ __global__ __launch_bounds__(256) void normalize_kernel(const float* __restrict_
     const float* x = wav + starts[blockIdx.x];
     const int len = wlen[blockIdx.x];                        // every window is normalised over its own samples
     float* o = xn + (int64_t)blockIdx.x * maxlen;
+    if (!NORM) {
+        for (int i = threadIdx.x; i < len; i += 256) o[i] = x[i];
+        return;
+    }
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     double s = 0.0;
     for (int i = threadIdx.x; i < len; i += 256) s += (double)x[i];
@@ -272,9 +288,10 @@ __device__ __forceinline__ void split2_w(float xs, unsigned short& h, unsigned s
 // thread <-> channel(s); the 10 samples of a frame are wave-uniform (scalar loads).  Statistics pass: per slab and channel
 // the sum, the sum of squares and the largest |y| (the bound behind the window's plane scale).  Apply pass: the output
 // goes out as the two fp16 planes of GELU(a y + b) * scale[window] (A operand of conv1).
-template <int CPT, bool APPLY>
+// BIAS (RSAF_W2V2_CONV_BIAS): the conv bias joins y before the statistics, as in the checkpoint's Conv1d
+template <int CPT, bool APPLY, bool BIAS>
 __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn, const float* __restrict__ w0,
-                                                    float* __restrict__ part, const float* __restrict__ ab,
+                                                    const float* __restrict__ cb, float* __restrict__ part, const float* __restrict__ ab,
                                                     const float* __restrict__ scale,
                                                     unsigned short* __restrict__ outp, int64_t plane, int len,
                                                     const int* __restrict__ T0w, int T0, int C, int slab, int slabs) {
@@ -282,7 +299,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
     const int chunk = blockIdx.y, sl = blockIdx.x;
     const int t0 = sl * slab, t1 = min(T0w[chunk], t0 + slab);
     const float* __restrict__ x = xn + (int64_t)chunk * len;
-    float wr[CPT][10], a[CPT], b[CPT], s[CPT], q[CPT], mx[CPT];
+    float wr[CPT][10], a[CPT], b[CPT], s[CPT], q[CPT], mx[CPT], bi[CPT];
     int ch[CPT];
     const float sc = APPLY ? scale[chunk] : 1.0f;
 #pragma unroll
@@ -290,6 +307,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
         ch[k] = CPT * threadIdx.x + k;                      // adjacent channels: the planes go out as packed pairs
 #pragma unroll
         for (int j = 0; j < 10; ++j) wr[k][j] = w0[ch[k] * 10 + j];
+        bi[k] = BIAS ? cb[ch[k]] : 0.f;
         s[k] = 0.f; q[k] = 0.f; mx[k] = 0.f;
         if (APPLY) { a[k] = ab[((int64_t)chunk * 2 + 0) * C + ch[k]]; b[k] = ab[((int64_t)chunk * 2 + 1) * C + ch[k]]; }
     }
@@ -304,6 +322,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
             float y = 0.f;
 #pragma unroll
             for (int j = 0; j < 10; ++j) y = fmaf(wr[k][j], xv[j], y);
+            if (BIAS) y += bi[k];
             if (APPLY) {
                 gv[k] = fmaf(y, a[k], b[k]);
             } else {
@@ -347,6 +366,161 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
     }
 }
 
+// ---- layer-norm feature encoder (RSAF_W2V2_LAYER_FEAT_NORM): conv -> LayerNorm over the C channels of a frame -> GELU --------
+// The conv GEMMs read their A operand through a strided, overlapping row view (lda = stride C), so the planes of a conv layer's
+// output carry one power of two per window.  A bound that needs no pass over the data: a normalised element is at most
+// sqrt(C - 1) in magnitude, so |GELU(g n + b)| <= max(max|g| sqrt(C) + max|b|, 0.17) (GELU >= -0.17).  It depends on the
+// weights only: one scale per layer, the same for every window (about 23x loose at C = 512, which the three-product
+// arithmetic absorbs: tests/test_gemm_gpu.py runs scales 4 096x too loose at fp32 accuracy).
+// Wave i < 6 writes layer i's scale into scale[i * G + w] for every window slot w of a group.
+__global__ __launch_bounds__(384) void lnconv_scale_kernel(const float* __restrict__ cln, int C, int G, float* __restrict__ scale) {
+    const int i = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const float* g = cln + (int64_t)2 * i * C;
+    const float* b = g + C;
+    float mg = 0.f, mb = 0.f;
+    for (int c = lane; c < C; c += 64) { mg = fmaxf(mg, fabsf(g[c])); mb = fmaxf(mb, fabsf(b[c])); }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { mg = fmaxf(mg, __shfl_xor(mg, o, 64)); mb = fmaxf(mb, __shfl_xor(mb, o, 64)); }
+    const float bound = fmaxf(mg * sqrtf((float)C) * 1.0001f + mb, 0.17f) * 1.0001f;
+    const float sc = f16x2_scale_for_bound(bound);
+    for (int w = lane; w < G; w += 64) scale[(int64_t)i * G + w] = sc;
+}
+
+// max |bias| of conv1..5 (RSAF_W2V2_CONV_BIAS, group mode): the additive term of the bound behind each layer's plane scale
+__global__ __launch_bounds__(64) void conv_bias_max_kernel(const float* __restrict__ cb, int C, float* __restrict__ out) {
+    for (int i = 1; i < 6; ++i) {
+        float m = 0.f;
+        for (int c = threadIdx.x; c < C; c += 64) m = fmaxf(m, fabsf(cb[(int64_t)i * C + c]));
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        if (threadIdx.x == 0) out[i] = m * 1.000001f;
+    }
+}
+
+// the LayerNorm (eps 1e-5: nn.LayerNorm's default, not layer_norm_eps) of C values spread as CPT per lane over one wave
+template <int CPT>
+__device__ __forceinline__ void conv_ln_gelu_lanes(float (&y)[CPT], const bool (&ok)[CPT], const float (&g)[CPT],
+                                                   const float (&b)[CPT], int C) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) s += ok[k] ? y[k] : 0.f;
+    const float mean = wave_sum(s) / C;
+    float q = 0.f;
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) { const float d = y[k] - mean; q += ok[k] ? d * d : 0.f; }
+    const float rstd = 1.0f / sqrtf(wave_sum(q) / C + 1e-5f);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) y[k] = (y[k] - mean) * rstd * g[k] + b[k];
+#pragma unroll
+    for (int k = 0; k < CPT; k += 2) {
+        const gelu_f32x2 g2 = gelu_pair(gelu_f32x2{y[k], y[k + 1 < CPT ? k + 1 : k]});
+        y[k] = g2.x;
+        if (k + 1 < CPT) y[k + 1] = g2.y;
+    }
+}
+
+// conv0 (1 -> C, k 10, s 5, optional bias) + LayerNorm over the channels + GELU in one pass: one wave per frame, lane l holds
+// channels CPT l .. CPT l + CPT - 1; the output goes out as the two fp16 planes of conv1's A under the window's scale
+template <int CPT>
+__global__ __launch_bounds__(256) void conv0_ln_kernel(const float* __restrict__ xn, const float* __restrict__ w0,
+                                                       const float* __restrict__ cb, const float* __restrict__ lg,
+                                                       const float* __restrict__ lb, const float* __restrict__ scale,
+                                                       unsigned short* __restrict__ outp, int64_t plane, int len,
+                                                       const int* __restrict__ T0w, int T0, int C, int frames) {
+    const int chunk = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int t0 = blockIdx.x * frames, t1 = min(T0w[chunk], t0 + frames);
+    const float* __restrict__ x = xn + (int64_t)chunk * len;
+    float wr[CPT][10], bi[CPT], g[CPT], b[CPT];
+    bool ok[CPT];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        const int c = CPT * lane + k;
+        ok[k] = c < C;
+        const int cc = ok[k] ? c : 0;
+#pragma unroll
+        for (int j = 0; j < 10; ++j) wr[k][j] = w0[cc * 10 + j];
+        bi[k] = cb ? cb[cc] : 0.f;
+        g[k] = lg[cc];
+        b[k] = lb[cc];
+    }
+    const float sc = scale[chunk];
+    for (int t = t0 + wv; t < t1; t += 4) {
+        float xv[10];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) xv[j] = x[5 * t + j];
+        float y[CPT];
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            float v = 0.f;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) v = fmaf(wr[k][j], xv[j], v);
+            y[k] = v + bi[k];
+        }
+        conv_ln_gelu_lanes<CPT>(y, ok, g, b, C);
+        unsigned short hh[CPT], ll[CPT];
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) split2_w(y[k] * sc, hh[k], ll[k]);
+        const int64_t o = ((int64_t)chunk * T0 + t) * C + CPT * lane;
+        if (CPT % 2 == 0) {                                 // 4-byte stores of channel pairs (ok[k] implies ok[k + 1]: C even)
+#pragma unroll
+            for (int k = 0; k < CPT; k += 2)
+                if (ok[k]) {
+                    *reinterpret_cast<unsigned*>(outp + o + k) = hh[k] | ((unsigned)hh[k + 1 < CPT ? k + 1 : k] << 16);
+                    *reinterpret_cast<unsigned*>(outp + plane + o + k) = ll[k] | ((unsigned)ll[k + 1 < CPT ? k + 1 : k] << 16);
+                }
+        } else {
+#pragma unroll
+            for (int k = 0; k < CPT; ++k)
+                if (ok[k]) { outp[o + k] = hh[k]; outp[plane + o + k] = ll[k]; }
+        }
+    }
+}
+
+// conv1..5 in layer mode: the GEMM wrote fp32 rows (window w's frame t at row w Ti + t); LayerNorm -> GELU -> the planes of the
+// next conv's A under the window's scale.  One wave per row (C <= 1024); rows past a window's own frame count are skipped.
+__global__ __launch_bounds__(256) void conv_ln_gelu_kernel(const float* __restrict__ src, const float* __restrict__ lg,
+                                                           const float* __restrict__ lb, const float* __restrict__ scale,
+                                                           unsigned short* __restrict__ outp, int64_t plane, int64_t rows,
+                                                           int Ti, const int* __restrict__ Tiw, int C) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int w = (int)(row / Ti);
+    if (row - (int64_t)w * Ti >= Tiw[w]) return;
+    const int lane = threadIdx.x & 63, C4 = C >> 2;
+    const float4* s4 = reinterpret_cast<const float4*>(src + row * C);
+    const float4* g4 = reinterpret_cast<const float4*>(lg);
+    const float4* b4 = reinterpret_cast<const float4*>(lb);
+    float y[16], g[16], b[16];
+    bool ok[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = lane + 64 * i;
+        const bool v = idx < C4;
+        const float4 a = v ? s4[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 gg = v ? g4[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float4 bb = v ? b4[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+        y[4 * i] = a.x; y[4 * i + 1] = a.y; y[4 * i + 2] = a.z; y[4 * i + 3] = a.w;
+        g[4 * i] = gg.x; g[4 * i + 1] = gg.y; g[4 * i + 2] = gg.z; g[4 * i + 3] = gg.w;
+        b[4 * i] = bb.x; b[4 * i + 1] = bb.y; b[4 * i + 2] = bb.z; b[4 * i + 3] = bb.w;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ok[4 * i + k] = v;
+    }
+    conv_ln_gelu_lanes<16>(y, ok, g, b, C);
+    const float sc = scale[w];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = lane + 64 * i;
+        if (idx < C4) {
+            unsigned short hh[4], ll[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) split2_w(y[4 * i + k] * sc, hh[k], ll[k]);
+            unsigned short* pp = outp + row * C + 4 * idx;
+            *reinterpret_cast<uint2*>(pp) = make_uint2(hh[0] | ((unsigned)hh[1] << 16), hh[2] | ((unsigned)hh[3] << 16));
+            *reinterpret_cast<uint2*>(pp + plane) = make_uint2(ll[0] | ((unsigned)ll[1] << 16), ll[2] | ((unsigned)ll[3] << 16));
+        }
+    }
+}
+
 // GroupNorm coefficients per (window, channel) and the window's bound: |GELU(a y + b)| <= |a| max|y| + |b|
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, const float* __restrict__ g,
                                                           const float* __restrict__ be, float* __restrict__ ab,
@@ -378,6 +552,9 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 // Optional outputs for the GEMM that reads the result: the row as two fp16 planes times the power of two that puts the
 // row's largest magnitude into [2^14, 2^15) (scale_out[row]: exact, the wave holds the whole row), and the scale the NEXT
 // GEMM's plane output may use for this row (bound_scale_out): |GELU(y W^T + b)| <= |y|_2 max_n |w_n|_2 + max |b|.
+// VAR 1 (stable-layer-norm encoder): the un-normalised sum x + r also goes to aux (the fp32 residual stream).
+// VAR 2 (conv6 of the layer-norm feature encoder): the row first takes its conv LayerNorm (pg, pb, eps 1e-5) and GELU.
+template <int VAR>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ r,
                                                         const float* __restrict__ g, const float* __restrict__ b,
                                                         float* __restrict__ out, int64_t rows, int D, float eps,
@@ -386,7 +563,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                                                         unsigned short* __restrict__ planes, int64_t plane, int panel,
                                                         float* __restrict__ scale_out, const unsigned* __restrict__ bound_w,
                                                         const unsigned* __restrict__ bound_b, float* __restrict__ bound_scale_out,
-                                                        unsigned* __restrict__ win_norm) {
+                                                        unsigned* __restrict__ win_norm, const float* __restrict__ pg,
+                                                        const float* __restrict__ pb, float* __restrict__ aux) {
     // panel != 0: the planes go out in the k16-panel layout of `rows` rows (gemm_f16x3.h), staged through LDS so that the
     // four rows of the workgroup leave as full 128-byte lines per panel (scattering 8-byte pieces from the row layout cost
     // this kernel + 77 %)
@@ -412,6 +590,32 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             v[i] = x4[idx];
             if (r4) { const float4 t = r4[idx]; v[i].x += t.x; v[i].y += t.y; v[i].z += t.z; v[i].w += t.w; }
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+            if (VAR == 1 && valid) reinterpret_cast<float4*>(aux + row * D)[idx] = v[i];
+        }
+    }
+    if constexpr (VAR == 2) {
+        const float m0 = wave_sum(s) / D;
+        float q0 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = lane + 64 * i;
+            if (idx < D4) {
+                const float a = v[i].x - m0, bb = v[i].y - m0, c = v[i].z - m0, d = v[i].w - m0;
+                q0 += (a * a + bb * bb) + (c * c + d * d);
+            }
+        }
+        const float r0 = 1.0f / sqrtf(wave_sum(q0) / D + 1e-5f);
+        s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = lane + 64 * i;
+            if (idx < D4) {
+                const float4 gg = reinterpret_cast<const float4*>(pg)[idx], bb = reinterpret_cast<const float4*>(pb)[idx];
+                const gelu_f32x2 e0 = gelu_pair(gelu_f32x2{(v[i].x - m0) * r0 * gg.x + bb.x, (v[i].y - m0) * r0 * gg.y + bb.y});
+                const gelu_f32x2 e1 = gelu_pair(gelu_f32x2{(v[i].z - m0) * r0 * gg.z + bb.z, (v[i].w - m0) * r0 * gg.w + bb.w});
+                v[i] = make_float4(e0.x, e0.y, e1.x, e1.y);
+                s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+            }
         }
     }
     const float mean = wave_sum(s) / D;
@@ -994,20 +1198,28 @@ static int ln(const float* x, const float* r, const float* g, const float* b, fl
               float eps, hipStream_t s, const int64_t* out_row_start = nullptr, const int* rowwin = nullptr,
               const int64_t* row0 = nullptr, unsigned short* planes = nullptr, bool panel = false, float* scale_out = nullptr,
               const unsigned* bound_w = nullptr, const unsigned* bound_b = nullptr, float* bound_scale_out = nullptr,
-              unsigned* win_norm = nullptr) {
+              unsigned* win_norm = nullptr, int var = 0, const float* pg = nullptr, const float* pb = nullptr,
+              float* aux = nullptr) {
     const int64_t blocks = (rows + 3) / 4;
     RSAF_CHECK_ARG(blocks <= 0x7fffffffLL, "too many rows");
     RSAF_CHECK_ARG(!planes || scale_out, "planes need their scale array");
     RSAF_CHECK_ARG(!win_norm || rowwin, "the per-window norm needs the row -> window map");
-    ProfScope prof("w2v2_layernorm", s, 0.0, (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0)));
-    hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, r, g, b, out, rows, D, eps,
-                       out_row_start, rowwin, row0, planes, rows * D, panel ? 1 : 0, scale_out, bound_w, bound_b, bound_scale_out, win_norm);
+    RSAF_CHECK_ARG((var != 1 || aux) && (var != 2 || (pg && pb)), "layernorm variant without its operands");
+    ProfScope prof("w2v2_layernorm", s, 0.0, (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0) + (aux ? 4 : 0)));
+#define RSAF_LN(V)                                                                                                         \
+    hipLaunchKernelGGL(layernorm_kernel<V>, dim3((unsigned)blocks), dim3(256), 0, s, x, r, g, b, out, rows, D, eps,         \
+                       out_row_start, rowwin, row0, planes, rows * D, panel ? 1 : 0, scale_out, bound_w, bound_b, bound_scale_out, \
+                       win_norm, pg, pb, aux)
+    if (var == 1) RSAF_LN(1);
+    else if (var == 2) RSAF_LN(2);
+    else RSAF_LN(0);
+#undef RSAF_LN
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
 
-template <bool APPLY>
-static int conv0_launch(const Cfg& c, const float* xn, const float* w0, float* part, const float* ab, const float* scale,
+template <bool APPLY, bool BIAS>
+static int conv0_launch(const Cfg& c, const float* xn, const float* w0, const float* cb, float* part, const float* ab, const float* scale,
                         unsigned short* outp, int64_t plane, int n, int len, const int* T0w, int T0, int slab, int slabs, hipStream_t s) {
     const int threads = c.C <= 256 ? c.C : 256;
     const int cpt = c.C / threads;
@@ -1018,7 +1230,7 @@ static int conv0_launch(const Cfg& c, const float* xn, const float* w0, float* p
     ProfScope prof(APPLY ? "w2v2_conv0_apply" : "w2v2_conv0_stats", s, 0.0,
                    APPLY ? (double)n * ((double)c.C * T0 * 4.0 + 4.0 * (5.0 * T0 + 5.0)) : (double)n * 4.0 * (5.0 * T0 + 5.0));
 #define RSAF_C0(CPT)                                                                                       \
-    hipLaunchKernelGGL((conv0_kernel<CPT, APPLY>), grid, dim3(threads), 0, s, xn, w0, part, ab, scale, outp, plane, len, T0w, T0, \
+    hipLaunchKernelGGL((conv0_kernel<CPT, APPLY, BIAS>), grid, dim3(threads), 0, s, xn, w0, cb, part, ab, scale, outp, plane, len, T0w, T0, \
                        c.C, slab, slabs)
     switch (cpt) {
         case 1: RSAF_C0(1); break;
@@ -1028,6 +1240,32 @@ static int conv0_launch(const Cfg& c, const float* xn, const float* w0, float* p
         default: set_error("conv0: unsupported conv_dim"); return RSAF_ERR_ARG;
     }
 #undef RSAF_C0
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// conv0 + LayerNorm + GELU of the layer-norm feature encoder (one pass, 64 frames per workgroup)
+static int conv0_ln_launch(const Cfg& c, const float* xn, const float* w0, const float* cb, const float* lg, const float* lb,
+                           const float* scale, unsigned short* outp, int64_t plane, int n, int len, const int* T0w, int T0,
+                           int T0g, hipStream_t s) {
+    constexpr int FR = 64;
+    dim3 grid((unsigned)((T0g + FR - 1) / FR), (unsigned)n);
+    ProfScope prof("w2v2_conv0_ln", s, 0.0, (double)n * ((double)c.C * T0g * 4.0 + 4.0 * (5.0 * T0g + 5.0)));
+    const int cpt = (c.C + 63) / 64;
+#define RSAF_C0L(CPT)                                                                                                      \
+    hipLaunchKernelGGL((conv0_ln_kernel<CPT>), grid, dim3(256), 0, s, xn, w0, cb, lg, lb, scale, outp, plane, len, T0w, T0, \
+                       c.C, FR)
+    switch (cpt) {
+        case 1: RSAF_C0L(1); break;
+        case 2: RSAF_C0L(2); break;
+        case 3: RSAF_C0L(3); break;
+        case 4: RSAF_C0L(4); break;
+        case 8: RSAF_C0L(8); break;
+        case 12: RSAF_C0L(12); break;
+        case 16: RSAF_C0L(16); break;
+        default: set_error("conv0: unsupported conv_dim"); return RSAF_ERR_ARG;
+    }
+#undef RSAF_C0L
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
@@ -1053,9 +1291,22 @@ int64_t rsaf_w2v2_weight_floats(int conv_dim, int hidden, int layers, int heads,
     return make_layout(c).total;
 }
 
+int64_t rsaf_w2v2_weight_floats_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                   int pos_groups, int flags) {
+    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
+    if (check_cfg(c) != RSAF_OK) return -1;
+    return make_layout(c).total;
+}
+
 int rsaf_w2v2_weight_offsets(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                              int pos_groups, int64_t* offsets_host, int cap, int* n_host) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f};
+    return rsaf_w2v2_weight_offsets_ex(conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 0, offsets_host,
+                                       cap, n_host);
+}
+
+int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                int pos_groups, int flags, int64_t* offsets_host, int cap, int* n_host) {
+    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
     int rc = check_cfg(c);
     if (rc != RSAF_OK) return rc;
     RSAF_CHECK_ARG(offsets_host && n_host, "NULL output");
@@ -1066,6 +1317,9 @@ int rsaf_w2v2_weight_offsets(int conv_dim, int hidden, int layers, int heads, in
     for (const LayerOff& lo : L.layers)
         for (int64_t o : {lo.wqkv, lo.bqkv, lo.wo, lo.bo, lo.ln1g, lo.ln1b, lo.w1, lo.b1, lo.w2, lo.b2, lo.ln2g, lo.ln2b})
             v.push_back(o);
+    // appended segments, one offset per C-float row: conv biases 0..6, then {gamma, beta} of the conv LayerNorms 0..6
+    if (L.cb >= 0) for (int i = 0; i < 7; ++i) v.push_back(L.cb + (int64_t)i * c.C);
+    if (L.cln >= 0) for (int i = 0; i < 14; ++i) v.push_back(L.cln + (int64_t)i * c.C);
     RSAF_CHECK_ARG(cap >= (int)v.size(), "offsets_host too small");
     for (size_t i = 0; i < v.size(); ++i) offsets_host[i] = v[i];
     *n_host = (int)v.size();
@@ -1089,7 +1343,13 @@ int64_t rsaf_w2v2_workspace_bytes(int n_chunks, int chunk_len, int conv_dim, int
 
 int64_t rsaf_w2v2_workspace_bytes_ragged(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
                                          int intermediate, int pos_kernel, int pos_groups) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f};
+    return rsaf_w2v2_workspace_bytes_ragged_ex(chunk_len_host, n_chunks, conv_dim, hidden, layers, heads, intermediate, pos_kernel,
+                                               pos_groups, 0);
+}
+
+int64_t rsaf_w2v2_workspace_bytes_ragged_ex(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
+                                            int intermediate, int pos_kernel, int pos_groups, int flags) {
+    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
     if (check_cfg(c) != RSAF_OK || n_chunks <= 0 || !chunk_len_host) return -1;
     Rag R;
     if (make_rag(chunk_len_host, n_chunks, R) != RSAF_OK) return -1;
@@ -1115,7 +1375,16 @@ int rsaf_w2v2_forward_ragged(const float* wav, const int64_t* chunk_start, const
                              int n_chunks, int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                              int pos_groups, float layer_norm_eps, const float* weights, void* workspace,
                              int64_t workspace_bytes, float* out, const int64_t* out_row_start, rsaf_stream_t stream) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps};
+    return rsaf_w2v2_forward_ragged_ex(wav, chunk_start, chunk_len, chunk_len_host, n_chunks, conv_dim, hidden, layers, heads,
+                                       intermediate, pos_kernel, pos_groups, layer_norm_eps, 0, weights, workspace, workspace_bytes,
+                                       out, out_row_start, stream);
+}
+
+int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, const int* chunk_len, const int* chunk_len_host,
+                                int n_chunks, int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                int pos_groups, float layer_norm_eps, int flags, const float* weights, void* workspace,
+                                int64_t workspace_bytes, float* out, const int64_t* out_row_start, rsaf_stream_t stream) {
+    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags};
     int rc = check_cfg(c);
     if (rc != RSAF_OK) return rc;
     RSAF_CHECK_ARG(n_chunks >= 0, "negative chunk count");
@@ -1217,22 +1486,65 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     const int n_groups = (n + W.G - 1) / W.G, gstep = (n + n_groups - 1) / n_groups;
     float* cscale = ws + W.conv_scale;                       // [7][G]: scale of layer i's plane output, per window of the group
     unsigned* camax = bits_at(W.conv_amax);                  // [7][G]: largest |output| of layer i (layer 0: its bound)
+    const bool layer_norm = c.flags & F_LAYER_FEAT_NORM, conv_bias = c.flags & F_CONV_BIAS;
+    const float* cbias = conv_bias ? Wt + L.cb : nullptr;    // [7][C]
+    const float* cln = Wt + L.cln;                           // [7][2][C] (layer mode)
+    float* cb_max = conv_bias ? ws + W.cb_max : nullptr;     // [8]: max |bias| of conv1..5 at 1..5
+    if (layer_norm) {                                        // layer mode: the planes' scales depend on the weights only
+        hipLaunchKernelGGL(lnconv_scale_kernel, dim3(1), dim3(384), 0, s, cln, C, W.G, cscale);
+        RSAF_CHECK_HIP(hipGetLastError());
+    } else if (conv_bias) {
+        hipLaunchKernelGGL(conv_bias_max_kernel, dim3(1), dim3(64), 0, s, cbias, C, cb_max);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
     for (int g0 = 0; g0 < n; g0 += gstep) {
         const int g = std::min(gstep, n - g0);
         // the group's longest window is its first (lengths are non-increasing): its frame counts size the group's launches
         int Tg[7];
         chunk_lengths(R.len[g0], Tg);
-        RSAF_CHECK_HIP(hipMemsetAsync(camax, 0, sizeof(unsigned) * 7 * W.G, s));
-        // 1. per-chunk normalisation (HF feature extractor)
+        if (!layer_norm) RSAF_CHECK_HIP(hipMemsetAsync(camax, 0, sizeof(unsigned) * 7 * W.G, s));
+        // 1. per-chunk normalisation (HF feature extractor; NO_INPUT_NORM: do_normalize=False, a copy)
         {
             ProfScope prof("w2v2_normalize", s, 0.0, (double)g * R.len[g0] * 4 * 3);
-            hipLaunchKernelGGL(normalize_kernel, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
+            if (c.flags & F_NO_INPUT_NORM)
+                hipLaunchKernelGGL(normalize_kernel<false>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
+            else
+                hipLaunchKernelGGL(normalize_kernel<true>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
             RSAF_CHECK_HIP(hipGetLastError());
+        }
+        if (layer_norm) {
+            // 2-3 (layer mode). conv0 + LayerNorm + GELU in one pass; conv1..6 as GEMMs writing fp32 rows (+ bias) into the Q buffer,
+            // then LayerNorm -> GELU -> planes back into P (the GEMM has consumed them); conv6 writes its packed rows, and its
+            // LayerNorm + GELU join the feature projection's LayerNorm (step 4)
+            if ((rc = conv0_ln_launch(c, ws + W.xn, Wt + L.conv0, cbias, cln, cln + C, cscale, planes_at(W.P), (int64_t)W.G * T[0] * C,
+                                      g, R.maxlen, Tw + g0, T[0], Tg[0], s))) return rc;
+            for (int i = 1; i < 7; ++i) {
+                const bool last = i == 6;
+                Out o{};
+                if (last) { o.Cf = ws + W.c6; o.sC = 0; }
+                else { o.Cf = ws + W.Q; o.sC = (int64_t)T[i] * C; }
+                rc = gemm3(planes_at(W.P), (int64_t)W.G * T[i - 1] * C, (int64_t)STRD[i] * C, (int64_t)T[i - 1] * C, cscale + (int64_t)(i - 1) * W.G,
+                           1, 0, planes_at(W.wp_conv[i - 1]), ws + W.ws_conv[i - 1], Tg[i], C, KERN[i] * C, o,
+                           conv_bias ? cbias + (int64_t)i * C : nullptr, nullptr, g, ACT_NONE, "w2v2_gemm", false, nullptr, 0, nullptr, 0,
+                           ztab + ((int64_t)(i - 1) * n + g0) * 2);
+                if (rc) return rc;
+                if (!last) {
+                    const int64_t lrows = (int64_t)g * T[i];
+                    ProfScope prof("w2v2_conv_ln", s, 0.0, (double)lrows * C * 8.0);
+                    hipLaunchKernelGGL(conv_ln_gelu_kernel, dim3((unsigned)((lrows + 3) / 4)), dim3(256), 0, s, ws + W.Q,
+                                       cln + (int64_t)2 * i * C, cln + (int64_t)(2 * i + 1) * C, cscale + (int64_t)i * W.G,
+                                       planes_at(W.P), (int64_t)W.G * T[i] * C, lrows, T[i], Tw + (int64_t)i * n + g0, C);
+                    RSAF_CHECK_HIP(hipGetLastError());
+                }
+            }
+            continue;
         }
         // 2. conv0 + GroupNorm + GELU (stats pass, finalize, apply pass); the apply pass writes fp16 plane pairs
         const int slabs_g = (Tg[0] + STAT_SLAB - 1) / STAT_SLAB;
-        rc = conv0_launch<false>(c, ws + W.xn, Wt + L.conv0, ws + W.part, nullptr, nullptr, nullptr, 0, g, R.maxlen, Tw + g0, T[0],
-                                 STAT_SLAB, slabs_g, s);
+        rc = conv_bias ? conv0_launch<false, true>(c, ws + W.xn, Wt + L.conv0, cbias, ws + W.part, nullptr, nullptr, nullptr, 0, g,
+                                                   R.maxlen, Tw + g0, T[0], STAT_SLAB, slabs_g, s)
+                       : conv0_launch<false, false>(c, ws + W.xn, Wt + L.conv0, nullptr, ws + W.part, nullptr, nullptr, nullptr, 0, g,
+                                                    R.maxlen, Tw + g0, T[0], STAT_SLAB, slabs_g, s);
         if (rc) return rc;
         {
             const int64_t tot = (int64_t)g * C;
@@ -1243,8 +1555,10 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
         }
         {
             const int slab = 128;
-            rc = conv0_launch<true>(c, ws + W.xn, Wt + L.conv0, nullptr, ws + W.ab, cscale, planes_at(W.P), (int64_t)W.G * T[0] * C, g,
-                                    R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s);
+            rc = conv_bias ? conv0_launch<true, true>(c, ws + W.xn, Wt + L.conv0, cbias, nullptr, ws + W.ab, cscale, planes_at(W.P),
+                                                      (int64_t)W.G * T[0] * C, g, R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s)
+                           : conv0_launch<true, false>(c, ws + W.xn, Wt + L.conv0, nullptr, nullptr, ws + W.ab, cscale, planes_at(W.P),
+                                                       (int64_t)W.G * T[0] * C, g, R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s);
             if (rc) return rc;
         }
         // 3. conv1..6 as GEMMs over the channels-last sequence (lda = stride * C, K = taps * C) with fused GELU;
@@ -1261,13 +1575,15 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
             Out o{};
             if (last) { o.Cf = ws + W.c6; o.sC = 0; }
             else {
+                // (CONV_BIAS: + max |bias| of layer i)
                 if ((rc = launch_scale_from_bound(camax + (int64_t)(i - 1) * W.G, g, reinterpret_cast<const float*>(wstat(wstat_conv(i - 1))),
-                                                  sqrtf((float)K) * 1.00001f, nullptr, cscale + (int64_t)i * W.G, s))) return rc;
+                                                  sqrtf((float)K) * 1.00001f, conv_bias ? cb_max + i : nullptr, cscale + (int64_t)i * W.G, s))) return rc;
                 o.Cp = nxt; o.c_plane = (int64_t)W.G * T[i] * C; o.sCp = (int64_t)T[i] * C; o.sC = (int64_t)T[i] * C;
                 o.c_scale = cscale + (int64_t)i * W.G; o.cs_zs = 1; o.cs_ms = 0;
             }
             rc = gemm3(cur, (int64_t)W.G * T[i - 1] * C, (int64_t)STRD[i] * C, (int64_t)T[i - 1] * C, cscale + (int64_t)(i - 1) * W.G, 1, 0,
-                       planes_at(W.wp_conv[i - 1]), ws + W.ws_conv[i - 1], Tg[i], C, K, o, nullptr, nullptr, g, ACT_GELU, "w2v2_gemm",
+                       planes_at(W.wp_conv[i - 1]), ws + W.ws_conv[i - 1], Tg[i], C, K, o, conv_bias ? cbias + (int64_t)i * C : nullptr,
+                       nullptr, g, ACT_GELU, "w2v2_gemm",
                        false, last ? nullptr : camax + (int64_t)i * W.G, 1, nullptr, 0, ztab + ((int64_t)(i - 1) * n + g0) * 2);
             if (rc) return rc;
             std::swap(cur, nxt);
@@ -1275,7 +1591,11 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     }
     // 4. feature projection: LayerNorm (-> planes, exact row scales) + Linear; its epilogue reports max |x| per window
     RSAF_CHECK_HIP(hipMemsetAsync(ws + W.fp_amax, 0, sizeof(unsigned) * n, s));
-    rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true, ws + W.s_lnfp);
+    if (layer_norm)                                          // conv6's LayerNorm (eps 1e-5) + GELU first, in the same row pass
+        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true,
+                ws + W.s_lnfp, nullptr, nullptr, nullptr, nullptr, 2, cln + (int64_t)12 * C, cln + (int64_t)13 * C);
+    else
+        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true, ws + W.s_lnfp);
     if (rc) return rc;
     {
         Out o{}; o.Cf = ws + W.x;
@@ -1370,11 +1690,19 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
         }
         // (fused attention: this LayerNorm also reports the window's largest row norm, behind the scale of layer 0's q / k / v)
         if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
-        rc = ln(ws + W.x, ws + W.y, Wt + L.elng, Wt + L.elnb, ws + W.x, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp), true, ws + W.s_x,
-                nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr);
+        if (c.flags & F_PRE_LN)   // stable layer norm: h = x + pos stays un-normalised (the residual stream); layer 0's LN1(h) -> planes
+            rc = ln(ws + W.x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0,
+                    planes_at(W.xp), true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 1, nullptr, nullptr,
+                    ws + W.x);
+        else
+            rc = ln(ws + W.x, ws + W.y, Wt + L.elng, Wt + L.elnb, ws + W.x, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp), true, ws + W.s_x,
+                    nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr);
         if (rc) return rc;
     }
-    // 6. encoder layers (post-LN)
+    // 6. encoder layers.  Post-LN: y = attn + x, x = LN1(y), y = ffn(x) + x, x = LN2(y).  PRE_LN (stable layer norm): the
+    //    residual stream h ping-pongs between x and y: y = attn(LN1(x)) + x, x = ffn(LN2(y)) + y, and the LayerNorms write
+    //    planes only (LN1 of the next layer, or encoder.layer_norm into `out` after the last one)
+    const bool pre_ln = c.flags & F_PRE_LN;
     float* x = ws + W.x;
     for (int l = 0; l < c.L; ++l) {
         const LayerOff& lo = L.layers[l];
@@ -1451,8 +1779,12 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
             rc = gemm3(planes_at(W.attp), rows * Hd, Hd, 0, fused ? ws + W.s_qkv : ws + W.s_att, 0, 1, planes_at(W.wp_o[l]), ws + W.ws_o[l], (int)rows, Hd, Hd, o,
                        Wt + lo.bo, x, 1, ACT_NONE, "w2v2_gemm", true);
             if (rc) return rc;
-            rc = ln(ws + W.y, nullptr, Wt + lo.ln1g, Wt + lo.ln1b, x, rows, Hd, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.xp), true, ws + W.s_x,
-                    wstat(b0 + 2), wstat(b0 + 4), ws + W.s_ffn);
+            if (pre_ln)
+                rc = ln(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, nullptr, rows, Hd, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.xp), true,
+                        ws + W.s_x, wstat(b0 + 2), wstat(b0 + 4), ws + W.s_ffn);
+            else
+                rc = ln(ws + W.y, nullptr, Wt + lo.ln1g, Wt + lo.ln1b, x, rows, Hd, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.xp), true, ws + W.s_x,
+                        wstat(b0 + 2), wstat(b0 + 4), ws + W.s_ffn);
             if (rc) return rc;
         }
         {   // feed forward: the GELU output only exists as planes (A of the second GEMM)
@@ -1460,11 +1792,23 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
             rc = gemm3(planes_at(W.xp), rows * Hd, Hd, 0, ws + W.s_x, 0, 1, planes_at(W.wp_1[l]), ws + W.ws_1[l], (int)rows, c.I, Hd, o1,
                        Wt + lo.b1, nullptr, 1, ACT_GELU, "w2v2_gemm", true);
             if (rc) return rc;
-            Out o2{}; o2.Cf = ws + W.y;
+            Out o2{}; o2.Cf = pre_ln ? x : ws + W.y;
             rc = gemm3(planes_at(W.ffnp), rows * c.I, c.I, 0, ws + W.s_ffn, 0, 1, planes_at(W.wp_2[l]), ws + W.ws_2[l], (int)rows, Hd, c.I, o2,
-                       Wt + lo.b2, x, 1, ACT_NONE, "w2v2_gemm", true);
+                       Wt + lo.b2, pre_ln ? ws + W.y : x, 1, ACT_NONE, "w2v2_gemm", true);
             if (rc) return rc;
             const bool last = (l == c.L - 1);
+            if (pre_ln) {
+                if (last) {
+                    rc = ln(x, nullptr, Wt + L.elng, Wt + L.elnb, out, rows, Hd, c.eps, s, out_row_start, rowwin, row0);
+                } else {
+                    if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
+                    const LayerOff& ln_next = L.layers[l + 1];
+                    rc = ln(x, nullptr, Wt + ln_next.ln1g, Wt + ln_next.ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp),
+                            true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr);
+                }
+                if (rc) return rc;
+                continue;
+            }
             // the last LayerNorm writes frame t of window w at out_row_start[w] + t (or packed, window after window)
             if (fused && !last) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
             rc = ln(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, last ? out : x, rows, Hd, c.eps, s,

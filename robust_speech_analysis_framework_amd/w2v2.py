@@ -28,16 +28,16 @@ def _cfg_args(cfg: W2V2Config):
 
 def weight_offsets(cfg: W2V2Config):
     lib = _lib.load()
-    cap = 32 + 12 * cfg.num_hidden_layers
+    cap = 32 + 21 + 12 * cfg.num_hidden_layers
     buf = (C.c_int64 * cap)()
     n = C.c_int(0)
-    _lib.check(lib.rsaf_w2v2_weight_offsets(*_cfg_args(cfg), buf, cap, C.byref(n)), "rsaf_w2v2_weight_offsets")
-    return [int(buf[i]) for i in range(n.value)], int(lib.rsaf_w2v2_weight_floats(*_cfg_args(cfg)))
+    _lib.check(lib.rsaf_w2v2_weight_offsets_ex(*_cfg_args(cfg), cfg.flags, buf, cap, C.byref(n)), "rsaf_w2v2_weight_offsets_ex")
+    return [int(buf[i]) for i in range(n.value)], int(lib.rsaf_w2v2_weight_floats_ex(*_cfg_args(cfg), cfg.flags))
 
 
 def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
-    """HF-keyed state_dict -> the float32 blob of ``rsaf_w2v2_forward`` (weight norm folded,
-    conv kernels tap-major, q/k/v fused)."""
+    """HF-keyed state_dict -> the float32 blob of ``rsaf_w2v2_forward_ragged_ex`` (weight norm folded,
+    conv kernels tap-major, q/k/v fused; conv biases and conv LayerNorms appended per ``cfg.flags``)."""
     cfg.validate()
     offs, total = weight_offsets(cfg)
     blob = np.zeros(total, dtype=np.float32)
@@ -49,9 +49,11 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
         blob[o:o + a.size] = a.astype(np.float32)
 
     g = lambda k: np.asarray(sd[k], dtype=np.float64)                               # noqa: E731
+    layer = cfg.feat_extract_norm == "layer"
     put(g("feature_extractor.conv_layers.0.conv.weight")[:, 0, :])
-    put(g("feature_extractor.conv_layers.0.layer_norm.weight"))
-    put(g("feature_extractor.conv_layers.0.layer_norm.bias"))
+    # GroupNorm slots (layer mode: unused, left zero; layer 0's LayerNorm goes to the appended segment)
+    put(0.0 * g("feature_extractor.conv_layers.0.layer_norm.weight") if layer else g("feature_extractor.conv_layers.0.layer_norm.weight"))
+    put(0.0 * g("feature_extractor.conv_layers.0.layer_norm.bias") if layer else g("feature_extractor.conv_layers.0.layer_norm.bias"))
     for i in range(1, 7):
         w = g(f"feature_extractor.conv_layers.{i}.conv.weight")                  # [Cout, Cin, k]
         put(np.ascontiguousarray(w.transpose(0, 2, 1)).reshape(w.shape[0], -1))
@@ -72,6 +74,13 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
         put(g(p + "feed_forward.intermediate_dense.weight")); put(g(p + "feed_forward.intermediate_dense.bias"))
         put(g(p + "feed_forward.output_dense.weight")); put(g(p + "feed_forward.output_dense.bias"))
         put(g(p + "final_layer_norm.weight")); put(g(p + "final_layer_norm.bias"))
+    if cfg.conv_bias:
+        for i in range(7):
+            put(g(f"feature_extractor.conv_layers.{i}.conv.bias"))
+    if layer:
+        for i in range(7):
+            put(g(f"feature_extractor.conv_layers.{i}.layer_norm.weight")); put(g(f"feature_extractor.conv_layers.{i}.layer_norm.bias"))
+    assert next(it, None) is None, "weight layout has segments pack_weights does not fill"
     return blob
 
 
@@ -92,7 +101,7 @@ class W2V2Engine:
 
     def _workspace(self, lens_c, n):
         import torch
-        need = _lib.load().rsaf_w2v2_workspace_bytes_ragged(lens_c, n, *_cfg_args(self.cfg))
+        need = _lib.load().rsaf_w2v2_workspace_bytes_ragged_ex(lens_c, n, *_cfg_args(self.cfg), self.cfg.flags)
         if need < 0:
             raise _lib.RsafError("a window is shorter than the encoder's receptive field (or the lengths are not non-increasing)")
         if self._ws is None or self._ws.numel() * 4 < need:
@@ -103,7 +112,7 @@ class W2V2Engine:
     def forward_windows(self, wav, starts, lens, out, out_rows, stream=None):
         """wav: 1-D float32 device tensor; starts / lens / out_rows: host arrays (sample offset and length of each window in
         ``wav``; first output row of each window in ``out`` [rows, hidden]).  Windows of any mix of lengths run together
-        (``rsaf_w2v2_forward_ragged``): they are ordered by length here, longest first, and cut into balanced sub-batches."""
+        (``rsaf_w2v2_forward_ragged``, or its ``_ex`` form with the config's flags): they are ordered by length here, longest first, and cut into balanced sub-batches."""
         import torch
         lib = _lib.load()
         cfg = self.cfg
@@ -132,10 +141,14 @@ class W2V2Engine:
             dev = host.to(self.device, non_blocking=True)
             lens_c = (C.c_int * n)(*[int(v) for v in lens[b0:b0 + n]])
             ws = self._workspace(lens_c, n)
-            _lib.check(lib.rsaf_w2v2_forward_ragged(
-                _lib.ptr(wav), C.c_void_p(dev.data_ptr()), C.c_void_p(dev.data_ptr() + 16 * n), lens_c, n,
-                *_cfg_args(cfg), float(cfg.layer_norm_eps), _lib.ptr(self.blob), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(out),
-                C.c_void_p(dev.data_ptr() + 8 * n), _lib.stream_ptr(stream)), "rsaf_w2v2_forward_ragged")
+            head = (_lib.ptr(wav), C.c_void_p(dev.data_ptr()), C.c_void_p(dev.data_ptr() + 16 * n), lens_c, n, *_cfg_args(cfg),
+                    float(cfg.layer_norm_eps))
+            tail = (_lib.ptr(self.blob), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(out), C.c_void_p(dev.data_ptr() + 8 * n),
+                    _lib.stream_ptr(stream))
+            if cfg.flags:                                                      # the large checkpoints' variants
+                _lib.check(lib.rsaf_w2v2_forward_ragged_ex(*head, cfg.flags, *tail), "rsaf_w2v2_forward_ragged_ex")
+            else:                                                              # base architecture (= _ex with flags 0)
+                _lib.check(lib.rsaf_w2v2_forward_ragged(*head, *tail), "rsaf_w2v2_forward_ragged")
             self._keep = (host, dev)                                           # alive until the next call's copy is queued
         return out
 
@@ -197,7 +210,8 @@ def get_engine(model_name, device="cuda"):
 
 def extract_wav2vec2_sequences(input_df, model_name="facebook/wav2vec2-base-960h", audio_file_column="filepath",
                                chunk_seconds=5, overlap_seconds=1, verbose=True, batch_files=64):
-    """Drop-in for ``src/foundation_model_extractor.py:37-131``: dict basename -> float32 [T, 768].
+    """Drop-in for ``src/foundation_model_extractor.py:37-131``: dict basename -> float32 [T, hidden_size] (768 for base,
+    1024 for the large / XLS-R checkpoints).
 
     Files shorter than 0.5 s (``:88``) or failing to load are absent; a model that cannot be
     loaded gives the reference's convention ``print + {}`` (``:73-74``)."""
