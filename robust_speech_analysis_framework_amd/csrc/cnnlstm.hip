@@ -554,8 +554,7 @@ __global__ __launch_bounds__(256) void zero_pad_rows_kernel(unsigned short* __re
 
 // widths the fp16-split GEMM takes (K and N multiples of 16); anything else (test geometries) stays on the exact-fp32 MFMA
 static bool use_f16x3(int input_dim, int channels) {
-    static const bool off = [] { const char* e = getenv("RSAF_CNN_F32"); return e && e[0] == '1'; }();
-    return !off && input_dim % 16 == 0 && channels % 16 == 0;
+    return input_dim % 16 == 0 && channels % 16 == 0;
 }
 
 struct F16Ws {          // float offsets into the workspace behind the fp32 buffers

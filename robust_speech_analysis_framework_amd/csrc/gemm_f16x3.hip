@@ -26,7 +26,6 @@
 // flight; the two 16-byte chunks of a 32-byte row are swapped on the SOURCE side for rows with (row >> 3) & 1 so that
 // the ds_read_b128 fragment reads are conflict-free; the two waves of a SIMD run half a k-tile apart.
 #include <algorithm>
-#include <cstdlib>
 
 #include "gemm_f16x3.h"
 
@@ -645,14 +644,12 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
         for (int kt = 0; kt < pp.K / 16; ++kt)
             RSAF_CHECK_ARG((int)(((unsigned)kt * (unsigned)pp.a_tap_inv) >> 16) == kt / pp.a_tap_panels, "a_tap_panels: K too long for the reciprocal");
     }
-    // persistent workgroups, one per CU (RSAF_GEMM_WGS overrides the count: a measurement knob)
+    // persistent workgroups, one per CU
     int persistent_wgs = 256;
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             persistent_wgs = cus;
-        static const int forced = [] { const char* e = getenv("RSAF_GEMM_WGS"); return e ? atoi(e) : 0; }();
-        if (forced > 0) persistent_wgs = forced;
     }
     const bool f32o = p.C != nullptr, plo = p.Cp != nullptr, hr = p.R != nullptr;
     // the combinations the Wav2Vec2 / CNN stages use (anything else is an argument error, not a silent fallback)

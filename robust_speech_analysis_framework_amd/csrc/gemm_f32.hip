@@ -11,7 +11,6 @@
 // multiplied.  Workgroup ids are remapped so that the 8 XCDs each own a contiguous range of tiles
 // (tiles sharing an A row-panel hit the same L2).  The plain NT shapes with K % 32 == 0 (all Wav2Vec2 layers)
 // take the LDS-DMA variant further down (global_load_lds, swizzled unpadded image): +2.5-6 % on those shapes.
-#include <cstdlib>
 
 #include "gemm_f32.h"
 
@@ -25,8 +24,8 @@ __device__ __forceinline__ float act_apply(float v, int act) {
     return v;
 }
 
-template <int BM, int BN, int WM, int WN, bool BKN, bool DB>
-__global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(const GemmParams p) {
+template <int BM, int BN, int WM, int WN, bool BKN>
+__global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmParams p) {
     constexpr int BK = 32;
     constexpr int LDS_K = BK + 4;                 // 36-float rows (NT images)
     constexpr int LDB_N = BN + 4;                 // KN image row
@@ -36,9 +35,9 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(const GemmPar
     constexpr int B_IT = BN / 32;
     constexpr int A_FLOATS = BM * LDS_K;
     constexpr int B_FLOATS = BKN ? BK * LDB_N : BN * LDS_K;
-    // DB: two LDS images, the next k-tile is written to the other image right after the multiply and
+    // two LDS images: the next k-tile is written to the other image right after the multiply and
     // one barrier per k-tile remains (the image being overwritten was last read one barrier ago)
-    __shared__ __attribute__((aligned(16))) float smem[(DB ? 2 : 1) * (A_FLOATS + B_FLOATS)];
+    __shared__ __attribute__((aligned(16))) float smem[2 * (A_FLOATS + B_FLOATS)];
     constexpr int STAGE = A_FLOATS + B_FLOATS;
     int wr_off = 0, rd_off = 0;                   // float offsets of the LDS image being written / read
 #define As (smem + wr_off)
@@ -178,25 +177,19 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(const GemmPar
 
     RSAF_GLOAD(0);
     RSAF_LSTORE(0);
-    if constexpr (DB) {
-        if (nk > 1) RSAF_GLOAD(1);
-    }
+    if (nk > 1) RSAF_GLOAD(1);
     __syncthreads();
 
     for (int kt = 0; kt < nk; ++kt) {
-        if constexpr (DB) {
-            // software pipeline, depth 2: registers hold tile kt+1 (loaded one iteration ago, so its
-            // latency is long hidden) -> store it to the other LDS image, refill the registers with
-            // tile kt+2, then multiply tile kt.  One barrier per k-tile; the image written here was
-            // last read before the previous barrier.
-            rd_off = (kt & 1) * STAGE;
-            if (kt + 1 < nk) {
-                wr_off = ((kt + 1) & 1) * STAGE;
-                RSAF_LSTORE(kt + 1);
-                if (kt + 2 < nk) RSAF_GLOAD(kt + 2);
-            }
-        } else {
-            if (kt + 1 < nk) RSAF_GLOAD(kt + 1);
+        // software pipeline, depth 2: registers hold tile kt+1 (loaded one iteration ago, so its
+        // latency is long hidden) -> store it to the other LDS image, refill the registers with
+        // tile kt+2, then multiply tile kt.  One barrier per k-tile; the image written here was
+        // last read before the previous barrier.
+        rd_off = (kt & 1) * STAGE;
+        if (kt + 1 < nk) {
+            wr_off = ((kt + 1) & 1) * STAGE;
+            RSAF_LSTORE(kt + 1);
+            if (kt + 2 < nk) RSAF_GLOAD(kt + 2);
         }
 #pragma unroll
         for (int g = 0; g < BK / 8; ++g) {
@@ -228,15 +221,7 @@ __global__ __launch_bounds__(256, DB ? 2 : 3) void gemm_f32_kernel(const GemmPar
                         acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[mt][j], bf[nt][j],
                                                                            acc[mt][nt], 0, 0, 0);
         }
-        if constexpr (DB) {
-            __syncthreads();
-        } else {
-            __syncthreads();
-            if (kt + 1 < nk) {
-                RSAF_LSTORE(kt + 1);
-                __syncthreads();
-            }
-        }
+        __syncthreads();
     }
 
     // ---- epilogue: alpha, bias, residual, activation; C/D map: col = lane&31,
@@ -450,25 +435,12 @@ static int launch_glds_cfg(const GemmParams& p, hipStream_t s) {
     return RSAF_OK;
 }
 
-static int launch_glds(const GemmParams& p, hipStream_t s) {
-    // RSAF_GEMM_TALL=1: 256 x 128 tiles (8 waves, one workgroup per CU, 25 % less global->LDS traffic per FLOP)
-    static const int tall = [] { const char* e = getenv("RSAF_GEMM_TALL"); return e ? atoi(e) : 0; }();
-    if (tall && p.M >= 2048) return launch_glds_cfg<256, 128>(p, s);
-    return launch_glds_cfg<128, 128>(p, s);
-}
-
 template <int BM, int BN, int WM, int WN>
 static int launch_cfg(const GemmParams& p, hipStream_t s) {
     const int tiles = ((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM);
     dim3 grid((unsigned)tiles, (unsigned)p.nz);
-    static const bool db = [] { const char* e = getenv("RSAF_GEMM_DB"); return e ? atoi(e) != 0 : true; }();
-    if (p.b_kn) {
-        if (db) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true, false>), grid, dim3(256), 0, s, p);
-    } else {
-        if (db) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, true>), grid, dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false, false>), grid, dim3(256), 0, s, p);
-    }
+    if (p.b_kn) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, true>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, WM, WN, false>), grid, dim3(256), 0, s, p);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
@@ -490,8 +462,7 @@ int launch_gemm_f32(const GemmParams& p, hipStream_t stream, const char* tag) {
     RSAF_CHECK_ARG(!p.R || p.ldr > 0, "residual needs ldr");
     const double flops = 2.0 * p.M * (double)p.N * p.K * p.nz;
     ProfScope prof(tag ? tag : "gemm_f32", stream, flops, 0.0);
-    static const int glds = [] { const char* e = getenv("RSAF_GEMM_GLDS"); return e ? atoi(e) : 1; }();   // 0: register-staged kernel everywhere
-    if (glds && !p.b_kn && p.a_pad_k == 0 && p.K % 32 == 0 && p.K >= 32 && p.N > 64) return launch_glds(p, stream);
+    if (!p.b_kn && p.a_pad_k == 0 && p.K % 32 == 0 && p.K >= 32 && p.N > 64) return launch_glds_cfg<128, 128>(p, stream);
     if (p.N <= 32) return launch_cfg<128, 32, 32, 32>(p, stream);
     if (p.N <= 64) return launch_cfg<128, 64, 64, 32>(p, stream);
     return launch_cfg<128, 128, 64, 64>(p, stream);

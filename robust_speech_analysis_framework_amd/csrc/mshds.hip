@@ -51,14 +51,13 @@ struct ClipInfo {       // one entry per clip of a launch (host-built)
 
 struct PitchParams {
     double dt, min_pitch, ceiling, voicing_thr, octave_cost, dt_window;
-    double refine_margin;   // > 0: only candidates within this margin of the best first-pass strength are refined
+    int cheb_all_full;      // no candidate of this analysis can have its interpolation depth clipped by the array ends
+    int cheb_clipped;       // the Chebyshev table is followed by the tables of the clipped depths 1 .. refine_depth - 1
     int nsamp_window, half_window, nsamp_period, half_period, min_lag, max_lag, brent_ixmax, max_cand;
     int refine_depth, is_cc;
     int nfft;               // AC: FFT length, the smallest power of two >= 1.5 nsamp_window (Praat's nsampFFT)
     double voicing_thr2;    // >= 0: also emit the candidate lists for this (lower) voicing threshold into out2
     int debug_stop;         // profiling aid (env RSAF_PITCH_STOP): leave the frame kernel after phase k; 0 = run all
-    int cheb_all_full;      // no candidate of this analysis can have its interpolation depth clipped by the array ends
-    int cheb_clipped;       // the Chebyshev table is followed by the tables of the clipped depths 1 .. refine_depth - 1
 };
 
 // Sampled_xToLowIndex / xToNearestIndex / xToHighIndex of the sound (0-based), x1 = time of its first sample
@@ -444,21 +443,17 @@ __device__ void improve_max_cheb(const double* __restrict__ Pc, int x0, bool liv
 }
 
 struct RefineArgs {
-    const double* r; int RN, RC, depth, nz_lo, nz_hi, ncand; double margin;
+    const double* r; int RN, RC, depth, nz_lo, nz_hi, ncand;
     const int* place; double* cf; double* cs;
 };
-// refine every kept candidate: maximise the sinc-interpolated correlation, 256/G candidates per round.
-// With every path cost zero (harmonicity pass) a candidate far below the best first-pass strength could
-// be left unrefined (margin > 0); that is off by default because it moved a few frames' selection.
+// refine every kept candidate: maximise the sinc-interpolated correlation, 256/G candidates per round
 template <int G, bool RECUR>
 __device__ void refine_candidates(const RefineArgs& A, int tid, int nthreads) {
     const int lane = tid & 63, lg = lane & (G - 1), gidx = (tid >> 6) * (64 / G) + lane / G;
-    double best_first = 0.0;
-    for (int k = 1; k < A.ncand; ++k) best_first = fmax(best_first, A.cs[k]);
     __syncthreads();
     for (int kb = 1; kb < A.ncand; kb += nthreads / G) {
         const int k = kb + gidx;
-        const bool live = k < A.ncand && (A.margin <= 0.0 || A.cs[k < A.ncand ? k : 1] >= best_first - A.margin);
+        const bool live = k < A.ncand;
         double xm, ym;
         improve_max_group<G, RECUR>(A.r, A.RN, (double)(A.place[live ? k : 1] + A.RC), A.depth, A.nz_lo, A.nz_hi, lg,
                                     live, xm, ym);
@@ -467,15 +462,10 @@ __device__ void refine_candidates(const RefineArgs& A, int tid, int nthreads) {
     }
 }
 
-// ---- AC: windowed autocorrelation by FFT ---------------------------------------------------------------------
-// Praat's Sound_to_Pitch (ac) transforms the windowed frame with an FFT of nsampFFT >= 1.5 nsamp_window points, squares
-// the spectrum and transforms back; so does this kernel, in fp64: about 2.5 N log2 N flops per transform against
-// 2 nw L for the direct sum (nine times fewer at nw = 960, L = 512).  The real transform of N points is a complex
-// transform of M = N / 2 points on z[j] = x[2 j] + i x[2 j + 1] (the zero-padded frame, as it lies in LDS, IS z), a
-// pass that separates X[k], squares it and packs the even spectrum P back into M complex points, and a second complex
-// transform whose output is r[2 j] + i r[2 j + 1].  The complex transform is a Stockham autosort FFT (radix 4, a final
-// radix 2 when M is not a power of 4): natural order in and out, ping-pong between two LDS buffers, 256 threads.
-// Twiddles W_N^k = exp(-2 pi i k / N), k < N / 2, come from a table built on the host in double precision.
+// ---- Stockham FFT of the workgroup cross-correlation kernel -------------------------------------------------------
+// A complex transform of M points as a Stockham autosort FFT (radix 4, a final radix 2 when M is not a power of 4):
+// natural order in and out, ping-pong between two LDS buffers, 256 threads.  Twiddles W_N^k = exp(-2 pi i k / N),
+// k < N / 2, come from a table built on the host in double precision.
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ double2_t cmul(double2_t a, double2_t b) {
@@ -530,7 +520,7 @@ __device__ __forceinline__ void fft_load_twiddles(FftTw<LOG2M>& R, const double2
 
 // Between the first two radix-4 stages element e lives at slot fsw(e) (low two bits XOR-ed with bits 3-4): stage 0 writes
 // elements 4 j + r from lane j, a 64-byte lane stride = 4-way bank conflict for the 16-byte stores of 8 consecutive lanes
-// (PMC: 30 % of the LDS-active cycles of the autocorrelation kernel were conflict cycles, the LDS busy 65 % of the time);
+// (PMC on the former workgroup autocorrelation kernel: 30 % of the LDS-active cycles were conflict cycles, the LDS busy 65 %);
 // swizzled, the 8 lanes hit 8 different slots of the 128-byte bank row, and the unit-stride reads of stage 1 stay
 // conflict-free (the permutation stays inside aligned blocks of 4 slots).  Every other pass sees the natural order.
 __device__ __forceinline__ int fsw(int e) { return e ^ ((e >> 3) & 3); }
@@ -599,125 +589,6 @@ __device__ __forceinline__ double2_t* fft_stockham(double2_t* a, double2_t* b, c
         double2_t* t_ = src; src = dst; dst = t_;
     }
     return src;
-}
-
-constexpr int AC_FRAMES_PER_WG = 16;
-
-template <int LOG2M>
-__global__ __launch_bounds__(256) void pitch_ac_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
-                                                       const double* __restrict__ gpeak, const double* __restrict__ win,
-                                                       const double* __restrict__ wr, const PitchParams P,
-                                                       const double2_t* __restrict__ tw, double* __restrict__ rbuf,
-                                                       int rstride, int max_frames) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const ClipInfo c = ci[blockIdx.y];
-    if ((int)blockIdx.x * AC_FRAMES_PER_WG >= c.n_frames) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr int N = FftPlan<LOG2M>::N, M = FftPlan<LOG2M>::M;
-    const int nw = P.nsamp_window, L = P.brent_ixmax;
-    FftTw<LOG2M> twr;
-    fft_load_twiddles<LOG2M>(twr, tw, tid);                // in flight during the passes over the samples
-    constexpr int NPK = (M / 2) / 256 + 1;                  // spectrum pass: k = tid + 256 i <= M / 2
-    double2_t twp[NPK];
-#pragma unroll
-    for (int i = 0; i < NPK; ++i) twp[i] = tw[tid + 256 * i <= M / 2 ? tid + 256 * i : 0];
-    double* seg = reinterpret_cast<double*>(smem_raw);      // [N]: the windowed frame, zero-padded = M complex points
-    double* buf = seg + N;                                  // [N]
-    double* s_red = buf + N;                                // [4]
-    double* s_val = s_red + 4;                              // [4]
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples;
-    const double gp = gpeak[blockIdx.y];
-    // a workgroup takes AC_FRAMES_PER_WG consecutive frames: the twiddles (72 KB of table reads per workgroup at M = 1024)
-    // are fetched once for all of them
-    for (int f = blockIdx.x * AC_FRAMES_PER_WG; f < (int)(blockIdx.x + 1) * AC_FRAMES_PER_WG && f < c.n_frames; ++f) {
-    double* rb = rbuf + ((int64_t)blockIdx.y * max_frames + f) * rstride;   // r[0..L], then the intensity
-    const double t = c.t1 + f * P.dt;
-    const int64_t left = low_index(t, c.x1), right = left + 1;
-    // local mean over one longest period to each side (divisor 2*nsamp_period as in Praat)
-    {
-        int64_t s0 = right - P.nsamp_period, s1 = left + P.nsamp_period;
-        s0 = s0 < 0 ? 0 : (s0 > n - 1 ? n - 1 : s0);
-        s1 = s1 < 0 ? 0 : (s1 > n - 1 ? n - 1 : s1);
-        double s = 0.0;
-        for (int64_t i = s0 + tid; i <= s1; i += 256) s += (double)x[i];
-        s = group_sum<64>(s);
-        if (lane == 0) s_red[wv] = s;
-    }
-    __syncthreads();
-    const double local_mean = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (2.0 * P.nsamp_period);
-    const int64_t start = right - P.half_window;
-    if (start >= 0 && start + nw <= n) {                    // the window lies inside the sound: no index clamps
-        const float* xs = x + start;
-#pragma unroll 4
-        for (int j = tid; j < N; j += 256) seg[j] = j < nw ? ((double)xs[j] - local_mean) * win[j] : 0.0;
-    } else {
-        for (int j = tid; j < N; j += 256) {
-            int64_t i = start + j;
-            i = i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
-            seg[j] = j < nw ? ((double)x[i] - local_mean) * win[j] : 0.0;
-        }
-    }
-    __syncthreads();
-    // local peak over half a longest period around the window centre
-    {
-        int a = P.half_window - P.half_period, b = P.half_window + P.half_period;
-        a = a < 0 ? 0 : a;
-        b = b > nw ? nw : b;
-        double m = 0.0;
-        for (int j = a + tid; j < b; j += 256) m = fmax(m, fabs(seg[j]));
-        m = wave_max_dpp(m);
-        if (lane == 0) s_val[wv] = m;
-    }
-    __syncthreads();
-    const double local_peak = fmax(fmax(s_val[0], s_val[1]), fmax(s_val[2], s_val[3]));
-    const double intensity = gp > 0.0 ? (local_peak > gp ? 1.0 : local_peak / gp) : 0.0;
-    if (P.debug_stop == 1) { __syncthreads(); continue; }
-
-    double2_t* za = reinterpret_cast<double2_t*>(seg);
-    double2_t* zb = reinterpret_cast<double2_t*>(buf);
-    double2_t* Z = fft_stockham<LOG2M>(za, zb, twr, tw, tid);
-    double2_t* Y = Z == za ? zb : za;
-    // X[k] = E + W^k O, X[M - k] = conj(E - W^k O) with E = (Z[k] + conj Z[M-k]) / 2, O = (Z[k] - conj Z[M-k]) / 2i;
-    // P = |X|^2 is real and even, and the M-point input of the transform back is
-    // Y[k] = (P[k] + P[M-k]) + i conj(W^k) (P[k] - P[M-k]); it is stored conjugated (inverse by the forward transform)
-#pragma unroll
-    for (int i = 0; i < NPK; ++i) {
-        const int k = tid + 256 * i;
-        if (k > M / 2) continue;
-        if (k == 0) {
-            const double2_t z0 = Z[0];
-            const double p0 = (z0.x + z0.y) * (z0.x + z0.y), pm = (z0.x - z0.y) * (z0.x - z0.y);
-            Y[0] = double2_t{p0 + pm, -(p0 - pm)};
-        } else if (k == M / 2) {
-            const double2_t zk = Z[k];
-            Y[k] = double2_t{2.0 * (zk.x * zk.x + zk.y * zk.y), 0.0};
-        } else {
-            const double2_t zk = Z[k], zm = Z[M - k];
-            const double2_t E = double2_t{0.5 * (zk.x + zm.x), 0.5 * (zk.y - zm.y)};
-            const double2_t D = double2_t{0.5 * (zk.x - zm.x), 0.5 * (zk.y + zm.y)};
-            const double2_t O = double2_t{D.y, -D.x};
-            const double2_t w = twp[i];
-            const double2_t T = cmul(w, O);
-            const double2_t xa = E + T, xb = E - T;
-            const double pk = xa.x * xa.x + xa.y * xa.y, pm = xb.x * xb.x + xb.y * xb.y;
-            const double sum = pk + pm, d = pk - pm;
-            Y[k] = double2_t{sum + w.y * d, -(w.x * d)};
-            Y[M - k] = double2_t{sum - w.y * d, -(w.x * d)};
-        }
-    }
-    __syncthreads();
-    const double* r = reinterpret_cast<const double*>(fft_stockham<LOG2M>(Y, Y == za ? zb : za, twr, tw, tid));
-    if (P.debug_stop == 2) continue;
-    // r[2 j] = Re, r[2 j + 1] = -Im of the (conjugated) output; normalise into the global row
-    if (tid == 0) { rb[0] = 1.0; rb[L + 1] = intensity; }
-    const double r0 = r[0];
-    for (int l = 1 + tid; l <= L; l += 256) {
-        const double v = (l & 1) ? -r[l] : r[l];
-        rb[l] = r0 > 0.0 ? v / (r0 * wr[l]) : 0.0;
-    }
-    __syncthreads();                                        // the next frame overwrites both buffers
-    }
 }
 
 // ---- CC: forward cross-correlation by FFT ----------------------------------------------------------------------
@@ -909,6 +780,11 @@ __device__ __forceinline__ double wave_scan_incl(double v, int lane) {
     return v + (row == 0 ? 0.0 : (row == 1 ? t0 : (row == 2 ? t0 + t1 : (t0 + t1) + t2)));
 }
 
+// AC: Praat's Sound_to_Pitch (ac) transforms the windowed frame with an FFT of nsampFFT >= 1.5 nsamp_window points, squares
+// the spectrum and transforms back; so does pitch_ac_wave_kernel, in fp64: about 2.5 N log2 N flops per transform against
+// 2 nw L for the direct sum (nine times fewer at nw = 960, L = 512).  The real transform of N points is a complex transform
+// of S = N / 2 points on z[j] = x[2 j] + i x[2 j + 1] (the zero-padded frame), a pass that separates X[k], squares it and
+// packs the even spectrum P back into S complex points, and a second complex transform whose output is r[2 j] + i r[2 j + 1].
 template <int R>
 __global__ __launch_bounds__(64, R == 32 ? 2 : (R == 16 ? 3 : 4)) void pitch_ac_wave_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
                                                            const double* __restrict__ gpeak, const double* __restrict__ win,
@@ -1585,7 +1461,7 @@ __global__ __launch_bounds__(64) void pitch_cand_kernel(const ClipInfo* __restri
         }
         const int nref = nc - 1;
         const int span = P.refine_depth < 2 * L ? P.refine_depth : 2 * L;    // longest half kernel
-        RefineArgs A{r, RN, RC, P.refine_depth, nz_lo, nz_hi, nc, P.refine_margin, place_lag, cf, cs};
+        RefineArgs A{r, RN, RC, P.refine_depth, nz_lo, nz_hi, nc, place_lag, cf, cs};
         if (nref <= 4) { if (span >= 6 * 64) refine_candidates<64, true>(A, tid, CT); else refine_candidates<64, false>(A, tid, CT); }
         else if (nref <= 8) { if (span >= 6 * 32) refine_candidates<32, true>(A, tid, CT); else refine_candidates<32, false>(A, tid, CT); }
         else { if (span >= 6 * 16) refine_candidates<16, true>(A, tid, CT); else refine_candidates<16, false>(A, tid, CT); }
@@ -3592,7 +3468,7 @@ int rsaf_mshds_intensity(const float* wav, const void* clip_info, int n_clips, i
 }
 
 // W_N^k = exp(-2 pi i k / N), k < N / 2, in double precision (host libm), one table per (device, N), kept for the
-// life of the process (pitch_ac_kernel)
+// life of the process (the pitch correlation kernels)
 static int fft_twiddles(int N, const double** out) {
     static std::mutex mu;
     static std::map<std::pair<int, int>, double*> cache;
@@ -3648,7 +3524,6 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
     P.cheb_clipped = table_mode == 1 ? 1 : 0;
     P.voicing_thr2 = dual ? voicing_thr2 : -1.0;
     { const char* e = getenv("RSAF_PITCH_STOP"); P.debug_stop = e ? atoi(e) : 0; }
-    P.refine_margin = 0.0;   // lazy refinement is off: it changed a few frames' selection (parity first)
     P.half_window = P.nsamp_window / 2;
     P.half_period = P.nsamp_period / 2 + 1;
     RSAF_CHECK_ARG(P.max_cand >= 2 && P.max_cand <= MAXC - 1, "max_candidates must be in [2, 15]");
@@ -3666,8 +3541,8 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
     while (ncc < seg_len) ncc *= 2;
     RSAF_CHECK_ARG(!P.is_cc || ncc <= 4096, "cross-correlation window + lag range longer than 4 095 samples is not supported");
     RSAF_CHECK_ARG(P.is_cc || P.nfft <= 4096, "autocorrelation window longer than 2 730 samples is not supported");
-    const size_t lds_corr = P.is_cc ? (size_t)ncc * 2 * 2 * sizeof(double) + (size_t)(((Lr + 2) & ~1) + 32) * sizeof(double)   // two complex buffers + sumy2 + scratch
-                                    : (size_t)(2 * P.nfft + 8) * sizeof(double);
+    // the workgroup cross-correlation kernel: two complex buffers + sumy2 + scratch
+    const size_t lds_corr = P.is_cc ? (size_t)ncc * 2 * 2 * sizeof(double) + (size_t)(((Lr + 2) & ~1) + 32) * sizeof(double) : 0;
     // in-kernel refinement (the form before the refinement kernels existed): the A/B reference of the tests
     const bool defer = getenv("RSAF_PITCH_INKERNEL") == nullptr;
     const bool grouped = defer && table_mode == 2 && !dual && P.is_cc && sinc_cheb != nullptr;
@@ -3689,33 +3564,18 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
     while ((2 << log2m) < P.nfft) ++log2m;                           // nfft = 2 M = 2^(log2m + 1)
     int log2n = 0;
     while ((1 << log2n) < ncc) ++log2n;
-    // transform lengths of 512 .. 2048 complex points run one wave per frame (RSAF_PITCH_FFT=wg: the workgroup kernels)
+    // transform lengths of 512 .. 2048 complex points run one wave per frame: every autocorrelation (nfft <= 4096) and
+    // every cross-correlation but the 4 096-point one, which takes the workgroup kernel pitch_cc_kernel<12>.
+    // A shorter transform is zero-padded up to the smallest wave size: the correlation is linear as long as the lags stay
+    // below (transform length - window), so a longer transform returns the same values (autocorrelation: 512 complex =
+    // 1024 real points; cross-correlation: 1024 points, whose transform back has the 512 the wave kernel needs).
     int wave_r = 0;
-    {
-        const char* e = getenv("RSAF_PITCH_FFT");
-        const bool want = !(e && e[0] == 'w' && e[1] == 'g');
-#ifndef RSAF_TEST_KERNELS
-        // the workgroup-FFT kernels the one-wave kernels superseded (transforms of up to 2 048 points) are compiled only into
-        // a test build (RSAF_BUILD_TEST_KERNELS=1 python -m ...build), where they serve as an independent A/B check
-        RSAF_CHECK_ARG(want, "RSAF_PITCH_FFT=wg needs a library built with RSAF_BUILD_TEST_KERNELS=1");
-#endif
-        // A shorter transform is zero-padded up to the smallest wave size: the correlation is linear as long as the lags stay
-        // below (transform length - window), so a longer transform returns the same values (autocorrelation: 512 complex =
-        // 1024 real points; cross-correlation: 1024 points, whose transform back has the 512 the wave kernel needs).
-        if (want && !P.is_cc && log2m <= 11) wave_r = log2m <= 9 ? 8 : 1 << (log2m - 6);
-        if (want && P.is_cc && log2n <= 11) wave_r = log2n <= 10 ? 16 : 32;
-    }
+    if (!P.is_cc) wave_r = log2m <= 9 ? 8 : 1 << (log2m - 6);
+    else if (log2n <= 11) wave_r = log2n <= 10 ? 16 : 32;
     if (wave_r && !P.is_cc) P.nfft = 128 * wave_r;                  // 2 S real points
     if (wave_r && P.is_cc) ncc = 64 * wave_r;
-    if (!wave_r && lds_corr > 48 * 1024) {
-#ifdef RSAF_TEST_KERNELS
-        const void* fn = (const void*)pitch_ac_kernel<11>;            // 4 096 points: 64 KB (the only AC instance above 48 KB)
-        if (P.is_cc) fn = log2n == 11 ? (const void*)pitch_cc_kernel<11> : (const void*)pitch_cc_kernel<12>;   // 64 / 128 KB
-#else
-        const void* fn = (const void*)pitch_cc_kernel<12>;            // 4 096-point cross-correlation: the one transform above the wave sizes
-#endif
-        RSAF_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_corr));
-    }
+    if (!wave_r)                                                    // 128 KB of LDS and more
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cc_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_corr));
     const double* twiddles = nullptr;
     const double* twiddles2 = nullptr;
     if (!P.is_cc) {
@@ -3740,7 +3600,7 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
         P.cheb_all_full = unclipped ? 1 : 0;
         if (cheb == nullptr) P.cheb_clipped = 0;
         // clipped analyses keep the Chebyshev form only with the per-depth tables behind the shared one
-        if ((!unclipped && !P.cheb_clipped) || getenv("RSAF_PITCH_NO_CHEB")) cheb = nullptr;
+        if (!unclipped && !P.cheb_clipped) cheb = nullptr;
     }
     // per-cell tables (mshds.sinc_cell_tables): cells b_lo .. b_hi, the lags 0 .. L (r is symmetric: the two taps that meet
     // a lag are summed in the table) padded to a multiple of four
@@ -3765,7 +3625,7 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
         // each transform, the staging pass and the spectrum pass): the kernel's own roofline is the LDS, not the FLOPs
         // (one wave per frame, wave_fft.h: two exchanges per transform, each writing and reading the S complex doubles, and the
         // paired spectrum step: 160 S bytes per autocorrelation frame, 120 S + the running sums per cross-correlation frame)
-        const double ac_lds = wave_r ? 160.0 * Mfft : 16.0 * Mfft * (2.0 * ceil(log2(Mfft) / 2.0) + 3.0) * 2.0;
+        const double ac_lds = 160.0 * Mfft;
         const double cc_lds = wave_r ? 120.0 * ncc + 16.0 * Lr
                                      : 16.0 * ncc * (ceil(log2((double)ncc) / 2.0) + 2.0) * 2.0 + 16.0 * 0.5 * ncc * (ceil(log2(0.5 * ncc) / 2.0) + 1.0) * 2.0;
         for (int c0 = 0; c0 < n_clips; c0 += group) {
@@ -3797,38 +3657,12 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
                     switch (wave_r) { RSAF_ACW_CASE(8) RSAF_ACW_CASE(16) RSAF_ACW_CASE(32) default: break; }
 #undef RSAF_ACW_CASE
                 }
-            } else if (P.is_cc) {
-#define RSAF_CC_CASE(LG)                                                                                              \
-    case LG:                                                                                                          \
-        hipLaunchKernelGGL(pitch_cc_kernel<LG>, dim3((max_frames + CC_FRAMES_PER_WG - 1) / CC_FRAMES_PER_WG, nc),      \
-                           dim3(256), lds_corr, s, wav, cig, gpeak + c0, P,                                           \
-                           reinterpret_cast<const double2_t*>(twiddles), reinterpret_cast<const double2_t*>(twiddles2), \
-                           (double*)workspace, rstride, max_frames);                                                  \
-        break;
-                switch (log2n) {
-#ifdef RSAF_TEST_KERNELS
-                    RSAF_CC_CASE(6) RSAF_CC_CASE(7) RSAF_CC_CASE(8) RSAF_CC_CASE(9) RSAF_CC_CASE(10) RSAF_CC_CASE(11)
-#endif
-                    RSAF_CC_CASE(12)
-                    default: set_error("rsaf_mshds_pitch: unsupported FFT length"); return RSAF_ERR_ARG;
-                }
-#undef RSAF_CC_CASE
             } else {
-#define RSAF_AC_CASE(LG)                                                                                              \
-    case LG:                                                                                                          \
-        hipLaunchKernelGGL(pitch_ac_kernel<LG>, dim3((max_frames + AC_FRAMES_PER_WG - 1) / AC_FRAMES_PER_WG, nc),      \
-                           dim3(256), lds_corr, s, wav, cig, gpeak + c0,                                              \
-                           window, window_r, P, reinterpret_cast<const double2_t*>(twiddles), (double*)workspace,     \
-                           rstride, max_frames);                                                                      \
-        break;
-                switch (log2m) {
-#ifdef RSAF_TEST_KERNELS
-                    RSAF_AC_CASE(3) RSAF_AC_CASE(4) RSAF_AC_CASE(5) RSAF_AC_CASE(6) RSAF_AC_CASE(7) RSAF_AC_CASE(8)
-                    RSAF_AC_CASE(9) RSAF_AC_CASE(10) RSAF_AC_CASE(11)
-#endif
-                    default: set_error("rsaf_mshds_pitch: unsupported FFT length"); return RSAF_ERR_ARG;
-                }
-#undef RSAF_AC_CASE
+                // 4 096-point cross-correlation: the workgroup kernel
+                hipLaunchKernelGGL(pitch_cc_kernel<12>, dim3((max_frames + CC_FRAMES_PER_WG - 1) / CC_FRAMES_PER_WG, nc),
+                                   dim3(256), lds_corr, s, wav, cig, gpeak + c0, P,
+                                   reinterpret_cast<const double2_t*>(twiddles), reinterpret_cast<const double2_t*>(twiddles2),
+                                   (double*)workspace, rstride, max_frames);
             }
             RSAF_CHECK_HIP(hipGetLastError());
             }
@@ -3856,7 +3690,7 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
             if (defer && P.debug_stop == 0) {
                 if (grouped) {
                     // one table per cell on the fp64 matrix pipe: <= 28 cells per frame x (2 L + 1) taps x 16 coefficients
-                    static const int chunk_frames = [] { const char* e = getenv("RSAF_PITCH_CELL_CHUNK"); const int v = e ? atoi(e) : 4096; return v >= 256 && v % 256 == 0 ? v : 4096; }();
+                    constexpr int chunk_frames = 4096;               // frames per workgroup
                     const int64_t n_chunks = (gframes + chunk_frames - 1) / chunk_frames;
                     const int64_t n_wg = 8 * (int64_t)cell_n_b * ((n_chunks + 7) / 8);
                     RSAF_CHECK_ARG(n_wg <= 0x7fffffffLL, "per-cell tables: too many workgroups");

@@ -1605,8 +1605,7 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     }
     const int hd = Hd / c.NH;
     const float scale = 1.0f / sqrtf((float)hd);
-    static const bool fused_attn = [] { const char* e = getenv("RSAF_W2V2_FUSED_ATTN"); return e ? atoi(e) != 0 : true; }();
-    const bool fused = fused_attn && hd == 64 && Tt <= 256;  // attention on the fp16 matrix pipe, q / k / v as plane pairs
+    const bool fused = hd == 64 && Tt <= 256;  // attention on the fp16 matrix pipe, q / k / v as plane pairs
     // 5. positional conv embedding (grouped, weight norm folded), GELU, x = LN(x + pos)
     {
         const int cg = Hd / c.PG;

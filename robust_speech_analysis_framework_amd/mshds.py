@@ -251,8 +251,7 @@ class MshdsEngine:
         self.device = torch.device(device)
         self._tables = {}
         self.fo_doubles = _lib.load().rsaf_mshds_frameout_doubles()
-        import os
-        self.n_streams = int(os.environ.get("RSAF_MSHDS_STREAMS", "3"))     # 1: every analysis on the caller's stream
+        self.n_streams = 3                 # HIP streams for the independent analyses of a range group; 1: the caller's stream
         self._aux = None
 
     # ---- cached device tables ----

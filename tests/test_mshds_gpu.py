@@ -501,50 +501,6 @@ def test_time_axis_shifts_times_but_not_windows(eng):
         assert (np.abs(g[i][cols] - r[cols]) <= 1e-9 * np.maximum(np.abs(r[cols]), 1e-3)).all(), (g[i], r)
 
 
-def test_one_wave_pitch_kernels_agree_with_the_workgroup_kernels_on_30s_clips(eng, monkeypatch):
-    """The correlation kernels exist twice: one wavefront per frame with the transform in registers (csrc/wave_fft.h, the
-    product path) and the workgroup-wide Stockham kernels of round 2 (RSAF_PITCH_FFT=wg).  Two independent implementations
-    of the same arithmetic must pick the same path through every frame of full-length clips (6 000 frames each) for every
-    parameter set the extractor uses - a size-independent check at BASELINE's clip length, where the oracle is too slow."""
-    import torch
-    from robust_speech_analysis_framework_amd import _lib
-    clips = [synth.synth_clip(900 + k, 30.0) for k in range(3)]
-    wav, offs, lens = _pack(clips)
-    gp = eng.clip_peaks(wav, offs, lens)
-    hnr = dict(max_candidates=15, silence_threshold=0.1, voicing_threshold=0.0, octave_cost=0.0, octave_jump_cost=0.0,
-               voiced_unvoiced_cost=0.0, periods=4.5, is_cc=True, refine_depth=700)
-    cfgs = [dict(time_step=0.005, floor=50.0, ceiling=600.0),                                  # wide AC, 1 024 complex points
-            dict(time_step=0.005, floor=100.0, ceiling=500.0, voicing_threshold2=0.3),         # 512 points, both thresholds
-            dict(time_step=0.02, floor=30.0, ceiling=450.0, max_candidates=4, voicing_threshold=0.25,
-                 voiced_unvoiced_cost=0.25),                                                    # speech rate: 2 048 points
-            dict(time_step=0.005, floor=60.0, ceiling=8000.0, **hnr),                           # CC, 2 048 -> 1 024 points
-            dict(time_step=0.005, floor=100.0, ceiling=8000.0, **hnr),                          # CC, 1 024 -> 512 points
-            dict(time_step=0.005, floor=100.0, ceiling=500.0, periods=1.0, is_cc=True, refine_depth=70)]   # padded up to 1 024
-    for kw in cfgs:
-        monkeypatch.delenv("RSAF_PITCH_FFT", raising=False)
-        a = eng.pitch(wav, offs, lens, gp, **kw)
-        torch.cuda.synchronize()
-        monkeypatch.setenv("RSAF_PITCH_FFT", "wg")
-        try:
-            b = eng.pitch(wav, offs, lens, gp, **kw)
-        except _lib.RsafError as e:
-            if "RSAF_BUILD_TEST_KERNELS" in str(e):
-                monkeypatch.delenv("RSAF_PITCH_FFT", raising=False)
-                pytest.skip("the superseded workgroup-FFT kernels are only in a test build (RSAF_BUILD_TEST_KERNELS=1); the one-wave "
-                            "kernels are checked frame by frame against the oracle in test_known_answers_gpu.py")
-            raise
-        torch.cuda.synchronize()
-        fa, fb = a["sel_freq"].cpu().numpy(), b["sel_freq"].cpu().numpy()
-        sa, sb = a["sel_strength"].cpu().numpy(), b["sel_strength"].cpu().numpy()
-        assert fa.shape == fb.shape and fa.size >= 3 * 1400
-        # The two forms differ by rounding (~1e-15 in the correlation), which can only matter where the path finder meets a
-        # numerical tie: allow one frame in a thousand to take another candidate, nothing else
-        differs = ((fa > 0) != (fb > 0)) | (np.abs(fa - fb) > 1e-7 * np.maximum(np.abs(fb), 1.0)) | (np.abs(sa - sb) > 1e-9)
-        print(f"pitch A/B floor {kw['floor']:g} cc {kw.get('is_cc', False)}: {int(differs.sum())} of {fa.size} frames differ")
-        assert differs.mean() <= 1e-3, (kw, int(differs.sum()), fa.size)
-    monkeypatch.delenv("RSAF_PITCH_FFT", raising=False)
-
-
 def test_refinement_kernels_agree_with_the_in_kernel_refinement(eng, monkeypatch):
     """Candidate refinement exists twice: inside the candidate kernel (RSAF_PITCH_INKERNEL=1: one wave per frame, the form
     before round 4; the harmonicity pass at a 100 Hz floor evaluates Praat's clipped sinc sums directly there) and as the
