@@ -285,6 +285,24 @@ int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, co
                                 int intermediate, int pos_kernel, int pos_groups, float layer_norm_eps, int flags,
                                 const float* weights, void* workspace, int64_t workspace_bytes, float* out,
                                 const int64_t* out_row_start, rsaf_stream_t stream);
+/* rsaf_w2v2_forward_ragged_ex that also writes encoder hidden states: transformers'
+ * Wav2Vec2Model(..., output_hidden_states=True).hidden_states[k], k = 0..layers (layers + 1 of them, hidden_states[layers] ==
+ * `out` bit for bit).  hidden_index_host: n_hidden STRICTLY INCREASING indices in [0, layers] on the host; state
+ * hidden_index_host[j] goes to hidden_out + j * hidden_plane_floats, in the row layout of `out` (rows out_row_start[i] .. +T_i,
+ * or packed).  hidden_out 16-byte aligned, hidden_plane_floats a multiple of 4 and at least the call's frames x hidden.
+ * What each state is (RSAF_W2V2_PRE_LN clear / set):
+ *   k = 0            encoder.layer_norm(x + pos_conv(x))      /  x + pos_conv(x), not normalised
+ *   0 < k < layers   output of layer k - 1 (final_layer_norm) /  residual stream after layer k - 1, not normalised
+ *   k = layers       last_hidden_state (= out)
+ * Each state is written by the LayerNorm launch that already reads or writes it: no extra launch, no extra workspace
+ * (size it with rsaf_w2v2_workspace_bytes_ragged_ex).  Bad indices return RSAF_ERR_ARG before any launch; n_hidden == 0 is
+ * rsaf_w2v2_forward_ragged_ex (same kernels, same bits).                                                               */
+int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start, const int* chunk_len,
+                                    const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
+                                    int intermediate, int pos_kernel, int pos_groups, float layer_norm_eps, int flags,
+                                    const float* weights, void* workspace, int64_t workspace_bytes, float* out,
+                                    const int64_t* out_row_start, const int* hidden_index_host, int n_hidden,
+                                    float* hidden_out, int64_t hidden_plane_floats, rsaf_stream_t stream);
 
 /* ---- Praat-style analyses behind the MSHDS features (float64) ---------------------------------------
  * Replace the parselmouth/Praat calls of src/mshds_extractor.py: To Intensity (:41,198), To Pitch
@@ -455,6 +473,12 @@ int rsaf_resample_praat(const float* in, int64_t n_in, double fs_in, double fs_o
  * Replaces merged_df.groupby('unique_participant_id').agg(['mean', 'std']), src/utils.py:49. */
 int rsaf_segment_mean_std(const double* rows, int64_t ld, const int* row_index, const int* seg_off, int n_seg, int width,
                           double* out, rsaf_stream_t stream);
+/* out[plane][seg][col] = mean over rows seg_off[seg] .. seg_off[seg+1] (device int64, n_seg + 1 entries) of
+ * rows[plane * plane_floats + row * ld + col], float32 in and out, summed in fp64 in row order (deterministic); NaN for an empty
+ * segment.  Pools n_planes Wav2Vec2 hidden states per file at once: np.mean(sequence, axis=0),
+ * src/foundation_model_extractor.py:160. */
+int rsaf_rows_segment_mean_f32(const float* rows, int64_t ld, int64_t plane_floats, int n_planes, const int64_t* seg_off,
+                               int n_seg, int width, float* out, rsaf_stream_t stream);
 /* dst[r][0..width) = src[src_row[r]][0..width), zeros where src_row[r] < 0.
  * Replaces np.vstack(participant_sequences), src/utils.py:96, and the zero padding of collate_fn,
  * src/dl_cv_strategies.py:81-84. */

@@ -88,6 +88,7 @@ SIGNATURES = {
     "rsaf_praat_lowpass_max_samples": (_L, []),
     "rsaf_resample_praat": (_I, [_P, _L, C.c_double, C.c_double, _I, _P, _L, _P, _L, _P]),
     "rsaf_segment_mean_std": (_I, [_P, _L, _P, _P, _I, _I, _P, _P]),
+    "rsaf_rows_segment_mean_f32": (_I, [_P, _L, _L, _I, _P, _I, _I, _P, _P]),
     "rsaf_gather_rows_f32": (_I, [_P, _L, _P, _L, _I, _P, _L, _P]),
     "rsaf_w2v2_frames": (_I, [_I]),
     "rsaf_w2v2_weight_floats": (_L, [_I] * 7),
@@ -100,6 +101,8 @@ SIGNATURES = {
     "rsaf_w2v2_weight_offsets_ex": (_I, [_I] * 8 + [C.POINTER(_L), _I, C.POINTER(_I)]),
     "rsaf_w2v2_workspace_bytes_ragged_ex": (_L, [C.POINTER(_I), _I] + [_I] * 8),
     "rsaf_w2v2_forward_ragged_ex": (_I, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _L, _P, _P, _P]),
+    "rsaf_w2v2_forward_ragged_hidden": (_I, [_P, _P, _P, C.POINTER(_I), _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P, _P, _L, _P, _P,
+                                             C.POINTER(_I), _I, _P, _L, _P]),
 }
 
 _lib = None

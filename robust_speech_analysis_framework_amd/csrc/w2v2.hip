@@ -554,7 +554,10 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 // GEMM's plane output may use for this row (bound_scale_out): |GELU(y W^T + b)| <= |y|_2 max_n |w_n|_2 + max |b|.
 // VAR 1 (stable-layer-norm encoder): the un-normalised sum x + r also goes to aux (the fp32 residual stream).
 // VAR 2 (conv6 of the layer-norm feature encoder): the row first takes its conv LayerNorm (pg, pb, eps 1e-5) and GELU.
-template <int VAR>
+// TAP (hidden-state extraction): the row also goes to `tap`, at row tap_row_start[w] + t (or row `row` when that table is
+// NULL): TAP 1 the normalised output y, TAP 2 the un-normalised input v = x (+ r).  TAP 0 never reads the two trailing
+// arguments, so the untapped instances keep their code.
+template <int VAR, int TAP = 0>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, const float* __restrict__ r,
                                                         const float* __restrict__ g, const float* __restrict__ b,
                                                         float* __restrict__ out, int64_t rows, int D, float eps,
@@ -564,7 +567,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                                                         float* __restrict__ scale_out, const unsigned* __restrict__ bound_w,
                                                         const unsigned* __restrict__ bound_b, float* __restrict__ bound_scale_out,
                                                         unsigned* __restrict__ win_norm, const float* __restrict__ pg,
-                                                        const float* __restrict__ pb, float* __restrict__ aux) {
+                                                        const float* __restrict__ pb, float* __restrict__ aux,
+                                                        float* __restrict__ tap, const int64_t* __restrict__ tap_row_start) {
     // panel != 0: the planes go out in the k16-panel layout of `rows` rows (gemm_f16x3.h), staged through LDS so that the
     // four rows of the workgroup leave as full 128-byte lines per panel (scattering 8-byte pieces from the row layout cost
     // this kernel + 77 %)
@@ -580,6 +584,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     const int D4 = D >> 2;
     const float4* x4 = reinterpret_cast<const float4*>(x + row * D);
     const float4* r4 = r ? reinterpret_cast<const float4*>(r + row * D) : nullptr;
+    float4* t4 = nullptr;
+    if constexpr (TAP != 0) {
+        int64_t trow = row;
+        if (tap_row_start) { const int w = rowwin[row]; trow = tap_row_start[w] + (row - row0[w]); }
+        t4 = reinterpret_cast<float4*>(tap + trow * D);
+    }
     float4 v[4];
     float s = 0.f;
 #pragma unroll
@@ -591,6 +601,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             if (r4) { const float4 t = r4[idx]; v[i].x += t.x; v[i].y += t.y; v[i].z += t.z; v[i].w += t.w; }
             s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
             if (VAR == 1 && valid) reinterpret_cast<float4*>(aux + row * D)[idx] = v[i];
+            if (TAP == 2 && valid) t4[idx] = v[i];
         }
     }
     if constexpr (VAR == 2) {
@@ -641,6 +652,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             const float4 y = make_float4((v[i].x - mean) * rstd * gg.x + bb.x, (v[i].y - mean) * rstd * gg.y + bb.y,
                                          (v[i].z - mean) * rstd * gg.z + bb.z, (v[i].w - mean) * rstd * gg.w + bb.w);
             if (o4 && valid) o4[idx] = y;
+            if (TAP == 1 && valid) t4[idx] = y;
             v[i] = y;
             mx = fmaxf(mx, fmaxf(fmaxf(fabsf(y.x), fabsf(y.y)), fmaxf(fabsf(y.z), fabsf(y.w))));
             n2 += (y.x * y.x + y.y * y.y) + (y.z * y.z + y.w * y.w);
@@ -1199,18 +1211,25 @@ static int ln(const float* x, const float* r, const float* g, const float* b, fl
               const int64_t* row0 = nullptr, unsigned short* planes = nullptr, bool panel = false, float* scale_out = nullptr,
               const unsigned* bound_w = nullptr, const unsigned* bound_b = nullptr, float* bound_scale_out = nullptr,
               unsigned* win_norm = nullptr, int var = 0, const float* pg = nullptr, const float* pb = nullptr,
-              float* aux = nullptr) {
+              float* aux = nullptr, float* tap = nullptr, int tap_mode = 0, const int64_t* tap_row_start = nullptr) {
     const int64_t blocks = (rows + 3) / 4;
     RSAF_CHECK_ARG(blocks <= 0x7fffffffLL, "too many rows");
     RSAF_CHECK_ARG(!planes || scale_out, "planes need their scale array");
     RSAF_CHECK_ARG(!win_norm || rowwin, "the per-window norm needs the row -> window map");
     RSAF_CHECK_ARG((var != 1 || aux) && (var != 2 || (pg && pb)), "layernorm variant without its operands");
-    ProfScope prof("w2v2_layernorm", s, 0.0, (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0) + (aux ? 4 : 0)));
-#define RSAF_LN(V)                                                                                                         \
-    hipLaunchKernelGGL(layernorm_kernel<V>, dim3((unsigned)blocks), dim3(256), 0, s, x, r, g, b, out, rows, D, eps,         \
+    RSAF_CHECK_ARG(!tap || ((tap_mode == 1 && var == 0) || (tap_mode == 2 && var != 2)), "layernorm tap mode not built");
+    RSAF_CHECK_ARG(!tap_row_start || (rowwin && row0), "the tap row map needs the row -> window map");
+    ProfScope prof(tap ? "w2v2_layernorm_tap" : "w2v2_layernorm", s, 0.0,
+                   (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0) + (aux ? 4 : 0) + (tap ? 4 : 0)));
+#define RSAF_LN(...)                                                                                                       \
+    hipLaunchKernelGGL((layernorm_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, s, x, r, g, b, out, rows, D, eps, \
                        out_row_start, rowwin, row0, planes, rows * D, panel ? 1 : 0, scale_out, bound_w, bound_b, bound_scale_out, \
-                       win_norm, pg, pb, aux)
-    if (var == 1) RSAF_LN(1);
+                       win_norm, pg, pb, aux, tap, tap_row_start)
+    if (tap) {                                               // hidden-state taps: post-LN outputs, pre-LN residual streams
+        if (tap_mode == 1) RSAF_LN(0, 1);
+        else if (var == 1) RSAF_LN(1, 2);
+        else RSAF_LN(0, 2);
+    } else if (var == 1) RSAF_LN(1);
     else if (var == 2) RSAF_LN(2);
     else RSAF_LN(0);
 #undef RSAF_LN
@@ -1328,7 +1347,7 @@ int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads,
 
 static int forward_impl(const float* wav, const int64_t* chunk_start, const int* len_dev_or_null, const Rag& R, const Cfg& c,
                         const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
-                        hipStream_t s);
+                        hipStream_t s, float* const* taps = nullptr);
 
 int64_t rsaf_w2v2_workspace_bytes(int n_chunks, int chunk_len, int conv_dim, int hidden, int layers, int heads,
                                   int intermediate, int pos_kernel, int pos_groups) {
@@ -1395,11 +1414,46 @@ int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, co
     return forward_impl(wav, chunk_start, chunk_len, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream);
 }
 
+int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start, const int* chunk_len, const int* chunk_len_host,
+                                    int n_chunks, int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
+                                    int pos_groups, float layer_norm_eps, int flags, const float* weights, void* workspace,
+                                    int64_t workspace_bytes, float* out, const int64_t* out_row_start, const int* hidden_index_host,
+                                    int n_hidden, float* hidden_out, int64_t hidden_plane_floats, rsaf_stream_t stream) {
+    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags};
+    int rc = check_cfg(c);
+    if (rc != RSAF_OK) return rc;
+    // the taps are checked on the host before anything else: strictly increasing layer indices in [0, layers]
+    RSAF_CHECK_ARG(n_hidden >= 0 && n_hidden <= layers + 1, "n_hidden out of range");
+    if (n_hidden == 0)
+        return rsaf_w2v2_forward_ragged_ex(wav, chunk_start, chunk_len, chunk_len_host, n_chunks, conv_dim, hidden, layers, heads,
+                                           intermediate, pos_kernel, pos_groups, layer_norm_eps, flags, weights, workspace,
+                                           workspace_bytes, out, out_row_start, stream);
+    RSAF_CHECK_ARG(hidden_index_host && hidden_out, "NULL hidden-state index list or output");
+    for (int j = 0; j < n_hidden; ++j) {
+        RSAF_CHECK_ARG(hidden_index_host[j] >= 0 && hidden_index_host[j] <= layers, "hidden-state index outside [0, layers]");
+        RSAF_CHECK_ARG(j == 0 || hidden_index_host[j] > hidden_index_host[j - 1], "hidden-state indices not strictly increasing");
+    }
+    RSAF_CHECK_ARG(hidden_plane_floats >= 0 && hidden_plane_floats % 4 == 0 && (reinterpret_cast<uintptr_t>(hidden_out) & 15) == 0,
+                   "hidden-state planes must be 16-byte aligned");
+    RSAF_CHECK_ARG(n_chunks >= 0, "negative chunk count");
+    if (n_chunks == 0) return RSAF_OK;
+    RSAF_CHECK_ARG(chunk_len && chunk_len_host, "NULL length table");
+    Rag R;
+    if ((rc = make_rag(chunk_len_host, n_chunks, R))) return rc;
+    RSAF_CHECK_ARG(hidden_plane_floats >= R.rows * (int64_t)hidden, "hidden_plane_floats smaller than the call's frames");
+    std::vector<float*> taps((size_t)layers + 1, nullptr);
+    for (int j = 0; j < n_hidden; ++j) taps[hidden_index_host[j]] = hidden_out + (int64_t)j * hidden_plane_floats;
+    return forward_impl(wav, chunk_start, chunk_len, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream,
+                        taps.data());
+}
+
 }  // extern "C"
 
 static int forward_impl(const float* wav, const int64_t* chunk_start, const int* len_dev_or_null, const Rag& R, const Cfg& c,
                         const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
-                        hipStream_t s) {
+                        hipStream_t s, float* const* taps) {
+    // taps (NULL: no hidden states): taps[k], k = 0..L, receives hidden_states[k] in the row layout of `out`, or is NULL
+    auto tap = [&](int k) -> float* { return taps ? taps[k] : nullptr; };
     int rc = RSAF_OK;
     const int n_chunks = R.n;
     RSAF_CHECK_ARG(n_chunks <= 65535 / std::max(c.NH, c.PG), "too many chunks per call");
@@ -1689,13 +1743,14 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
         }
         // (fused attention: this LayerNorm also reports the window's largest row norm, behind the scale of layer 0's q / k / v)
         if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
+        // (hidden_states[0]: the tap of this launch; PRE_LN the un-normalised h, post-LN the LayerNorm's output)
         if (c.flags & F_PRE_LN)   // stable layer norm: h = x + pos stays un-normalised (the residual stream); layer 0's LN1(h) -> planes
             rc = ln(ws + W.x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0,
                     planes_at(W.xp), true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 1, nullptr, nullptr,
-                    ws + W.x);
+                    ws + W.x, tap(0), 2, out_row_start);
         else
             rc = ln(ws + W.x, ws + W.y, Wt + L.elng, Wt + L.elnb, ws + W.x, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp), true, ws + W.s_x,
-                    nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr);
+                    nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr, tap(0), 1, out_row_start);
         if (rc) return rc;
     }
     // 6. encoder layers.  Post-LN: y = attn + x, x = LN1(y), y = ffn(x) + x, x = LN2(y).  PRE_LN (stable layer norm): the
@@ -1797,22 +1852,28 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
             if (rc) return rc;
             const bool last = (l == c.L - 1);
             if (pre_ln) {
+                // hidden_states[l + 1]: the residual stream h read by the next layer's LN1 (un-normalised), or, after the last
+                // layer, encoder.layer_norm's output (= out)
                 if (last) {
-                    rc = ln(x, nullptr, Wt + L.elng, Wt + L.elnb, out, rows, Hd, c.eps, s, out_row_start, rowwin, row0);
+                    rc = ln(x, nullptr, Wt + L.elng, Wt + L.elnb, out, rows, Hd, c.eps, s, out_row_start, rowwin, row0, nullptr, false,
+                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, tap(l + 1), 1, out_row_start);
                 } else {
                     if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
                     const LayerOff& ln_next = L.layers[l + 1];
                     rc = ln(x, nullptr, Wt + ln_next.ln1g, Wt + ln_next.ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp),
-                            true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr);
+                            true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr,
+                            tap(l + 1), 2, out_row_start);
                 }
                 if (rc) return rc;
                 continue;
             }
-            // the last LayerNorm writes frame t of window w at out_row_start[w] + t (or packed, window after window)
+            // the last LayerNorm writes frame t of window w at out_row_start[w] + t (or packed, window after window);
+            // hidden_states[l + 1] is this LayerNorm's output
             if (fused && !last) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
             rc = ln(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, last ? out : x, rows, Hd, c.eps, s,
                     last ? out_row_start : nullptr, rowwin, row0, last ? nullptr : planes_at(W.xp), true, ws + W.s_x,
-                    nullptr, nullptr, nullptr, (fused && !last) ? bits_at(W.win_norm) : nullptr);
+                    nullptr, nullptr, nullptr, (fused && !last) ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr,
+                    tap(l + 1), 1, out_row_start);
             if (rc) return rc;
         }
     }

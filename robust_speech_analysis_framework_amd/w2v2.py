@@ -6,6 +6,10 @@ The reference walks each file in 5 s windows every 4 s, normalises every window 
 clips of a batch are planned with the same integer arithmetic, grouped by length and pushed through
 ``rsaf_w2v2_forward`` in large sub-batches; the final LayerNorm writes each window's frames straight
 to its ``np.vstack`` position, so the values per window are those of the batch-1 reference.
+
+``output_layers`` selects transformers' ``hidden_states`` (``output_hidden_states=True``) instead of ``last_hidden_state``:
+the LayerNorm launches of the same forward copy them out (``rsaf_w2v2_forward_ragged_hidden``), and the pooled embeddings
+are averaged on the device (``rsaf_rows_segment_mean_f32``).
 """
 from __future__ import annotations
 
@@ -19,6 +23,29 @@ from .w2v2_config import SAMPLE_RATE, W2V2Config, chunk_plan, load_local_model, 
 from .wavio import read_wav_mono_device
 
 _KERNELS = (10, 3, 3, 3, 3, 2, 2)
+# Device bytes of hidden-state planes per forward call of the drop-ins (n_sel x frames x hidden x 4): a file batch whose
+# planes would exceed it runs as several groups of whole files.  64 files x 30 s with all 13 base states take 4.9 GB.
+HIDDEN_TAP_BUDGET_BYTES = 8 << 30
+
+
+def layer_selection(output_layers, num_layers=None):
+    """Validate ``output_layers`` (an int, or a non-empty list / tuple of ints) against ``num_layers`` encoder layers
+    (``num_layers + 1`` hidden states; Python-style negatives, -1 = the last).  Returns ``(layers, unique, pos)``: the
+    requested indices made non-negative in the requested order, the strictly increasing distinct ones the forward taps,
+    and for every requested index its position in ``unique``.  With ``num_layers=None`` only the types are checked."""
+    items = [output_layers] if isinstance(output_layers, (int, np.integer)) else output_layers
+    if not isinstance(items, (list, tuple)) or not items or \
+            any(isinstance(k, bool) or not isinstance(k, (int, np.integer)) for k in items):
+        raise ValueError(f"output_layers must be an int or a non-empty list / tuple of ints, not {output_layers!r}")
+    if num_layers is None:
+        return None
+    n = num_layers + 1
+    bad = [int(k) for k in items if not -n <= k < n]
+    if bad:
+        raise ValueError(f"output_layers {bad} out of range: this model has hidden states 0..{num_layers} (or -{n}..-1)")
+    layers = [int(k) % n for k in items]
+    unique = sorted(set(layers))
+    return layers, unique, [unique.index(k) for k in layers]
 
 
 def _cfg_args(cfg: W2V2Config):
@@ -109,10 +136,13 @@ class W2V2Engine:
             self._ws = torch.empty(need // 4 + 4, dtype=torch.float32, device=self.device)
         return self._ws
 
-    def forward_windows(self, wav, starts, lens, out, out_rows, stream=None):
+    def forward_windows(self, wav, starts, lens, out, out_rows, stream=None, hidden=None):
         """wav: 1-D float32 device tensor; starts / lens / out_rows: host arrays (sample offset and length of each window in
         ``wav``; first output row of each window in ``out`` [rows, hidden]).  Windows of any mix of lengths run together
-        (``rsaf_w2v2_forward_ragged``, or its ``_ex`` form with the config's flags): they are ordered by length here, longest first, and cut into balanced sub-batches."""
+        (``rsaf_w2v2_forward_ragged``, or its ``_ex`` form with the config's flags): they are ordered by length here, longest first, and cut into balanced sub-batches.
+
+        hidden: strictly increasing hidden-state indices in [0, num_hidden_layers]; then the call returns ``(out, planes)``,
+        planes [len(hidden), rows of out, hidden_size] holding ``hidden_states[hidden[j]]`` in the row layout of ``out``."""
         import torch
         lib = _lib.load()
         cfg = self.cfg
@@ -120,8 +150,16 @@ class W2V2Engine:
         lens = np.asarray(lens, dtype=np.int32)
         out_rows = np.asarray(out_rows, dtype=np.int64)
         n_total = len(starts)
+        planes = None
+        if hidden is not None:
+            hidden = [int(k) for k in hidden]
+            if not hidden or any(not 0 <= k <= cfg.num_hidden_layers for k in hidden) or \
+                    any(b <= a for a, b in zip(hidden, hidden[1:])):
+                raise ValueError(f"hidden must be strictly increasing indices in [0, {cfg.num_hidden_layers}], not {hidden}")
+            planes = torch.empty((len(hidden), out.shape[0], cfg.hidden_size), dtype=torch.float32, device=self.device)
+            hidden_c = (C.c_int * len(hidden))(*hidden)
         if n_total == 0:
-            return out
+            return out if planes is None else (out, planes)
         order = np.argsort(-lens.astype(np.int64), kind="stable")
         starts, lens, out_rows = starts[order], lens[order], out_rows[order]
         # balanced sub-batches: ceil(n / max) calls of (almost) equal size instead of full ones and a remainder (7 000 windows
@@ -145,12 +183,16 @@ class W2V2Engine:
                     float(cfg.layer_norm_eps))
             tail = (_lib.ptr(self.blob), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(out), C.c_void_p(dev.data_ptr() + 8 * n),
                     _lib.stream_ptr(stream))
-            if cfg.flags:                                                      # the large checkpoints' variants
+            if planes is not None:                                             # + the hidden-state taps
+                _lib.check(lib.rsaf_w2v2_forward_ragged_hidden(*head, cfg.flags, *tail[:-1], hidden_c, len(hidden), _lib.ptr(planes),
+                                                                out.shape[0] * cfg.hidden_size, tail[-1]),
+                           "rsaf_w2v2_forward_ragged_hidden")
+            elif cfg.flags:                                                    # the large checkpoints' variants
                 _lib.check(lib.rsaf_w2v2_forward_ragged_ex(*head, cfg.flags, *tail), "rsaf_w2v2_forward_ragged_ex")
             else:                                                              # base architecture (= _ex with flags 0)
                 _lib.check(lib.rsaf_w2v2_forward_ragged(*head, *tail), "rsaf_w2v2_forward_ragged")
             self._keep = (host, dev)                                           # alive until the next call's copy is queued
-        return out
+        return out if planes is None else (out, planes)
 
     def plan(self, lengths, chunk_seconds=5, overlap_seconds=1):
         """Integer-exact window plan of a batch: per clip [(start, len, frames)] + total frames."""
@@ -161,11 +203,13 @@ class W2V2Engine:
             totals.append(sum(f for _, _, f in pl))
         return per_clip, totals
 
-    def extract_packed(self, wav, clip_offsets, lengths, chunk_seconds=5, overlap_seconds=1, stream=None):
+    def extract_packed(self, wav, clip_offsets, lengths, chunk_seconds=5, overlap_seconds=1, stream=None, layers=None):
         """All clips of a packed batch -> (out [sum frames, hidden] device tensor, frame offsets).
 
         wav: 1-D float32 device tensor holding the clips back to back; clip c = samples
-        [clip_offsets[c], clip_offsets[c] + lengths[c])."""
+        [clip_offsets[c], clip_offsets[c] + lengths[c]).
+        layers: strictly increasing hidden-state indices; then the result is (out, frame offsets, planes) with planes
+        [len(layers), sum frames, hidden] (``forward_windows``' ``hidden``)."""
         import torch
         per_clip, totals = self.plan(lengths, chunk_seconds, overlap_seconds)
         frame_off = np.zeros(len(lengths) + 1, dtype=np.int64)
@@ -179,8 +223,42 @@ class W2V2Engine:
                 lens.append(l)
                 rows.append(row)
                 row += f
-        self.forward_windows(wav, starts, lens, out, rows, stream)
-        return out[:int(frame_off[-1])], frame_off
+        if layers is None:
+            self.forward_windows(wav, starts, lens, out, rows, stream)
+            return out[:int(frame_off[-1])], frame_off
+        _, planes = self.forward_windows(wav, starts, lens, out, rows, stream, hidden=layers)
+        return out[:int(frame_off[-1])], frame_off, planes[:, :int(frame_off[-1])]
+
+    def pooled_hidden(self, wav, clip_offsets, lengths, layers, chunk_seconds=5, overlap_seconds=1, stream=None):
+        """Time mean per clip of the hidden states ``layers`` (strictly increasing) -> (means [len(layers), clips, hidden]
+        device tensor, frame offsets); a clip without frames gets NaN.  The planes never leave the device: one
+        ``rsaf_rows_segment_mean_f32`` launch pools all of them (fp64 sums in frame order)."""
+        import torch
+        _, frame_off, planes = self.extract_packed(wav, clip_offsets, lengths, chunk_seconds, overlap_seconds, stream, layers)
+        H = self.cfg.hidden_size
+        means = torch.empty((len(layers), len(lengths), H), dtype=torch.float32, device=self.device)
+        seg = torch.from_numpy(frame_off).to(self.device)
+        _lib.check(_lib.load().rsaf_rows_segment_mean_f32(_lib.ptr(planes), H, planes.shape[1] * H, len(layers), _lib.ptr(seg),
+                                                          len(lengths), H, _lib.ptr(means), _lib.stream_ptr(stream)),
+                   "rsaf_rows_segment_mean_f32")
+        return means, frame_off
+
+    def file_groups(self, lengths, n_planes, chunk_seconds=5, overlap_seconds=1, budget=None):
+        """Split clips (by index) into runs of consecutive clips whose ``n_planes`` hidden-state planes fit the device
+        budget (``HIDDEN_TAP_BUDGET_BYTES``); a clip larger than the budget runs alone."""
+        budget = HIDDEN_TAP_BUDGET_BYTES if budget is None else budget
+        _, totals = self.plan(lengths, chunk_seconds, overlap_seconds)
+        per_frame = n_planes * self.cfg.hidden_size * 4
+        groups, cur, used = [], [], 0
+        for i, f in enumerate(totals):
+            if cur and used + f * per_frame > budget:
+                groups.append(cur)
+                cur, used = [], 0
+            cur.append(i)
+            used += f * per_frame
+        if cur:
+            groups.append(cur)
+        return groups
 
 
 _ENGINES = {}
@@ -208,14 +286,49 @@ def get_engine(model_name, device="cuda"):
     return _ENGINES[key]
 
 
+def _model_layers(model_name):
+    """num_hidden_layers of the model the drop-ins would load, from its config only (None when it cannot be read: the
+    model load reports that)."""
+    try:
+        if os.path.isdir(str(model_name)):
+            import json
+            with open(os.path.join(str(model_name), "config.json")) as f:
+                return W2V2Config.from_hf_dict(json.load(f)).num_hidden_layers
+        if os.environ.get("RSAF_W2V2_RANDOM_SEED") is not None:
+            return W2V2Config().num_hidden_layers
+    except Exception:
+        pass
+    return None
+
+
 def extract_wav2vec2_sequences(input_df, model_name="facebook/wav2vec2-base-960h", audio_file_column="filepath",
-                               chunk_seconds=5, overlap_seconds=1, verbose=True, batch_files=64):
+                               chunk_seconds=5, overlap_seconds=1, verbose=True, batch_files=64, output_layers=None):
     """Drop-in for ``src/foundation_model_extractor.py:37-131``: dict basename -> float32 [T, hidden_size] (768 for base,
     1024 for the large / XLS-R checkpoints).
 
     Files shorter than 0.5 s (``:88``) or failing to load are absent; a model that cannot be
-    loaded gives the reference's convention ``print + {}`` (``:73-74``)."""
+    loaded gives the reference's convention ``print + {}`` (``:73-74``).
+
+    output_layers: None (default) = ``last_hidden_state``.  An int k = transformers' ``hidden_states[k]`` (0 = the encoder
+    input, num_hidden_layers = the last layer; negatives count from the end, -1 = ``last_hidden_state`` bit for bit), still
+    [T, hidden_size] per file.  A list / tuple = float32 [len(output_layers), T, hidden_size] per file, in the requested
+    order.  An index out of range raises ValueError before any device work."""
+    return _extract(input_df, model_name, audio_file_column, chunk_seconds, overlap_seconds, verbose, batch_files,
+                    output_layers, pooled=False)[0]
+
+
+def _extract(input_df, model_name, audio_file_column, chunk_seconds, overlap_seconds, verbose, batch_files, output_layers,
+             pooled):
+    """The drop-ins' file loop -> ({basename: result}, layer_selection(...) or None).  pooled=False: per file the frames
+    ([T, H], or [n_sel, T, H] for a list of layers); pooled=True (output_layers given): per file the time means ([H], or
+    [n_sel, H]), averaged on the device."""
     import torch
+    sel = None
+    if output_layers is not None:
+        layer_selection(output_layers)                                     # the types, before anything else
+        n_layers = _model_layers(model_name)
+        if n_layers is not None:
+            sel = layer_selection(output_layers, n_layers)
     device = "cuda" if torch.cuda.is_available() else "cpu"
     if verbose:
         print(f"Using device: {device}")
@@ -225,7 +338,9 @@ def extract_wav2vec2_sequences(input_df, model_name="facebook/wav2vec2-base-960h
         eng = get_engine(model_name, device)
     except Exception as e:
         print(f"Error loading model '{model_name}': {e}")
-        return {}
+        return {}, sel
+    if output_layers is not None:
+        sel = layer_selection(output_layers, eng.cfg.num_hidden_layers)
     sequences = {}
     paths = list(input_df[audio_file_column])
     for b0 in range(0, len(paths), batch_files):
@@ -257,12 +372,50 @@ def extract_wav2vec2_sequences(input_df, model_name="facebook/wav2vec2-base-960h
             torch.cuda.synchronize()
             return out.cpu().numpy(), frame_off
 
+        def run_layers(batch_clips):
+            """-> per clip: [n_sel, T, H] frames (pooled: [n_sel, H] means), or None when no window survived."""
+            _, unique, pos = sel
+            res = [None] * len(batch_clips)
+            for grp in eng.file_groups([int(batch_clips[i].numel()) for i in range(len(batch_clips))],
+                                       len(unique), chunk_seconds, overlap_seconds):
+                gc = [batch_clips[i] for i in grp]
+                lengths = [int(c.numel()) for c in gc]
+                offs = np.zeros(len(gc) + 1, dtype=np.int64)
+                offs[1:] = np.cumsum(lengths)
+                wav = torch.cat(gc) if len(gc) > 1 else gc[0].contiguous()
+                if pooled:
+                    means, frame_off = eng.pooled_hidden(wav, offs[:-1], lengths, unique, chunk_seconds, overlap_seconds)
+                    torch.cuda.synchronize()
+                    host = means.cpu().numpy()
+                    for k, i in enumerate(grp):
+                        if int(frame_off[k + 1]) > int(frame_off[k]):
+                            res[i] = host[pos, k]
+                else:
+                    _, frame_off, planes = eng.extract_packed(wav, offs[:-1], lengths, chunk_seconds, overlap_seconds,
+                                                              layers=unique)
+                    torch.cuda.synchronize()
+                    host = planes.cpu().numpy()
+                    del planes
+                    for k, i in enumerate(grp):
+                        a, b = int(frame_off[k]), int(frame_off[k + 1])
+                        if b > a:
+                            res[i] = host[pos, a:b]                            # fancy index: a copy per file
+            return res
+
+        def per_clip(batch_clips):
+            if sel is not None:
+                return run_layers(batch_clips)
+            host, frame_off = run(batch_clips)
+            return [host[int(frame_off[i]):int(frame_off[i + 1])].copy() if int(frame_off[i + 1]) > int(frame_off[i]) else None
+                    for i in range(len(batch_clips))]
+
+        def keep(fn, r):
+            if r is not None:                                                  # :123 (no chunk survived)
+                sequences[fn] = r[0] if isinstance(output_layers, (int, np.integer)) else r
+
         try:
-            host, frame_off = run(clips)
-            for i, fn in enumerate(names):
-                a, b = int(frame_off[i]), int(frame_off[i + 1])
-                if b > a:                                                      # :123 (no chunk survived)
-                    sequences[fn] = host[a:b].copy()
+            for fn, r in zip(names, per_clip(clips)):
+                keep(fn, r)
         except (_lib.RsafError, torch.cuda.OutOfMemoryError) as e:
             # one bad file (or an allocation failure of the whole batch) must not take the other files of the batch or
             # the files already done with it: the reference skips only the offending file (:127-129).  Any other
@@ -271,25 +424,55 @@ def extract_wav2vec2_sequences(input_df, model_name="facebook/wav2vec2-base-960h
                 print(f"WARNING: batch of {len(clips)} files failed ({e}); retrying file by file.")
             for fn, c in zip(names, clips):
                 try:
-                    host, frame_off = run([c])
-                    if int(frame_off[1]) > 0:
-                        sequences[fn] = host[:int(frame_off[1])].copy()
+                    keep(fn, per_clip([c])[0])
                 except (_lib.RsafError, torch.cuda.OutOfMemoryError) as e1:
                     if verbose:
                         print(f"FATAL ERROR processing file '{fn}': {e1}. Skipping.")
-    return sequences
+    return sequences, sel
 
 
 def extract_wav2vec2_embeddings(input_df, **kwargs):
-    """Drop-in for ``src/foundation_model_extractor.py:133-166``: time-mean per file."""
+    """Drop-in for ``src/foundation_model_extractor.py:133-166``: time-mean per file.
+
+    output_layers (see ``extract_wav2vec2_sequences``): the means of the selected hidden states, pooled on the device
+    (only [files, n_sel, hidden] reaches the host).  Columns: ``dim_{k}`` for an int, ``l{layer}_dim_{k}`` for a list
+    (layer = the non-negative index), then ``filename``."""
     import pandas as pd
-    seqs = extract_wav2vec2_sequences(input_df, **kwargs)
-    if not seqs:
+    output_layers = kwargs.pop("output_layers", None)                   # keyword only: the reference's (input_df, **kwargs)
+    if output_layers is None:
+        seqs = extract_wav2vec2_sequences(input_df, **kwargs)
+        if not seqs:
+            return pd.DataFrame()
+        rows = []
+        for filename, seq in seqs.items():
+            m = np.mean(seq, axis=0)
+            d = {f"dim_{k}": v for k, v in enumerate(m)}
+            d["filename"] = filename
+            rows.append(d)
+        return pd.DataFrame(rows)
+    args = dict(model_name="facebook/wav2vec2-base-960h", audio_file_column="filepath", chunk_seconds=5, overlap_seconds=1,
+                verbose=True, batch_files=64)
+    unknown = set(kwargs) - set(args)
+    if unknown:
+        raise TypeError(f"extract_wav2vec2_embeddings() got unexpected keyword arguments {sorted(unknown)}")
+    args.update(kwargs)
+    means, sel = _extract(input_df, output_layers=output_layers, pooled=True, **args)
+    if not means:
         return pd.DataFrame()
+    return pd.DataFrame(embedding_rows(means, None if isinstance(output_layers, (int, np.integer)) else sel[0]))
+
+
+def embedding_rows(means, layers):
+    """{filename: means} -> the rows of ``extract_wav2vec2_embeddings``: ``dim_{k}`` of [H] means when ``layers`` is None,
+    else ``l{layers[j]}_dim_{k}`` of [len(layers), H] means; then ``filename``."""
     rows = []
-    for filename, seq in seqs.items():
-        m = np.mean(seq, axis=0)
-        d = {f"dim_{k}": v for k, v in enumerate(m)}
+    for filename, m in means.items():
+        if layers is None:
+            d = {f"dim_{k}": v for k, v in enumerate(m)}
+        else:
+            d = {}
+            for j, layer in enumerate(layers):
+                d.update({f"l{int(layer)}_dim_{k}": v for k, v in enumerate(m[j])})
         d["filename"] = filename
         rows.append(d)
-    return pd.DataFrame(rows)
+    return rows
