@@ -269,11 +269,30 @@ int rsaf_w2v2_forward_ragged(const float* wav, const int64_t* chunk_start, const
  *   CONV_BIAS:        cbias[7][C] (conv layer i's bias)
  *   LAYER_FEAT_NORM:  cln[7][2][C] ({gamma, beta} of conv layer i's LayerNorm; layer 0's lives here, the GroupNorm slots
  *                     gn_gamma / gn_beta are unused)
- * Weight floats, offsets and workspace bytes depend on the flags: size every buffer with the _ex calls.                */
+ * Weight floats, offsets and workspace bytes depend on the flags: size every buffer with the _ex calls.
+ *
+ * The HuBERT and WavLM families are two more variants of the same forward:
+ *   RSAF_W2V2_NO_FEAT_PROJ_LN  HubertConfig.feat_proj_layer_norm=False: the feature projection reads the conv output as it is
+ *                              (feature_projection.layer_norm does not exist; its two weight slots are unused).  Not with
+ *                              RSAF_W2V2_LAYER_FEAT_NORM (RSAF_ERR_ARG): no published geometry pairs them
+ *   RSAF_W2V2_REL_POS_BIAS     WavLM's gated relative position bias: scores = q.k / sqrt(hd) + gate[q][head] * tab[head][k - q]
+ *                              with gate = a * (b * gru_rel_pos_const[head] - 1) + 2, a = sigmoid(x_in[q, head] . ga + ba),
+ *                              b = sigmoid(x_in[q, head] . gb + bb); x_in = the rows the q/k/v projection reads; ga / gb = the
+ *                              sums of rows 0..3 / 4..7 of gru_rel_pos_linear.weight, ba / bb those of its bias
+ * Their weight segments follow the ones above (REL_POS_BIAS only):
+ *   per layer, four offsets:  ga[hd], gb[hd], {ba, bb}, gru_rel_pos_const[heads]
+ *   once, one offset:         tab[heads][2 RSAF_W2V2_REL_SPAN - 1], tab[h][d + RSAF_W2V2_REL_SPAN - 1] =
+ *                             rel_attn_embed[bucket(d)][h] for |d| < RSAF_W2V2_REL_SPAN; the kernels clamp d to that range,
+ *                             which is exact when max_bucket_distance < RSAF_W2V2_REL_SPAN (bucket() is constant beyond it).
+ *                             The packer builds it with transformers' sequence of torch operations
+ * The gates take rows x heads floats of workspace per call.                                                             */
 #define RSAF_W2V2_LAYER_FEAT_NORM 1
 #define RSAF_W2V2_CONV_BIAS 2
 #define RSAF_W2V2_PRE_LN 4
 #define RSAF_W2V2_NO_INPUT_NORM 8
+#define RSAF_W2V2_NO_FEAT_PROJ_LN 32 /* (bit 16 stays an unknown bit: RSAF_ERR_ARG, as callers of ABI 7 were promised) */
+#define RSAF_W2V2_REL_POS_BIAS 64
+#define RSAF_W2V2_REL_SPAN 1024
 int64_t rsaf_w2v2_weight_floats_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                    int pos_groups, int flags);
 int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,

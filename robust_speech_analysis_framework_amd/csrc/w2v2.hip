@@ -25,7 +25,10 @@ namespace rsaf {
 namespace w2v2 {
 
 // flags: the forward variants of the _ex entry points (include/rsaf.h)
-constexpr int F_LAYER_FEAT_NORM = 1, F_CONV_BIAS = 2, F_PRE_LN = 4, F_NO_INPUT_NORM = 8, F_ALL = 15;
+constexpr int F_LAYER_FEAT_NORM = RSAF_W2V2_LAYER_FEAT_NORM, F_CONV_BIAS = RSAF_W2V2_CONV_BIAS, F_PRE_LN = RSAF_W2V2_PRE_LN,
+              F_NO_INPUT_NORM = RSAF_W2V2_NO_INPUT_NORM, F_NO_FEAT_PROJ_LN = RSAF_W2V2_NO_FEAT_PROJ_LN,
+              F_REL_POS_BIAS = RSAF_W2V2_REL_POS_BIAS, F_ALL = 15 | F_NO_FEAT_PROJ_LN | F_REL_POS_BIAS;
+constexpr int REL_SPAN = RSAF_W2V2_REL_SPAN, REL_TAB = 2 * REL_SPAN - 1;    // the distance table of a head: |k - q| < REL_SPAN
 
 struct Cfg {
     int C, Hd, L, NH, I, PK, PG;
@@ -45,6 +48,9 @@ struct Layout {
     int64_t conv0, gng, gnb, conv[6], fplg, fplb, fpw, fpb, posw, posb, elng, elnb;
     std::vector<LayerOff> layers;
     int64_t cb = -1, cln = -1;       // appended segments: conv biases [7][C] (CONV_BIAS), conv LayerNorms [7][2][C] (LAYER_FEAT_NORM)
+    // REL_POS_BIAS: per layer the gate's two summed weight rows ga / gb [hd], {ba, bb} and gru_rel_pos_const [NH]; the table
+    std::vector<int64_t> ga, gb, gbias, gconst;
+    int64_t reltab = -1;             // [NH][REL_TAB]
     int64_t total;
 };
 
@@ -70,6 +76,13 @@ static Layout make_layout(const Cfg& c) {
     }
     if (c.flags & F_CONV_BIAS) L.cb = take((int64_t)7 * c.C);
     if (c.flags & F_LAYER_FEAT_NORM) L.cln = take((int64_t)14 * c.C);
+    if (c.flags & F_REL_POS_BIAS) {
+        for (int l = 0; l < c.L; ++l) {
+            L.ga.push_back(take(c.Hd / c.NH)); L.gb.push_back(take(c.Hd / c.NH));
+            L.gbias.push_back(take(2)); L.gconst.push_back(take(c.NH));
+        }
+        L.reltab = take((int64_t)c.NH * REL_TAB);
+    }
     L.total = o;
     return L;
 }
@@ -84,6 +97,8 @@ static int check_cfg(const Cfg& c) {
     RSAF_CHECK_ARG(c.PG >= 1 && c.Hd % c.PG == 0 && (c.Hd / c.PG) % 4 == 0 && c.PK >= 2 && c.PK % 2 == 0,
                    "positional conv: channels/group multiple of 4, even kernel");
     RSAF_CHECK_ARG((c.flags & ~F_ALL) == 0, "unknown RSAF_W2V2_* flag bits");
+    RSAF_CHECK_ARG(!((c.flags & F_NO_FEAT_PROJ_LN) && (c.flags & F_LAYER_FEAT_NORM)),
+                   "RSAF_W2V2_NO_FEAT_PROJ_LN with RSAF_W2V2_LAYER_FEAT_NORM is not built");
     return RSAF_OK;
 }
 
@@ -109,6 +124,7 @@ struct Workspace {
     // the call (pos_scale, fp_amax, win_norm; wlen: the length table of an equal-window call) and per frame (ln / ffn / qkv scales)
     int64_t conv_scale, conv_amax, pos_scale, fp_amax, wlen, win_norm, s_lnfp, s_x, s_ffn, s_att, s_qkv;
     int64_t cb_max;                                      // CONV_BIAS: max |bias| of conv1..5 (appended after the tables)
+    int64_t gate;                                        // REL_POS_BIAS: the bias gates [rows][NH] of the current layer (appended)
     int64_t t_Tw, t_row0, t_ztab, t_rowwin;              // window tables (int32 / int64 views of the float workspace)
     int slabs, Tp, G;
 };
@@ -203,6 +219,7 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     w.t_Tw = take((int64_t)7 * n); w.t_row0 = take(2 * ((int64_t)n + 1)); w.t_ztab = take((int64_t)7 * n * 2 * 2);
     w.t_rowwin = take(rows);
     w.cb_max = (c.flags & F_CONV_BIAS) ? take(8) : -1;
+    w.gate = (c.flags & F_REL_POS_BIAS) ? take(rows * c.NH) : -1;
     w.total = o;
     return w;
 }
@@ -554,6 +571,7 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
 // GEMM's plane output may use for this row (bound_scale_out): |GELU(y W^T + b)| <= |y|_2 max_n |w_n|_2 + max |b|.
 // VAR 1 (stable-layer-norm encoder): the un-normalised sum x + r also goes to aux (the fp32 residual stream).
 // VAR 2 (conv6 of the layer-norm feature encoder): the row first takes its conv LayerNorm (pg, pb, eps 1e-5) and GELU.
+// VAR 3 (NO_FEAT_PROJ_LN): identity, y = x (+ r); g, b and eps are not read.  The row only changes its form: planes and scales.
 // TAP (hidden-state extraction): the row also goes to `tap`, at row tap_row_start[w] + t (or row `row` when that table is
 // NULL): TAP 1 the normalised output y, TAP 2 the un-normalised input v = x (+ r).  TAP 0 never reads the two trailing
 // arguments, so the untapped instances keep their code.
@@ -629,17 +647,20 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
             }
         }
     }
-    const float mean = wave_sum(s) / D;
-    float q = 0.f;
+    float mean = 0.f, rstd = 1.f;
+    if constexpr (VAR != 3) {
+        mean = wave_sum(s) / D;
+        float q = 0.f;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int idx = lane + 64 * i;
-        if (idx < D4) {
-            const float a = v[i].x - mean, bb = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
-            q += (a * a + bb * bb) + (c * c + d * d);
+        for (int i = 0; i < 4; ++i) {
+            const int idx = lane + 64 * i;
+            if (idx < D4) {
+                const float a = v[i].x - mean, bb = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+                q += (a * a + bb * bb) + (c * c + d * d);
+            }
         }
+        rstd = 1.0f / sqrtf(wave_sum(q) / D + eps);
     }
-    const float rstd = 1.0f / sqrtf(wave_sum(q) / D + eps);
     float4* o4 = out ? reinterpret_cast<float4*>(out + orow * D) : nullptr;
     const float4* g4 = reinterpret_cast<const float4*>(g);
     const float4* b4 = reinterpret_cast<const float4*>(b);
@@ -648,9 +669,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     for (int i = 0; i < 4; ++i) {
         const int idx = lane + 64 * i;
         if (idx < D4) {
-            const float4 gg = g4[idx], bb = b4[idx];
-            const float4 y = make_float4((v[i].x - mean) * rstd * gg.x + bb.x, (v[i].y - mean) * rstd * gg.y + bb.y,
-                                         (v[i].z - mean) * rstd * gg.z + bb.z, (v[i].w - mean) * rstd * gg.w + bb.w);
+            float4 y = v[i];
+            if constexpr (VAR != 3) {
+                const float4 gg = g4[idx], bb = b4[idx];
+                y = make_float4((v[i].x - mean) * rstd * gg.x + bb.x, (v[i].y - mean) * rstd * gg.y + bb.y,
+                                (v[i].z - mean) * rstd * gg.z + bb.z, (v[i].w - mean) * rstd * gg.w + bb.w);
+            }
             if (o4 && valid) o4[idx] = y;
             if (TAP == 1 && valid) t4[idx] = y;
             v[i] = y;
@@ -733,14 +757,21 @@ typedef const __attribute__((address_space(1))) void* attn_glb_ptr;
 //     ((row >> 1) & 1) << 2 so that the four rows of a transposed read sit on disjoint banks;
 //   * O = acc 2^-14 is already in the window's scale: it leaves as the plane pair of the out-projection's A operand.
 // Matrix cycles: 192 MFMAs of 32 cycles per wave against 512 of 64 on the fp32 pipe.
+// RELPOS (WavLM, REL_POS_BIAS): score(q, key) += gate[q][head] * tab[head][key - q].  The head's table over |key - q| <= 255
+// (511 floats of reltab, 2 KB of static LDS beside the 64 KB of K / V blocks: still two workgroups per CU) is staged once per
+// workgroup; a lane loads its query's gate once and reads tab at (255 - q) + key: the keys of a lane are compile-time
+// offsets, and the 32 queries of a half-wave read 32 consecutive words (no bank conflict).  The plain instance reads neither
+// of the two trailing arguments and keeps its code.
 using ah8 = __attribute__((ext_vector_type(8))) _Float16;
 typedef short atr4 __attribute__((__vector_size__(4 * sizeof(short))));
 
+template <bool RELPOS>
 __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short* __restrict__ qkvp, int64_t in_plane,
                                                             unsigned short* __restrict__ planes, int64_t plane_stride,
                                                             int64_t n_rows, const int* __restrict__ Tw,
                                                             const int64_t* __restrict__ row0, int NH, int Hd, float scale,
-                                                            const float* __restrict__ row_scale) {
+                                                            const float* __restrict__ row_scale,
+                                                            const float* __restrict__ gate, const float* __restrict__ reltab) {
     constexpr int HD = 64, KB = 128, PLANE = KB * HD, TILE = 2 * PLANE;          // one staged block: 2 planes x 16 KB (halfs)
     extern __shared__ __attribute__((aligned(1024))) unsigned short kvh[];      // two blocks
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -755,6 +786,15 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short
     const int nblk = (T + KB - 1) / KB;                                         // 1 or 2 key blocks
     const float sw = row_scale[wrow0];                                          // the window's power of two
     const float sinv = pow2_inverse(sw);
+    float qgate = 0.0f;                                                         // RELPOS: this lane's query
+    const float* qtab = nullptr;                                                //         tab[key - q] = qtab[key]
+    if constexpr (RELPOS) {
+        __shared__ float tabs[512];
+        for (int i = tid; i < 511; i += 256) tabs[i] = reltab[(int64_t)head * REL_TAB + (REL_SPAN - 256) + i];   // d = i - 255
+        const int q = blockIdx.y * 128 + wv * 32 + l31;                         // <= 255 (published by the first drain())
+        qgate = gate[(wrow0 + (q < T ? q : T - 1)) * NH + head];
+        qtab = tabs + (255 - q);
+    }
 
     // Q fragments (B operand of S^T = K Q^T): lane (query l31, half h) holds d = 16 s + 8 h + j, both planes
     ah8 qh[4], ql[4];
@@ -828,7 +868,13 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int key = 32 * kt + (e & 3) + 8 * (e >> 2) + 4 * h;
-            const float v = key < T ? sc[kt][e] * sscale : -INFINITY;
+            float v;
+            if constexpr (RELPOS) {                                             // (the table read is unconditional: in bounds for every key)
+                const float sv = fmaf(qgate, qtab[key], sc[kt][e] * sscale);
+                v = key < T ? sv : -INFINITY;
+            } else {
+                v = key < T ? sc[kt][e] * sscale : -INFINITY;
+            }
             sc[kt][e] = v;
             m = fmaxf(m, v);
         }
@@ -942,14 +988,63 @@ __global__ __launch_bounds__(256) void qkv_scale_kernel(const unsigned* __restri
     row_scale[r] = f16x2_scale_for_bound(bound);
 }
 
+// ---- WavLM's bias gate (REL_POS_BIAS): gate[row][head] = a (b const[head] - 1) + 2, a = sigmoid(x . ga + ba), b = sigmoid(x . gb + bb)
+// over the head's hd values of the fp32 row the q/k/v projection reads.  16 lanes per (row, head): a wave instruction reads
+// four whole 64-wide heads (1 KB contiguous); the two weight rows sit in LDS.
+__global__ __launch_bounds__(256) void relpos_gate_kernel(const float* __restrict__ x, int64_t items, int NH, int hd,
+                                                          const float* __restrict__ ga, const float* __restrict__ gb,
+                                                          const float* __restrict__ gbias, const float* __restrict__ gconst,
+                                                          float* __restrict__ gate) {
+    extern __shared__ __attribute__((aligned(16))) float gw[];                  // ga[hd] | gb[hd]
+    for (int i = threadIdx.x; i < 2 * hd; i += 256) gw[i] = i < hd ? ga[i] : gb[i - hd];
+    __syncthreads();
+    const int sub = threadIdx.x & 15;
+    const int64_t raw = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+    const int64_t item = raw < items ? raw : items - 1;                         // = row * NH + head; its values start at item * hd
+    const float4* xp = reinterpret_cast<const float4*>(x + item * hd);
+    const float4* a4 = reinterpret_cast<const float4*>(gw);
+    const float4* b4 = reinterpret_cast<const float4*>(gw + hd);
+    float a = 0.0f, b = 0.0f;
+    for (int k = sub; k < (hd >> 2); k += 16) {
+        const float4 v = xp[k], wa = a4[k], wb = b4[k];
+        a += (v.x * wa.x + v.y * wa.y) + (v.z * wa.z + v.w * wa.w);
+        b += (v.x * wb.x + v.y * wb.y) + (v.z * wb.z + v.w * wb.w);
+    }
+#pragma unroll
+    for (int o = 8; o >= 1; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+    if (sub == 0 && raw < items) {
+        const float sa = 1.0f / (1.0f + expf(-(a + gbias[0]))), sb = 1.0f / (1.0f + expf(-(b + gbias[1])));
+        gate[item] = sa * (sb * gconst[item % NH] - 1.0f) + 2.0f;
+    }
+}
+
 // ---- row softmax in place, one wave per row of length T (row stride Tp, pad columns zeroed) ---------
 // Tp <= 256 (every Wav2Vec2 window: T <= 249): the row lives in one float4 per lane, one load + one store
-template <bool SMALL>
-__global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, int64_t rows, int T, int Tp) {
+// RELPOS (REL_POS_BIAS): row = (window, head, q) of a run of equal windows whose first encoder row is xrow0; the row takes
+// + gate[q][head] * tab[head][c - q] while it is read (c - q clamped to the table: exact, see rsaf.h).  The plain instances
+// never read the four trailing arguments.
+template <bool SMALL, bool RELPOS = false>
+__global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, int64_t rows, int T, int Tp,
+                                                      const float* __restrict__ gate, const float* __restrict__ reltab, int NH,
+                                                      int64_t xrow0) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
     const int lane = threadIdx.x & 63;
     float* p = S + row * Tp;
+    float g = 0.0f;
+    const float* tab = nullptr;                               // the head's table, tab[0] = distance 0
+    int q = 0;
+    if constexpr (RELPOS) {
+        const int64_t wh = row / T;
+        q = (int)(row - wh * T);
+        const int head = (int)(wh % NH);
+        g = gate[(xrow0 + (wh / NH) * T + q) * NH + head];
+        tab = reltab + (int64_t)head * REL_TAB + (REL_SPAN - 1);
+    }
+    auto bias = [&](int c) {                                  // key c of this row's query
+        const int d = c - q;
+        return g * tab[d < -(REL_SPAN - 1) ? -(REL_SPAN - 1) : (d > REL_SPAN - 1 ? REL_SPAN - 1 : d)];
+    };
     if (SMALL) {
         const int c0 = 4 * lane;
         float4 v = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
@@ -957,7 +1052,11 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, int
         float e[4] = {v.x, v.y, v.z, v.w};
         float m = -INFINITY;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) { if (c0 + i >= T) e[i] = -INFINITY; m = fmaxf(m, e[i]); }
+        for (int i = 0; i < 4; ++i) {
+            if constexpr (RELPOS) { if (c0 + i < T) e[i] += bias(c0 + i); }
+            if (c0 + i >= T) e[i] = -INFINITY;
+            m = fmaxf(m, e[i]);
+        }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
         float s = 0.f;
@@ -969,7 +1068,10 @@ __global__ __launch_bounds__(256) void softmax_kernel(float* __restrict__ S, int
         return;
     }
     float m = -INFINITY;
-    for (int c = lane; c < T; c += 64) m = fmaxf(m, p[c]);
+    for (int c = lane; c < T; c += 64) {
+        if constexpr (RELPOS) p[c] += bias(c);
+        m = fmaxf(m, p[c]);
+    }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
     float s = 0.f;
@@ -1217,7 +1319,7 @@ static int ln(const float* x, const float* r, const float* g, const float* b, fl
     RSAF_CHECK_ARG(!planes || scale_out, "planes need their scale array");
     RSAF_CHECK_ARG(!win_norm || rowwin, "the per-window norm needs the row -> window map");
     RSAF_CHECK_ARG((var != 1 || aux) && (var != 2 || (pg && pb)), "layernorm variant without its operands");
-    RSAF_CHECK_ARG(!tap || ((tap_mode == 1 && var == 0) || (tap_mode == 2 && var != 2)), "layernorm tap mode not built");
+    RSAF_CHECK_ARG(!tap || ((tap_mode == 1 && var == 0) || (tap_mode == 2 && var < 2)), "layernorm tap mode not built");
     RSAF_CHECK_ARG(!tap_row_start || (rowwin && row0), "the tap row map needs the row -> window map");
     ProfScope prof(tap ? "w2v2_layernorm_tap" : "w2v2_layernorm", s, 0.0,
                    (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0) + (aux ? 4 : 0) + (tap ? 4 : 0)));
@@ -1231,6 +1333,7 @@ static int ln(const float* x, const float* r, const float* g, const float* b, fl
         else RSAF_LN(0, 2);
     } else if (var == 1) RSAF_LN(1);
     else if (var == 2) RSAF_LN(2);
+    else if (var == 3) RSAF_LN(3);
     else RSAF_LN(0);
 #undef RSAF_LN
     RSAF_CHECK_HIP(hipGetLastError());
@@ -1339,6 +1442,12 @@ int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads,
     // appended segments, one offset per C-float row: conv biases 0..6, then {gamma, beta} of the conv LayerNorms 0..6
     if (L.cb >= 0) for (int i = 0; i < 7; ++i) v.push_back(L.cb + (int64_t)i * c.C);
     if (L.cln >= 0) for (int i = 0; i < 14; ++i) v.push_back(L.cln + (int64_t)i * c.C);
+    // REL_POS_BIAS: per layer {ga, gb, {ba, bb}, gru_rel_pos_const}, then the distance table
+    if (L.reltab >= 0) {
+        for (int l = 0; l < c.L; ++l)
+            for (int64_t o : {L.ga[l], L.gb[l], L.gbias[l], L.gconst[l]}) v.push_back(o);
+        v.push_back(L.reltab);
+    }
     RSAF_CHECK_ARG(cap >= (int)v.size(), "offsets_host too small");
     for (size_t i = 0; i < v.size(); ++i) offsets_host[i] = v[i];
     *n_host = (int)v.size();
@@ -1648,8 +1757,9 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     if (layer_norm)                                          // conv6's LayerNorm (eps 1e-5) + GELU first, in the same row pass
         rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true,
                 ws + W.s_lnfp, nullptr, nullptr, nullptr, nullptr, 2, cln + (int64_t)12 * C, cln + (int64_t)13 * C);
-    else
-        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true, ws + W.s_lnfp);
+    else                                                     // (NO_FEAT_PROJ_LN: the conv output itself, as planes)
+        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true, ws + W.s_lnfp,
+                nullptr, nullptr, nullptr, nullptr, (c.flags & F_NO_FEAT_PROJ_LN) ? 3 : 0);
     if (rc) return rc;
     {
         Out o{}; o.Cf = ws + W.x;
@@ -1660,6 +1770,11 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     const int hd = Hd / c.NH;
     const float scale = 1.0f / sqrtf((float)hd);
     const bool fused = hd == 64 && Tt <= 256;  // attention on the fp16 matrix pipe, q / k / v as plane pairs
+    // REL_POS_BIAS: the gates come from the fp32 rows the q/k/v projection reads: x (post-LN), or LN1(h), which the
+    // stable-layer-norm LayerNorms then also write in fp32 into the att buffer (free until the attention writes it)
+    const bool relpos = c.flags & F_REL_POS_BIAS;
+    const float* reltab = relpos ? Wt + L.reltab : nullptr;
+    float* gate = relpos ? ws + W.gate : nullptr;
     // 5. positional conv embedding (grouped, weight norm folded), GELU, x = LN(x + pos)
     {
         const int cg = Hd / c.PG;
@@ -1745,7 +1860,7 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
         if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
         // (hidden_states[0]: the tap of this launch; PRE_LN the un-normalised h, post-LN the LayerNorm's output)
         if (c.flags & F_PRE_LN)   // stable layer norm: h = x + pos stays un-normalised (the residual stream); layer 0's LN1(h) -> planes
-            rc = ln(ws + W.x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0,
+            rc = ln(ws + W.x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, relpos ? ws + W.att : nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0,
                     planes_at(W.xp), true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 1, nullptr, nullptr,
                     ws + W.x, tap(0), 2, out_row_start);
         else
@@ -1777,15 +1892,28 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
                        Wt + lo.bqkv, nullptr, 1, ACT_NONE, "w2v2_gemm", true);
             if (rc) return rc;
         }
+        if (relpos) {
+            const int64_t items = rows * c.NH;
+            RSAF_CHECK_ARG((items + 15) / 16 <= 0x7fffffffLL, "too many rows");
+            ProfScope prof("w2v2_relpos_gate", s, 0.0, (double)rows * Hd * 4 + (double)items * 4);
+            hipLaunchKernelGGL(relpos_gate_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 2 * hd * sizeof(float), s,
+                               pre_ln ? ws + W.att : x, items, c.NH, hd, Wt + L.ga[l], Wt + L.gb[l], Wt + L.gbias[l], Wt + L.gconst[l], gate);
+            RSAF_CHECK_HIP(hipGetLastError());
+        }
         if (fused) {
             // 2 x 2 T^2 hd flops per (chunk, head)
             double att_flops = 0.0;
             for (const auto& tg : R.tgroups) att_flops += 4.0 * (tg.second - tg.first) * c.NH * (double)R.T6[tg.first] * R.T6[tg.first] * hd;
             ProfScope prof("w2v2_attn_fused", s, att_flops, 0.0);
-            RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_f16x3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 128 * 64 * 2));
-            hipLaunchKernelGGL(attn_f16x3_kernel, dim3((unsigned)(n * c.NH), (unsigned)((Tt + 127) / 128)), dim3(256), 2 * 2 * 128 * 64 * 2, s,
-                               planes_at(W.qkv), rows * 3 * Hd, planes_at(W.attp), rows * Hd, rows, Tw + (int64_t)6 * n, row0, c.NH, Hd, scale,
-                               ws + W.s_qkv);
+#define RSAF_ATTN(RP)                                                                                                          \
+    do {                                                                                                                       \
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_f16x3_kernel<RP>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 128 * 64 * 2)); \
+        hipLaunchKernelGGL(attn_f16x3_kernel<RP>, dim3((unsigned)(n * c.NH), (unsigned)((Tt + 127) / 128)), dim3(256), 2 * 2 * 128 * 64 * 2, s, \
+                           planes_at(W.qkv), rows * 3 * Hd, planes_at(W.attp), rows * Hd, rows, Tw + (int64_t)6 * n, row0, c.NH, Hd, scale, \
+                           ws + W.s_qkv, gate, reltab);                                                                        \
+    } while (0)
+            if (relpos) RSAF_ATTN(true); else RSAF_ATTN(false);
+#undef RSAF_ATTN
             RSAF_CHECK_HIP(hipGetLastError());
         } else {
         // three launches per run of equal windows (head widths other than 64: test geometries)
@@ -1805,12 +1933,12 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
         {
             const int64_t srows = (int64_t)nw * c.NH * Tq;
             ProfScope prof("w2v2_softmax", s, 0.0, (double)srows * Tpq * 8);
-            if (Tpq <= 256)
-                hipLaunchKernelGGL(softmax_kernel<true>, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, s, ws + W.S,
-                                   srows, Tq, Tpq);
-            else
-                hipLaunchKernelGGL(softmax_kernel<false>, dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, s, ws + W.S,
-                                   srows, Tq, Tpq);
+#define RSAF_SOFTMAX(...)                                                                                                      \
+    hipLaunchKernelGGL((softmax_kernel<__VA_ARGS__>), dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, s, ws + W.S, srows, Tq, Tpq, \
+                       gate, reltab, c.NH, r0)
+            if (Tpq <= 256) { if (relpos) RSAF_SOFTMAX(true, true); else RSAF_SOFTMAX(true); }
+            else { if (relpos) RSAF_SOFTMAX(false, true); else RSAF_SOFTMAX(false); }
+#undef RSAF_SOFTMAX
             RSAF_CHECK_HIP(hipGetLastError());
         }
         {   // O = P V per (chunk, head), V is [T, hd] with N contiguous
@@ -1860,7 +1988,7 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
                 } else {
                     if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
                     const LayerOff& ln_next = L.layers[l + 1];
-                    rc = ln(x, nullptr, Wt + ln_next.ln1g, Wt + ln_next.ln1b, nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp),
+                    rc = ln(x, nullptr, Wt + ln_next.ln1g, Wt + ln_next.ln1b, relpos ? ws + W.att : nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp),
                             true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr,
                             tap(l + 1), 2, out_row_start);
                 }

@@ -19,7 +19,8 @@ import os
 import numpy as np
 
 from . import _lib
-from .w2v2_config import SAMPLE_RATE, W2V2Config, chunk_plan, load_local_model, random_state_dict
+from .w2v2_config import (SAMPLE_RATE, W2V2Config, chunk_plan, load_local_model, random_state_dict,
+                          relative_position_table)
 from .wavio import read_wav_mono_device
 
 _KERNELS = (10, 3, 3, 3, 3, 2, 2)
@@ -55,7 +56,7 @@ def _cfg_args(cfg: W2V2Config):
 
 def weight_offsets(cfg: W2V2Config):
     lib = _lib.load()
-    cap = 32 + 21 + 12 * cfg.num_hidden_layers
+    cap = 32 + 21 + 16 * cfg.num_hidden_layers + 1
     buf = (C.c_int64 * cap)()
     n = C.c_int(0)
     _lib.check(lib.rsaf_w2v2_weight_offsets_ex(*_cfg_args(cfg), cfg.flags, buf, cap, C.byref(n)), "rsaf_w2v2_weight_offsets_ex")
@@ -64,7 +65,8 @@ def weight_offsets(cfg: W2V2Config):
 
 def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
     """HF-keyed state_dict -> the float32 blob of ``rsaf_w2v2_forward_ragged_ex`` (weight norm folded,
-    conv kernels tap-major, q/k/v fused; conv biases and conv LayerNorms appended per ``cfg.flags``)."""
+    conv kernels tap-major, q/k/v fused; conv biases, conv LayerNorms, WavLM's summed gate rows and its distance table
+    appended per ``cfg.flags``)."""
     cfg.validate()
     offs, total = weight_offsets(cfg)
     blob = np.zeros(total, dtype=np.float32)
@@ -84,7 +86,10 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
     for i in range(1, 7):
         w = g(f"feature_extractor.conv_layers.{i}.conv.weight")                  # [Cout, Cin, k]
         put(np.ascontiguousarray(w.transpose(0, 2, 1)).reshape(w.shape[0], -1))
-    put(g("feature_projection.layer_norm.weight")); put(g("feature_projection.layer_norm.bias"))
+    if cfg.feat_proj_layer_norm:
+        put(g("feature_projection.layer_norm.weight")); put(g("feature_projection.layer_norm.bias"))
+    else:                                                    # NO_FEAT_PROJ_LN: the two slots stay, unused
+        put(np.zeros(cfg.conv_dim[-1])); put(np.zeros(cfg.conv_dim[-1]))
     put(g("feature_projection.projection.weight")); put(g("feature_projection.projection.bias"))
     wg = g("encoder.pos_conv_embed.conv.parametrizations.weight.original0")      # [1,1,K]
     wv = g("encoder.pos_conv_embed.conv.parametrizations.weight.original1")      # [H, H/G, K]
@@ -107,6 +112,15 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
     if layer:
         for i in range(7):
             put(g(f"feature_extractor.conv_layers.{i}.layer_norm.weight")); put(g(f"feature_extractor.conv_layers.{i}.layer_norm.bias"))
+    if cfg.model_type == "wavlm":
+        # the gate's 8 outputs are summed in two groups of 4 before the sigmoids: sum the weight rows (float64) instead
+        for l in range(cfg.num_hidden_layers):
+            p = f"encoder.layers.{l}.attention."
+            w, b = g(p + "gru_rel_pos_linear.weight"), g(p + "gru_rel_pos_linear.bias")
+            put(w[:4].sum(axis=0)); put(w[4:].sum(axis=0))
+            put(np.array([b[:4].sum(), b[4:].sum()]))
+            put(g(p + "gru_rel_pos_const"))
+        put(relative_position_table(cfg, sd["encoder.layers.0.attention.rel_attn_embed.weight"]))
     assert next(it, None) is None, "weight layout has segments pack_weights does not fill"
     return blob
 

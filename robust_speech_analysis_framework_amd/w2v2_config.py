@@ -8,6 +8,11 @@ for seeded random weights of the base geometry (benchmarks / parity tests).
 Besides base-960h's architecture (GroupNorm feature encoder, no conv bias, post-LN encoder) the
 large checkpoints' variants run too: ``feat_extract_norm="layer"``, ``conv_bias=True``,
 ``do_stable_layer_norm=True`` and a preprocessor with ``do_normalize=False`` (``flags``).
+
+Two sibling families run on the same forward (``model_type`` in config.json): HuBERT, which is Wav2Vec2's arithmetic with
+an optional feature-projection LayerNorm (``feat_proj_layer_norm``), and WavLM, whose attention adds a gated relative
+position bias to the scores (``num_buckets``, ``max_bucket_distance``).  Any other ``model_type`` is refused by name: a
+checkpoint whose keys merely contain Wav2Vec2's would otherwise run without the terms it adds.
 """
 from __future__ import annotations
 
@@ -18,8 +23,10 @@ from dataclasses import dataclass, field
 import numpy as np
 
 # forward variants of rsaf_w2v2_forward_ragged_ex (include/rsaf.h)
-LAYER_FEAT_NORM, CONV_BIAS, PRE_LN, NO_INPUT_NORM = 1, 2, 4, 8
+LAYER_FEAT_NORM, CONV_BIAS, PRE_LN, NO_INPUT_NORM, NO_FEAT_PROJ_LN, REL_POS_BIAS = 1, 2, 4, 8, 32, 64
 MAX_HIDDEN = 1024                  # LayerNorm runs one wave per row
+REL_SPAN = 1024                    # RSAF_W2V2_REL_SPAN: the packed distance table covers |k - q| < REL_SPAN, clamped beyond
+MODEL_TYPES = ("wav2vec2", "hubert", "wavlm")
 
 
 @dataclass
@@ -38,6 +45,10 @@ class W2V2Config:
     conv_bias: bool = False
     do_stable_layer_norm: bool = False         # pre-LN encoder
     do_normalize: bool = True                  # preprocessor_config.json: zero-mean / unit-variance windows
+    model_type: str = "wav2vec2"               # "wav2vec2", "hubert" or "wavlm"
+    feat_proj_layer_norm: bool = True          # hubert: False = no LayerNorm before the feature projection
+    num_buckets: int = 320                     # wavlm: rows of rel_attn_embed
+    max_bucket_distance: int = 800             # wavlm: bucket() is constant from this distance on
     extras: dict = field(default_factory=dict)
 
     @property
@@ -48,7 +59,8 @@ class W2V2Config:
     def flags(self) -> int:
         """The RSAF_W2V2_* bits of this architecture (0 for base-960h's)."""
         return ((LAYER_FEAT_NORM if self.feat_extract_norm == "layer" else 0) | (CONV_BIAS if self.conv_bias else 0)
-                | (PRE_LN if self.do_stable_layer_norm else 0) | (0 if self.do_normalize else NO_INPUT_NORM))
+                | (PRE_LN if self.do_stable_layer_norm else 0) | (0 if self.do_normalize else NO_INPUT_NORM)
+                | (0 if self.feat_proj_layer_norm else NO_FEAT_PROJ_LN) | (REL_POS_BIAS if self.model_type == "wavlm" else 0))
 
     def frames(self, n_samples: int) -> int:
         """Feature-encoder output length (transformers ``_get_feat_extract_output_lengths``)."""
@@ -74,14 +86,37 @@ class W2V2Config:
             raise ValueError(f"feat_extract_norm={self.feat_extract_norm!r} is not supported (need 'group' or 'layer')")
         if self.hidden_size % self.num_attention_heads or self.head_dim % 4:
             raise ValueError("head_dim must be a multiple of 4")
+        if self.model_type not in MODEL_TYPES:
+            raise ValueError(f"model_type={self.model_type!r} is not supported (need one of {MODEL_TYPES})")
+        if not self.feat_proj_layer_norm and (self.model_type != "hubert" or self.feat_extract_norm == "layer"):
+            raise ValueError("feat_proj_layer_norm=False is built for hubert with feat_extract_norm='group' only")
+        if self.model_type == "wavlm":
+            if self.num_buckets < 4 or self.num_buckets % 4:
+                raise ValueError(f"num_buckets={self.num_buckets} must be a positive multiple of 4")
+            if not self.num_buckets // 4 < self.max_bucket_distance < REL_SPAN:
+                raise ValueError(f"max_bucket_distance={self.max_bucket_distance} must lie in (num_buckets / 4, {REL_SPAN}): "
+                                 f"the packed distance table covers |k - q| < {REL_SPAN}")
         g = self.num_conv_pos_embedding_groups
         if self.hidden_size % g or (self.hidden_size // g) % 4 or self.num_conv_pos_embeddings % 2:
             raise ValueError("pos-conv: channels per group must be a multiple of 4, kernel even")
 
     @staticmethod
     def from_hf_dict(d: dict, do_normalize: bool = True) -> "W2V2Config":
-        """``config.json`` of a Wav2Vec2 checkpoint -> config; raises for anything this build cannot run.
-        ``do_normalize``: the preprocessor's switch (``preprocessor_config.json``), not part of config.json."""
+        """``config.json`` of a Wav2Vec2, HuBERT or WavLM checkpoint -> config; raises for anything this build cannot run
+        (any other ``model_type`` by name).  ``do_normalize``: the preprocessor's switch (``preprocessor_config.json``), not
+        part of config.json."""
+        model_type = d.get("model_type", "wav2vec2")
+        if model_type not in MODEL_TYPES:
+            raise ValueError(f"config.json: model_type={model_type!r} is not supported (need one of {MODEL_TYPES}); its "
+                             "weights may load as Wav2Vec2's, its forward is another one")
+        family = {}
+        if model_type == "hubert":
+            if d.get("conv_pos_batch_norm", False):
+                raise ValueError("config.json: conv_pos_batch_norm=true is not supported")
+            family["feat_proj_layer_norm"] = bool(d.get("feat_proj_layer_norm", True))
+        elif model_type == "wavlm":
+            family["num_buckets"] = int(d.get("num_buckets", 320))
+            family["max_bucket_distance"] = int(d.get("max_bucket_distance", 800))
         for key, want in (("feat_extract_activation", "gelu"), ("hidden_act", "gelu")):
             if d.get(key, want) != want:
                 raise ValueError(f"config.json: {key}={d.get(key)!r} is not supported (need {want!r})")
@@ -103,11 +138,12 @@ class W2V2Config:
                           num_conv_pos_embedding_groups=d["num_conv_pos_embedding_groups"],
                           layer_norm_eps=d.get("layer_norm_eps", 1e-5),
                           feat_extract_norm=d.get("feat_extract_norm", "group"), conv_bias=bool(d.get("conv_bias", False)),
-                          do_stable_layer_norm=bool(d.get("do_stable_layer_norm", False)), do_normalize=bool(do_normalize))
+                          do_stable_layer_norm=bool(d.get("do_stable_layer_norm", False)), do_normalize=bool(do_normalize),
+                          model_type=model_type, **family)
 
 
 def hf_shapes(cfg: W2V2Config) -> dict:
-    """state_dict keys/shapes of ``transformers.Wav2Vec2Model`` for this geometry."""
+    """state_dict keys/shapes of ``transformers.Wav2Vec2Model`` (``HubertModel``, ``WavLMModel``) for this geometry."""
     sh = {}
     cin = 1
     for i, (c, k) in enumerate(zip(cfg.conv_dim, cfg.conv_kernel)):
@@ -125,8 +161,9 @@ def hf_shapes(cfg: W2V2Config) -> dict:
         for i in range(7):
             sh[f"feature_extractor.conv_layers.{i}.conv.bias"] = (cfg.conv_dim[i],)
     Hd, Cc = cfg.hidden_size, cfg.conv_dim[-1]
-    sh["feature_projection.layer_norm.weight"] = (Cc,)
-    sh["feature_projection.layer_norm.bias"] = (Cc,)
+    if cfg.feat_proj_layer_norm:
+        sh["feature_projection.layer_norm.weight"] = (Cc,)
+        sh["feature_projection.layer_norm.bias"] = (Cc,)
     sh["feature_projection.projection.weight"] = (Hd, Cc)
     sh["feature_projection.projection.bias"] = (Hd,)
     K, G = cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups
@@ -148,7 +185,38 @@ def hf_shapes(cfg: W2V2Config) -> dict:
         sh[p + "feed_forward.output_dense.bias"] = (Hd,)
         sh[p + "final_layer_norm.weight"] = (Hd,)
         sh[p + "final_layer_norm.bias"] = (Hd,)
+    # WavLM's keys come last: the draws of random_state_dict for the keys above stay what they were
+    if cfg.model_type == "wavlm":
+        for l in range(cfg.num_hidden_layers):
+            p = f"encoder.layers.{l}.attention."
+            sh[p + "gru_rel_pos_const"] = (1, cfg.num_attention_heads, 1, 1)
+            sh[p + "gru_rel_pos_linear.weight"] = (8, cfg.head_dim)
+            sh[p + "gru_rel_pos_linear.bias"] = (8,)
+        sh["encoder.layers.0.attention.rel_attn_embed.weight"] = (cfg.num_buckets, cfg.num_attention_heads)
     return sh
+
+
+def relative_position_table(cfg: W2V2Config, rel_attn_embed) -> np.ndarray:
+    """[heads, 2 REL_SPAN - 1] float32: entry [h, d + REL_SPAN - 1] = rel_attn_embed[bucket(d), h], d = key - query.  The
+    buckets come from the torch operations of ``WavLMAttention._relative_positions_bucket`` in their order (a float32
+    ``log``, two float32 scalings, a truncation): one ulp at a bucket edge would swap a whole embedding row."""
+    import math
+
+    import torch
+    d = torch.arange(-(REL_SPAN - 1), REL_SPAN, dtype=torch.long)
+    num_buckets = cfg.num_buckets // 2
+    buckets = (d > 0).to(torch.long) * num_buckets
+    d = torch.abs(d)
+    max_exact = num_buckets // 2
+    is_small = d < max_exact
+    large = torch.log(d.float() / max_exact)
+    large = large / math.log(cfg.max_bucket_distance / max_exact)
+    large = large * (num_buckets - max_exact)
+    large = (max_exact + large).to(torch.long)
+    large = torch.min(large, torch.full_like(large, num_buckets - 1))
+    buckets += torch.where(is_small, d, large)
+    emb = np.asarray(rel_attn_embed, dtype=np.float32)
+    return np.ascontiguousarray(emb[buckets.numpy()].T)
 
 
 def random_state_dict(cfg: W2V2Config, seed: int = 0) -> dict:
@@ -159,6 +227,8 @@ def random_state_dict(cfg: W2V2Config, seed: int = 0) -> dict:
     for k, shape in hf_shapes(cfg).items():
         if k.endswith("layer_norm.weight"):
             v = 1.0 + 0.1 * rng.standard_normal(shape)
+        elif "gru_rel_pos" in k or "rel_attn_embed" in k:       # O(1): the gated bias moves the scores
+            v = rng.standard_normal(shape)
         elif k.endswith("bias"):
             v = 0.05 * rng.standard_normal(shape)
         elif k.endswith("original0"):
@@ -174,12 +244,15 @@ def random_state_dict(cfg: W2V2Config, seed: int = 0) -> dict:
 
 
 def _strip_prefix(sd: dict) -> dict:
-    """base-960h is a Wav2Vec2ForCTC checkpoint: keys carry a ``wav2vec2.`` prefix; ``lm_head`` is unused.  The heads of
-    Wav2Vec2ForPreTraining checkpoints (XLSR-53, XLS-R: ``quantizer``, ``project_q``, ``project_hid``) are unused too."""
+    """base-960h is a Wav2Vec2ForCTC checkpoint: keys carry a ``wav2vec2.`` prefix (``hubert.`` / ``wavlm.`` in those
+    families' CTC and classification checkpoints); ``lm_head`` is unused.  The heads of Wav2Vec2ForPreTraining checkpoints
+    (XLSR-53, XLS-R: ``quantizer``, ``project_q``, ``project_hid``) are unused too."""
     out = {}
     for k, v in sd.items():
-        if k.startswith("wav2vec2."):
-            k = k[len("wav2vec2."):]
+        for prefix in ("wav2vec2.", "hubert.", "wavlm."):
+            if k.startswith(prefix):
+                k = k[len(prefix):]
+                break
         if k.startswith(("lm_head", "quantizer.", "project_q.", "project_hid.")) or k == "masked_spec_embed":
             continue
         k = k.replace("pos_conv_embed.conv.weight_g", "pos_conv_embed.conv.parametrizations.weight.original0")
@@ -230,6 +303,10 @@ def save_local_model(model_dir: str, cfg: W2V2Config, sd: dict):
          "layer_norm_eps": cfg.layer_norm_eps, "feat_extract_norm": cfg.feat_extract_norm, "feat_extract_activation": "gelu",
          "hidden_act": "gelu", "do_stable_layer_norm": bool(cfg.do_stable_layer_norm), "conv_bias": bool(cfg.conv_bias),
          "model_type": "wav2vec2"}
+    if cfg.model_type == "hubert":
+        d.update(model_type="hubert", feat_proj_layer_norm=bool(cfg.feat_proj_layer_norm))
+    elif cfg.model_type == "wavlm":
+        d.update(model_type="wavlm", num_buckets=cfg.num_buckets, max_bucket_distance=cfg.max_bucket_distance)
     with open(os.path.join(model_dir, "config.json"), "w") as f:
         json.dump(d, f)
     if not cfg.do_normalize:

@@ -1,9 +1,11 @@
-"""Rate of the Wav2Vec2 stage at the base geometry and at the large stable-layer-norm geometry.
+"""Rate of the Wav2Vec2 stage per architecture: Wav2Vec2 base and large stable-layer-norm, WavLM base, HuBERT base.
 
 Times ``W2V2Engine.extract_packed`` on 64 x 30 s synthetic clips (the reference's 5 s / 4 s window plan: 448 windows)
-with seeded random weights, and prints audio seconds per second for each architecture.
+with seeded random weights, and prints audio seconds per second for each architecture.  The architectures alternate
+within every repetition (one process, one device), so a drift of the device hits all of them alike; ratios are taken
+per repetition.
 
-    python tools/w2v2_variant_rate.py [--clips 64] [--seconds 30] [--reps 5] [--out FILE]
+    python tools/w2v2_variant_rate.py [--models base,wavlm_base] [--clips 64] [--seconds 30] [--reps 10] [--out FILE]
 """
 import argparse
 import json
@@ -26,41 +28,57 @@ LARGE = dict(conv_dim=(512,) * 7, hidden_size=1024, num_hidden_layers=24, num_at
              feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True)
 
 
-def rate(cfg, wav, offs, lengths, reps):
-    eng = W2V2Engine(cfg, random_state_dict(cfg, seed=0))
-    eng.extract_packed(wav, offs, lengths)                 # warm-up (workspace, weight planes, code objects)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        t0 = time.perf_counter()
-        out, _ = eng.extract_packed(wav, offs, lengths)
-        torch.cuda.synchronize()
-        times.append(time.perf_counter() - t0)
-    audio = sum(lengths) / 16000.0
-    med = float(np.median(times))
-    return {"flags": cfg.flags, "hidden": cfg.hidden_size, "layers": cfg.num_hidden_layers, "frames": int(out.shape[0]),
-            "median_s": med, "min_s": float(min(times)), "audio_s": audio, "audio_s_per_s": audio / med}
+BASE = dict(conv_dim=(512,) * 7, hidden_size=768, num_hidden_layers=12, num_attention_heads=12, intermediate_size=3072)
+MODELS = {
+    "base": W2V2Config(),
+    "large_stable_ln": W2V2Config(**LARGE),
+    "wavlm_base": W2V2Config(**BASE, model_type="wavlm"),
+    "hubert_base": W2V2Config(**BASE, model_type="hubert", feat_proj_layer_norm=False),
+}
 
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="base,large_stable_ln", help="comma-separated: " + ", ".join(MODELS))
     ap.add_argument("--clips", type=int, default=64)
     ap.add_argument("--seconds", type=float, default=30.0)
-    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    names = a.models.split(",")
+    unknown = [n for n in names if n not in MODELS]
+    if unknown:
+        ap.error(f"unknown models {unknown}")
     clips = synth.synth_batch(a.clips, a.seconds, pool=8)
     lengths = [clips.shape[1]] * a.clips
     offs = np.arange(a.clips, dtype=np.int64) * clips.shape[1]
     wav = torch.from_numpy(clips.reshape(-1)).cuda()
-    res = {"device": torch.cuda.get_device_name(0), "clips": a.clips, "seconds": a.seconds, "reps": a.reps}
-    for name, cfg in (("base", W2V2Config()), ("large_stable_ln", W2V2Config(**LARGE))):
-        r = rate(cfg, wav, offs, lengths, a.reps)
-        res[name] = r
-        print(f"{name:16s} flags {r['flags']:2d}  {r['audio_s']:.0f} audio-s in {r['median_s'] * 1e3:.1f} ms (median of {a.reps})"
-              f"  -> {r['audio_s_per_s']:.0f} audio-s/s", flush=True)
-    res["base_over_large"] = res["base"]["audio_s_per_s"] / res["large_stable_ln"]["audio_s_per_s"]
-    print(f"base / large: {res['base_over_large']:.2f}x")
+    audio = sum(lengths) / 16000.0
+    engines, frames = {}, {}
+    for n in names:                                        # warm-up (workspace, weight planes, code objects)
+        engines[n] = W2V2Engine(MODELS[n], random_state_dict(MODELS[n], seed=0))
+        frames[n] = int(engines[n].extract_packed(wav, offs, lengths)[0].shape[0])
+    torch.cuda.synchronize()
+    times = {n: [] for n in names}
+    for rep in range(a.reps):                              # the architectures alternate within every repetition
+        for n in names[rep % len(names):] + names[:rep % len(names)]:
+            t0 = time.perf_counter()
+            engines[n].extract_packed(wav, offs, lengths)
+            torch.cuda.synchronize()
+            times[n].append(time.perf_counter() - t0)
+    res = {"device": torch.cuda.get_device_name(0), "clips": a.clips, "seconds": a.seconds, "reps": a.reps, "order": "alternating"}
+    for n in names:
+        cfg, t = MODELS[n], np.array(times[n])
+        med = float(np.median(t))
+        res[n] = {"model_type": cfg.model_type, "flags": cfg.flags, "hidden": cfg.hidden_size, "layers": cfg.num_hidden_layers,
+                  "frames": frames[n], "median_s": med, "min_s": float(t.min()), "max_s": float(t.max()), "audio_s": audio,
+                  "audio_s_per_s": audio / med, "times_s": [float(v) for v in t]}
+        print(f"{n:16s} {cfg.model_type:8s} flags {cfg.flags:3d}  {audio:.0f} audio-s in {med * 1e3:.1f} ms (median of {a.reps}, "
+              f"{t.min() * 1e3:.1f} .. {t.max() * 1e3:.1f})  -> {audio / med:.0f} audio-s/s", flush=True)
+    for n in names[1:]:                                    # time ratio to the first model, per repetition
+        r = np.array(times[n]) / np.array(times[names[0]])
+        res[f"{n}_over_{names[0]}_time"] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
+        print(f"{n} / {names[0]} time: median {np.median(r):.4f} ({r.min():.4f} .. {r.max():.4f})")
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
