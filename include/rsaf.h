@@ -214,6 +214,42 @@ int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int
                                 int64_t saved_floats, float* scratch, int64_t scratch_floats,
                                 const float* dlogits, float* grads, rsaf_stream_t stream);
 
+/* ---- Group training step: K independent replicas of one architecture in one call -----------------------
+ * The reference trains models of identical architecture and hyper-parameters on different data one after another
+ * (the inner folds of an Optuna trial, src/dl_cv_strategies.py:224-251; the folds of :399-422).  A group call runs
+ * the step above for K such replicas (own weights, own batch of own shape B x T, own masks) on one stream, with the
+ * LSTM recurrences of all replicas in ONE launch per layer and pass; everything else runs per replica.  The results
+ * are those of K single calls, bit for bit.  Every field of an item means what the argument of the same name means
+ * above; sizes per item from rsaf_cnnlstm_train_saved_floats / _scratch_floats / _param_floats.  Each replica needs
+ * its own `scratch` (stages of different replicas interleave).  forward reads x .. bn_stats_out, backward x ..
+ * scratch_floats, dlogits and grads.  All checks of the single entries apply per item, plus 1 <= K <=
+ * RSAF_CNNLSTM_GROUP_MAX and no two items overlapping in saved, scratch, logits (forward) or grads (backward); they
+ * all run before the first launch, and rsaf_last_error() names the item.  A group in which a batch exceeds the
+ * 4-row recurrence threshold (RSAF_LSTM_SMALL_MAX, default 1 024) runs that recurrence per replica. */
+#define RSAF_CNNLSTM_GROUP_MAX 16
+typedef struct {
+    const float* x;
+    int B, T;
+    const float* params;
+    const float* mask_block1;
+    const float* mask_block2;
+    const float* const* mask_lstm_host;
+    const float* mask_fc;
+    float* saved;
+    int64_t saved_floats;
+    float* scratch;
+    int64_t scratch_floats;
+    float* logits;                 /* forward */
+    float* bn_stats_out;           /* forward, optional */
+    const float* dlogits;          /* backward */
+    float* grads;                  /* backward */
+} rsaf_cnnlstm_train_item;
+int rsaf_cnnlstm_train_group_max(void);
+int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels,
+                                     int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
+int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels,
+                                      int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
+
 /* ---- Wav2Vec2 frame embeddings for a batch of equal-length chunks -----------------------------------
  * Replaces, per chunk, `processor(chunk).input_values` + `Wav2Vec2Model(...)(input_values)
  * .last_hidden_state` (src/foundation_model_extractor.py:113-116; third-party transformers

@@ -27,6 +27,14 @@ _I = C.c_int
 _L = C.c_int64
 _F = C.c_float
 
+
+class TrainItem(C.Structure):
+    """``rsaf_cnnlstm_train_item``: one replica of a group training step (``mask_lstm_host``: host array of device pointers)."""
+    _fields_ = [("x", _P), ("B", _I), ("T", _I), ("params", _P), ("mask_block1", _P), ("mask_block2", _P),
+                ("mask_lstm_host", _P), ("mask_fc", _P), ("saved", _P), ("saved_floats", _L), ("scratch", _P),
+                ("scratch_floats", _L), ("logits", _P), ("bn_stats_out", _P), ("dlogits", _P), ("grads", _P)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -60,6 +68,9 @@ SIGNATURES = {
     "rsaf_cnnlstm_train_scratch_floats": (_L, [_I, _I, _I, _I, _I, _I]),
     "rsaf_cnnlstm_train_forward": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]),
     "rsaf_cnnlstm_train_backward": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P]),
+    "rsaf_cnnlstm_train_group_max": (_I, []),
+    "rsaf_cnnlstm_train_forward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_train_backward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),
     "rsaf_mshds_intensity": (_I, [_P, _P, _I, _I, _P, _I, C.c_double, _I, _P, _P, _P]),

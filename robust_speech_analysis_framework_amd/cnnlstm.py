@@ -287,6 +287,42 @@ def draw_masks(model, B, T, device):
             "fc": mk((B, 2 * d["hidden"]), float(model.dropout.p))}
 
 
+def _pack_train_blob(model, device):
+    """The module's parameters in the blob layout of ``rsaf_cnnlstm_train_param_offsets``: (segments, blob)."""
+    segs, total = _train_segments(model)
+    blob = torch.zeros(total, dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for off, n, pack, _ in segs:
+            blob[off:off + n] = pack()
+    return segs, blob
+
+
+def _update_running_stats(model, stats, B, T):
+    """Running statistics, as nn.BatchNorm1d in training mode (momentum, unbiased variance); stats [5][3][C] of the step."""
+    with torch.no_grad():
+        for i, (bn, n) in enumerate(zip(_bn_modules(model), (B * T, B * T, B * T, B * (T // 2), B * (T // 2)))):
+            if bn is None or not bn.track_running_stats or bn.running_mean is None:
+                continue
+            bn.num_batches_tracked += 1
+            m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+            bn.running_mean.mul_(1 - m).add_(stats[i, 0], alpha=m)
+            bn.running_var.mul_(1 - m).add_(stats[i, 1], alpha=m * (n / (n - 1.0) if n > 1 else 1.0))
+
+
+def _unpack_grads(segs, params, grads):
+    by_param = {id(prm): (off, n, unpack) for off, n, _, outs in segs for prm, unpack in outs}
+    out = []
+    for prm in params:
+        off, n, unpack = by_param[id(prm)]
+        out.append(unpack(grads[off:off + n]).reshape(prm.shape).contiguous())
+    return out
+
+
+def _lstm_mask_ptrs(masks):
+    lm = masks["lstm"]
+    return (C.c_void_p * max(len(lm), 1))(*[(_lib.ptr(m) if m is not None else None) for m in lm]) if lm else None
+
+
 class _TrainStep(torch.autograd.Function):
     """logits = CNNLSTM(x) in training mode; backward fills the parameter gradients (none for x)."""
 
@@ -295,11 +331,7 @@ class _TrainStep(torch.autograd.Function):
         lib = _lib.load()
         d = model.dims
         B, T, D = x.shape
-        segs, total = _train_segments(model)
-        blob = torch.zeros(total, dtype=torch.float32, device=x.device)
-        with torch.no_grad():
-            for off, n, pack, _ in segs:
-                blob[off:off + n] = pack()
+        segs, blob = _pack_train_blob(model, x.device)
         a = (B, T, D, d["channels"], d["hidden"], d["layers"])
         n_saved, n_scr = int(lib.rsaf_cnnlstm_train_saved_floats(*a)), int(lib.rsaf_cnnlstm_train_scratch_floats(*a))
         if n_saved < 0 or n_scr < 0:
@@ -310,8 +342,7 @@ class _TrainStep(torch.autograd.Function):
         scratch = model._train_scratch
         logits = torch.empty((B, d["num_classes"]), dtype=torch.float32, device=x.device)
         stats = torch.empty((5, 3, d["channels"]), dtype=torch.float32, device=x.device)
-        lm = masks["lstm"]
-        lstm_ptrs = (C.c_void_p * max(len(lm), 1))(*[(_lib.ptr(m) if m is not None else None) for m in lm]) if lm else None
+        lstm_ptrs = _lstm_mask_ptrs(masks)
         ctx.call = (x, B, T, D, d["channels"], d["hidden"], d["num_classes"], d["layers"], _ACT_CODE[model.activation_name])
         ctx.bufs = (blob, masks, lstm_ptrs, saved, scratch)
         ctx.segs = segs
@@ -322,15 +353,7 @@ class _TrainStep(torch.autograd.Function):
             _lib.ptr(x), *ctx.call[1:], _lib.ptr(blob), optr(masks["res_block1"]), optr(masks["res_block2"]), lstm_ptrs,
             optr(masks["fc"]), _lib.ptr(saved), n_saved, _lib.ptr(scratch), scratch.numel(), _lib.ptr(logits),
             _lib.ptr(stats), _lib.stream_ptr(None)), "rsaf_cnnlstm_train_forward")
-        # running statistics, as nn.BatchNorm1d in training mode (momentum, unbiased variance)
-        with torch.no_grad():
-            for i, (bn, n) in enumerate(zip(_bn_modules(model), (B * T, B * T, B * T, B * (T // 2), B * (T // 2)))):
-                if bn is None or not bn.track_running_stats or bn.running_mean is None:
-                    continue
-                bn.num_batches_tracked += 1
-                m = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-                bn.running_mean.mul_(1 - m).add_(stats[i, 0], alpha=m)
-                bn.running_var.mul_(1 - m).add_(stats[i, 1], alpha=m * (n / (n - 1.0) if n > 1 else 1.0))
+        _update_running_stats(model, stats, B, T)
         return logits
 
     @staticmethod
@@ -350,12 +373,7 @@ class _TrainStep(torch.autograd.Function):
             optr(masks["fc"]), _lib.ptr(saved), saved.numel(), _lib.ptr(scratch), scratch.numel(), _lib.ptr(dl),
             _lib.ptr(grads), _lib.stream_ptr(None)), "rsaf_cnnlstm_train_backward")
         ctx.bufs = None
-        by_param = {id(prm): (off, n, unpack) for off, n, _, outs in ctx.segs for prm, unpack in outs}
-        out = []
-        for prm in ctx.params:
-            off, n, unpack = by_param[id(prm)]
-            out.append(unpack(grads[off:off + n]).reshape(prm.shape).contiguous())
-        return (None, None, None, *out)
+        return (None, None, None, *_unpack_grads(ctx.segs, ctx.params, grads))
 
 
 class CNNLSTM(nn.Module):
@@ -453,3 +471,220 @@ def collate_zero_pad(seqs, device="cuda"):
 def eval_outputs(logits):
     """``_eval_model`` post-processing (``src/dl_cv_strategies.py:183-194``): P(class 1) and argmax."""
     return torch.softmax(logits, dim=1)[:, 1], torch.argmax(logits, dim=1)
+
+
+# ---- group training step: K independent replicas of one architecture in one step --------------------------------------
+# The reference trains models of identical architecture and hyper-parameters on different data one after another (the
+# inner folds of an Optuna trial, ``src/dl_cv_strategies.py:224-251``; the folds of ``:399-422``).  One such training
+# keeps 2 of the chip's 256 CUs busy during its LSTM recurrences, which are most of the step; K of them side by side
+# put the recurrences of all replicas into one launch per layer and pass (``rsaf_cnnlstm_train_forward_group`` /
+# ``_backward_group``).  Everything else runs per replica, so the results are those of K separate steps, bit for bit.
+
+def train_group_max():
+    """Replicas per C call (``rsaf_cnnlstm_train_group_max``); longer lists are split into chunks of this size."""
+    return int(_lib.load().rsaf_cnnlstm_train_group_max())
+
+
+def _group_call(fn, what, reps, dims, act, backward):
+    """One ``rsaf_cnnlstm_train_{forward,backward}_group`` call per chunk of ``train_group_max()`` replicas."""
+    gmax = train_group_max()
+    optr = lambda t: t.data_ptr() if t is not None else None                         # noqa: E731
+    for c0 in range(0, len(reps), gmax):
+        chunk = reps[c0:c0 + gmax]
+        items = (_lib.TrainItem * len(chunk))()
+        for it, r in zip(items, chunk):
+            mk = r["masks"]
+            it.x, it.B, it.T, it.params = r["x"].data_ptr(), r["B"], r["T"], r["blob"].data_ptr()
+            it.mask_block1, it.mask_block2, it.mask_fc = optr(mk["res_block1"]), optr(mk["res_block2"]), optr(mk["fc"])
+            it.mask_lstm_host = C.cast(r["lstm_ptrs"], C.c_void_p) if r["lstm_ptrs"] is not None else None
+            it.saved, it.saved_floats = r["saved"].data_ptr(), r["saved"].numel()
+            it.scratch, it.scratch_floats = r["scratch"].data_ptr(), r["scratch"].numel()
+            if backward:
+                it.dlogits, it.grads = r["dlogits"].data_ptr(), r["grads"].data_ptr()
+            else:
+                it.logits, it.bn_stats_out = r["logits"].data_ptr(), r["stats"].data_ptr()
+        _lib.check(fn(items, len(chunk), dims["input_dim"], dims["channels"], dims["hidden"], dims["num_classes"],
+                      dims["layers"], _ACT_CODE[act], _lib.stream_ptr(None)), what)
+
+
+class _TrainGroupStep(torch.autograd.Function):
+    """(logits_0, ..., logits_K-1) of K replicas in training mode; backward fills the parameter gradients of every
+    replica whose output received a gradient."""
+
+    @staticmethod
+    def forward(ctx, models, xs, masks, *params):
+        lib = _lib.load()
+        ctx.set_materialize_grads(False)          # an output outside the loss arrives as None, not as zeros
+        d = models[0].dims
+        reps, p0 = [], 0
+        for model, x, mk in zip(models, xs, masks):
+            B, T, D = x.shape
+            segs, blob = _pack_train_blob(model, x.device)
+            a = (B, T, D, d["channels"], d["hidden"], d["layers"])
+            n_saved, n_scr = int(lib.rsaf_cnnlstm_train_saved_floats(*a)), int(lib.rsaf_cnnlstm_train_scratch_floats(*a))
+            if n_saved < 0 or n_scr < 0:
+                raise ValueError("sequence length must be >= 2")
+            if model._train_scratch is None or model._train_scratch.numel() < n_scr or model._train_scratch.device != x.device:
+                model._train_scratch = torch.empty(n_scr, dtype=torch.float32, device=x.device)
+            n_par = sum(len(outs) for _, _, _, outs in segs)
+            reps.append({"model": model, "x": x, "B": B, "T": T, "segs": segs, "blob": blob, "masks": mk,
+                         "lstm_ptrs": _lstm_mask_ptrs(mk), "scratch": model._train_scratch,
+                         "saved": torch.empty(n_saved, dtype=torch.float32, device=x.device),
+                         "logits": torch.empty((B, d["num_classes"]), dtype=torch.float32, device=x.device),
+                         "stats": torch.empty((5, 3, d["channels"]), dtype=torch.float32, device=x.device),
+                         "params": params[p0:p0 + n_par]})
+            p0 += n_par
+        ctx.reps, ctx.dims, ctx.act = reps, d, models[0].activation_name
+        _group_call(lib.rsaf_cnnlstm_train_forward_group, "rsaf_cnnlstm_train_forward_group", reps, d, ctx.act, False)
+        for r in reps:
+            _update_running_stats(r["model"], r["stats"], r["B"], r["T"])
+        return tuple(r["logits"] for r in reps)
+
+    @staticmethod
+    def backward(ctx, *dlogits):
+        lib = _lib.load()
+        if ctx.reps is None:
+            raise RuntimeError("CNNLSTM group training step: backward can run once per forward (the saved activations "
+                               "are consumed)")
+        live = []
+        for r, dl in zip(ctx.reps, dlogits):
+            if dl is None:
+                continue
+            if r["scratch"] is not r["model"]._train_scratch:
+                r["scratch"] = torch.empty_like(r["scratch"])
+            r["dlogits"] = dl.to(torch.float32).contiguous()
+            r["grads"] = torch.zeros_like(r["blob"])
+            live.append(r)
+        _group_call(lib.rsaf_cnnlstm_train_backward_group, "rsaf_cnnlstm_train_backward_group", live, ctx.dims, ctx.act, True)
+        out = []
+        for r, dl in zip(ctx.reps, dlogits):
+            out += [None] * len(r["params"]) if dl is None else _unpack_grads(r["segs"], r["params"], r["grads"])
+        ctx.reps = None
+        return (None, None, None, *out)
+
+
+def cnnlstm_train_group(models, xs, masks=None):
+    """One training-mode forward of K independent ``CNNLSTM`` replicas (same ``dims`` and activation; own weights, own
+    batch ``xs[k]`` of own shape [B_k, T_k, D]) -> list of K logits tensors.  Sum the K losses and call ``backward()``
+    once: the replicas share nothing, so each model's ``.grad`` is the gradient of its own loss, and an output that
+    stays out of the loss leaves its model without gradients.  Logits, gradients and BatchNorm buffers are those of K
+    separate ``model(x)`` steps, bit for bit; the LSTM recurrences of all replicas run in one launch per layer and pass.
+
+    ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
+    model's ``forced_masks`` if set and draws them from torch's device RNG otherwise, replica by replica."""
+    models, xs = list(models), list(xs)
+    if not models:
+        raise ValueError("cnnlstm_train_group needs at least one replica")
+    if len(models) != len(xs):
+        raise ValueError(f"{len(models)} models but {len(xs)} inputs")
+    if masks is not None and len(masks) != len(models):
+        raise ValueError(f"{len(models)} models but {len(masks)} mask sets")
+    first = models[0]
+    seen_modules, seen_params = {}, {}
+    for k, m in enumerate(models):
+        if m.dims != first.dims or m.activation_name != first.activation_name:
+            raise ValueError(f"replica {k} differs from replica 0: dims {m.dims} / activation {m.activation_name!r} against "
+                             f"{first.dims} / {first.activation_name!r}")
+        if not m.training:
+            raise ValueError(f"replica {k} is in eval mode: the group step is the training step (model.train())")
+        if id(m) in seen_modules:
+            raise ValueError(f"replicas {seen_modules[id(m)]} and {k} are the same module")
+        seen_modules[id(m)] = k
+        for name, prm in m.named_parameters():
+            if id(prm) in seen_params:
+                raise ValueError(f"replicas {seen_params[id(prm)]} and {k} share the parameter {name}")
+        for prm in m.parameters():
+            seen_params[id(prm)] = k
+    D = first.dims["input_dim"]
+    for k, x in enumerate(xs):
+        if x.dim() != 3 or x.shape[2] != D:
+            raise ValueError(f"replica {k}: expected input [B, T, {D}], got {tuple(x.shape)}")
+        if x.shape[0] * (x.shape[1] // 2) <= 1:
+            raise ValueError(f"replica {k}: Expected more than 1 value per channel when training")
+    for k, x in enumerate(xs):
+        if not x.is_cuda:
+            raise _lib.RsafError(f"cnnlstm_train_group needs HIP (cuda) tensors (replica {k}): there is no CPU fallback")
+    xs = [x.detach().to(torch.float32).contiguous() for x in xs]
+    mks = []
+    for k, (m, x) in enumerate(zip(models, xs)):
+        mk = masks[k] if masks is not None else None
+        if mk is None:
+            mk = m.forced_masks if m.forced_masks is not None else draw_masks(m, x.shape[0], x.shape[1], x.device)
+        mks.append(mk)
+    params = [p for m in models for _, _, _, outs in _train_segments(m)[0] for p, _ in outs]
+    return list(_TrainGroupStep.apply(models, xs, mks, *params))
+
+
+class CNNLSTMGroup(nn.Module):
+    """K ``CNNLSTM`` replicas of one architecture that train side by side.  ``forward(xs)`` takes one batch per replica
+    (``None``: the replica sits out and its output is ``None``): in training mode the group step over the others, in
+    eval mode each model's own inference forward.  ``state_dict`` keys are ``models.<k>.<reference key>``, so a
+    replica's weights load into a plain ``CNNLSTM``."""
+
+    def __init__(self, models):
+        super().__init__()
+        self.models = nn.ModuleList(models)
+        if len(self.models) == 0:
+            raise ValueError("CNNLSTMGroup needs at least one replica")
+        for k, m in enumerate(self.models):
+            if not isinstance(m, CNNLSTM):
+                raise TypeError(f"replica {k} is a {type(m).__name__}, not a CNNLSTM")
+
+    def forward(self, xs):
+        xs = list(xs)
+        if len(xs) != len(self.models):
+            raise ValueError(f"{len(self.models)} replicas but {len(xs)} inputs")
+        live = [k for k, x in enumerate(xs) if x is not None]
+        outs = [None] * len(xs)
+        if self.training:
+            if live:
+                for k, o in zip(live, cnnlstm_train_group([self.models[k] for k in live], [xs[k] for k in live])):
+                    outs[k] = o
+        else:
+            for k in live:
+                outs[k] = self.models[k](xs[k])
+        return outs
+
+
+def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device):
+    """The reference's inner training loop (``src/dl_cv_strategies.py:244-248``: ``zero_grad / model(seq) / loss /
+    backward / step`` per batch, a fixed number of epochs) for K replicas over K loaders in lock step: step i of an
+    epoch takes batch i of every loader through one group step.  Loaders may differ in length; a replica whose epoch
+    is exhausted sits out until the others finish theirs.  Returns the mean training loss per epoch of every replica
+    (``histories[k][epoch]``, accumulated as the reference's ``train_model`` does, ``:120-129``); the K losses of a
+    step come to the host in one copy.
+
+    Parameters, buffers and losses equal those of K sequential trainings bit for bit as long as the replicas see the
+    same batches and dropout masks.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
+    its permutations from torch's global RNG: in lock step the K loaders draw in a different order than K sequential
+    trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  The same holds
+    for dropout masks, which come from the device RNG replica by replica within a step."""
+    models, optimizers, loaders = list(models), list(optimizers), list(loaders)
+    if not (len(models) == len(optimizers) == len(loaders)):
+        raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
+    histories = [[] for _ in models]
+    for _ in range(epochs):
+        for m in models:
+            m.train()
+        its = [iter(ld) for ld in loaders]
+        total, count = [0.0] * len(models), [0] * len(models)
+        while True:
+            batches = [next(it, None) for it in its]
+            live = [k for k, b in enumerate(batches) if b is not None]
+            if not live:
+                break
+            xs = [batches[k][0].to(device) for k in live]
+            labs = [batches[k][1].to(device) for k in live]
+            for k in live:
+                optimizers[k].zero_grad()
+            outs = cnnlstm_train_group([models[k] for k in live], xs)
+            losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
+            torch.stack(losses).sum().backward()
+            for k in live:
+                optimizers[k].step()
+            for k, v in zip(live, torch.stack([ls.detach() for ls in losses]).tolist()):
+                total[k] += v
+                count[k] += 1
+        for k in range(len(models)):
+            histories[k].append(total[k] / max(count[k], 1))
+    return histories

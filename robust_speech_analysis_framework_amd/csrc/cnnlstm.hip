@@ -201,17 +201,19 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_rec_kernel(const float* xpro
 // (column c = 16*gate + u).  W_hh stays register-resident (H registers per lane: the lane's column over all k), h
 // is broadcast from LDS.  The gate pre-activations of one (row, unit) land in four lanes (one per gate); they are
 // exchanged through a wave-private LDS tile so that lane (q, u) updates cell (row q, unit u).
+// The body is shared by the one-recurrence kernel and the group kernel below: `dir` and `tile` (the 4-row tile of the
+// batch) are what blockIdx.y / blockIdx.x are to the former.
 template <int H, bool SAVE>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_kernel(const float* xproj, const float* __restrict__ whh,
-                                                                float* __restrict__ hout, float* gates_save,
-                                                                float* __restrict__ c_save, int B, int T) {
+__device__ __forceinline__ void lstm_rec4_body(const float* xproj, const float* __restrict__ whh,
+                                               float* __restrict__ hout, float* gates_save,
+                                               float* __restrict__ c_save, int B, int T, int dir, int tile) {
     constexpr int LDH = H + 4;
     constexpr int NW = H / 16;
     __shared__ __attribute__((aligned(16))) float hbuf[2][4][LDH];
     __shared__ float gx[NW][4][80];                 // [wave][row][16*gate + u], row stride 80: conflict-free both ways
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int gq = lane >> 4, u = lane & 15;        // as a column: gate gq of unit u; as a cell owner: row gq of unit u
-    const int dir = blockIdx.y, b0 = blockIdx.x * 4;
+    const int b0 = tile * 4;
     const int unit = 16 * w + u;
 
     float breg[H];
@@ -303,6 +305,24 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_kernel(const float* xpr
     }
 }
 
+template <int H, bool SAVE>
+__global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_kernel(const float* xproj, const float* __restrict__ whh,
+                                                                float* __restrict__ hout, float* gates_save,
+                                                                float* __restrict__ c_save, int B, int T) {
+    lstm_rec4_body<H, SAVE>(xproj, whh, hout, gates_save, c_save, B, T, blockIdx.y, blockIdx.x);
+}
+
+// Several independent recurrences (same H; own weights, own B and T) in one launch: grid (max tiles, 2, K), blockIdx.z
+// selects the descriptor.  The descriptors are kernel arguments (wave-uniform: they load through scalar registers), so
+// a launch needs no device table and no copy.  A workgroup whose tile lies beyond its recurrence's batch leaves before
+// it touches LDS or a barrier; the others loop over their own T.
+template <int H, bool SAVE>
+__global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_group_kernel(const LstmRecGroup g) {
+    const LstmRecItem& it = g.item[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= it.B) return;
+    lstm_rec4_body<H, SAVE>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, blockIdx.y, blockIdx.x);
+}
+
 // ---- attention pooling (softmax over time) + final Linear -----------------------------------------
 template <int NF>   // features per lane: 2H = 64*NF
 __global__ __launch_bounds__(256) void attnpool_fc_kernel(const float* __restrict__ seq, const float* __restrict__ watt,
@@ -373,8 +393,7 @@ int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* ga
     RSAF_CHECK_ARG((gates_save == nullptr) == (c_save == nullptr), "gates_save and c_save go together");
     ProfScope prof("lstm_recurrent", s, 2.0 * B * T * 2.0 * 4 * H * H, 0.0);
     // 4-row workgroups while they still fit the chip about twice over; the 16-row tile beyond (same pipe time for 4x the rows)
-    static const int small_max = [] { const char* e = getenv("RSAF_LSTM_SMALL_MAX"); return e ? atoi(e) : 1024; }();
-    const bool small = B <= small_max;
+    const bool small = B <= lstm_small_max();
     dim3 grid(small ? (B + 3) / 4 : (B + 15) / 16, 2);
 #define RSAF_LSTM_LAUNCH(KERNEL, HH, SV) \
     hipLaunchKernelGGL((KERNEL<HH, SV>), grid, dim3(HH / 16 * 64), 0, s, xproj, whh, hout, gates_save, c_save, B, T)
@@ -385,6 +404,38 @@ int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* ga
         if (gates_save) { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec_kernel, 128, true); else RSAF_LSTM_LAUNCH(lstm_rec_kernel, 64, true); }
         else { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec_kernel, 128, false); else RSAF_LSTM_LAUNCH(lstm_rec_kernel, 64, false); }
     }
+#undef RSAF_LSTM_LAUNCH
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int lstm_small_max() {
+    static const int v = [] { const char* e = getenv("RSAF_LSTM_SMALL_MAX"); return e ? atoi(e) : 1024; }();
+    return v;
+}
+
+int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s) {
+    using namespace cnnlstm;
+    RSAF_CHECK_ARG(H == 64 || H == 128, "lstm_hidden_dim must be 64 or 128");
+    RSAF_CHECK_ARG(items && K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "a group holds 1 to 16 recurrences");
+    LstmRecGroup g{};
+    const bool save = items[0].gates_save != nullptr;
+    int tiles = 0;
+    double flops = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const LstmRecItem& it = items[k];
+        RSAF_CHECK_ARG(it.B >= 1 && it.B <= lstm_small_max() && it.T >= 1, "a grouped recurrence runs on the 4-row tiles");
+        RSAF_CHECK_ARG((it.gates_save != nullptr) == save && (it.c_save != nullptr) == save,
+                       "gates_save and c_save go together, for all recurrences of a group or for none");
+        g.item[k] = it;
+        tiles = std::max(tiles, (it.B + 3) / 4);
+        flops += 2.0 * it.B * it.T * 2.0 * 4 * H * H;
+    }
+    ProfScope prof("lstm_recurrent", s, flops, 0.0);
+    dim3 grid(tiles, 2, K);
+#define RSAF_LSTM_LAUNCH(HH, SV) hipLaunchKernelGGL((lstm_rec4_group_kernel<HH, SV>), grid, dim3(HH / 16 * 64), 0, s, g)
+    if (save) { if (H == 128) RSAF_LSTM_LAUNCH(128, true); else RSAF_LSTM_LAUNCH(64, true); }
+    else { if (H == 128) RSAF_LSTM_LAUNCH(128, false); else RSAF_LSTM_LAUNCH(64, false); }
 #undef RSAF_LSTM_LAUNCH
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;

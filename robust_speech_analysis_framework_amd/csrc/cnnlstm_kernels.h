@@ -11,6 +11,25 @@ namespace rsaf {
 int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* gates_save, float* c_save, int B, int T,
                     int H, hipStream_t s);
 
+// The same for up to RSAF_CNNLSTM_GROUP_MAX independent recurrences of one H (own weights, own B and T) in ONE launch of the
+// 4-row kernel: every B must be <= lstm_small_max(), and all of them save gates / cell states or none does.  The
+// descriptors travel by value in the kernel arguments.
+struct LstmRecItem {
+    const float* xproj;
+    const float* whh;
+    float* hout;
+    float* gates_save;
+    float* c_save;
+    int B, T;
+};
+struct LstmRecGroup {
+    LstmRecItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s);
+
+// Largest batch that runs on the 4-row recurrence kernels (environment RSAF_LSTM_SMALL_MAX, read once; default 1 024).
+int lstm_small_max();
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter, i.e. waits for
 // the write acknowledgements of the per-step global stores of the recurrences - a few hundred cycles on every time step
 // for data no other wave of the workgroup reads.

@@ -661,17 +661,17 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_bwd_kernel(float* gates, con
 // instruction are 4 gates x 4 groups of 4 units, i.e. lane (g, u) contracts the H rows of gate g against unit u (its
 // W_hh column slice is register-resident, H registers) and a two-step butterfly over the gate lanes completes the sum
 // in a fixed order.  No partial products through LDS.
+// The body is shared by the one-recurrence kernel and the group kernel below (`dir`, `tile`: direction and 4-row tile).
 template <int H>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_kernel(float* gates, const float* __restrict__ cst,
-                                                                const float* __restrict__ dh_out, const float* __restrict__ whh,
-                                                                int B, int T) {
+__device__ __forceinline__ void lstm_bwd4_body(float* gates, const float* __restrict__ cst, const float* __restrict__ dh_out,
+                                               const float* __restrict__ whh, int B, int T, int dir, int tile) {
     constexpr int NW = H / 16;
     constexpr int LDG = 4 * H + 20;                 // row stride = 20 banks (mod 32): the four rows of a fragment read and the
                                                     // 16-lane row groups of the cell owners' writes land on distinct banks
     __shared__ __attribute__((aligned(16))) float dg[2][4][LDG];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q = lane >> 4, u = lane & 15;
-    const int dir = blockIdx.y, b0 = blockIdx.x * 4;
+    const int b0 = tile * 4;
     const int unit = 16 * w + u;
     const int arow = lane & 3;
 
@@ -761,6 +761,34 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_kernel(float* gates, co
         cur ^= 1;
         ig = nig; fg = nfg; gg = ngg; og = nog; cc = ncc; dho = ndho;
     }
+}
+
+template <int H>
+__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_kernel(float* gates, const float* __restrict__ cst,
+                                                                const float* __restrict__ dh_out, const float* __restrict__ whh,
+                                                                int B, int T) {
+    lstm_bwd4_body<H>(gates, cst, dh_out, whh, B, T, blockIdx.y, blockIdx.x);
+}
+
+// The BPTT recurrences of several independent replicas in one launch, as lstm_rec4_group_kernel (cnnlstm.hip) does for the
+// forward ones: grid (max tiles, 2, K), descriptors by value in the kernel arguments, a workgroup beyond its replica's
+// batch leaves before it touches LDS or a barrier.
+struct LstmBwdItem {
+    float* gates;
+    const float* cst;
+    const float* dh;
+    const float* whh;
+    int B, T;
+};
+struct LstmBwdGroup {
+    LstmBwdItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+template <int H>
+__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_group_kernel(const LstmBwdGroup g) {
+    const LstmBwdItem& it = g.item[blockIdx.z];
+    if ((int)blockIdx.x * 4 >= it.B) return;
+    lstm_bwd4_body<H>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, blockIdx.y, blockIdx.x);
 }
 
 // ---- host-side helpers ------------------------------------------------------------------------------------------
@@ -888,6 +916,408 @@ static int conv3_dgrad(const Ctx& c, const float* dy, const float* w, float* dx,
 
 #define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
 
+static int launch_lstm_bwd(float* gates, const float* cst, const float* dh, const float* whh, int B, int T, int H, hipStream_t s) {
+    ProfScope prof("lstm_bwd_recurrent", s, 2.0 * B * T * 2.0 * 4 * H * H, 0.0);
+    if (B <= lstm_small_max()) {
+        dim3 grid((B + 3) / 4, 2);
+        if (H == 128) hipLaunchKernelGGL(lstm_bwd4_kernel<128>, grid, dim3(512), 0, s, gates, cst, dh, whh, B, T);
+        else hipLaunchKernelGGL(lstm_bwd4_kernel<64>, grid, dim3(256), 0, s, gates, cst, dh, whh, B, T);
+    } else {
+        dim3 grid((B + 15) / 16, 2);
+        const size_t lds = (size_t)2 * 16 * (4 * H + 4) * sizeof(float);
+        if (H == 128)
+            RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)lstm_bwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (H == 128) hipLaunchKernelGGL(lstm_bwd_kernel<128>, grid, dim3(512), lds, s, gates, cst, dh, whh, B, T);
+        else hipLaunchKernelGGL(lstm_bwd_kernel<64>, grid, dim3(256), lds, s, gates, cst, dh, whh, B, T);
+    }
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// every B <= lstm_small_max() (the caller's choice of path)
+static int launch_lstm_bwd_group(const LstmBwdItem* items, int K, int H, hipStream_t s) {
+    LstmBwdGroup g{};
+    int tiles = 0;
+    double flops = 0.0;
+    for (int k = 0; k < K; ++k) {
+        g.item[k] = items[k];
+        tiles = std::max(tiles, (items[k].B + 3) / 4);
+        flops += 2.0 * items[k].B * items[k].T * 2.0 * 4 * H * H;
+    }
+    ProfScope prof("lstm_bwd_recurrent", s, flops, 0.0);
+    dim3 grid(tiles, 2, K);
+    if (H == 128) hipLaunchKernelGGL(lstm_bwd4_group_kernel<128>, grid, dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(lstm_bwd4_group_kernel<64>, grid, dim3(256), 0, s, g);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// ---- one replica's step, cut at its recurrences into phases -----------------------------------------------------------
+// forward:  fwd_cnn (+ layer-0 input projection) | per layer: recurrence | fwd_after_rec (dropout + next input projection)
+//           | fwd_head;   backward:  bwd_head | per layer: BPTT recurrence | bwd_after_rec | bwd_blocks.
+// The single entries run the phases of their one replica with the one-recurrence launchers; the group entries run every
+// phase for all replicas and one grouped recurrence launch in between.
+struct Replica {
+    rsaf_cnnlstm_train_item it;
+    SLayout S;
+    WLayout WL;
+    Ctx c;
+    const float* lin;               // forward: input of the next LSTM layer, `in` features wide
+    int in;
+    float *dcur, *dnext;            // backward: gradient w.r.t. the output of the current layer | the free buffer
+};
+
+static int fail(int code, const char* who, int idx, const char* msg) {
+    set_error(std::string(who) + ": " + (idx >= 0 ? "item " + std::to_string(idx) + ": " : std::string()) + msg);
+    return code;
+}
+
+// argument checks of one replica (idx < 0: the single entries, whose messages carry no item)
+static int check_item(const Dims& d, const rsaf_cnnlstm_train_item& it, bool backward, hipStream_t s, const char* who, int idx,
+                      Replica* r) {
+    if (!(it.B >= 1 && it.B <= 65535)) return fail(RSAF_ERR_ARG, who, idx, "batch must be in [1, 65535]");
+    if (!(it.T >= 2)) return fail(RSAF_ERR_ARG, who, idx, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
+    if (!((int64_t)it.B * it.T <= 0x3fffffffLL)) return fail(RSAF_ERR_ARG, who, idx, "B*T too large");
+    const bool ptrs = it.x && it.params && it.saved && it.scratch && (backward ? it.dlogits && it.grads : it.logits != nullptr);
+    if (!ptrs) return fail(RSAF_ERR_ARG, who, idx, "NULL pointer");
+    r->it = it;
+    r->S = make_slayout(d, it.B, it.T);
+    r->WL = make_wlayout(d, it.B, it.T);
+    if (it.saved_floats < r->S.total || it.scratch_floats < r->WL.total)
+        return fail(RSAF_ERR_WORKSPACE, who, idx, "saved/scratch buffer too small");
+    r->c = Ctx{d, s, it.scratch, r->WL};
+    r->lin = nullptr; r->in = 0; r->dcur = r->dnext = nullptr;
+    return RSAF_OK;
+}
+
+static bool overlap(const float* a, int64_t na, const float* b, int64_t nb) { return a < b + nb && b < a + na; }
+
+static int check_group(const Dims& d, const rsaf_cnnlstm_train_item* items, int K, bool backward, hipStream_t s, const char* who,
+                       Replica* reps) {
+    TRY(check_dims(d));
+    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    if (!items) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    for (int k = 0; k < K; ++k) TRY(check_item(d, items[k], backward, s, who, k, &reps[k]));
+    const int64_t np = make_playout(d).total;
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const rsaf_cnnlstm_train_item &a = items[j], &b = items[k];
+            const char* what = overlap(a.saved, reps[j].S.total, b.saved, reps[k].S.total) ? "saved"
+                               : overlap(a.scratch, reps[j].WL.total, b.scratch, reps[k].WL.total) ? "scratch"
+                               : !backward && overlap(a.logits, (int64_t)a.B * d.NC, b.logits, (int64_t)b.B * d.NC) ? "logits"
+                               : backward && overlap(a.grads, np, b.grads, np) ? "grads" : nullptr;
+            if (what) return fail(RSAF_ERR_ARG, who, k, (std::string("shares `") + what + "` with item " + std::to_string(j)).c_str());
+        }
+    return RSAF_OK;
+}
+
+static int fwd_inproj(Replica& r, const PLayout& L, int l) {
+    const Dims& d = r.c.d;
+    const int64_t rows2 = (int64_t)r.it.B * (r.it.T / 2);
+    GemmParams p = gemm_params_plain(r.lin, r.it.params + L.wih[l], r.it.saved + r.S.gates[l], (int)rows2, 8 * d.H, r.in, r.in, r.in, 8 * d.H);
+    p.bias = r.it.params + L.bsum[l];
+    return launch_gemm_f32(p, r.c.s, "train_lstm_inproj_gemm");
+}
+
+static int fwd_cnn(Replica& r, const PLayout& L) {
+    const Ctx& c = r.c;
+    const Dims& d = c.d;
+    const SLayout& S = r.S;
+    hipStream_t s = c.s;
+    const int B = r.it.B, T = r.it.T, D = d.D, C = d.C, Tp = T / 2, act = d.act;
+    const int64_t rows = (int64_t)B * T, rows2 = (int64_t)B * Tp;
+    const float* x = r.it.x;
+    const float* P = r.it.params;
+    float* saved = r.it.saved;
+    float* st = saved + S.stat;
+    auto stat = [&](int i) { return st + (int64_t)i * 3 * C; };
+    float* r1 = r.it.scratch + r.WL.bufA;
+
+    // ---- res_block1 (src/models.py:64-76) --------------------------------------------------------------------
+    TRY(conv3(x, P + L.c1.w, P + L.c1.b, saved + S.y1, B, T, D, C, s, "train_conv_gemm"));
+    TRY(bn_stats(c, saved + S.y1, rows, stat(0)));
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 12);
+        hipLaunchKernelGGL(bn_act_mask_kernel, dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(saved + S.y1),
+                           stat(0), P + L.c1.g, P + L.c1.be, reinterpret_cast<const float4*>(r.it.mask_block1),
+                           reinterpret_cast<float4*>(saved + S.a1d), act, rows * C / 4, C);
+    }
+    if (D != C) {
+        GemmParams p = gemm_params_plain(x, P + L.sc.w, saved + S.ysc, (int)rows, C, D, D, D, C);
+        p.bias = P + L.sc.b;
+        TRY(launch_gemm_f32(p, s, "train_conv_gemm"));
+        TRY(bn_stats(c, saved + S.ysc, rows, stat(1)));
+    }
+    TRY(conv3(saved + S.a1d, P + L.c2.w, P + L.c2.b, saved + S.y2, B, T, C, C, s, "train_conv_gemm"));
+    TRY(bn_stats(c, saved + S.y2, rows, stat(2)));
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 16);
+        hipLaunchKernelGGL(bn_add_act_kernel, dim3(ew_blocks(rows * C)), dim3(256), 0, s, saved + S.y2, stat(2), P + L.c2.g, P + L.c2.be,
+                           D != C ? saved + S.ysc : nullptr, stat(1), D != C ? P + L.sc.g : nullptr, D != C ? P + L.sc.be : nullptr,
+                           x, (int64_t)D, saved + S.z1, r1, act, rows * C, C);
+    }
+    // ---- max_pool1d(2) (:177) -----------------------------------------------------------------------------------
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 6);
+        hipLaunchKernelGGL(pool2_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(r1),
+                           reinterpret_cast<float4*>(saved + S.p), B, T, Tp, C / 4);
+    }
+    // ---- res_block2, identity shortcut (:178) ----------------------------------------------------------------------
+    TRY(conv3(saved + S.p, P + L.c3.w, P + L.c3.b, saved + S.y3, B, Tp, C, C, s, "train_conv_gemm"));
+    TRY(bn_stats(c, saved + S.y3, rows2, stat(3)));
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
+        hipLaunchKernelGGL(bn_act_mask_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(saved + S.y3),
+                           stat(3), P + L.c3.g, P + L.c3.be, reinterpret_cast<const float4*>(r.it.mask_block2),
+                           reinterpret_cast<float4*>(saved + S.a3d), act, rows2 * C / 4, C);
+    }
+    TRY(conv3(saved + S.a3d, P + L.c4.w, P + L.c4.b, saved + S.y4, B, Tp, C, C, s, "train_conv_gemm"));
+    TRY(bn_stats(c, saved + S.y4, rows2, stat(4)));
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 16);
+        hipLaunchKernelGGL(bn_add_act_kernel, dim3(ew_blocks(rows2 * C)), dim3(256), 0, s, saved + S.y4, stat(4), P + L.c4.g, P + L.c4.be,
+                           nullptr, nullptr, nullptr, nullptr, saved + S.p, (int64_t)C, saved + S.z2, saved + S.r2, act, rows2 * C, C);
+    }
+    RSAF_CHECK_HIP(hipGetLastError());
+    // ---- LSTM (:184): input projection of the first layer ------------------------------------------------------------
+    r.lin = saved + S.r2;
+    r.in = C;
+    return fwd_inproj(r, L, 0);
+}
+
+static LstmRecItem fwd_rec_item(const Replica& r, const PLayout& L, int l) {
+    float* gates = r.it.saved + r.S.gates[l];
+    return LstmRecItem{gates, r.it.params + L.whh[l], r.it.saved + r.S.hout[l], gates, r.it.saved + r.S.cst[l], r.it.B, r.it.T / 2};
+}
+
+// dropout between the layers and the next layer's input projection
+static int fwd_after_rec(Replica& r, const PLayout& L, int l) {
+    const Dims& d = r.c.d;
+    hipStream_t s = r.c.s;
+    const int H = d.H;
+    const int64_t rows2 = (int64_t)r.it.B * (r.it.T / 2);
+    r.lin = r.it.saved + r.S.hout[l];
+    r.in = 2 * H;
+    if (l == d.L - 1) return RSAF_OK;
+    const float* mk = r.it.mask_lstm_host ? r.it.mask_lstm_host[l] : nullptr;
+    if (mk) {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * 2 * H * 12);
+        hipLaunchKernelGGL(mul_kernel, dim3(ew_blocks(rows2 * 2 * H / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(r.lin),
+                           reinterpret_cast<const float4*>(mk), reinterpret_cast<float4*>(r.it.saved + r.S.hdrop[l]), rows2 * 2 * H / 4);
+        RSAF_CHECK_HIP(hipGetLastError());
+        r.lin = r.it.saved + r.S.hdrop[l];
+    }
+    return fwd_inproj(r, L, l + 1);
+}
+
+// attention pooling + dropout + classifier (:187-191)
+static int fwd_head(Replica& r, const PLayout& L) {
+    const Dims& d = r.c.d;
+    const SLayout& S = r.S;
+    hipStream_t s = r.c.s;
+    const int B = r.it.B, Tp = r.it.T / 2, H = d.H;
+    const int64_t rows2 = (int64_t)B * Tp;
+    const float* P = r.it.params;
+    float* saved = r.it.saved;
+    {
+        ProfScope prof("train_attnpool", s, 0.0, (double)rows2 * 2 * H * 8);
+        if (H == 128)
+            hipLaunchKernelGGL(attnpool_train_kernel<4>, dim3(B), dim3(ATT_WAVES * 64), 0, s, r.lin, P + L.watt, P + L.batt, saved + S.prob, saved + S.ctx, Tp);
+        else
+            hipLaunchKernelGGL(attnpool_train_kernel<2>, dim3(B), dim3(ATT_WAVES * 64), 0, s, r.lin, P + L.watt, P + L.batt, saved + S.prob, saved + S.ctx, Tp);
+        hipLaunchKernelGGL(fc_fwd_kernel, dim3(B), dim3(256), 0, s, saved + S.ctx, r.it.mask_fc, P + L.wfc, P + L.bfc, r.it.logits, 2 * H, d.NC);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    if (r.it.bn_stats_out)
+        RSAF_CHECK_HIP(hipMemcpyAsync(r.it.bn_stats_out, saved + S.stat, sizeof(float) * 5 * 3 * d.C, hipMemcpyDeviceToDevice, s));
+    return RSAF_OK;
+}
+
+// classifier + attention pooling
+static int bwd_head(Replica& r, const PLayout& L) {
+    const Ctx& c = r.c;
+    const Dims& d = c.d;
+    const SLayout& S = r.S;
+    hipStream_t s = c.s;
+    const int B = r.it.B, Tp = r.it.T / 2, H = d.H, F = 2 * H;
+    const int64_t rows2 = (int64_t)B * Tp;
+    const float* P = r.it.params;
+    float* G = r.it.grads;
+    float* saved = r.it.saved;
+    float* small = r.it.scratch + r.WL.small;
+    float* dctx = small + 2 * 1024 + 64;               // after the BN `sums` area
+    float* dwatt_part = dctx + (int64_t)B * F;
+    float* dbatt_part = dwatt_part + (int64_t)B * F;
+    float* dp_scr = dbatt_part + B + 4;
+    const float* seq_top = saved + S.hout[d.L - 1];
+    float* dseq = r.it.scratch + r.WL.bufA;             // [rows2][2H]
+    {
+        ProfScope prof("train_attnpool", s, 0.0, (double)rows2 * F * 12);
+        hipLaunchKernelGGL(fc_bwd_kernel, dim3((F + 255) / 256), dim3(256), 0, s, r.it.dlogits, saved + S.ctx, r.it.mask_fc, P + L.wfc,
+                           G + L.wfc, G + L.bfc, dctx, B, F, d.NC);
+        if (H == 128)
+            hipLaunchKernelGGL(attn_bwd_kernel<4>, dim3(B), dim3(ATT_WAVES * 64), 0, s, seq_top, saved + S.prob, dctx, P + L.watt, dp_scr, dseq,
+                               dwatt_part, dbatt_part, Tp);
+        else
+            hipLaunchKernelGGL(attn_bwd_kernel<2>, dim3(B), dim3(ATT_WAVES * 64), 0, s, seq_top, saved + S.prob, dctx, P + L.watt, dp_scr, dseq,
+                               dwatt_part, dbatt_part, Tp);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    TRY(colsum(c, dwatt_part, F, B, F, G + L.watt));
+    TRY(colsum(c, dbatt_part, 1, B, 1, G + L.batt));
+    r.dcur = dseq;                                      // gradient w.r.t. the output of the top layer  [rows2][2H]
+    r.dnext = r.it.scratch + r.WL.bufB;
+    return RSAF_OK;
+}
+
+static LstmBwdItem bwd_rec_item(const Replica& r, const PLayout& L, int l) {
+    return LstmBwdItem{r.it.saved + r.S.gates[l], r.it.saved + r.S.cst[l], r.dcur, r.it.params + L.whh[l], r.it.B, r.it.T / 2};
+}
+
+// after the BPTT recurrence of layer l, `gates` holds dgates (pre-activation gradients) [rows2][8H]: bias, weight and
+// input gradients
+static int bwd_after_rec(Replica& r, const PLayout& L, int l) {
+    const Ctx& c = r.c;
+    const Dims& d = c.d;
+    const SLayout& S = r.S;
+    hipStream_t s = c.s;
+    const int B = r.it.B, Tp = r.it.T / 2, C = d.C, H = d.H, F = 2 * H;
+    const int64_t rows2 = (int64_t)B * Tp;
+    const float* P = r.it.params;
+    float* G = r.it.grads;
+    float* saved = r.it.saved;
+    const float* const* mask_lstm_host = r.it.mask_lstm_host;
+    float* gates = saved + S.gates[l];
+    const int in = l == 0 ? C : 2 * H;
+    const float* lin = l == 0 ? saved + S.r2
+                              : ((mask_lstm_host && mask_lstm_host[l - 1]) ? saved + S.hdrop[l - 1] : saved + S.hout[l - 1]);
+    TRY(colsum(c, gates, 8 * H, rows2, 8 * H, G + L.bsum[l]));
+    TRY(wgrad(c, gates, 8 * H, 8 * H, lin, in, in, 1, 0, B, Tp, G + L.wih[l]));
+    for (int dir = 0; dir < 2; ++dir)
+        TRY(wgrad(c, gates + dir * 4 * H, 8 * H, 4 * H, saved + S.hout[l] + dir * H, 2 * H, H, 1, dir ? +1 : -1, B, Tp,
+                  G + L.whh[l] + (int64_t)dir * 4 * H * H));
+    // input gradient: dgates . W_ih  (B operand [K = 8H][N = in])
+    {
+        GemmParams p = gemm_params_plain(gates, P + L.wih[l], r.dnext, (int)rows2, in, 8 * H, 8 * H, in, in);
+        p.b_kn = 1;
+        TRY(launch_gemm_f32(p, s, "train_dgrad_gemm"));
+    }
+    if (l > 0 && mask_lstm_host && mask_lstm_host[l - 1]) {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * F * 12);
+        hipLaunchKernelGGL(mul_kernel, dim3(ew_blocks(rows2 * F / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(r.dnext),
+                           reinterpret_cast<const float4*>(mask_lstm_host[l - 1]), reinterpret_cast<float4*>(r.dnext), rows2 * F / 4);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    std::swap(r.dcur, r.dnext);
+    return RSAF_OK;
+}
+
+// the two residual blocks; r.dcur = dr2 [rows2][C], r.dnext (the other of bufA, bufB) is free
+static int bwd_blocks(Replica& r, const PLayout& L) {
+    const Ctx& c = r.c;
+    const Dims& d = c.d;
+    const SLayout& S = r.S;
+    hipStream_t s = c.s;
+    const int B = r.it.B, T = r.it.T, Tp = T / 2, D = d.D, C = d.C, act = d.act;
+    const int64_t rows = (int64_t)B * T, rows2 = (int64_t)B * Tp;
+    const float* x = r.it.x;
+    const float* P = r.it.params;
+    float* G = r.it.grads;
+    float* saved = r.it.saved;
+    float* st = saved + S.stat;
+    auto stat = [&](int i) { return st + (int64_t)i * 3 * C; };
+    float* bufA = r.it.scratch + r.WL.bufA;
+    float* bufB = r.it.scratch + r.WL.bufB;
+    float* bufC = r.it.scratch + r.WL.bufC;
+    float* dr2 = r.dcur;
+    float* dz2 = r.dnext;
+    // ---- res_block2 -------------------------------------------------------------------------------------------------------
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
+        hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_blocks(rows2 * C)), dim3(256), 0, s, dr2, saved + S.z2, dz2, act, rows2 * C);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    float* dy = dr2;                                    // reuse
+    TRY(bn_backward(c, dz2, nullptr, false, saved + S.y4, stat(4), P + L.c4.g, P + L.c4.be, rows2, G + L.c4.g, G + L.c4.be, dy));
+    TRY(colsum(c, dy, C, rows2, C, G + L.c4.b));
+    TRY(wgrad(c, dy, C, C, saved + S.a3d, C, C, 3, 0, B, Tp, G + L.c4.w));
+    float* da = bufC;
+    TRY(conv3_dgrad(c, dy, P + L.c4.w, da, B, Tp, C, C));
+    TRY(bn_backward(c, da, r.it.mask_block2, true, saved + S.y3, stat(3), P + L.c3.g, P + L.c3.be, rows2, G + L.c3.g, G + L.c3.be, dy));
+    TRY(colsum(c, dy, C, rows2, C, G + L.c3.b));
+    TRY(wgrad(c, dy, C, C, saved + S.p, C, C, 3, 0, B, Tp, G + L.c3.w));
+    TRY(conv3_dgrad(c, dy, P + L.c3.w, da, B, Tp, C, C));
+    float* dpool = dy;                                  // dp = dgrad + dz2 (identity shortcut)
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
+        hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(da),
+                           reinterpret_cast<const float4*>(dz2), reinterpret_cast<float4*>(dpool), rows2 * C / 4);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    // ---- max_pool1d backward + activation backward of res_block1 ------------------------------------------------------------
+    float* dz1 = bufC;                                  // [rows][C]  (da is dead)
+    {
+        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 10);
+        hipLaunchKernelGGL(pool_bwd_act_kernel, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dpool, saved + S.z1, dz1, act, B, T, Tp, C);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    // ---- res_block1 -------------------------------------------------------------------------------------------------------
+    float* dy1 = dz2 == bufA ? bufA : bufB;             // any buffer other than dz1 (bufC)
+    float* dy2 = dy1 == bufA ? bufB : bufA;
+    if (D != C) {
+        TRY(bn_backward(c, dz1, nullptr, false, saved + S.ysc, stat(1), P + L.sc.g, P + L.sc.be, rows, G + L.sc.g, G + L.sc.be, dy1));
+        TRY(colsum(c, dy1, C, rows, C, G + L.sc.b));
+        TRY(wgrad(c, dy1, C, C, x, D, D, 1, 0, B, T, G + L.sc.w));
+    }
+    TRY(bn_backward(c, dz1, nullptr, false, saved + S.y2, stat(2), P + L.c2.g, P + L.c2.be, rows, G + L.c2.g, G + L.c2.be, dy2));
+    TRY(colsum(c, dy2, C, rows, C, G + L.c2.b));
+    TRY(wgrad(c, dy2, C, C, saved + S.a1d, C, C, 3, 0, B, T, G + L.c2.w));
+    TRY(conv3_dgrad(c, dy2, P + L.c2.w, dy1, B, T, C, C));           // dy1 now holds d(a1d)
+    TRY(bn_backward(c, dy1, r.it.mask_block1, true, saved + S.y1, stat(0), P + L.c1.g, P + L.c1.be, rows, G + L.c1.g, G + L.c1.be, dy2));
+    TRY(colsum(c, dy2, C, rows, C, G + L.c1.b));
+    TRY(wgrad(c, dy2, C, C, x, D, D, 3, 0, B, T, G + L.c1.w));
+    return RSAF_OK;
+}
+
+// `grouped`: one launch carries the recurrences of all replicas (4-row kernels; needs every batch at or under the threshold),
+// otherwise one launch per replica through the one-recurrence launchers
+static int run_forward(Replica* reps, int K, const Dims& d, bool grouped) {
+    const PLayout L = make_playout(d);
+    hipStream_t s = reps[0].c.s;
+    for (int k = 0; k < K; ++k) grouped = grouped && reps[k].it.B <= lstm_small_max();
+    for (int k = 0; k < K; ++k) TRY(fwd_cnn(reps[k], L));
+    for (int l = 0; l < d.L; ++l) {
+        LstmRecItem items[RSAF_CNNLSTM_GROUP_MAX];
+        for (int k = 0; k < K; ++k) items[k] = fwd_rec_item(reps[k], L, l);
+        if (grouped) TRY(launch_lstm_rec_group(items, K, d.H, s));
+        else
+            for (int k = 0; k < K; ++k)
+                TRY(launch_lstm_rec(items[k].xproj, items[k].whh, items[k].hout, items[k].gates_save, items[k].c_save, items[k].B,
+                                    items[k].T, d.H, s));
+        for (int k = 0; k < K; ++k) TRY(fwd_after_rec(reps[k], L, l));
+    }
+    for (int k = 0; k < K; ++k) TRY(fwd_head(reps[k], L));
+    return RSAF_OK;
+}
+
+static int run_backward(Replica* reps, int K, const Dims& d, bool grouped) {
+    const PLayout L = make_playout(d);
+    hipStream_t s = reps[0].c.s;
+    for (int k = 0; k < K; ++k) grouped = grouped && reps[k].it.B <= lstm_small_max();
+    for (int k = 0; k < K; ++k) TRY(bwd_head(reps[k], L));
+    for (int l = d.L - 1; l >= 0; --l) {                 // LSTM layers, top down
+        LstmBwdItem items[RSAF_CNNLSTM_GROUP_MAX];
+        for (int k = 0; k < K; ++k) items[k] = bwd_rec_item(reps[k], L, l);
+        if (grouped) TRY(launch_lstm_bwd_group(items, K, d.H, s));
+        else
+            for (int k = 0; k < K; ++k)
+                TRY(launch_lstm_bwd(items[k].gates, items[k].cst, items[k].dh, items[k].whh, items[k].B, items[k].T, d.H, s));
+        for (int k = 0; k < K; ++k) TRY(bwd_after_rec(reps[k], L, l));
+    }
+    for (int k = 0; k < K; ++k) TRY(bwd_blocks(reps[k], L));
+    return RSAF_OK;
+}
+
 }  // namespace cnntrain
 }  // namespace rsaf
 
@@ -940,106 +1370,11 @@ int rsaf_cnnlstm_train_forward(const float* x, int B, int T, int input_dim, int 
                                float* bn_stats_out, rsaf_stream_t stream) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
     TRY(check_dims(d));
-    RSAF_CHECK_ARG(B >= 1 && B <= 65535, "batch must be in [1, 65535]");
-    RSAF_CHECK_ARG(T >= 2, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
-    RSAF_CHECK_ARG((int64_t)B * T <= 0x3fffffffLL, "B*T too large");
-    RSAF_CHECK_ARG(x && params && saved && scratch && logits, "NULL pointer");
-    const SLayout S = make_slayout(d, B, T);
-    const WLayout WL = make_wlayout(d, B, T);
-    if (saved_floats < S.total || scratch_floats < WL.total) {
-        set_error("rsaf_cnnlstm_train_forward: saved/scratch buffer too small");
-        return RSAF_ERR_WORKSPACE;
-    }
-    const PLayout L = make_playout(d);
-    hipStream_t s = (hipStream_t)stream;
-    Ctx c{d, s, scratch, WL};
-    const int D = d.D, C = d.C, H = d.H, Tp = T / 2;
-    const int64_t rows = (int64_t)B * T, rows2 = (int64_t)B * Tp;
-    const float* P = params;
-    float* st = saved + S.stat;
-    auto stat = [&](int i) { return st + (int64_t)i * 3 * C; };
-    float* r1 = scratch + WL.bufA;
-
-    // ---- res_block1 (src/models.py:64-76) --------------------------------------------------------------------
-    TRY(conv3(x, P + L.c1.w, P + L.c1.b, saved + S.y1, B, T, D, C, s, "train_conv_gemm"));
-    TRY(bn_stats(c, saved + S.y1, rows, stat(0)));
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 12);
-        hipLaunchKernelGGL(bn_act_mask_kernel, dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(saved + S.y1),
-                           stat(0), P + L.c1.g, P + L.c1.be, reinterpret_cast<const float4*>(mask_block1),
-                           reinterpret_cast<float4*>(saved + S.a1d), act, rows * C / 4, C);
-    }
-    if (D != C) {
-        GemmParams p = gemm_params_plain(x, P + L.sc.w, saved + S.ysc, (int)rows, C, D, D, D, C);
-        p.bias = P + L.sc.b;
-        TRY(launch_gemm_f32(p, s, "train_conv_gemm"));
-        TRY(bn_stats(c, saved + S.ysc, rows, stat(1)));
-    }
-    TRY(conv3(saved + S.a1d, P + L.c2.w, P + L.c2.b, saved + S.y2, B, T, C, C, s, "train_conv_gemm"));
-    TRY(bn_stats(c, saved + S.y2, rows, stat(2)));
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 16);
-        hipLaunchKernelGGL(bn_add_act_kernel, dim3(ew_blocks(rows * C)), dim3(256), 0, s, saved + S.y2, stat(2), P + L.c2.g, P + L.c2.be,
-                           D != C ? saved + S.ysc : nullptr, stat(1), D != C ? P + L.sc.g : nullptr, D != C ? P + L.sc.be : nullptr,
-                           x, (int64_t)D, saved + S.z1, r1, act, rows * C, C);
-    }
-    // ---- max_pool1d(2) (:177) -----------------------------------------------------------------------------------
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 6);
-        hipLaunchKernelGGL(pool2_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(r1),
-                           reinterpret_cast<float4*>(saved + S.p), B, T, Tp, C / 4);
-    }
-    // ---- res_block2, identity shortcut (:178) ----------------------------------------------------------------------
-    TRY(conv3(saved + S.p, P + L.c3.w, P + L.c3.b, saved + S.y3, B, Tp, C, C, s, "train_conv_gemm"));
-    TRY(bn_stats(c, saved + S.y3, rows2, stat(3)));
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
-        hipLaunchKernelGGL(bn_act_mask_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(saved + S.y3),
-                           stat(3), P + L.c3.g, P + L.c3.be, reinterpret_cast<const float4*>(mask_block2),
-                           reinterpret_cast<float4*>(saved + S.a3d), act, rows2 * C / 4, C);
-    }
-    TRY(conv3(saved + S.a3d, P + L.c4.w, P + L.c4.b, saved + S.y4, B, Tp, C, C, s, "train_conv_gemm"));
-    TRY(bn_stats(c, saved + S.y4, rows2, stat(4)));
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 16);
-        hipLaunchKernelGGL(bn_add_act_kernel, dim3(ew_blocks(rows2 * C)), dim3(256), 0, s, saved + S.y4, stat(4), P + L.c4.g, P + L.c4.be,
-                           nullptr, nullptr, nullptr, nullptr, saved + S.p, (int64_t)C, saved + S.z2, saved + S.r2, act, rows2 * C, C);
-    }
-    RSAF_CHECK_HIP(hipGetLastError());
-    // ---- LSTM (:184): dropout between the layers ----------------------------------------------------------------------
-    const float* lin = saved + S.r2;
-    int in = C;
-    for (int l = 0; l < d.L; ++l) {
-        float* gates = saved + S.gates[l];
-        GemmParams p = gemm_params_plain(lin, P + L.wih[l], gates, (int)rows2, 8 * H, in, in, in, 8 * H);
-        p.bias = P + L.bsum[l];
-        TRY(launch_gemm_f32(p, s, "train_lstm_inproj_gemm"));
-        TRY(launch_lstm_rec(gates, P + L.whh[l], saved + S.hout[l], gates, saved + S.cst[l], B, Tp, H, s));
-        lin = saved + S.hout[l];
-        in = 2 * H;
-        if (l < d.L - 1) {
-            const float* mk = mask_lstm_host ? mask_lstm_host[l] : nullptr;
-            if (mk) {
-                ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * 2 * H * 12);
-                hipLaunchKernelGGL(mul_kernel, dim3(ew_blocks(rows2 * 2 * H / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(lin),
-                                   reinterpret_cast<const float4*>(mk), reinterpret_cast<float4*>(saved + S.hdrop[l]), rows2 * 2 * H / 4);
-                RSAF_CHECK_HIP(hipGetLastError());
-                lin = saved + S.hdrop[l];
-            }
-        }
-    }
-    // ---- attention pooling + dropout + classifier (:187-191) --------------------------------------------------------------
-    {
-        ProfScope prof("train_attnpool", s, 0.0, (double)rows2 * 2 * H * 8);
-        if (H == 128)
-            hipLaunchKernelGGL(attnpool_train_kernel<4>, dim3(B), dim3(ATT_WAVES * 64), 0, s, lin, P + L.watt, P + L.batt, saved + S.prob, saved + S.ctx, Tp);
-        else
-            hipLaunchKernelGGL(attnpool_train_kernel<2>, dim3(B), dim3(ATT_WAVES * 64), 0, s, lin, P + L.watt, P + L.batt, saved + S.prob, saved + S.ctx, Tp);
-        hipLaunchKernelGGL(fc_fwd_kernel, dim3(B), dim3(256), 0, s, saved + S.ctx, mask_fc, P + L.wfc, P + L.bfc, logits, 2 * H, d.NC);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    if (bn_stats_out) RSAF_CHECK_HIP(hipMemcpyAsync(bn_stats_out, st, sizeof(float) * 5 * 3 * C, hipMemcpyDeviceToDevice, s));
-    return RSAF_OK;
+    const rsaf_cnnlstm_train_item it{x, B, T, params, mask_block1, mask_block2, mask_lstm_host, mask_fc, saved, saved_floats,
+                                     scratch, scratch_floats, logits, bn_stats_out, nullptr, nullptr};
+    Replica r;
+    TRY(check_item(d, it, false, (hipStream_t)stream, __func__, -1, &r));
+    return run_forward(&r, 1, d, false);
 }
 
 int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
@@ -1049,145 +1384,29 @@ int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int
                                 rsaf_stream_t stream) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
     TRY(check_dims(d));
-    RSAF_CHECK_ARG(B >= 1 && B <= 65535 && T >= 2, "bad batch / sequence length");
-    RSAF_CHECK_ARG((int64_t)B * T <= 0x3fffffffLL, "B*T too large");
-    RSAF_CHECK_ARG(x && params && saved && scratch && dlogits && grads, "NULL pointer");
-    const SLayout S = make_slayout(d, B, T);
-    const WLayout WL = make_wlayout(d, B, T);
-    if (saved_floats < S.total || scratch_floats < WL.total) {
-        set_error("rsaf_cnnlstm_train_backward: saved/scratch buffer too small");
-        return RSAF_ERR_WORKSPACE;
-    }
-    const PLayout L = make_playout(d);
-    hipStream_t s = (hipStream_t)stream;
-    Ctx c{d, s, scratch, WL};
-    const int D = d.D, C = d.C, H = d.H, Tp = T / 2, F = 2 * H;
-    const int64_t rows = (int64_t)B * T, rows2 = (int64_t)B * Tp;
-    const float* P = params;
-    float* G = grads;
-    float* st = saved + S.stat;
-    auto stat = [&](int i) { return st + (int64_t)i * 3 * C; };
-    float* bufA = scratch + WL.bufA;
-    float* bufB = scratch + WL.bufB;
-    float* bufC = scratch + WL.bufC;
-    float* small = scratch + WL.small;
-    float* dctx = small + 2 * 1024 + 64;               // after the BN `sums` area
-    float* dwatt_part = dctx + (int64_t)B * F;
-    float* dbatt_part = dwatt_part + (int64_t)B * F;
-    float* dp_scr = dbatt_part + B + 4;
+    const rsaf_cnnlstm_train_item it{x, B, T, params, mask_block1, mask_block2, mask_lstm_host, mask_fc, saved, saved_floats,
+                                     scratch, scratch_floats, nullptr, nullptr, dlogits, grads};
+    Replica r;
+    TRY(check_item(d, it, true, (hipStream_t)stream, __func__, -1, &r));
+    return run_backward(&r, 1, d, false);
+}
 
-    // ---- classifier + attention pooling ----------------------------------------------------------------------------
-    const float* seq_top = saved + S.hout[d.L - 1];
-    float* dseq = bufA;                                 // [rows2][2H]
-    {
-        ProfScope prof("train_attnpool", s, 0.0, (double)rows2 * F * 12);
-        hipLaunchKernelGGL(fc_bwd_kernel, dim3((F + 255) / 256), dim3(256), 0, s, dlogits, saved + S.ctx, mask_fc, P + L.wfc, G + L.wfc,
-                           G + L.bfc, dctx, B, F, d.NC);
-        if (H == 128)
-            hipLaunchKernelGGL(attn_bwd_kernel<4>, dim3(B), dim3(ATT_WAVES * 64), 0, s, seq_top, saved + S.prob, dctx, P + L.watt, dp_scr, dseq,
-                               dwatt_part, dbatt_part, Tp);
-        else
-            hipLaunchKernelGGL(attn_bwd_kernel<2>, dim3(B), dim3(ATT_WAVES * 64), 0, s, seq_top, saved + S.prob, dctx, P + L.watt, dp_scr, dseq,
-                               dwatt_part, dbatt_part, Tp);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    TRY(colsum(c, dwatt_part, F, B, F, G + L.watt));
-    TRY(colsum(c, dbatt_part, 1, B, 1, G + L.batt));
+int rsaf_cnnlstm_train_group_max(void) { return RSAF_CNNLSTM_GROUP_MAX; }
 
-    // ---- LSTM layers, top down -----------------------------------------------------------------------------------------
-    float* dcur = dseq;                                 // gradient w.r.t. the output of layer l  [rows2][2H]
-    float* dnext = bufB;
-    for (int l = d.L - 1; l >= 0; --l) {
-        float* gates = saved + S.gates[l];
-        const int in = l == 0 ? C : 2 * H;
-        const float* lin = l == 0 ? saved + S.r2
-                                  : ((mask_lstm_host && mask_lstm_host[l - 1]) ? saved + S.hdrop[l - 1] : saved + S.hout[l - 1]);
-        {
-            ProfScope prof("lstm_bwd_recurrent", s, 2.0 * B * Tp * 2.0 * 4 * H * H, 0.0);
-            static const int small_max = [] { const char* e = getenv("RSAF_LSTM_SMALL_MAX"); return e ? atoi(e) : 1024; }();
-            if (B <= small_max) {
-                dim3 grid((B + 3) / 4, 2);
-                if (H == 128) hipLaunchKernelGGL(lstm_bwd4_kernel<128>, grid, dim3(512), 0, s, gates, saved + S.cst[l], dcur, P + L.whh[l], B, Tp);
-                else hipLaunchKernelGGL(lstm_bwd4_kernel<64>, grid, dim3(256), 0, s, gates, saved + S.cst[l], dcur, P + L.whh[l], B, Tp);
-            } else {
-                dim3 grid((B + 15) / 16, 2);
-                const size_t lds = (size_t)2 * 16 * (4 * H + 4) * sizeof(float);
-                if (H == 128)
-                    RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)lstm_bwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                if (H == 128) hipLaunchKernelGGL(lstm_bwd_kernel<128>, grid, dim3(512), lds, s, gates, saved + S.cst[l], dcur, P + L.whh[l], B, Tp);
-                else hipLaunchKernelGGL(lstm_bwd_kernel<64>, grid, dim3(256), lds, s, gates, saved + S.cst[l], dcur, P + L.whh[l], B, Tp);
-            }
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        // gates now holds dgates (pre-activation gradients) [rows2][8H]
-        TRY(colsum(c, gates, 8 * H, rows2, 8 * H, G + L.bsum[l]));
-        TRY(wgrad(c, gates, 8 * H, 8 * H, lin, in, in, 1, 0, B, Tp, G + L.wih[l]));
-        for (int dir = 0; dir < 2; ++dir)
-            TRY(wgrad(c, gates + dir * 4 * H, 8 * H, 4 * H, saved + S.hout[l] + dir * H, 2 * H, H, 1, dir ? +1 : -1, B, Tp,
-                      G + L.whh[l] + (int64_t)dir * 4 * H * H));
-        // input gradient: dgates . W_ih  (B operand [K = 8H][N = in])
-        {
-            GemmParams p = gemm_params_plain(gates, P + L.wih[l], dnext, (int)rows2, in, 8 * H, 8 * H, in, in);
-            p.b_kn = 1;
-            TRY(launch_gemm_f32(p, s, "train_dgrad_gemm"));
-        }
-        if (l > 0 && mask_lstm_host && mask_lstm_host[l - 1]) {
-            ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * F * 12);
-            hipLaunchKernelGGL(mul_kernel, dim3(ew_blocks(rows2 * F / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(dnext),
-                               reinterpret_cast<const float4*>(mask_lstm_host[l - 1]), reinterpret_cast<float4*>(dnext), rows2 * F / 4);
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        std::swap(dcur, dnext);
-    }
-    // dcur = dr2 [rows2][C]; the other of (bufA, bufB) is free
-    float* dr2 = dcur;
-    float* dz2 = dnext;
-    // ---- res_block2 -------------------------------------------------------------------------------------------------------
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
-        hipLaunchKernelGGL(act_bwd_kernel, dim3(ew_blocks(rows2 * C)), dim3(256), 0, s, dr2, saved + S.z2, dz2, act, rows2 * C);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    float* dy = dr2;                                    // reuse
-    TRY(bn_backward(c, dz2, nullptr, false, saved + S.y4, stat(4), P + L.c4.g, P + L.c4.be, rows2, G + L.c4.g, G + L.c4.be, dy));
-    TRY(colsum(c, dy, C, rows2, C, G + L.c4.b));
-    TRY(wgrad(c, dy, C, C, saved + S.a3d, C, C, 3, 0, B, Tp, G + L.c4.w));
-    float* da = bufC;
-    TRY(conv3_dgrad(c, dy, P + L.c4.w, da, B, Tp, C, C));
-    TRY(bn_backward(c, da, mask_block2, true, saved + S.y3, stat(3), P + L.c3.g, P + L.c3.be, rows2, G + L.c3.g, G + L.c3.be, dy));
-    TRY(colsum(c, dy, C, rows2, C, G + L.c3.b));
-    TRY(wgrad(c, dy, C, C, saved + S.p, C, C, 3, 0, B, Tp, G + L.c3.w));
-    TRY(conv3_dgrad(c, dy, P + L.c3.w, da, B, Tp, C, C));
-    float* dpool = dy;                                  // dp = dgrad + dz2 (identity shortcut)
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
-        hipLaunchKernelGGL(add_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(da),
-                           reinterpret_cast<const float4*>(dz2), reinterpret_cast<float4*>(dpool), rows2 * C / 4);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    // ---- max_pool1d backward + activation backward of res_block1 ------------------------------------------------------------
-    float* dz1 = bufC;                                  // [rows][C]  (da is dead)
-    {
-        ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 10);
-        hipLaunchKernelGGL(pool_bwd_act_kernel, dim3(ew_blocks(rows * C)), dim3(256), 0, s, dpool, saved + S.z1, dz1, act, B, T, Tp, C);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    // ---- res_block1 -------------------------------------------------------------------------------------------------------
-    float* dy1 = dz2 == bufA ? bufA : bufB;             // any buffer other than dz1 (bufC)
-    float* dy2 = dy1 == bufA ? bufB : bufA;
-    if (D != C) {
-        TRY(bn_backward(c, dz1, nullptr, false, saved + S.ysc, stat(1), P + L.sc.g, P + L.sc.be, rows, G + L.sc.g, G + L.sc.be, dy1));
-        TRY(colsum(c, dy1, C, rows, C, G + L.sc.b));
-        TRY(wgrad(c, dy1, C, C, x, D, D, 1, 0, B, T, G + L.sc.w));
-    }
-    TRY(bn_backward(c, dz1, nullptr, false, saved + S.y2, stat(2), P + L.c2.g, P + L.c2.be, rows, G + L.c2.g, G + L.c2.be, dy2));
-    TRY(colsum(c, dy2, C, rows, C, G + L.c2.b));
-    TRY(wgrad(c, dy2, C, C, saved + S.a1d, C, C, 3, 0, B, T, G + L.c2.w));
-    TRY(conv3_dgrad(c, dy2, P + L.c2.w, dy1, B, T, C, C));           // dy1 now holds d(a1d)
-    TRY(bn_backward(c, dy1, mask_block1, true, saved + S.y1, stat(0), P + L.c1.g, P + L.c1.be, rows, G + L.c1.g, G + L.c1.be, dy2));
-    TRY(colsum(c, dy2, C, rows, C, G + L.c1.b));
-    TRY(wgrad(c, dy2, C, C, x, D, D, 3, 0, B, T, G + L.c1.w));
-    return RSAF_OK;
+int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels, int hidden,
+                                     int num_classes, int lstm_layers, int act, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group(d, items_host, K, false, (hipStream_t)stream, __func__, reps));
+    return run_forward(reps, K, d, true);
+}
+
+int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels, int hidden,
+                                      int num_classes, int lstm_layers, int act, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group(d, items_host, K, true, (hipStream_t)stream, __func__, reps));
+    return run_backward(reps, K, d, true);
 }
 
 }  // extern "C"
