@@ -126,10 +126,14 @@ struct Workspace {
     int64_t cb_max;                                      // CONV_BIAS: max |bias| of conv1..5 (appended after the tables)
     int64_t gate;                                        // REL_POS_BIAS: the bias gates [rows][NH] of the current layer (appended)
     int64_t t_Tw, t_row0, t_ztab, t_rowwin;              // window tables (int32 / int64 views of the float workspace)
-    int slabs, Tp, G;
 };
 constexpr int STAT_SLAB = 512;
 constexpr int CONV_GROUP = 512;      // windows per pass of the feature encoder (its ping-pong buffers are the big ones)
+
+// What sizes the workspace and picks the forward's path with it (make_ws and Forward read the same three):
+static inline int conv_group(int n) { return n < CONV_GROUP ? n : CONV_GROUP; }                  // window slots of a feature-encoder pass
+static inline bool fused_attention(const Cfg& c, int Tt) { return c.Hd / c.NH == 64 && Tt <= 256; }   // else three launches and the score buffer
+static inline bool posconv_on_f16x3(const Cfg& c) { return (c.Hd / c.PG) % 16 == 0; }             // else the exact-fp32 GEMM
 
 static inline int64_t planes_floats(int64_t n) { return pad4(n); }
 
@@ -148,9 +152,11 @@ struct Rag {
     std::vector<int> T6;
 };
 
-static int make_rag(const int* len_host, int n, Rag& R) {
+// len_host NULL: n windows of `len` samples each
+static int make_rag(const int* len_host, int n, int len, Rag& R) {
     R.n = n;
-    R.len.assign(len_host, len_host + n);
+    if (len_host) R.len.assign(len_host, len_host + n);
+    else R.len.assign((size_t)n, len);
     R.row0.assign(n + 1, 0);
     R.T6.resize(n);
     for (int w = 0; w < n; ++w) {
@@ -176,12 +182,9 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     auto take = [&](int64_t k) { int64_t s = o; o += pad4(k); return s; };
     const int Tt = T[6];
     const int64_t rows = R.rows;
-    const int G = n < CONV_GROUP ? n : CONV_GROUP;
-    w.G = G;
-    w.slabs = (T[0] + STAT_SLAB - 1) / STAT_SLAB;
-    w.Tp = (int)pad4(Tt);
+    const int G = conv_group(n), slabs = (T[0] + STAT_SLAB - 1) / STAT_SLAB;
     w.xn = take((int64_t)G * R.maxlen);
-    w.part = take((int64_t)G * w.slabs * 3 * c.C);
+    w.part = take((int64_t)G * slabs * 3 * c.C);
     w.ab = take((int64_t)G * 2 * c.C);
     w.P = take(planes_floats((int64_t)G * T[0] * c.C));
     w.Q = take(planes_floats((int64_t)G * T[1] * c.C));
@@ -194,7 +197,7 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     w.attp = take(planes_floats(rows * c.Hd));
     w.xg = take((int64_t)n * (Tt + c.PK - 1) * c.Hd);                     // fp32 or two fp16 planes (same size)
     w.qkv = take(rows * 3 * c.Hd);
-    w.S = take((c.Hd / c.NH == 64 && Tt <= 256) ? 4 : (int64_t)n * c.NH * Tt * w.Tp);   // scores: only the three-launch attention
+    w.S = take(fused_attention(c, Tt) ? 4 : (int64_t)n * c.NH * Tt * pad4(Tt));   // scores: only the three-launch attention
     w.ffnp = take(planes_floats(rows * c.I));
     // weight planes and row scales (built once per forward call)
     for (int i = 0; i < 6; ++i) {
@@ -1303,44 +1306,80 @@ __global__ __launch_bounds__(512, 1) void posconv_f16x3_kernel(const unsigned sh
     }
 }
 
+// a step of a sequence that ends at the first error
+#define RSAF_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
 static int posconv_rows_alloc(int split, int PK) { return (PC_ROWS / split + PK - 1 + 31) & ~31; }
 static size_t posconv_lds_bytes(int cg, int PK, int split) {
     return ((size_t)2 * (cg / 16) * posconv_rows_alloc(split, PK) * 16 + (size_t)4 * split * 4 * cg * 16) * sizeof(unsigned short);
 }
+// posconv_f16x3_kernel keeps a window's regrouped image in LDS: the row split of a window, and whether the image fits
+static int posconv_split(int Tt) { return Tt <= PC_ROWS / 2 ? 2 : 1; }
+static bool posconv_resident(const Cfg& c, int Tt) {
+    const int cg = c.Hd / c.PG, split = posconv_split(Tt);
+    return cg <= 64 && Tt <= PC_ROWS && (c.PK * (cg / 16)) % (4 * split) == 0 && posconv_lds_bytes(cg, c.PK, split) <= 160 * 1024;
+}
 
-static int ln(const float* x, const float* r, const float* g, const float* b, float* out, int64_t rows, int D,
-              float eps, hipStream_t s, const int64_t* out_row_start = nullptr, const int* rowwin = nullptr,
-              const int64_t* row0 = nullptr, unsigned short* planes = nullptr, bool panel = false, float* scale_out = nullptr,
-              const unsigned* bound_w = nullptr, const unsigned* bound_b = nullptr, float* bound_scale_out = nullptr,
-              unsigned* win_norm = nullptr, int var = 0, const float* pg = nullptr, const float* pb = nullptr,
-              float* aux = nullptr, float* tap = nullptr, int tap_mode = 0, const int64_t* tap_row_start = nullptr) {
+// Operands of one layernorm_kernel launch (every pointer optional unless its group says otherwise)
+struct LnArgs {
+    // input and residual: the row is x (+ r)
+    const float *x = nullptr, *r = nullptr;
+    // affine
+    const float *g = nullptr, *b = nullptr;
+    // fp32 output; with out_row_start, frame t of window w lands at row out_row_start[w] + t.  rowwin / row0: the row -> window
+    // map and the windows' first rows, which out_row_start, win_norm and tap_row_start read
+    float* out = nullptr;
+    const int64_t* out_row_start = nullptr;
+    const int* rowwin = nullptr;
+    const int64_t* row0 = nullptr;
+    // planes output (A of the next GEMM; panel: its k16-panel layout) and the exact row scales that go with it
+    unsigned short* planes = nullptr;
+    bool panel = false;
+    float* scale_out = nullptr;
+    // bound inputs {max row norm, max |bias|} of the next GEMM's weights, and the scale of that GEMM's plane output per row
+    const unsigned *bound_w = nullptr, *bound_b = nullptr;
+    float* bound_scale_out = nullptr;
+    // largest row norm per window (bit patterns, atomicMax): behind the scale of the fused attention's q / k / v
+    unsigned* win_norm = nullptr;
+    // variant (layernorm_kernel's VAR) and its operands: 1 writes x + r to aux, 2 applies the conv LayerNorm pg / pb first
+    int var = 0;
+    const float *pg = nullptr, *pb = nullptr;
+    float* aux = nullptr;
+    // hidden-state tap: mode 1 the output, mode 2 the un-normalised x (+ r); rows mapped like out_row_start
+    float* tap = nullptr;
+    int tap_mode = 0;
+    const int64_t* tap_row_start = nullptr;
+};
+
+static int ln(const LnArgs& a, int64_t rows, int D, float eps, hipStream_t s) {
     const int64_t blocks = (rows + 3) / 4;
     RSAF_CHECK_ARG(blocks <= 0x7fffffffLL, "too many rows");
-    RSAF_CHECK_ARG(!planes || scale_out, "planes need their scale array");
-    RSAF_CHECK_ARG(!win_norm || rowwin, "the per-window norm needs the row -> window map");
-    RSAF_CHECK_ARG((var != 1 || aux) && (var != 2 || (pg && pb)), "layernorm variant without its operands");
-    RSAF_CHECK_ARG(!tap || ((tap_mode == 1 && var == 0) || (tap_mode == 2 && var < 2)), "layernorm tap mode not built");
-    RSAF_CHECK_ARG(!tap_row_start || (rowwin && row0), "the tap row map needs the row -> window map");
-    ProfScope prof(tap ? "w2v2_layernorm_tap" : "w2v2_layernorm", s, 0.0,
-                   (double)rows * D * (4 * (r ? 2 : 1) + (out ? 4 : 0) + (planes ? 4 : 0) + (aux ? 4 : 0) + (tap ? 4 : 0)));
+    RSAF_CHECK_ARG(!a.planes || a.scale_out, "planes need their scale array");
+    RSAF_CHECK_ARG(!a.win_norm || a.rowwin, "the per-window norm needs the row -> window map");
+    RSAF_CHECK_ARG((a.var != 1 || a.aux) && (a.var != 2 || (a.pg && a.pb)), "layernorm variant without its operands");
+    RSAF_CHECK_ARG(!a.tap || ((a.tap_mode == 1 && a.var == 0) || (a.tap_mode == 2 && a.var < 2)), "layernorm tap mode not built");
+    RSAF_CHECK_ARG(!a.tap_row_start || (a.rowwin && a.row0), "the tap row map needs the row -> window map");
+    ProfScope prof(a.tap ? "w2v2_layernorm_tap" : "w2v2_layernorm", s, 0.0,
+                   (double)rows * D * (4 * (a.r ? 2 : 1) + (a.out ? 4 : 0) + (a.planes ? 4 : 0) + (a.aux ? 4 : 0) + (a.tap ? 4 : 0)));
 #define RSAF_LN(...)                                                                                                       \
-    hipLaunchKernelGGL((layernorm_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, s, x, r, g, b, out, rows, D, eps, \
-                       out_row_start, rowwin, row0, planes, rows * D, panel ? 1 : 0, scale_out, bound_w, bound_b, bound_scale_out, \
-                       win_norm, pg, pb, aux, tap, tap_row_start)
-    if (tap) {                                               // hidden-state taps: post-LN outputs, pre-LN residual streams
-        if (tap_mode == 1) RSAF_LN(0, 1);
-        else if (var == 1) RSAF_LN(1, 2);
+    hipLaunchKernelGGL((layernorm_kernel<__VA_ARGS__>), dim3((unsigned)blocks), dim3(256), 0, s, a.x, a.r, a.g, a.b, a.out, rows, D, eps, \
+                       a.out_row_start, a.rowwin, a.row0, a.planes, rows * D, a.panel ? 1 : 0, a.scale_out, a.bound_w, a.bound_b,   \
+                       a.bound_scale_out, a.win_norm, a.pg, a.pb, a.aux, a.tap, a.tap_row_start)
+    if (a.tap) {                                             // hidden-state taps: post-LN outputs, pre-LN residual streams
+        if (a.tap_mode == 1) RSAF_LN(0, 1);
+        else if (a.var == 1) RSAF_LN(1, 2);
         else RSAF_LN(0, 2);
-    } else if (var == 1) RSAF_LN(1);
-    else if (var == 2) RSAF_LN(2);
-    else if (var == 3) RSAF_LN(3);
+    } else if (a.var == 1) RSAF_LN(1);
+    else if (a.var == 2) RSAF_LN(2);
+    else if (a.var == 3) RSAF_LN(3);
     else RSAF_LN(0);
 #undef RSAF_LN
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
 
-template <bool APPLY, bool BIAS>
+// cb: the conv bias (RSAF_W2V2_CONV_BIAS) or NULL
+template <bool APPLY>
 static int conv0_launch(const Cfg& c, const float* xn, const float* w0, const float* cb, float* part, const float* ab, const float* scale,
                         unsigned short* outp, int64_t plane, int n, int len, const int* T0w, int T0, int slab, int slabs, hipStream_t s) {
     const int threads = c.C <= 256 ? c.C : 256;
@@ -1351,17 +1390,20 @@ static int conv0_launch(const Cfg& c, const float* xn, const float* w0, const fl
     // 10-tap convolution: Cin = 1, 0.16 GFLOP per window)
     ProfScope prof(APPLY ? "w2v2_conv0_apply" : "w2v2_conv0_stats", s, 0.0,
                    APPLY ? (double)n * ((double)c.C * T0 * 4.0 + 4.0 * (5.0 * T0 + 5.0)) : (double)n * 4.0 * (5.0 * T0 + 5.0));
-#define RSAF_C0(CPT)                                                                                       \
+#define RSAF_C0K(CPT, BIAS)                                                                                \
     hipLaunchKernelGGL((conv0_kernel<CPT, APPLY, BIAS>), grid, dim3(threads), 0, s, xn, w0, cb, part, ab, scale, outp, plane, len, T0w, T0, \
                        c.C, slab, slabs)
-    switch (cpt) {
-        case 1: RSAF_C0(1); break;
-        case 2: RSAF_C0(2); break;
-        case 3: RSAF_C0(3); break;
-        case 4: RSAF_C0(4); break;
-        default: set_error("conv0: unsupported conv_dim"); return RSAF_ERR_ARG;
+#define RSAF_C0(BIAS)                                                                                      \
+    switch (cpt) {                                                                                         \
+        case 1: RSAF_C0K(1, BIAS); break;                                                                  \
+        case 2: RSAF_C0K(2, BIAS); break;                                                                  \
+        case 3: RSAF_C0K(3, BIAS); break;                                                                  \
+        case 4: RSAF_C0K(4, BIAS); break;                                                                  \
+        default: set_error("conv0: unsupported conv_dim"); return RSAF_ERR_ARG;                            \
     }
+    if (cb) { RSAF_C0(true) } else { RSAF_C0(false) }
 #undef RSAF_C0
+#undef RSAF_C0K
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
@@ -1392,6 +1434,564 @@ static int conv0_ln_launch(const Cfg& c, const float* xn, const float* w0, const
     return RSAF_OK;
 }
 
+// Operands of one f16x3 GEMM, C = act(A B^T + bias (+ R)): A and B as fp16 plane pairs with their power-of-two scales
+struct GemmA {
+    const uint16_t* planes = nullptr;
+    int64_t plane = 0, lda = 0, sA = 0;                      // plane stride, row stride, batch stride
+    const float* scale = nullptr;
+    int scale_zs = 0, scale_ms = 0;                          // stride of the scale per batch / per row
+    bool panel = false;                                      // k16-panel layout (lda, sA unused)
+};
+struct GemmB {                                               // weights: k16 panels of N rows, one scale per row
+    const uint16_t* planes = nullptr;
+    const float* scale = nullptr;
+};
+// the epilogue: what joins the product, where it goes (fp32 rows Cf and / or the planes Cp under c_scale), and the largest
+// |output| it reports (amax: per batch at stride amax_zs, or per row slot; columns from amax_col_min on)
+struct Out {
+    const float* bias = nullptr;
+    const float* R = nullptr;                                // residual, laid out like Cf
+    int act = ACT_NONE;
+    float* Cf = nullptr;
+    int64_t sC = 0;
+    uint16_t* Cp = nullptr;
+    int64_t c_plane = 0, sCp = 0;
+    const float* c_scale = nullptr;
+    int cs_zs = 0, cs_ms = 0;
+    bool cp_panel = false;
+    unsigned* amax = nullptr;
+    int amax_zs = 0;
+    const int* amax_row_slot = nullptr;
+    int amax_col_min = 0;
+};
+
+// One forward call: its geometry, buffers and device tables, and one member function per phase (forward_impl runs them in order)
+struct Forward {
+    const Cfg& c;
+    const Rag& R;
+    const Layout L;
+    const Workspace& W;
+    const float* Wt;
+    float* ws;
+    hipStream_t s;
+    // the call's input and outputs.  taps (NULL: no hidden states): taps[k], k = 0..L, receives hidden_states[k] in the row
+    // layout of `out`, or is NULL
+    const float* wav = nullptr;
+    const int64_t* chunk_start = nullptr;
+    float* out = nullptr;
+    const int64_t* out_row_start = nullptr;
+    float* const* taps = nullptr;
+    // geometry.  T: frames of the LONGEST window per layer (strides, grids); G: window slots of a feature-encoder pass
+    const int n, C, Hd, Tt, G, hd;
+    const int* T;
+    const int64_t rows;
+    const float scale;
+    // fused: attention on the fp16 matrix pipe, q / k / v as plane pairs.  relpos (REL_POS_BIAS): the gates come from the fp32
+    // rows the q/k/v projection reads: x (post-LN), or LN1(h), which the stable-layer-norm LayerNorms then also write in fp32
+    // into the att buffer (free until the attention writes it)
+    const bool fused, relpos, pre_ln, layer_norm, conv_bias;
+    // window tables on the device (every window has its own length: the reference's tail windows)
+    int* Tw;                                                 // [7][n]
+    int64_t* row0;
+    int64_t* ztab;                                           // [7][n][2]
+    int* rowwin;
+    const int* wlen = nullptr;
+    // feature encoder: scale of layer i's plane output per window of the group, largest |output| of layer i (layer 0: its
+    // bound), the conv biases [7][C], the conv LayerNorms [7][2][C] (layer mode), max |bias| of conv1..5 at 1..5
+    float* cscale;                                           // [7][G]
+    unsigned* camax;                                         // [7][G]
+    const float* cbias;
+    const float* cln;
+    float* cb_max;                                           // [8]
+    float* x;                                                // the encoder's fp32 rows (post-LN: LN outputs; PRE_LN: the residual stream)
+
+    Forward(const Cfg& c_, const Rag& R_, const Workspace& W_, const float* weights, void* workspace, hipStream_t s_)
+        : c(c_), R(R_), L(make_layout(c_)), W(W_), Wt(weights), ws(static_cast<float*>(workspace)), s(s_), n(R_.n), C(c_.C), Hd(c_.Hd),
+          Tt(R_.Tmax[6]), G(conv_group(R_.n)), hd(c_.Hd / c_.NH), T(R_.Tmax), rows(R_.rows), scale(1.0f / sqrtf((float)hd)),
+          fused(fused_attention(c_, Tt)), relpos(c_.flags & F_REL_POS_BIAS), pre_ln(c_.flags & F_PRE_LN),
+          layer_norm(c_.flags & F_LAYER_FEAT_NORM), conv_bias(c_.flags & F_CONV_BIAS),
+          Tw(reinterpret_cast<int*>(ws + W.t_Tw)), row0(reinterpret_cast<int64_t*>(ws + W.t_row0)),
+          ztab(reinterpret_cast<int64_t*>(ws + W.t_ztab)), rowwin(reinterpret_cast<int*>(ws + W.t_rowwin)),
+          cscale(ws + W.conv_scale), camax(bits_at(W.conv_amax)), cbias(conv_bias ? Wt + L.cb : nullptr), cln(Wt + L.cln),
+          cb_max(conv_bias ? ws + W.cb_max : nullptr), x(ws + W.x) {}
+
+    uint16_t* planes_at(int64_t off) const { return reinterpret_cast<uint16_t*>(ws + off); }
+    unsigned* bits_at(int64_t off) const { return reinterpret_cast<unsigned*>(ws + off); }
+    unsigned* wstat(int idx) const { return bits_at(W.wstat) + 2 * idx; }   // {max row norm, max |element|} of matrix idx
+    float* tap(int k) const { return taps ? taps[k] : nullptr; }
+    float* gate_rows() const { return relpos ? ws + W.att : nullptr; }     // PRE_LN: where LN1(h) goes in fp32 for the gates
+    float* gate() const { return relpos ? ws + W.gate : nullptr; }
+    const float* reltab() const { return relpos ? Wt + L.reltab : nullptr; }
+
+    int gemm3(const GemmA& A, const GemmB& B, const Out& o, int M, int N, int K, int nz = 1, const int64_t* zt = nullptr) {
+        GemmH3Params p{};
+        p.a_panel = A.panel; p.b_panel = 1; p.cp_panel = o.cp_panel;
+        p.A = A.planes; p.a_plane = A.plane; p.lda = A.lda; p.sA = A.sA; p.a_scale = A.scale; p.a_scale_zs = A.scale_zs; p.a_scale_ms = A.scale_ms;
+        p.B = B.planes; p.b_plane = (int64_t)N * K; p.ldb = 16; p.b_scale = B.scale;
+        p.C = o.Cf; p.ldc = N; p.sC = o.sC;
+        p.Cp = o.Cp; p.c_plane = o.c_plane; p.ldcp = N; p.sCp = o.sCp; p.c_scale = o.c_scale; p.c_scale_zs = o.cs_zs; p.c_scale_ms = o.cs_ms;
+        p.amax_out = o.amax; p.amax_zs = o.amax_zs; p.amax_row_slot = o.amax_row_slot; p.amax_col_min = o.amax_col_min;
+        p.bias = o.bias; p.R = o.R; p.ldr = N; p.sR = o.sC;
+        p.M = M; p.N = N; p.K = K; p.nz = nz; p.ztab = zt; p.act = o.act; p.alpha = 1.0f; p.group_m = 0;
+        return launch_gemm_f16x3(p, s, "w2v2_gemm");
+    }
+    // A = all `rows` encoder rows of K columns as panels, each row with its own scale
+    GemmA rows_a(int64_t planes_off, int K, const float* row_scale) const {
+        GemmA A;
+        A.planes = planes_at(planes_off); A.plane = rows * K; A.lda = K; A.scale = row_scale; A.scale_ms = 1; A.panel = true;
+        return A;
+    }
+    // A of conv i: the channels-last output of layer i - 1, one batch and one scale per window; tap k of a frame = a row shift
+    GemmA conv_a(const uint16_t* planes, int i) const {
+        GemmA A;
+        A.planes = planes; A.plane = (int64_t)G * T[i - 1] * C; A.lda = (int64_t)STRD[i] * C; A.sA = (int64_t)T[i - 1] * C;
+        A.scale = cscale + (int64_t)(i - 1) * G; A.scale_zs = 1;
+        return A;
+    }
+    GemmB weights_b(int64_t planes_off, int64_t scale_off) const { return GemmB{planes_at(planes_off), ws + scale_off}; }
+
+    // window tables; len_dev NULL (equal windows): the length table is filled here
+    int window_tables(const int* len_dev) {
+        wlen = len_dev;
+        if (!wlen) {
+            int* wl = reinterpret_cast<int*>(ws + W.wlen);
+            hipLaunchKernelGGL(fill_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, wl, n, R.maxlen);
+            wlen = wl;
+        }
+        hipLaunchKernelGGL(w2v2_tables_kernel, dim3(1), dim3(256), 0, s, wlen, n, C, Hd, Tw, row0, ztab);
+        hipLaunchKernelGGL(w2v2_rowwin_kernel, dim3(n), dim3(256), 0, s, row0, rowwin);
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+
+    int split_wp(int64_t src_off, int64_t nrows, int K, int64_t dst_off, int64_t scale_off, int stat_idx) {
+        RSAF_TRY(launch_f16x2_row_scales(Wt + src_off, nrows, K, K, ws + scale_off, nullptr, wstat(stat_idx), s));
+        return launch_split_f16x2(Wt + src_off, nrows, K, K, ws + scale_off, 1, planes_at(dst_off), nrows * K, 1, s);
+    }
+    // 0. weights of the dense layers as fp16 plane pairs in the k16-panel layout, each row with its own power-of-two scale
+    //    (once per call: 0.4 GB at base geometry, < 1 ms), and per matrix the largest row norm: the Cauchy-Schwarz factor of
+    //    the bound behind the scale of a GEMM's PLANE output (conv1..5, ffn1)
+    int weight_planes() {
+        RSAF_CHECK_HIP(hipMemsetAsync(ws + W.wstat, 0, sizeof(float) * 2 * (WSTAT_LAYER0 + WSTAT_PER_LAYER * c.L), s));
+        for (int i = 0; i < 6; ++i)
+            RSAF_TRY(split_wp(L.conv[i], C, KERN[i + 1] * C, W.wp_conv[i], W.ws_conv[i], wstat_conv(i)));
+        RSAF_TRY(split_wp(L.fpw, Hd, C, W.wp_fp, W.ws_fp, WSTAT_FP));
+        if (posconv_on_f16x3(c)) {                           // [G cg][PK cg] as panels of Hd rows
+            RSAF_TRY(split_wp(L.posw, Hd, c.PK * (Hd / c.PG), W.wp_pos, W.ws_pos, WSTAT_POS));
+        }
+        for (int l = 0; l < c.L; ++l) {
+            const LayerOff& lo = L.layers[l];
+            const int b0 = WSTAT_LAYER0 + WSTAT_PER_LAYER * l;
+            RSAF_TRY(split_wp(lo.wqkv, 3 * Hd, Hd, W.wp_qkv[l], W.ws_qkv[l], b0));
+            RSAF_TRY(split_wp(lo.wo, Hd, Hd, W.wp_o[l], W.ws_o[l], b0 + 1));
+            RSAF_TRY(split_wp(lo.w1, c.I, Hd, W.wp_1[l], W.ws_1[l], b0 + 2));
+            RSAF_TRY(split_wp(lo.w2, Hd, c.I, W.wp_2[l], W.ws_2[l], b0 + 3));
+            // max |b1| (word 1 of the statistics of the bias seen as one row); the scale it writes goes to a scratch slot
+            RSAF_TRY(launch_f16x2_row_scales(Wt + lo.b1, 1, c.I, c.I, ws + W.pos_scale, nullptr, wstat(b0 + 4), s));
+            RSAF_TRY(launch_f16x2_row_scales(Wt + lo.bqkv, 1, 3 * Hd, 3 * Hd, ws + W.pos_scale, nullptr, wstat(b0 + 5), s));
+        }
+        return RSAF_OK;
+    }
+
+    // 1-3. feature encoder, G windows at a time (its activations are the large ones: 15 999 x 512 per window)
+    int feature_encoder() {
+        // window groups of (almost) equal size: ceil(n / G) groups instead of full ones and a small remainder
+        const int n_groups = (n + G - 1) / G, gstep = (n + n_groups - 1) / n_groups;
+        if (layer_norm) {                                    // layer mode: the planes' scales depend on the weights only
+            hipLaunchKernelGGL(lnconv_scale_kernel, dim3(1), dim3(384), 0, s, cln, C, G, cscale);
+            RSAF_CHECK_HIP(hipGetLastError());
+        } else if (conv_bias) {
+            hipLaunchKernelGGL(conv_bias_max_kernel, dim3(1), dim3(64), 0, s, cbias, C, cb_max);
+            RSAF_CHECK_HIP(hipGetLastError());
+        }
+        for (int g0 = 0; g0 < n; g0 += gstep) {
+            const int g = std::min(gstep, n - g0);
+            // the group's longest window is its first (lengths are non-increasing): its frame counts size the group's launches
+            int Tg[7];
+            chunk_lengths(R.len[g0], Tg);
+            if (!layer_norm) RSAF_CHECK_HIP(hipMemsetAsync(camax, 0, sizeof(unsigned) * 7 * G, s));
+            // 1. per-chunk normalisation (HF feature extractor; NO_INPUT_NORM: do_normalize=False, a copy)
+            {
+                ProfScope prof("w2v2_normalize", s, 0.0, (double)g * R.len[g0] * 4 * 3);
+                if (c.flags & F_NO_INPUT_NORM)
+                    hipLaunchKernelGGL(normalize_kernel<false>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
+                else
+                    hipLaunchKernelGGL(normalize_kernel<true>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
+                RSAF_CHECK_HIP(hipGetLastError());
+            }
+            RSAF_TRY(layer_norm ? convs_layer_norm(g0, g, Tg) : convs_group_norm(g0, g, Tg));
+        }
+        return RSAF_OK;
+    }
+    // conv i of the windows g0 .. g0 + g - 1: every window keeps the longest window's row allotment (batch stride T[i] rows)
+    // and has its own row count (ztab); the last layer writes its rows packed (window w at row row0[w])
+    int conv_gemm(int i, const uint16_t* a_planes, Out& o, int g0, int g, const int* Tg) {
+        if (i == 6) { o.Cf = ws + W.c6; o.sC = 0; }
+        o.bias = conv_bias ? cbias + (int64_t)i * C : nullptr;
+        return gemm3(conv_a(a_planes, i), weights_b(W.wp_conv[i - 1], W.ws_conv[i - 1]), o, Tg[i], C, KERN[i] * C, g,
+                     ztab + ((int64_t)(i - 1) * n + g0) * 2);
+    }
+    // 2-3 (layer mode). conv0 + LayerNorm + GELU in one pass; conv1..6 as GEMMs writing fp32 rows (+ bias) into the Q buffer,
+    // then LayerNorm -> GELU -> planes back into P (the GEMM has consumed them); conv6 writes its packed rows, and its
+    // LayerNorm + GELU join the feature projection's LayerNorm (step 4)
+    int convs_layer_norm(int g0, int g, const int* Tg) {
+        RSAF_TRY(conv0_ln_launch(c, ws + W.xn, Wt + L.conv0, cbias, cln, cln + C, cscale, planes_at(W.P), (int64_t)G * T[0] * C,
+                                  g, R.maxlen, Tw + g0, T[0], Tg[0], s));
+        for (int i = 1; i < 7; ++i) {
+            Out o;
+            o.Cf = ws + W.Q; o.sC = (int64_t)T[i] * C;
+            RSAF_TRY(conv_gemm(i, planes_at(W.P), o, g0, g, Tg));
+            if (i < 6) {
+                const int64_t lrows = (int64_t)g * T[i];
+                ProfScope prof("w2v2_conv_ln", s, 0.0, (double)lrows * C * 8.0);
+                hipLaunchKernelGGL(conv_ln_gelu_kernel, dim3((unsigned)((lrows + 3) / 4)), dim3(256), 0, s, ws + W.Q,
+                                   cln + (int64_t)2 * i * C, cln + (int64_t)(2 * i + 1) * C, cscale + (int64_t)i * G,
+                                   planes_at(W.P), (int64_t)G * T[i] * C, lrows, T[i], Tw + (int64_t)i * n + g0, C);
+                RSAF_CHECK_HIP(hipGetLastError());
+            }
+        }
+        return RSAF_OK;
+    }
+    // 2-3 (group mode)
+    int convs_group_norm(int g0, int g, const int* Tg) {
+        // 2. conv0 + GroupNorm + GELU (stats pass, finalize, apply pass); the apply pass writes fp16 plane pairs
+        const int slabs_g = (Tg[0] + STAT_SLAB - 1) / STAT_SLAB;
+        RSAF_TRY(conv0_launch<false>(c, ws + W.xn, Wt + L.conv0, cbias, ws + W.part, nullptr, nullptr, nullptr, 0, g, R.maxlen, Tw + g0,
+                                      T[0], STAT_SLAB, slabs_g, s));
+        const int64_t tot = (int64_t)g * C;
+        hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ws + W.part,
+                           Wt + L.gng, Wt + L.gnb, ws + W.ab, camax, g, C, slabs_g, Tw + g0);
+        RSAF_CHECK_HIP(hipGetLastError());
+        RSAF_TRY(launch_scale_from_bound(camax, g, nullptr, 1.0f, nullptr, cscale, s));
+        const int slab = 128;
+        RSAF_TRY(conv0_launch<true>(c, ws + W.xn, Wt + L.conv0, cbias, nullptr, ws + W.ab, cscale, planes_at(W.P), (int64_t)G * T[0] * C, g,
+                                     R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s));
+        // 3. conv1..6 as GEMMs over the channels-last sequence (lda = stride * C, K = taps * C) with fused GELU;
+        //    the output goes out as planes (the next layer's A), the last one as fp32 rows for the LayerNorm.
+        //    Scale of layer i's output, per window: |GELU(x)| <= |x| <= |a|_2 |w|_2 <= sqrt(K) max|a| max_n |w_n|_2 with
+        //    max|a| = the largest |output| of layer i - 1, which that layer's epilogue reported (layer 0: the GroupNorm bound).
+        uint16_t* cur = planes_at(W.P);
+        uint16_t* nxt = planes_at(W.Q);
+        for (int i = 1; i < 7; ++i) {
+            Out o;
+            o.act = ACT_GELU;
+            if (i < 6) {
+                // (CONV_BIAS: + max |bias| of layer i)
+                RSAF_TRY(launch_scale_from_bound(camax + (int64_t)(i - 1) * G, g, reinterpret_cast<const float*>(wstat(wstat_conv(i - 1))),
+                                                  sqrtf((float)(KERN[i] * C)) * 1.00001f, conv_bias ? cb_max + i : nullptr,
+                                                  cscale + (int64_t)i * G, s));
+                o.Cp = nxt; o.c_plane = (int64_t)G * T[i] * C; o.sCp = (int64_t)T[i] * C; o.sC = (int64_t)T[i] * C;
+                o.c_scale = cscale + (int64_t)i * G; o.cs_zs = 1; o.cs_ms = 0;
+                o.amax = camax + (int64_t)i * G;
+            }
+            o.amax_zs = 1;
+            RSAF_TRY(conv_gemm(i, cur, o, g0, g, Tg));
+            std::swap(cur, nxt);
+        }
+        return RSAF_OK;
+    }
+
+    // 4. feature projection: LayerNorm (-> planes, exact row scales) + Linear; its epilogue reports max |x| per window
+    int feature_projection() {
+        RSAF_CHECK_HIP(hipMemsetAsync(ws + W.fp_amax, 0, sizeof(unsigned) * n, s));
+        LnArgs a;
+        a.x = ws + W.c6; a.g = Wt + L.fplg; a.b = Wt + L.fplb;
+        a.planes = planes_at(W.lnfp); a.panel = true; a.scale_out = ws + W.s_lnfp;
+        if (layer_norm) {                                    // conv6's LayerNorm (eps 1e-5) + GELU first, in the same row pass
+            a.var = 2; a.pg = cln + (int64_t)12 * C; a.pb = cln + (int64_t)13 * C;
+        } else if (c.flags & F_NO_FEAT_PROJ_LN) {            // the conv output itself, as planes
+            a.var = 3;
+        }
+        RSAF_TRY(ln(a, rows, C, c.eps, s));
+        Out o;
+        o.Cf = x; o.bias = Wt + L.fpb;
+        o.amax = bits_at(W.fp_amax); o.amax_row_slot = rowwin;
+        return gemm3(rows_a(W.lnfp, C, ws + W.s_lnfp), weights_b(W.wp_fp, W.ws_fp), o, (int)rows, Hd, C);
+    }
+
+    // 5. positional conv embedding (grouped, weight norm folded), GELU, then the first LayerNorm of the encoder: x = LN(x + pos),
+    //    or, stable layer norm, h = x + pos stays un-normalised (the residual stream) and layer 0's LN1(h) goes to the planes
+    int positional_conv() {
+        if (posconv_on_f16x3(c)) {
+            RSAF_TRY(posconv_regroup_planes());
+            const bool pc_off = [] { const char* e = getenv("RSAF_W2V2_POSCONV_GEMM"); return e && e[0] == '1'; }();   // per call: the tests toggle it
+            RSAF_TRY((!pc_off && posconv_resident(c, Tt)) ? posconv_lds() : posconv_batched_gemm());
+        } else {
+            RSAF_TRY(posconv_fp32());
+        }
+        if (pre_ln) return ln_to_qkv(x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, gate_rows(), 0, true, x);
+        return ln_to_qkv(x, ws + W.y, Wt + L.elng, Wt + L.elnb, x, 0, true);
+    }
+    // the regrouped sequence as k16 panels of T_w + PK - 1 rows per (window, group): tap k = one row down
+    int posconv_regroup_planes() {
+        const int TT = Tt + c.PK - 1;
+        const int64_t tot4 = (int64_t)n * TT * (Hd / 4);
+        ProfScope prof("w2v2_regroup", s, 0.0, (double)tot4 * 32);
+        hipLaunchKernelGGL(regroup_planes_kernel, dim3((unsigned)std::min<int64_t>((tot4 + 255) / 256, 4096)), dim3(256),
+                           0, s, reinterpret_cast<const float4*>(ws + W.x), reinterpret_cast<unsigned short*>(planes_at(W.xg)),
+                           (int64_t)n * TT * Hd, n, Tt, Hd / 4, c.PG, c.PK, Tw + (int64_t)6 * n, row0, bits_at(W.fp_amax), ws + W.pos_scale);
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+    template <int NT, int SP>
+    int posconv_lds_launch() {
+        const int cg = Hd / c.PG, TT = Tt + c.PK - 1;
+        const size_t lds = posconv_lds_bytes(cg, c.PK, SP);
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)posconv_f16x3_kernel<NT, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((posconv_f16x3_kernel<NT, SP>), dim3((unsigned)(n * c.PG)), dim3(512), lds, s,
+                           reinterpret_cast<const unsigned short*>(planes_at(W.xg)), (int64_t)n * TT * Hd,
+                           reinterpret_cast<const unsigned short*>(planes_at(W.wp_pos)), (int64_t)Hd * c.PK * cg, Hd,
+                           ws + W.pos_scale, ws + W.ws_pos, Wt + L.posb, Tw + (int64_t)6 * n, row0, ws + W.y, c.PG, TT, c.PK,
+                           posconv_rows_alloc(SP, c.PK));
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+    template <int SP>
+    int posconv_lds_launch_nt() {
+        switch (Hd / c.PG / 16) {
+            case 1: return posconv_lds_launch<1, SP>();
+            case 2: return posconv_lds_launch<2, SP>();
+            case 3: return posconv_lds_launch<3, SP>();
+            default: return posconv_lds_launch<4, SP>();
+        }
+    }
+    // the window's image stays in LDS (posconv_f16x3_kernel); RSAF_W2V2_POSCONV_GEMM=1: the batched GEMM below (A/B)
+    int posconv_lds() {
+        const int cg = Hd / c.PG;
+        ProfScope prof("w2v2_posconv_gemm", s, 2.0 * (double)rows * cg * (double)c.PK * cg * c.PG, 0.0);
+        return posconv_split(Tt) == 2 ? posconv_lds_launch_nt<2>() : posconv_lds_launch_nt<1>();
+    }
+    // grouped conv as a two-level batched GEMM on the f16x3 kernel's 256 x 64 tile: batch (window, group), M = T_w rows,
+    // N = cg output channels, K = PK cg
+    int posconv_batched_gemm() {
+        const int cg = Hd / c.PG, TT = Tt + c.PK - 1;
+        GemmH3Params p{};
+        p.A = planes_at(W.xg); p.a_plane = (int64_t)n * TT * Hd; p.lda = 16; p.sA = (int64_t)c.PG * TT * cg; p.sA2 = (int64_t)TT * cg;
+        p.a_panel = 1; p.a_panel_rows = TT; p.a_tap_panels = cg / 16;
+        p.a_scale = ws + W.pos_scale; p.a_scale_zs = 1; p.a_scale_ms = 0;
+        p.B = planes_at(W.wp_pos); p.b_plane = (int64_t)Hd * c.PK * cg; p.ldb = 16; p.b_panel = 1; p.b_panel_rows = Hd; p.sB2 = (int64_t)cg * 16;
+        p.b_scale = ws + W.ws_pos;
+        p.C = ws + W.y; p.ldc = Hd; p.sC = 0; p.sC2 = cg;
+        p.bias = Wt + L.posb; p.sBias2 = cg;
+        p.M = Tt; p.ztab = ztab + (int64_t)6 * n * 2; p.N = cg; p.K = c.PK * cg; p.nz = n * c.PG; p.nz2 = c.PG; p.act = ACT_GELU; p.alpha = 1.0f;
+        return launch_gemm_f16x3(p, s, "w2v2_posconv_gemm");
+    }
+    // group widths that are no multiple of 16 (test geometries): exact-fp32 GEMM, one launch per run of equal windows
+    int posconv_fp32() {
+        const int cg = Hd / c.PG;
+        for (const auto& tg : R.tgroups) {
+            const int nw = tg.second - tg.first, Tq = R.T6[tg.first], TTq = Tq + c.PK - 1;
+            const int64_t r0 = R.row0[tg.first];
+            const int64_t t4 = (int64_t)nw * TTq * (Hd / 4);
+            {
+                ProfScope prof("w2v2_regroup", s, 0.0, (double)t4 * 32);
+                hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)std::min<int64_t>((t4 + 255) / 256, 4096)), dim3(256),
+                                   0, s, reinterpret_cast<const float4*>(ws + W.x + r0 * Hd), reinterpret_cast<float4*>(ws + W.xg),
+                                   nw, Tq, Hd / 4, c.PG, c.PK);
+                RSAF_CHECK_HIP(hipGetLastError());
+            }
+            GemmParams p = gemm_params_plain(ws + W.xg, Wt + L.posw, ws + W.y + r0 * Hd, Tq, cg, c.PK * cg, cg, (int64_t)c.PK * cg, Hd);
+            p.nz = nw * c.PG; p.nz2 = c.PG;
+            p.sA1 = (int64_t)c.PG * TTq * cg; p.sA2 = (int64_t)TTq * cg;
+            p.sB1 = 0; p.sB2 = (int64_t)cg * c.PK * cg;
+            p.sC1 = (int64_t)Tq * Hd; p.sC2 = cg;
+            p.bias = Wt + L.posb; p.sBias2 = cg; p.act = ACT_GELU;
+            RSAF_TRY(launch_gemm_f32(p, s, "w2v2_posconv_gemm"));
+        }
+        return RSAF_OK;
+    }
+
+    // The LayerNorm between two q/k/v projections: LN(src (+ res)) under g / b, fp32 rows into dst (x, the att buffer for the
+    // gates, the call's `out`, or none), hidden_states[k] into its tap.
+    // next: layer k follows and reads the planes in W.xp under the scales in W.s_x (fused attention: this LayerNorm also reports
+    // the window's largest row norm, behind the scale of that layer's q / k / v).  Else dst is `out`: frame t of window w at
+    // row out_row_start[w] + t (or packed, window after window).
+    // The tap takes this LayerNorm's output, except in the PRE_LN flow while a layer follows: there hidden_states[k] is the
+    // un-normalised residual stream h that this LayerNorm reads.  sum (PRE_LN after the positional conv): src + res goes there.
+    int ln_to_qkv(const float* src, const float* res, const float* g, const float* b, float* dst, int k, bool next,
+                  float* sum = nullptr) {
+        LnArgs a;
+        a.x = src; a.r = res; a.g = g; a.b = b;
+        a.out = dst; a.rowwin = rowwin; a.row0 = row0;
+        if (next) {
+            if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
+            a.planes = planes_at(W.xp); a.panel = true; a.scale_out = ws + W.s_x;
+            a.win_norm = fused ? bits_at(W.win_norm) : nullptr;
+        } else {
+            a.out_row_start = out_row_start;
+        }
+        a.var = sum ? 1 : 0; a.aux = sum;
+        a.tap = tap(k); a.tap_mode = (pre_ln && next) ? 2 : 1; a.tap_row_start = out_row_start;
+        return ln(a, rows, Hd, c.eps, s);
+    }
+
+    // fused q,k,v projection of layer l (A = the planes the previous LayerNorm wrote beside x).  Fused attention: the output
+    // leaves as the fp16 plane pair the attention kernel multiplies, under one power of two per window (the bound over its
+    // rows).  REL_POS_BIAS: then the bias gates of the layer
+    int qkv_projection(int l) {
+        const int b0 = WSTAT_LAYER0 + WSTAT_PER_LAYER * l;
+        Out o;
+        o.bias = Wt + L.layers[l].bqkv;
+        if (fused) {
+            hipLaunchKernelGGL(qkv_scale_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bits_at(W.win_norm), rowwin, rows,
+                               wstat(b0), wstat(b0 + 5), ws + W.s_qkv);
+            RSAF_CHECK_HIP(hipGetLastError());
+            o.Cp = planes_at(W.qkv); o.c_plane = rows * 3 * Hd; o.c_scale = ws + W.s_qkv; o.cs_zs = 0; o.cs_ms = 1;
+        } else {
+            o.Cf = ws + W.qkv;
+        }
+        const int rc = gemm3(rows_a(W.xp, Hd, ws + W.s_x), weights_b(W.wp_qkv[l], W.ws_qkv[l]), o, (int)rows, 3 * Hd, Hd);
+        if (rc || !relpos) return rc;
+        const int64_t items = rows * c.NH;
+        RSAF_CHECK_ARG((items + 15) / 16 <= 0x7fffffffLL, "too many rows");
+        ProfScope prof("w2v2_relpos_gate", s, 0.0, (double)rows * Hd * 4 + (double)items * 4);
+        hipLaunchKernelGGL(relpos_gate_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 2 * hd * sizeof(float), s,
+                           pre_ln ? ws + W.att : x, items, c.NH, hd, Wt + L.ga[l], Wt + L.gb[l], Wt + L.gbias[l], Wt + L.gconst[l], gate());
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+
+    // attention of a layer: the planes of its output in W.attp (scales: W.s_qkv fused, W.s_att three-launch)
+    int attention() { return fused ? (relpos ? attention_fused<true>() : attention_fused<false>()) : attention_three_launch(); }
+    template <bool RP>
+    int attention_fused() {
+        // 2 x 2 T^2 hd flops per (chunk, head)
+        double att_flops = 0.0;
+        for (const auto& tg : R.tgroups) att_flops += 4.0 * (tg.second - tg.first) * c.NH * (double)R.T6[tg.first] * R.T6[tg.first] * hd;
+        ProfScope prof("w2v2_attn_fused", s, att_flops, 0.0);
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_f16x3_kernel<RP>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 128 * 64 * 2));
+        hipLaunchKernelGGL(attn_f16x3_kernel<RP>, dim3((unsigned)(n * c.NH), (unsigned)((Tt + 127) / 128)), dim3(256), 2 * 2 * 128 * 64 * 2, s,
+                           planes_at(W.qkv), rows * 3 * Hd, planes_at(W.attp), rows * Hd, rows, Tw + (int64_t)6 * n, row0, c.NH, Hd, scale,
+                           ws + W.s_qkv, gate(), reltab());
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+    // three launches per run of equal windows (head widths other than 64: test geometries), then the planes of the result
+    // (the fused kernel writes them itself)
+    int attention_three_launch() {
+        for (const auto& tg : R.tgroups) {
+            const int nw = tg.second - tg.first, Tq = R.T6[tg.first], Tpq = (int)pad4(Tq);
+            const int64_t r0 = R.row0[tg.first];
+            const float* qkvg = ws + W.qkv + r0 * 3 * Hd;
+            {   // S = scale * Q K^T per (chunk, head)
+                GemmParams p = gemm_params_plain(qkvg, qkvg + Hd, ws + W.S, Tq, Tq, hd, 3 * Hd, 3 * Hd, Tpq);
+                p.nz = nw * c.NH; p.nz2 = c.NH;
+                p.sA1 = (int64_t)Tq * 3 * Hd; p.sA2 = hd; p.sB1 = p.sA1; p.sB2 = hd;
+                p.sC1 = (int64_t)c.NH * Tq * Tpq; p.sC2 = (int64_t)Tq * Tpq;
+                p.alpha = scale;
+                RSAF_TRY(launch_gemm_f32(p, s, "w2v2_attn_gemm"));
+            }
+            {
+                const int64_t srows = (int64_t)nw * c.NH * Tq;
+                ProfScope prof("w2v2_softmax", s, 0.0, (double)srows * Tpq * 8);
+#define RSAF_SOFTMAX(...)                                                                                                      \
+    hipLaunchKernelGGL((softmax_kernel<__VA_ARGS__>), dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, s, ws + W.S, srows, Tq, Tpq, \
+                       gate(), reltab(), c.NH, r0)
+                if (Tpq <= 256) { if (relpos) RSAF_SOFTMAX(true, true); else RSAF_SOFTMAX(true); }
+                else { if (relpos) RSAF_SOFTMAX(false, true); else RSAF_SOFTMAX(false); }
+#undef RSAF_SOFTMAX
+                RSAF_CHECK_HIP(hipGetLastError());
+            }
+            {   // O = P V per (chunk, head), V is [T, hd] with N contiguous
+                GemmParams p = gemm_params_plain(ws + W.S, qkvg + 2 * Hd, ws + W.att + r0 * Hd, Tq, hd, Tq, Tpq, 3 * Hd, Hd);
+                p.nz = nw * c.NH; p.nz2 = c.NH; p.b_kn = 1;
+                p.sA1 = (int64_t)c.NH * Tq * Tpq; p.sA2 = (int64_t)Tq * Tpq;
+                p.sB1 = (int64_t)Tq * 3 * Hd; p.sB2 = hd;
+                p.sC1 = (int64_t)Tq * Hd; p.sC2 = hd;
+                RSAF_TRY(launch_gemm_f32(p, s, "w2v2_attn_gemm"));
+            }
+        }
+        RSAF_TRY(launch_f16x2_row_scales(ws + W.att, rows, Hd, Hd, ws + W.s_att, nullptr, nullptr, s));
+        return launch_split_f16x2(ws + W.att, rows, Hd, Hd, ws + W.s_att, 1, planes_at(W.attp), rows * Hd, 1, s);
+    }
+
+    // y = attn Wo^T + bo + x
+    int out_projection(int l) {
+        Out o;
+        o.Cf = ws + W.y; o.bias = Wt + L.layers[l].bo; o.R = x;
+        return gemm3(rows_a(W.attp, Hd, fused ? ws + W.s_qkv : ws + W.s_att), weights_b(W.wp_o[l], W.ws_o[l]), o, (int)rows, Hd, Hd);
+    }
+    // LN(y) under g / b as the planes the feed forward reads, with the bound behind the scale of the ffn1 output; fp32 rows
+    // into dst (or none)
+    int ln_to_ffn(int l, const float* g, const float* b, float* dst) {
+        const int b0 = WSTAT_LAYER0 + WSTAT_PER_LAYER * l;
+        LnArgs a;
+        a.x = ws + W.y; a.g = g; a.b = b; a.out = dst;
+        a.planes = planes_at(W.xp); a.panel = true; a.scale_out = ws + W.s_x;
+        a.bound_w = wstat(b0 + 2); a.bound_b = wstat(b0 + 4); a.bound_scale_out = ws + W.s_ffn;
+        return ln(a, rows, Hd, c.eps, s);
+    }
+    // dst = GELU(xp W1^T + b1) W2^T + b2 + res; the GELU output only exists as planes (A of the second GEMM)
+    int feed_forward(int l, float* dst, const float* res) {
+        const LayerOff& lo = L.layers[l];
+        Out o1;
+        o1.Cp = planes_at(W.ffnp); o1.c_plane = rows * c.I; o1.c_scale = ws + W.s_ffn; o1.cs_zs = 0; o1.cs_ms = 1; o1.cp_panel = true;
+        o1.bias = Wt + lo.b1; o1.act = ACT_GELU;
+        RSAF_TRY(gemm3(rows_a(W.xp, Hd, ws + W.s_x), weights_b(W.wp_1[l], W.ws_1[l]), o1, (int)rows, c.I, Hd));
+        Out o2;
+        o2.Cf = dst; o2.bias = Wt + lo.b2; o2.R = res;
+        return gemm3(rows_a(W.ffnp, c.I, ws + W.s_ffn), weights_b(W.wp_2[l], W.ws_2[l]), o2, (int)rows, Hd, c.I);
+    }
+
+    // 6. encoder layer l.  Post-LN: y = attn + x, x = LN1(y), y = ffn(x) + x, x = LN2(y): hidden_states[l + 1], which after the
+    //    last layer goes into `out`
+    int layer_post_ln(int l) {
+        const LayerOff& lo = L.layers[l];
+        const bool last = l == c.L - 1;
+        RSAF_TRY(out_projection(l));
+        RSAF_TRY(ln_to_ffn(l, Wt + lo.ln1g, Wt + lo.ln1b, x));
+        RSAF_TRY(feed_forward(l, ws + W.y, x));
+        return ln_to_qkv(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, last ? out : x, l + 1, !last);
+    }
+    //    PRE_LN (stable layer norm): the residual stream h ping-pongs between x and y: y = attn(LN1(x)) + x, x = ffn(LN2(y)) + y,
+    //    and the LayerNorms write planes only: LN1 of the next layer (hidden_states[l + 1] = h), or encoder.layer_norm into `out`
+    //    after the last one (= hidden_states[L])
+    int layer_pre_ln(int l) {
+        const LayerOff& lo = L.layers[l];
+        RSAF_TRY(out_projection(l));
+        RSAF_TRY(ln_to_ffn(l, Wt + lo.ln2g, Wt + lo.ln2b, nullptr));
+        RSAF_TRY(feed_forward(l, x, ws + W.y));
+        if (l == c.L - 1) return ln_to_qkv(x, nullptr, Wt + L.elng, Wt + L.elnb, out, l + 1, false);
+        const LayerOff& nx = L.layers[l + 1];
+        return ln_to_qkv(x, nullptr, Wt + nx.ln1g, Wt + nx.ln1b, gate_rows(), l + 1, true);
+    }
+    int encoder_layer(int l) {
+        RSAF_TRY(qkv_projection(l));
+        RSAF_TRY(attention());
+        return pre_ln ? layer_pre_ln(l) : layer_post_ln(l);
+    }
+};
+
+static int forward_impl(const float* wav, const int64_t* chunk_start, const int* len_dev_or_null, const Rag& R, const Cfg& c,
+                        const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
+                        hipStream_t s, float* const* taps = nullptr) {
+    RSAF_CHECK_ARG(R.n <= 65535 / std::max(c.NH, c.PG), "too many chunks per call");
+    RSAF_CHECK_ARG(wav && chunk_start && weights && workspace && out, "NULL pointer");
+    const Workspace W = make_ws(c, R);
+    if (workspace_bytes < W.total * (int64_t)sizeof(float)) {
+        set_error("rsaf_w2v2_forward: workspace too small");
+        return RSAF_ERR_WORKSPACE;
+    }
+    RSAF_CHECK_ARG(R.rows <= 0x7fffffffLL, "too many frames per call");
+    Forward f(c, R, W, weights, workspace, s);
+    f.wav = wav; f.chunk_start = chunk_start; f.out = out; f.out_row_start = out_row_start; f.taps = taps;
+    RSAF_TRY(f.window_tables(len_dev_or_null));
+    RSAF_TRY(f.weight_planes());
+    RSAF_TRY(f.feature_encoder());
+    RSAF_TRY(f.feature_projection());
+    RSAF_TRY(f.positional_conv());
+    for (int l = 0; l < c.L; ++l)
+        RSAF_TRY(f.encoder_layer(l));
+    return RSAF_OK;
+}
+
+// Cfg of an entry point's geometry arguments, checked
+static int make_cfg(Cfg& c, int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel, int pos_groups,
+                    float eps, int flags) {
+    c = Cfg{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, eps, flags};
+    return check_cfg(c);
+}
+
 }  // namespace w2v2
 }  // namespace rsaf
 
@@ -1408,15 +2008,13 @@ int rsaf_w2v2_frames(int chunk_len) {
 
 int64_t rsaf_w2v2_weight_floats(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                 int pos_groups) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f};
-    if (check_cfg(c) != RSAF_OK) return -1;
-    return make_layout(c).total;
+    return rsaf_w2v2_weight_floats_ex(conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 0);
 }
 
 int64_t rsaf_w2v2_weight_floats_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                    int pos_groups, int flags) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
-    if (check_cfg(c) != RSAF_OK) return -1;
+    Cfg c;
+    if (make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags) != RSAF_OK) return -1;
     return make_layout(c).total;
 }
 
@@ -1428,9 +2026,8 @@ int rsaf_w2v2_weight_offsets(int conv_dim, int hidden, int layers, int heads, in
 
 int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                 int pos_groups, int flags, int64_t* offsets_host, int cap, int* n_host) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
-    int rc = check_cfg(c);
-    if (rc != RSAF_OK) return rc;
+    Cfg c;
+    RSAF_TRY(make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags));
     RSAF_CHECK_ARG(offsets_host && n_host, "NULL output");
     const Layout L = make_layout(c);
     std::vector<int64_t> v = {L.conv0, L.gng, L.gnb};
@@ -1454,19 +2051,11 @@ int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads,
     return RSAF_OK;
 }
 
-static int forward_impl(const float* wav, const int64_t* chunk_start, const int* len_dev_or_null, const Rag& R, const Cfg& c,
-                        const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
-                        hipStream_t s, float* const* taps = nullptr);
-
 int64_t rsaf_w2v2_workspace_bytes(int n_chunks, int chunk_len, int conv_dim, int hidden, int layers, int heads,
                                   int intermediate, int pos_kernel, int pos_groups) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f};
-    if (check_cfg(c) != RSAF_OK || n_chunks <= 0) return -1;
-    if (rsaf_w2v2_frames(chunk_len) <= 0) return -1;
-    std::vector<int> len((size_t)n_chunks, chunk_len);
-    Rag R;
-    if (make_rag(len.data(), n_chunks, R) != RSAF_OK) return -1;
-    return make_ws(c, R).total * (int64_t)sizeof(float);
+    const std::vector<int> len((size_t)std::max(n_chunks, 1), chunk_len);
+    return rsaf_w2v2_workspace_bytes_ragged_ex(len.data(), n_chunks, conv_dim, hidden, layers, heads, intermediate, pos_kernel,
+                                               pos_groups, 0);
 }
 
 int64_t rsaf_w2v2_workspace_bytes_ragged(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
@@ -1477,10 +2066,11 @@ int64_t rsaf_w2v2_workspace_bytes_ragged(const int* chunk_len_host, int n_chunks
 
 int64_t rsaf_w2v2_workspace_bytes_ragged_ex(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers, int heads,
                                             int intermediate, int pos_kernel, int pos_groups, int flags) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags};
-    if (check_cfg(c) != RSAF_OK || n_chunks <= 0 || !chunk_len_host) return -1;
+    Cfg c;
+    if (make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, 1e-5f, flags) != RSAF_OK || n_chunks <= 0 ||
+        !chunk_len_host) return -1;
     Rag R;
-    if (make_rag(chunk_len_host, n_chunks, R) != RSAF_OK) return -1;
+    if (make_rag(chunk_len_host, n_chunks, 0, R) != RSAF_OK) return -1;
     return make_ws(c, R).total * (int64_t)sizeof(float);
 }
 
@@ -1488,14 +2078,12 @@ int rsaf_w2v2_forward(const float* wav, const int64_t* chunk_start, int n_chunks
                       int hidden, int layers, int heads, int intermediate, int pos_kernel, int pos_groups,
                       float layer_norm_eps, const float* weights, void* workspace, int64_t workspace_bytes,
                       float* out, const int64_t* out_row_start, rsaf_stream_t stream) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps};
-    int rc = check_cfg(c);
-    if (rc != RSAF_OK) return rc;
+    Cfg c;
+    RSAF_TRY(make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, 0));
     RSAF_CHECK_ARG(n_chunks >= 0, "negative chunk count");
     if (n_chunks == 0) return RSAF_OK;
-    std::vector<int> len((size_t)n_chunks, chunk_len);
     Rag R;
-    if ((rc = make_rag(len.data(), n_chunks, R))) return rc;
+    RSAF_TRY(make_rag(nullptr, n_chunks, chunk_len, R));
     return forward_impl(wav, chunk_start, nullptr, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream);
 }
 
@@ -1512,14 +2100,13 @@ int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, co
                                 int n_chunks, int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                 int pos_groups, float layer_norm_eps, int flags, const float* weights, void* workspace,
                                 int64_t workspace_bytes, float* out, const int64_t* out_row_start, rsaf_stream_t stream) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags};
-    int rc = check_cfg(c);
-    if (rc != RSAF_OK) return rc;
+    Cfg c;
+    RSAF_TRY(make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags));
     RSAF_CHECK_ARG(n_chunks >= 0, "negative chunk count");
     if (n_chunks == 0) return RSAF_OK;
     RSAF_CHECK_ARG(chunk_len && chunk_len_host, "NULL length table");
     Rag R;
-    if ((rc = make_rag(chunk_len_host, n_chunks, R))) return rc;
+    RSAF_TRY(make_rag(chunk_len_host, n_chunks, 0, R));
     return forward_impl(wav, chunk_start, chunk_len, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream);
 }
 
@@ -1528,9 +2115,8 @@ int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start
                                     int pos_groups, float layer_norm_eps, int flags, const float* weights, void* workspace,
                                     int64_t workspace_bytes, float* out, const int64_t* out_row_start, const int* hidden_index_host,
                                     int n_hidden, float* hidden_out, int64_t hidden_plane_floats, rsaf_stream_t stream) {
-    Cfg c{conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags};
-    int rc = check_cfg(c);
-    if (rc != RSAF_OK) return rc;
+    Cfg c;
+    RSAF_TRY(make_cfg(c, conv_dim, hidden, layers, heads, intermediate, pos_kernel, pos_groups, layer_norm_eps, flags));
     // the taps are checked on the host before anything else: strictly increasing layer indices in [0, layers]
     RSAF_CHECK_ARG(n_hidden >= 0 && n_hidden <= layers + 1, "n_hidden out of range");
     if (n_hidden == 0)
@@ -1548,7 +2134,7 @@ int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start
     if (n_chunks == 0) return RSAF_OK;
     RSAF_CHECK_ARG(chunk_len && chunk_len_host, "NULL length table");
     Rag R;
-    if ((rc = make_rag(chunk_len_host, n_chunks, R))) return rc;
+    RSAF_TRY(make_rag(chunk_len_host, n_chunks, 0, R));
     RSAF_CHECK_ARG(hidden_plane_floats >= R.rows * (int64_t)hidden, "hidden_plane_floats smaller than the call's frames");
     std::vector<float*> taps((size_t)layers + 1, nullptr);
     for (int j = 0; j < n_hidden; ++j) taps[hidden_index_host[j]] = hidden_out + (int64_t)j * hidden_plane_floats;
@@ -1557,453 +2143,3 @@ int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start
 }
 
 }  // extern "C"
-
-static int forward_impl(const float* wav, const int64_t* chunk_start, const int* len_dev_or_null, const Rag& R, const Cfg& c,
-                        const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
-                        hipStream_t s, float* const* taps) {
-    // taps (NULL: no hidden states): taps[k], k = 0..L, receives hidden_states[k] in the row layout of `out`, or is NULL
-    auto tap = [&](int k) -> float* { return taps ? taps[k] : nullptr; };
-    int rc = RSAF_OK;
-    const int n_chunks = R.n;
-    RSAF_CHECK_ARG(n_chunks <= 65535 / std::max(c.NH, c.PG), "too many chunks per call");
-    RSAF_CHECK_ARG(wav && chunk_start && weights && workspace && out, "NULL pointer");
-    const int* T = R.Tmax;                                   // frames of the LONGEST window per layer (strides, grids)
-    const Workspace W = make_ws(c, R);
-    if (workspace_bytes < W.total * (int64_t)sizeof(float)) {
-        set_error("rsaf_w2v2_forward: workspace too small");
-        return RSAF_ERR_WORKSPACE;
-    }
-    const Layout L = make_layout(c);
-    float* ws = static_cast<float*>(workspace);
-    const float* Wt = weights;
-    const int n = n_chunks, C = c.C, Hd = c.Hd, Tt = T[6];
-    const int64_t rows = R.rows;
-    RSAF_CHECK_ARG(rows <= 0x7fffffffLL, "too many frames per call");
-
-    auto planes_at = [&](int64_t off) { return reinterpret_cast<uint16_t*>(ws + off); };
-    auto bits_at = [&](int64_t off) { return reinterpret_cast<unsigned*>(ws + off); };
-    auto wstat = [&](int idx) { return bits_at(W.wstat) + 2 * idx; };        // {max row norm, max |element|} of matrix idx
-    // window tables on the device (every window has its own length: the reference's tail windows)
-    int* Tw = reinterpret_cast<int*>(ws + W.t_Tw);           // [7][n]
-    int64_t* row0 = reinterpret_cast<int64_t*>(ws + W.t_row0);
-    int64_t* ztab = reinterpret_cast<int64_t*>(ws + W.t_ztab);   // [7][n][2]
-    int* rowwin = reinterpret_cast<int*>(ws + W.t_rowwin);
-    const int* wlen = len_dev_or_null;
-    {
-        if (!wlen) {                                         // equal windows: the length table is filled here
-            int* wl = reinterpret_cast<int*>(ws + W.wlen);
-            hipLaunchKernelGGL(fill_i32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, wl, n, R.maxlen);
-            wlen = wl;
-        }
-        hipLaunchKernelGGL(w2v2_tables_kernel, dim3(1), dim3(256), 0, s, wlen, n, C, Hd, Tw, row0, ztab);
-        hipLaunchKernelGGL(w2v2_rowwin_kernel, dim3(n), dim3(256), 0, s, row0, rowwin);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    // helper: C = act(A B^T + bias (+ R)) on the f16x3 kernel; A / B as fp16 plane pairs with their scales
-    struct Out { float* Cf; int64_t sC; uint16_t* Cp; int64_t c_plane, sCp; const float* c_scale; int cs_zs, cs_ms; bool cp_panel; };
-    auto gemm3 = [&](const uint16_t* A, int64_t a_plane, int64_t lda, int64_t sA, const float* a_scale, int as_zs, int as_ms,
-                     const uint16_t* B, const float* b_scale, int M, int N, int K, const Out& o, const float* bias, const float* Rr,
-                     int nz, int act, const char* tag, bool a_panel, unsigned* amax = nullptr, int amax_zs = 0,
-                     const int* amax_row_slot = nullptr, int amax_col_min = 0, const int64_t* ztab = nullptr) {
-        GemmH3Params p{};
-        p.a_panel = a_panel; p.b_panel = 1; p.cp_panel = o.cp_panel;
-        p.A = A; p.a_plane = a_plane; p.lda = lda; p.sA = sA; p.a_scale = a_scale; p.a_scale_zs = as_zs; p.a_scale_ms = as_ms;
-        p.B = B; p.b_plane = (int64_t)N * K; p.ldb = 16; p.b_scale = b_scale;
-        p.C = o.Cf; p.ldc = N; p.sC = o.sC;
-        p.Cp = o.Cp; p.c_plane = o.c_plane; p.ldcp = N; p.sCp = o.sCp; p.c_scale = o.c_scale; p.c_scale_zs = o.cs_zs; p.c_scale_ms = o.cs_ms;
-        p.amax_out = amax; p.amax_zs = amax_zs; p.amax_row_slot = amax_row_slot; p.amax_col_min = amax_col_min;
-        p.bias = bias; p.R = Rr; p.ldr = N; p.sR = o.sC;
-        p.M = M; p.N = N; p.K = K; p.nz = nz; p.ztab = ztab; p.act = act; p.alpha = 1.0f; p.group_m = 0;
-        return launch_gemm_f16x3(p, s, tag);
-    };
-    // 0. weights of the dense layers as fp16 plane pairs in the k16-panel layout, each row with its own power-of-two scale
-    //    (once per call: 0.4 GB at base geometry, < 1 ms), and per matrix the largest row norm: the Cauchy-Schwarz factor of
-    //    the bound behind the scale of a GEMM's PLANE output (conv1..5, ffn1)
-    RSAF_CHECK_HIP(hipMemsetAsync(ws + W.wstat, 0, sizeof(float) * 2 * (WSTAT_LAYER0 + WSTAT_PER_LAYER * c.L), s));
-    {
-        auto split_wp = [&](int64_t src_off, int64_t nrows, int K, int64_t dst_off, int64_t scale_off, int stat_idx) {
-            int r2 = launch_f16x2_row_scales(Wt + src_off, nrows, K, K, ws + scale_off, nullptr, wstat(stat_idx), s);
-            if (r2) return r2;
-            return launch_split_f16x2(Wt + src_off, nrows, K, K, ws + scale_off, 1, planes_at(dst_off), nrows * K, 1, s);
-        };
-        for (int i = 0; i < 6; ++i)
-            if ((rc = split_wp(L.conv[i], C, KERN[i + 1] * C, W.wp_conv[i], W.ws_conv[i], wstat_conv(i)))) return rc;
-        if ((rc = split_wp(L.fpw, Hd, C, W.wp_fp, W.ws_fp, WSTAT_FP))) return rc;
-        if ((Hd / c.PG) % 16 == 0) {                       // positional conv on the f16x3 GEMM: [G cg][PK cg] as panels of Hd rows
-            if ((rc = split_wp(L.posw, Hd, c.PK * (Hd / c.PG), W.wp_pos, W.ws_pos, WSTAT_POS))) return rc;
-        }
-        for (int l = 0; l < c.L; ++l) {
-            const LayerOff& lo = L.layers[l];
-            const int b0 = WSTAT_LAYER0 + WSTAT_PER_LAYER * l;
-            if ((rc = split_wp(lo.wqkv, 3 * Hd, Hd, W.wp_qkv[l], W.ws_qkv[l], b0))) return rc;
-            if ((rc = split_wp(lo.wo, Hd, Hd, W.wp_o[l], W.ws_o[l], b0 + 1))) return rc;
-            if ((rc = split_wp(lo.w1, c.I, Hd, W.wp_1[l], W.ws_1[l], b0 + 2))) return rc;
-            if ((rc = split_wp(lo.w2, Hd, c.I, W.wp_2[l], W.ws_2[l], b0 + 3))) return rc;
-            // max |b1| (word 1 of the statistics of the bias seen as one row); the scale it writes goes to a scratch slot
-            if ((rc = launch_f16x2_row_scales(Wt + lo.b1, 1, c.I, c.I, ws + W.pos_scale, nullptr, wstat(b0 + 4), s))) return rc;
-            if ((rc = launch_f16x2_row_scales(Wt + lo.bqkv, 1, 3 * Hd, 3 * Hd, ws + W.pos_scale, nullptr, wstat(b0 + 5), s))) return rc;
-        }
-    }
-    // 1-3. feature encoder, CONV_GROUP windows at a time (its activations are the large ones: 15 999 x 512 per window)
-    // window groups of (almost) equal size: ceil(n / G) groups instead of full ones and a small remainder
-    const int n_groups = (n + W.G - 1) / W.G, gstep = (n + n_groups - 1) / n_groups;
-    float* cscale = ws + W.conv_scale;                       // [7][G]: scale of layer i's plane output, per window of the group
-    unsigned* camax = bits_at(W.conv_amax);                  // [7][G]: largest |output| of layer i (layer 0: its bound)
-    const bool layer_norm = c.flags & F_LAYER_FEAT_NORM, conv_bias = c.flags & F_CONV_BIAS;
-    const float* cbias = conv_bias ? Wt + L.cb : nullptr;    // [7][C]
-    const float* cln = Wt + L.cln;                           // [7][2][C] (layer mode)
-    float* cb_max = conv_bias ? ws + W.cb_max : nullptr;     // [8]: max |bias| of conv1..5 at 1..5
-    if (layer_norm) {                                        // layer mode: the planes' scales depend on the weights only
-        hipLaunchKernelGGL(lnconv_scale_kernel, dim3(1), dim3(384), 0, s, cln, C, W.G, cscale);
-        RSAF_CHECK_HIP(hipGetLastError());
-    } else if (conv_bias) {
-        hipLaunchKernelGGL(conv_bias_max_kernel, dim3(1), dim3(64), 0, s, cbias, C, cb_max);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    for (int g0 = 0; g0 < n; g0 += gstep) {
-        const int g = std::min(gstep, n - g0);
-        // the group's longest window is its first (lengths are non-increasing): its frame counts size the group's launches
-        int Tg[7];
-        chunk_lengths(R.len[g0], Tg);
-        if (!layer_norm) RSAF_CHECK_HIP(hipMemsetAsync(camax, 0, sizeof(unsigned) * 7 * W.G, s));
-        // 1. per-chunk normalisation (HF feature extractor; NO_INPUT_NORM: do_normalize=False, a copy)
-        {
-            ProfScope prof("w2v2_normalize", s, 0.0, (double)g * R.len[g0] * 4 * 3);
-            if (c.flags & F_NO_INPUT_NORM)
-                hipLaunchKernelGGL(normalize_kernel<false>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
-            else
-                hipLaunchKernelGGL(normalize_kernel<true>, dim3(g), dim3(256), 0, s, wav, chunk_start + g0, wlen + g0, R.maxlen, ws + W.xn);
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        if (layer_norm) {
-            // 2-3 (layer mode). conv0 + LayerNorm + GELU in one pass; conv1..6 as GEMMs writing fp32 rows (+ bias) into the Q buffer,
-            // then LayerNorm -> GELU -> planes back into P (the GEMM has consumed them); conv6 writes its packed rows, and its
-            // LayerNorm + GELU join the feature projection's LayerNorm (step 4)
-            if ((rc = conv0_ln_launch(c, ws + W.xn, Wt + L.conv0, cbias, cln, cln + C, cscale, planes_at(W.P), (int64_t)W.G * T[0] * C,
-                                      g, R.maxlen, Tw + g0, T[0], Tg[0], s))) return rc;
-            for (int i = 1; i < 7; ++i) {
-                const bool last = i == 6;
-                Out o{};
-                if (last) { o.Cf = ws + W.c6; o.sC = 0; }
-                else { o.Cf = ws + W.Q; o.sC = (int64_t)T[i] * C; }
-                rc = gemm3(planes_at(W.P), (int64_t)W.G * T[i - 1] * C, (int64_t)STRD[i] * C, (int64_t)T[i - 1] * C, cscale + (int64_t)(i - 1) * W.G,
-                           1, 0, planes_at(W.wp_conv[i - 1]), ws + W.ws_conv[i - 1], Tg[i], C, KERN[i] * C, o,
-                           conv_bias ? cbias + (int64_t)i * C : nullptr, nullptr, g, ACT_NONE, "w2v2_gemm", false, nullptr, 0, nullptr, 0,
-                           ztab + ((int64_t)(i - 1) * n + g0) * 2);
-                if (rc) return rc;
-                if (!last) {
-                    const int64_t lrows = (int64_t)g * T[i];
-                    ProfScope prof("w2v2_conv_ln", s, 0.0, (double)lrows * C * 8.0);
-                    hipLaunchKernelGGL(conv_ln_gelu_kernel, dim3((unsigned)((lrows + 3) / 4)), dim3(256), 0, s, ws + W.Q,
-                                       cln + (int64_t)2 * i * C, cln + (int64_t)(2 * i + 1) * C, cscale + (int64_t)i * W.G,
-                                       planes_at(W.P), (int64_t)W.G * T[i] * C, lrows, T[i], Tw + (int64_t)i * n + g0, C);
-                    RSAF_CHECK_HIP(hipGetLastError());
-                }
-            }
-            continue;
-        }
-        // 2. conv0 + GroupNorm + GELU (stats pass, finalize, apply pass); the apply pass writes fp16 plane pairs
-        const int slabs_g = (Tg[0] + STAT_SLAB - 1) / STAT_SLAB;
-        rc = conv_bias ? conv0_launch<false, true>(c, ws + W.xn, Wt + L.conv0, cbias, ws + W.part, nullptr, nullptr, nullptr, 0, g,
-                                                   R.maxlen, Tw + g0, T[0], STAT_SLAB, slabs_g, s)
-                       : conv0_launch<false, false>(c, ws + W.xn, Wt + L.conv0, nullptr, ws + W.part, nullptr, nullptr, nullptr, 0, g,
-                                                    R.maxlen, Tw + g0, T[0], STAT_SLAB, slabs_g, s);
-        if (rc) return rc;
-        {
-            const int64_t tot = (int64_t)g * C;
-            hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ws + W.part,
-                               Wt + L.gng, Wt + L.gnb, ws + W.ab, camax, g, C, slabs_g, Tw + g0);
-            RSAF_CHECK_HIP(hipGetLastError());
-            if ((rc = launch_scale_from_bound(camax, g, nullptr, 1.0f, nullptr, cscale, s))) return rc;
-        }
-        {
-            const int slab = 128;
-            rc = conv_bias ? conv0_launch<true, true>(c, ws + W.xn, Wt + L.conv0, cbias, nullptr, ws + W.ab, cscale, planes_at(W.P),
-                                                      (int64_t)W.G * T[0] * C, g, R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s)
-                           : conv0_launch<true, false>(c, ws + W.xn, Wt + L.conv0, nullptr, nullptr, ws + W.ab, cscale, planes_at(W.P),
-                                                       (int64_t)W.G * T[0] * C, g, R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s);
-            if (rc) return rc;
-        }
-        // 3. conv1..6 as GEMMs over the channels-last sequence (lda = stride * C, K = taps * C) with fused GELU;
-        //    the output goes out as planes (the next layer's A), the last one as fp32 rows for the LayerNorm.
-        //    Scale of layer i's output, per window: |GELU(x)| <= |x| <= |a|_2 |w|_2 <= sqrt(K) max|a| max_n |w_n|_2 with
-        //    max|a| = the largest |output| of layer i - 1, which that layer's epilogue reported (layer 0: the GroupNorm bound).
-        //    Every window keeps the longest window's row allotment (batch stride T[i] rows) and has its own row count
-        //    (ztab); the last layer writes its rows packed (window w at row row0[w]).
-        uint16_t* cur = planes_at(W.P);
-        uint16_t* nxt = planes_at(W.Q);
-        for (int i = 1; i < 7; ++i) {
-            const bool last = i == 6;
-            const int K = KERN[i] * C;
-            Out o{};
-            if (last) { o.Cf = ws + W.c6; o.sC = 0; }
-            else {
-                // (CONV_BIAS: + max |bias| of layer i)
-                if ((rc = launch_scale_from_bound(camax + (int64_t)(i - 1) * W.G, g, reinterpret_cast<const float*>(wstat(wstat_conv(i - 1))),
-                                                  sqrtf((float)K) * 1.00001f, conv_bias ? cb_max + i : nullptr, cscale + (int64_t)i * W.G, s))) return rc;
-                o.Cp = nxt; o.c_plane = (int64_t)W.G * T[i] * C; o.sCp = (int64_t)T[i] * C; o.sC = (int64_t)T[i] * C;
-                o.c_scale = cscale + (int64_t)i * W.G; o.cs_zs = 1; o.cs_ms = 0;
-            }
-            rc = gemm3(cur, (int64_t)W.G * T[i - 1] * C, (int64_t)STRD[i] * C, (int64_t)T[i - 1] * C, cscale + (int64_t)(i - 1) * W.G, 1, 0,
-                       planes_at(W.wp_conv[i - 1]), ws + W.ws_conv[i - 1], Tg[i], C, K, o, conv_bias ? cbias + (int64_t)i * C : nullptr,
-                       nullptr, g, ACT_GELU, "w2v2_gemm",
-                       false, last ? nullptr : camax + (int64_t)i * W.G, 1, nullptr, 0, ztab + ((int64_t)(i - 1) * n + g0) * 2);
-            if (rc) return rc;
-            std::swap(cur, nxt);
-        }
-    }
-    // 4. feature projection: LayerNorm (-> planes, exact row scales) + Linear; its epilogue reports max |x| per window
-    RSAF_CHECK_HIP(hipMemsetAsync(ws + W.fp_amax, 0, sizeof(unsigned) * n, s));
-    if (layer_norm)                                          // conv6's LayerNorm (eps 1e-5) + GELU first, in the same row pass
-        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true,
-                ws + W.s_lnfp, nullptr, nullptr, nullptr, nullptr, 2, cln + (int64_t)12 * C, cln + (int64_t)13 * C);
-    else                                                     // (NO_FEAT_PROJ_LN: the conv output itself, as planes)
-        rc = ln(ws + W.c6, nullptr, Wt + L.fplg, Wt + L.fplb, nullptr, rows, C, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.lnfp), true, ws + W.s_lnfp,
-                nullptr, nullptr, nullptr, nullptr, (c.flags & F_NO_FEAT_PROJ_LN) ? 3 : 0);
-    if (rc) return rc;
-    {
-        Out o{}; o.Cf = ws + W.x;
-        rc = gemm3(planes_at(W.lnfp), rows * C, C, 0, ws + W.s_lnfp, 0, 1, planes_at(W.wp_fp), ws + W.ws_fp, (int)rows, Hd, C, o,
-                   Wt + L.fpb, nullptr, 1, ACT_NONE, "w2v2_gemm", true, bits_at(W.fp_amax), 0, rowwin);
-        if (rc) return rc;
-    }
-    const int hd = Hd / c.NH;
-    const float scale = 1.0f / sqrtf((float)hd);
-    const bool fused = hd == 64 && Tt <= 256;  // attention on the fp16 matrix pipe, q / k / v as plane pairs
-    // REL_POS_BIAS: the gates come from the fp32 rows the q/k/v projection reads: x (post-LN), or LN1(h), which the
-    // stable-layer-norm LayerNorms then also write in fp32 into the att buffer (free until the attention writes it)
-    const bool relpos = c.flags & F_REL_POS_BIAS;
-    const float* reltab = relpos ? Wt + L.reltab : nullptr;
-    float* gate = relpos ? ws + W.gate : nullptr;
-    // 5. positional conv embedding (grouped, weight norm folded), GELU, x = LN(x + pos)
-    {
-        const int cg = Hd / c.PG;
-        const int TT = Tt + c.PK - 1;
-        const int64_t tot4 = (int64_t)n * TT * (Hd / 4);
-        if (cg % 16 == 0) {
-            // grouped conv as a two-level batched GEMM on the f16x3 kernel's 256 x 64 tile: batch (window, group), M = T_w rows
-            // (the regrouped sequence as k16 panels of T_w + PK - 1 rows: tap k = one row down), N = cg output channels, K = PK cg
-            const int64_t plane = (int64_t)n * TT * Hd;
-            {
-                ProfScope prof("w2v2_regroup", s, 0.0, (double)tot4 * 32);
-                hipLaunchKernelGGL(regroup_planes_kernel, dim3((unsigned)std::min<int64_t>((tot4 + 255) / 256, 4096)), dim3(256),
-                                   0, s, reinterpret_cast<const float4*>(ws + W.x), reinterpret_cast<unsigned short*>(planes_at(W.xg)),
-                                   plane, n, Tt, Hd / 4, c.PG, c.PK, Tw + (int64_t)6 * n, row0, bits_at(W.fp_amax), ws + W.pos_scale);
-                RSAF_CHECK_HIP(hipGetLastError());
-            }
-            const bool pc_off = [] { const char* e = getenv("RSAF_W2V2_POSCONV_GEMM"); return e && e[0] == '1'; }();   // per call: the tests toggle it
-            const int split = Tt <= PC_ROWS / 2 ? 2 : 1;
-            const bool resident = !pc_off && cg <= 64 && Tt <= PC_ROWS && (c.PK * (cg / 16)) % (4 * split) == 0 &&
-                                  posconv_lds_bytes(cg, c.PK, split) <= 160 * 1024;
-            if (resident) {
-                // the window's image stays in LDS (posconv_f16x3_kernel); RSAF_W2V2_POSCONV_GEMM=1: the batched GEMM below (A/B)
-                const int rows_alloc = posconv_rows_alloc(split, c.PK);
-                const size_t lds = posconv_lds_bytes(cg, c.PK, split);
-                ProfScope prof("w2v2_posconv_gemm", s, 2.0 * (double)rows * cg * (double)c.PK * cg * c.PG, 0.0);
-#define RSAF_PC_LAUNCH(NT_, SP_)                                                                                               \
-    do {                                                                                                                       \
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)posconv_f16x3_kernel<NT_, SP_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((posconv_f16x3_kernel<NT_, SP_>), dim3((unsigned)(n * c.PG)), dim3(512), lds, s,                    \
-                           reinterpret_cast<const unsigned short*>(planes_at(W.xg)), plane,                                    \
-                           reinterpret_cast<const unsigned short*>(planes_at(W.wp_pos)), (int64_t)Hd * c.PK * cg, Hd,          \
-                           ws + W.pos_scale, ws + W.ws_pos, Wt + L.posb, Tw + (int64_t)6 * n, row0, ws + W.y, c.PG, TT, c.PK,   \
-                           rows_alloc);                                                                                        \
-    } while (0)
-#define RSAF_PC_LAUNCH_NT(SP_)                                                                                                 \
-    switch (cg / 16) {                                                                                                         \
-        case 1: RSAF_PC_LAUNCH(1, SP_); break;                                                                                 \
-        case 2: RSAF_PC_LAUNCH(2, SP_); break;                                                                                 \
-        case 3: RSAF_PC_LAUNCH(3, SP_); break;                                                                                 \
-        default: RSAF_PC_LAUNCH(4, SP_); break;                                                                                \
-    }
-                if (split == 2) { RSAF_PC_LAUNCH_NT(2) } else { RSAF_PC_LAUNCH_NT(1) }
-#undef RSAF_PC_LAUNCH_NT
-#undef RSAF_PC_LAUNCH
-                RSAF_CHECK_HIP(hipGetLastError());
-            } else {
-            GemmH3Params p{};
-            p.A = planes_at(W.xg); p.a_plane = plane; p.lda = 16; p.sA = (int64_t)c.PG * TT * cg; p.sA2 = (int64_t)TT * cg;
-            p.a_panel = 1; p.a_panel_rows = TT; p.a_tap_panels = cg / 16;
-            p.a_scale = ws + W.pos_scale; p.a_scale_zs = 1; p.a_scale_ms = 0;
-            p.B = planes_at(W.wp_pos); p.b_plane = (int64_t)Hd * c.PK * cg; p.ldb = 16; p.b_panel = 1; p.b_panel_rows = Hd; p.sB2 = (int64_t)cg * 16;
-            p.b_scale = ws + W.ws_pos;
-            p.C = ws + W.y; p.ldc = Hd; p.sC = 0; p.sC2 = cg;
-            p.bias = Wt + L.posb; p.sBias2 = cg;
-            p.M = Tt; p.ztab = ztab + (int64_t)6 * n * 2; p.N = cg; p.K = c.PK * cg; p.nz = n * c.PG; p.nz2 = c.PG; p.act = ACT_GELU; p.alpha = 1.0f;
-            rc = launch_gemm_f16x3(p, s, "w2v2_posconv_gemm");
-            if (rc) return rc;
-            }
-        } else {
-            // group widths that are no multiple of 16 (test geometries): exact-fp32 GEMM, one launch per run of equal windows
-            for (const auto& tg : R.tgroups) {
-                const int nw = tg.second - tg.first, Tq = R.T6[tg.first], TTq = Tq + c.PK - 1;
-                const int64_t r0 = R.row0[tg.first];
-                const int64_t t4 = (int64_t)nw * TTq * (Hd / 4);
-                {
-                    ProfScope prof("w2v2_regroup", s, 0.0, (double)t4 * 32);
-                    hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)std::min<int64_t>((t4 + 255) / 256, 4096)), dim3(256),
-                                       0, s, reinterpret_cast<const float4*>(ws + W.x + r0 * Hd), reinterpret_cast<float4*>(ws + W.xg),
-                                       nw, Tq, Hd / 4, c.PG, c.PK);
-                    RSAF_CHECK_HIP(hipGetLastError());
-                }
-                GemmParams p = gemm_params_plain(ws + W.xg, Wt + L.posw, ws + W.y + r0 * Hd, Tq, cg, c.PK * cg, cg, (int64_t)c.PK * cg, Hd);
-                p.nz = nw * c.PG; p.nz2 = c.PG;
-                p.sA1 = (int64_t)c.PG * TTq * cg; p.sA2 = (int64_t)TTq * cg;
-                p.sB1 = 0; p.sB2 = (int64_t)cg * c.PK * cg;
-                p.sC1 = (int64_t)Tq * Hd; p.sC2 = cg;
-                p.bias = Wt + L.posb; p.sBias2 = cg; p.act = ACT_GELU;
-                rc = launch_gemm_f32(p, s, "w2v2_posconv_gemm");
-                if (rc) return rc;
-            }
-        }
-        // (fused attention: this LayerNorm also reports the window's largest row norm, behind the scale of layer 0's q / k / v)
-        if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
-        // (hidden_states[0]: the tap of this launch; PRE_LN the un-normalised h, post-LN the LayerNorm's output)
-        if (c.flags & F_PRE_LN)   // stable layer norm: h = x + pos stays un-normalised (the residual stream); layer 0's LN1(h) -> planes
-            rc = ln(ws + W.x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, relpos ? ws + W.att : nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0,
-                    planes_at(W.xp), true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 1, nullptr, nullptr,
-                    ws + W.x, tap(0), 2, out_row_start);
-        else
-            rc = ln(ws + W.x, ws + W.y, Wt + L.elng, Wt + L.elnb, ws + W.x, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp), true, ws + W.s_x,
-                    nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr, tap(0), 1, out_row_start);
-        if (rc) return rc;
-    }
-    // 6. encoder layers.  Post-LN: y = attn + x, x = LN1(y), y = ffn(x) + x, x = LN2(y).  PRE_LN (stable layer norm): the
-    //    residual stream h ping-pongs between x and y: y = attn(LN1(x)) + x, x = ffn(LN2(y)) + y, and the LayerNorms write
-    //    planes only (LN1 of the next layer, or encoder.layer_norm into `out` after the last one)
-    const bool pre_ln = c.flags & F_PRE_LN;
-    float* x = ws + W.x;
-    for (int l = 0; l < c.L; ++l) {
-        const LayerOff& lo = L.layers[l];
-        const int b0 = WSTAT_LAYER0 + WSTAT_PER_LAYER * l;
-        // fused q,k,v projection (A = the planes the previous LayerNorm wrote beside x).  Fused attention: the output leaves as
-        // the fp16 plane pair the attention kernel multiplies, under one power of two per window (the bound over its rows)
-        if (fused) {
-            hipLaunchKernelGGL(qkv_scale_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, s, bits_at(W.win_norm), rowwin, rows,
-                               wstat(b0), wstat(b0 + 5), ws + W.s_qkv);
-            RSAF_CHECK_HIP(hipGetLastError());
-            Out o{}; o.Cp = planes_at(W.qkv); o.c_plane = rows * 3 * Hd; o.c_scale = ws + W.s_qkv; o.cs_zs = 0; o.cs_ms = 1;
-            rc = gemm3(planes_at(W.xp), rows * Hd, Hd, 0, ws + W.s_x, 0, 1, planes_at(W.wp_qkv[l]), ws + W.ws_qkv[l], (int)rows, 3 * Hd, Hd, o,
-                       Wt + lo.bqkv, nullptr, 1, ACT_NONE, "w2v2_gemm", true);
-            if (rc) return rc;
-        } else {
-            Out o{}; o.Cf = ws + W.qkv;
-            rc = gemm3(planes_at(W.xp), rows * Hd, Hd, 0, ws + W.s_x, 0, 1, planes_at(W.wp_qkv[l]), ws + W.ws_qkv[l], (int)rows, 3 * Hd, Hd, o,
-                       Wt + lo.bqkv, nullptr, 1, ACT_NONE, "w2v2_gemm", true);
-            if (rc) return rc;
-        }
-        if (relpos) {
-            const int64_t items = rows * c.NH;
-            RSAF_CHECK_ARG((items + 15) / 16 <= 0x7fffffffLL, "too many rows");
-            ProfScope prof("w2v2_relpos_gate", s, 0.0, (double)rows * Hd * 4 + (double)items * 4);
-            hipLaunchKernelGGL(relpos_gate_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 2 * hd * sizeof(float), s,
-                               pre_ln ? ws + W.att : x, items, c.NH, hd, Wt + L.ga[l], Wt + L.gb[l], Wt + L.gbias[l], Wt + L.gconst[l], gate);
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        if (fused) {
-            // 2 x 2 T^2 hd flops per (chunk, head)
-            double att_flops = 0.0;
-            for (const auto& tg : R.tgroups) att_flops += 4.0 * (tg.second - tg.first) * c.NH * (double)R.T6[tg.first] * R.T6[tg.first] * hd;
-            ProfScope prof("w2v2_attn_fused", s, att_flops, 0.0);
-#define RSAF_ATTN(RP)                                                                                                          \
-    do {                                                                                                                       \
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_f16x3_kernel<RP>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * 128 * 64 * 2)); \
-        hipLaunchKernelGGL(attn_f16x3_kernel<RP>, dim3((unsigned)(n * c.NH), (unsigned)((Tt + 127) / 128)), dim3(256), 2 * 2 * 128 * 64 * 2, s, \
-                           planes_at(W.qkv), rows * 3 * Hd, planes_at(W.attp), rows * Hd, rows, Tw + (int64_t)6 * n, row0, c.NH, Hd, scale, \
-                           ws + W.s_qkv, gate, reltab);                                                                        \
-    } while (0)
-            if (relpos) RSAF_ATTN(true); else RSAF_ATTN(false);
-#undef RSAF_ATTN
-            RSAF_CHECK_HIP(hipGetLastError());
-        } else {
-        // three launches per run of equal windows (head widths other than 64: test geometries)
-        for (const auto& tg : R.tgroups) {
-            const int nw = tg.second - tg.first, Tq = R.T6[tg.first], Tpq = (int)pad4(Tq);
-            const int64_t r0 = R.row0[tg.first];
-            const float* qkvg = ws + W.qkv + r0 * 3 * Hd;
-        {   // S = scale * Q K^T per (chunk, head)
-            GemmParams p = gemm_params_plain(qkvg, qkvg + Hd, ws + W.S, Tq, Tq, hd, 3 * Hd, 3 * Hd, Tpq);
-            p.nz = nw * c.NH; p.nz2 = c.NH;
-            p.sA1 = (int64_t)Tq * 3 * Hd; p.sA2 = hd; p.sB1 = p.sA1; p.sB2 = hd;
-            p.sC1 = (int64_t)c.NH * Tq * Tpq; p.sC2 = (int64_t)Tq * Tpq;
-            p.alpha = scale;
-            rc = launch_gemm_f32(p, s, "w2v2_attn_gemm");
-            if (rc) return rc;
-        }
-        {
-            const int64_t srows = (int64_t)nw * c.NH * Tq;
-            ProfScope prof("w2v2_softmax", s, 0.0, (double)srows * Tpq * 8);
-#define RSAF_SOFTMAX(...)                                                                                                      \
-    hipLaunchKernelGGL((softmax_kernel<__VA_ARGS__>), dim3((unsigned)((srows + 3) / 4)), dim3(256), 0, s, ws + W.S, srows, Tq, Tpq, \
-                       gate, reltab, c.NH, r0)
-            if (Tpq <= 256) { if (relpos) RSAF_SOFTMAX(true, true); else RSAF_SOFTMAX(true); }
-            else { if (relpos) RSAF_SOFTMAX(false, true); else RSAF_SOFTMAX(false); }
-#undef RSAF_SOFTMAX
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        {   // O = P V per (chunk, head), V is [T, hd] with N contiguous
-            GemmParams p = gemm_params_plain(ws + W.S, qkvg + 2 * Hd, ws + W.att + r0 * Hd, Tq, hd, Tq, Tpq, 3 * Hd, Hd);
-            p.nz = nw * c.NH; p.nz2 = c.NH; p.b_kn = 1;
-            p.sA1 = (int64_t)c.NH * Tq * Tpq; p.sA2 = (int64_t)Tq * Tpq;
-            p.sB1 = (int64_t)Tq * 3 * Hd; p.sB2 = hd;
-            p.sC1 = (int64_t)Tq * Hd; p.sC2 = hd;
-            rc = launch_gemm_f32(p, s, "w2v2_attn_gemm");
-            if (rc) return rc;
-        }
-        }
-            // (the fused kernel writes the planes itself)
-            if ((rc = launch_f16x2_row_scales(ws + W.att, rows, Hd, Hd, ws + W.s_att, nullptr, nullptr, s))) return rc;
-            rc = launch_split_f16x2(ws + W.att, rows, Hd, Hd, ws + W.s_att, 1, planes_at(W.attp), rows * Hd, 1, s);
-            if (rc) return rc;
-        }
-        {   // y = attn Wo^T + bo + x ; x = LN(y), with the bound behind the scale of the ffn1 output
-            Out o{}; o.Cf = ws + W.y;
-            rc = gemm3(planes_at(W.attp), rows * Hd, Hd, 0, fused ? ws + W.s_qkv : ws + W.s_att, 0, 1, planes_at(W.wp_o[l]), ws + W.ws_o[l], (int)rows, Hd, Hd, o,
-                       Wt + lo.bo, x, 1, ACT_NONE, "w2v2_gemm", true);
-            if (rc) return rc;
-            if (pre_ln)
-                rc = ln(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, nullptr, rows, Hd, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.xp), true,
-                        ws + W.s_x, wstat(b0 + 2), wstat(b0 + 4), ws + W.s_ffn);
-            else
-                rc = ln(ws + W.y, nullptr, Wt + lo.ln1g, Wt + lo.ln1b, x, rows, Hd, c.eps, s, nullptr, nullptr, nullptr, planes_at(W.xp), true, ws + W.s_x,
-                        wstat(b0 + 2), wstat(b0 + 4), ws + W.s_ffn);
-            if (rc) return rc;
-        }
-        {   // feed forward: the GELU output only exists as planes (A of the second GEMM)
-            Out o1{}; o1.Cp = planes_at(W.ffnp); o1.c_plane = rows * c.I; o1.c_scale = ws + W.s_ffn; o1.cs_zs = 0; o1.cs_ms = 1; o1.cp_panel = true;
-            rc = gemm3(planes_at(W.xp), rows * Hd, Hd, 0, ws + W.s_x, 0, 1, planes_at(W.wp_1[l]), ws + W.ws_1[l], (int)rows, c.I, Hd, o1,
-                       Wt + lo.b1, nullptr, 1, ACT_GELU, "w2v2_gemm", true);
-            if (rc) return rc;
-            Out o2{}; o2.Cf = pre_ln ? x : ws + W.y;
-            rc = gemm3(planes_at(W.ffnp), rows * c.I, c.I, 0, ws + W.s_ffn, 0, 1, planes_at(W.wp_2[l]), ws + W.ws_2[l], (int)rows, Hd, c.I, o2,
-                       Wt + lo.b2, pre_ln ? ws + W.y : x, 1, ACT_NONE, "w2v2_gemm", true);
-            if (rc) return rc;
-            const bool last = (l == c.L - 1);
-            if (pre_ln) {
-                // hidden_states[l + 1]: the residual stream h read by the next layer's LN1 (un-normalised), or, after the last
-                // layer, encoder.layer_norm's output (= out)
-                if (last) {
-                    rc = ln(x, nullptr, Wt + L.elng, Wt + L.elnb, out, rows, Hd, c.eps, s, out_row_start, rowwin, row0, nullptr, false,
-                            nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, tap(l + 1), 1, out_row_start);
-                } else {
-                    if (fused) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
-                    const LayerOff& ln_next = L.layers[l + 1];
-                    rc = ln(x, nullptr, Wt + ln_next.ln1g, Wt + ln_next.ln1b, relpos ? ws + W.att : nullptr, rows, Hd, c.eps, s, nullptr, rowwin, row0, planes_at(W.xp),
-                            true, ws + W.s_x, nullptr, nullptr, nullptr, fused ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr,
-                            tap(l + 1), 2, out_row_start);
-                }
-                if (rc) return rc;
-                continue;
-            }
-            // the last LayerNorm writes frame t of window w at out_row_start[w] + t (or packed, window after window);
-            // hidden_states[l + 1] is this LayerNorm's output
-            if (fused && !last) RSAF_CHECK_HIP(hipMemsetAsync(ws + W.win_norm, 0, sizeof(unsigned) * n, s));
-            rc = ln(ws + W.y, nullptr, Wt + lo.ln2g, Wt + lo.ln2b, last ? out : x, rows, Hd, c.eps, s,
-                    last ? out_row_start : nullptr, rowwin, row0, last ? nullptr : planes_at(W.xp), true, ws + W.s_x,
-                    nullptr, nullptr, nullptr, (fused && !last) ? bits_at(W.win_norm) : nullptr, 0, nullptr, nullptr, nullptr,
-                    tap(l + 1), 1, out_row_start);
-            if (rc) return rc;
-        }
-    }
-    return RSAF_OK;
-}
