@@ -250,6 +250,30 @@ int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, 
 int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels,
                                       int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
 
+/* ---- Group inference forward: K independent eval-mode forwards of one architecture in one call -----------------
+ * The other half of the reference's loops: the validation pass of every epoch (src/dl_cv_strategies.py:131-139) and
+ * _eval_model (:183-194).  No weight changes between the batches of such a pass, so every batch of every model is an
+ * independent forward.  A group call runs rsaf_cnnlstm_forward for K of them (own batch of own shape B x T, own
+ * workspace, own logits) on one stream, with the LSTM recurrences of all items in ONE launch per layer and the
+ * attention pooling + classifier of all items in ONE launch; everything else runs per item.  The logits are those of
+ * K single calls, bit for bit.  Every field means what the argument of the same name means in rsaf_cnnlstm_forward;
+ * workspace size per item from rsaf_cnnlstm_workspace_bytes.  Items may share `weights` (several batches of one
+ * model): the fp16 plane pairs of the weights are then prepared once, in the workspace of the first item that carries
+ * the blob, and the later items read them there.  All checks of the single entry apply per item (with B >= 1), plus
+ * 1 <= K <= RSAF_CNNLSTM_GROUP_MAX and no two items overlapping in workspace or logits; they all run before the first
+ * launch, and rsaf_last_error() names the item.  An item whose batch exceeds the 4-row recurrence threshold
+ * (RSAF_LSTM_SMALL_MAX, default 1 024) has its recurrences launched on its own. */
+typedef struct {
+    const float* x;
+    int B, T;
+    const float* weights;
+    void* workspace;
+    int64_t workspace_bytes;
+    float* logits;
+} rsaf_cnnlstm_forward_item;
+int rsaf_cnnlstm_forward_group(const rsaf_cnnlstm_forward_item* items_host, int K, int input_dim, int channels,
+                               int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
+
 /* ---- Wav2Vec2 frame embeddings for a batch of equal-length chunks -----------------------------------
  * Replaces, per chunk, `processor(chunk).input_values` + `Wav2Vec2Model(...)(input_values)
  * .last_hidden_state` (src/foundation_model_extractor.py:113-116; third-party transformers

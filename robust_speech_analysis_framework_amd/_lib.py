@@ -35,6 +35,11 @@ class TrainItem(C.Structure):
                 ("scratch_floats", _L), ("logits", _P), ("bn_stats_out", _P), ("dlogits", _P), ("grads", _P)]
 
 
+class ForwardItem(C.Structure):
+    """``rsaf_cnnlstm_forward_item``: one eval-mode forward of a group call."""
+    _fields_ = [("x", _P), ("B", _I), ("T", _I), ("weights", _P), ("workspace", _P), ("workspace_bytes", _L), ("logits", _P)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -71,6 +76,7 @@ SIGNATURES = {
     "rsaf_cnnlstm_train_group_max": (_I, []),
     "rsaf_cnnlstm_train_forward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_cnnlstm_train_backward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_forward_group": (_I, [C.POINTER(ForwardItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),
     "rsaf_mshds_intensity": (_I, [_P, _P, _I, _I, _P, _I, C.c_double, _I, _P, _P, _P]),

@@ -16,6 +16,7 @@ Training: in ``model.train()`` mode ``forward`` runs ``r
 """
 from __future__ import annotations
 
+import copy
 import ctypes as C
 
 import numpy as np
@@ -479,6 +480,9 @@ def eval_outputs(logits):
 # keeps 2 of the chip's 256 CUs busy during its LSTM recurrences, which are most of the step; K of them side by side
 # put the recurrences of all replicas into one launch per layer and pass (``rsaf_cnnlstm_train_forward_group`` /
 # ``_backward_group``).  Everything else runs per replica, so the results are those of K separate steps, bit for bit.
+# The eval-mode half of the same loops (the validation pass of every epoch, ``:131-139``; ``_eval_model``, ``:183-194``)
+# is grouped further below (``cnnlstm_forward_group``): there every batch of every model is an item of its own, since no
+# weight changes during a pass.
 
 def train_group_max():
     """Replicas per C call (``rsaf_cnnlstm_train_group_max``); longer lists are split into chunks of this size."""
@@ -615,10 +619,94 @@ def cnnlstm_train_group(models, xs, masks=None):
     return list(_TrainGroupStep.apply(models, xs, mks, *params))
 
 
+# ---- group eval forward: K independent eval-mode forwards of one architecture in one call --------------------------------
+# ``rsaf_cnnlstm_forward_group``: the recurrences of all items in one launch per layer, their heads in one launch, the
+# fp16 planes of the weights once per distinct model; everything else per item.  The logits are those of ``model(x)``,
+# bit for bit.
+
+_group_workspace = {}               # device -> cached workspace tensor of the group calls (grown on demand)
+_WS_ALIGN = 256                     # bytes between the items' slices
+
+
+def _group_forward_chunk(lib, items, dims, act, device):
+    """One C call: ``items`` = [(x, blob)] with B >= 1 -> list of logits (views of one tensor)."""
+    a = (dims["input_dim"], dims["channels"], dims["hidden"], dims["layers"])
+    needs = [int(lib.rsaf_cnnlstm_workspace_bytes(x.shape[0], x.shape[1], *a)) for x, _ in items]
+    offs, total = [], 0
+    for n in needs:
+        offs.append(total)
+        total += (n + _WS_ALIGN - 1) // _WS_ALIGN * _WS_ALIGN
+    ws = _group_workspace.get(str(device))
+    if ws is None or ws.numel() * 4 < total:
+        ws = _group_workspace[str(device)] = torch.empty(total // 4, dtype=torch.float32, device=device)
+    nc = dims["num_classes"]
+    rows = [x.shape[0] for x, _ in items]
+    logits = torch.empty((sum(rows), nc), dtype=torch.float32, device=device)
+    arr = (_lib.ForwardItem * len(items))()
+    r0 = 0
+    for it, (x, blob), n, off, B in zip(arr, items, needs, offs, rows):
+        it.x, it.B, it.T, it.weights = x.data_ptr(), B, x.shape[1], blob.data_ptr()
+        it.workspace, it.workspace_bytes = ws.data_ptr() + off, n
+        it.logits = logits.data_ptr() + r0 * nc * 4
+        r0 += B
+    _lib.check(lib.rsaf_cnnlstm_forward_group(arr, len(items), dims["input_dim"], dims["channels"], dims["hidden"], nc,
+                                              dims["layers"], _ACT_CODE[act], _lib.stream_ptr(None)),
+               "rsaf_cnnlstm_forward_group")
+    return list(torch.split(logits, rows))
+
+
+def cnnlstm_forward_group(models, xs):
+    """Eval-mode forward of the pairs ``(models[i], xs[i])`` (same ``dims`` and activation; ``xs[i]`` of own shape
+    [B_i, T_i, D]) under ``no_grad`` -> list of logits tensors, each equal to ``models[i](xs[i])`` bit for bit.  ``models``
+    may name the same module several times (the batches of one validation loader): its weights are packed and split
+    once.  Lists longer than ``train_group_max()`` are split into chunks of that size."""
+    models, xs = list(models), list(xs)
+    if not models:
+        raise ValueError("cnnlstm_forward_group needs at least one (model, input) pair")
+    if len(models) != len(xs):
+        raise ValueError(f"{len(models)} models but {len(xs)} inputs")
+    first = models[0]
+    for k, m in enumerate(models):
+        if m.dims != first.dims or m.activation_name != first.activation_name:
+            raise ValueError(f"replica {k} differs from replica 0: dims {m.dims} / activation {m.activation_name!r} against "
+                             f"{first.dims} / {first.activation_name!r}")
+        if m.training:
+            raise ValueError(f"replica {k} is in training mode: the group forward is the inference forward (model.eval())")
+    D = first.dims["input_dim"]
+    for k, x in enumerate(xs):
+        if x.dim() != 3 or x.shape[2] != D:
+            raise ValueError(f"replica {k}: expected input [B, T, {D}], got {tuple(x.shape)}")
+        if x.shape[0] > 0 and x.shape[1] < 2:
+            raise ValueError(f"replica {k}: sequence length must be >= 2")
+    for k, x in enumerate(xs):
+        if not x.is_cuda:
+            raise _lib.RsafError(f"cnnlstm_forward_group needs HIP (cuda) tensors (replica {k}): there is no CPU fallback")
+    lib = _lib.load()
+    gmax = train_group_max()
+    device = xs[0].device
+    with torch.no_grad():
+        blobs = {}
+        for m in models:
+            if id(m) not in blobs:
+                blobs[id(m)] = m.packed_weights(device)
+        xs = [x.detach().to(torch.float32).contiguous() for x in xs]
+        outs = [None] * len(xs)
+        live = [k for k, x in enumerate(xs) if x.shape[0] > 0]
+        for k in range(len(xs)):
+            if xs[k].shape[0] == 0:
+                outs[k] = torch.empty((0, first.dims["num_classes"]), dtype=torch.float32, device=device)
+        for c0 in range(0, len(live), gmax):
+            chunk = live[c0:c0 + gmax]
+            got = _group_forward_chunk(lib, [(xs[k], blobs[id(models[k])]) for k in chunk], first.dims, first.activation_name, device)
+            for k, o in zip(chunk, got):
+                outs[k] = o
+    return outs
+
+
 class CNNLSTMGroup(nn.Module):
     """K ``CNNLSTM`` replicas of one architecture that train side by side.  ``forward(xs)`` takes one batch per replica
     (``None``: the replica sits out and its output is ``None``): in training mode the group step over the others, in
-    eval mode each model's own inference forward.  ``state_dict`` keys are ``models.<k>.<reference key>``, so a
+    eval mode the group inference forward over them (``cnnlstm_forward_group``).  ``state_dict`` keys are ``models.<k>.<reference key>``, so a
     replica's weights load into a plain ``CNNLSTM``."""
 
     def __init__(self, models):
@@ -640,9 +728,9 @@ class CNNLSTMGroup(nn.Module):
             if live:
                 for k, o in zip(live, cnnlstm_train_group([self.models[k] for k in live], [xs[k] for k in live])):
                     outs[k] = o
-        else:
-            for k in live:
-                outs[k] = self.models[k](xs[k])
+        elif live:
+            for k, o in zip(live, cnnlstm_forward_group([self.models[k] for k in live], [xs[k] for k in live])):
+                outs[k] = o
         return outs
 
 
@@ -688,3 +776,114 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
         for k in range(len(models)):
             histories[k].append(total[k] / max(count[k], 1))
     return histories
+
+
+def _grouped_eval_batches(pairs, device):
+    """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models -> yields ``(tag, logits, lab on the device)``
+    in the same order, the forwards pooled into group calls of up to ``train_group_max()`` batches.  The batches stay as
+    collated: zero padding is not masked (``src/dl_cv_strategies.py:81-84``), so regrouping sequences would change the
+    results."""
+    gmax = train_group_max()
+    pend = []
+
+    def flush():
+        outs = cnnlstm_forward_group([p[1] for p in pend], [p[2] for p in pend])
+        res = [(p[0], o, p[3]) for p, o in zip(pend, outs)]
+        pend.clear()
+        return res
+
+    for tag, model, seq, lab in pairs:
+        pend.append((tag, model, seq.to(device), lab.to(device)))
+        if len(pend) == gmax:
+            yield from flush()
+    if pend:
+        yield from flush()
+
+
+def eval_replicas_lockstep(models, loaders, device):
+    """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) for K models over K loaders: all (model, batch) pairs are
+    pooled into group calls.  Returns K triples ``(labels, preds, probs)`` of NumPy arrays in loader order, equal to
+    what the reference's loop returns model by model; the results of a replica come to the host in one copy each."""
+    models, loaders = list(models), list(loaders)
+    if len(models) != len(loaders):
+        raise ValueError(f"{len(models)} models but {len(loaders)} loaders")
+    for m in models:
+        m.eval()
+    parts = [([], [], []) for _ in models]
+    with torch.no_grad():
+        pairs = ((k, m, seq, lab) for k, (m, ld) in enumerate(zip(models, loaders)) for seq, lab in ld)
+        for k, out, lab in _grouped_eval_batches(pairs, device):
+            prob, pred = eval_outputs(out)
+            for lst, v in zip(parts[k], (lab, pred, prob)):
+                lst.append(v)
+    res = []
+    for labs, preds, probs in parts:
+        if not labs:
+            res.append((np.array([]), np.array([]), np.array([])))
+            continue
+        res.append(tuple(torch.cat(v).cpu().numpy() for v in (labs, preds, probs)))
+    return res
+
+
+def eval_model_grouped(model, data_loader, device):
+    """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) with all batches of the loader as items of group calls:
+    ``(labels, preds, probs)`` as NumPy arrays in loader order."""
+    return eval_replicas_lockstep([model], [data_loader], device)[0]
+
+
+def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, val_loaders, loss_fn, epochs, patience, device):
+    """``_train_eval_loop`` (``src/dl_cv_strategies.py:112-165``) for K replicas: per epoch the training pass of
+    ``train_replicas_lockstep`` over the replicas still running, then the validation pass of all of them in group calls
+    (``val_loss`` accumulated batch by batch in loader order; the losses of a pass come to the host in one copy), then per
+    replica ``scheduler.step(avg_val_loss)`` (``schedulers[k]`` may be ``None``), best-weights checkpointing and early
+    stopping as the reference does them.  A replica that stopped early sits out of the later epochs.  Returns
+    ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded."""
+    models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
+    train_loaders, val_loaders = list(train_loaders), list(val_loaders)
+    K = len(models)
+    if not (K == len(optimizers) == len(schedulers) == len(train_loaders) == len(val_loaders)):
+        raise ValueError(f"{K} models, {len(optimizers)} optimizers, {len(schedulers)} schedulers, {len(train_loaders)} training "
+                         f"loaders and {len(val_loaders)} validation loaders")
+    train_hist, val_hist = [[] for _ in models], [[] for _ in models]
+    best_val_loss = [float("inf")] * K
+    epochs_no_improve = [0] * K
+    best_model_weights = [None] * K
+    running = list(range(K))
+    for _ in range(epochs):
+        if not running:
+            break
+        hist = train_replicas_lockstep([models[k] for k in running], [optimizers[k] for k in running],
+                                       [train_loaders[k] for k in running], loss_fn, 1, device)
+        for k, h in zip(running, hist):
+            train_hist[k].append(h[0])
+        for k in running:
+            models[k].eval()
+        tags, losses = [], []
+        with torch.no_grad():
+            pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
+            for k, out, lab in _grouped_eval_batches(pairs, device):
+                tags.append(k)
+                losses.append(loss_fn(out, lab))
+        val_loss, count = {k: 0 for k in running}, {k: 0 for k in running}
+        for k, v in zip(tags, torch.stack(losses).tolist() if losses else []):
+            val_loss[k] += v
+            count[k] += 1
+        still = []
+        for k in running:
+            avg_val_loss = val_loss[k] / count[k]
+            val_hist[k].append(avg_val_loss)
+            if schedulers[k] is not None:
+                schedulers[k].step(avg_val_loss)
+            if avg_val_loss < best_val_loss[k]:
+                best_val_loss[k] = avg_val_loss
+                best_model_weights[k] = copy.deepcopy(models[k].state_dict())
+                epochs_no_improve[k] = 0
+            else:
+                epochs_no_improve[k] += 1
+            if epochs_no_improve[k] < patience:
+                still.append(k)
+        running = still
+    for k in range(K):
+        if best_model_weights[k]:
+            models[k].load_state_dict(best_model_weights[k])
+    return [(models[k], train_hist[k], val_hist[k]) for k in range(K)]

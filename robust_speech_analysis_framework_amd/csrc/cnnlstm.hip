@@ -19,6 +19,7 @@
 // register index), h_t goes to LDS (double-buffered, one barrier per step) and to HBM.
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 
 #include "cnnlstm_kernels.h"
 #include "gemm_f32.h"
@@ -324,14 +325,14 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_group_kernel(const Lstm
 }
 
 // ---- attention pooling (softmax over time) + final Linear -----------------------------------------
+// The body is shared by the one-batch kernel and the group kernel below: `b` (the batch row) is what blockIdx.x is to both.
 template <int NF>   // features per lane: 2H = 64*NF
-__global__ __launch_bounds__(256) void attnpool_fc_kernel(const float* __restrict__ seq, const float* __restrict__ watt,
-                                                          const float* __restrict__ batt, const float* __restrict__ wfc,
-                                                          const float* __restrict__ bfc, float* __restrict__ logits,
-                                                          float* __restrict__ pooled_out, int T, int NC) {
+__device__ __forceinline__ void attnpool_fc_body(const float* __restrict__ seq, const float* __restrict__ watt,
+                                                 const float* __restrict__ batt, const float* __restrict__ wfc,
+                                                 const float* __restrict__ bfc, float* __restrict__ logits,
+                                                 float* __restrict__ pooled_out, int T, int NC, int b) {
     constexpr int F = 64 * NF;
     __shared__ float s_m[4], s_l[4], s_ctx[4][F], s_red[4][16];
-    const int b = blockIdx.x;
     const int lane = threadIdx.x & 63;
     const int w = threadIdx.x >> 6;
     const float* sb = seq + (int64_t)b * T * F;
@@ -382,6 +383,24 @@ __global__ __launch_bounds__(256) void attnpool_fc_kernel(const float* __restric
         logits[(int64_t)b * NC + threadIdx.x] =
             s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x] +
             bfc[threadIdx.x];
+}
+
+template <int NF>
+__global__ __launch_bounds__(256) void attnpool_fc_kernel(const float* __restrict__ seq, const float* __restrict__ watt,
+                                                          const float* __restrict__ batt, const float* __restrict__ wfc,
+                                                          const float* __restrict__ bfc, float* __restrict__ logits,
+                                                          float* __restrict__ pooled_out, int T, int NC) {
+    attnpool_fc_body<NF>(seq, watt, batt, wfc, bfc, logits, pooled_out, T, NC, blockIdx.x);
+}
+
+// The heads of several independent forwards (same H and NC; own sequences, own weights, own B and T) in one launch: grid
+// (max B, K), blockIdx.y selects the descriptor, which travels by value in the kernel arguments like the recurrences' above.
+// A workgroup whose row lies beyond its item's batch leaves before it touches LDS or a barrier.
+template <int NF>
+__global__ __launch_bounds__(256) void attnpool_fc_group_kernel(const AttnPoolGroup g, int NC) {
+    const AttnPoolItem& it = g.item[blockIdx.y];
+    if ((int)blockIdx.x >= it.B) return;
+    attnpool_fc_body<NF>(it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits, it.pooled_out, it.T, NC, blockIdx.x);
 }
 
 }  // namespace cnnlstm
@@ -636,42 +655,175 @@ static F16Ws make_f16_ws(const Dims& d, int B, int T) {
     return w;
 }
 
-static int forward_f16x3(const float* x, int B, int T, const Dims& d, const Layout& L, const float* W, float* ws, float* f16base,
-                         float* logits, float* res1_out, float* res2_out, float* lstm_out, float* pooled_out, hipStream_t s) {
-    int rc = RSAF_OK;
-    const int D = d.D, C = d.C, H = d.H, Tp = T / 2;
-    const int64_t conv = pad4((int64_t)B * T * C);
-    float* bufA = ws;
-    float* bufB = ws + conv;
-    float* bufC = ws + 2 * conv;
-    float* xproj = ws + 3 * conv;
-    float* seq0 = xproj + pad4((int64_t)B * Tp * 8 * H);
-    float* seq1 = seq0 + pad4((int64_t)B * Tp * 2 * H);
-    const F16Ws F = make_f16_ws(d, B, T);
-    auto planes = [&](int64_t off) { return reinterpret_cast<uint16_t*>(f16base + off); };
-    unsigned* stat = reinterpret_cast<unsigned*>(f16base + F.stat);          // [CNN_NSTAT][2]: {max row norm, max |element|}
-    unsigned* amax = reinterpret_cast<unsigned*>(f16base + F.amax);          // [6][B]: x, shortcut, conv1, conv2, conv3, (spare)
-    float* scale = f16base + F.scale;                                       // [6][B]: x, conv1, pooled, conv3, conv4, (spare)
-    float* one = f16base + F.one;
-    enum { AX = 0, ASC = 1, AC1 = 2, AC2 = 3, AC3 = 4, AC4 = 5 };
-    enum { SX = 0, SC1 = 1, SPOOL = 2, SC3 = 3, SC4 = 4 };
+#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
+
+// ---- one forward, cut at its recurrences into phases -------------------------------------------------------------------
+//   prep_weights (f16x3 path: the weights as plane pairs, once per distinct blob) | front (CNN + layer-0 input projection)
+//   | per layer: recurrence, inproj of the next layer | head.
+// The single entries run the phases of their one forward with the one-batch launchers; the group entry runs every phase for
+// all items, one grouped recurrence launch per layer in between and one grouped head.  Per item these are the same kernels
+// with the same launch parameters in the same order, so the logits are those of K single calls, bit for bit.
+struct Fwd {
+    const float* x; int B, T;
+    const float* W;
+    float* logits;
+    float *res1_out, *res2_out, *lstm_out, *pooled_out;     // stage taps (rsaf_cnnlstm_forward_stages), else NULL
+    float *bufA, *bufB, *bufC, *xproj, *seq0, *seq1;        // fp32 buffers of the workspace
+    // f16x3 path: own activation planes, amax and scale | the weight planes, row scales, statistics and `one`, which live
+    // in this item's workspace (prep) or in that of the first item of the group that carries the same `weights`
+    bool f16, prep;
+    float* f16base; F16Ws F;
+    float* wbase; F16Ws WF;
+    const float* lin;               // input of the next LSTM layer
+    float* lout;                    // output buffer of the next recurrence
+};
+
+enum { AX = 0, ASC = 1, AC1 = 2, AC2 = 3, AC3 = 4, AC4 = 5 };   // amax [6][B]: x, shortcut, conv1, conv2, conv3, conv4
+enum { SX = 0, SC1 = 1, SPOOL = 2, SC3 = 3, SC4 = 4 };          // scale [6][B]: x, conv1, pooled, conv3, conv4, (spare)
+
+static uint16_t* planes_at(float* base, int64_t off) { return reinterpret_cast<uint16_t*>(base + off); }
+
+static int fail(int code, const char* who, int idx, const std::string& msg) {
+    set_error(std::string(who) + ": " + (idx >= 0 ? "item " + std::to_string(idx) + ": " : std::string()) + msg);
+    return code;
+}
+
+// argument checks of one forward (idx < 0: the single entries, whose messages carry no item) and its buffers
+static int check_item(const Dims& d, const float* x, int B, int T, const float* weights, void* workspace, int64_t workspace_bytes,
+                      float* logits, const char* who, int idx, Fwd* f) {
+    if (!(B >= 1 && B <= 65535)) return fail(RSAF_ERR_ARG, who, idx, "batch must be in [1, 65535]");
+    if (!(T >= 2)) return fail(RSAF_ERR_ARG, who, idx, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
+    if (!((int64_t)B * (T / 2) <= 0x7fffffffLL)) return fail(RSAF_ERR_ARG, who, idx, "B*T too large");
+    if (!(x && weights && workspace && logits)) return fail(RSAF_ERR_ARG, who, idx, "NULL pointer");
+    if (workspace_bytes < rsaf_cnnlstm_workspace_bytes(B, T, d.D, d.C, d.H, d.L)) return fail(RSAF_ERR_WORKSPACE, who, idx, "workspace too small");
+    *f = Fwd{};
+    f->x = x; f->B = B; f->T = T; f->W = weights; f->logits = logits;
+    const int Tp = T / 2;
+    float* ws = static_cast<float*>(workspace);
+    const int64_t conv = pad4((int64_t)B * T * d.C);
+    f->bufA = ws;
+    f->bufB = ws + conv;
+    f->bufC = ws + 2 * conv;
+    f->xproj = ws + 3 * conv;
+    f->seq0 = f->xproj + pad4((int64_t)B * Tp * 8 * d.H);
+    f->seq1 = f->seq0 + pad4((int64_t)B * Tp * 2 * d.H);
+    f->f16 = use_f16x3(d.D, d.C);
+    if (f->f16) {
+        f->f16base = f->seq1 + pad4((int64_t)B * Tp * 2 * d.H);
+        f->F = make_f16_ws(d, B, T);
+        f->prep = true; f->wbase = f->f16base; f->WF = f->F;
+    }
+    return RSAF_OK;
+}
+
+static bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
+    const char *p = static_cast<const char*>(a), *q = static_cast<const char*>(b);
+    return p < q + nb && q < p + na;
+}
+
+// weights -> plane pairs in k16 panels with their row scales; statistics {max row norm, max |element|}: matrix i at slot i,
+// its bias at slot 5 + i, wih[l] at slot 10 + l.  A pure function of the blob.
+static int prep_weights(const Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
+    const int D = d.D, C = d.C, H = d.H;
+    const float* W = f.W;
+    const F16Ws& F = f.WF;
+    float* base = f.wbase;
+    unsigned* stat = reinterpret_cast<unsigned*>(base + F.stat);
+    float* one = base + F.one;
     RSAF_CHECK_HIP(hipMemsetAsync(stat, 0, sizeof(unsigned) * 2 * CNN_NSTAT, s));
-    RSAF_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(unsigned) * CNN_NAMAX * B, s));
-    // weights -> plane pairs in k16 panels with their row scales; statistics: matrix i at slot i, its bias at slot 5 + i
     const int64_t woff[5] = {L.w1, L.wsc, L.w2, L.w3, L.w4}, boff[5] = {L.b1, L.bsc, L.b2, L.b3, L.b4};
     const int wk[5] = {3 * D, D, 3 * C, 3 * C, 3 * C};
     for (int i = 0; i < 5; ++i) {
         if (woff[i] < 0) continue;                                          // no 1x1 shortcut when D == C
-        if ((rc = launch_f16x2_row_scales(W + woff[i], C, wk[i], wk[i], f16base + F.ws[i], nullptr, stat + 2 * i, s))) return rc;
-        if ((rc = launch_split_f16x2(W + woff[i], C, wk[i], wk[i], f16base + F.ws[i], 1, planes(F.wp[i]), (int64_t)C * wk[i], 1, s))) return rc;
-        if ((rc = launch_f16x2_row_scales(W + boff[i], 1, C, C, one, nullptr, stat + 2 * (5 + i), s))) return rc;
+        TRY(launch_f16x2_row_scales(W + woff[i], C, wk[i], wk[i], base + F.ws[i], nullptr, stat + 2 * i, s));
+        TRY(launch_split_f16x2(W + woff[i], C, wk[i], wk[i], base + F.ws[i], 1, planes_at(base, F.wp[i]), (int64_t)C * wk[i], 1, s));
+        TRY(launch_f16x2_row_scales(W + boff[i], 1, C, C, one, nullptr, stat + 2 * (5 + i), s));
     }
     for (int l = 0; l < d.L; ++l) {
         const int in = l == 0 ? C : 2 * H;
-        if ((rc = launch_f16x2_row_scales(W + L.wih[l], 8 * H, in, in, f16base + F.wih_s[l], nullptr, stat + 2 * (10 + l), s))) return rc;
-        if ((rc = launch_split_f16x2(W + L.wih[l], 8 * H, in, in, f16base + F.wih_s[l], 1, planes(F.wih_p[l]), (int64_t)8 * H * in, 1, s))) return rc;
+        TRY(launch_f16x2_row_scales(W + L.wih[l], 8 * H, in, in, base + F.wih_s[l], nullptr, stat + 2 * (10 + l), s));
+        TRY(launch_split_f16x2(W + L.wih[l], 8 * H, in, in, base + F.wih_s[l], 1, planes_at(base, F.wih_p[l]), (int64_t)8 * H * in, 1, s));
     }
     RSAF_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(one), 0x46800000, 1, s));   // 16384.0f: |h| < 1 for every LSTM output
+    return RSAF_OK;
+}
+
+// input projection of layer l for all time steps, into xproj
+static int inproj(Fwd& f, const Dims& d, const Layout& L, int l, hipStream_t s) {
+    const int B = f.B, C = d.C, H = d.H, Tp = f.T / 2;
+    const int in = l == 0 ? C : 2 * H;
+    const int64_t rows = (int64_t)B * Tp;
+    if (!f.f16) {
+        GemmParams p = gemm_params_plain(f.lin, f.W + L.wih[l], f.xproj, (int)rows, 8 * H, in, in, in, 8 * H);
+        p.bias = f.W + L.bih[l];
+        return launch_gemm_f32(p, s, "lstm_inproj_gemm");
+    }
+    // layer 0 reads conv4's planes (one scale per sequence), the layers behind it the plane pair of the previous layer's
+    // output under the fixed scale 2^14
+    float* one = f.wbase + f.WF.one;
+    GemmH3Params p{};
+    p.B = planes_at(f.wbase, f.WF.wih_p[l]); p.b_plane = (int64_t)8 * H * in; p.ldb = 16; p.b_panel = 1; p.b_scale = f.wbase + f.WF.wih_s[l];
+    p.C = f.xproj; p.ldc = 8 * H; p.bias = f.W + L.bih[l]; p.N = 8 * H; p.K = in; p.act = ACT_NONE; p.alpha = 1.0f;
+    if (l == 0) {
+        p.A = planes_at(f.f16base, f.F.c4p); p.a_plane = (int64_t)B * Tp * C; p.lda = C; p.sA = (int64_t)Tp * C;
+        p.a_scale = f.f16base + f.F.scale + SC4 * B; p.a_scale_zs = 1; p.a_scale_ms = 0;
+        p.M = Tp; p.nz = B; p.sC = (int64_t)Tp * 8 * H;
+    } else {
+        TRY(launch_split_f16x2(f.lin, rows, in, in, one, 0, planes_at(f.f16base, f.F.hp), rows * in, 1, s));
+        p.A = planes_at(f.f16base, f.F.hp); p.a_plane = rows * in; p.lda = 16; p.a_panel = 1;
+        p.a_scale = one; p.a_scale_zs = 0; p.a_scale_ms = 0;
+        p.M = (int)rows; p.nz = 1;
+    }
+    return launch_gemm_f16x3(p, s, "lstm_inproj_gemm");
+}
+
+// the two residual blocks on the exact-fp32 MFMA GEMM
+static int front_f32(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
+    const int B = f.B, T = f.T, D = d.D, C = d.C, Tp = T / 2;
+    const float* x = f.x;
+    const float* W = f.W;
+    float *bufA = f.bufA, *bufB = f.bufB, *bufC = f.bufC;
+    // res_block1 (src/models.py:64-76, :175)
+    TRY(conv3(x, W + L.w1, W + L.b1, nullptr, 0, 0, bufA, B, T, D, C, d.act, s));
+    const float* sc = x;
+    int64_t ldsc = D;
+    if (D != C) {
+        GemmParams p = gemm_params_plain(x, W + L.wsc, bufB, T, C, D, D, D, C);
+        p.bias = W + L.bsc; p.nz = B; p.sA1 = (int64_t)T * D; p.sC1 = (int64_t)T * C;
+        TRY(launch_gemm_f32(p, s, "cnn_conv_gemm"));
+        sc = bufB; ldsc = C;
+    }
+    TRY(conv3(bufA, W + L.w2, W + L.b2, sc, ldsc, (int64_t)T * ldsc, bufC, B, T, C, C, d.act, s));
+    TRY(tap_copy(f.res1_out, bufC, (int64_t)B * T * C, s));
+    // max_pool1d(2) (:177)
+    {
+        const int64_t n4 = (int64_t)B * Tp * (C / 4);
+        const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 256 * 16);
+        ProfScope prof("cnn_pool2", s, 0.0, (double)B * T * C * 4 * 1.5);
+        hipLaunchKernelGGL(pool2_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(bufC),
+                           reinterpret_cast<float4*>(bufA), B, T, Tp, C / 4);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    // res_block2, identity shortcut (:178)
+    TRY(conv3(bufA, W + L.w3, W + L.b3, nullptr, 0, 0, bufB, B, Tp, C, C, d.act, s));
+    TRY(conv3(bufB, W + L.w4, W + L.b4, bufA, C, (int64_t)Tp * C, bufC, B, Tp, C, C, d.act, s));
+    return tap_copy(f.res2_out, bufC, (int64_t)B * Tp * C, s);
+}
+
+// the same with the convolutions on the fp16-split GEMM, up to conv4's output as the plane pair of the first input projection
+static int front_f16x3(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
+    const int B = f.B, T = f.T, D = d.D, C = d.C, Tp = T / 2;
+    const float* x = f.x;
+    const float* W = f.W;
+    float *bufA = f.bufA, *bufB = f.bufB, *bufC = f.bufC;
+    float* f16base = f.f16base;
+    const F16Ws& F = f.F;
+    const F16Ws& WF = f.WF;
+    auto planes = [&](int64_t off) { return planes_at(f16base, off); };
+    const unsigned* stat = reinterpret_cast<const unsigned*>(f.wbase + WF.stat);   // [CNN_NSTAT][2], see prep_weights
+    unsigned* amax = reinterpret_cast<unsigned*>(f16base + F.amax);
+    float* scale = f16base + F.scale;
+    RSAF_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(unsigned) * CNN_NAMAX * B, s));
     auto cnn_scale = [&](int a_in, int a_res, int w_slot, int b_slot, float factor, int s_out) {
         hipLaunchKernelGGL(cnn_scale_kernel, dim3((B + 255) / 256), dim3(256), 0, s, amax + (int64_t)a_in * B,
                            a_res >= 0 ? amax + (int64_t)a_res * B : nullptr, w_slot >= 0 ? stat + 2 * w_slot : nullptr,
@@ -691,7 +843,7 @@ static int forward_f16x3(const float* x, int B, int T, const Dims& d, const Layo
             p.a_tap_panels = K > a_panels * 16 ? a_panels : 0;
         }
         p.a_scale = scale + (int64_t)s_in * B; p.a_scale_zs = 1; p.a_scale_ms = 0;
-        p.B = planes(F.wp[widx]); p.b_plane = (int64_t)N * K; p.ldb = 16; p.b_panel = 1; p.b_scale = f16base + F.ws[widx];
+        p.B = planes_at(f.wbase, WF.wp[widx]); p.b_plane = (int64_t)N * K; p.ldb = 16; p.b_panel = 1; p.b_scale = f.wbase + WF.ws[widx];
         p.C = Cf; p.ldc = N; p.sC = (int64_t)M * N;
         p.Cp = Cp ? Cp + (int64_t)cp_row0 * N : nullptr; p.c_plane = c_plane; p.ldcp = N; p.sCp = cp_seq_rows * N;
         p.c_scale = s_out >= 0 ? scale + (int64_t)s_out * B : nullptr; p.c_scale_zs = 1; p.c_scale_ms = 0;
@@ -727,21 +879,16 @@ static int forward_f16x3(const float* x, int B, int T, const Dims& d, const Layo
     cnn_scale(AX, -1, 0, 5, sqrtf((float)(3 * D)) * 1.00001f, SC1);
     hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(64), dim3(256), 0, s, planes(F.c1p), pl_c, B, T, C / 8);
     a_panels = x_panels ? D / 16 : 0;
-    rc = gemm(planes(F.xp), pl_x, T + 2, 0, D, SX, 0, T, C, 3 * D, nullptr, planes(F.c1p), pl_c, T + 2, 1, SC1, W + L.b1, nullptr,
-              d.act, AC1, "cnn_conv_gemm");
-    if (rc) return rc;
+    TRY(gemm(planes(F.xp), pl_x, T + 2, 0, D, SX, 0, T, C, 3 * D, nullptr, planes(F.c1p), pl_c, T + 2, 1, SC1, W + L.b1, nullptr,
+             d.act, AC1, "cnn_conv_gemm"));
     const float* sc = x;
-    int sc_amax = AX;
     if (D != C) {
-        rc = gemm(planes(F.xp), pl_x, T + 2, 1, D, SX, 1, T, C, D, bufB, nullptr, 0, 0, 0, -1, W + L.bsc, nullptr, ACT_NONE, ASC, "cnn_conv_gemm");
-        if (rc) return rc;
-        sc = bufB; sc_amax = ASC;
+        TRY(gemm(planes(F.xp), pl_x, T + 2, 1, D, SX, 1, T, C, D, bufB, nullptr, 0, 0, 0, -1, W + L.bsc, nullptr, ACT_NONE, ASC, "cnn_conv_gemm"));
+        sc = bufB;
     }
     a_panels = 0;
-    rc = gemm(planes(F.c1p), pl_c, T + 2, 0, C, SC1, 2, T, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b2, sc, d.act, AC2, "cnn_conv_gemm");
-    if (rc) return rc;
-    (void)sc_amax;
-    if ((rc = tap_copy(res1_out, bufC, (int64_t)B * T * C, s))) return rc;
+    TRY(gemm(planes(F.c1p), pl_c, T + 2, 0, C, SC1, 2, T, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b2, sc, d.act, AC2, "cnn_conv_gemm"));
+    TRY(tap_copy(f.res1_out, bufC, (int64_t)B * T * C, s));
     // max_pool1d(2) (:177): pooled fp32 rows (the residual of res_block2) + padded planes; max |pooled| <= max |conv2 output|
     cnn_scale(AC2, -1, -1, -1, 1.0f, SPOOL);
     {
@@ -755,12 +902,10 @@ static int forward_f16x3(const float* x, int B, int T, const Dims& d, const Layo
     // res_block2, identity shortcut (:178)
     cnn_scale(AC2, -1, 3, 8, sqrtf((float)(3 * C)) * 1.00001f, SC3);
     hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(64), dim3(256), 0, s, planes(F.c3p), pl_p, B, Tp, C / 8);
-    rc = gemm(planes(F.poolp), pl_p, Tp + 2, 0, C, SPOOL, 3, Tp, C, 3 * C, nullptr, planes(F.c3p), pl_p, Tp + 2, 1, SC3, W + L.b3, nullptr,
-              d.act, AC3, "cnn_conv_gemm");
-    if (rc) return rc;
-    rc = gemm(planes(F.c3p), pl_p, Tp + 2, 0, C, SC3, 4, Tp, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b4, bufA, d.act, AC4, "cnn_conv_gemm");
-    if (rc) return rc;
-    if ((rc = tap_copy(res2_out, bufC, (int64_t)B * Tp * C, s))) return rc;
+    TRY(gemm(planes(F.poolp), pl_p, Tp + 2, 0, C, SPOOL, 3, Tp, C, 3 * C, nullptr, planes(F.c3p), pl_p, Tp + 2, 1, SC3, W + L.b3, nullptr,
+             d.act, AC3, "cnn_conv_gemm"));
+    TRY(gemm(planes(F.c3p), pl_p, Tp + 2, 0, C, SC3, 4, Tp, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b4, bufA, d.act, AC4, "cnn_conv_gemm"));
+    TRY(tap_copy(f.res2_out, bufC, (int64_t)B * Tp * C, s));
     // conv4's output as the plane pair of the first input projection, under the exact maximum of every sequence
     cnn_scale(AC4, -1, -1, -1, 1.0f, SC4);
     {
@@ -769,46 +914,82 @@ static int forward_f16x3(const float* x, int B, int T, const Dims& d, const Layo
                            reinterpret_cast<const float4*>(bufC), B, (int64_t)Tp * (C / 4), scale + SC4 * B, planes(F.c4p), (int64_t)B * Tp * C);
         RSAF_CHECK_HIP(hipGetLastError());
     }
-    // LSTM (:184): input projections on the same GEMM; layer 0 reads conv4's planes (one scale per sequence), the layers
-    // behind it the plane pair of the previous layer's output under the fixed scale 2^14
-    const float* lin = bufC;
-    float* lout = seq0;
-    for (int l = 0; l < d.L; ++l) {
-        const int in = l == 0 ? C : 2 * H;
-        GemmH3Params p{};
-        p.B = planes(F.wih_p[l]); p.b_plane = (int64_t)8 * H * in; p.ldb = 16; p.b_panel = 1; p.b_scale = f16base + F.wih_s[l];
-        p.C = xproj; p.ldc = 8 * H; p.bias = W + L.bih[l]; p.N = 8 * H; p.K = in; p.act = ACT_NONE; p.alpha = 1.0f;
-        if (l == 0) {
-            p.A = planes(F.c4p); p.a_plane = (int64_t)B * Tp * C; p.lda = C; p.sA = (int64_t)Tp * C;
-            p.a_scale = scale + SC4 * B; p.a_scale_zs = 1; p.a_scale_ms = 0;
-            p.M = Tp; p.nz = B; p.sC = (int64_t)Tp * 8 * H;
-        } else {
-            const int64_t rows = (int64_t)B * Tp;
-            RSAF_CHECK_ARG(rows <= 0x7fffffffLL, "B*T too large");
-            if ((rc = launch_split_f16x2(lin, rows, in, in, one, 0, planes(F.hp), rows * in, 1, s))) return rc;
-            p.A = planes(F.hp); p.a_plane = rows * in; p.lda = 16; p.a_panel = 1;
-            p.a_scale = one; p.a_scale_zs = 0; p.a_scale_ms = 0;
-            p.M = (int)rows; p.nz = 1;
-        }
-        rc = launch_gemm_f16x3(p, s, "lstm_inproj_gemm");
-        if (rc) return rc;
-        rc = launch_lstm_rec(xproj, W + L.whh[l], lout, nullptr, nullptr, B, Tp, H, s);
-        if (rc) return rc;
-        lin = lout;
-        lout = (lout == seq0) ? seq1 : seq0;
-    }
-    if ((rc = tap_copy(lstm_out, lin, (int64_t)B * Tp * 2 * H, s))) return rc;
-    {
-        ProfScope prof("attnpool_fc", s, 0.0, (double)B * Tp * 2 * H * 4);
-        if (H == 128)
-            hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(B), dim3(256), 0, s, lin, W + L.watt, W + L.batt,
-                               W + L.wfc, W + L.bfc, logits, pooled_out, Tp, d.NC);
-        else
-            hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(B), dim3(256), 0, s, lin, W + L.watt, W + L.batt,
-                               W + L.wfc, W + L.bfc, logits, pooled_out, Tp, d.NC);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
     return RSAF_OK;
+}
+
+// the CNN front up to and including the input projection of the first LSTM layer (:184)
+static int front(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
+    TRY(f.f16 ? front_f16x3(f, d, L, s) : front_f32(f, d, L, s));
+    f.lin = f.bufC;
+    f.lout = f.seq0;
+    return inproj(f, d, L, 0, s);
+}
+
+static LstmRecItem rec_item(const Fwd& f, const Dims& d, const Layout& L, int l) {
+    return LstmRecItem{f.xproj, f.W + L.whh[l], f.lout, nullptr, nullptr, f.B, f.T / 2};
+}
+
+static AttnPoolItem head_item(const Fwd& f, const Layout& L) {
+    return AttnPoolItem{f.lin, f.W + L.watt, f.W + L.batt, f.W + L.wfc, f.W + L.bfc, f.logits, f.pooled_out, f.B, f.T / 2};
+}
+
+// attention pooling + fc (:187-191): one launch per forward, or one for the heads of all of them
+static int head(const Fwd* fs, int K, const Dims& d, const Layout& L, bool grouped, hipStream_t s) {
+    const int H = d.H;
+    if (!grouped) {
+        for (int k = 0; k < K; ++k) {
+            const AttnPoolItem it = head_item(fs[k], L);
+            ProfScope prof("attnpool_fc", s, 0.0, (double)it.B * it.T * 2 * H * 4);
+            if (H == 128)
+                hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
+                                   it.pooled_out, it.T, d.NC);
+            else
+                hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
+                                   it.pooled_out, it.T, d.NC);
+            RSAF_CHECK_HIP(hipGetLastError());
+        }
+        return RSAF_OK;
+    }
+    AttnPoolGroup g{};
+    int rows = 0;
+    double bytes = 0.0;
+    for (int k = 0; k < K; ++k) {
+        g.item[k] = head_item(fs[k], L);
+        rows = std::max(rows, fs[k].B);
+        bytes += (double)g.item[k].B * g.item[k].T * 2 * H * 4;
+    }
+    ProfScope prof("attnpool_fc", s, 0.0, bytes);
+    if (H == 128) hipLaunchKernelGGL(attnpool_fc_group_kernel<4>, dim3(rows, K), dim3(256), 0, s, g, d.NC);
+    else hipLaunchKernelGGL(attnpool_fc_group_kernel<2>, dim3(rows, K), dim3(256), 0, s, g, d.NC);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// `grouped`: one launch per layer carries the recurrences of all items whose batch runs on the 4-row kernel (an item above
+// lstm_small_max() has its recurrence launched on its own), and one launch the heads; otherwise one launch per item
+static int run_forward(Fwd* fs, int K, const Dims& d, bool grouped, hipStream_t s) {
+    const Layout L = make_layout(d);
+    for (int k = 0; k < K; ++k)
+        if (fs[k].f16 && fs[k].prep) TRY(prep_weights(fs[k], d, L, s));
+    for (int k = 0; k < K; ++k) TRY(front(fs[k], d, L, s));
+    for (int l = 0; l < d.L; ++l) {
+        LstmRecItem small[RSAF_CNNLSTM_GROUP_MAX];
+        int n_small = 0;
+        for (int k = 0; k < K; ++k) {
+            const LstmRecItem it = rec_item(fs[k], d, L, l);
+            if (grouped && it.B <= lstm_small_max()) small[n_small++] = it;
+            else TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, nullptr, nullptr, it.B, it.T, d.H, s));
+        }
+        if (n_small) TRY(launch_lstm_rec_group(small, n_small, d.H, s));
+        for (int k = 0; k < K; ++k) {
+            Fwd& f = fs[k];
+            f.lin = f.lout;
+            f.lout = (f.lout == f.seq0) ? f.seq1 : f.seq0;
+            if (l + 1 < d.L) TRY(inproj(f, d, L, l + 1, s));
+        }
+    }
+    for (int k = 0; k < K; ++k) TRY(tap_copy(fs[k].lstm_out, fs[k].lin, (int64_t)fs[k].B * (fs[k].T / 2) * 2 * d.H, s));
+    return head(fs, K, d, L, grouped, s);
 }
 
 }  // namespace cnnlstm
@@ -858,112 +1039,65 @@ int64_t rsaf_cnnlstm_workspace_bytes(int B, int T, int input_dim, int channels, 
     return (3 * conv + xp + 2 * sq + f16) * (int64_t)sizeof(float);
 }
 
-static int forward_impl(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
-                        int lstm_layers, int act, const float* weights, void* workspace,
-                        int64_t workspace_bytes, float* logits, float* res1_out, float* res2_out, float* lstm_out,
-                        float* pooled_out, rsaf_stream_t stream) {
+static int forward_single(const char* who, const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
+                          int lstm_layers, int act, const float* weights, void* workspace, int64_t workspace_bytes, float* logits,
+                          float* res1_out, float* res2_out, float* lstm_out, float* pooled_out, rsaf_stream_t stream) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
-    int rc = check_dims(d);
-    if (rc != RSAF_OK) return rc;
-    RSAF_CHECK_ARG(B >= 0 && B <= 65535, "batch must be in [0, 65535]");
+    TRY(check_dims(d));
     if (B == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(T >= 2, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
-    RSAF_CHECK_ARG(x && weights && workspace && logits, "NULL pointer");
-    const int64_t need = rsaf_cnnlstm_workspace_bytes(B, T, input_dim, channels, hidden, lstm_layers);
-    if (workspace_bytes < need) {
-        set_error("rsaf_cnnlstm_forward: workspace too small");
-        return RSAF_ERR_WORKSPACE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    const Layout L = make_layout(d);
-    const int D = d.D, C = d.C, H = d.H, Tp = T / 2;
-    float* ws = static_cast<float*>(workspace);
-    const int64_t conv = pad4((int64_t)B * T * C);
-    float* bufA = ws;
-    float* bufB = ws + conv;
-    float* bufC = ws + 2 * conv;
-    float* xproj = ws + 3 * conv;
-    float* seq0 = xproj + pad4((int64_t)B * Tp * 8 * H);
-    float* seq1 = seq0 + pad4((int64_t)B * Tp * 2 * H);
-    const float* W = weights;
-    if (use_f16x3(D, C))
-        return forward_f16x3(x, B, T, d, L, W, ws, seq1 + pad4((int64_t)B * Tp * 2 * H), logits, res1_out, res2_out, lstm_out,
-                             pooled_out, s);
-
-    // res_block1 (src/models.py:64-76, :175)
-    rc = conv3(x, W + L.w1, W + L.b1, nullptr, 0, 0, bufA, B, T, D, C, d.act, s);
-    if (rc) return rc;
-    const float* sc = x;
-    int64_t ldsc = D;
-    if (D != C) {
-        GemmParams p = gemm_params_plain(x, W + L.wsc, bufB, T, C, D, D, D, C);
-        p.bias = W + L.bsc; p.nz = B; p.sA1 = (int64_t)T * D; p.sC1 = (int64_t)T * C;
-        rc = launch_gemm_f32(p, s, "cnn_conv_gemm");
-        if (rc) return rc;
-        sc = bufB; ldsc = C;
-    }
-    rc = conv3(bufA, W + L.w2, W + L.b2, sc, ldsc, (int64_t)T * ldsc, bufC, B, T, C, C, d.act, s);
-    if (rc) return rc;
-    if ((rc = tap_copy(res1_out, bufC, (int64_t)B * T * C, s))) return rc;
-    // max_pool1d(2) (:177)
-    {
-        const int64_t n4 = (int64_t)B * Tp * (C / 4);
-        const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 256 * 16);
-        ProfScope prof("cnn_pool2", s, 0.0, (double)B * T * C * 4 * 1.5);
-        hipLaunchKernelGGL(pool2_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(bufC),
-                           reinterpret_cast<float4*>(bufA), B, T, Tp, C / 4);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    // res_block2, identity shortcut (:178)
-    rc = conv3(bufA, W + L.w3, W + L.b3, nullptr, 0, 0, bufB, B, Tp, C, C, d.act, s);
-    if (rc) return rc;
-    rc = conv3(bufB, W + L.w4, W + L.b4, bufA, C, (int64_t)Tp * C, bufC, B, Tp, C, C, d.act, s);
-    if (rc) return rc;
-    if ((rc = tap_copy(res2_out, bufC, (int64_t)B * Tp * C, s))) return rc;
-    // LSTM (:184)
-    const float* lin = bufC;
-    int in = C;
-    float* lout = seq0;
-    for (int l = 0; l < d.L; ++l) {
-        const int64_t rows = (int64_t)B * Tp;
-        RSAF_CHECK_ARG(rows <= 0x7fffffffLL, "B*T too large");
-        GemmParams p = gemm_params_plain(lin, W + L.wih[l], xproj, (int)rows, 8 * H, in, in, in, 8 * H);
-        p.bias = W + L.bih[l];
-        rc = launch_gemm_f32(p, s, "lstm_inproj_gemm");
-        if (rc) return rc;
-        rc = launch_lstm_rec(xproj, W + L.whh[l], lout, nullptr, nullptr, B, Tp, H, s);
-        if (rc) return rc;
-        lin = lout; in = 2 * H;
-        lout = (lout == seq0) ? seq1 : seq0;
-    }
-    if ((rc = tap_copy(lstm_out, lin, (int64_t)B * Tp * 2 * H, s))) return rc;
-    // attention pooling + fc (:187-191)
-    {
-        ProfScope prof("attnpool_fc", s, 0.0, (double)B * Tp * 2 * H * 4);
-        if (H == 128)
-            hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(B), dim3(256), 0, s, lin, W + L.watt, W + L.batt,
-                               W + L.wfc, W + L.bfc, logits, pooled_out, Tp, d.NC);
-        else
-            hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(B), dim3(256), 0, s, lin, W + L.watt, W + L.batt,
-                               W + L.wfc, W + L.bfc, logits, pooled_out, Tp, d.NC);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    return RSAF_OK;
+    Fwd f;
+    TRY(check_item(d, x, B, T, weights, workspace, workspace_bytes, logits, who, -1, &f));
+    f.res1_out = res1_out; f.res2_out = res2_out; f.lstm_out = lstm_out; f.pooled_out = pooled_out;
+    return run_forward(&f, 1, d, false, (hipStream_t)stream);
 }
 
 int rsaf_cnnlstm_forward(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
                          int lstm_layers, int act, const float* weights, void* workspace,
                          int64_t workspace_bytes, float* logits, rsaf_stream_t stream) {
-    return forward_impl(x, B, T, input_dim, channels, hidden, num_classes, lstm_layers, act, weights, workspace,
-                        workspace_bytes, logits, nullptr, nullptr, nullptr, nullptr, stream);
+    return forward_single(__func__, x, B, T, input_dim, channels, hidden, num_classes, lstm_layers, act, weights, workspace,
+                          workspace_bytes, logits, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 int rsaf_cnnlstm_forward_stages(const float* x, int B, int T, int input_dim, int channels, int hidden,
                                 int num_classes, int lstm_layers, int act, const float* weights, void* workspace,
                                 int64_t workspace_bytes, float* logits, float* res1_out, float* res2_out,
                                 float* lstm_out, float* pooled_out, rsaf_stream_t stream) {
-    return forward_impl(x, B, T, input_dim, channels, hidden, num_classes, lstm_layers, act, weights, workspace,
-                        workspace_bytes, logits, res1_out, res2_out, lstm_out, pooled_out, stream);
+    return forward_single(__func__, x, B, T, input_dim, channels, hidden, num_classes, lstm_layers, act, weights, workspace,
+                          workspace_bytes, logits, res1_out, res2_out, lstm_out, pooled_out, stream);
+}
+
+int rsaf_cnnlstm_forward_group(const rsaf_cnnlstm_forward_item* items_host, int K, int input_dim, int channels, int hidden,
+                               int num_classes, int lstm_layers, int act, rsaf_stream_t stream) {
+    const char* who = __func__;
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
+    Fwd fs[RSAF_CNNLSTM_GROUP_MAX];
+    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (RSAF_CNNLSTM_GROUP_MAX)");
+    if (!items_host) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    // widths the layouts cannot be computed for are refused here; the full check of the dims follows the item checks (it is
+    // the same for every item, and the item checks name the item)
+    if (!(input_dim > 0 && channels > 0 && hidden > 0 && lstm_layers >= 1 && lstm_layers <= 4)) return check_dims(d);
+    for (int k = 0; k < K; ++k) {
+        const rsaf_cnnlstm_forward_item& it = items_host[k];
+        TRY(check_item(d, it.x, it.B, it.T, it.weights, it.workspace, it.workspace_bytes, it.logits, who, k, &fs[k]));
+    }
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const rsaf_cnnlstm_forward_item &a = items_host[j], &b = items_host[k];
+            const char* what =
+                overlap(a.workspace, rsaf_cnnlstm_workspace_bytes(a.B, a.T, d.D, d.C, d.H, d.L), b.workspace,
+                        rsaf_cnnlstm_workspace_bytes(b.B, b.T, d.D, d.C, d.H, d.L)) ? "workspace"
+                : overlap(a.logits, (int64_t)a.B * d.NC * 4, b.logits, (int64_t)b.B * d.NC * 4) ? "logits" : nullptr;
+            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
+        }
+    TRY(check_dims(d));
+    // weight preparation once per distinct blob: later items read the planes, scales and statistics of the first one
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j)
+            if (fs[k].f16 && fs[j].prep && fs[j].W == fs[k].W) {
+                fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
+                break;
+            }
+    return run_forward(fs, K, d, true, (hipStream_t)stream);
 }
 
 int64_t rsaf_cnn_resblock_workspace_bytes(int B, int T, int out_channels) {

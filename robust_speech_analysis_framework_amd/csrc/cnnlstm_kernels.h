@@ -27,6 +27,23 @@ struct LstmRecGroup {
 };
 int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s);
 
+// Attention pooling + classifier (the head of the inference forward) of up to RSAF_CNNLSTM_GROUP_MAX independent forwards of
+// one H and one num_classes in ONE launch; the descriptors travel by value in the kernel arguments.  seq [B][T][2H];
+// pooled_out may be NULL.
+struct AttnPoolItem {
+    const float* seq;
+    const float* watt;
+    const float* batt;
+    const float* wfc;
+    const float* bfc;
+    float* logits;
+    float* pooled_out;
+    int B, T;
+};
+struct AttnPoolGroup {
+    AttnPoolItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
 // Largest batch that runs on the 4-row recurrence kernels (environment RSAF_LSTM_SMALL_MAX, read once; default 1 024).
 int lstm_small_max();
 
