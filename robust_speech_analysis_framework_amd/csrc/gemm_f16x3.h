@@ -33,6 +33,10 @@ struct GemmH3Params {
     // optional, ragged windows of one launch: ztab[2 z1] = rows of batch z1 (<= M; tiles past it are skipped),
     // ztab[2 z1 + 1] = element offset of the batch's fp32 output (packed windows), or -1 for z1 * sC
     const int64_t* ztab;
+    // optional, windows packed along M in one batch (nz = 1): row_tab[2 m] = window slot of row m (the index into a_scale,
+    // c_scale and amax_out, which then take no strides), row_tab[2 m + 1] = the row of C / Cp that receives row m, or -1 for
+    // a row that is computed and dropped (never stored, never counted in amax_out)
+    const int* row_tab;
     int act;
     float alpha;
     int group_m;             // row-tiles per L2 group of the tile order (0 = default)

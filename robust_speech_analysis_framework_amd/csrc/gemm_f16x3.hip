@@ -55,7 +55,8 @@ struct H3Cfg {
     static constexpr int STAGE = NPL * (A_PLANE + B_PLANE);
     static constexpr int A_INSTR = BM / 32, B_INSTR = BN / 32;          // 1 KiB DMA wave-instructions per plane
     static constexpr int PATCH_BYTES = WM * WN * 32 * 36 * 4;           // wave-private transposition patches of the epilogue
-    static constexpr int TAB_BYTES = 2 * (BM + BN) * 4;                 // the tile's row / column scales and biases (epilogue)
+    static constexpr int TAB_BYTES = 2 * (BM + BN) * 4 + 2 * BM * 4;    // the tile's row / column scales and biases (epilogue)
+                                                                        // + the rows' window slots and destinations (row_tab)
     // The patches do not alias stages 0 and 1: the next tile's first two k-tiles land there while the epilogue runs.  Stage 2
     // is free from the end of a tile's main loop until the next tile's first refill (issued inside that tile's main loop):
     // the 512 x 128 configuration, whose three 40 KB stages leave no room beside them, keeps its patches there.
@@ -79,7 +80,8 @@ struct H3Cfg {
         (glb_ptr3)(sp_ + lb_);                                                                                 \
     })
 
-template <class CFG, int ACT, bool OUT_F32, bool OUT_PLANES, bool HAS_R>
+// ROWTAB: the rows carry a table (GemmH3Params::row_tab); launches without one run the instantiations without its fields
+template <class CFG, int ACT, bool OUT_F32, bool OUT_PLANES, bool HAS_R, bool ROWTAB = false>
 __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void gemm_f16x3_kernel(const GemmH3Params p) {
     extern __shared__ __attribute__((aligned(1024))) unsigned short smem3[];
     constexpr int BM = CFG::BM, BN = CFG::BN, BK = CFG::BK, STAGE = CFG::STAGE, NST = CFG::NST, NPL = CFG::NPL;
@@ -203,7 +205,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
     constexpr int TPT = (BM + BN + CFG::THREADS - 1) / CFG::THREADS;     // table entries per thread (1; 2 for the 512 x 128 tile)
     float* tab0 = reinterpret_cast<float*>(smem3 + NST * STAGE) + (CFG::PATCH_IN_STAGE2 ? 0 : NW * (32 * PATCH_LD));   // [BM] a_scale | [BN] b_scale
     float* tab1 = tab0 + (BM + BN);                                                        // [BM] c_scale | [BN] bias
+    int* tab_slot = reinterpret_cast<int*>(tab1 + (BM + BN));                              // [BM] window slot | [BM] destination row
+    int* tab_dest = tab_slot + BM;
     float e0[TPT], e1[TPT];
+    int e_slot[TPT], e_dest[TPT];                                                          // (ROWTAB only)
     auto load_epi = [&](const Tile& T) {
 #pragma unroll
         for (int u = 0; u < TPT; ++u) {
@@ -211,8 +216,15 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
             e0[u] = 1.0f; e1[u] = 0.0f;
             if (i < BM) {
                 const int row = T.m0 + i < T.Mz ? T.m0 + i : T.Mz - 1;                      // clamped: rows past M are never stored
-                e0[u] = p.a_scale[T.z1 * p.a_scale_zs + (int64_t)row * p.a_scale_ms];
-                e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[T.z1 * p.c_scale_zs + (int64_t)row * p.c_scale_ms] : 1.0f;
+                if (ROWTAB) {
+                    const int2 rt = reinterpret_cast<const int2*>(p.row_tab)[row];
+                    e_slot[u] = rt.x; e_dest[u] = rt.y;
+                    e0[u] = p.a_scale[rt.x];
+                    e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[rt.x] : 1.0f;
+                } else {
+                    e0[u] = p.a_scale[T.z1 * p.a_scale_zs + (int64_t)row * p.a_scale_ms];
+                    e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[T.z1 * p.c_scale_zs + (int64_t)row * p.c_scale_ms] : 1.0f;
+                }
             } else if (i < BM + BN) {
                 const int col = T.n0 + i - BM;
                 e0[u] = col < p.N ? p.b_scale[T.z2 * p.sBias2 + col] : 1.0f;
@@ -347,6 +359,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
     for (int u = 0; u < TPT; ++u) {
         const int i = tid + u * CFG::THREADS;
         if (i < BM + BN) { tab0[i] = e0[u]; tab1[i] = e1[u]; }
+        if (ROWTAB && i < BM) { tab_slot[i] = e_slot[u]; tab_dest[i] = e_dest[u]; }
     }
     if (HAS_R) load_r(0, 0);
 
@@ -368,11 +381,13 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
     for (int mt = 0; mt < TM; ++mt) {
         const int tm = m0 + wm0 + mt * 32;
         float asi[NQ], csc[NQ], row_amax[NQ];
+        int drow[NQ];                                    // where the row goes: itself, or its row_tab destination (< 0: dropped)
 #pragma unroll
         for (int q = 0; q < NQ; ++q) {
             asi[q] = p.alpha * pow2_inverse(tab0[wm0 + mt * 32 + RPI * q + lr]);
             csc[q] = tab1[wm0 + mt * 32 + RPI * q + lr];
             row_amax[q] = 0.0f;
+            drow[q] = ROWTAB ? tab_dest[wm0 + mt * 32 + RPI * q + lr] : tm + RPI * q + lr;
         }
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
@@ -424,8 +439,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
             if (HAS_R && sub < LAST) load_r((sub + 1) / TN, (sub + 1) % TN);   // the next residual, in front of this sub-tile's stores
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
-                const int row = tm + RPI * q + lr;
-                const bool ok = c_ok && row < Mz;
+                const int row = drow[q];
+                const bool ok = c_ok && tm + RPI * q + lr < Mz && (!ROWTAB || row >= 0);
                 if (p.amax_out && ok && gc >= p.amax_col_min) {
 #pragma unroll
                     for (int j = 0; j < CW; ++j) row_amax[q] = fmaxf(row_amax[q], fabsf(v[q][j]));
@@ -460,8 +475,9 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const int row = tm + RPI * q + lr;
-                const bool r_ok = row < Mz;
-                const int slot = !r_ok ? -1 : (int)(z1 * p.amax_zs) + (p.amax_row_slot ? p.amax_row_slot[row] : 0);
+                const bool r_ok = row < Mz && (!ROWTAB || drow[q] >= 0);
+                const int slot = !r_ok ? -1 : ROWTAB ? tab_slot[wm0 + mt * 32 + RPI * q + lr]
+                                                     : (int)(z1 * p.amax_zs) + (p.amax_row_slot ? p.amax_row_slot[row] : 0);
                 unsigned long long todo = __ballot(r_ok);
                 while (todo) {
                     const int first = __ffsll((long long)todo) - 1;
@@ -607,6 +623,8 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
                    "a_tap_panels: A in panels with a_panel_rows, K = taps x a_tap_panels x 16");
     RSAF_CHECK_ARG(p.ldc < (1 << 24) && p.ldcp < (1 << 24) && p.ldr < (1 << 24), "leading dimensions must be below 2^24");
     RSAF_CHECK_ARG(!p.R || p.C, "the residual comes with the fp32 output");
+    RSAF_CHECK_ARG(!p.row_tab || (p.nz == 1 && !p.ztab && p.nz2 <= 1 && !p.cp_panel && !p.a_panel && !p.amax_row_slot),
+                   "a row table: one batch, row-major A and plane output, no ztab / amax_row_slot");
     RSAF_CHECK_ARG(p.nz2 <= 1 || (p.C && !p.Cp && !p.R && (!p.a_panel || p.a_panel_rows > 0) && p.nz % p.nz2 == 0),
                    "two-level batches: fp32 output only, no residual, A row-major or panels with a_panel_rows, nz a multiple of nz2");
     // algorithmic FLOPs of the contraction (2 M N K); the matrix pipe executes three fp16 products per term
@@ -616,19 +634,19 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
     using CfgM = H3Cfg<4, 2, 4, 2, 3, 1>;                // 512 x 128: N <= 128 (the CNN-LSTM's 128 channels): the wave tile of the
                                                          // 256 x 256 configuration (24 MFMAs per k-tile and wave; a 256 x 128 tile's 12
                                                          // left the main loop bound by its barriers and DMA issue: 110 TFLOP/s-equivalent)
-#define H3_LAUNCH_CFG(CFG, ACT, F32, PL, HR)                                                                            \
+#define H3_LAUNCH_CFG(CFG, ACT, F32, PL, HR, ...)                                                                       \
     do {                                                                                                                \
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f16x3_kernel<CFG, ACT, F32, PL, HR>,                        \
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f16x3_kernel<CFG, ACT, F32, PL, HR, ##__VA_ARGS__>,         \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES));                 \
         const int64_t tiles = (int64_t)((p.N + CFG::BN - 1) / CFG::BN) * ((p.M + CFG::BM - 1) / CFG::BM) * p.nz;        \
         RSAF_CHECK_ARG(tiles <= 0x7fffffffLL, "too many tiles");                                                        \
-        hipLaunchKernelGGL((gemm_f16x3_kernel<CFG, ACT, F32, PL, HR>), dim3((unsigned)std::min<int64_t>(tiles, persistent_wgs)), \
-                           dim3(CFG::THREADS), CFG::LDS_BYTES, stream, pp);                                              \
+        hipLaunchKernelGGL((gemm_f16x3_kernel<CFG, ACT, F32, PL, HR, ##__VA_ARGS__>),                                    \
+                           dim3((unsigned)std::min<int64_t>(tiles, persistent_wgs)), dim3(CFG::THREADS), CFG::LDS_BYTES, stream, pp); \
     } while (0)
-#define H3_LAUNCH(ACT, F32, PL, HR)                                                                                     \
+#define H3_LAUNCH(ACT, F32, PL, HR, ...)                                                                                \
     do {                                                                                                                \
-        if (p.N <= 64) H3_LAUNCH_CFG(CfgN, ACT, F32, PL, HR);                                                            \
-        else H3_LAUNCH_CFG(CfgA, ACT, F32, PL, HR);                                                                      \
+        if (p.N <= 64) H3_LAUNCH_CFG(CfgN, ACT, F32, PL, HR, ##__VA_ARGS__);                                             \
+        else H3_LAUNCH_CFG(CfgA, ACT, F32, PL, HR, ##__VA_ARGS__);                                                       \
     } while (0)
     // the CNN-LSTM's shapes (N = 128 channels: the 256 x 128 tile) take three tile configurations
 #define H3_LAUNCH3(ACT, F32, PL, HR)                                                                                    \
@@ -653,7 +671,14 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
     }
     const bool f32o = p.C != nullptr, plo = p.Cp != nullptr, hr = p.R != nullptr;
     // the combinations the Wav2Vec2 / CNN stages use (anything else is an argument error, not a silent fallback)
-    if (p.act == ACT_NONE && f32o && !plo && !hr) H3_LAUNCH3(ACT_NONE, true, false, false);
+    if (p.row_tab) {                                         // the feature encoder's convolutions, windows packed along M
+        if (p.act == ACT_GELU && !f32o && plo && !hr) H3_LAUNCH(ACT_GELU, false, true, false, true);
+        else if (p.act == ACT_GELU && f32o && !plo && !hr) H3_LAUNCH(ACT_GELU, true, false, false, true);
+        else {
+            set_error("launch_gemm_f16x3: a row table comes with GELU and one output (planes or fp32)");
+            return RSAF_ERR_ARG;
+        }
+    } else if (p.act == ACT_NONE && f32o && !plo && !hr) H3_LAUNCH3(ACT_NONE, true, false, false);
     else if (p.act == ACT_NONE && f32o && !plo && hr) H3_LAUNCH(ACT_NONE, true, false, true);
     else if (p.act == ACT_GELU && !f32o && plo && !hr) H3_LAUNCH3(ACT_GELU, false, true, false);
     else if (p.act == ACT_SILU && !f32o && plo && !hr) H3_LAUNCH3(ACT_SILU, false, true, false);

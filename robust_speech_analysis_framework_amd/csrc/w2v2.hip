@@ -126,6 +126,7 @@ struct Workspace {
     int64_t cb_max;                                      // CONV_BIAS: max |bias| of conv1..5 (appended after the tables)
     int64_t gate;                                        // REL_POS_BIAS: the bias gates [rows][NH] of the current layer (appended)
     int64_t t_Tw, t_row0, t_ztab, t_rowwin;              // window tables (int32 / int64 views of the float workspace)
+    int64_t t_coff, t_crow;                              // packed conv row spaces of the current group (see packed_in_rows)
 };
 constexpr int STAT_SLAB = 512;
 constexpr int CONV_GROUP = 512;      // windows per pass of the feature encoder (its ping-pong buffers are the big ones)
@@ -136,6 +137,25 @@ static inline bool fused_attention(const Cfg& c, int Tt) { return c.Hd / c.NH ==
 static inline bool posconv_on_f16x3(const Cfg& c) { return (c.Hd / c.PG) % 16 == 0; }             // else the exact-fp32 GEMM
 
 static inline int64_t planes_floats(int64_t n) { return pad4(n); }
+
+// Packed row spaces of the feature encoder (group-norm mode).  Conv i (1..6) of a group of windows is ONE GEMM whose rows
+// are the windows' frames back to back: in the OUTPUT row space of layer i window w owns T_i[w] + 1 rows from off_i[w] (the
+// extra row is junk: it absorbs the last tap reaching one input row further), and the layer's INPUT row space, the
+// channels-last planes of layer i - 1, starts the window at row 2 off_i[w] (T_{i-1} <= 2 T_i + 2, so it fits; GEMM row R
+// reads K = k C contiguous elements at lda = 2 C).  Gap rows of the input space are read by junk rows only.
+// Rows a buffer needs to hold the input space of layer i for G windows of at most Ti frames: the last junk row reads one
+// row past the 2 M_i rows of the space.
+static inline int64_t packed_in_rows(int G, int Ti) { return 2 * (int64_t)G * (Ti + 1) + 1; }
+// the P buffer holds the inputs of conv1 / 3 / 5 (and layer mode's G x T[0] rows), Q those of conv2 / 4 / 6 (layer mode:
+// G x T[1] fp32 rows); T_{i-1} <= 2 T_i + 2 makes the packed sizes the larger ones
+static inline int64_t p_rows(int G, const int* T) { return packed_in_rows(G, T[1]); }
+static inline int64_t q_rows(int G, const int* T) { return packed_in_rows(G, T[2]); }
+// first entry of layer i's row table (i = 1..6): G (T[j] + 1) rows per earlier layer j
+static inline int64_t packed_tab_base(int G, const int* T, int i) {
+    int64_t b = 0;
+    for (int j = 1; j < i; ++j) b += (int64_t)G * (T[j] + 1);
+    return b;
+}
 
 // index of a weight matrix in the wstat table
 static inline int wstat_conv(int i) { return i; }                       // i = 0..5 (conv1..6)
@@ -186,8 +206,8 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     w.xn = take((int64_t)G * R.maxlen);
     w.part = take((int64_t)G * slabs * 3 * c.C);
     w.ab = take((int64_t)G * 2 * c.C);
-    w.P = take(planes_floats((int64_t)G * T[0] * c.C));
-    w.Q = take(planes_floats((int64_t)G * T[1] * c.C));
+    w.P = take(planes_floats(p_rows(G, T) * c.C));
+    w.Q = take(planes_floats(q_rows(G, T) * c.C));
     w.c6 = take(rows * c.C);
     w.lnfp = take(planes_floats(rows * c.C));
     w.x = take(rows * c.Hd);
@@ -221,6 +241,8 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     // {rows, output offset} of conv1..6 and of the positional conv), rowwin[rows] window of every encoder row
     w.t_Tw = take((int64_t)7 * n); w.t_row0 = take(2 * ((int64_t)n + 1)); w.t_ztab = take((int64_t)7 * n * 2 * 2);
     w.t_rowwin = take(rows);
+    // packed conv row spaces of a group: off[7][G + 1] (int32) and per layer and row {window slot, destination row} (int32 x 2)
+    w.t_coff = take((int64_t)7 * (G + 1)); w.t_crow = take(2 * packed_tab_base(G, T, 7));
     w.cb_max = (c.flags & F_CONV_BIAS) ? take(8) : -1;
     w.gate = (c.flags & F_REL_POS_BIAS) ? take(rows * c.NH) : -1;
     w.total = o;
@@ -249,6 +271,26 @@ __global__ __launch_bounds__(256) void w2v2_tables_kernel(const int* __restrict_
         ztab[((int64_t)5 * n + w) * 2] = Tw[(int64_t)6 * n + w]; ztab[((int64_t)5 * n + w) * 2 + 1] = row0[w] * C;
         ztab[((int64_t)6 * n + w) * 2] = Tw[(int64_t)6 * n + w]; ztab[((int64_t)6 * n + w) * 2 + 1] = row0[w] * Hd;
     }
+}
+// Packed conv row spaces of the windows of one group (Tw, row0: already at the group's first window): off[i][w] = first row
+// of window w in the output row space of conv i, off[i][g] = M_i, the rows of that layer's GEMM
+__global__ __launch_bounds__(64) void w2v2_pack_offsets_kernel(const int* __restrict__ Tw, int n, int g, int G, int* __restrict__ off) {
+    const int i = threadIdx.x + 1;
+    if (i > 6) return;
+    int r = 0;
+    for (int w = 0; w < g; ++w) { off[(int64_t)i * (G + 1) + w] = r; r += Tw[(int64_t)i * n + w] + 1; }
+    off[(int64_t)i * (G + 1) + g] = r;
+}
+// the row table of conv i = blockIdx.y + 1, window blockIdx.x: {slot, destination} of its T_i + 1 rows.  Frame t goes to
+// row 2 off_{i+1}[w] + t of the next layer's input space (conv6: to the call's packed row row0[w] + t); the junk row to -1
+struct PackBases { int64_t b[7]; };
+__global__ __launch_bounds__(256) void w2v2_pack_rows_kernel(const int* __restrict__ Tw, int n, int G, const int* __restrict__ off,
+                                                             const int64_t* __restrict__ row0, int* __restrict__ tab, PackBases bases) {
+    const int w = blockIdx.x, i = blockIdx.y + 1;
+    const int Ti = Tw[(int64_t)i * n + w];
+    const int dst0 = i < 6 ? 2 * off[(int64_t)(i + 1) * (G + 1) + w] : (int)row0[w];
+    int2* t2 = reinterpret_cast<int2*>(tab) + bases.b[i] + off[(int64_t)i * (G + 1) + w];
+    for (int t = threadIdx.x; t <= Ti; t += 256) t2[t] = make_int2(w, t < Ti ? dst0 + t : -1);
 }
 __global__ __launch_bounds__(256) void w2v2_rowwin_kernel(const int64_t* __restrict__ row0, int* __restrict__ rowwin) {
     const int w = blockIdx.x;
@@ -314,8 +356,10 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
                                                     const float* __restrict__ cb, float* __restrict__ part, const float* __restrict__ ab,
                                                     const float* __restrict__ scale,
                                                     unsigned short* __restrict__ outp, int64_t plane, int len,
-                                                    const int* __restrict__ T0w, int T0, int C, int slab, int slabs) {
-    // len / T0: the longest window's samples / frames (strides of xn and of the output); T0w: frames of every window
+                                                    const int* __restrict__ T0w, const int* __restrict__ out_off, int C, int slab,
+                                                    int slabs) {
+    // len: the longest window's samples (stride of xn); T0w: frames of every window; out_off[w]: HALF the first output row of
+    // window w (its first row in conv1's packed output row space)
     const int chunk = blockIdx.y, sl = blockIdx.x;
     const int t0 = sl * slab, t1 = min(T0w[chunk], t0 + slab);
     const float* __restrict__ x = xn + (int64_t)chunk * len;
@@ -363,7 +407,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
             }
         }
         if (APPLY) {
-            const int64_t o = ((int64_t)chunk * T0 + t) * C + ch[0];
+            const int64_t o = (2 * (int64_t)out_off[chunk] + t) * C + ch[0];
             if (CPT % 2 == 0) {                             // 4-byte stores of channel pairs (C and ch[0] are even)
 #pragma unroll
                 for (int k = 0; k < CPT; k += 2) {
@@ -1381,7 +1425,8 @@ static int ln(const LnArgs& a, int64_t rows, int D, float eps, hipStream_t s) {
 // cb: the conv bias (RSAF_W2V2_CONV_BIAS) or NULL
 template <bool APPLY>
 static int conv0_launch(const Cfg& c, const float* xn, const float* w0, const float* cb, float* part, const float* ab, const float* scale,
-                        unsigned short* outp, int64_t plane, int n, int len, const int* T0w, int T0, int slab, int slabs, hipStream_t s) {
+                        unsigned short* outp, int64_t plane, int n, int len, const int* T0w, const int* out_off, int T0, int slab, int slabs,
+                        hipStream_t s) {
     const int threads = c.C <= 256 ? c.C : 256;
     const int cpt = c.C / threads;
     dim3 grid((unsigned)slabs, (unsigned)n);
@@ -1391,8 +1436,8 @@ static int conv0_launch(const Cfg& c, const float* xn, const float* w0, const fl
     ProfScope prof(APPLY ? "w2v2_conv0_apply" : "w2v2_conv0_stats", s, 0.0,
                    APPLY ? (double)n * ((double)c.C * T0 * 4.0 + 4.0 * (5.0 * T0 + 5.0)) : (double)n * 4.0 * (5.0 * T0 + 5.0));
 #define RSAF_C0K(CPT, BIAS)                                                                                \
-    hipLaunchKernelGGL((conv0_kernel<CPT, APPLY, BIAS>), grid, dim3(threads), 0, s, xn, w0, cb, part, ab, scale, outp, plane, len, T0w, T0, \
-                       c.C, slab, slabs)
+    hipLaunchKernelGGL((conv0_kernel<CPT, APPLY, BIAS>), grid, dim3(threads), 0, s, xn, w0, cb, part, ab, scale, outp, plane, len, T0w, \
+                       out_off, c.C, slab, slabs)
 #define RSAF_C0(BIAS)                                                                                      \
     switch (cpt) {                                                                                         \
         case 1: RSAF_C0K(1, BIAS); break;                                                                  \
@@ -1463,6 +1508,7 @@ struct Out {
     int amax_zs = 0;
     const int* amax_row_slot = nullptr;
     int amax_col_min = 0;
+    const int* row_tab = nullptr;                            // packed windows: {slot, destination} per row (GemmH3Params::row_tab)
 };
 
 // One forward call: its geometry, buffers and device tables, and one member function per phase (forward_impl runs them in order)
@@ -1495,6 +1541,8 @@ struct Forward {
     int64_t* row0;
     int64_t* ztab;                                           // [7][n][2]
     int* rowwin;
+    int* coff;                                               // [7][G + 1] packed conv row spaces of the current group
+    int* crow;                                               // per conv layer and packed row {slot, destination}
     const int* wlen = nullptr;
     // feature encoder: scale of layer i's plane output per window of the group, largest |output| of layer i (layer 0: its
     // bound), the conv biases [7][C], the conv LayerNorms [7][2][C] (layer mode), max |bias| of conv1..5 at 1..5
@@ -1512,6 +1560,7 @@ struct Forward {
           layer_norm(c_.flags & F_LAYER_FEAT_NORM), conv_bias(c_.flags & F_CONV_BIAS),
           Tw(reinterpret_cast<int*>(ws + W.t_Tw)), row0(reinterpret_cast<int64_t*>(ws + W.t_row0)),
           ztab(reinterpret_cast<int64_t*>(ws + W.t_ztab)), rowwin(reinterpret_cast<int*>(ws + W.t_rowwin)),
+          coff(reinterpret_cast<int*>(ws + W.t_coff)), crow(reinterpret_cast<int*>(ws + W.t_crow)),
           cscale(ws + W.conv_scale), camax(bits_at(W.conv_amax)), cbias(conv_bias ? Wt + L.cb : nullptr), cln(Wt + L.cln),
           cb_max(conv_bias ? ws + W.cb_max : nullptr), x(ws + W.x) {}
 
@@ -1532,7 +1581,7 @@ struct Forward {
         p.Cp = o.Cp; p.c_plane = o.c_plane; p.ldcp = N; p.sCp = o.sCp; p.c_scale = o.c_scale; p.c_scale_zs = o.cs_zs; p.c_scale_ms = o.cs_ms;
         p.amax_out = o.amax; p.amax_zs = o.amax_zs; p.amax_row_slot = o.amax_row_slot; p.amax_col_min = o.amax_col_min;
         p.bias = o.bias; p.R = o.R; p.ldr = N; p.sR = o.sC;
-        p.M = M; p.N = N; p.K = K; p.nz = nz; p.ztab = zt; p.act = o.act; p.alpha = 1.0f; p.group_m = 0;
+        p.M = M; p.N = N; p.K = K; p.nz = nz; p.ztab = zt; p.row_tab = o.row_tab; p.act = o.act; p.alpha = 1.0f; p.group_m = 0;
         return launch_gemm_f16x3(p, s, "w2v2_gemm");
     }
     // A = all `rows` encoder rows of K columns as panels, each row with its own scale
@@ -1546,6 +1595,13 @@ struct Forward {
         GemmA A;
         A.planes = planes; A.plane = (int64_t)G * T[i - 1] * C; A.lda = (int64_t)STRD[i] * C; A.sA = (int64_t)T[i - 1] * C;
         A.scale = cscale + (int64_t)(i - 1) * G; A.scale_zs = 1;
+        return A;
+    }
+    // A of conv i over the packed row space: row R of the GEMM starts at plane row 2 R; the scale comes by the row's window slot
+    GemmA conv_a_packed(const uint16_t* planes, int64_t plane, int i) const {
+        GemmA A;
+        A.planes = planes; A.plane = plane; A.lda = (int64_t)STRD[i] * C;
+        A.scale = cscale + (int64_t)(i - 1) * G;
         return A;
     }
     GemmB weights_b(int64_t planes_off, int64_t scale_off) const { return GemmB{planes_at(planes_off), ws + scale_off}; }
@@ -1623,7 +1679,7 @@ struct Forward {
         }
         return RSAF_OK;
     }
-    // conv i of the windows g0 .. g0 + g - 1: every window keeps the longest window's row allotment (batch stride T[i] rows)
+    // layer mode: conv i of the windows g0 .. g0 + g - 1, one batch per window: every window keeps the longest window's row allotment (batch stride T[i] rows)
     // and has its own row count (ztab); the last layer writes its rows packed (window w at row row0[w])
     int conv_gemm(int i, const uint16_t* a_planes, Out& o, int g0, int g, const int* Tg) {
         if (i == 6) { o.Cf = ws + W.c6; o.sC = 0; }
@@ -1652,41 +1708,60 @@ struct Forward {
         }
         return RSAF_OK;
     }
-    // 2-3 (group mode)
+    // 2-3 (group mode): the windows of the group packed along M (packed_in_rows above)
     int convs_group_norm(int g0, int g, const int* Tg) {
+        // rows of every layer's GEMM, and the tables behind them
+        int64_t M[7] = {};
+        for (int w = g0; w < g0 + g; ++w) {
+            int Tw_[7];
+            chunk_lengths(R.len[w], Tw_);
+            for (int i = 1; i < 7; ++i) M[i] += Tw_[i] + 1;
+        }
+        RSAF_CHECK_ARG(2 * M[1] + 1 < 0x7fffffffLL && rows < 0x7fffffffLL, "too many conv rows in one group");
+        PackBases bases{};
+        for (int i = 1; i < 7; ++i) bases.b[i] = packed_tab_base(G, T, i);
+        hipLaunchKernelGGL(w2v2_pack_offsets_kernel, dim3(1), dim3(64), 0, s, Tw + g0, n, g, G, coff);
+        hipLaunchKernelGGL(w2v2_pack_rows_kernel, dim3(g, 6), dim3(256), 0, s, Tw + g0, n, G, coff, row0 + g0, crow, bases);
+        RSAF_CHECK_HIP(hipGetLastError());
         // 2. conv0 + GroupNorm + GELU (stats pass, finalize, apply pass); the apply pass writes fp16 plane pairs
         const int slabs_g = (Tg[0] + STAT_SLAB - 1) / STAT_SLAB;
         RSAF_TRY(conv0_launch<false>(c, ws + W.xn, Wt + L.conv0, cbias, ws + W.part, nullptr, nullptr, nullptr, 0, g, R.maxlen, Tw + g0,
-                                      T[0], STAT_SLAB, slabs_g, s));
+                                      nullptr, T[0], STAT_SLAB, slabs_g, s));
         const int64_t tot = (int64_t)g * C;
         hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ws + W.part,
                            Wt + L.gng, Wt + L.gnb, ws + W.ab, camax, g, C, slabs_g, Tw + g0);
         RSAF_CHECK_HIP(hipGetLastError());
         RSAF_TRY(launch_scale_from_bound(camax, g, nullptr, 1.0f, nullptr, cscale, s));
         const int slab = 128;
-        RSAF_TRY(conv0_launch<true>(c, ws + W.xn, Wt + L.conv0, cbias, nullptr, ws + W.ab, cscale, planes_at(W.P), (int64_t)G * T[0] * C, g,
-                                     R.maxlen, Tw + g0, T[0], slab, (Tg[0] + slab - 1) / slab, s));
+        const int64_t plane_p = p_rows(G, T) * C, plane_q = q_rows(G, T) * C;
+        RSAF_TRY(conv0_launch<true>(c, ws + W.xn, Wt + L.conv0, cbias, nullptr, ws + W.ab, cscale, planes_at(W.P), plane_p, g,
+                                     R.maxlen, Tw + g0, coff + (G + 1), T[0], slab, (Tg[0] + slab - 1) / slab, s));
         // 3. conv1..6 as GEMMs over the channels-last sequence (lda = stride * C, K = taps * C) with fused GELU;
         //    the output goes out as planes (the next layer's A), the last one as fp32 rows for the LayerNorm.
         //    Scale of layer i's output, per window: |GELU(x)| <= |x| <= |a|_2 |w|_2 <= sqrt(K) max|a| max_n |w_n|_2 with
         //    max|a| = the largest |output| of layer i - 1, which that layer's epilogue reported (layer 0: the GroupNorm bound).
         uint16_t* cur = planes_at(W.P);
         uint16_t* nxt = planes_at(W.Q);
+        int64_t plane_cur = plane_p, plane_nxt = plane_q;
         for (int i = 1; i < 7; ++i) {
             Out o;
             o.act = ACT_GELU;
+            o.row_tab = crow + 2 * bases.b[i];
             if (i < 6) {
                 // (CONV_BIAS: + max |bias| of layer i)
                 RSAF_TRY(launch_scale_from_bound(camax + (int64_t)(i - 1) * G, g, reinterpret_cast<const float*>(wstat(wstat_conv(i - 1))),
                                                   sqrtf((float)(KERN[i] * C)) * 1.00001f, conv_bias ? cb_max + i : nullptr,
                                                   cscale + (int64_t)i * G, s));
-                o.Cp = nxt; o.c_plane = (int64_t)G * T[i] * C; o.sCp = (int64_t)T[i] * C; o.sC = (int64_t)T[i] * C;
-                o.c_scale = cscale + (int64_t)i * G; o.cs_zs = 1; o.cs_ms = 0;
+                o.Cp = nxt; o.c_plane = plane_nxt;
+                o.c_scale = cscale + (int64_t)i * G;
                 o.amax = camax + (int64_t)i * G;
+            } else {
+                o.Cf = ws + W.c6;
             }
-            o.amax_zs = 1;
-            RSAF_TRY(conv_gemm(i, cur, o, g0, g, Tg));
+            o.bias = conv_bias ? cbias + (int64_t)i * C : nullptr;
+            RSAF_TRY(gemm3(conv_a_packed(cur, plane_cur, i), weights_b(W.wp_conv[i - 1], W.ws_conv[i - 1]), o, (int)M[i], C, KERN[i] * C));
             std::swap(cur, nxt);
+            std::swap(plane_cur, plane_nxt);
         }
         return RSAF_OK;
     }

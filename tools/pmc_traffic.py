@@ -9,7 +9,8 @@ Wav2Vec2 GEMM kernel PER SHAPE beside the algorithmic bytes of that shape.
 
 Shapes: gemm_f16x3 runs persistent workgroups (one per CU), so the grid size no longer tells its shapes apart; every dispatch
 is labelled by its template variant (activation / outputs / residual, in the kernel name) and its position in the forward
-call: [conv1..5 (GELU -> planes), conv6 (GELU -> fp32)] per window group, feature projection, then per layer qkv (-> planes),
+call: [conv1..5 (GELU -> planes), conv6 (GELU -> fp32)] per window group - ONE launch per layer and group, the windows packed
+along M with one junk row each (csrc/w2v2.hip: packed_in_rows) -, feature projection, then per layer qkv (-> planes),
 out-projection (+R), ffn1 (GELU -> planes), ffn2 (+R).  The 512 x 128 tile configuration (the CNN-LSTM's GEMMs) is left out.
 The calls of a step and their window counts are replayed from the engine's own batching (w2v2.forward_windows).
 
@@ -91,7 +92,8 @@ def frames(n):
 def call_sequence(lens, conv_group=512, C=512, H=768, inter=3072, layers=12, pos_k=128, pos_g=16):
     """[(label, variant, algorithmic bytes)] of the gemm_f16x3 dispatches of one forward call, in launch order.
     Algorithmic bytes: every operand element once as two fp16 planes (4 B), outputs as fp32 (4 B) or planes (4 B), fp32
-    residual 4 B."""
+    residual 4 B.  A packed convolution (M = frames + one junk row per window) also reads its row table, 8 B per row; the junk
+    rows store nothing and the input rows they alone read are not counted."""
     n = len(lens)
     Tw = [frames(l) for l in lens]
     rows = sum(t[6] for t in Tw)
@@ -104,7 +106,8 @@ def call_sequence(lens, conv_group=512, C=512, H=768, inter=3072, layers=12, pos
             k = 3 if i <= 4 else 2
             a = 4.0 * C * sum(t[i - 1] for t in grp)
             o = 4.0 * C * sum(t[i] for t in grp)
-            seq.append((f"conv{i} (K = {k * C})", ("A", 1, i == 6, i != 6, False), a + o + 4.0 * C * k * C))
+            M = sum(t[i] + 1 for t in grp)
+            seq.append((f"conv{i} (K = {k * C})", ("A", 1, i == 6, i != 6, False), a + o + 4.0 * C * k * C + 8.0 * M))
     alg = lambda nn, kk, resid: 4.0 * (rows * kk + nn * kk) + rows * nn * (4.0 + 4.0 * resid)      # noqa: E731
     seq.append(("feature projection", ("A", 0, True, False, False), alg(H, C, 0)))
     # (the positional convolution is its own kernel since round 4: posconv_f16x3_kernel, listed under other_kernels)
