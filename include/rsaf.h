@@ -250,6 +250,73 @@ int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, 
 int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels,
                                       int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
 
+/* ---- Rest of the training step: cross-entropy, Adam and BatchNorm running statistics, one launch per group ------
+ * What the reference's loop does around the model (src/dl_cv_strategies.py:122-125,236-248): nn.CrossEntropyLoss()
+ * with its defaults on the logits, torch.optim.Adam(model.parameters()).step(), and nn.BatchNorm1d's update of its
+ * running statistics.  Each entry takes K <= RSAF_CNNLSTM_GROUP_MAX items (host array) and issues ONE launch.
+ *
+ * rsaf_ce_loss_group: loss_out[0] = mean over the B rows of (logsumexp(logits[b]) - logits[b][labels[b]]), computed
+ * with the row maximum subtracted; dlogits_out [B][nc] = (softmax - onehot) / B, or NULL (validation passes: the
+ * loss alone, same bits).  Any num_classes >= 2.  A label outside [0, num_classes) makes the item's loss NaN and is
+ * never used as an index. */
+typedef struct {
+    const float* logits;           /* [B][num_classes] */
+    const int64_t* labels;         /* [B] */
+    int B;
+    float* loss_out;               /* one float */
+    float* dlogits_out;            /* [B][num_classes] or NULL */
+} rsaf_ce_loss_item;
+int rsaf_ce_loss_group(const rsaf_ce_loss_item* items_host, int K, int num_classes, rsaf_stream_t stream);
+
+/* rsaf_cnnlstm_adam_group: the published Adam update (bias-corrected moments, eps outside the square root, no weight
+ * decay, no amsgrad) of K replicas of one architecture, on the parameters in their natural torch layouts.
+ * The parameters of a replica are numbered in blob order, rsaf_cnnlstm_adam_param_count() of them:
+ *   per convolution (five, or four when input_dim == channels): weight [Cout][Cin][k], bias, BN weight, BN bias;
+ *   per LSTM layer: weight_ih, weight_ih_reverse, bias_ih, bias_hh, bias_ih_reverse, bias_hh_reverse, weight_hh,
+ *   weight_hh_reverse;  then attention weight, attention bias, fc weight, fc bias.
+ * `table`: DEVICE array of device pointers, [3][P] = parameter, exp_avg, exp_avg_sq of every parameter (float32,
+ * contiguous; entries of skipped parameters are not read), or [4][P] with the gradients in the parameters' layouts
+ * as fourth row when `grads` is NULL.  Otherwise `grads` is a gradient blob as rsaf_cnnlstm_train_backward_group
+ * wrote it: the conv kernels are read tap-major, and b_ih and b_hh of a direction both receive the gradient of
+ * their sum.  Bit i of `skip` leaves parameter i and its moments as they are (requires_grad = False, or no gradient).
+ * lr, betas, eps and the 1-based `step` of the bias corrections are per item.  Items must not share parameters or
+ * moments.
+ *
+ * rsaf_cnnlstm_pack_params_group: params = the blob of rsaf_cnnlstm_train_forward, written from the parameters where
+ * they live (row 0 of `table`): conv kernels tap-major, b_ih + b_hh summed.  The padding floats between segments are
+ * not written.  One launch at the head of a step replaces the host-side packing, and since the blob is rebuilt from
+ * the parameters every step, no edit of them (load_state_dict, an in-place change, also one through `.data` that no
+ * version counter sees) can leave it stale. */
+typedef struct {
+    const float* grads;            /* gradient blob, or NULL: gradients from the table's fourth row */
+    const void* const* table;      /* device array [3][P] or [4][P] of device pointers */
+    uint64_t skip;
+    double lr, beta1, beta2, eps;
+    int64_t step;
+} rsaf_cnnlstm_adam_item;
+typedef struct {
+    const void* const* table;      /* device array [>= 1][P] of device pointers: row 0 = the parameters */
+    float* params;                 /* parameter blob, written */
+} rsaf_cnnlstm_pack_item;
+int rsaf_cnnlstm_pack_params_group(const rsaf_cnnlstm_pack_item* items_host, int K, int input_dim, int channels,
+                                   int hidden, int num_classes, int lstm_layers, rsaf_stream_t stream);
+int rsaf_cnnlstm_adam_param_count(int input_dim, int channels, int hidden, int num_classes, int lstm_layers);
+int rsaf_cnnlstm_adam_group(const rsaf_cnnlstm_adam_item* items_host, int K, int input_dim, int channels, int hidden,
+                            int num_classes, int lstm_layers, rsaf_stream_t stream);
+
+/* rsaf_bn_running_stats_group: running = (1 - momentum) * running + momentum * batch value for the five BatchNorm
+ * layers of a replica, from the [5][3][C] statistics of the step (bn_stats_out above); the batch variance is scaled
+ * by `unbias[i]` = n / (n - 1), n the rows that layer saw.  A layer whose running_mean is NULL is left out (no
+ * shortcut BatchNorm when input_dim == channels; track_running_stats = False). */
+typedef struct {
+    const float* stats;            /* [5][3][C] */
+    float* running_mean[5];
+    float* running_var[5];
+    double momentum[5];
+    double unbias[5];
+} rsaf_bn_running_item;
+int rsaf_bn_running_stats_group(const rsaf_bn_running_item* items_host, int K, int channels, rsaf_stream_t stream);
+
 /* ---- Group inference forward: K independent eval-mode forwards of one architecture in one call -----------------
  * The other half of the reference's loops: the validation pass of every epoch (src/dl_cv_strategies.py:131-139) and
  * _eval_model (:183-194).  No weight changes between the batches of such a pass, so every batch of every model is an

@@ -40,6 +40,28 @@ class ForwardItem(C.Structure):
     _fields_ = [("x", _P), ("B", _I), ("T", _I), ("weights", _P), ("workspace", _P), ("workspace_bytes", _L), ("logits", _P)]
 
 
+class CeLossItem(C.Structure):
+    """``rsaf_ce_loss_item``: logits and labels of one replica, its loss and (optionally) the gradient of its logits."""
+    _fields_ = [("logits", _P), ("labels", _P), ("B", _I), ("loss_out", _P), ("dlogits_out", _P)]
+
+
+class AdamItem(C.Structure):
+    """``rsaf_cnnlstm_adam_item``: one replica of a group Adam step (``table``: device array of device pointers)."""
+    _fields_ = [("grads", _P), ("table", _P), ("skip", C.c_uint64), ("lr", C.c_double),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", _L)]
+
+
+class PackItem(C.Structure):
+    """``rsaf_cnnlstm_pack_item``: the pointer table of one replica's parameters and the blob to write."""
+    _fields_ = [("table", _P), ("params", _P)]
+
+
+class BnRunningItem(C.Structure):
+    """``rsaf_bn_running_item``: the five BatchNorm layers of one replica (NULL ``running_mean``: layer left out)."""
+    _fields_ = [("stats", _P), ("running_mean", _P * 5), ("running_var", _P * 5), ("momentum", C.c_double * 5),
+                ("unbias", C.c_double * 5)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -76,6 +98,11 @@ SIGNATURES = {
     "rsaf_cnnlstm_train_group_max": (_I, []),
     "rsaf_cnnlstm_train_forward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_cnnlstm_train_backward_group": (_I, [C.POINTER(TrainItem), _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_ce_loss_group": (_I, [C.POINTER(CeLossItem), _I, _I, _P]),
+    "rsaf_cnnlstm_pack_params_group": (_I, [C.POINTER(PackItem), _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_adam_param_count": (_I, [_I, _I, _I, _I, _I]),
+    "rsaf_cnnlstm_adam_group": (_I, [C.POINTER(AdamItem), _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_bn_running_stats_group": (_I, [C.POINTER(BnRunningItem), _I, _I, _P]),
     "rsaf_cnnlstm_forward_group": (_I, [C.POINTER(ForwardItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),

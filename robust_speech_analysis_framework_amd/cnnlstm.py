@@ -567,18 +567,12 @@ class _TrainGroupStep(torch.autograd.Function):
         return (None, None, None, *out)
 
 
-def cnnlstm_train_group(models, xs, masks=None):
-    """One training-mode forward of K independent ``CNNLSTM`` replicas (same ``dims`` and activation; own weights, own
-    batch ``xs[k]`` of own shape [B_k, T_k, D]) -> list of K logits tensors.  Sum the K losses and call ``backward()``
-    once: the replicas share nothing, so each model's ``.grad`` is the gradient of its own loss, and an output that
-    stays out of the loss leaves its model without gradients.  Logits, gradients and BatchNorm buffers are those of K
-    separate ``model(x)`` steps, bit for bit; the LSTM recurrences of all replicas run in one launch per layer and pass.
-
-    ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
-    model's ``forced_masks`` if set and draws them from torch's device RNG otherwise, replica by replica."""
+def _check_train_group(models, xs, masks, who):
+    """Argument checks of a group training step; returns (models, float32 contiguous inputs, one mask set per replica:
+    ``masks[k]``, else the model's ``forced_masks``, else drawn from torch's device RNG, replica by replica)."""
     models, xs = list(models), list(xs)
     if not models:
-        raise ValueError("cnnlstm_train_group needs at least one replica")
+        raise ValueError(f"{who} needs at least one replica")
     if len(models) != len(xs):
         raise ValueError(f"{len(models)} models but {len(xs)} inputs")
     if masks is not None and len(masks) != len(models):
@@ -607,7 +601,7 @@ def cnnlstm_train_group(models, xs, masks=None):
             raise ValueError(f"replica {k}: Expected more than 1 value per channel when training")
     for k, x in enumerate(xs):
         if not x.is_cuda:
-            raise _lib.RsafError(f"cnnlstm_train_group needs HIP (cuda) tensors (replica {k}): there is no CPU fallback")
+            raise _lib.RsafError(f"{who} needs HIP (cuda) tensors (replica {k}): there is no CPU fallback")
     xs = [x.detach().to(torch.float32).contiguous() for x in xs]
     mks = []
     for k, (m, x) in enumerate(zip(models, xs)):
@@ -615,8 +609,417 @@ def cnnlstm_train_group(models, xs, masks=None):
         if mk is None:
             mk = m.forced_masks if m.forced_masks is not None else draw_masks(m, x.shape[0], x.shape[1], x.device)
         mks.append(mk)
+    return models, xs, mks
+
+
+def cnnlstm_train_group(models, xs, masks=None):
+    """One training-mode forward of K independent ``CNNLSTM`` replicas (same ``dims`` and activation; own weights, own
+    batch ``xs[k]`` of own shape [B_k, T_k, D]) -> list of K logits tensors.  Sum the K losses and call ``backward()``
+    once: the replicas share nothing, so each model's ``.grad`` is the gradient of its own loss, and an output that
+    stays out of the loss leaves its model without gradients.  Logits, gradients and BatchNorm buffers are those of K
+    separate ``model(x)`` steps, bit for bit; the LSTM recurrences of all replicas run in one launch per layer and pass.
+
+    ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
+    model's ``forced_masks`` if set and draws them from torch's device RNG otherwise, replica by replica."""
+    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_group")
     params = [p for m in models for _, _, _, outs in _train_segments(m)[0] for p, _ in outs]
     return list(_TrainGroupStep.apply(models, xs, mks, *params))
+
+
+# ---- fused training step: cross-entropy, Adam and the running statistics in HIP ------------------------------------------
+# Around the model the reference's loop runs ``nn.CrossEntropyLoss()``, ``loss.backward()`` and ``Adam.step()``
+# (``src/dl_cv_strategies.py:122-125,236-248``).  Through autograd that costs, per replica and step, the packing of the
+# parameter blob, the unpacking of the gradient blob, the BatchNorm buffer updates and the loss and optimizer kernels of
+# torch: elementwise work on a few hundred thousand floats spread over 100+ small ops.  Here the blob is written from the
+# parameters where they live (``rsaf_cnnlstm_pack_params_group``), ``rsaf_cnnlstm_adam_group`` reads the gradient blob and
+# updates the parameters in their torch layouts, the loss and its gradient come from ``rsaf_ce_loss_group`` and the running
+# statistics from ``rsaf_bn_running_stats_group``: one launch each per group step.
+
+def _adam_order(model):
+    """The parameters in the numbering of ``rsaf_cnnlstm_adam_group`` (blob order; include/rsaf.h)."""
+    order = [p for _, _, _, outs in _train_segments(model)[0] for p, _ in outs]
+    d = model.dims
+    n = int(_lib.load().rsaf_cnnlstm_adam_param_count(d["input_dim"], d["channels"], d["hidden"], d["num_classes"], d["layers"]))
+    if n != len(order) or len(order) != len(list(model.parameters())):
+        raise _lib.RsafError(f"CNNLSTM has {len(list(model.parameters()))} parameters, {len(order)} of them in the blob, "
+                             f"but rsaf_cnnlstm_adam_group numbers {n}")
+    return order
+
+
+def _pointer_table(rows, device):
+    """Device int64 tensor of device pointers; the host copy travels through pinned staging on the current stream."""
+    return torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+
+
+class FusedAdam(torch.optim.Optimizer):
+    """``torch.optim.Adam(model.parameters(), lr, betas, eps)`` for one ``CNNLSTM`` on the HIP path: the whole update of
+    the model is one launch of ``rsaf_cnnlstm_adam_group`` (published Adam: bias-corrected moments, eps outside the
+    square root; no weight decay, no amsgrad).  ``param_groups[0]['lr']`` is read at every step, so the schedulers of
+    ``torch.optim.lr_scheduler`` drive it unchanged; ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.Adam``'s
+    format (per parameter ``step``, ``exp_avg``, ``exp_avg_sq``) in both directions.
+
+    ``step()`` consumes ordinary ``.grad`` tensors (a parameter without one is skipped, as torch does), so the
+    reference's loop works with only the optimizer swapped.  ``cnnlstm_train_step_group`` feeds the gradient blob of the
+    group backward to the same kernel and never touches ``.grad``.
+
+    The kernels reach the parameters and moments through a device table of pointers, cached while the pointers are
+    stable (``.to()`` or a loaded optimizer state rebuild it).  They write through raw pointers, so after every step the
+    versions of everything written are bumped: ``packed_weights()`` and every other version-keyed cache see the change."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+        if not isinstance(model, CNNLSTM):
+            raise ValueError(f"FusedAdam: model must be a CNNLSTM, got {type(model).__name__}")
+        if weight_decay != 0:
+            raise ValueError("FusedAdam: weight_decay is not supported (the reference uses Adam's default, 0)")
+        if amsgrad:
+            raise ValueError("FusedAdam: amsgrad is not supported")
+        if maximize:
+            raise ValueError("FusedAdam: maximize is not supported")
+        if not 0.0 <= lr:
+            raise ValueError(f"FusedAdam: invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"FusedAdam: invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdam: invalid betas: {betas}")
+        params = list(model.parameters())
+        if any(not p.is_cuda for p in params):
+            raise ValueError("FusedAdam: the CNNLSTM must be on a HIP device (model.to('cuda') first): there is no CPU fallback")
+        if any(p.dtype != torch.float32 for p in params):
+            raise ValueError("FusedAdam: the parameters must be float32")
+        # the keys of torch.optim.Adam's own param_groups, so that state dicts load in both directions
+        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).defaults)
+        super().__init__(params, defaults)
+        self.model = model
+        self._order = _adam_order(model)
+        self._steps = None                  # step count per parameter of _order (host mirror of state[p]['step']), None = unknown
+        self._state_gen = 0                 # bumped whenever a moment tensor is created or replaced
+        self._table = self._table_key = None
+        self._blob = None                   # blob buffer of the fused step, rewritten from the parameters every step
+
+    # -- optimizer state ------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._steps = None
+        self._state_gen += 1
+
+    def _hyper(self):
+        g = self.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("FusedAdam: weight_decay, amsgrad and maximize are not supported")
+        return float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+    def _ensure_state(self, skip):
+        """Moments of every parameter that is about to be updated (created as torch.optim.Adam creates them)."""
+        if self._steps is None:
+            for p in self._order:
+                st = self.state.get(p)
+                if st and not torch.is_tensor(st["step"]):
+                    st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+                if st and not (st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()
+                               and st["exp_avg"].dtype == st["exp_avg_sq"].dtype == torch.float32):
+                    st["exp_avg"] = st["exp_avg"].to(torch.float32).contiguous()
+                    st["exp_avg_sq"] = st["exp_avg_sq"].to(torch.float32).contiguous()
+            self._steps = [int(self.state[p]["step"]) if self.state.get(p) else 0 for p in self._order]
+        for i, p in enumerate(self._order):
+            if not (skip >> i) & 1 and "exp_avg" not in self.state[p]:
+                st = self.state[p]
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._state_gen += 1
+
+    def _rows(self):
+        rows = [[], [], []]
+        for p in self._order:
+            if not p.is_contiguous():
+                raise _lib.RsafError("FusedAdam: the parameters must be contiguous")
+            st = self.state.get(p) or {}
+            rows[0].append(p.data_ptr())
+            rows[1].append(st["exp_avg"].data_ptr() if "exp_avg" in st else 0)
+            rows[2].append(st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else 0)
+        return rows
+
+    def _cached_table(self):
+        """[3][P] device table of parameter / exp_avg / exp_avg_sq pointers, cached while the pointers are stable."""
+        tkey = (self._state_gen,) + tuple(p.data_ptr() for p in self._order)
+        if self._table is None or self._table_key != tkey:
+            self._table = _pointer_table(self._rows(), self._order[0].device)
+            self._table_key = tkey
+        return self._table
+
+    def _launches(self, skip):
+        """[(step, skip mask)]: one launch per distinct step count among the parameters to update (one, unless some
+        parameter sat out earlier steps: torch keeps a step count per parameter)."""
+        by_step = {}
+        for i in range(len(self._order)):
+            if not (skip >> i) & 1:
+                by_step[self._steps[i] + 1] = by_step.get(self._steps[i] + 1, 0) | (1 << i)
+        full = (1 << len(self._order)) - 1
+        return [(t, full & ~mask) for t, mask in sorted(by_step.items())]
+
+    def _stepped(self, skip):
+        live = [i for i in range(len(self._order)) if not (skip >> i) & 1]
+        torch._foreach_add_([self.state[self._order[i]]["step"] for i in live], 1)
+        for i in live:
+            self._steps[i] += 1
+
+    def _frozen(self):
+        skip = 0
+        for i, p in enumerate(self._order):
+            if not p.requires_grad:
+                skip |= 1 << i
+        return skip
+
+    def _blob_buffer(self):
+        """Zero-initialised buffer for the parameter blob (its padding floats are never written again)."""
+        device = self._order[0].device
+        if self._blob is None or self._blob.device != device:
+            total = train_param_offsets(self.model.dims)[1]
+            self._blob = torch.zeros(total, dtype=torch.float32, device=device)
+        return self._blob
+
+    def _written(self, tensors):
+        """The kernels wrote ``tensors`` through raw pointers: bump their versions, as an in-place torch op would."""
+        torch.autograd.graph.increment_version(tensors)
+
+    def packed_blob(self):
+        """The parameters in the blob layout of ``rsaf_cnnlstm_train_param_offsets``, packed on the device
+        (``rsaf_cnnlstm_pack_params_group``); equal to what ``_pack_train_blob`` builds with torch ops, bit for bit.
+        The tensor is the optimizer's own buffer and is overwritten by the next fused step."""
+        return _pack_group([self])[0]
+
+    @torch.no_grad()
+    def step_blob(self, grads):
+        """One Adam step from a gradient blob in the layout of ``rsaf_cnnlstm_train_param_offsets`` (what
+        ``rsaf_cnnlstm_train_backward_group`` writes); parameters with ``requires_grad = False`` are left alone."""
+        total = train_param_offsets(self.model.dims)[1]
+        if not grads.is_cuda or grads.dtype != torch.float32 or grads.shape != (total,) or not grads.is_contiguous():
+            raise ValueError(f"expected a contiguous float32 HIP (cuda) gradient blob of {total} floats")
+        skip = self._frozen()
+        if skip == (1 << len(self._order)) - 1:
+            return
+        self._ensure_state(skip)
+        _adam_group([(self, grads, self._cached_table(), skip)])
+        self._written([p for i, p in enumerate(self._order) if not (skip >> i) & 1])
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        skip, grads = 0, []
+        for i, p in enumerate(self._order):
+            g = p.grad
+            if g is None:
+                skip |= 1 << i
+                grads.append(None)
+                continue
+            if g.is_sparse or not g.is_cuda:
+                raise _lib.RsafError("FusedAdam: gradients must be dense HIP (cuda) tensors")
+            grads.append(g.to(torch.float32).contiguous())
+        if skip == (1 << len(self._order)) - 1:
+            return loss
+        self._ensure_state(skip)
+        rows = self._rows() + [[g.data_ptr() if g is not None else 0 for g in grads]]
+        table = _pointer_table(rows, self._order[0].device)
+        _adam_group([(self, None, table, skip)])
+        self._written([p for i, p in enumerate(self._order) if not (skip >> i) & 1])
+        return loss
+
+
+def _adam_group(entries):
+    """``entries``: [(optimizer, gradient blob or None, pointer table, skip mask)] of one architecture ->
+    ``rsaf_cnnlstm_adam_group`` in chunks of ``train_group_max()``; a replica whose parameters stand at different step
+    counts takes one launch per count."""
+    lib = _lib.load()
+    gmax = train_group_max()
+    d = entries[0][0].model.dims
+    plans = [opt._launches(skip) for opt, _, _, skip in entries]
+    for j in range(max(len(pl) for pl in plans)):
+        live = [(e, pl[j]) for e, pl in zip(entries, plans) if j < len(pl)]
+        for c0 in range(0, len(live), gmax):
+            chunk = live[c0:c0 + gmax]
+            items = (_lib.AdamItem * len(chunk))()
+            for it, ((opt, grads, table, _), (t, mask)) in zip(items, chunk):
+                it.grads = grads.data_ptr() if grads is not None else None
+                it.table, it.skip, it.step = table.data_ptr(), mask, t
+                it.lr, it.beta1, it.beta2, it.eps = opt._hyper()
+            _lib.check(lib.rsaf_cnnlstm_adam_group(items, len(chunk), d["input_dim"], d["channels"], d["hidden"],
+                                                   d["num_classes"], d["layers"], _lib.stream_ptr(None)), "rsaf_cnnlstm_adam_group")
+    for opt, _, _, skip in entries:
+        opt._stepped(skip)
+
+
+def _pack_group(optimizers):
+    """The parameter blobs of the optimizers' models, written on the device from the parameters where they live: one
+    launch of ``rsaf_cnnlstm_pack_params_group`` per chunk of ``train_group_max()``."""
+    lib = _lib.load()
+    gmax = train_group_max()
+    d = optimizers[0].model.dims
+    blobs = [opt._blob_buffer() for opt in optimizers]
+    tables = [opt._cached_table() for opt in optimizers]
+    for c0 in range(0, len(optimizers), gmax):
+        n = min(gmax, len(optimizers) - c0)
+        items = (_lib.PackItem * n)()
+        for j, it in enumerate(items):
+            it.table, it.params = tables[c0 + j].data_ptr(), blobs[c0 + j].data_ptr()
+        _lib.check(lib.rsaf_cnnlstm_pack_params_group(items, n, d["input_dim"], d["channels"], d["hidden"], d["num_classes"],
+                                                      d["layers"], _lib.stream_ptr(None)), "rsaf_cnnlstm_pack_params_group")
+    return blobs
+
+
+def ce_loss_group(logits, labels, with_grad=True):
+    """Mean-reduced cross-entropy of K (logits [B_k, nc], int64 labels [B_k]) pairs in one launch of
+    ``rsaf_ce_loss_group`` (``nn.CrossEntropyLoss()`` with its defaults) -> (losses [K] on the device, list of
+    d loss_k / d logits_k, or None without ``with_grad``).  Lists longer than ``train_group_max()`` are chunked."""
+    lib = _lib.load()
+    logits, labels = list(logits), list(labels)
+    if len(logits) != len(labels) or not logits:
+        raise ValueError(f"{len(logits)} logits but {len(labels)} label tensors")
+    nc, device = logits[0].shape[1], logits[0].device
+    labs = []
+    for k, (o, lab) in enumerate(zip(logits, labels)):
+        if not o.is_cuda:
+            raise _lib.RsafError(f"ce_loss_group needs HIP (cuda) tensors (item {k}): there is no CPU fallback")
+        if o.dim() != 2 or o.shape[1] != nc or o.dtype != torch.float32 or not o.is_contiguous():
+            raise ValueError(f"item {k}: expected contiguous float32 logits [B, {nc}], got {o.dtype} {tuple(o.shape)}")
+        if lab.dim() != 1 or lab.shape[0] != o.shape[0] or lab.dtype.is_floating_point:
+            raise ValueError(f"item {k}: expected {o.shape[0]} integer class labels, got {lab.dtype} {tuple(lab.shape)}")
+        labs.append(lab.to(device, torch.int64).contiguous())
+    losses = torch.empty(len(logits), dtype=torch.float32, device=device)
+    dl = [torch.empty_like(o) for o in logits] if with_grad else None
+    gmax = train_group_max()
+    for c0 in range(0, len(logits), gmax):
+        n = min(gmax, len(logits) - c0)
+        items = (_lib.CeLossItem * n)()
+        for j, it in enumerate(items):
+            k = c0 + j
+            it.logits, it.labels, it.B = logits[k].data_ptr(), labs[k].data_ptr(), logits[k].shape[0]
+            it.loss_out = losses.data_ptr() + 4 * k
+            it.dlogits_out = dl[k].data_ptr() if with_grad else None
+        _lib.check(lib.rsaf_ce_loss_group(items, n, nc, _lib.stream_ptr(None)), "rsaf_ce_loss_group")
+    return losses, dl
+
+
+def _bn_running_group(reps, channels):
+    """Running statistics of the replicas ``reps`` (dicts with model, stats, B, T) after a step: one launch of
+    ``rsaf_bn_running_stats_group`` per chunk, ``num_batches_tracked`` incremented on the host side in one foreach op.
+    A replica with a ``momentum=None`` layer (cumulative average) takes the torch ops of ``_update_running_stats``.
+    Returns the buffers written."""
+    lib = _lib.load()
+    fused, counters, written = [], [], []
+    for r in reps:
+        bns = [bn for bn in _bn_modules(r["model"]) if bn is not None and bn.track_running_stats and bn.running_mean is not None]
+        written += [t for bn in bns for t in (bn.running_mean, bn.running_var)]
+        if any(bn.momentum is None for bn in bns):
+            _update_running_stats(r["model"], r["stats"], r["B"], r["T"])
+        elif bns:
+            fused.append(r)
+            counters += [bn.num_batches_tracked for bn in bns]
+    gmax = train_group_max()
+    for c0 in range(0, len(fused), gmax):
+        chunk = fused[c0:c0 + gmax]
+        items = (_lib.BnRunningItem * len(chunk))()
+        for it, r in zip(items, chunk):
+            B, T = r["B"], r["T"]
+            it.stats = r["stats"].data_ptr()
+            for i, (bn, n) in enumerate(zip(_bn_modules(r["model"]), (B * T, B * T, B * T, B * (T // 2), B * (T // 2)))):
+                if bn is None or not bn.track_running_stats or bn.running_mean is None:
+                    continue
+                if not (bn.running_mean.is_contiguous() and bn.running_var.is_contiguous()
+                        and bn.running_mean.dtype == bn.running_var.dtype == torch.float32):
+                    raise _lib.RsafError("the BatchNorm running statistics must be contiguous float32 tensors")
+                it.running_mean[i], it.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+                it.momentum[i], it.unbias[i] = float(bn.momentum), (n / (n - 1.0) if n > 1 else 1.0)
+        _lib.check(lib.rsaf_bn_running_stats_group(items, len(chunk), channels, _lib.stream_ptr(None)), "rsaf_bn_running_stats_group")
+    if counters:
+        torch._foreach_add_(counters, 1)
+    return written
+
+
+def _train_step_chunk(models, optimizers, xs, labels, masks):
+    """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k])."""
+    lib = _lib.load()
+    d, act, device = models[0].dims, models[0].activation_name, xs[0].device
+    K, nc, C = len(models), d["num_classes"], d["channels"]
+    rows = [x.shape[0] for x in xs]
+    logits_all = torch.empty((sum(rows), nc), dtype=torch.float32, device=device)
+    stats_all = torch.empty((K, 5, 3, C), dtype=torch.float32, device=device)
+    logits = list(torch.split(logits_all, rows))
+    blobs = _pack_group(optimizers)
+    reps = []
+    for k, (model, opt, x, mk) in enumerate(zip(models, optimizers, xs, masks)):
+        B, T, D = x.shape
+        blob = blobs[k]
+        a = (B, T, D, C, d["hidden"], d["layers"])
+        n_saved, n_scr = int(lib.rsaf_cnnlstm_train_saved_floats(*a)), int(lib.rsaf_cnnlstm_train_scratch_floats(*a))
+        if n_saved < 0 or n_scr < 0:
+            raise ValueError("sequence length must be >= 2")
+        if model._train_scratch is None or model._train_scratch.numel() < n_scr or model._train_scratch.device != device:
+            model._train_scratch = torch.empty(n_scr, dtype=torch.float32, device=device)
+        reps.append({"model": model, "x": x, "B": B, "T": T, "blob": blob, "masks": mk, "lstm_ptrs": _lstm_mask_ptrs(mk),
+                     "scratch": model._train_scratch, "saved": torch.empty(n_saved, dtype=torch.float32, device=device),
+                     "logits": logits[k], "stats": stats_all[k]})
+    _group_call(lib.rsaf_cnnlstm_train_forward_group, "rsaf_cnnlstm_train_forward_group", reps, d, act, False)
+    losses, dl = ce_loss_group(logits, labels)
+    grads = torch.zeros((K, blob.numel()), dtype=torch.float32, device=device)       # one zero fill for the group
+    for k, r in enumerate(reps):
+        r["dlogits"], r["grads"] = dl[k], grads[k]
+    _group_call(lib.rsaf_cnnlstm_train_backward_group, "rsaf_cnnlstm_train_backward_group", reps, d, act, True)
+    entries = []
+    for k, opt in enumerate(optimizers):
+        skip = opt._frozen()
+        opt._ensure_state(skip)
+        entries.append((opt, grads[k], opt._cached_table(), skip))
+    live = [e for e in entries if e[3] != (1 << len(e[0]._order)) - 1]
+    if live:
+        _adam_group(live)
+    buffers = _bn_running_group(reps, C)
+    for opt, _, _, skip in entries:
+        own = set(id(t) for t in opt.model.buffers())
+        opt._written([p for i, p in enumerate(opt._order) if not (skip >> i) & 1] + [t for t in buffers if id(t) in own])
+    return losses, logits
+
+
+def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
+    """One whole training step of K independent ``CNNLSTM`` replicas, ``optimizers[k]`` the ``FusedAdam`` of ``models[k]``:
+    group forward in training mode, ``nn.CrossEntropyLoss()`` (defaults) of ``labels[k]``, group backward, Adam and the
+    BatchNorm running statistics -> ``(losses [K] on the device, [logits_k])``.  No autograd graph is built and ``.grad``
+    is not touched; the packing of the parameter blobs, the loss, the optimizer and the running statistics are one launch
+    each for the group.  A parameter with ``requires_grad = False`` keeps its value and its moments.
+
+    Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` are honoured, and
+    masks are drawn replica by replica in the same order, so with equal RNG state both paths see equal masks).  Lists
+    longer than ``train_group_max()`` are split into chunks of that size."""
+    optimizers, labels = list(optimizers), list(labels)
+    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group")
+    if not (len(optimizers) == len(labels) == len(models)):
+        raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(labels)} label tensors")
+    for k, (m, opt) in enumerate(zip(models, optimizers)):
+        if not isinstance(opt, FusedAdam) or opt.model is not m:
+            raise ValueError(f"optimizers[{k}] is not the FusedAdam of models[{k}]")
+    for k, (x, lab) in enumerate(zip(xs, labels)):
+        if lab.dim() != 1 or lab.shape[0] != x.shape[0] or lab.dtype.is_floating_point:
+            raise ValueError(f"replica {k}: expected {x.shape[0]} integer class labels, got {lab.dtype} {tuple(lab.shape)}")
+    gmax = train_group_max()
+    losses, logits = [], []
+    with torch.no_grad():
+        for c0 in range(0, len(models), gmax):
+            s = slice(c0, c0 + gmax)
+            ls, lg = _train_step_chunk(models[s], optimizers[s], xs[s], labels[s], mks[s])
+            losses.append(ls)
+            logits += lg
+    return (losses[0] if len(losses) == 1 else torch.cat(losses)), logits
+
+
+def _fused_step_applies(optimizers, models, loss_fn):
+    """The lockstep loops take the fused step when the loss is ``nn.CrossEntropyLoss`` with its default options and
+    every optimizer is the ``FusedAdam`` of its model."""
+    if type(loss_fn) is not nn.CrossEntropyLoss or loss_fn.weight is not None or loss_fn.reduction != "mean" \
+            or loss_fn.label_smoothing != 0 or loss_fn.ignore_index != -100:
+        return False
+    return all(isinstance(o, FusedAdam) and o.model is m for o, m in zip(optimizers, models))
 
 
 # ---- group eval forward: K independent eval-mode forwards of one architecture in one call --------------------------------
@@ -743,7 +1146,9 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     step come to the host in one copy.
 
     Parameters, buffers and losses equal those of K sequential trainings bit for bit as long as the replicas see the
-    same batches and dropout masks.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
+    same batches and dropout masks.  When ``loss_fn`` is ``nn.CrossEntropyLoss()`` with its default options and every
+    optimizer of the call is the ``FusedAdam`` of its model, a step is one ``cnnlstm_train_step_group`` call (loss, Adam and running
+    statistics in HIP, no autograd graph); anything else runs the loop above as written.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
     its permutations from torch's global RNG: in lock step the K loaders draw in a different order than K sequential
     trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  The same holds
     for dropout masks, which come from the device RNG replica by replica within a step."""
@@ -751,6 +1156,7 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
     histories = [[] for _ in models]
+    fused = _fused_step_applies(optimizers, models, loss_fn)      # decided once for the call: no replica changes path mid-epoch
     for _ in range(epochs):
         for m in models:
             m.train()
@@ -763,14 +1169,18 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
                 break
             xs = [batches[k][0].to(device) for k in live]
             labs = [batches[k][1].to(device) for k in live]
-            for k in live:
-                optimizers[k].zero_grad()
-            outs = cnnlstm_train_group([models[k] for k in live], xs)
-            losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
-            torch.stack(losses).sum().backward()
-            for k in live:
-                optimizers[k].step()
-            for k, v in zip(live, torch.stack([ls.detach() for ls in losses]).tolist()):
+            if fused:
+                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs)[0]
+            else:
+                for k in live:
+                    optimizers[k].zero_grad()
+                outs = cnnlstm_train_group([models[k] for k in live], xs)
+                losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
+                torch.stack(losses).sum().backward()
+                for k in live:
+                    optimizers[k].step()
+                step_losses = torch.stack([ls.detach() for ls in losses])
+            for k, v in zip(live, step_losses.tolist()):
                 total[k] += v
                 count[k] += 1
         for k in range(len(models)):
@@ -858,14 +1268,22 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
             train_hist[k].append(h[0])
         for k in running:
             models[k].eval()
-        tags, losses = [], []
+        tags, outs, labs = [], [], []
+        fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], loss_fn)
         with torch.no_grad():
             pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
             for k, out, lab in _grouped_eval_batches(pairs, device):
                 tags.append(k)
-                losses.append(loss_fn(out, lab))
+                outs.append(out)
+                labs.append(lab)
+            if not outs:
+                losses = []
+            elif fused and all(o.shape[0] > 0 for o in outs):           # the losses of the pass in group launches, no gradient
+                losses = ce_loss_group(outs, labs, with_grad=False)[0].tolist()
+            else:
+                losses = torch.stack([loss_fn(o, lab) for o, lab in zip(outs, labs)]).tolist()
         val_loss, count = {k: 0 for k in running}, {k: 0 for k in running}
-        for k, v in zip(tags, torch.stack(losses).tolist() if losses else []):
+        for k, v in zip(tags, losses):
             val_loss[k] += v
             count[k] += 1
         still = []

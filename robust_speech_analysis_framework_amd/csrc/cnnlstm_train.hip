@@ -1318,6 +1318,277 @@ static int run_backward(Replica* reps, int K, const Dims& d, bool grouped) {
     return RSAF_OK;
 }
 
+// ---- the rest of the step: blob packing, cross-entropy, Adam, BatchNorm running statistics; one launch per group each
+// All four are elementwise work on at most a few hundred thousand floats per replica.  The item descriptors travel
+// by value in the kernel arguments, as the group recurrence kernels take theirs.
+
+// One workgroup per item.  Rows are few (a batch) and classes fewer, so every row is computed in double by one lane
+// and the row losses are summed by a fixed tree: the float results are the correctly rounded ones, deterministic.
+struct CeItem {
+    const float* logits;
+    const long long* labels;
+    float* loss;
+    float* dlogits;
+    int B;
+};
+struct CeGroup {
+    CeItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void ce_loss_group_kernel(const CeGroup g, int nc) {
+    const CeItem& it = g.item[blockIdx.x];
+    __shared__ double part[256];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < it.B; b += 256) {
+        const float* row = it.logits + (int64_t)b * nc;
+        float mx = row[0];
+        for (int c = 1; c < nc; ++c) mx = fmaxf(mx, row[c]);
+        double s = 0.0;
+        for (int c = 0; c < nc; ++c) s += exp((double)row[c] - (double)mx);
+        const long long lab = it.labels[b];
+        const bool ok = lab >= 0 && lab < nc;
+        const double lse = (double)mx + log(s);
+        acc += ok ? lse - (double)row[ok ? lab : 0] : __builtin_nan("");
+        if (it.dlogits) {
+            const double inv = 1.0 / (s * it.B);
+            for (int c = 0; c < nc; ++c) {
+                const double p = exp((double)row[c] - (double)mx) * inv;
+                it.dlogits[(int64_t)b * nc + c] = (float)(ok && c == lab ? p - 1.0 / it.B : p);
+            }
+        }
+    }
+    part[threadIdx.x] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) it.loss[0] = (float)(part[0] / it.B);
+}
+
+// Adam and the packing of the parameter blob.  A segment is one parameter tensor (ADAM_PLAIN, ADAM_CONV) or the
+// b_ih / b_hh pair of one direction (ADAM_BIAS) and maps to a run of the blob.  Threads walk the PARAMETER's index space
+// four floats at a time, so the parameter-side streams (p, m, v read and written) are full-width vector accesses; the
+// blob side (gradient read in adam_group_kernel, blob write in pack_group_kernel) is contiguous too except for conv
+// kernels, whose blob image is tap-major: there a wave's 256 consecutive [Cin][k] elements fall into k contiguous runs
+// of the blob, which it gathers or scatters by dword.
+enum { ADAM_PLAIN = 0, ADAM_CONV = 1, ADAM_BIAS = 2 };
+static const int ADAM_MAX_SEGS = 56;            // 5 * 4 + 4 layers * 6 + 4 = 48 at most
+static const int ADAM_BLOCK_FLOATS = 1024;      // 256 threads x 4
+
+struct AdamSeg {
+    int blob_off, n, block0;                    // first blob float | floats | first workgroup of the segment
+    int cin;                                    // ADAM_CONV: the kernel is [Cout][cin][taps] in torch, [Cout][taps][cin] in the blob
+    unsigned char kind, taps, pa, pb;           // parameter numbers (pb: ADAM_BIAS only)
+};
+struct AdamRep {
+    const float* grads;                         // gradient blob or NULL (gradients by the table's fourth row)
+    const unsigned long long* table;            // [3 or 4][P] device pointers
+    unsigned long long skip;
+    double step_size, b1, b2, eps, inv_sqrt_bc2;
+};
+struct AdamGroup {
+    AdamSeg seg[ADAM_MAX_SEGS];
+    AdamRep rep[RSAF_CNNLSTM_GROUP_MAX];
+    int nseg, P;
+};
+static_assert(sizeof(AdamGroup) <= 3584, "the descriptors must fit the kernel argument segment");
+
+__device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, const AdamRep& r) {
+    const double gd = g;
+    const double md = r.b1 * (double)m + (1.0 - r.b1) * gd;
+    const double vd = r.b2 * (double)v + (1.0 - r.b2) * gd * gd;
+    m = (float)md;
+    v = (float)vd;
+    return (float)((double)p - r.step_size * md / (sqrt(vd) * r.inv_sqrt_bc2 + r.eps));
+}
+
+struct AdamTensor {
+    float *p, *m, *v;
+    const float* g;                             // gradient in the parameter's layout, or NULL
+};
+
+__device__ __forceinline__ AdamTensor adam_tensor(const AdamGroup& G, const AdamRep& r, int idx) {
+    AdamTensor t;
+    t.p = reinterpret_cast<float*>(r.table[idx]);
+    t.m = reinterpret_cast<float*>(r.table[G.P + idx]);
+    t.v = reinterpret_cast<float*>(r.table[2 * G.P + idx]);
+    t.g = r.grads ? nullptr : reinterpret_cast<const float*>(r.table[3 * G.P + idx]);
+    return t;
+}
+
+__device__ __forceinline__ bool aligned16(const AdamTensor& t) {
+    return ((reinterpret_cast<uintptr_t>(t.p) | reinterpret_cast<uintptr_t>(t.m) | reinterpret_cast<uintptr_t>(t.v) |
+             reinterpret_cast<uintptr_t>(t.g)) & 15) == 0;
+}
+
+// blob index (relative to the segment) of element q of a conv kernel [Cout][cin][taps]
+__device__ __forceinline__ int conv_blob_index(int q, int cin, int taps) {
+    const int tap = q % taps, r = q / taps;
+    const int co = r / cin, ci = r - co * cin;
+    return (co * taps + tap) * cin + ci;
+}
+
+__global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) {
+    const AdamRep& r = G.rep[blockIdx.y];
+    int s = 0;
+    while (s + 1 < G.nseg && (int)blockIdx.x >= G.seg[s + 1].block0) ++s;
+    const AdamSeg sg = G.seg[s];
+    const bool skip_a = (r.skip >> sg.pa) & 1, skip_b = sg.kind != ADAM_BIAS || ((r.skip >> sg.pb) & 1);
+    if (skip_a && skip_b) return;
+    const int q0 = (((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x) * 4;
+    if (q0 >= sg.n) return;
+    const float* gblob = r.grads ? r.grads + sg.blob_off : nullptr;
+
+    if (sg.kind == ADAM_BIAS) {                 // the blob holds b_ih + b_hh: both receive the gradient of the sum
+        const AdamTensor a = adam_tensor(G, r, sg.pa), b = adam_tensor(G, r, sg.pb);
+        for (int q = q0; q < min(q0 + 4, sg.n); ++q) {
+            if (!skip_a) {
+                float m = a.m[q], v = a.v[q];
+                a.p[q] = adam_one(a.p[q], gblob ? gblob[q] : a.g[q], m, v, r);
+                a.m[q] = m; a.v[q] = v;
+            }
+            if (!skip_b) {
+                float m = b.m[q], v = b.v[q];
+                b.p[q] = adam_one(b.p[q], gblob ? gblob[q] : b.g[q], m, v, r);
+                b.m[q] = m; b.v[q] = v;
+            }
+        }
+        return;
+    }
+
+    const AdamTensor t = adam_tensor(G, r, sg.pa);
+    const bool conv = sg.kind == ADAM_CONV;
+    if (q0 + 4 <= sg.n && aligned16(t)) {
+        f32x4 p = *reinterpret_cast<const f32x4*>(t.p + q0);
+        f32x4 m = *reinterpret_cast<const f32x4*>(t.m + q0);
+        f32x4 v = *reinterpret_cast<const f32x4*>(t.v + q0);
+        f32x4 g;
+        if (t.g) g = *reinterpret_cast<const f32x4*>(t.g + q0);
+        else if (!conv) g = *reinterpret_cast<const f32x4*>(gblob + q0);
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j] = gblob[conv_blob_index(q0 + j, sg.cin, sg.taps)];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {           // constant indices after unrolling: the vectors stay in registers
+            float mj = m[j], vj = v[j];
+            p[j] = adam_one(p[j], g[j], mj, vj, r);
+            m[j] = mj; v[j] = vj;
+        }
+        *reinterpret_cast<f32x4*>(t.p + q0) = p;
+        *reinterpret_cast<f32x4*>(t.m + q0) = m;
+        *reinterpret_cast<f32x4*>(t.v + q0) = v;
+        return;
+    }
+    for (int q = q0; q < min(q0 + 4, sg.n); ++q) {            // tail of a segment, or tensors off the 16-byte grid
+        const int bi = conv ? conv_blob_index(q, sg.cin, sg.taps) : q;
+        float m = t.m[q], v = t.v[q];
+        t.p[q] = adam_one(t.p[q], t.g ? t.g[q] : gblob[bi], m, v, r);
+        t.m[q] = m; t.v[q] = v;
+    }
+}
+
+// The parameter blob of the next forward, read from the parameters where they live: one launch per group step instead of
+// ~35 slice assignments per replica, and nothing resident that an edit of the parameters could leave stale.
+struct PackRep {
+    const unsigned long long* table;            // [>= 1][P] device pointers: row 0 = the parameters
+    float* blob;
+};
+struct PackGroup {
+    AdamSeg seg[ADAM_MAX_SEGS];
+    PackRep rep[RSAF_CNNLSTM_GROUP_MAX];
+    int nseg, P;
+};
+
+__global__ __launch_bounds__(256) void pack_group_kernel(const PackGroup G) {
+    const PackRep& r = G.rep[blockIdx.y];
+    int s = 0;
+    while (s + 1 < G.nseg && (int)blockIdx.x >= G.seg[s + 1].block0) ++s;
+    const AdamSeg sg = G.seg[s];
+    const int q0 = (((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x) * 4;
+    if (q0 >= sg.n) return;
+    float* blob = r.blob + sg.blob_off;
+    const float* a = reinterpret_cast<const float*>(r.table[sg.pa]);
+    const float* b = sg.kind == ADAM_BIAS ? reinterpret_cast<const float*>(r.table[sg.pb]) : nullptr;
+    const bool conv = sg.kind == ADAM_CONV;
+    if (q0 + 4 <= sg.n && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) {
+        f32x4 p = *reinterpret_cast<const f32x4*>(a + q0);
+        if (b) p += *reinterpret_cast<const f32x4*>(b + q0);
+        if (!conv) *reinterpret_cast<f32x4*>(blob + q0) = p;
+        else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) blob[conv_blob_index(q0 + j, sg.cin, sg.taps)] = p[j];
+        }
+        return;
+    }
+    for (int q = q0; q < min(q0 + 4, sg.n); ++q)
+        blob[conv ? conv_blob_index(q, sg.cin, sg.taps) : q] = b ? a[q] + b[q] : a[q];
+}
+
+// the segments of one architecture, in the parameter numbering of rsaf_cnnlstm_adam_group (include/rsaf.h)
+static int make_adam_segs(const Dims& d, AdamSeg* segs, int* nseg, int64_t* blocks) {
+    const PLayout L = make_playout(d);
+    int n = 0, P = 0;
+    int64_t blk = 0;
+    auto add = [&](int kind, int64_t off, int64_t floats, int taps, int cin, int pa, int pb) {
+        AdamSeg& sg = segs[n++];
+        sg.blob_off = (int)off; sg.n = (int)floats; sg.block0 = (int)blk;
+        sg.cin = cin; sg.kind = (unsigned char)kind; sg.taps = (unsigned char)taps;
+        sg.pa = (unsigned char)pa; sg.pb = (unsigned char)pb;
+        blk += (floats + ADAM_BLOCK_FLOATS - 1) / ADAM_BLOCK_FLOATS;
+    };
+    auto conv = [&](const ConvP& c, int taps, int cin) {
+        add(taps > 1 ? ADAM_CONV : ADAM_PLAIN, c.w, (int64_t)d.C * taps * cin, taps, cin, P, 0);
+        add(ADAM_PLAIN, c.b, d.C, 1, 0, P + 1, 0);
+        add(ADAM_PLAIN, c.g, d.C, 1, 0, P + 2, 0);
+        add(ADAM_PLAIN, c.be, d.C, 1, 0, P + 3, 0);
+        P += 4;
+    };
+    conv(L.c1, 3, d.D);
+    if (d.D != d.C) conv(L.sc, 1, d.D);
+    conv(L.c2, 3, d.C); conv(L.c3, 3, d.C); conv(L.c4, 3, d.C);
+    for (int l = 0; l < d.L; ++l) {
+        const int64_t in = l == 0 ? d.C : 2 * d.H, nih = (int64_t)4 * d.H * in, nhh = (int64_t)4 * d.H * d.H;
+        add(ADAM_PLAIN, L.wih[l], nih, 1, 0, P, 0);
+        add(ADAM_PLAIN, L.wih[l] + nih, nih, 1, 0, P + 1, 0);
+        add(ADAM_BIAS, L.bsum[l], 4 * d.H, 1, 0, P + 2, P + 3);
+        add(ADAM_BIAS, L.bsum[l] + 4 * d.H, 4 * d.H, 1, 0, P + 4, P + 5);
+        add(ADAM_PLAIN, L.whh[l], nhh, 1, 0, P + 6, 0);
+        add(ADAM_PLAIN, L.whh[l] + nhh, nhh, 1, 0, P + 7, 0);
+        P += 8;
+    }
+    add(ADAM_PLAIN, L.watt, 2 * d.H, 1, 0, P, 0);
+    add(ADAM_PLAIN, L.batt, 1, 1, 0, P + 1, 0);
+    add(ADAM_PLAIN, L.wfc, (int64_t)d.NC * 2 * d.H, 1, 0, P + 2, 0);
+    add(ADAM_PLAIN, L.bfc, d.NC, 1, 0, P + 3, 0);
+    P += 4;
+    *nseg = n;
+    *blocks = blk;
+    return P;
+}
+
+struct BnRunItem {
+    const float* stats;
+    float* mean[5];
+    float* var[5];
+    double momentum[5], unbias[5];
+};
+struct BnRunGroup {
+    BnRunItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+// grid (C / 256, 5 layers, K)
+__global__ __launch_bounds__(256) void bn_running_group_kernel(const BnRunGroup g, int C) {
+    const BnRunItem& it = g.item[blockIdx.z];
+    const int i = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C || !it.mean[i]) return;
+    // running.mul_(1 - m).add_(batch, alpha = m [* n / (n - 1)]) with the scalars rounded to float as torch rounds them
+    const float keep = (float)(1.0 - it.momentum[i]), am = (float)it.momentum[i], av = (float)(it.momentum[i] * it.unbias[i]);
+    it.mean[i][c] = __fmaf_rn(am, it.stats[(i * 3 + 0) * C + c], __fmul_rn(it.mean[i][c], keep));
+    it.var[i][c] = __fmaf_rn(av, it.stats[(i * 3 + 1) * C + c], __fmul_rn(it.var[i][c], keep));
+}
+
 }  // namespace cnntrain
 }  // namespace rsaf
 
@@ -1407,6 +1678,119 @@ int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host,
     Replica reps[RSAF_CNNLSTM_GROUP_MAX];
     TRY(check_group(d, items_host, K, true, (hipStream_t)stream, __func__, reps));
     return run_backward(reps, K, d, true);
+}
+
+int rsaf_ce_loss_group(const rsaf_ce_loss_item* items_host, int K, int num_classes, rsaf_stream_t stream) {
+    RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    RSAF_CHECK_ARG(items_host, "items_host is NULL");
+    RSAF_CHECK_ARG(num_classes >= 2, "num_classes must be >= 2");
+    CeGroup g{};
+    double bytes = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const rsaf_ce_loss_item& it = items_host[k];
+        if (!(it.B >= 1 && (int64_t)it.B * num_classes <= 0x3fffffffLL)) return fail(RSAF_ERR_ARG, __func__, k, "batch must be >= 1 and B * num_classes < 2^30");
+        if (!(it.logits && it.labels && it.loss_out)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        g.item[k] = CeItem{it.logits, reinterpret_cast<const long long*>(it.labels), it.loss_out, it.dlogits_out, it.B};
+        bytes += (double)it.B * (num_classes * (it.dlogits_out ? 8 : 4) + 8);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_ce", s, 0.0, bytes);
+    hipLaunchKernelGGL(ce_loss_group_kernel, dim3(K), dim3(256), 0, s, g, num_classes);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_cnnlstm_adam_param_count(int input_dim, int channels, int hidden, int num_classes, int lstm_layers) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    if (check_dims(d) != RSAF_OK) return -1;
+    return (d.D != d.C ? 20 : 16) + 8 * d.L + 4;
+}
+
+int rsaf_cnnlstm_adam_group(const rsaf_cnnlstm_adam_item* items_host, int K, int input_dim, int channels, int hidden,
+                            int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    TRY(check_dims(d));
+    RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    RSAF_CHECK_ARG(items_host, "items_host is NULL");
+    const int64_t total = make_playout(d).total;
+    RSAF_CHECK_ARG(total <= 0x3fffffffLL && d.D <= 0xffffff, "parameter blob too large");
+    AdamGroup G{};
+    int64_t blocks = 0;
+    G.P = make_adam_segs(d, G.seg, &G.nseg, &blocks);
+    RSAF_CHECK_ARG(G.P <= 64 && blocks <= 0x7fffffffLL, "too many parameters");
+    for (int k = 0; k < K; ++k) {
+        const rsaf_cnnlstm_adam_item& it = items_host[k];
+        if (!it.table) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        if (reinterpret_cast<uintptr_t>(it.grads) & 15) return fail(RSAF_ERR_ARG, __func__, k, "grads must be 16-byte aligned");
+        if (!(it.step >= 1)) return fail(RSAF_ERR_ARG, __func__, k, "step counts from 1");
+        if (!(it.beta1 >= 0.0 && it.beta1 < 1.0 && it.beta2 >= 0.0 && it.beta2 < 1.0 && it.eps >= 0.0 && it.lr >= 0.0))
+            return fail(RSAF_ERR_ARG, __func__, k, "needs 0 <= beta < 1, eps >= 0, lr >= 0");
+        for (int j = 0; j < k; ++j)
+            if (items_host[j].table == it.table)
+                return fail(RSAF_ERR_ARG, __func__, k, ("shares its table with item " + std::to_string(j)).c_str());
+        AdamRep& r = G.rep[k];
+        r.grads = it.grads;
+        r.table = reinterpret_cast<const unsigned long long*>(it.table);
+        r.skip = it.skip;
+        r.b1 = it.beta1; r.b2 = it.beta2; r.eps = it.eps;
+        r.step_size = it.lr / (1.0 - std::pow(it.beta1, (double)it.step));
+        r.inv_sqrt_bc2 = 1.0 / std::sqrt(1.0 - std::pow(it.beta2, (double)it.step));
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_adam", s, 0.0, (double)K * total * 4 * 7);
+    hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_cnnlstm_pack_params_group(const rsaf_cnnlstm_pack_item* items_host, int K, int input_dim, int channels, int hidden,
+                                   int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    TRY(check_dims(d));
+    RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    RSAF_CHECK_ARG(items_host, "items_host is NULL");
+    const int64_t total = make_playout(d).total;
+    RSAF_CHECK_ARG(total <= 0x3fffffffLL && d.D <= 0xffffff, "parameter blob too large");
+    PackGroup G{};
+    int64_t blocks = 0;
+    G.P = make_adam_segs(d, G.seg, &G.nseg, &blocks);
+    RSAF_CHECK_ARG(blocks <= 0x7fffffffLL, "too many parameters");
+    for (int k = 0; k < K; ++k) {
+        const rsaf_cnnlstm_pack_item& it = items_host[k];
+        if (!(it.table && it.params)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        if (reinterpret_cast<uintptr_t>(it.params) & 15) return fail(RSAF_ERR_ARG, __func__, k, "params must be 16-byte aligned");
+        for (int j = 0; j < k; ++j)
+            if (overlap(items_host[j].params, total, it.params, total))
+                return fail(RSAF_ERR_ARG, __func__, k, ("shares `params` with item " + std::to_string(j)).c_str());
+        G.rep[k] = PackRep{reinterpret_cast<const unsigned long long*>(it.table), it.params};
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_pack", s, 0.0, (double)K * total * 4 * 2);
+    hipLaunchKernelGGL(pack_group_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_bn_running_stats_group(const rsaf_bn_running_item* items_host, int K, int channels, rsaf_stream_t stream) {
+    RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    RSAF_CHECK_ARG(items_host, "items_host is NULL");
+    RSAF_CHECK_ARG(channels >= 1 && channels <= 1024, "channels must be in [1, 1024]");
+    BnRunGroup g{};
+    for (int k = 0; k < K; ++k) {
+        const rsaf_bn_running_item& it = items_host[k];
+        if (!it.stats) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        g.item[k].stats = it.stats;
+        for (int i = 0; i < 5; ++i) {
+            if (it.running_mean[i] && !it.running_var[i]) return fail(RSAF_ERR_ARG, __func__, k, "running_mean without running_var");
+            g.item[k].mean[i] = it.running_mean[i]; g.item[k].var[i] = it.running_var[i];
+            g.item[k].momentum[i] = it.momentum[i]; g.item[k].unbias[i] = it.unbias[i];
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_bn_running", s, 0.0, (double)K * 5 * channels * 4 * 6);
+    hipLaunchKernelGGL(bn_running_group_kernel, dim3((channels + 255) / 256, 5, K), dim3(256), 0, s, g, channels);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
 }
 
 }  // extern "C"

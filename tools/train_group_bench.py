@@ -2,9 +2,13 @@
 backward / one Adam over all replicas' parameters) on the HIP path, with the per-kernel-family event breakdown of
 rsaf_prof_*.  Shapes are those of tools/train_bench.py (reference defaults D = 768, C = H = 128, silu), K runs over
 1, 2, 3, 5, 8, 16, and one ragged row has K = 3 replicas of different length.  One timed step per configuration after
-one warm-up step unless --steps says otherwise, as train_bench.py does.
+one warm-up step unless --steps says otherwise, as train_bench.py does.  Every row also prints wall - sum of the
+families: the time the step spends outside this project's kernels (torch ops, launches, host).
 
-    python tools/train_group_bench.py [--json PATH] [--only-shape I] [--ks 1,3,5]
+--fused runs the same shapes and K through cnnlstm_train_step_group with one FusedAdam per replica: cross-entropy, Adam,
+the packing of the parameter blobs and the BatchNorm running statistics are then one launch each per group step.
+
+    python tools/train_group_bench.py [--fused] [--json PATH] [--only-shape I] [--ks 1,3,5]
 """
 import argparse
 import json
@@ -22,6 +26,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=1)
 ap.add_argument("--ks", default="1,2,3,5,8,16")
 ap.add_argument("--only-shape", type=int, default=-1, help="0: reading task, 1: interview sessions, 2: the ragged row")
+ap.add_argument("--fused", action="store_true", help="FusedAdam per replica + cnnlstm_train_step_group")
 ap.add_argument("--json", default=None)
 args = ap.parse_args()
 lib = _lib.load()
@@ -45,15 +50,22 @@ def run(shapes, steps):
     models = [CNNLSTM().to("cuda").train() for _ in shapes]
     xs = [torch.randn((B, T, 768), device="cuda") for B, T in shapes]
     ys = [torch.randint(0, 2, (B,), device="cuda") for B, _ in shapes]
-    opt = torch.optim.Adam([p for m in models for p in m.parameters()], lr=1e-4)
-    loss_fn = torch.nn.CrossEntropyLoss()
+    if args.fused:
+        from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, cnnlstm_train_step_group
+        opts = [FusedAdam(m, lr=1e-4) for m in models]
 
-    def one():
-        opt.zero_grad()
-        outs = cnnlstm_train_group(models, xs)
-        loss = torch.stack([loss_fn(o, y) for o, y in zip(outs, ys)]).sum()
-        loss.backward()
-        opt.step()
+        def one():
+            cnnlstm_train_step_group(models, opts, xs, ys)
+    else:
+        opt = torch.optim.Adam([p for m in models for p in m.parameters()], lr=1e-4)
+        loss_fn = torch.nn.CrossEntropyLoss()
+
+        def one():
+            opt.zero_grad()
+            outs = cnnlstm_train_group(models, xs)
+            loss = torch.stack([loss_fn(o, y) for o, y in zip(outs, ys)]).sum()
+            loss.backward()
+            opt.step()
 
     one()
     torch.cuda.synchronize()
@@ -81,12 +93,13 @@ def row(tag, shapes):
         print(f"{head}: skipped, out of device memory", flush=True)
         return dict(rec, skipped="out of device memory")
     rec_ms = sum(v["ms"] for k, v in prof.items() if k in ("lstm_recurrent", "lstm_bwd_recurrent")) / args.steps
-    print(f"{head}: {dt * 1e3:.1f} ms per group step, {dt * 1e3 / len(shapes):.1f} ms per replica, recurrences {rec_ms:.1f} ms",
-          flush=True)
+    fam_ms = sum(v["ms"] for v in prof.values()) / args.steps
+    print(f"{head}: {dt * 1e3:.1f} ms per group step, {dt * 1e3 / len(shapes):.1f} ms per replica, recurrences {rec_ms:.1f} ms, "
+          f"families {fam_ms:.1f} ms, wall - families {dt * 1e3 - fam_ms:.1f} ms", flush=True)
     for k, v in sorted(prof.items(), key=lambda kv: -kv[1]["ms"]):
         print(f"   {k:26s} {v['launches'] / args.steps:6.0f} launches  {v['ms'] / args.steps:9.2f} ms", flush=True)
     torch.cuda.empty_cache()
-    return dict(rec, ms_per_step=dt * 1e3, recurrence_ms=rec_ms,
+    return dict(rec, fused=args.fused, ms_per_step=dt * 1e3, recurrence_ms=rec_ms, families_ms=fam_ms, outside_ms=dt * 1e3 - fam_ms,
                 families={k: {"launches": v["launches"] / args.steps, "ms": v["ms"] / args.steps} for k, v in prof.items()})
 
 
