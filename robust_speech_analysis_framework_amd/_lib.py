@@ -207,6 +207,11 @@ def ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def optr(t):
+    """``ptr(t)``, or NULL for ``None`` (an operand the call may leave out)."""
+    return ptr(t) if t is not None else None
+
+
 def c_void_p_off(t, elems: int):
     """Device pointer of element ``elems`` of a contiguous torch tensor."""
     if not t.is_contiguous():

@@ -1,0 +1,381 @@
+"""Fused training step of the CNN-LSTM: cross-entropy, Adam and the running statistics in HIP.
+
+Around the model the reference's loop runs ``nn.CrossEntropyLoss()``, ``loss.backward()`` and ``Adam.step()``
+(``src/dl_cv_strategies.py:122-125,236-248``).  Through autograd that costs, per replica and step, the packing of the
+parameter blob, the unpacking of the gradient blob, the BatchNorm buffer updates and the loss and optimizer kernels of
+torch: elementwise work on a few hundred thousand floats spread over 100+ small ops.  Here the blob is written from the
+parameters where they live (``rsaf_cnnlstm_pack_params_group``), ``rsaf_cnnlstm_adam_group`` reads the gradient blob and
+updates the parameters in their torch layouts, the loss and its gradient come from ``rsaf_ce_loss_group`` and the running
+statistics from ``rsaf_bn_running_stats_group``: one launch each per group step.
+
+Built on ``cnnlstm_train`` (replica plan, launchers, argument checks); ``cnnlstm`` re-exports the names of this module, so
+``CNNLSTM`` is imported where it is needed, not at the top.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from . import _lib
+from .cnnlstm_train import (_Replica, _blob_params, _check_train_group, _chunks, _dims5, _launch_chunked, _launch_group,
+                            _tracked_bn, _train_segments, _unbias, _update_running_stats, train_param_offsets)
+
+
+def _adam_order(model):
+    """The parameters in the numbering of ``rsaf_cnnlstm_adam_group`` (blob order; include/rsaf.h)."""
+    order = _blob_params(_train_segments(model)[0])
+    n = int(_lib.load().rsaf_cnnlstm_adam_param_count(*_dims5(model.dims)))
+    if n != len(order) or len(order) != len(list(model.parameters())):
+        raise _lib.RsafError(f"CNNLSTM has {len(list(model.parameters()))} parameters, {len(order)} of them in the blob, "
+                             f"but rsaf_cnnlstm_adam_group numbers {n}")
+    return order
+
+
+def _pointer_table(rows, device):
+    """Device int64 tensor of device pointers; the host copy travels through pinned staging on the current stream."""
+    return torch.tensor(rows, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+
+
+class FusedAdam(torch.optim.Optimizer):
+    """``torch.optim.Adam(model.parameters(), lr, betas, eps)`` for one ``CNNLSTM`` on the HIP path: the whole update of
+    the model is one launch of ``rsaf_cnnlstm_adam_group`` (published Adam: bias-corrected moments, eps outside the
+    square root; no weight decay, no amsgrad).  ``param_groups[0]['lr']`` is read at every step, so the schedulers of
+    ``torch.optim.lr_scheduler`` drive it unchanged; ``state_dict()`` / ``load_state_dict()`` use ``torch.optim.Adam``'s
+    format (per parameter ``step``, ``exp_avg``, ``exp_avg_sq``) in both directions.
+
+    ``step()`` consumes ordinary ``.grad`` tensors (a parameter without one is skipped, as torch does), so the
+    reference's loop works with only the optimizer swapped.  ``cnnlstm_train_step_group`` feeds the gradient blob of the
+    group backward to the same kernel and never touches ``.grad``.
+
+    The kernels reach the parameters and moments through a device table of pointers, cached while the pointers are
+    stable (``.to()`` or a loaded optimizer state rebuild it).  They write through raw pointers, so after every step the
+    versions of everything written are bumped: ``packed_weights()`` and every other version-keyed cache see the change."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+        from .cnnlstm import CNNLSTM
+        if not isinstance(model, CNNLSTM):
+            raise ValueError(f"FusedAdam: model must be a CNNLSTM, got {type(model).__name__}")
+        if weight_decay != 0:
+            raise ValueError("FusedAdam: weight_decay is not supported (the reference uses Adam's default, 0)")
+        if amsgrad:
+            raise ValueError("FusedAdam: amsgrad is not supported")
+        if maximize:
+            raise ValueError("FusedAdam: maximize is not supported")
+        if not 0.0 <= lr:
+            raise ValueError(f"FusedAdam: invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"FusedAdam: invalid epsilon value: {eps}")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"FusedAdam: invalid betas: {betas}")
+        params = list(model.parameters())
+        if any(not p.is_cuda for p in params):
+            raise ValueError("FusedAdam: the CNNLSTM must be on a HIP device (model.to('cuda') first): there is no CPU fallback")
+        if any(p.dtype != torch.float32 for p in params):
+            raise ValueError("FusedAdam: the parameters must be float32")
+        # the keys of torch.optim.Adam's own param_groups, so that state dicts load in both directions
+        defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).defaults)
+        super().__init__(params, defaults)
+        self.model = model
+        self._order = _adam_order(model)
+        self._steps = None                  # step count per parameter of _order (host mirror of state[p]['step']), None = unknown
+        self._state_gen = 0                 # bumped whenever a moment tensor is created or replaced
+        self._table = self._table_key = None
+        self._blob = None                   # blob buffer of the fused step, rewritten from the parameters every step
+
+    # -- skip masks: bit i set = parameter i of _order sits this step out ---------------------------------------------------
+    def _all_skipped(self, skip):
+        return skip == (1 << len(self._order)) - 1
+
+    def _live(self, skip):
+        """The parameters that ``skip`` leaves in."""
+        return [p for i, p in enumerate(self._order) if not (skip >> i) & 1]
+
+    # -- optimizer state ------------------------------------------------------------------------------------------------
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._steps = None
+        self._state_gen += 1
+
+    def _hyper(self):
+        g = self.param_groups[0]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("FusedAdam: weight_decay, amsgrad and maximize are not supported")
+        return float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+    def _ensure_state(self, skip):
+        """Moments of every parameter that is about to be updated (created as torch.optim.Adam creates them)."""
+        if self._steps is None:
+            for p in self._order:
+                st = self.state.get(p)
+                if st and not torch.is_tensor(st["step"]):
+                    st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+                if st and not (st["exp_avg"].is_contiguous() and st["exp_avg_sq"].is_contiguous()
+                               and st["exp_avg"].dtype == st["exp_avg_sq"].dtype == torch.float32):
+                    st["exp_avg"] = st["exp_avg"].to(torch.float32).contiguous()
+                    st["exp_avg_sq"] = st["exp_avg_sq"].to(torch.float32).contiguous()
+            self._steps = [int(self.state[p]["step"]) if self.state.get(p) else 0 for p in self._order]
+        for p in self._live(skip):
+            if "exp_avg" not in self.state[p]:
+                st = self.state[p]
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                self._state_gen += 1
+
+    def _rows(self):
+        rows = [[], [], []]
+        for p in self._order:
+            if not p.is_contiguous():
+                raise _lib.RsafError("FusedAdam: the parameters must be contiguous")
+            st = self.state.get(p) or {}
+            rows[0].append(p.data_ptr())
+            rows[1].append(st["exp_avg"].data_ptr() if "exp_avg" in st else 0)
+            rows[2].append(st["exp_avg_sq"].data_ptr() if "exp_avg_sq" in st else 0)
+        return rows
+
+    def _cached_table(self):
+        """[3][P] device table of parameter / exp_avg / exp_avg_sq pointers, cached while the pointers are stable."""
+        tkey = (self._state_gen,) + tuple(p.data_ptr() for p in self._order)
+        if self._table is None or self._table_key != tkey:
+            self._table = _pointer_table(self._rows(), self._order[0].device)
+            self._table_key = tkey
+        return self._table
+
+    def _launches(self, skip):
+        """[(step, skip mask)]: one launch per distinct step count among the parameters to update (one, unless some
+        parameter sat out earlier steps: torch keeps a step count per parameter)."""
+        by_step = {}
+        for i in range(len(self._order)):
+            if not (skip >> i) & 1:
+                by_step[self._steps[i] + 1] = by_step.get(self._steps[i] + 1, 0) | (1 << i)
+        full = (1 << len(self._order)) - 1
+        return [(t, full & ~mask) for t, mask in sorted(by_step.items())]
+
+    def _stepped(self, skip):
+        torch._foreach_add_([self.state[p]["step"] for p in self._live(skip)], 1)
+        for i in range(len(self._order)):
+            if not (skip >> i) & 1:
+                self._steps[i] += 1
+
+    def _frozen(self):
+        skip = 0
+        for i, p in enumerate(self._order):
+            if not p.requires_grad:
+                skip |= 1 << i
+        return skip
+
+    def _blob_buffer(self):
+        """Zero-initialised buffer for the parameter blob (its padding floats are never written again)."""
+        device = self._order[0].device
+        if self._blob is None or self._blob.device != device:
+            total = train_param_offsets(self.model.dims)[1]
+            self._blob = torch.zeros(total, dtype=torch.float32, device=device)
+        return self._blob
+
+    def _written(self, tensors):
+        """The kernels wrote ``tensors`` through raw pointers: bump their versions, as an in-place torch op would."""
+        torch.autograd.graph.increment_version(tensors)
+
+    def packed_blob(self):
+        """The parameters in the blob layout of ``rsaf_cnnlstm_train_param_offsets``, packed on the device
+        (``rsaf_cnnlstm_pack_params_group``); equal to what ``_pack_train_blob`` builds with torch ops, bit for bit.
+        The tensor is the optimizer's own buffer and is overwritten by the next fused step."""
+        return _pack_group([self])[0]
+
+    @torch.no_grad()
+    def step_blob(self, grads):
+        """One Adam step from a gradient blob in the layout of ``rsaf_cnnlstm_train_param_offsets`` (what
+        ``rsaf_cnnlstm_train_backward_group`` writes); parameters with ``requires_grad = False`` are left alone."""
+        total = train_param_offsets(self.model.dims)[1]
+        if not grads.is_cuda or grads.dtype != torch.float32 or grads.shape != (total,) or not grads.is_contiguous():
+            raise ValueError(f"expected a contiguous float32 HIP (cuda) gradient blob of {total} floats")
+        skip = self._frozen()
+        if self._all_skipped(skip):
+            return
+        self._ensure_state(skip)
+        _adam_group([(self, grads, self._cached_table(), skip)])
+        self._written(self._live(skip))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        skip, grads = 0, []
+        for i, p in enumerate(self._order):
+            g = p.grad
+            if g is None:
+                skip |= 1 << i
+                grads.append(None)
+                continue
+            if g.is_sparse or not g.is_cuda:
+                raise _lib.RsafError("FusedAdam: gradients must be dense HIP (cuda) tensors")
+            grads.append(g.to(torch.float32).contiguous())
+        if self._all_skipped(skip):
+            return loss
+        self._ensure_state(skip)
+        rows = self._rows() + [[g.data_ptr() if g is not None else 0 for g in grads]]
+        table = _pointer_table(rows, self._order[0].device)
+        _adam_group([(self, None, table, skip)])
+        self._written(self._live(skip))
+        return loss
+
+
+def _adam_group(entries):
+    """``entries``: [(optimizer, gradient blob or None, pointer table, skip mask)] of one architecture ->
+    ``rsaf_cnnlstm_adam_group`` in chunks of ``train_group_max()``; a replica whose parameters stand at different step
+    counts takes one launch per count."""
+    def fill(it, rec, _k):
+        (opt, grads, table, _), (t, mask) = rec
+        it.grads = grads.data_ptr() if grads is not None else None
+        it.table, it.skip, it.step = table.data_ptr(), mask, t
+        it.lr, it.beta1, it.beta2, it.eps = opt._hyper()
+
+    plans = [opt._launches(skip) for opt, _, _, skip in entries]
+    for j in range(max(len(pl) for pl in plans)):
+        live = [(e, pl[j]) for e, pl in zip(entries, plans) if j < len(pl)]
+        _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *_dims5(entries[0][0].model.dims))
+    for opt, _, _, skip in entries:
+        opt._stepped(skip)
+
+
+def _pack_group(optimizers):
+    """The parameter blobs of the optimizers' models, written on the device from the parameters where they live: one
+    launch of ``rsaf_cnnlstm_pack_params_group`` per chunk of ``train_group_max()``."""
+    pairs = [(opt._cached_table(), opt._blob_buffer()) for opt in optimizers]
+
+    def fill(it, pair, _k):
+        it.table, it.params = pair[0].data_ptr(), pair[1].data_ptr()
+
+    _launch_chunked("rsaf_cnnlstm_pack_params_group", _lib.PackItem, pairs, fill, *_dims5(optimizers[0].model.dims))
+    return [blob for _, blob in pairs]
+
+
+def ce_loss_group(logits, labels, with_grad=True):
+    """Mean-reduced cross-entropy of K (logits [B_k, nc], int64 labels [B_k]) pairs in one launch of
+    ``rsaf_ce_loss_group`` (``nn.CrossEntropyLoss()`` with its defaults) -> (losses [K] on the device, list of
+    d loss_k / d logits_k, or None without ``with_grad``).  Lists longer than ``train_group_max()`` are chunked."""
+    logits, labels = list(logits), list(labels)
+    if len(logits) != len(labels) or not logits:
+        raise ValueError(f"{len(logits)} logits but {len(labels)} label tensors")
+    nc, device = logits[0].shape[1], logits[0].device
+    labs = []
+    for k, (o, lab) in enumerate(zip(logits, labels)):
+        if not o.is_cuda:
+            raise _lib.RsafError(f"ce_loss_group needs HIP (cuda) tensors (item {k}): there is no CPU fallback")
+        if o.dim() != 2 or o.shape[1] != nc or o.dtype != torch.float32 or not o.is_contiguous():
+            raise ValueError(f"item {k}: expected contiguous float32 logits [B, {nc}], got {o.dtype} {tuple(o.shape)}")
+        if lab.dim() != 1 or lab.shape[0] != o.shape[0] or lab.dtype.is_floating_point:
+            raise ValueError(f"item {k}: expected {o.shape[0]} integer class labels, got {lab.dtype} {tuple(lab.shape)}")
+        labs.append(lab.to(device, torch.int64).contiguous())
+    losses = torch.empty(len(logits), dtype=torch.float32, device=device)
+    dl = [torch.empty_like(o) for o in logits] if with_grad else None
+
+    def fill(it, pair, k):
+        it.logits, it.labels, it.B = pair[0].data_ptr(), pair[1].data_ptr(), pair[0].shape[0]
+        it.loss_out = losses.data_ptr() + 4 * k
+        it.dlogits_out = dl[k].data_ptr() if with_grad else None
+
+    _launch_chunked("rsaf_ce_loss_group", _lib.CeLossItem, list(zip(logits, labs)), fill, nc)
+    return losses, dl
+
+
+def _bn_running_group(reps, channels):
+    """Running statistics of the replicas ``reps`` (``_Replica`` records) after a step: one launch of
+    ``rsaf_bn_running_stats_group`` per chunk, ``num_batches_tracked`` incremented on the host side in one foreach op.
+    A replica with a ``momentum=None`` layer (cumulative average) takes the torch ops of ``_update_running_stats``.
+    Returns the buffers written."""
+    fused, counters, written = [], [], []
+    for r in reps:
+        bns = [bn for _, bn, _ in _tracked_bn(r.model, r.B, r.T)]
+        written += [t for bn in bns for t in (bn.running_mean, bn.running_var)]
+        if any(bn.momentum is None for bn in bns):
+            _update_running_stats(r.model, r.stats, r.B, r.T)
+        elif bns:
+            fused.append(r)
+            counters += [bn.num_batches_tracked for bn in bns]
+
+    def fill(it, r, _k):
+        it.stats = r.stats.data_ptr()
+        for i, bn, n in _tracked_bn(r.model, r.B, r.T):
+            if not (bn.running_mean.is_contiguous() and bn.running_var.is_contiguous()
+                    and bn.running_mean.dtype == bn.running_var.dtype == torch.float32):
+                raise _lib.RsafError("the BatchNorm running statistics must be contiguous float32 tensors")
+            it.running_mean[i], it.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
+            it.momentum[i], it.unbias[i] = float(bn.momentum), _unbias(n)
+
+    _launch_chunked("rsaf_bn_running_stats_group", _lib.BnRunningItem, fused, fill, channels)
+    if counters:
+        torch._foreach_add_(counters, 1)
+    return written
+
+
+def _train_step_chunk(models, optimizers, xs, labels, masks):
+    """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k])."""
+    d, device = models[0].dims, xs[0].device
+    K, nc, C = len(models), d["num_classes"], d["channels"]
+    rows = [x.shape[0] for x in xs]
+    logits_all = torch.empty((sum(rows), nc), dtype=torch.float32, device=device)
+    stats_all = torch.empty((K, 5, 3, C), dtype=torch.float32, device=device)
+    logits = list(torch.split(logits_all, rows))
+    blobs = _pack_group(optimizers)
+    reps = [_Replica(model, x, mk, blobs[k], logits[k], stats_all[k]) for k, (model, x, mk) in enumerate(zip(models, xs, masks))]
+    _launch_group(reps, False)
+    losses, dl = ce_loss_group(logits, labels)
+    grads = torch.zeros((K, blobs[0].numel()), dtype=torch.float32, device=device)   # one zero fill for the group
+    for k, r in enumerate(reps):
+        r.dlogits, r.grads = dl[k], grads[k]
+    _launch_group(reps, True)
+    entries = []
+    for k, opt in enumerate(optimizers):
+        skip = opt._frozen()
+        opt._ensure_state(skip)
+        entries.append((opt, grads[k], opt._cached_table(), skip))
+    live = [e for e in entries if not e[0]._all_skipped(e[3])]
+    if live:
+        _adam_group(live)
+    buffers = _bn_running_group(reps, C)
+    for opt, _, _, skip in entries:
+        own = set(id(t) for t in opt.model.buffers())
+        opt._written(opt._live(skip) + [t for t in buffers if id(t) in own])
+    return losses, logits
+
+
+def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
+    """One whole training step of K independent ``CNNLSTM`` replicas, ``optimizers[k]`` the ``FusedAdam`` of ``models[k]``:
+    group forward in training mode, ``nn.CrossEntropyLoss()`` (defaults) of ``labels[k]``, group backward, Adam and the
+    BatchNorm running statistics -> ``(losses [K] on the device, [logits_k])``.  No autograd graph is built and ``.grad``
+    is not touched; the packing of the parameter blobs, the loss, the optimizer and the running statistics are one launch
+    each for the group.  A parameter with ``requires_grad = False`` keeps its value and its moments.
+
+    Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` are honoured, and
+    masks are drawn replica by replica in the same order, so with equal RNG state both paths see equal masks).  Lists
+    longer than ``train_group_max()`` are split into chunks of that size."""
+    optimizers, labels = list(optimizers), list(labels)
+    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group")
+    if not (len(optimizers) == len(labels) == len(models)):
+        raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(labels)} label tensors")
+    for k, (m, opt) in enumerate(zip(models, optimizers)):
+        if not isinstance(opt, FusedAdam) or opt.model is not m:
+            raise ValueError(f"optimizers[{k}] is not the FusedAdam of models[{k}]")
+    for k, (x, lab) in enumerate(zip(xs, labels)):
+        if lab.dim() != 1 or lab.shape[0] != x.shape[0] or lab.dtype.is_floating_point:
+            raise ValueError(f"replica {k}: expected {x.shape[0]} integer class labels, got {lab.dtype} {tuple(lab.shape)}")
+    losses, logits = [], []
+    with torch.no_grad():
+        # every chunk is a whole step of its replicas, so the chunks are cut here and not call by call
+        for _, chunk in _chunks(list(zip(models, optimizers, xs, labels, mks))):
+            ls, lg = _train_step_chunk(*zip(*chunk))
+            losses.append(ls)
+            logits += lg
+    return (losses[0] if len(losses) == 1 else torch.cat(losses)), logits
+
+
+def _fused_step_applies(optimizers, models, loss_fn):
+    """The lockstep loops take the fused step when the loss is ``nn.CrossEntropyLoss`` with its default options and
+    every optimizer is the ``FusedAdam`` of its model."""
+    if type(loss_fn) is not nn.CrossEntropyLoss or loss_fn.weight is not None or loss_fn.reduction != "mean" \
+            or loss_fn.label_smoothing != 0 or loss_fn.ignore_index != -100:
+        return False
+    return all(isinstance(o, FusedAdam) and o.model is m for o, m in zip(optimizers, models))

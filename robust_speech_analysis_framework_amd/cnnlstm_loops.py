@@ -1,0 +1,222 @@
+"""Training and evaluation loops of the reference for K CNN-LSTM replicas in lock step (``CNNLSTMGroup``,
+``train_replicas_lockstep``, ``eval_replicas_lockstep``, ``train_eval_replicas_lockstep``): every step of the loops is
+one group call of ``cnnlstm_train`` / ``cnnlstm_fused`` (training) or of ``cnnlstm.cnnlstm_forward_group`` (validation).
+
+``cnnlstm`` re-exports the names of this module, so what the loops need of it (``CNNLSTM``, ``cnnlstm_forward_group``,
+``eval_outputs``) is imported where it is used, not at the top.
+"""
+from __future__ import annotations
+
+import copy
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .cnnlstm_fused import _fused_step_applies, ce_loss_group, cnnlstm_train_step_group
+from .cnnlstm_train import cnnlstm_train_group, train_group_max
+
+
+class CNNLSTMGroup(nn.Module):
+    """K ``CNNLSTM`` replicas of one architecture that train side by side.  ``forward(xs)`` takes one batch per replica
+    (``None``: the replica sits out and its output is ``None``): in training mode the group step over the others, in
+    eval mode the group inference forward over them (``cnnlstm_forward_group``).  ``state_dict`` keys are ``models.<k>.<reference key>``, so a
+    replica's weights load into a plain ``CNNLSTM``."""
+
+    def __init__(self, models):
+        from .cnnlstm import CNNLSTM
+        super().__init__()
+        self.models = nn.ModuleList(models)
+        if len(self.models) == 0:
+            raise ValueError("CNNLSTMGroup needs at least one replica")
+        for k, m in enumerate(self.models):
+            if not isinstance(m, CNNLSTM):
+                raise TypeError(f"replica {k} is a {type(m).__name__}, not a CNNLSTM")
+
+    def forward(self, xs):
+        from .cnnlstm import cnnlstm_forward_group
+        xs = list(xs)
+        if len(xs) != len(self.models):
+            raise ValueError(f"{len(self.models)} replicas but {len(xs)} inputs")
+        live = [k for k, x in enumerate(xs) if x is not None]
+        outs = [None] * len(xs)
+        if self.training:
+            if live:
+                for k, o in zip(live, cnnlstm_train_group([self.models[k] for k in live], [xs[k] for k in live])):
+                    outs[k] = o
+        elif live:
+            for k, o in zip(live, cnnlstm_forward_group([self.models[k] for k in live], [xs[k] for k in live])):
+                outs[k] = o
+        return outs
+
+
+def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device):
+    """The reference's inner training loop (``src/dl_cv_strategies.py:244-248``: ``zero_grad / model(seq) / loss /
+    backward / step`` per batch, a fixed number of epochs) for K replicas over K loaders in lock step: step i of an
+    epoch takes batch i of every loader through one group step.  Loaders may differ in length; a replica whose epoch
+    is exhausted sits out until the others finish theirs.  Returns the mean training loss per epoch of every replica
+    (``histories[k][epoch]``, accumulated as the reference's ``train_model`` does, ``:120-129``); the K losses of a
+    step come to the host in one copy.
+
+    Parameters, buffers and losses equal those of K sequential trainings bit for bit as long as the replicas see the
+    same batches and dropout masks.  When ``loss_fn`` is ``nn.CrossEntropyLoss()`` with its default options and every
+    optimizer of the call is the ``FusedAdam`` of its model, a step is one ``cnnlstm_train_step_group`` call (loss, Adam and running
+    statistics in HIP, no autograd graph); anything else runs the loop above as written.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
+    its permutations from torch's global RNG: in lock step the K loaders draw in a different order than K sequential
+    trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  The same holds
+    for dropout masks, which come from the device RNG replica by replica within a step."""
+    models, optimizers, loaders = list(models), list(optimizers), list(loaders)
+    if not (len(models) == len(optimizers) == len(loaders)):
+        raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
+    histories = [[] for _ in models]
+    fused = _fused_step_applies(optimizers, models, loss_fn)      # decided once for the call: no replica changes path mid-epoch
+    for _ in range(epochs):
+        for m in models:
+            m.train()
+        its = [iter(ld) for ld in loaders]
+        total, count = [0.0] * len(models), [0] * len(models)
+        while True:
+            batches = [next(it, None) for it in its]
+            live = [k for k, b in enumerate(batches) if b is not None]
+            if not live:
+                break
+            xs = [batches[k][0].to(device) for k in live]
+            labs = [batches[k][1].to(device) for k in live]
+            if fused:
+                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs)[0]
+            else:
+                for k in live:
+                    optimizers[k].zero_grad()
+                outs = cnnlstm_train_group([models[k] for k in live], xs)
+                losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
+                torch.stack(losses).sum().backward()
+                for k in live:
+                    optimizers[k].step()
+                step_losses = torch.stack([ls.detach() for ls in losses])
+            for k, v in zip(live, step_losses.tolist()):
+                total[k] += v
+                count[k] += 1
+        for k in range(len(models)):
+            histories[k].append(total[k] / max(count[k], 1))
+    return histories
+
+
+def _grouped_eval_batches(pairs, device):
+    """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models -> yields ``(tag, logits, lab on the device)``
+    in the same order, the forwards pooled into group calls of up to ``train_group_max()`` batches.  The batches stay as
+    collated: zero padding is not masked (``src/dl_cv_strategies.py:81-84``), so regrouping sequences would change the
+    results."""
+    from .cnnlstm import cnnlstm_forward_group
+    gmax = train_group_max()
+    pend = []
+
+    def flush():
+        outs = cnnlstm_forward_group([p[1] for p in pend], [p[2] for p in pend])
+        res = [(p[0], o, p[3]) for p, o in zip(pend, outs)]
+        pend.clear()
+        return res
+
+    for tag, model, seq, lab in pairs:
+        pend.append((tag, model, seq.to(device), lab.to(device)))
+        if len(pend) == gmax:
+            yield from flush()
+    if pend:
+        yield from flush()
+
+
+def eval_replicas_lockstep(models, loaders, device):
+    """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) for K models over K loaders: all (model, batch) pairs are
+    pooled into group calls.  Returns K triples ``(labels, preds, probs)`` of NumPy arrays in loader order, equal to
+    what the reference's loop returns model by model; the results of a replica come to the host in one copy each."""
+    from .cnnlstm import eval_outputs
+    models, loaders = list(models), list(loaders)
+    if len(models) != len(loaders):
+        raise ValueError(f"{len(models)} models but {len(loaders)} loaders")
+    for m in models:
+        m.eval()
+    parts = [([], [], []) for _ in models]
+    with torch.no_grad():
+        pairs = ((k, m, seq, lab) for k, (m, ld) in enumerate(zip(models, loaders)) for seq, lab in ld)
+        for k, out, lab in _grouped_eval_batches(pairs, device):
+            prob, pred = eval_outputs(out)
+            for lst, v in zip(parts[k], (lab, pred, prob)):
+                lst.append(v)
+    res = []
+    for labs, preds, probs in parts:
+        if not labs:
+            res.append((np.array([]), np.array([]), np.array([])))
+            continue
+        res.append(tuple(torch.cat(v).cpu().numpy() for v in (labs, preds, probs)))
+    return res
+
+
+def eval_model_grouped(model, data_loader, device):
+    """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) with all batches of the loader as items of group calls:
+    ``(labels, preds, probs)`` as NumPy arrays in loader order."""
+    return eval_replicas_lockstep([model], [data_loader], device)[0]
+
+
+def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, val_loaders, loss_fn, epochs, patience, device):
+    """``_train_eval_loop`` (``src/dl_cv_strategies.py:112-165``) for K replicas: per epoch the training pass of
+    ``train_replicas_lockstep`` over the replicas still running, then the validation pass of all of them in group calls
+    (``val_loss`` accumulated batch by batch in loader order; the losses of a pass come to the host in one copy), then per
+    replica ``scheduler.step(avg_val_loss)`` (``schedulers[k]`` may be ``None``), best-weights checkpointing and early
+    stopping as the reference does them.  A replica that stopped early sits out of the later epochs.  Returns
+    ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded."""
+    models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
+    train_loaders, val_loaders = list(train_loaders), list(val_loaders)
+    K = len(models)
+    if not (K == len(optimizers) == len(schedulers) == len(train_loaders) == len(val_loaders)):
+        raise ValueError(f"{K} models, {len(optimizers)} optimizers, {len(schedulers)} schedulers, {len(train_loaders)} training "
+                         f"loaders and {len(val_loaders)} validation loaders")
+    train_hist, val_hist = [[] for _ in models], [[] for _ in models]
+    best_val_loss = [float("inf")] * K
+    epochs_no_improve = [0] * K
+    best_model_weights = [None] * K
+    running = list(range(K))
+    for _ in range(epochs):
+        if not running:
+            break
+        hist = train_replicas_lockstep([models[k] for k in running], [optimizers[k] for k in running],
+                                       [train_loaders[k] for k in running], loss_fn, 1, device)
+        for k, h in zip(running, hist):
+            train_hist[k].append(h[0])
+        for k in running:
+            models[k].eval()
+        tags, outs, labs = [], [], []
+        fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], loss_fn)
+        with torch.no_grad():
+            pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
+            for k, out, lab in _grouped_eval_batches(pairs, device):
+                tags.append(k)
+                outs.append(out)
+                labs.append(lab)
+            if not outs:
+                losses = []
+            elif fused and all(o.shape[0] > 0 for o in outs):           # the losses of the pass in group launches, no gradient
+                losses = ce_loss_group(outs, labs, with_grad=False)[0].tolist()
+            else:
+                losses = torch.stack([loss_fn(o, lab) for o, lab in zip(outs, labs)]).tolist()
+        val_loss, count = {k: 0 for k in running}, {k: 0 for k in running}
+        for k, v in zip(tags, losses):
+            val_loss[k] += v
+            count[k] += 1
+        still = []
+        for k in running:
+            avg_val_loss = val_loss[k] / count[k]
+            val_hist[k].append(avg_val_loss)
+            if schedulers[k] is not None:
+                schedulers[k].step(avg_val_loss)
+            if avg_val_loss < best_val_loss[k]:
+                best_val_loss[k] = avg_val_loss
+                best_model_weights[k] = copy.deepcopy(models[k].state_dict())
+                epochs_no_improve[k] = 0
+            else:
+                epochs_no_improve[k] += 1
+            if epochs_no_improve[k] < patience:
+                still.append(k)
+        running = still
+    for k in range(K):
+        if best_model_weights[k]:
+            models[k].load_state_dict(best_model_weights[k])
+    return [(models[k], train_hist[k], val_hist[k]) for k in range(K)]
