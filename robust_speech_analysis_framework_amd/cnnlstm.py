@@ -272,10 +272,11 @@ class CNNLSTM(nn.Module):
         return logits
 
 
-def cnnlstm_forward_stages(model: "CNNLSTM", x):
+def cnnlstm_forward_stages(model: "CNNLSTM", x, workspace=None):
     """Eval-mode forward that also returns what the reference's sub-modules return (forward hooks on
     ``res_block1`` / ``res_block2`` / ``lstm`` / ``attention_pooling`` of ``src/models.py``), channels-last:
-    dict(res1 [B,T,C], res2 [B,T/2,C], lstm [B,T/2,2H], pooled [B,2H], logits [B,NC])."""
+    dict(res1 [B,T,C], res2 [B,T/2,C], lstm [B,T/2,2H], pooled [B,2H], logits [B,NC]).  ``workspace``: a float32 device
+    tensor to work in when it is large enough (``rsaf_cnnlstm_workspace_bytes``), else a new one is taken."""
     lib = _lib.load()
     if not x.is_cuda:
         raise _lib.RsafError("cnnlstm_forward_stages needs a HIP (cuda) tensor")
@@ -283,7 +284,7 @@ def cnnlstm_forward_stages(model: "CNNLSTM", x):
     x = x.to(torch.float32).contiguous()
     B, T, _ = x.shape
     blob = model.packed_weights(x.device)
-    ws = _workspace(x, d, empty_ok=False)
+    ws = _workspace(x, d, workspace, empty_ok=False)
     e = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)            # noqa: E731
     out = {"res1": e(B, T, d["channels"]), "res2": e(B, T // 2, d["channels"]), "lstm": e(B, T // 2, 2 * d["hidden"]),
            "pooled": e(B, 2 * d["hidden"]), "logits": e(B, d["num_classes"])}

@@ -23,16 +23,26 @@ pytestmark = pytest.mark.gpu
 
 ULP = 2.0 ** -23
 ZERO_GRAD = ("conv1.bias", "conv2.bias", "shortcut.0.bias", "attention_weights.bias")    # mathematically zero
-GEOMETRIES = {"shortcut_conv_silu": (16, 32, 64, "silu"), "identity_shortcut_gelu": (32, 32, 64, "gelu")}
+GEOMETRIES = {
+    # D, C, H, act, num_classes, layers
+    "shortcut_conv_silu": (16, 32, 64, "silu", 2, 2),
+    "identity_shortcut_gelu": (32, 32, 64, "gelu", 2, 2),
+    # rows 2, 3 and 5 of tests/cnnlstm_geometry.py: Cin = 16 / 48, Cin = 64 / 16 with H = 128, Cin = 48 / 100 (one layer: no
+    # dropout between layers)
+    "geometry2_c48_l3_nc5": (16, 48, 64, "silu", 5, 3),
+    "geometry3_h128_l4_nc16": (64, 16, 128, "gelu", 16, 4),
+    "geometry5_c100_l1_nc3": (48, 100, 128, "silu", 3, 1),
+}
 RAGGED = [(4, 24), (3, 31), (5, 18)]
 P_BLOCK, P_RATE = 0.2, 0.5
 
 
-def build(D, C, H, seed, act, p_rate=0.0, p_block=0.0):
+def build(D, C, H, seed, act, p_rate=0.0, p_block=0.0, num_classes=2, layers=2):
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import CNNLSTM
-    m = CNNLSTM(input_dim=D, cnn_out_channels=C, lstm_hidden_dim=H, activation_fn=act, dropout_rate=p_rate)
-    sd = synth_state_dict(D, C, H, seed)
+    m = CNNLSTM(input_dim=D, num_classes=num_classes, cnn_out_channels=C, lstm_hidden_dim=H, lstm_layers=layers, activation_fn=act,
+                dropout_rate=p_rate)
+    sd = synth_state_dict(D, C, H, seed, num_classes=num_classes, layers=layers)
     full = m.state_dict()
     for k, v in sd.items():
         full[k] = torch.from_numpy(v)
@@ -164,9 +174,9 @@ def adam_bar(fused, torch_, oracle, what):
 def test_adam_kernel_on_prescribed_gradients(geom):
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, _pack_train_blob, train_param_offsets
-    D, C, H, act = GEOMETRIES[geom]
+    D, C, H, act, NC, L = GEOMETRIES[geom]
     lr = 1e-3
-    m, sd = build(D, C, H, 801, act)
+    m, sd = build(D, C, H, 801, act, num_classes=NC, layers=L)
     ref = copy.deepcopy(m)
     opt, topt = FusedAdam(m, lr=lr), torch.optim.Adam(ref.parameters(), lr=lr)
     total = train_param_offsets(m.dims)[1]
@@ -199,7 +209,8 @@ def test_adam_kernel_on_prescribed_gradients(geom):
         assert (bits(p)[~z] != before[k][~z]).any() or (~z).sum() == 0, k
     assert n_zero > 100
     # both biases of a direction took the same gradient from the same state: identical moments
-    for l in range(2):
+    assert m.dims["layers"] == L and m.dims["num_classes"] == NC
+    for l in range(m.dims["layers"]):
         for sfx in ("", "_reverse"):
             a, b = getattr(m.lstm, f"bias_ih_l{l}{sfx}"), getattr(m.lstm, f"bias_hh_l{l}{sfx}")
             same(bits(opt.state[a]["exp_avg"]), bits(opt.state[b]["exp_avg"]), f"exp_avg of the bias pair l{l}{sfx}")
@@ -218,7 +229,7 @@ def test_frozen_parameters_keep_their_bits():
     float32, a few ulp of the parameter per step on either side plus 1e-5 of the moves made)."""
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, _pack_train_blob, train_param_offsets
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     lr = 1e-3
     m, _ = build(D, C, H, 811, act)
     ref = copy.deepcopy(m)
@@ -265,9 +276,9 @@ def test_frozen_parameters_keep_their_bits():
 def test_fused_group_step_follows_the_oracle_loop(geom):
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, cnnlstm_train_group, cnnlstm_train_step_group
-    D, C, H, act = GEOMETRIES[geom]
+    D, C, H, act, NC, L = GEOMETRIES[geom]
     lr, steps = 1e-3, 3
-    models, sds = zip(*[build(D, C, H, 901 + 10 * k, act, P_RATE, P_BLOCK) for k in range(len(RAGGED))])
+    models, sds = zip(*[build(D, C, H, 901 + 10 * k, act, P_RATE, P_BLOCK, NC, L) for k in range(len(RAGGED))])
     for m in models:
         freeze_zero_grad(m)
     opts = [FusedAdam(m, lr=lr) for m in models]
@@ -276,8 +287,8 @@ def test_fused_group_step_follows_the_oracle_loop(geom):
     losses_o, losses_g = [], []
     for it in range(steps):
         xs = [synth_input(B, T, D, 950 + 10 * k + it) for k, (B, T) in enumerate(RAGGED)]
-        labels = [np.random.Generator(np.random.PCG64(960 + 10 * k + it)).integers(0, 2, B) for k, (B, _) in enumerate(RAGGED)]
-        mks = [to.make_masks(B, T, C, H, P_BLOCK, P_RATE, 970 + 10 * k + it) for k, (B, T) in enumerate(RAGGED)]
+        labels = [np.random.Generator(np.random.PCG64(960 + 10 * k + it)).integers(0, NC, B) for k, (B, _) in enumerate(RAGGED)]
+        mks = [to.make_masks(B, T, C, H, P_BLOCK, P_RATE, 970 + 10 * k + it, layers=L) for k, (B, T) in enumerate(RAGGED)]
         row = []
         for k in range(len(RAGGED)):
             r = to.forward_backward(params[k], xs[k], labels[k], act, masks=mks[k])
@@ -316,7 +327,7 @@ def test_group_longer_than_the_chunk():
     """K = train_group_max() + 1: the second chunk computes what a group of its own computes."""
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, cnnlstm_train_step_group, train_group_max
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     K = train_group_max() + 1
     models = [build(D, C, H, 1001 + (k % 3), act)[0] for k in range(K)]
     twins = [copy.deepcopy(models[0]), copy.deepcopy(models[K - 1])]
@@ -347,7 +358,7 @@ def fused_steps(m, opt, n, seed, D):
 def test_eval_after_fused_steps_sees_the_new_weights():
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import CNNLSTM, FusedAdam
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     m, _ = build(D, C, H, 1101, act)
     x = torch.from_numpy(synth_input(3, 20, D, 1102)).cuda()
     m.eval()
@@ -365,7 +376,7 @@ def test_eval_after_fused_steps_sees_the_new_weights():
 def test_fused_step_after_somebody_else_wrote_the_parameters(edit):
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import CNNLSTM, FusedAdam
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     m, _ = build(D, C, H, 1201, act)
     opt = FusedAdam(m)
     fused_steps(m, opt, 2, 1210, D)
@@ -386,7 +397,7 @@ def test_fused_step_after_somebody_else_wrote_the_parameters(edit):
 def test_state_dict_interchange_with_torch_adam():
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, train_param_offsets
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     lr = 1e-3
     total = train_param_offsets(build(D, C, H, 1301, act)[0].dims)[1]
     rng = np.random.Generator(np.random.PCG64(1302))
@@ -435,7 +446,7 @@ def test_state_dict_interchange_with_torch_adam():
 def test_reduce_lr_on_plateau_drives_the_fused_step():
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam, train_param_offsets
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
     total = train_param_offsets(build(D, C, H, 1401, act)[0].dims)[1]
     gb = torch.full((total,), 0.25, device="cuda")
     moves = []
@@ -457,7 +468,7 @@ def lockstep_setup(seed, make_opt, p=0.0, shuffle=True):
     import torch
     from torch.utils.data import DataLoader
     from robust_speech_analysis_framework_amd.cnnlstm import collate_zero_pad
-    D, C, H, act = GEOMETRIES["shortcut_conv_silu"]
+    D, C, H, act = GEOMETRIES["shortcut_conv_silu"][:4]
 
     def collate(batch):
         return collate_zero_pad([b[0] for b in batch], device="cpu"), torch.tensor([b[1] for b in batch], dtype=torch.long)
@@ -534,7 +545,7 @@ def test_reference_loop_with_only_the_optimizer_swapped():
     without a gradient is skipped."""
     import torch
     from robust_speech_analysis_framework_amd.cnnlstm import FusedAdam
-    D, C, H, act = GEOMETRIES["identity_shortcut_gelu"]
+    D, C, H, act = GEOMETRIES["identity_shortcut_gelu"][:4]
     lr = 1e-3
     (a, sd), (b, _) = build(D, C, H, 1701, act), build(D, C, H, 1701, act)
     fa, tb = FusedAdam(a, lr=lr), torch.optim.Adam(b.parameters(), lr=lr)

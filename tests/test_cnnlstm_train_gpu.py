@@ -211,25 +211,30 @@ def test_sixteen_row_recurrence_kernels_in_a_subprocess():
     code = r'''
 import sys, numpy as np, torch
 sys.path.insert(0, "tests/golden")
+sys.path.insert(0, "tests")
 from weights import synth_input, synth_state_dict
+import cnnlstm_geometry as geo
 from oracle import cnnlstm_train_oracle as to, cnnlstm_oracle as co
 from robust_speech_analysis_framework_amd.cnnlstm import CNNLSTM
-for D, C, H, act, B, T, seed in ((16, 32, 128, "silu", 19, 12, 305), (24, 64, 64, "gelu", 3, 31, 306)):
-    sd = synth_state_dict(D, C, H, seed)
-    m = CNNLSTM(input_dim=D, cnn_out_channels=C, lstm_hidden_dim=H, activation_fn=act, dropout_rate=0.5)
+def own_case(D, C, H, act, B, T, seed):
+    return ((D, C, H, act, 2, 2), synth_state_dict(D, C, H, seed), synth_input(B, T, D, seed + 1), np.arange(B) % 2,
+            to.make_masks(B, T, C, H, 0.2, 0.5, seed + 2))
+# the third entry is row 2 of tests/cnnlstm_geometry.py, with the weights, input, labels and masks of the table (whose
+# max-pool gap tests/test_cnnlstm_geometry_gpu.py asserts): three layers and five classes on the 16-row kernels
+cases = [own_case(16, 32, 128, "silu", 19, 12, 305), own_case(24, 64, 64, "gelu", 3, 31, 306),
+         (geo.geometry(2), geo.state_dict(2)) + geo.train_inputs(2)]
+for (D, C, H, act, NC, L), sd, x, labels, mk in cases:
+    m = CNNLSTM(input_dim=D, num_classes=NC, cnn_out_channels=C, lstm_hidden_dim=H, lstm_layers=L, activation_fn=act, dropout_rate=0.5)
     full = m.state_dict()
     full.update({k: torch.from_numpy(v) for k, v in sd.items()})
     m.load_state_dict(full)
     m = m.to("cuda")
-    x = synth_input(B, T, D, seed + 1)
     want_eval = co.forward_numpy(sd, x, act)
     got_eval = m.eval()(torch.from_numpy(x).cuda()).cpu().numpy()
     assert np.abs(got_eval - want_eval).max() < 1e-4 * max(np.abs(want_eval).max(), 1.0), "eval"
-    labels = np.arange(B) % 2
-    mk = to.make_masks(B, T, C, H, 0.2, 0.5, seed + 2)
     t = lambda a: torch.from_numpy(a).cuda()
     m.train()
-    m.forced_masks = {"res_block1": t(mk["res_block1"]), "res_block2": t(mk["res_block2"]), "lstm": [t(mk["lstm0"])], "fc": t(mk["fc"])}
+    m.forced_masks = {"res_block1": t(mk["res_block1"]), "res_block2": t(mk["res_block2"]), "lstm": [t(mk[f"lstm{l}"]) for l in range(L - 1)], "fc": t(mk["fc"])}
     out = m(t(x))
     torch.nn.CrossEntropyLoss()(out, t(labels)).backward()
     want = to.forward_backward(sd, x, labels, act, masks=mk)
