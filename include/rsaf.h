@@ -317,6 +317,38 @@ typedef struct {
 } rsaf_bn_running_item;
 int rsaf_bn_running_stats_group(const rsaf_bn_running_item* items_host, int K, int channels, rsaf_stream_t stream);
 
+/* ---- Dropout masks of a group training step from a counter-based generator, one launch per group ----------------
+ * Every mask element is a pure function of (seed, step, slot, element index): no generator state lives on the device,
+ * a mask does not depend on what else drew random numbers, and K replicas drawn in one call, one by one or in any order
+ * receive the same masks.  The masks are what rsaf_cnnlstm_train_forward reads: float32, 0 or 1 / (1 - p).
+ *
+ * The generator is the published Philox4x32-10 (Salmon et al., SC'11): multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * schedule constants 0x9E3779B9 / 0xBB67AE85, ten rounds, the key bumped between rounds.  The mapping, which any host
+ * can restate:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (j, slot, step & 0xffffffff, step >> 32),  j = e >> 2 the block of flat element index e
+ *   element e takes output word e & 3 of its block
+ *   thr     = (uint32) floor(p * 2^32), computed in double; the element is kept iff word >= thr
+ *   a kept element holds 1.0f / (float)(1.0 - p) (the subtraction in double, then the cast, then a float division),
+ *   every other element 0.0f; a slot with p >= 1 is all zeros.
+ * Slots (the element index is the flat index of the layout):
+ *   0 = res_block1 [B][T][C], 1 = res_block2 [B][T/2][C], 2 = fc [B][2H],
+ *   3 + l = LSTM inter-layer mask l [B][T/2][2H], l <= 2 (lstm_layers <= 4).
+ *
+ * rsaf_dropout_masks_group writes all drawn slots of K <= RSAF_CNNLSTM_GROUP_MAX items in ONE launch.  A slot with
+ * p <= 0 is not drawn: its pointer must be NULL (the training entries take NULL for "no mask").  No float at or beyond
+ * mask + n is written.  Checked before the launch, rsaf_last_error() naming item and slot: K in range; 0 <= n <= 2^32;
+ * p not NaN; a non-NULL slot has n >= 1, p > 0 and a 16-byte aligned pointer; no two drawn ranges of the call overlap.
+ * A call in which nothing is drawn returns RSAF_OK without a launch. */
+#define RSAF_DROPOUT_SLOTS 6
+typedef struct {
+    uint64_t seed, step;
+    float* mask[RSAF_DROPOUT_SLOTS];    /* NULL = slot not drawn */
+    int64_t n[RSAF_DROPOUT_SLOTS];      /* elements */
+    double p[RSAF_DROPOUT_SLOTS];
+} rsaf_dropout_item;
+int rsaf_dropout_masks_group(const rsaf_dropout_item* items_host, int K, rsaf_stream_t stream);
+
 /* ---- Group inference forward: K independent eval-mode forwards of one architecture in one call -----------------
  * The other half of the reference's loops: the validation pass of every epoch (src/dl_cv_strategies.py:131-139) and
  * _eval_model (:183-194).  No weight changes between the batches of such a pass, so every batch of every model is an

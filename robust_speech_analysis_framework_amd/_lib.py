@@ -62,6 +62,11 @@ class BnRunningItem(C.Structure):
                 ("unbias", C.c_double * 5)]
 
 
+class DropoutItem(C.Structure):
+    """``rsaf_dropout_item``: seed and step of one replica's stream and its up to six masks (NULL ``mask``: slot not drawn)."""
+    _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("mask", _P * 6), ("n", _L * 6), ("p", C.c_double * 6)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -103,6 +108,7 @@ SIGNATURES = {
     "rsaf_cnnlstm_adam_param_count": (_I, [_I, _I, _I, _I, _I]),
     "rsaf_cnnlstm_adam_group": (_I, [C.POINTER(AdamItem), _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_bn_running_stats_group": (_I, [C.POINTER(BnRunningItem), _I, _I, _P]),
+    "rsaf_dropout_masks_group": (_I, [C.POINTER(DropoutItem), _I, _P]),
     "rsaf_cnnlstm_forward_group": (_I, [C.POINTER(ForwardItem), _I, _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),

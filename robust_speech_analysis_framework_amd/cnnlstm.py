@@ -8,8 +8,8 @@ it folds BatchNorm into the convolutions, packs everything into one device blob 
 ``rsaf_cnnlstm_forward`` (fp32 MFMA GEMMs + persistent LSTM kernel).
 
 Training: in ``model.train()`` mode ``forward`` runs ``rsaf_cnnlstm_train_forward``
-(BatchNorm on batch statistics, dropout masks drawn from torch's device RNG, running statistics updated as
-``nn.BatchNorm1d`` does) inside a ``torch.autograd.Function`` whose backward is ``rsaf_cnnlstm_train_backward``:
+(BatchNorm on batch statistics, dropout masks drawn from torch's device RNG or, with ``model.dropout_stream`` set, from
+the counter-based generator of ``rsaf_dropout_masks_group``, running statistics updated as ``nn.BatchNorm1d`` does) inside a ``torch.autograd.Function`` whose backward is ``rsaf_cnnlstm_train_backward``:
 ``loss.backward()`` fills ``.grad`` of the ordinary parameters, so the reference's loops
 (``src/dl_cv_strategies.py:118-125,241-243``) and ``torch.optim.Adam(model.parameters())`` work unchanged.
 ``forward`` raises for CPU tensors instead of silently using a PyTorch fallback.
@@ -245,6 +245,7 @@ class CNNLSTM(nn.Module):
         self._workspace = None
         self._train_scratch = None
         self.forced_masks = None            # tests: explicit dropout masks for the next training-mode forward
+        self.dropout_stream = None          # a DropoutStream: masks from the counter-based generator instead of torch's RNG
 
     def packed_weights(self, device):
         """Folded weight blob on ``device`` (rebuilt when any parameter/buffer changed)."""
@@ -372,8 +373,8 @@ def cnnlstm_forward_group(models, xs):
 
 
 # ---- the other three modules of the CNN-LSTM path, under this import path ------------------------------------------------
-from .cnnlstm_train import (Segment, _pack_train_blob, _train_segments, _unpack_grads, cnnlstm_train_group,  # noqa: E402,F401
-                            draw_masks, train_group_max, train_param_offsets)
+from .cnnlstm_train import (DropoutStream, Segment, _pack_train_blob, _train_segments, _unpack_grads,  # noqa: E402,F401
+                            cnnlstm_train_group, draw_masks, draw_masks_group, train_group_max, train_param_offsets)
 from .cnnlstm_fused import FusedAdam, _adam_order, ce_loss_group, cnnlstm_train_step_group  # noqa: E402,F401
 from .cnnlstm_loops import (CNNLSTMGroup, eval_model_grouped, eval_replicas_lockstep,  # noqa: E402,F401
                             train_eval_replicas_lockstep, train_replicas_lockstep)

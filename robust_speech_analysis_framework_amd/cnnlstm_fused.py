@@ -349,9 +349,10 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
     is not touched; the packing of the parameter blobs, the loss, the optimizer and the running statistics are one launch
     each for the group.  A parameter with ``requires_grad = False`` keeps its value and its moments.
 
-    Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` are honoured, and
-    masks are drawn replica by replica in the same order, so with equal RNG state both paths see equal masks).  Lists
-    longer than ``train_group_max()`` are split into chunks of that size."""
+    Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` and
+    ``dropout_stream`` are honoured, and masks from torch's RNG are drawn replica by replica in the same order, so with
+    equal RNG state both paths see equal masks).  Lists longer than ``train_group_max()`` are split into chunks of that
+    size."""
     optimizers, labels = list(optimizers), list(labels)
     models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group")
     if not (len(optimizers) == len(labels) == len(models)):

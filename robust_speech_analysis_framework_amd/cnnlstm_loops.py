@@ -63,8 +63,11 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     optimizer of the call is the ``FusedAdam`` of its model, a step is one ``cnnlstm_train_step_group`` call (loss, Adam and running
     statistics in HIP, no autograd graph); anything else runs the loop above as written.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
     its permutations from torch's global RNG: in lock step the K loaders draw in a different order than K sequential
-    trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  The same holds
-    for dropout masks, which come from the device RNG replica by replica within a step."""
+    trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  Dropout masks
+    of a model that carries a ``DropoutStream`` (``model.dropout_stream``) are a function of the stream's seed and of the
+    number of steps the model has taken, so they are those of its sequential training whatever the grouping, and a
+    replica that sits out a step does not advance its stream.  Without a stream the masks come from torch's device RNG
+    replica by replica within a step, in another order than K sequential trainings draw them."""
     models, optimizers, loaders = list(models), list(optimizers), list(loaders)
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")

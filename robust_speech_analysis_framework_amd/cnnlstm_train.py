@@ -195,8 +195,106 @@ def draw_masks(model, B, T, device):
             "fc": mk((B, 2 * d["hidden"]), float(model.dropout.p))}
 
 
+class DropoutStream:
+    """Where a model's dropout masks come from when they are not torch's: ``seed`` (0 <= seed < 2**64) names the stream,
+    ``step`` counts the training steps that consulted it.  Every mask element is a pure function of (seed, step, mask
+    slot, element index) (``rsaf_dropout_masks_group``, include/rsaf.h), so the masks of a training do not depend on what
+    else draws random numbers, on how replicas are grouped or on their order, and ``state_dict()`` is all a checkpoint
+    needs to continue them.  Host state only: it is no module buffer, and ``model.state_dict()`` keeps the reference's keys.
+    Set it as ``model.dropout_stream``; one stream belongs to one model."""
+
+    def __init__(self, seed, step=0):
+        self.load_state_dict({"seed": seed, "step": step})
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, state):
+        seed, step = int(state["seed"]), int(state["step"])
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError(f"DropoutStream: seed must be in [0, 2**64), got {seed}")
+        if not 0 <= step < 2 ** 64:
+            raise ValueError(f"DropoutStream: step must be in [0, 2**64), got {step}")
+        self.seed, self.step = seed, step
+
+    def __repr__(self):
+        return f"DropoutStream(seed={self.seed}, step={self.step})"
+
+
+def _mask_slots(model, B, T):
+    """``(slot, shape, p)`` of the up to six masks of a step with input [B, T, D], slots as ``rsaf_dropout_masks_group``
+    numbers them: 0 res_block1, 1 res_block2, 2 fc, 3 + l the LSTM inter-layer mask l."""
+    d = model.dims
+    Tp, p_l = T // 2, float(model.lstm.dropout)
+    return [(0, (B, T, d["channels"]), float(model.res_block1.dropout.p)),
+            (1, (B, Tp, d["channels"]), float(model.res_block2.dropout.p)),
+            (2, (B, 2 * d["hidden"]), float(model.dropout.p))] + \
+           [(3 + l, (B, Tp, 2 * d["hidden"]), p_l) for l in range(d["layers"] - 1)]
+
+
+def draw_masks_group(models, shapes, streams, device):
+    """Dropout keep masks of one training step of K replicas, ``shapes[k] = (B_k, T_k)``, from ``streams[k]`` (a
+    ``DropoutStream`` each, no stream twice): a list of mask dicts in the format of ``draw_masks`` (None where p == 0).
+    All masks of up to ``train_group_max()`` replicas are views of one allocation (each starting at a multiple of 4
+    floats) and are written by one launch of ``rsaf_dropout_masks_group``.  The ``step`` of every stream that had a mask
+    to draw is used once and then incremented."""
+    models, shapes, streams = list(models), list(shapes), list(streams)
+    if not (len(models) == len(shapes) == len(streams)):
+        raise ValueError(f"{len(models)} models, {len(shapes)} shapes and {len(streams)} streams")
+    if torch.device(device).type != "cuda":
+        raise _lib.RsafError("draw_masks_group needs a HIP (cuda) device: there is no CPU fallback")
+    seen = {}
+    for k, st in enumerate(streams):
+        if not isinstance(st, DropoutStream):
+            raise ValueError(f"replica {k}: expected a DropoutStream, got {type(st).__name__}")
+        if id(st) in seen:
+            raise ValueError(f"replicas {seen[id(st)]} and {k} share one DropoutStream")
+        seen[id(st)] = k
+    records = []                                    # per replica: its stream and the (slot, shape, p) of the masks to draw
+    for model, (B, T), st in zip(models, shapes, streams):
+        records.append((st, [(slot, shape, p) for slot, shape, p in _mask_slots(model, int(B), int(T)) if p > 0.0]))
+    out = []
+    for _, chunk in _chunks(records):
+        total, placed = 0, []
+        for st, slots in chunk:
+            row = []
+            for slot, shape, p in slots:
+                n = 1
+                for v in shape:
+                    n *= v
+                row.append((slot, shape, p, total, n))
+                total += (n + 3) // 4 * 4
+            placed.append((st, row))
+        buf = torch.empty(total, dtype=torch.float32, device=device)
+        base = buf.data_ptr()
+
+        def fill(it, rec, _k):
+            st, row = rec
+            it.seed, it.step = st.seed, st.step
+            for slot, _, p, off, n in row:
+                it.mask[slot], it.n[slot], it.p[slot] = base + 4 * off, n, p
+
+        if total:                                   # a chunk of replicas without dropout has nothing to launch
+            _launch_chunked("rsaf_dropout_masks_group", _lib.DropoutItem, placed, fill)
+        for st, row in placed:
+            views = {slot: buf[off:off + n].view(shape) for slot, shape, _, off, n in row}
+            out.append(views)
+            if row:
+                st.step += 1
+    res = []
+    for model, views in zip(models, out):
+        res.append({"res_block1": views.get(0), "res_block2": views.get(1), "fc": views.get(2),
+                    "lstm": [views.get(3 + l) for l in range(model.dims["layers"] - 1)]})
+    return res
+
+
 def _masks_for(model, x):
-    return model.forced_masks if model.forced_masks is not None else draw_masks(model, x.shape[0], x.shape[1], x.device)
+    """Masks of a single-model training forward: ``forced_masks``, else the model's ``dropout_stream``, else torch's RNG."""
+    if model.forced_masks is not None:
+        return model.forced_masks
+    if model.dropout_stream is not None:
+        return draw_masks_group([model], [(x.shape[0], x.shape[1])], [model.dropout_stream], x.device)[0]
+    return draw_masks(model, x.shape[0], x.shape[1], x.device)
 
 
 def _tracked_bn(model, B, T):
@@ -349,7 +447,8 @@ def _train_step(models, xs, masks, single=False):
 # ---- group step ---------------------------------------------------------------------------------------------------------------
 def _check_train_group(models, xs, masks, who):
     """Argument checks of a group training step; returns (models, float32 contiguous inputs, one mask set per replica:
-    ``masks[k]``, else the model's ``forced_masks``, else drawn from torch's device RNG, replica by replica)."""
+    ``masks[k]``, else the model's ``forced_masks``, else from its ``dropout_stream`` (the replicas that come this far in
+    one launch), else drawn from torch's device RNG, replica by replica)."""
     models, xs = list(models), list(xs)
     if not models:
         raise ValueError(f"{who} needs at least one replica")
@@ -377,10 +476,18 @@ def _check_train_group(models, xs, masks, who):
 
     _check_group(models, xs, who, check_model, check_input)
     xs = [x.detach().to(torch.float32).contiguous() for x in xs]
-    mks = []
+    mks, streamed = [], []
     for k, (m, x) in enumerate(zip(models, xs)):
         mk = masks[k] if masks is not None else None
-        mks.append(mk if mk is not None else _masks_for(m, x))
+        if mk is None and m.forced_masks is None and m.dropout_stream is not None:
+            streamed.append(k)                     # drawn below, all such replicas in one launch
+        mks.append(mk if mk is not None else m.forced_masks if m.forced_masks is not None
+                   else None if m.dropout_stream is not None else draw_masks(m, x.shape[0], x.shape[1], x.device))
+    if streamed:
+        drawn = draw_masks_group([models[k] for k in streamed], [(xs[k].shape[0], xs[k].shape[1]) for k in streamed],
+                                 [models[k].dropout_stream for k in streamed], xs[0].device)
+        for k, mk in zip(streamed, drawn):
+            mks[k] = mk
     return models, xs, mks
 
 
@@ -392,5 +499,7 @@ def cnnlstm_train_group(models, xs, masks=None):
     separate ``model(x)`` steps, bit for bit; the LSTM recurrences of all replicas run in one launch per layer and pass.
 
     ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
-    model's ``forced_masks`` if set and draws them from torch's device RNG otherwise, replica by replica."""
+    model's ``forced_masks`` if set, else its ``dropout_stream`` if set (``draw_masks_group``: the masks of all such
+    replicas in one launch, each a function of its stream's seed and step alone), and draws them from torch's device RNG
+    otherwise, replica by replica.  A stream advances by one per step that consulted it."""
     return list(_train_step(*_check_train_group(models, xs, masks, "cnnlstm_train_group")))
