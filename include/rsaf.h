@@ -373,6 +373,49 @@ typedef struct {
 int rsaf_cnnlstm_forward_group(const rsaf_cnnlstm_forward_item* items_host, int K, int input_dim, int channels,
                                int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
 
+/* ---- Mixed groups: K replicas of different architecture in one call ---------------------------------------------
+ * The reference's hyper-parameter search (src/dl_cv_strategies.py:216-251) trains three inner folds per trial, and
+ * cnn_out_channels, lstm_hidden_dim and the activation change from trial to trial: a group of one architecture holds
+ * three replicas.  A mixed group holds K <= RSAF_CNNLSTM_GROUP_MAX replicas that share input_dim, num_classes and
+ * lstm_layers; item k has channels, hidden (64 or 128) and act of arch_host[k] (several trials in flight side by side).
+ * The three entries below do what rsaf_cnnlstm_train_forward_group, _backward_group and rsaf_cnnlstm_forward_group do,
+ * item k with its own architecture: ONE launch per LSTM layer and pass still carries the recurrences of all items,
+ * whatever their hidden size, and ONE launch the heads of all items of the inference forward.  Per item the arithmetic
+ * is that of the single entries, so every result equals, bit for bit, what the same items give through the single
+ * entries or through one group call per architecture; with all arch_host[k] equal it is what the group entry gives.
+ *
+ * The recurrence launches use 512-thread workgroups.  A hidden = 128 item runs as in the group entries (one workgroup
+ * per 4-row tile and direction).  The workgroup of a hidden = 64 item runs BOTH directions of its tile, waves 0-3 the
+ * forward and waves 4-7 the reverse direction, each half with LDS buffers of its own; both halves loop over the same
+ * T, so they take the same barriers, and the second-direction workgroups of such an item leave whole.  The rule the
+ * kernels keep: all eight waves of a workgroup either leave before the first LDS access or barrier, or take every
+ * barrier of the loop; no workgroup has some waves returned while others wait at a barrier.
+ *
+ * Checks, all before the first launch, rsaf_last_error() naming the item: 1 <= K <= RSAF_CNNLSTM_GROUP_MAX; items_host
+ * and arch_host non-NULL; the dims of every item as in the single entries; every per-item check of the group entries
+ * with the item's own architecture (sizes from rsaf_cnnlstm_train_saved_floats / _scratch_floats / _param_floats /
+ * rsaf_cnnlstm_workspace_bytes for that architecture), where a buffer smaller than the item's architecture needs
+ * (typically one sized for another item's) is RSAF_ERR_ARG; no two items overlapping as in the group entries.  In the
+ * inference entry, items that share `weights` must share an architecture (RSAF_ERR_ARG otherwise); the fp16 plane
+ * pairs are prepared once per distinct blob as in rsaf_cnnlstm_forward_group.  An item whose batch exceeds the 4-row
+ * recurrence threshold (RSAF_LSTM_SMALL_MAX) has its recurrences launched on its own; the others stay grouped.
+ *
+ * Around the model: rsaf_ce_loss_group and rsaf_dropout_masks_group know no architecture and take the whole mixed
+ * group in one launch.  rsaf_cnnlstm_pack_params_group, rsaf_cnnlstm_adam_group and rsaf_bn_running_stats_group carry
+ * the segment table of ONE architecture in their kernel arguments (six tables do not fit), so a mixed group calls each
+ * of them once per distinct architecture: a few element-wise launches in place of one. */
+typedef struct {
+    int channels, hidden, act;
+} rsaf_cnnlstm_arch;
+int rsaf_cnnlstm_train_forward_group_mixed(const rsaf_cnnlstm_train_item* items_host, const rsaf_cnnlstm_arch* arch_host,
+                                           int K, int input_dim, int num_classes, int lstm_layers,
+                                           rsaf_stream_t stream);
+int rsaf_cnnlstm_train_backward_group_mixed(const rsaf_cnnlstm_train_item* items_host,
+                                            const rsaf_cnnlstm_arch* arch_host, int K, int input_dim, int num_classes,
+                                            int lstm_layers, rsaf_stream_t stream);
+int rsaf_cnnlstm_forward_group_mixed(const rsaf_cnnlstm_forward_item* items_host, const rsaf_cnnlstm_arch* arch_host,
+                                     int K, int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream);
+
 /* ---- Wav2Vec2 frame embeddings for a batch of equal-length chunks -----------------------------------
  * Replaces, per chunk, `processor(chunk).input_values` + `Wav2Vec2Model(...)(input_values)
  * .last_hidden_state` (src/foundation_model_extractor.py:113-116; third-party transformers

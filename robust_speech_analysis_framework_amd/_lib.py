@@ -67,6 +67,11 @@ class DropoutItem(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("step", C.c_uint64), ("mask", _P * 6), ("n", _L * 6), ("p", C.c_double * 6)]
 
 
+class Arch(C.Structure):
+    """``rsaf_cnnlstm_arch``: what may differ between the items of a mixed group (``act``: 1 gelu, 2 silu)."""
+    _fields_ = [("channels", _I), ("hidden", _I), ("act", _I)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -110,6 +115,9 @@ SIGNATURES = {
     "rsaf_bn_running_stats_group": (_I, [C.POINTER(BnRunningItem), _I, _I, _P]),
     "rsaf_dropout_masks_group": (_I, [C.POINTER(DropoutItem), _I, _P]),
     "rsaf_cnnlstm_forward_group": (_I, [C.POINTER(ForwardItem), _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_train_forward_group_mixed": (_I, [C.POINTER(TrainItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_train_backward_group_mixed": (_I, [C.POINTER(TrainItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_forward_group_mixed": (_I, [C.POINTER(ForwardItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),
     "rsaf_mshds_intensity": (_I, [_P, _P, _I, _I, _P, _I, C.c_double, _I, _P, _P, _P]),

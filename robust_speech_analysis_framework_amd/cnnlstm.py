@@ -29,8 +29,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .cnnlstm_train import (_ACT_CODE, _check_group, _check_input, _chunks, _dims5, _launch_chunked, _masks_for, _sizes6,
-                            _train_step)
+from .cnnlstm_train import (_ACT_CODE, _SHARED_DIMS, _arch, _check_group, _check_input, _chunks, _dims5, _launch_chunked,
+                            _masks_for, _sizes6, _train_step)
 
 BN_EPS = 1e-5
 
@@ -320,11 +320,15 @@ _group_workspace = {}               # device -> cached workspace tensor of the g
 _WS_ALIGN = 256                     # bytes between the items' slices
 
 
-def cnnlstm_forward_group(models, xs):
+def cnnlstm_forward_group(models, xs, mixed=False):
     """Eval-mode forward of the pairs ``(models[i], xs[i])`` (same ``dims`` and activation; ``xs[i]`` of own shape
     [B_i, T_i, D]) under ``no_grad`` -> list of logits tensors, each equal to ``models[i](xs[i])`` bit for bit.  ``models``
     may name the same module several times (the batches of one validation loader): its weights are packed and split
-    once.  Lists longer than ``train_group_max()`` are split into chunks of that size."""
+    once.  Lists longer than ``train_group_max()`` are split into chunks of that size.
+
+    ``mixed=True``: the models may differ in ``cnn_out_channels``, ``lstm_hidden_dim`` (64 or 128) and activation; they share
+    ``input_dim``, ``num_classes`` and ``lstm_layers``.  The recurrences of all items still run in one launch per layer and
+    their heads in one launch (``rsaf_cnnlstm_forward_group_mixed``); the logits are the same bits."""
     models, xs = list(models), list(xs)
     if not models:
         raise ValueError("cnnlstm_forward_group needs at least one (model, input) pair")
@@ -338,7 +342,7 @@ def cnnlstm_forward_group(models, xs):
         if x.shape[0] > 0 and x.shape[1] < 2:
             raise ValueError(f"replica {k}: sequence length must be >= 2")
 
-    _check_group(models, xs, "cnnlstm_forward_group", check_model, check_input)
+    _check_group(models, xs, "cnnlstm_forward_group", check_model, check_input, mixed)
     lib = _lib.load()
     dims, device = models[0].dims, xs[0].device
     with torch.no_grad():
@@ -350,7 +354,7 @@ def cnnlstm_forward_group(models, xs):
         rows = [x.shape[0] for x in xs]
         outs = list(torch.split(torch.empty((sum(rows), dims["num_classes"]), dtype=torch.float32, device=device), rows))
         live = [k for k, B in enumerate(rows) if B > 0]                 # an empty batch is no item: its logits are [0, NC]
-        needs = [int(lib.rsaf_cnnlstm_workspace_bytes(*_sizes6(rows[k], xs[k].shape[1], dims))) for k in live]
+        needs = [int(lib.rsaf_cnnlstm_workspace_bytes(*_sizes6(rows[k], xs[k].shape[1], models[k].dims))) for k in live]
         offs, total = [], 0                                             # the items of a call side by side in one workspace
         for _, chunk in _chunks(needs):
             end = 0
@@ -367,8 +371,12 @@ def cnnlstm_forward_group(models, xs):
             it.workspace, it.workspace_bytes = ws.data_ptr() + offs[j], needs[j]
             it.logits = outs[k].data_ptr()
 
-        _launch_chunked("rsaf_cnnlstm_forward_group", _lib.ForwardItem, live, fill, *_dims5(dims),
-                        _ACT_CODE[models[0].activation_name])
+        if mixed:
+            _launch_chunked("rsaf_cnnlstm_forward_group_mixed", _lib.ForwardItem, live, fill, *[dims[f] for f in _SHARED_DIMS],
+                            arch=lambda k: _arch(models[k]))
+        else:
+            _launch_chunked("rsaf_cnnlstm_forward_group", _lib.ForwardItem, live, fill, *_dims5(dims),
+                            _ACT_CODE[models[0].activation_name])
     return outs
 
 

@@ -6,7 +6,9 @@ parameter blob, the unpacking of the gradient blob, the BatchNorm buffer updates
 torch: elementwise work on a few hundred thousand floats spread over 100+ small ops.  Here the blob is written from the
 parameters where they live (``rsaf_cnnlstm_pack_params_group``), ``rsaf_cnnlstm_adam_group`` reads the gradient blob and
 updates the parameters in their torch layouts, the loss and its gradient come from ``rsaf_ce_loss_group`` and the running
-statistics from ``rsaf_bn_running_stats_group``: one launch each per group step.
+statistics from ``rsaf_bn_running_stats_group``: one launch each per group step.  In a mixed group (replicas of different
+architecture, ``mixed=True``) the loss is still one launch; the packing, Adam and the running statistics, whose kernels carry
+the segment table of one architecture in their arguments, take one launch per distinct architecture of the group.
 
 Built on ``cnnlstm_train`` (replica plan, launchers, argument checks); ``cnnlstm`` re-exports the names of this module, so
 ``CNNLSTM`` is imported where it is needed, not at the top.
@@ -222,34 +224,45 @@ class FusedAdam(torch.optim.Optimizer):
         return loss
 
 
+def _by_dims(records, dims_of):
+    """``records`` split by the model dimensions the blob layout depends on, in order of first appearance: one list per
+    distinct ``_dims5`` (a group of one architecture gives one list)."""
+    parts = {}
+    for rec in records:
+        parts.setdefault(_dims5(dims_of(rec)), []).append(rec)
+    return list(parts.items())
+
+
 def _adam_group(entries):
-    """``entries``: [(optimizer, gradient blob or None, pointer table, skip mask)] of one architecture ->
-    ``rsaf_cnnlstm_adam_group`` in chunks of ``train_group_max()``; a replica whose parameters stand at different step
-    counts takes one launch per count."""
+    """``entries``: [(optimizer, gradient blob or None, pointer table, skip mask)] -> ``rsaf_cnnlstm_adam_group`` in
+    chunks of ``train_group_max()``, one series of launches per distinct architecture among the entries; a replica whose
+    parameters stand at different step counts takes one launch per count."""
     def fill(it, rec, _k):
         (opt, grads, table, _), (t, mask) = rec
         it.grads = grads.data_ptr() if grads is not None else None
         it.table, it.skip, it.step = table.data_ptr(), mask, t
         it.lr, it.beta1, it.beta2, it.eps = opt._hyper()
 
-    plans = [opt._launches(skip) for opt, _, _, skip in entries]
-    for j in range(max(len(pl) for pl in plans)):
-        live = [(e, pl[j]) for e, pl in zip(entries, plans) if j < len(pl)]
-        _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *_dims5(entries[0][0].model.dims))
+    for dims5, part in _by_dims(entries, lambda e: e[0].model.dims):
+        plans = [opt._launches(skip) for opt, _, _, skip in part]
+        for j in range(max(len(pl) for pl in plans)):
+            live = [(e, pl[j]) for e, pl in zip(part, plans) if j < len(pl)]
+            _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *dims5)
     for opt, _, _, skip in entries:
         opt._stepped(skip)
 
 
 def _pack_group(optimizers):
     """The parameter blobs of the optimizers' models, written on the device from the parameters where they live: one
-    launch of ``rsaf_cnnlstm_pack_params_group`` per chunk of ``train_group_max()``."""
-    pairs = [(opt._cached_table(), opt._blob_buffer()) for opt in optimizers]
+    launch of ``rsaf_cnnlstm_pack_params_group`` per chunk of ``train_group_max()`` and distinct architecture."""
+    pairs = [(opt._cached_table(), opt._blob_buffer(), opt.model.dims) for opt in optimizers]
 
     def fill(it, pair, _k):
         it.table, it.params = pair[0].data_ptr(), pair[1].data_ptr()
 
-    _launch_chunked("rsaf_cnnlstm_pack_params_group", _lib.PackItem, pairs, fill, *_dims5(optimizers[0].model.dims))
-    return [blob for _, blob in pairs]
+    for dims5, part in _by_dims(pairs, lambda pair: pair[2]):
+        _launch_chunked("rsaf_cnnlstm_pack_params_group", _lib.PackItem, part, fill, *dims5)
+    return [blob for _, blob, _ in pairs]
 
 
 def ce_loss_group(logits, labels, with_grad=True):
@@ -281,9 +294,10 @@ def ce_loss_group(logits, labels, with_grad=True):
     return losses, dl
 
 
-def _bn_running_group(reps, channels):
+def _bn_running_group(reps):
     """Running statistics of the replicas ``reps`` (``_Replica`` records) after a step: one launch of
-    ``rsaf_bn_running_stats_group`` per chunk, ``num_batches_tracked`` incremented on the host side in one foreach op.
+    ``rsaf_bn_running_stats_group`` per chunk and distinct channel count, ``num_batches_tracked`` incremented on the host
+    side in one foreach op.
     A replica with a ``momentum=None`` layer (cumulative average) takes the torch ops of ``_update_running_stats``.
     Returns the buffers written."""
     fused, counters, written = [], [], []
@@ -305,28 +319,36 @@ def _bn_running_group(reps, channels):
             it.running_mean[i], it.running_var[i] = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
             it.momentum[i], it.unbias[i] = float(bn.momentum), _unbias(n)
 
-    _launch_chunked("rsaf_bn_running_stats_group", _lib.BnRunningItem, fused, fill, channels)
+    by_channels = {}
+    for r in fused:
+        by_channels.setdefault(r.model.dims["channels"], []).append(r)
+    for channels, part in by_channels.items():
+        _launch_chunked("rsaf_bn_running_stats_group", _lib.BnRunningItem, part, fill, channels)
     if counters:
         torch._foreach_add_(counters, 1)
     return written
 
 
-def _train_step_chunk(models, optimizers, xs, labels, masks):
-    """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k])."""
-    d, device = models[0].dims, xs[0].device
-    K, nc, C = len(models), d["num_classes"], d["channels"]
+def _train_step_chunk(models, optimizers, xs, labels, masks, mixed=False):
+    """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k]).  The statistics and gradient
+    blobs of the replicas are slices of one allocation each, of every replica's own size (in a mixed group the channel
+    count and the blob length differ; every size is a multiple of 4 floats, so the slices stay 16-byte aligned)."""
+    device = xs[0].device
+    nc = models[0].dims["num_classes"]
     rows = [x.shape[0] for x in xs]
     logits_all = torch.empty((sum(rows), nc), dtype=torch.float32, device=device)
-    stats_all = torch.empty((K, 5, 3, C), dtype=torch.float32, device=device)
     logits = list(torch.split(logits_all, rows))
+    stats = [t.view(5, 3, -1) for t in torch.split(torch.empty(sum(15 * m.dims["channels"] for m in models), dtype=torch.float32,
+                                                               device=device), [15 * m.dims["channels"] for m in models])]
     blobs = _pack_group(optimizers)
-    reps = [_Replica(model, x, mk, blobs[k], logits[k], stats_all[k]) for k, (model, x, mk) in enumerate(zip(models, xs, masks))]
-    _launch_group(reps, False)
+    reps = [_Replica(model, x, mk, blobs[k], logits[k], stats[k]) for k, (model, x, mk) in enumerate(zip(models, xs, masks))]
+    _launch_group(reps, False, mixed)
     losses, dl = ce_loss_group(logits, labels)
-    grads = torch.zeros((K, blobs[0].numel()), dtype=torch.float32, device=device)   # one zero fill for the group
+    sizes = [b.numel() for b in blobs]
+    grads = torch.split(torch.zeros(sum(sizes), dtype=torch.float32, device=device), sizes)     # one zero fill for the group
     for k, r in enumerate(reps):
         r.dlogits, r.grads = dl[k], grads[k]
-    _launch_group(reps, True)
+    _launch_group(reps, True, mixed)
     entries = []
     for k, opt in enumerate(optimizers):
         skip = opt._frozen()
@@ -335,14 +357,14 @@ def _train_step_chunk(models, optimizers, xs, labels, masks):
     live = [e for e in entries if not e[0]._all_skipped(e[3])]
     if live:
         _adam_group(live)
-    buffers = _bn_running_group(reps, C)
+    buffers = _bn_running_group(reps)
     for opt, _, _, skip in entries:
         own = set(id(t) for t in opt.model.buffers())
         opt._written(opt._live(skip) + [t for t in buffers if id(t) in own])
     return losses, logits
 
 
-def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
+def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=False):
     """One whole training step of K independent ``CNNLSTM`` replicas, ``optimizers[k]`` the ``FusedAdam`` of ``models[k]``:
     group forward in training mode, ``nn.CrossEntropyLoss()`` (defaults) of ``labels[k]``, group backward, Adam and the
     BatchNorm running statistics -> ``(losses [K] on the device, [logits_k])``.  No autograd graph is built and ``.grad``
@@ -352,9 +374,13 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
     Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` and
     ``dropout_stream`` are honoured, and masks from torch's RNG are drawn replica by replica in the same order, so with
     equal RNG state both paths see equal masks).  Lists longer than ``train_group_max()`` are split into chunks of that
-    size."""
+    size, in list order.
+
+    ``mixed=True``: replicas of different architecture, as in ``cnnlstm_train_group``.  Forward and backward of a chunk are
+    one mixed call each and the loss stays one launch; the packing, Adam and the running statistics run once per distinct
+    architecture of the chunk.  Results equal those of one group step per architecture, bit for bit."""
     optimizers, labels = list(optimizers), list(labels)
-    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group")
+    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group", mixed)
     if not (len(optimizers) == len(labels) == len(models)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(labels)} label tensors")
     for k, (m, opt) in enumerate(zip(models, optimizers)):
@@ -367,7 +393,7 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None):
     with torch.no_grad():
         # every chunk is a whole step of its replicas, so the chunks are cut here and not call by call
         for _, chunk in _chunks(list(zip(models, optimizers, xs, labels, mks))):
-            ls, lg = _train_step_chunk(*zip(*chunk))
+            ls, lg = _train_step_chunk(*zip(*chunk), mixed=mixed)
             losses.append(ls)
             logits += lg
     return (losses[0] if len(losses) == 1 else torch.cat(losses)), logits

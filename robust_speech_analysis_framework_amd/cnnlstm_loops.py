@@ -18,15 +18,17 @@ from .cnnlstm_train import cnnlstm_train_group, train_group_max
 
 
 class CNNLSTMGroup(nn.Module):
-    """K ``CNNLSTM`` replicas of one architecture that train side by side.  ``forward(xs)`` takes one batch per replica
+    """K ``CNNLSTM`` replicas of one architecture (``mixed=True``: of any mix of architectures that share ``input_dim``,
+    ``num_classes`` and ``lstm_layers``) that train side by side.  ``forward(xs)`` takes one batch per replica
     (``None``: the replica sits out and its output is ``None``): in training mode the group step over the others, in
     eval mode the group inference forward over them (``cnnlstm_forward_group``).  ``state_dict`` keys are ``models.<k>.<reference key>``, so a
     replica's weights load into a plain ``CNNLSTM``."""
 
-    def __init__(self, models):
+    def __init__(self, models, mixed=False):
         from .cnnlstm import CNNLSTM
         super().__init__()
         self.models = nn.ModuleList(models)
+        self.mixed = bool(mixed)
         if len(self.models) == 0:
             raise ValueError("CNNLSTMGroup needs at least one replica")
         for k, m in enumerate(self.models):
@@ -42,15 +44,15 @@ class CNNLSTMGroup(nn.Module):
         outs = [None] * len(xs)
         if self.training:
             if live:
-                for k, o in zip(live, cnnlstm_train_group([self.models[k] for k in live], [xs[k] for k in live])):
+                for k, o in zip(live, cnnlstm_train_group([self.models[k] for k in live], [xs[k] for k in live], mixed=self.mixed)):
                     outs[k] = o
         elif live:
-            for k, o in zip(live, cnnlstm_forward_group([self.models[k] for k in live], [xs[k] for k in live])):
+            for k, o in zip(live, cnnlstm_forward_group([self.models[k] for k in live], [xs[k] for k in live], mixed=self.mixed)):
                 outs[k] = o
         return outs
 
 
-def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device):
+def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device, mixed=False):
     """The reference's inner training loop (``src/dl_cv_strategies.py:244-248``: ``zero_grad / model(seq) / loss /
     backward / step`` per batch, a fixed number of epochs) for K replicas over K loaders in lock step: step i of an
     epoch takes batch i of every loader through one group step.  Loaders may differ in length; a replica whose epoch
@@ -67,7 +69,10 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     of a model that carries a ``DropoutStream`` (``model.dropout_stream``) are a function of the stream's seed and of the
     number of steps the model has taken, so they are those of its sequential training whatever the grouping, and a
     replica that sits out a step does not advance its stream.  Without a stream the masks come from torch's device RNG
-    replica by replica within a step, in another order than K sequential trainings draw them."""
+    replica by replica within a step, in another order than K sequential trainings draw them.
+
+    ``mixed=True``: the replicas may differ in architecture (``cnnlstm_train_group``): several trials of a hyper-parameter
+    search, each with its folds, in one lock-step training."""
     models, optimizers, loaders = list(models), list(optimizers), list(loaders)
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
@@ -86,11 +91,11 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
             xs = [batches[k][0].to(device) for k in live]
             labs = [batches[k][1].to(device) for k in live]
             if fused:
-                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs)[0]
+                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs, mixed=mixed)[0]
             else:
                 for k in live:
                     optimizers[k].zero_grad()
-                outs = cnnlstm_train_group([models[k] for k in live], xs)
+                outs = cnnlstm_train_group([models[k] for k in live], xs, mixed=mixed)
                 losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
                 torch.stack(losses).sum().backward()
                 for k in live:
@@ -104,8 +109,8 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     return histories
 
 
-def _grouped_eval_batches(pairs, device):
-    """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models -> yields ``(tag, logits, lab on the device)``
+def _grouped_eval_batches(pairs, device, mixed=False):
+    """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models (``mixed``: of architectures too) -> yields ``(tag, logits, lab on the device)``
     in the same order, the forwards pooled into group calls of up to ``train_group_max()`` batches.  The batches stay as
     collated: zero padding is not masked (``src/dl_cv_strategies.py:81-84``), so regrouping sequences would change the
     results."""
@@ -114,7 +119,7 @@ def _grouped_eval_batches(pairs, device):
     pend = []
 
     def flush():
-        outs = cnnlstm_forward_group([p[1] for p in pend], [p[2] for p in pend])
+        outs = cnnlstm_forward_group([p[1] for p in pend], [p[2] for p in pend], mixed=mixed)
         res = [(p[0], o, p[3]) for p, o in zip(pend, outs)]
         pend.clear()
         return res
@@ -127,10 +132,11 @@ def _grouped_eval_batches(pairs, device):
         yield from flush()
 
 
-def eval_replicas_lockstep(models, loaders, device):
+def eval_replicas_lockstep(models, loaders, device, mixed=False):
     """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) for K models over K loaders: all (model, batch) pairs are
     pooled into group calls.  Returns K triples ``(labels, preds, probs)`` of NumPy arrays in loader order, equal to
-    what the reference's loop returns model by model; the results of a replica come to the host in one copy each."""
+    what the reference's loop returns model by model; the results of a replica come to the host in one copy each.
+    ``mixed=True``: the models may differ in architecture (``cnnlstm_forward_group``)."""
     from .cnnlstm import eval_outputs
     models, loaders = list(models), list(loaders)
     if len(models) != len(loaders):
@@ -140,7 +146,7 @@ def eval_replicas_lockstep(models, loaders, device):
     parts = [([], [], []) for _ in models]
     with torch.no_grad():
         pairs = ((k, m, seq, lab) for k, (m, ld) in enumerate(zip(models, loaders)) for seq, lab in ld)
-        for k, out, lab in _grouped_eval_batches(pairs, device):
+        for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
             prob, pred = eval_outputs(out)
             for lst, v in zip(parts[k], (lab, pred, prob)):
                 lst.append(v)
@@ -159,13 +165,15 @@ def eval_model_grouped(model, data_loader, device):
     return eval_replicas_lockstep([model], [data_loader], device)[0]
 
 
-def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, val_loaders, loss_fn, epochs, patience, device):
+def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, val_loaders, loss_fn, epochs, patience, device,
+                                 mixed=False):
     """``_train_eval_loop`` (``src/dl_cv_strategies.py:112-165``) for K replicas: per epoch the training pass of
     ``train_replicas_lockstep`` over the replicas still running, then the validation pass of all of them in group calls
     (``val_loss`` accumulated batch by batch in loader order; the losses of a pass come to the host in one copy), then per
     replica ``scheduler.step(avg_val_loss)`` (``schedulers[k]`` may be ``None``), best-weights checkpointing and early
     stopping as the reference does them.  A replica that stopped early sits out of the later epochs.  Returns
-    ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded."""
+    ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded.  ``mixed=True``: the
+    replicas may differ in architecture, in the training pass and in the validation pass alike."""
     models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
     train_loaders, val_loaders = list(train_loaders), list(val_loaders)
     K = len(models)
@@ -181,7 +189,7 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         if not running:
             break
         hist = train_replicas_lockstep([models[k] for k in running], [optimizers[k] for k in running],
-                                       [train_loaders[k] for k in running], loss_fn, 1, device)
+                                       [train_loaders[k] for k in running], loss_fn, 1, device, mixed=mixed)
         for k, h in zip(running, hist):
             train_hist[k].append(h[0])
         for k in running:
@@ -190,7 +198,7 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], loss_fn)
         with torch.no_grad():
             pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
-            for k, out, lab in _grouped_eval_batches(pairs, device):
+            for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
                 tags.append(k)
                 outs.append(out)
                 labs.append(lab)

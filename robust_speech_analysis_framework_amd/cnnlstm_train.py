@@ -5,7 +5,8 @@ Each replica's step is planned once (``_Replica``: sizes, saved activations, scr
 is read by ``_launch_single`` (``rsaf_cnnlstm_train_forward`` / ``_backward``, the one-replica case) and by
 ``_launch_chunked`` (every ``*_group`` entry of the library, ``train_group_max()`` items per call).
 
-Group training step: K independent replicas of one architecture in one step.
+Group training step: K independent replicas of one architecture in one step (``mixed=True``: of any mix of
+``cnn_out_channels``, ``lstm_hidden_dim`` and activation, see ``cnnlstm_train_group``).
 The reference trains models of identical architecture and hyper-parameters on different data one after another (the
 inner folds of an Optuna trial, ``src/dl_cv_strategies.py:224-251``; the folds of ``:399-422``).  One such training
 keeps 2 of the chip's 256 CUs busy during its LSTM recurrences, which are most of the step; K of them side by side
@@ -52,15 +53,26 @@ def _chunks(records):
         yield c0, records[c0:c0 + gmax]
 
 
-def _launch_chunked(entry, item_type, records, fill, *tail):
+def _launch_chunked(entry, item_type, records, fill, *tail, arch=None):
     """One call of the library's ``entry(items, n, *tail, stream)`` per chunk of ``records``; ``fill(item, record, k)``
-    writes the ctypes ``item_type`` of record ``k``, ``k`` counting over all of ``records``."""
+    writes the ctypes ``item_type`` of record ``k``, ``k`` counting over all of ``records``.  ``arch(record)`` (the
+    ``*_mixed`` entries): the ``(channels, hidden, act code)`` of a record; the call is then ``entry(items, archs, n,
+    *tail, stream)``."""
     fn = getattr(_lib.load(), entry)
     for c0, chunk in _chunks(records):
         items = (item_type * len(chunk))()
         for j, (it, r) in enumerate(zip(items, chunk)):
             fill(it, r, c0 + j)
-        _lib.check(fn(items, len(chunk), *tail, _lib.stream_ptr(None)), entry)
+        head = (items,) if arch is None else (items, (_lib.Arch * len(chunk))(*[_lib.Arch(*arch(r)) for r in chunk]))
+        _lib.check(fn(*head, len(chunk), *tail, _lib.stream_ptr(None)), entry)
+
+
+def _arch(model):
+    """What may differ between the replicas of a mixed group, as ``rsaf_cnnlstm_arch`` takes it."""
+    return model.dims["channels"], model.dims["hidden"], _ACT_CODE[model.activation_name]
+
+
+_SHARED_DIMS = ("input_dim", "num_classes", "layers")        # what the replicas of a mixed group have in common
 
 
 def _check_input(x, D, where=""):
@@ -68,12 +80,18 @@ def _check_input(x, D, where=""):
         raise ValueError(f"{where}expected input [B, T, {D}], got {tuple(x.shape)}")
 
 
-def _check_group(models, xs, who, check_model, check_input):
-    """The checks every group call makes: one architecture, inputs [B, T, D], HIP tensors.  ``check_model(k, m)`` and
-    ``check_input(k, x)`` are the caller's own checks of a replica, made right after the shared one of that replica."""
+def _check_group(models, xs, who, check_model, check_input, mixed=False):
+    """The checks every group call makes: one architecture (``mixed``: one ``input_dim``, ``num_classes`` and number of
+    LSTM layers), inputs [B, T, D], HIP tensors.  ``check_model(k, m)`` and ``check_input(k, x)`` are the caller's own
+    checks of a replica, made right after the shared one of that replica."""
     first = models[0]
     for k, m in enumerate(models):
-        if m.dims != first.dims or m.activation_name != first.activation_name:
+        if mixed:
+            for field in _SHARED_DIMS:
+                if m.dims[field] != first.dims[field]:
+                    raise ValueError(f"replica {k} differs from replica 0 in {field}: {m.dims[field]} against "
+                                     f"{first.dims[field]} (a mixed group shares {', '.join(_SHARED_DIMS)})")
+        elif m.dims != first.dims or m.activation_name != first.activation_name:
             raise ValueError(f"replica {k} differs from replica 0: dims {m.dims} / activation {m.activation_name!r} against "
                              f"{first.dims} / {first.activation_name!r}")
         check_model(k, m)
@@ -368,12 +386,19 @@ def _fill_train_item(backward):
     return fill
 
 
-def _launch_group(reps, backward):
-    """``rsaf_cnnlstm_train_{forward,backward}_group`` over the replicas ``reps`` of one architecture."""
-    if reps:
-        m = reps[0].model
-        _launch_chunked(f"rsaf_cnnlstm_train_{'backward' if backward else 'forward'}_group", _lib.TrainItem, reps,
-                        _fill_train_item(backward), *_dims5(m.dims), _ACT_CODE[m.activation_name])
+def _launch_group(reps, backward, mixed=False):
+    """``rsaf_cnnlstm_train_{forward,backward}_group`` over the replicas ``reps`` of one architecture; ``mixed``: the
+    ``_group_mixed`` entries over replicas of any mix of architectures."""
+    if not reps:
+        return
+    d = reps[0].model.dims
+    entry = f"rsaf_cnnlstm_train_{'backward' if backward else 'forward'}_group"
+    if mixed:
+        _launch_chunked(entry + "_mixed", _lib.TrainItem, reps, _fill_train_item(backward),
+                        *[d[f] for f in _SHARED_DIMS], arch=lambda r: _arch(r.model))
+    else:
+        _launch_chunked(entry, _lib.TrainItem, reps, _fill_train_item(backward), *_dims5(d),
+                        _ACT_CODE[reps[0].model.activation_name])
 
 
 def _launch_single(r, backward):
@@ -389,30 +414,31 @@ def _launch_single(r, backward):
         r.scratch.numel(), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.stream_ptr(None)), entry)
 
 
-def _launch(reps, backward, single):
-    if single:
+def _launch(reps, backward, path):
+    """``path``: "single" (the one replica of ``model(x)``), "group" or "mixed"."""
+    if path == "single":
         for r in reps:
             _launch_single(r, backward)
     else:
-        _launch_group(reps, backward)
+        _launch_group(reps, backward, mixed=path == "mixed")
 
 
 # ---- autograd function ------------------------------------------------------------------------------------------------------
 class _TrainStep(torch.autograd.Function):
     """(logits_0, ..., logits_K-1) of K replicas in training mode; backward fills the parameter gradients of every
-    replica whose output received a gradient (none for the inputs).  ``single``: the one replica of ``model(x)``, which
-    goes through the single entries."""
+    replica whose output received a gradient (none for the inputs).  ``path``: "single" is the one replica of
+    ``model(x)``, which goes through the single entries; "group" / "mixed" as ``_launch`` takes it."""
 
     @staticmethod
-    def forward(ctx, models, xs, masks, segments, single, *params):
+    def forward(ctx, models, xs, masks, segments, path, *params):
         ctx.set_materialize_grads(False)          # an output outside the loss arrives as None, not as zeros
         reps = []
         for model, x, mk, sg in zip(models, xs, masks, segments):
             r = _Replica(model, x, mk, _pack_train_blob(model, x.device, sg)[1])
             r.segs, r.params = sg[0], _blob_params(sg[0])        # ``params``, replica by replica: the order of the gradients
             reps.append(r)
-        ctx.reps, ctx.single = reps, single
-        _launch(reps, False, single)
+        ctx.reps, ctx.path = reps, path
+        _launch(reps, False, path)
         for r in reps:
             _update_running_stats(r.model, r.stats, r.B, r.T)
         return tuple(r.logits for r in reps)
@@ -420,7 +446,7 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *dlogits):
         if ctx.reps is None:
-            raise RuntimeError(f"CNNLSTM {'' if ctx.single else 'group '}training step: backward can run once per forward "
+            raise RuntimeError(f"CNNLSTM {'' if ctx.path == 'single' else 'group '}training step: backward can run once per forward "
                                "(the saved activations are consumed)")
         live = []
         for r, dl in zip(ctx.reps, dlogits):
@@ -430,7 +456,7 @@ class _TrainStep(torch.autograd.Function):
             r.dlogits = dl.to(torch.float32).contiguous()
             r.grads = torch.zeros_like(r.blob)
             live.append(r)
-        _launch(live, True, ctx.single)
+        _launch(live, True, ctx.path)
         out = []
         for r, dl in zip(ctx.reps, dlogits):
             out += [None] * len(r.params) if dl is None else _unpack_grads(r.segs, r.params, r.grads)
@@ -438,14 +464,15 @@ class _TrainStep(torch.autograd.Function):
         return (None, None, None, None, None, *out)
 
 
-def _train_step(models, xs, masks, single=False):
+def _train_step(models, xs, masks, single=False, mixed=False):
     """Training-mode forward of checked replicas -> tuple of logits on the autograd graph of their parameters."""
     segments = [_train_segments(m) for m in models]
-    return _TrainStep.apply(models, xs, masks, segments, single, *[p for sg in segments for p in _blob_params(sg[0])])
+    path = "single" if single else "mixed" if mixed else "group"
+    return _TrainStep.apply(models, xs, masks, segments, path, *[p for sg in segments for p in _blob_params(sg[0])])
 
 
 # ---- group step ---------------------------------------------------------------------------------------------------------------
-def _check_train_group(models, xs, masks, who):
+def _check_train_group(models, xs, masks, who, mixed=False):
     """Argument checks of a group training step; returns (models, float32 contiguous inputs, one mask set per replica:
     ``masks[k]``, else the model's ``forced_masks``, else from its ``dropout_stream`` (the replicas that come this far in
     one launch), else drawn from torch's device RNG, replica by replica)."""
@@ -474,7 +501,7 @@ def _check_train_group(models, xs, masks, who):
         if x.shape[0] * (x.shape[1] // 2) <= 1:
             raise ValueError(f"replica {k}: Expected more than 1 value per channel when training")
 
-    _check_group(models, xs, who, check_model, check_input)
+    _check_group(models, xs, who, check_model, check_input, mixed)
     xs = [x.detach().to(torch.float32).contiguous() for x in xs]
     mks, streamed = [], []
     for k, (m, x) in enumerate(zip(models, xs)):
@@ -491,7 +518,7 @@ def _check_train_group(models, xs, masks, who):
     return models, xs, mks
 
 
-def cnnlstm_train_group(models, xs, masks=None):
+def cnnlstm_train_group(models, xs, masks=None, mixed=False):
     """One training-mode forward of K independent ``CNNLSTM`` replicas (same ``dims`` and activation; own weights, own
     batch ``xs[k]`` of own shape [B_k, T_k, D]) -> list of K logits tensors.  Sum the K losses and call ``backward()``
     once: the replicas share nothing, so each model's ``.grad`` is the gradient of its own loss, and an output that
@@ -501,5 +528,10 @@ def cnnlstm_train_group(models, xs, masks=None):
     ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
     model's ``forced_masks`` if set, else its ``dropout_stream`` if set (``draw_masks_group``: the masks of all such
     replicas in one launch, each a function of its stream's seed and step alone), and draws them from torch's device RNG
-    otherwise, replica by replica.  A stream advances by one per step that consulted it."""
-    return list(_train_step(*_check_train_group(models, xs, masks, "cnnlstm_train_group")))
+    otherwise, replica by replica.  A stream advances by one per step that consulted it.
+
+    ``mixed=True``: the replicas may differ in ``cnn_out_channels``, ``lstm_hidden_dim`` (64 or 128) and activation (the
+    trials of a hyper-parameter search side by side); they share ``input_dim``, ``num_classes`` and ``lstm_layers``.  One
+    launch per layer and pass still carries the recurrences of all replicas (``rsaf_cnnlstm_train_forward_group_mixed``
+    / ``_backward_group_mixed``), and the results are still those of K separate steps, bit for bit."""
+    return list(_train_step(*_check_train_group(models, xs, masks, "cnnlstm_train_group", mixed), mixed=mixed))

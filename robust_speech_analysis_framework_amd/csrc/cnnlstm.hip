@@ -65,13 +65,20 @@ static Layout make_layout(const Dims& d) {
     return L;
 }
 
+// what is wrong with the dims, or NULL
+static const char* dims_problem(const Dims& d) {
+    if (!(d.D > 0 && d.D % 4 == 0)) return "input_dim must be a positive multiple of 4";
+    if (!(d.C > 0 && d.C % 4 == 0)) return "cnn_out_channels must be a positive multiple of 4";
+    if (!(d.H == 64 || d.H == 128)) return "lstm_hidden_dim must be 64 or 128 (reference search space)";
+    if (!(d.NC >= 1 && d.NC <= 16)) return "num_classes must be in [1, 16]";
+    if (!(d.L >= 1 && d.L <= 4)) return "lstm_layers must be in [1, 4]";
+    if (!(d.act == ACT_GELU || d.act == ACT_SILU)) return "activation must be gelu (1) or silu (2)";
+    return nullptr;
+}
+
 static int check_dims(const Dims& d) {
-    RSAF_CHECK_ARG(d.D > 0 && d.D % 4 == 0, "input_dim must be a positive multiple of 4");
-    RSAF_CHECK_ARG(d.C > 0 && d.C % 4 == 0, "cnn_out_channels must be a positive multiple of 4");
-    RSAF_CHECK_ARG(d.H == 64 || d.H == 128, "lstm_hidden_dim must be 64 or 128 (reference search space)");
-    RSAF_CHECK_ARG(d.NC >= 1 && d.NC <= 16, "num_classes must be in [1, 16]");
-    RSAF_CHECK_ARG(d.L >= 1 && d.L <= 4, "lstm_layers must be in [1, 4]");
-    RSAF_CHECK_ARG(d.act == ACT_GELU || d.act == ACT_SILU, "activation must be gelu (1) or silu (2)");
+    const char* problem = dims_problem(d);
+    RSAF_CHECK_ARG(!problem, problem);
     return RSAF_OK;
 }
 
@@ -204,15 +211,21 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_rec_kernel(const float* xpro
 // exchanged through a wave-private LDS tile so that lane (q, u) updates cell (row q, unit u).
 // The body is shared by the one-recurrence kernel and the group kernel below: `dir` and `tile` (the 4-row tile of the
 // batch) are what blockIdx.y / blockIdx.x are to the former.
-template <int H, bool SAVE>
+// HALVES = 2 (the mixed group kernel, H = 64): the workgroup is two such bodies side by side, threads [0, 16 H) and
+// [16 H, 32 H), each on its own half of the LDS buffers; `dir` is then the half's own direction.  Both halves take the
+// same B and T, so they meet at every barrier.
+template <int H, bool SAVE, int HALVES = 1>
 __device__ __forceinline__ void lstm_rec4_body(const float* xproj, const float* __restrict__ whh,
                                                float* __restrict__ hout, float* gates_save,
                                                float* __restrict__ c_save, int B, int T, int dir, int tile) {
     constexpr int LDH = H + 4;
     constexpr int NW = H / 16;
-    __shared__ __attribute__((aligned(16))) float hbuf[2][4][LDH];
-    __shared__ float gx[NW][4][80];                 // [wave][row][16*gate + u], row stride 80: conflict-free both ways
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ __attribute__((aligned(16))) float hbuf_all[HALVES][2][4][LDH];
+    __shared__ float gx_all[HALVES][NW][4][80];     // [wave][row][16*gate + u], row stride 80: conflict-free both ways
+    const int half = HALVES == 1 ? 0 : (int)threadIdx.x / (NW * 64);
+    auto& hbuf = hbuf_all[half];
+    auto& gx = gx_all[half];
+    const int tid = HALVES == 1 ? (int)threadIdx.x : (int)threadIdx.x - half * (NW * 64), lane = tid & 63, w = tid >> 6;
     const int gq = lane >> 4, u = lane & 15;        // as a column: gate gq of unit u; as a cell owner: row gq of unit u
     const int b0 = tile * 4;
     const int unit = 16 * w + u;
@@ -324,6 +337,23 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_group_kernel(const Lstm
     lstm_rec4_body<H, SAVE>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, blockIdx.y, blockIdx.x);
 }
 
+// Recurrences of different H in one launch (LstmRecMixedItem, cnnlstm_kernels.h): grid (max tiles, 2, K), 512 threads.  Every
+// exit below is taken by the whole workgroup (the descriptor and the block index are uniform) and comes before the first
+// LDS access or barrier; a workgroup that enters a body runs all eight waves through every barrier of its loop.
+template <bool SAVE>
+__global__ __launch_bounds__(512) void lstm_rec4_group_mixed_kernel(const LstmRecMixedGroup g) {
+    const LstmRecMixedItem& m = g.item[blockIdx.z];
+    const LstmRecItem& it = m.rec;
+    if ((int)blockIdx.x * 4 >= it.B) return;
+    if (m.H == 128) {
+        lstm_rec4_body<128, SAVE>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, blockIdx.y, blockIdx.x);
+        return;
+    }
+    if (blockIdx.y != 0) return;                       // H = 64: the blockIdx.y == 0 workgroup runs both directions
+    const int dir = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+    lstm_rec4_body<64, SAVE, 2>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, dir, blockIdx.x);
+}
+
 // ---- attention pooling (softmax over time) + final Linear -----------------------------------------
 // The body is shared by the one-batch kernel and the group kernel below: `b` (the batch row) is what blockIdx.x is to both.
 template <int NF>   // features per lane: 2H = 64*NF
@@ -403,6 +433,16 @@ __global__ __launch_bounds__(256) void attnpool_fc_group_kernel(const AttnPoolGr
     attnpool_fc_body<NF>(it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits, it.pooled_out, it.T, NC, blockIdx.x);
 }
 
+// The same for heads of different H (AttnPoolMixedItem): the features per lane are the item's.  Both exits are taken by the
+// whole workgroup.
+__global__ __launch_bounds__(256) void attnpool_fc_group_mixed_kernel(const AttnPoolMixedGroup g, int NC) {
+    const AttnPoolMixedItem& m = g.item[blockIdx.y];
+    const AttnPoolItem& it = m.head;
+    if ((int)blockIdx.x >= it.B) return;
+    if (m.H == 128) attnpool_fc_body<4>(it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits, it.pooled_out, it.T, NC, blockIdx.x);
+    else attnpool_fc_body<2>(it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits, it.pooled_out, it.T, NC, blockIdx.x);
+}
+
 }  // namespace cnnlstm
 
 int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* gates_save, float* c_save, int B, int T,
@@ -456,6 +496,32 @@ int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s)
     if (save) { if (H == 128) RSAF_LSTM_LAUNCH(128, true); else RSAF_LSTM_LAUNCH(64, true); }
     else { if (H == 128) RSAF_LSTM_LAUNCH(128, false); else RSAF_LSTM_LAUNCH(64, false); }
 #undef RSAF_LSTM_LAUNCH
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int launch_lstm_rec_group_mixed(const LstmRecMixedItem* items, int K, hipStream_t s) {
+    using namespace cnnlstm;
+    RSAF_CHECK_ARG(items && K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "a group holds 1 to 16 recurrences");
+    LstmRecMixedGroup g{};
+    const bool save = items[0].rec.gates_save != nullptr;
+    int tiles = 0;
+    double flops = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const LstmRecItem& it = items[k].rec;
+        const int H = items[k].H;
+        RSAF_CHECK_ARG(H == 64 || H == 128, "lstm_hidden_dim must be 64 or 128");
+        RSAF_CHECK_ARG(it.B >= 1 && it.B <= lstm_small_max() && it.T >= 1, "a grouped recurrence runs on the 4-row tiles");
+        RSAF_CHECK_ARG((it.gates_save != nullptr) == save && (it.c_save != nullptr) == save,
+                       "gates_save and c_save go together, for all recurrences of a group or for none");
+        g.item[k] = items[k];
+        tiles = std::max(tiles, (it.B + 3) / 4);
+        flops += 2.0 * it.B * it.T * 2.0 * 4 * H * H;
+    }
+    ProfScope prof("lstm_recurrent", s, flops, 0.0);
+    dim3 grid(tiles, 2, K);
+    if (save) hipLaunchKernelGGL(lstm_rec4_group_mixed_kernel<true>, grid, dim3(512), 0, s, g);
+    else hipLaunchKernelGGL(lstm_rec4_group_mixed_kernel<false>, grid, dim3(512), 0, s, g);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
@@ -664,6 +730,7 @@ static F16Ws make_f16_ws(const Dims& d, int B, int T) {
 // all items, one grouped recurrence launch per layer in between and one grouped head.  Per item these are the same kernels
 // with the same launch parameters in the same order, so the logits are those of K single calls, bit for bit.
 struct Fwd {
+    Dims d; Layout L;               // the item's own architecture (one for all items, except in a mixed group)
     const float* x; int B, T;
     const float* W;
     float* logits;
@@ -688,15 +755,17 @@ static int fail(int code, const char* who, int idx, const std::string& msg) {
     return code;
 }
 
-// argument checks of one forward (idx < 0: the single entries, whose messages carry no item) and its buffers
+// argument checks of one forward (idx < 0: the single entries, whose messages carry no item) and its buffers; `short_code`:
+// what a workspace below the item's need returns
 static int check_item(const Dims& d, const float* x, int B, int T, const float* weights, void* workspace, int64_t workspace_bytes,
-                      float* logits, const char* who, int idx, Fwd* f) {
+                      float* logits, const char* who, int idx, Fwd* f, int short_code = RSAF_ERR_WORKSPACE) {
     if (!(B >= 1 && B <= 65535)) return fail(RSAF_ERR_ARG, who, idx, "batch must be in [1, 65535]");
     if (!(T >= 2)) return fail(RSAF_ERR_ARG, who, idx, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
     if (!((int64_t)B * (T / 2) <= 0x7fffffffLL)) return fail(RSAF_ERR_ARG, who, idx, "B*T too large");
     if (!(x && weights && workspace && logits)) return fail(RSAF_ERR_ARG, who, idx, "NULL pointer");
-    if (workspace_bytes < rsaf_cnnlstm_workspace_bytes(B, T, d.D, d.C, d.H, d.L)) return fail(RSAF_ERR_WORKSPACE, who, idx, "workspace too small");
+    if (workspace_bytes < rsaf_cnnlstm_workspace_bytes(B, T, d.D, d.C, d.H, d.L)) return fail(short_code, who, idx, short_code == RSAF_ERR_WORKSPACE ? "workspace too small" : "workspace too small for this item's architecture");
     *f = Fwd{};
+    f->d = d; f->L = make_layout(d);
     f->x = x; f->B = B; f->T = T; f->W = weights; f->logits = logits;
     const int Tp = T / 2;
     float* ws = static_cast<float*>(workspace);
@@ -933,63 +1002,76 @@ static AttnPoolItem head_item(const Fwd& f, const Layout& L) {
     return AttnPoolItem{f.lin, f.W + L.watt, f.W + L.batt, f.W + L.wfc, f.W + L.bfc, f.logits, f.pooled_out, f.B, f.T / 2};
 }
 
-// attention pooling + fc (:187-191): one launch per forward, or one for the heads of all of them
-static int head(const Fwd* fs, int K, const Dims& d, const Layout& L, bool grouped, hipStream_t s) {
-    const int H = d.H;
-    if (!grouped) {
+// attention pooling + fc (:187-191): one launch per forward (SINGLE), one for the heads of all of them (GROUPED: one
+// architecture; MIXED: an architecture per item)
+enum { SINGLE = 0, GROUPED = 1, MIXED = 2 };
+
+static int head(const Fwd* fs, int K, int mode, hipStream_t s) {
+    const int NC = fs[0].d.NC;
+    if (mode == SINGLE) {
         for (int k = 0; k < K; ++k) {
-            const AttnPoolItem it = head_item(fs[k], L);
+            const int H = fs[k].d.H;
+            const AttnPoolItem it = head_item(fs[k], fs[k].L);
             ProfScope prof("attnpool_fc", s, 0.0, (double)it.B * it.T * 2 * H * 4);
             if (H == 128)
                 hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
-                                   it.pooled_out, it.T, d.NC);
+                                   it.pooled_out, it.T, NC);
             else
                 hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
-                                   it.pooled_out, it.T, d.NC);
+                                   it.pooled_out, it.T, NC);
             RSAF_CHECK_HIP(hipGetLastError());
         }
         return RSAF_OK;
     }
     AttnPoolGroup g{};
+    AttnPoolMixedGroup gm{};
     int rows = 0;
     double bytes = 0.0;
     for (int k = 0; k < K; ++k) {
-        g.item[k] = head_item(fs[k], L);
+        g.item[k] = head_item(fs[k], fs[k].L);
+        gm.item[k] = AttnPoolMixedItem{g.item[k], fs[k].d.H};
         rows = std::max(rows, fs[k].B);
-        bytes += (double)g.item[k].B * g.item[k].T * 2 * H * 4;
+        bytes += (double)g.item[k].B * g.item[k].T * 2 * fs[k].d.H * 4;
     }
     ProfScope prof("attnpool_fc", s, 0.0, bytes);
-    if (H == 128) hipLaunchKernelGGL(attnpool_fc_group_kernel<4>, dim3(rows, K), dim3(256), 0, s, g, d.NC);
-    else hipLaunchKernelGGL(attnpool_fc_group_kernel<2>, dim3(rows, K), dim3(256), 0, s, g, d.NC);
+    if (mode == MIXED) hipLaunchKernelGGL(attnpool_fc_group_mixed_kernel, dim3(rows, K), dim3(256), 0, s, gm, NC);
+    else if (fs[0].d.H == 128) hipLaunchKernelGGL(attnpool_fc_group_kernel<4>, dim3(rows, K), dim3(256), 0, s, g, NC);
+    else hipLaunchKernelGGL(attnpool_fc_group_kernel<2>, dim3(rows, K), dim3(256), 0, s, g, NC);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
 
-// `grouped`: one launch per layer carries the recurrences of all items whose batch runs on the 4-row kernel (an item above
-// lstm_small_max() has its recurrence launched on its own), and one launch the heads; otherwise one launch per item
-static int run_forward(Fwd* fs, int K, const Dims& d, bool grouped, hipStream_t s) {
-    const Layout L = make_layout(d);
+// GROUPED / MIXED: one launch per layer carries the recurrences of all items whose batch runs on the 4-row kernel (an item
+// above lstm_small_max() has its recurrence launched on its own), and one launch the heads; SINGLE: one launch per item.
+// Every item carries its own dims and layout; only a MIXED call has items that differ in them (never in D, NC or L).
+static int run_forward(Fwd* fs, int K, int mode, hipStream_t s) {
+    const int layers = fs[0].d.L;
     for (int k = 0; k < K; ++k)
-        if (fs[k].f16 && fs[k].prep) TRY(prep_weights(fs[k], d, L, s));
-    for (int k = 0; k < K; ++k) TRY(front(fs[k], d, L, s));
-    for (int l = 0; l < d.L; ++l) {
-        LstmRecItem small[RSAF_CNNLSTM_GROUP_MAX];
+        if (fs[k].f16 && fs[k].prep) TRY(prep_weights(fs[k], fs[k].d, fs[k].L, s));
+    for (int k = 0; k < K; ++k) TRY(front(fs[k], fs[k].d, fs[k].L, s));
+    for (int l = 0; l < layers; ++l) {
+        LstmRecMixedItem small[RSAF_CNNLSTM_GROUP_MAX];
         int n_small = 0;
         for (int k = 0; k < K; ++k) {
-            const LstmRecItem it = rec_item(fs[k], d, L, l);
-            if (grouped && it.B <= lstm_small_max()) small[n_small++] = it;
-            else TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, nullptr, nullptr, it.B, it.T, d.H, s));
+            const LstmRecItem it = rec_item(fs[k], fs[k].d, fs[k].L, l);
+            if (mode != SINGLE && it.B <= lstm_small_max()) small[n_small++] = LstmRecMixedItem{it, fs[k].d.H};
+            else TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, nullptr, nullptr, it.B, it.T, fs[k].d.H, s));
         }
-        if (n_small) TRY(launch_lstm_rec_group(small, n_small, d.H, s));
+        if (n_small && mode == MIXED) TRY(launch_lstm_rec_group_mixed(small, n_small, s));
+        else if (n_small) {
+            LstmRecItem same[RSAF_CNNLSTM_GROUP_MAX];
+            for (int k = 0; k < n_small; ++k) same[k] = small[k].rec;
+            TRY(launch_lstm_rec_group(same, n_small, fs[0].d.H, s));
+        }
         for (int k = 0; k < K; ++k) {
             Fwd& f = fs[k];
             f.lin = f.lout;
             f.lout = (f.lout == f.seq0) ? f.seq1 : f.seq0;
-            if (l + 1 < d.L) TRY(inproj(f, d, L, l + 1, s));
+            if (l + 1 < layers) TRY(inproj(f, f.d, f.L, l + 1, s));
         }
     }
-    for (int k = 0; k < K; ++k) TRY(tap_copy(fs[k].lstm_out, fs[k].lin, (int64_t)fs[k].B * (fs[k].T / 2) * 2 * d.H, s));
-    return head(fs, K, d, L, grouped, s);
+    for (int k = 0; k < K; ++k) TRY(tap_copy(fs[k].lstm_out, fs[k].lin, (int64_t)fs[k].B * (fs[k].T / 2) * 2 * fs[k].d.H, s));
+    return head(fs, K, mode, s);
 }
 
 }  // namespace cnnlstm
@@ -1048,7 +1130,7 @@ static int forward_single(const char* who, const float* x, int B, int T, int inp
     Fwd f;
     TRY(check_item(d, x, B, T, weights, workspace, workspace_bytes, logits, who, -1, &f));
     f.res1_out = res1_out; f.res2_out = res2_out; f.lstm_out = lstm_out; f.pooled_out = pooled_out;
-    return run_forward(&f, 1, d, false, (hipStream_t)stream);
+    return run_forward(&f, 1, SINGLE, (hipStream_t)stream);
 }
 
 int rsaf_cnnlstm_forward(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
@@ -1097,7 +1179,42 @@ int rsaf_cnnlstm_forward_group(const rsaf_cnnlstm_forward_item* items_host, int 
                 fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
                 break;
             }
-    return run_forward(fs, K, d, true, (hipStream_t)stream);
+    return run_forward(fs, K, GROUPED, (hipStream_t)stream);
+}
+
+int rsaf_cnnlstm_forward_group_mixed(const rsaf_cnnlstm_forward_item* items_host, const rsaf_cnnlstm_arch* arch_host, int K,
+                                     int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    const char* who = __func__;
+    Fwd fs[RSAF_CNNLSTM_GROUP_MAX];
+    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (RSAF_CNNLSTM_GROUP_MAX)");
+    if (!items_host) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    if (!arch_host) return fail(RSAF_ERR_ARG, who, -1, "arch_host is NULL");
+    int64_t bytes[RSAF_CNNLSTM_GROUP_MAX];
+    for (int k = 0; k < K; ++k) {
+        const rsaf_cnnlstm_forward_item& it = items_host[k];
+        const Dims d{input_dim, arch_host[k].channels, arch_host[k].hidden, num_classes, lstm_layers, arch_host[k].act};
+        if (const char* problem = dims_problem(d)) return fail(RSAF_ERR_ARG, who, k, problem);
+        TRY(check_item(d, it.x, it.B, it.T, it.weights, it.workspace, it.workspace_bytes, it.logits, who, k, &fs[k], RSAF_ERR_ARG));
+        bytes[k] = rsaf_cnnlstm_workspace_bytes(it.B, it.T, d.D, d.C, d.H, d.L);
+    }
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const rsaf_cnnlstm_forward_item &a = items_host[j], &b = items_host[k];
+            const char* what = overlap(a.workspace, bytes[j], b.workspace, bytes[k]) ? "workspace"
+                               : overlap(a.logits, (int64_t)a.B * num_classes * 4, b.logits, (int64_t)b.B * num_classes * 4) ? "logits" : nullptr;
+            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
+            const rsaf_cnnlstm_arch &p = arch_host[j], &q = arch_host[k];
+            if (a.weights == b.weights && !(p.channels == q.channels && p.hidden == q.hidden && p.act == q.act))
+                return fail(RSAF_ERR_ARG, who, k, "shares `weights` with item " + std::to_string(j) + " but not its architecture");
+        }
+    // weight preparation once per distinct blob, as in rsaf_cnnlstm_forward_group
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j)
+            if (fs[k].f16 && fs[j].prep && fs[j].W == fs[k].W) {
+                fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
+                break;
+            }
+    return run_forward(fs, K, MIXED, (hipStream_t)stream);
 }
 
 int64_t rsaf_cnn_resblock_workspace_bytes(int B, int T, int out_channels) {

@@ -27,6 +27,20 @@ struct LstmRecGroup {
 };
 int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s);
 
+// The same for recurrences of different H (mixed groups: replicas of different architecture) in ONE launch of 512-thread
+// workgroups.  An H = 128 item runs as above, grid.y its direction.  The workgroup of an H = 64 item runs BOTH directions of
+// its tile, waves 0-3 direction 0 and waves 4-7 direction 1, each half on LDS buffers of its own: the halves loop over the
+// same T, so all eight waves meet at every barrier, and the grid.y == 1 workgroups of such an item leave whole.  No
+// workgroup ever has some of its waves returned while others wait at a barrier.
+struct LstmRecMixedItem {
+    LstmRecItem rec;
+    int H;
+};
+struct LstmRecMixedGroup {
+    LstmRecMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+int launch_lstm_rec_group_mixed(const LstmRecMixedItem* items, int K, hipStream_t s);
+
 // Attention pooling + classifier (the head of the inference forward) of up to RSAF_CNNLSTM_GROUP_MAX independent forwards of
 // one H and one num_classes in ONE launch; the descriptors travel by value in the kernel arguments.  seq [B][T][2H];
 // pooled_out may be NULL.
@@ -42,6 +56,14 @@ struct AttnPoolItem {
 };
 struct AttnPoolGroup {
     AttnPoolItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+// the heads of forwards of different H (one num_classes) in ONE launch
+struct AttnPoolMixedItem {
+    AttnPoolItem head;
+    int H;
+};
+struct AttnPoolMixedGroup {
+    AttnPoolMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
 };
 
 // Largest batch that runs on the 4-row recurrence kernels (environment RSAF_LSTM_SMALL_MAX, read once; default 1 024).

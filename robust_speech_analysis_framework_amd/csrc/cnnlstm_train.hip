@@ -132,13 +132,20 @@ static WLayout make_wlayout(const Dims& d, int B, int T) {
     return W;
 }
 
+// what is wrong with the dims, or NULL
+static const char* dims_problem(const Dims& d) {
+    if (!(d.D > 0 && d.D % 4 == 0)) return "input_dim must be a positive multiple of 4";
+    if (!(d.C > 0 && d.C % 4 == 0 && d.C <= 1024)) return "cnn_out_channels must be a multiple of 4 in [4, 1024]";
+    if (!(d.H == 64 || d.H == 128)) return "lstm_hidden_dim must be 64 or 128 (reference search space)";
+    if (!(d.NC >= 1 && d.NC <= 16)) return "num_classes must be in [1, 16]";
+    if (!(d.L >= 1 && d.L <= 4)) return "lstm_layers must be in [1, 4]";
+    if (!(d.act == ACT_GELU || d.act == ACT_SILU)) return "activation must be gelu (1) or silu (2)";
+    return nullptr;
+}
+
 static int check_dims(const Dims& d) {
-    RSAF_CHECK_ARG(d.D > 0 && d.D % 4 == 0, "input_dim must be a positive multiple of 4");
-    RSAF_CHECK_ARG(d.C > 0 && d.C % 4 == 0 && d.C <= 1024, "cnn_out_channels must be a multiple of 4 in [4, 1024]");
-    RSAF_CHECK_ARG(d.H == 64 || d.H == 128, "lstm_hidden_dim must be 64 or 128 (reference search space)");
-    RSAF_CHECK_ARG(d.NC >= 1 && d.NC <= 16, "num_classes must be in [1, 16]");
-    RSAF_CHECK_ARG(d.L >= 1 && d.L <= 4, "lstm_layers must be in [1, 4]");
-    RSAF_CHECK_ARG(d.act == ACT_GELU || d.act == ACT_SILU, "activation must be gelu (1) or silu (2)");
+    const char* problem = dims_problem(d);
+    RSAF_CHECK_ARG(!problem, problem);
     return RSAF_OK;
 }
 
@@ -661,15 +668,19 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_bwd_kernel(float* gates, con
 // instruction are 4 gates x 4 groups of 4 units, i.e. lane (g, u) contracts the H rows of gate g against unit u (its
 // W_hh column slice is register-resident, H registers) and a two-step butterfly over the gate lanes completes the sum
 // in a fixed order.  No partial products through LDS.
-// The body is shared by the one-recurrence kernel and the group kernel below (`dir`, `tile`: direction and 4-row tile).
-template <int H>
+// The body is shared by the one-recurrence kernel and the group kernels below (`dir`, `tile`: direction and 4-row tile).
+// HALVES = 2 (the mixed group kernel, H = 64): two such bodies side by side in one workgroup, threads [0, 16 H) and
+// [16 H, 32 H), each on its own half of the LDS buffer and with its own `dir`, as lstm_rec4_body (cnnlstm.hip) does it.
+template <int H, int HALVES = 1>
 __device__ __forceinline__ void lstm_bwd4_body(float* gates, const float* __restrict__ cst, const float* __restrict__ dh_out,
                                                const float* __restrict__ whh, int B, int T, int dir, int tile) {
     constexpr int NW = H / 16;
     constexpr int LDG = 4 * H + 20;                 // row stride = 20 banks (mod 32): the four rows of a fragment read and the
                                                     // 16-lane row groups of the cell owners' writes land on distinct banks
-    __shared__ __attribute__((aligned(16))) float dg[2][4][LDG];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    __shared__ __attribute__((aligned(16))) float dg_all[HALVES][2][4][LDG];
+    const int half = HALVES == 1 ? 0 : (int)threadIdx.x / (NW * 64);
+    auto& dg = dg_all[half];
+    const int tid = HALVES == 1 ? (int)threadIdx.x : (int)threadIdx.x - half * (NW * 64), lane = tid & 63, w = tid >> 6;
     const int q = lane >> 4, u = lane & 15;
     const int b0 = tile * 4;
     const int unit = 16 * w + u;
@@ -789,6 +800,31 @@ __global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_group_kernel(const Lstm
     const LstmBwdItem& it = g.item[blockIdx.z];
     if ((int)blockIdx.x * 4 >= it.B) return;
     lstm_bwd4_body<H>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, blockIdx.y, blockIdx.x);
+}
+
+// BPTT recurrences of different H in one launch, as lstm_rec4_group_mixed_kernel (cnnlstm.hip) runs the forward ones: 512
+// threads; an H = 128 item takes grid.y as its direction, the grid.y == 0 workgroup of an H = 64 item runs both directions
+// (waves 0-3 and 4-7, same T, own LDS halves) and its grid.y == 1 workgroup leaves whole.  Every exit is taken by the whole
+// workgroup before the first LDS access or barrier; a workgroup that enters a body runs all eight waves through every barrier.
+struct LstmBwdMixedItem {
+    LstmBwdItem rec;
+    int H;
+};
+struct LstmBwdMixedGroup {
+    LstmBwdMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(512) void lstm_bwd4_group_mixed_kernel(const LstmBwdMixedGroup g) {
+    const LstmBwdMixedItem& m = g.item[blockIdx.z];
+    const LstmBwdItem& it = m.rec;
+    if ((int)blockIdx.x * 4 >= it.B) return;
+    if (m.H == 128) {
+        lstm_bwd4_body<128>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, blockIdx.y, blockIdx.x);
+        return;
+    }
+    if (blockIdx.y != 0) return;
+    const int dir = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
+    lstm_bwd4_body<64, 2>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, dir, blockIdx.x);
 }
 
 // ---- host-side helpers ------------------------------------------------------------------------------------------
@@ -952,6 +988,22 @@ static int launch_lstm_bwd_group(const LstmBwdItem* items, int K, int H, hipStre
     return RSAF_OK;
 }
 
+// every B <= lstm_small_max(), every H 64 or 128 (the caller's checks)
+static int launch_lstm_bwd_group_mixed(const LstmBwdMixedItem* items, int K, hipStream_t s) {
+    LstmBwdMixedGroup g{};
+    int tiles = 0;
+    double flops = 0.0;
+    for (int k = 0; k < K; ++k) {
+        g.item[k] = items[k];
+        tiles = std::max(tiles, (items[k].rec.B + 3) / 4);
+        flops += 2.0 * items[k].rec.B * items[k].rec.T * 2.0 * 4 * items[k].H * items[k].H;
+    }
+    ProfScope prof("lstm_bwd_recurrent", s, flops, 0.0);
+    hipLaunchKernelGGL(lstm_bwd4_group_mixed_kernel, dim3(tiles, 2, K), dim3(512), 0, s, g);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
 // ---- one replica's step, cut at its recurrences into phases -----------------------------------------------------------
 // forward:  fwd_cnn (+ layer-0 input projection) | per layer: recurrence | fwd_after_rec (dropout + next input projection)
 //           | fwd_head;   backward:  bwd_head | per layer: BPTT recurrence | bwd_after_rec | bwd_blocks.
@@ -959,6 +1011,7 @@ static int launch_lstm_bwd_group(const LstmBwdItem* items, int K, int H, hipStre
 // phase for all replicas and one grouped recurrence launch in between.
 struct Replica {
     rsaf_cnnlstm_train_item it;
+    PLayout L;                      // the replica's own architecture is c.d (one for all replicas, except in a mixed group)
     SLayout S;
     WLayout WL;
     Ctx c;
@@ -973,18 +1026,21 @@ static int fail(int code, const char* who, int idx, const char* msg) {
 }
 
 // argument checks of one replica (idx < 0: the single entries, whose messages carry no item)
+// `short_code`: what a saved / scratch buffer below the replica's need returns
 static int check_item(const Dims& d, const rsaf_cnnlstm_train_item& it, bool backward, hipStream_t s, const char* who, int idx,
-                      Replica* r) {
+                      Replica* r, int short_code = RSAF_ERR_WORKSPACE) {
     if (!(it.B >= 1 && it.B <= 65535)) return fail(RSAF_ERR_ARG, who, idx, "batch must be in [1, 65535]");
     if (!(it.T >= 2)) return fail(RSAF_ERR_ARG, who, idx, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
     if (!((int64_t)it.B * it.T <= 0x3fffffffLL)) return fail(RSAF_ERR_ARG, who, idx, "B*T too large");
     const bool ptrs = it.x && it.params && it.saved && it.scratch && (backward ? it.dlogits && it.grads : it.logits != nullptr);
     if (!ptrs) return fail(RSAF_ERR_ARG, who, idx, "NULL pointer");
     r->it = it;
+    r->L = make_playout(d);
     r->S = make_slayout(d, it.B, it.T);
     r->WL = make_wlayout(d, it.B, it.T);
     if (it.saved_floats < r->S.total || it.scratch_floats < r->WL.total)
-        return fail(RSAF_ERR_WORKSPACE, who, idx, "saved/scratch buffer too small");
+        return fail(short_code, who, idx, short_code == RSAF_ERR_WORKSPACE ? "saved/scratch buffer too small"
+                                                                           : "saved/scratch buffer too small for this item's architecture");
     r->c = Ctx{d, s, it.scratch, r->WL};
     r->lin = nullptr; r->in = 0; r->dcur = r->dnext = nullptr;
     return RSAF_OK;
@@ -992,23 +1048,42 @@ static int check_item(const Dims& d, const rsaf_cnnlstm_train_item& it, bool bac
 
 static bool overlap(const float* a, int64_t na, const float* b, int64_t nb) { return a < b + nb && b < a + na; }
 
+// no two replicas overlapping in what the pass writes (reps[k].c.d: the replica's own dims)
+static int check_overlaps(const rsaf_cnnlstm_train_item* items, int K, bool backward, const char* who, const Replica* reps) {
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const rsaf_cnnlstm_train_item &a = items[j], &b = items[k];
+            const int NC = reps[k].c.d.NC;
+            const char* what = overlap(a.saved, reps[j].S.total, b.saved, reps[k].S.total) ? "saved"
+                               : overlap(a.scratch, reps[j].WL.total, b.scratch, reps[k].WL.total) ? "scratch"
+                               : !backward && overlap(a.logits, (int64_t)a.B * NC, b.logits, (int64_t)b.B * NC) ? "logits"
+                               : backward && overlap(a.grads, reps[j].L.total, b.grads, reps[k].L.total) ? "grads" : nullptr;
+            if (what) return fail(RSAF_ERR_ARG, who, k, (std::string("shares `") + what + "` with item " + std::to_string(j)).c_str());
+        }
+    return RSAF_OK;
+}
+
 static int check_group(const Dims& d, const rsaf_cnnlstm_train_item* items, int K, bool backward, hipStream_t s, const char* who,
                        Replica* reps) {
     TRY(check_dims(d));
     if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
     if (!items) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
     for (int k = 0; k < K; ++k) TRY(check_item(d, items[k], backward, s, who, k, &reps[k]));
-    const int64_t np = make_playout(d).total;
-    for (int k = 1; k < K; ++k)
-        for (int j = 0; j < k; ++j) {
-            const rsaf_cnnlstm_train_item &a = items[j], &b = items[k];
-            const char* what = overlap(a.saved, reps[j].S.total, b.saved, reps[k].S.total) ? "saved"
-                               : overlap(a.scratch, reps[j].WL.total, b.scratch, reps[k].WL.total) ? "scratch"
-                               : !backward && overlap(a.logits, (int64_t)a.B * d.NC, b.logits, (int64_t)b.B * d.NC) ? "logits"
-                               : backward && overlap(a.grads, np, b.grads, np) ? "grads" : nullptr;
-            if (what) return fail(RSAF_ERR_ARG, who, k, (std::string("shares `") + what + "` with item " + std::to_string(j)).c_str());
-        }
-    return RSAF_OK;
+    return check_overlaps(items, K, backward, who, reps);
+}
+
+// the same for a mixed group: the dims of item k are (input_dim, arch[k], num_classes, lstm_layers), and every message names its item
+static int check_group_mixed(const rsaf_cnnlstm_train_item* items, const rsaf_cnnlstm_arch* arch, int K, int input_dim, int num_classes,
+                             int lstm_layers, bool backward, hipStream_t s, const char* who, Replica* reps) {
+    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    if (!items) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    if (!arch) return fail(RSAF_ERR_ARG, who, -1, "arch_host is NULL");
+    for (int k = 0; k < K; ++k) {
+        const Dims d{input_dim, arch[k].channels, arch[k].hidden, num_classes, lstm_layers, arch[k].act};
+        if (const char* problem = dims_problem(d)) return fail(RSAF_ERR_ARG, who, k, problem);
+        TRY(check_item(d, items[k], backward, s, who, k, &reps[k], RSAF_ERR_ARG));
+    }
+    return check_overlaps(items, K, backward, who, reps);
 }
 
 static int fwd_inproj(Replica& r, const PLayout& L, int l) {
@@ -1279,42 +1354,59 @@ static int bwd_blocks(Replica& r, const PLayout& L) {
     return RSAF_OK;
 }
 
-// `grouped`: one launch carries the recurrences of all replicas (4-row kernels; needs every batch at or under the threshold),
-// otherwise one launch per replica through the one-recurrence launchers
-static int run_forward(Replica* reps, int K, const Dims& d, bool grouped) {
-    const PLayout L = make_playout(d);
+// GROUPED (one architecture): one launch carries the recurrences of all replicas (4-row kernels; needs every batch at or
+// under the threshold, else all run per replica).  MIXED (an architecture per replica): one launch carries those at or under
+// the threshold, and a replica above it has its recurrence launched on its own.  SINGLE: one launch per replica through the
+// one-recurrence launchers.  Every replica carries its own dims (c.d) and layouts.
+enum { SINGLE = 0, GROUPED = 1, MIXED = 2 };
+
+static int run_forward(Replica* reps, int K, int mode) {
     hipStream_t s = reps[0].c.s;
-    for (int k = 0; k < K; ++k) grouped = grouped && reps[k].it.B <= lstm_small_max();
-    for (int k = 0; k < K; ++k) TRY(fwd_cnn(reps[k], L));
-    for (int l = 0; l < d.L; ++l) {
-        LstmRecItem items[RSAF_CNNLSTM_GROUP_MAX];
-        for (int k = 0; k < K; ++k) items[k] = fwd_rec_item(reps[k], L, l);
-        if (grouped) TRY(launch_lstm_rec_group(items, K, d.H, s));
-        else
-            for (int k = 0; k < K; ++k)
-                TRY(launch_lstm_rec(items[k].xproj, items[k].whh, items[k].hout, items[k].gates_save, items[k].c_save, items[k].B,
-                                    items[k].T, d.H, s));
-        for (int k = 0; k < K; ++k) TRY(fwd_after_rec(reps[k], L, l));
+    const int layers = reps[0].c.d.L;
+    if (mode == GROUPED)
+        for (int k = 0; k < K; ++k)
+            if (reps[k].it.B > lstm_small_max()) mode = SINGLE;
+    for (int k = 0; k < K; ++k) TRY(fwd_cnn(reps[k], reps[k].L));
+    for (int l = 0; l < layers; ++l) {
+        LstmRecItem same[RSAF_CNNLSTM_GROUP_MAX];
+        LstmRecMixedItem mixed[RSAF_CNNLSTM_GROUP_MAX];
+        int n = 0;
+        for (int k = 0; k < K; ++k) {
+            const LstmRecItem it = fwd_rec_item(reps[k], reps[k].L, l);
+            if (mode == SINGLE || it.B > lstm_small_max())
+                TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, reps[k].c.d.H, s));
+            else { same[n] = it; mixed[n++] = LstmRecMixedItem{it, reps[k].c.d.H}; }
+        }
+        if (n && mode == MIXED) TRY(launch_lstm_rec_group_mixed(mixed, n, s));
+        else if (n) TRY(launch_lstm_rec_group(same, n, reps[0].c.d.H, s));
+        for (int k = 0; k < K; ++k) TRY(fwd_after_rec(reps[k], reps[k].L, l));
     }
-    for (int k = 0; k < K; ++k) TRY(fwd_head(reps[k], L));
+    for (int k = 0; k < K; ++k) TRY(fwd_head(reps[k], reps[k].L));
     return RSAF_OK;
 }
 
-static int run_backward(Replica* reps, int K, const Dims& d, bool grouped) {
-    const PLayout L = make_playout(d);
+static int run_backward(Replica* reps, int K, int mode) {
     hipStream_t s = reps[0].c.s;
-    for (int k = 0; k < K; ++k) grouped = grouped && reps[k].it.B <= lstm_small_max();
-    for (int k = 0; k < K; ++k) TRY(bwd_head(reps[k], L));
-    for (int l = d.L - 1; l >= 0; --l) {                 // LSTM layers, top down
-        LstmBwdItem items[RSAF_CNNLSTM_GROUP_MAX];
-        for (int k = 0; k < K; ++k) items[k] = bwd_rec_item(reps[k], L, l);
-        if (grouped) TRY(launch_lstm_bwd_group(items, K, d.H, s));
-        else
-            for (int k = 0; k < K; ++k)
-                TRY(launch_lstm_bwd(items[k].gates, items[k].cst, items[k].dh, items[k].whh, items[k].B, items[k].T, d.H, s));
-        for (int k = 0; k < K; ++k) TRY(bwd_after_rec(reps[k], L, l));
+    const int layers = reps[0].c.d.L;
+    if (mode == GROUPED)
+        for (int k = 0; k < K; ++k)
+            if (reps[k].it.B > lstm_small_max()) mode = SINGLE;
+    for (int k = 0; k < K; ++k) TRY(bwd_head(reps[k], reps[k].L));
+    for (int l = layers - 1; l >= 0; --l) {              // LSTM layers, top down
+        LstmBwdItem same[RSAF_CNNLSTM_GROUP_MAX];
+        LstmBwdMixedItem mixed[RSAF_CNNLSTM_GROUP_MAX];
+        int n = 0;
+        for (int k = 0; k < K; ++k) {
+            const LstmBwdItem it = bwd_rec_item(reps[k], reps[k].L, l);
+            if (mode == SINGLE || it.B > lstm_small_max())
+                TRY(launch_lstm_bwd(it.gates, it.cst, it.dh, it.whh, it.B, it.T, reps[k].c.d.H, s));
+            else { same[n] = it; mixed[n++] = LstmBwdMixedItem{it, reps[k].c.d.H}; }
+        }
+        if (n && mode == MIXED) TRY(launch_lstm_bwd_group_mixed(mixed, n, s));
+        else if (n) TRY(launch_lstm_bwd_group(same, n, reps[0].c.d.H, s));
+        for (int k = 0; k < K; ++k) TRY(bwd_after_rec(reps[k], reps[k].L, l));
     }
-    for (int k = 0; k < K; ++k) TRY(bwd_blocks(reps[k], L));
+    for (int k = 0; k < K; ++k) TRY(bwd_blocks(reps[k], reps[k].L));
     return RSAF_OK;
 }
 
@@ -1645,7 +1737,7 @@ int rsaf_cnnlstm_train_forward(const float* x, int B, int T, int input_dim, int 
                                      scratch, scratch_floats, logits, bn_stats_out, nullptr, nullptr};
     Replica r;
     TRY(check_item(d, it, false, (hipStream_t)stream, __func__, -1, &r));
-    return run_forward(&r, 1, d, false);
+    return run_forward(&r, 1, SINGLE);
 }
 
 int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
@@ -1659,7 +1751,7 @@ int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int
                                      scratch, scratch_floats, nullptr, nullptr, dlogits, grads};
     Replica r;
     TRY(check_item(d, it, true, (hipStream_t)stream, __func__, -1, &r));
-    return run_backward(&r, 1, d, false);
+    return run_backward(&r, 1, SINGLE);
 }
 
 int rsaf_cnnlstm_train_group_max(void) { return RSAF_CNNLSTM_GROUP_MAX; }
@@ -1669,7 +1761,7 @@ int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, 
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
     Replica reps[RSAF_CNNLSTM_GROUP_MAX];
     TRY(check_group(d, items_host, K, false, (hipStream_t)stream, __func__, reps));
-    return run_forward(reps, K, d, true);
+    return run_forward(reps, K, GROUPED);
 }
 
 int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels, int hidden,
@@ -1677,7 +1769,21 @@ int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host,
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
     Replica reps[RSAF_CNNLSTM_GROUP_MAX];
     TRY(check_group(d, items_host, K, true, (hipStream_t)stream, __func__, reps));
-    return run_backward(reps, K, d, true);
+    return run_backward(reps, K, GROUPED);
+}
+
+int rsaf_cnnlstm_train_forward_group_mixed(const rsaf_cnnlstm_train_item* items_host, const rsaf_cnnlstm_arch* arch_host, int K,
+                                           int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group_mixed(items_host, arch_host, K, input_dim, num_classes, lstm_layers, false, (hipStream_t)stream, __func__, reps));
+    return run_forward(reps, K, MIXED);
+}
+
+int rsaf_cnnlstm_train_backward_group_mixed(const rsaf_cnnlstm_train_item* items_host, const rsaf_cnnlstm_arch* arch_host, int K,
+                                            int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group_mixed(items_host, arch_host, K, input_dim, num_classes, lstm_layers, true, (hipStream_t)stream, __func__, reps));
+    return run_backward(reps, K, MIXED);
 }
 
 int rsaf_ce_loss_group(const rsaf_ce_loss_item* items_host, int K, int num_classes, rsaf_stream_t stream) {
