@@ -304,6 +304,69 @@ int rsaf_cnnlstm_adam_param_count(int input_dim, int channels, int hidden, int n
 int rsaf_cnnlstm_adam_group(const rsaf_cnnlstm_adam_item* items_host, int K, int input_dim, int channels, int hidden,
                             int num_classes, int lstm_layers, rsaf_stream_t stream);
 
+/* ---- Class weights and gradient-norm clipping in the fused step --------------------------------------------------
+ * nn.CrossEntropyLoss(weight = w) and clip_grad_norm_(model.parameters(), max_norm) between backward and step, on data
+ * the step already holds on the device.  New entries beside the ones above, which keep their code and their bits.
+ * Checks of all three, before any launch, rsaf_last_error() naming the item: 1 <= K <= RSAF_CNNLSTM_GROUP_MAX, the
+ * pointers that are not marked optional, and no two ranges that the items of the call write overlapping.
+ *
+ * rsaf_ce_loss_weighted_group: rsaf_ce_loss_group with per-item class weights (reduction "mean"):
+ *   loss_out[0]    = sum_b w[y_b] nll_b / sum_b w[y_b],  nll_b = logsumexp(logits[b]) - logits[b][y_b] (row maximum subtracted)
+ *   dlogits_out[b] = w[y_b] (softmax(logits[b]) - onehot(y_b)) / sum_b w[y_b]
+ * One launch, one workgroup per item, rows in double by one lane each, both sums by the fixed tree of
+ * rsaf_ce_loss_group.  A class of weight 0 is allowed; sum_b w[y_b] = 0 gives a NaN loss, as torch does.  A label
+ * outside [0, num_classes) makes the item's loss (and that row of dlogits_out) NaN and indexes neither the row nor w.
+ * An item with class_weight == NULL returns the bits of rsaf_ce_loss_group.  num_classes >= 2. */
+typedef struct {
+    const float* logits;           /* [B][num_classes] */
+    const int64_t* labels;         /* [B] */
+    int B;
+    float* loss_out;               /* one float */
+    float* dlogits_out;            /* [B][num_classes] or NULL */
+    const float* class_weight;     /* [num_classes] device floats, or NULL: the unweighted mean */
+} rsaf_ce_loss_weighted_item;
+int rsaf_ce_loss_weighted_group(const rsaf_ce_loss_weighted_item* items_host, int K, int num_classes, rsaf_stream_t stream);
+
+/* rsaf_cnnlstm_grad_norm_group: norm_out[0] = sqrt(sum_p ||g_p||^2) over the PARAMETERS of the numbering above whose
+ * bit in `skip` is clear, and scale_out[0] = min(1, max_norm / (norm + 1e-6)): what clip_grad_norm_ (2-norm) multiplies
+ * the gradients by.  The gradients come from `grads` / `table` exactly as in rsaf_cnnlstm_adam_item.  With a gradient
+ * blob, b_ih and b_hh of a direction both receive the gradient of the one segment of their sum, so that segment counts
+ * twice with both live, once with one of them skipped and not at all with both skipped; the padding floats between
+ * segments are never read, and the tap-major image of a conv kernel is a permutation.  The sum runs over the segments
+ * and workgroups of rsaf_cnnlstm_adam_group: each workgroup sums the squares of its <= 1024 floats in double through a
+ * fixed tree into one of the item's `partials`, a second launch adds the partials in a fixed order, and norm and scale
+ * are rounded to float once.  No floating-point atomics: the results do not depend on K, on the item's position or on
+ * scheduling.  max_norm > 0 and not NaN; +inf gives scale 1 with the norm still reported, and a zero gradient gives
+ * scale 1.  `partials`: 8-byte aligned, at least rsaf_cnnlstm_grad_norm_partials() doubles (-1: unsupported
+ * dimensions), scratch.  Two launches per call.
+ *
+ * rsaf_cnnlstm_adam_scaled_group: rsaf_cnnlstm_adam_group on g * grad_scale[0] (the product rounded once in double);
+ * grad_scale is read on the device, so nothing waits for the norm.  NULL means 1, and a scale of exactly 1.0f leaves
+ * the update of rsaf_cnnlstm_adam_group bit for bit.  One launch. */
+typedef struct {
+    const float* grads;            /* gradient blob, or NULL: gradients from the table's fourth row */
+    const void* const* table;      /* device array [4][P] of device pointers (read only when grads is NULL) */
+    uint64_t skip;
+    double max_norm;
+    double* partials;              /* scratch, partials_count doubles */
+    int64_t partials_count;
+    float* norm_out;               /* one float */
+    float* scale_out;              /* one float */
+} rsaf_cnnlstm_grad_norm_item;
+typedef struct {
+    const float* grads;
+    const void* const* table;
+    uint64_t skip;
+    double lr, beta1, beta2, eps;
+    int64_t step;
+    const float* grad_scale;       /* one device float, or NULL: 1 */
+} rsaf_cnnlstm_adam_scaled_item;
+int64_t rsaf_cnnlstm_grad_norm_partials(int input_dim, int channels, int hidden, int num_classes, int lstm_layers);
+int rsaf_cnnlstm_grad_norm_group(const rsaf_cnnlstm_grad_norm_item* items_host, int K, int input_dim, int channels,
+                                 int hidden, int num_classes, int lstm_layers, rsaf_stream_t stream);
+int rsaf_cnnlstm_adam_scaled_group(const rsaf_cnnlstm_adam_scaled_item* items_host, int K, int input_dim, int channels,
+                                   int hidden, int num_classes, int lstm_layers, rsaf_stream_t stream);
+
 /* rsaf_bn_running_stats_group: running = (1 - momentum) * running + momentum * batch value for the five BatchNorm
  * layers of a replica, from the [5][3][C] statistics of the step (bn_stats_out above); the batch variance is scaled
  * by `unbias[i]` = n / (n - 1), n the rows that layer saw.  A layer whose running_mean is NULL is left out (no

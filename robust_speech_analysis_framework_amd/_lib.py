@@ -51,6 +51,23 @@ class AdamItem(C.Structure):
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("step", _L)]
 
 
+class CeLossWeightedItem(C.Structure):
+    """``rsaf_ce_loss_weighted_item``: ``rsaf_ce_loss_item`` plus the class weights of the replica (NULL: unweighted)."""
+    _fields_ = CeLossItem._fields_ + [("class_weight", _P)]
+
+
+class GradNormItem(C.Structure):
+    """``rsaf_cnnlstm_grad_norm_item``: the gradients of one replica as ``rsaf_cnnlstm_adam_item`` names them, the clipping
+    norm, scratch for the partial sums and where the norm and the scale go."""
+    _fields_ = [("grads", _P), ("table", _P), ("skip", C.c_uint64), ("max_norm", C.c_double), ("partials", _P),
+                ("partials_count", _L), ("norm_out", _P), ("scale_out", _P)]
+
+
+class AdamScaledItem(C.Structure):
+    """``rsaf_cnnlstm_adam_scaled_item``: ``rsaf_cnnlstm_adam_item`` plus the device float its gradients are scaled by."""
+    _fields_ = AdamItem._fields_ + [("grad_scale", _P)]
+
+
 class PackItem(C.Structure):
     """``rsaf_cnnlstm_pack_item``: the pointer table of one replica's parameters and the blob to write."""
     _fields_ = [("table", _P), ("params", _P)]
@@ -112,6 +129,10 @@ SIGNATURES = {
     "rsaf_cnnlstm_pack_params_group": (_I, [C.POINTER(PackItem), _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_cnnlstm_adam_param_count": (_I, [_I, _I, _I, _I, _I]),
     "rsaf_cnnlstm_adam_group": (_I, [C.POINTER(AdamItem), _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_ce_loss_weighted_group": (_I, [C.POINTER(CeLossWeightedItem), _I, _I, _P]),
+    "rsaf_cnnlstm_grad_norm_partials": (_L, [_I, _I, _I, _I, _I]),
+    "rsaf_cnnlstm_grad_norm_group": (_I, [C.POINTER(GradNormItem), _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_adam_scaled_group": (_I, [C.POINTER(AdamScaledItem), _I, _I, _I, _I, _I, _I, _P]),
     "rsaf_bn_running_stats_group": (_I, [C.POINTER(BnRunningItem), _I, _I, _P]),
     "rsaf_dropout_masks_group": (_I, [C.POINTER(DropoutItem), _I, _P]),
     "rsaf_cnnlstm_forward_group": (_I, [C.POINTER(ForwardItem), _I, _I, _I, _I, _I, _I, _I, _P]),

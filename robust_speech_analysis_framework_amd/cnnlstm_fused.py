@@ -10,6 +10,13 @@ statistics from ``rsaf_bn_running_stats_group``: one launch each per group step.
 architecture, ``mixed=True``) the loss is still one launch; the packing, Adam and the running statistics, whose kernels carry
 the segment table of one architecture in their arguments, take one launch per distinct architecture of the group.
 
+Two options of the reference's users stay on this path.  Class weights (``nn.CrossEntropyLoss(weight=w)``, one ``w`` per
+replica) go through ``rsaf_ce_loss_weighted_group``, still one launch.  ``FusedAdam(max_grad_norm=...)`` is
+``clip_grad_norm_`` between backward and step: ``rsaf_cnnlstm_grad_norm_group`` reduces the gradient to its 2-norm over
+the parameters and to the scale ``min(1, max_norm / (norm + 1e-6))``, both left on the device, and
+``rsaf_cnnlstm_adam_scaled_group`` reads that scale; two more launches per group step and distinct architecture, no sync.
+Without either option the launches are the ones above.
+
 Built on ``cnnlstm_train`` (replica plan, launchers, argument checks); ``cnnlstm`` re-exports the names of this module, so
 ``CNNLSTM`` is imported where it is needed, not at the top.
 """
@@ -51,9 +58,18 @@ class FusedAdam(torch.optim.Optimizer):
 
     The kernels reach the parameters and moments through a device table of pointers, cached while the pointers are
     stable (``.to()`` or a loaded optimizer state rebuild it).  They write through raw pointers, so after every step the
-    versions of everything written are bumped: ``packed_weights()`` and every other version-keyed cache see the change."""
+    versions of everything written are bumped: ``packed_weights()`` and every other version-keyed cache see the change.
 
-    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False):
+    ``max_grad_norm``: ``torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)`` (2-norm) ahead of every
+    update, by ``step()``, ``step_blob()`` and the group step alike.  The norm runs over the parameters that the step
+    updates (not frozen, and with a gradient); Adam consumes ``g * min(1, max_grad_norm / (norm + 1e-6))``.  ``+inf``
+    clips nothing and still reports the norm.  ``step()`` does NOT modify ``.grad``: the scale is applied where Adam reads
+    the gradient.  ``last_grad_norm`` and ``last_grad_scale`` are device scalars of the last clipped step (``None`` before
+    it); reading them is the caller's sync, the step itself makes none.  The option is an attribute of the optimizer,
+    not an entry of ``param_groups``, which keep ``torch.optim.Adam``'s keys."""
+
+    def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False,
+                 max_grad_norm=None):
         from .cnnlstm import CNNLSTM
         if not isinstance(model, CNNLSTM):
             raise ValueError(f"FusedAdam: model must be a CNNLSTM, got {type(model).__name__}")
@@ -69,6 +85,7 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError(f"FusedAdam: invalid epsilon value: {eps}")
         if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError(f"FusedAdam: invalid betas: {betas}")
+        _check_max_grad_norm(max_grad_norm)
         params = list(model.parameters())
         if any(not p.is_cuda for p in params):
             raise ValueError("FusedAdam: the CNNLSTM must be on a HIP device (model.to('cuda') first): there is no CPU fallback")
@@ -83,6 +100,9 @@ class FusedAdam(torch.optim.Optimizer):
         self._state_gen = 0                 # bumped whenever a moment tensor is created or replaced
         self._table = self._table_key = None
         self._blob = None                   # blob buffer of the fused step, rewritten from the parameters every step
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = self.last_grad_scale = None
+        self._partials = None               # scratch of rsaf_cnnlstm_grad_norm_group
 
     # -- skip masks: bit i set = parameter i of _order sits this step out ---------------------------------------------------
     def _all_skipped(self, skip):
@@ -174,6 +194,14 @@ class FusedAdam(torch.optim.Optimizer):
             self._blob = torch.zeros(total, dtype=torch.float32, device=device)
         return self._blob
 
+    def _partials_buffer(self):
+        """Scratch for the partial sums of the gradient norm: one double per workgroup of the Adam launch."""
+        device = self._order[0].device
+        if self._partials is None or self._partials.device != device:
+            n = int(_lib.load().rsaf_cnnlstm_grad_norm_partials(*_dims5(self.model.dims)))
+            self._partials = torch.empty(n, dtype=torch.float64, device=device)
+        return self._partials
+
     def _written(self, tensors):
         """The kernels wrote ``tensors`` through raw pointers: bump their versions, as an in-place torch op would."""
         torch.autograd.graph.increment_version(tensors)
@@ -187,7 +215,8 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step_blob(self, grads):
         """One Adam step from a gradient blob in the layout of ``rsaf_cnnlstm_train_param_offsets`` (what
-        ``rsaf_cnnlstm_train_backward_group`` writes); parameters with ``requires_grad = False`` are left alone."""
+        ``rsaf_cnnlstm_train_backward_group`` writes); parameters with ``requires_grad = False`` are left alone (and
+        left out of the norm that ``max_grad_norm`` clips)."""
         total = train_param_offsets(self.model.dims)[1]
         if not grads.is_cuda or grads.dtype != torch.float32 or grads.shape != (total,) or not grads.is_contiguous():
             raise ValueError(f"expected a contiguous float32 HIP (cuda) gradient blob of {total} floats")
@@ -200,6 +229,9 @@ class FusedAdam(torch.optim.Optimizer):
 
     @torch.no_grad()
     def step(self, closure=None):
+        """``torch.optim.Adam.step`` on the ``.grad`` tensors.  With ``max_grad_norm`` the update is the one that follows
+        ``clip_grad_norm_(model.parameters(), max_grad_norm)``, but ``.grad`` itself is not modified: the norm is taken
+        over the gradients where they are, and the kernel scales what it reads."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -233,21 +265,63 @@ def _by_dims(records, dims_of):
     return list(parts.items())
 
 
+def _check_max_grad_norm(value):
+    if value is not None and not float(value) > 0:
+        raise ValueError(f"FusedAdam: max_grad_norm must be > 0 (None: no clipping; inf: the norm alone), got {value}")
+
+
+def _grad_norm_group(entries):
+    """Norm and clipping scale of the entries (as ``_adam_group`` takes them) whose optimizer has a ``max_grad_norm``:
+    ``rsaf_cnnlstm_grad_norm_group`` once per chunk and distinct architecture, over the parameters that the entry's skip
+    mask leaves in.  The results stay on the device as ``last_grad_norm`` / ``last_grad_scale`` of each optimizer."""
+    clipped = [e for e in entries if e[0].max_grad_norm is not None]
+    if not clipped:
+        return
+    out = torch.empty((len(clipped), 2), dtype=torch.float32, device=clipped[0][2].device)
+    for i, (opt, _, _, _) in enumerate(clipped):
+        _check_max_grad_norm(opt.max_grad_norm)
+        opt.last_grad_norm, opt.last_grad_scale = out[i, 0], out[i, 1]
+
+    def fill(it, e, _k):
+        opt, grads, table, skip = e
+        part = opt._partials_buffer()
+        it.grads = grads.data_ptr() if grads is not None else None
+        it.table, it.skip, it.max_norm = table.data_ptr(), skip, float(opt.max_grad_norm)
+        it.partials, it.partials_count = part.data_ptr(), part.numel()
+        it.norm_out, it.scale_out = opt.last_grad_norm.data_ptr(), opt.last_grad_scale.data_ptr()
+
+    for dims5, part in _by_dims(clipped, lambda e: e[0].model.dims):
+        _launch_chunked("rsaf_cnnlstm_grad_norm_group", _lib.GradNormItem, part, fill, *dims5)
+
+
 def _adam_group(entries):
     """``entries``: [(optimizer, gradient blob or None, pointer table, skip mask)] -> ``rsaf_cnnlstm_adam_group`` in
     chunks of ``train_group_max()``, one series of launches per distinct architecture among the entries; a replica whose
-    parameters stand at different step counts takes one launch per count."""
+    parameters stand at different step counts takes one launch per count.  Entries of optimizers with a ``max_grad_norm``
+    are clipped first (``_grad_norm_group``); an architecture with such an entry goes through
+    ``rsaf_cnnlstm_adam_scaled_group``, every launch of a replica reading the replica's one scale."""
+    _grad_norm_group(entries)
+
     def fill(it, rec, _k):
         (opt, grads, table, _), (t, mask) = rec
         it.grads = grads.data_ptr() if grads is not None else None
         it.table, it.skip, it.step = table.data_ptr(), mask, t
         it.lr, it.beta1, it.beta2, it.eps = opt._hyper()
 
+    def fill_scaled(it, rec, k):
+        fill(it, rec, k)
+        opt = rec[0][0]
+        it.grad_scale = opt.last_grad_scale.data_ptr() if opt.max_grad_norm is not None else None
+
     for dims5, part in _by_dims(entries, lambda e: e[0].model.dims):
         plans = [opt._launches(skip) for opt, _, _, skip in part]
+        scaled = any(opt.max_grad_norm is not None for opt, _, _, _ in part)
         for j in range(max(len(pl) for pl in plans)):
             live = [(e, pl[j]) for e, pl in zip(part, plans) if j < len(pl)]
-            _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *dims5)
+            if scaled:
+                _launch_chunked("rsaf_cnnlstm_adam_scaled_group", _lib.AdamScaledItem, live, fill_scaled, *dims5)
+            else:
+                _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *dims5)
     for opt, _, _, skip in entries:
         opt._stepped(skip)
 
@@ -265,14 +339,38 @@ def _pack_group(optimizers):
     return [blob for _, blob, _ in pairs]
 
 
-def ce_loss_group(logits, labels, with_grad=True):
+def _check_class_weights(weights, K, nc, device, who):
+    """``weights`` of a group call as a list of K contiguous float32 ``[nc]`` tensors on ``device`` or ``None`` entries; a
+    list of ``None`` alone comes back as ``None`` (the unweighted entry is called)."""
+    if weights is None:
+        return None
+    weights = list(weights)
+    if len(weights) != K:
+        raise ValueError(f"{who}: {K} items but {len(weights)} class-weight entries")
+    for k, w in enumerate(weights):
+        if w is None:
+            continue
+        if not torch.is_tensor(w) or w.dtype != torch.float32 or w.shape != (nc,) or w.device != device:
+            what = f"{w.dtype} {tuple(w.shape)} on {w.device}" if torch.is_tensor(w) else type(w).__name__
+            raise ValueError(f"{who}: item {k}: class weights must be a float32 tensor [{nc}] on {device}, got {what}")
+    if all(w is None for w in weights):
+        return None
+    return [w if w is None else w.contiguous() for w in weights]
+
+
+def ce_loss_group(logits, labels, with_grad=True, weights=None):
     """Mean-reduced cross-entropy of K (logits [B_k, nc], int64 labels [B_k]) pairs in one launch of
     ``rsaf_ce_loss_group`` (``nn.CrossEntropyLoss()`` with its defaults) -> (losses [K] on the device, list of
-    d loss_k / d logits_k, or None without ``with_grad``).  Lists longer than ``train_group_max()`` are chunked."""
+    d loss_k / d logits_k, or None without ``with_grad``).  Lists longer than ``train_group_max()`` are chunked.
+
+    ``weights``: per item a float32 ``[nc]`` device tensor of class weights (``nn.CrossEntropyLoss(weight=w)``: the mean is
+    the one weighted by ``w[label]``) or ``None``; the call is then one launch of ``rsaf_ce_loss_weighted_group``, in which
+    an item without weights gets the bits of the unweighted entry.  With no weights at all that entry itself is called."""
     logits, labels = list(logits), list(labels)
     if len(logits) != len(labels) or not logits:
         raise ValueError(f"{len(logits)} logits but {len(labels)} label tensors")
     nc, device = logits[0].shape[1], logits[0].device
+    weights = _check_class_weights(weights, len(logits), nc, device, "ce_loss_group")
     labs = []
     for k, (o, lab) in enumerate(zip(logits, labels)):
         if not o.is_cuda:
@@ -290,7 +388,14 @@ def ce_loss_group(logits, labels, with_grad=True):
         it.loss_out = losses.data_ptr() + 4 * k
         it.dlogits_out = dl[k].data_ptr() if with_grad else None
 
-    _launch_chunked("rsaf_ce_loss_group", _lib.CeLossItem, list(zip(logits, labs)), fill, nc)
+    def fill_weighted(it, rec, k):
+        fill(it, rec, k)
+        it.class_weight = rec[2].data_ptr() if rec[2] is not None else None
+
+    if weights is None:
+        _launch_chunked("rsaf_ce_loss_group", _lib.CeLossItem, list(zip(logits, labs)), fill, nc)
+    else:
+        _launch_chunked("rsaf_ce_loss_weighted_group", _lib.CeLossWeightedItem, list(zip(logits, labs, weights)), fill_weighted, nc)
     return losses, dl
 
 
@@ -329,7 +434,7 @@ def _bn_running_group(reps):
     return written
 
 
-def _train_step_chunk(models, optimizers, xs, labels, masks, mixed=False):
+def _train_step_chunk(models, optimizers, xs, labels, masks, weights, mixed=False):
     """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k]).  The statistics and gradient
     blobs of the replicas are slices of one allocation each, of every replica's own size (in a mixed group the channel
     count and the blob length differ; every size is a multiple of 4 floats, so the slices stay 16-byte aligned)."""
@@ -343,7 +448,7 @@ def _train_step_chunk(models, optimizers, xs, labels, masks, mixed=False):
     blobs = _pack_group(optimizers)
     reps = [_Replica(model, x, mk, blobs[k], logits[k], stats[k]) for k, (model, x, mk) in enumerate(zip(models, xs, masks))]
     _launch_group(reps, False, mixed)
-    losses, dl = ce_loss_group(logits, labels)
+    losses, dl = ce_loss_group(logits, labels, weights=weights)
     sizes = [b.numel() for b in blobs]
     grads = torch.split(torch.zeros(sum(sizes), dtype=torch.float32, device=device), sizes)     # one zero fill for the group
     for k, r in enumerate(reps):
@@ -364,7 +469,7 @@ def _train_step_chunk(models, optimizers, xs, labels, masks, mixed=False):
     return losses, logits
 
 
-def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=False):
+def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=False, class_weights=None):
     """One whole training step of K independent ``CNNLSTM`` replicas, ``optimizers[k]`` the ``FusedAdam`` of ``models[k]``:
     group forward in training mode, ``nn.CrossEntropyLoss()`` (defaults) of ``labels[k]``, group backward, Adam and the
     BatchNorm running statistics -> ``(losses [K] on the device, [logits_k])``.  No autograd graph is built and ``.grad``
@@ -378,7 +483,12 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=F
 
     ``mixed=True``: replicas of different architecture, as in ``cnnlstm_train_group``.  Forward and backward of a chunk are
     one mixed call each and the loss stays one launch; the packing, Adam and the running statistics run once per distinct
-    architecture of the chunk.  Results equal those of one group step per architecture, bit for bit."""
+    architecture of the chunk.  Results equal those of one group step per architecture, bit for bit.
+
+    ``class_weights``: one entry per replica, a float32 ``[num_classes]`` device tensor (the ``weight`` of
+    ``nn.CrossEntropyLoss``) or ``None``.  An optimizer with ``max_grad_norm`` clips its replica's gradient by its norm ahead
+    of Adam (``FusedAdam``); norm and scale stay on the device (``last_grad_norm``, ``last_grad_scale``).  Both are per
+    replica: the results of a replica do not depend on what the others of the group use."""
     optimizers, labels = list(optimizers), list(labels)
     models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group", mixed)
     if not (len(optimizers) == len(labels) == len(models)):
@@ -389,20 +499,52 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=F
     for k, (x, lab) in enumerate(zip(xs, labels)):
         if lab.dim() != 1 or lab.shape[0] != x.shape[0] or lab.dtype.is_floating_point:
             raise ValueError(f"replica {k}: expected {x.shape[0]} integer class labels, got {lab.dtype} {tuple(lab.shape)}")
+    weights = _check_class_weights(class_weights, len(models), models[0].dims["num_classes"], xs[0].device, "cnnlstm_train_step_group")
+    if weights is None:
+        weights = [None] * len(models)
     losses, logits = [], []
     with torch.no_grad():
         # every chunk is a whole step of its replicas, so the chunks are cut here and not call by call
-        for _, chunk in _chunks(list(zip(models, optimizers, xs, labels, mks))):
+        for _, chunk in _chunks(list(zip(models, optimizers, xs, labels, mks, weights))):
             ls, lg = _train_step_chunk(*zip(*chunk), mixed=mixed)
             losses.append(ls)
             logits += lg
     return (losses[0] if len(losses) == 1 else torch.cat(losses)), logits
 
 
-def _fused_step_applies(optimizers, models, loss_fn):
-    """The lockstep loops take the fused step when the loss is ``nn.CrossEntropyLoss`` with its default options and
-    every optimizer is the ``FusedAdam`` of its model."""
-    if type(loss_fn) is not nn.CrossEntropyLoss or loss_fn.weight is not None or loss_fn.reduction != "mean" \
+def _loss_list(loss_fn, K):
+    """``loss_fn`` of the lockstep loops as K losses: one loss for all replicas, or a sequence of K (per-fold weights)."""
+    if isinstance(loss_fn, (list, tuple)):
+        if len(loss_fn) != K:
+            raise ValueError(f"{K} replicas but {len(loss_fn)} losses")
+        return list(loss_fn)
+    return [loss_fn] * K
+
+
+def _fused_loss(loss_fn, model):
+    """``nn.CrossEntropyLoss`` with its default options, or with those and a ``weight`` the kernel can read as it is: a
+    float32 ``[num_classes]`` tensor on the model's device."""
+    if type(loss_fn) is not nn.CrossEntropyLoss or loss_fn.reduction != "mean" \
             or loss_fn.label_smoothing != 0 or loss_fn.ignore_index != -100:
+        return False
+    w = loss_fn.weight
+    if w is None:
+        return True
+    return (torch.is_tensor(w) and w.dtype == torch.float32 and w.shape == (model.dims["num_classes"],)
+            and w.device == next(model.parameters()).device)
+
+
+def _class_weights(loss_fns):
+    """The ``weight`` tensors of the losses for ``class_weights=``, or ``None`` when no loss has one."""
+    weights = [fn.weight for fn in loss_fns]
+    return None if all(w is None for w in weights) else weights
+
+
+def _fused_step_applies(optimizers, models, loss_fn):
+    """The lockstep loops take the fused step when the loss (every loss of a sequence of K) is ``nn.CrossEntropyLoss``
+    with its default options, or with those and a float32 ``[num_classes]`` ``weight`` on the model's device, and every
+    optimizer is the ``FusedAdam`` of its model."""
+    models = list(models)
+    if not all(_fused_loss(fn, m) for fn, m in zip(_loss_list(loss_fn, len(models)), models)):
         return False
     return all(isinstance(o, FusedAdam) and o.model is m for o, m in zip(optimizers, models))

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .cnnlstm_fused import _fused_step_applies, ce_loss_group, cnnlstm_train_step_group
+from .cnnlstm_fused import _class_weights, _fused_step_applies, _loss_list, ce_loss_group, cnnlstm_train_step_group
 from .cnnlstm_train import cnnlstm_train_group, train_group_max
 
 
@@ -63,7 +63,10 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     Parameters, buffers and losses equal those of K sequential trainings bit for bit as long as the replicas see the
     same batches and dropout masks.  When ``loss_fn`` is ``nn.CrossEntropyLoss()`` with its default options and every
     optimizer of the call is the ``FusedAdam`` of its model, a step is one ``cnnlstm_train_step_group`` call (loss, Adam and running
-    statistics in HIP, no autograd graph); anything else runs the loop above as written.  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
+    statistics in HIP, no autograd graph); anything else runs the loop above as written.  ``loss_fn`` may be a sequence of K
+    losses, one per replica (class weights of every fold's own balance); a ``weight`` that is a float32 ``[num_classes]``
+    tensor on the model's device keeps the fused step, and the decision is taken over all K losses.  ``FusedAdam(max_grad_norm=...)``
+    clips the gradient by its norm on both paths (in the fused step, and in ``FusedAdam.step()`` on the autograd loop).  Note that ``DataLoader(shuffle=True)`` without a ``generator`` of its own draws
     its permutations from torch's global RNG: in lock step the K loaders draw in a different order than K sequential
     trainings would, so give every loader its own ``torch.Generator`` where the batch order matters.  Dropout masks
     of a model that carries a ``DropoutStream`` (``model.dropout_stream``) are a function of the stream's seed and of the
@@ -77,7 +80,9 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
     histories = [[] for _ in models]
-    fused = _fused_step_applies(optimizers, models, loss_fn)      # decided once for the call: no replica changes path mid-epoch
+    loss_fns = _loss_list(loss_fn, len(models))
+    fused = _fused_step_applies(optimizers, models, loss_fns)     # decided once for the call: no replica changes path mid-epoch
+    weights = _class_weights(loss_fns) if fused else None
     for _ in range(epochs):
         for m in models:
             m.train()
@@ -91,12 +96,13 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
             xs = [batches[k][0].to(device) for k in live]
             labs = [batches[k][1].to(device) for k in live]
             if fused:
-                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs, mixed=mixed)[0]
+                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs, mixed=mixed,
+                                                       class_weights=weights and [weights[k] for k in live])[0]
             else:
                 for k in live:
                     optimizers[k].zero_grad()
                 outs = cnnlstm_train_group([models[k] for k in live], xs, mixed=mixed)
-                losses = [loss_fn(o, lab) for o, lab in zip(outs, labs)]
+                losses = [loss_fns[k](o, lab) for k, o, lab in zip(live, outs, labs)]
                 torch.stack(losses).sum().backward()
                 for k in live:
                     optimizers[k].step()
@@ -171,7 +177,8 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
     ``train_replicas_lockstep`` over the replicas still running, then the validation pass of all of them in group calls
     (``val_loss`` accumulated batch by batch in loader order; the losses of a pass come to the host in one copy), then per
     replica ``scheduler.step(avg_val_loss)`` (``schedulers[k]`` may be ``None``), best-weights checkpointing and early
-    stopping as the reference does them.  A replica that stopped early sits out of the later epochs.  Returns
+    stopping as the reference does them.  ``loss_fn``: one loss or a sequence of K, as in ``train_replicas_lockstep``; the
+    validation losses of a replica are those of its own loss (its class weights).  A replica that stopped early sits out of the later epochs.  Returns
     ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded.  ``mixed=True``: the
     replicas may differ in architecture, in the training pass and in the validation pass alike."""
     models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
@@ -181,6 +188,7 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         raise ValueError(f"{K} models, {len(optimizers)} optimizers, {len(schedulers)} schedulers, {len(train_loaders)} training "
                          f"loaders and {len(val_loaders)} validation loaders")
     train_hist, val_hist = [[] for _ in models], [[] for _ in models]
+    loss_fns = _loss_list(loss_fn, K)
     best_val_loss = [float("inf")] * K
     epochs_no_improve = [0] * K
     best_model_weights = [None] * K
@@ -189,13 +197,14 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         if not running:
             break
         hist = train_replicas_lockstep([models[k] for k in running], [optimizers[k] for k in running],
-                                       [train_loaders[k] for k in running], loss_fn, 1, device, mixed=mixed)
+                                       [train_loaders[k] for k in running], [loss_fns[k] for k in running], 1, device, mixed=mixed)
         for k, h in zip(running, hist):
             train_hist[k].append(h[0])
         for k in running:
             models[k].eval()
         tags, outs, labs = [], [], []
-        fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], loss_fn)
+        fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], [loss_fns[k] for k in running])
+        weights = _class_weights(loss_fns) if fused else None
         with torch.no_grad():
             pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
             for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
@@ -205,9 +214,9 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
             if not outs:
                 losses = []
             elif fused and all(o.shape[0] > 0 for o in outs):           # the losses of the pass in group launches, no gradient
-                losses = ce_loss_group(outs, labs, with_grad=False)[0].tolist()
+                losses = ce_loss_group(outs, labs, with_grad=False, weights=weights and [weights[k] for k in tags])[0].tolist()
             else:
-                losses = torch.stack([loss_fn(o, lab) for o, lab in zip(outs, labs)]).tolist()
+                losses = torch.stack([loss_fns[k](o, lab) for k, o, lab in zip(tags, outs, labs)]).tolist()
         val_loss, count = {k: 0 for k in running}, {k: 0 for k in running}
         for k, v in zip(tags, losses):
             val_loss[k] += v

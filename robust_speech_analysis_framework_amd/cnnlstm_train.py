@@ -186,10 +186,16 @@ def _pack_train_blob(model, device, segments=None):
 
 def _unpack_grads(segs, params, grads):
     by_param = {id(prm): (off, n, unpack) for off, n, _, outs in segs for prm, unpack in outs}
-    out = []
+    out, taken = [], set()
     for prm in params:
         off, n, unpack = by_param[id(prm)]
-        out.append(unpack(grads[off:off + n]).reshape(prm.shape).contiguous())
+        g = unpack(grads[off:off + n]).reshape(prm.shape).contiguous()
+        # b_ih and b_hh of a direction receive the same run of the blob; each gets memory of its own, since whatever edits
+        # `.grad` in place (clip_grad_norm_ multiplies it) would otherwise reach the shared floats once per parameter
+        if g.data_ptr() in taken:
+            g = g.clone()
+        taken.add(g.data_ptr())
+        out.append(g)
     return out
 
 

@@ -1427,9 +1427,7 @@ struct CeGroup {
     CeItem item[RSAF_CNNLSTM_GROUP_MAX];
 };
 
-__global__ __launch_bounds__(256) void ce_loss_group_kernel(const CeGroup g, int nc) {
-    const CeItem& it = g.item[blockIdx.x];
-    __shared__ double part[256];
+__device__ __forceinline__ void ce_item_mean(const CeItem& it, int nc, double* part) {
     double acc = 0.0;
     for (int b = threadIdx.x; b < it.B; b += 256) {
         const float* row = it.logits + (int64_t)b * nc;
@@ -1456,6 +1454,74 @@ __global__ __launch_bounds__(256) void ce_loss_group_kernel(const CeGroup g, int
         __syncthreads();
     }
     if (threadIdx.x == 0) it.loss[0] = (float)(part[0] / it.B);
+}
+
+__global__ __launch_bounds__(256) void ce_loss_group_kernel(const CeGroup g, int nc) {
+    __shared__ double part[256];
+    ce_item_mean(g.item[blockIdx.x], nc, part);
+}
+
+// nn.CrossEntropyLoss(weight = w): loss = sum_b w[y_b] nll_b / sum_b w[y_b], dlogits_b = w[y_b] (softmax - onehot) / sum_b w[y_b].
+// Both sums go through the tree of ce_item_mean; the gradient needs the second one, so the rows are walked twice (a batch
+// of rows of at most 16 classes: the exponentials are cheaper than a round trip through memory).  An item without weights
+// runs ce_item_mean itself: the bits of rsaf_ce_loss_group.
+struct CeWeightedItem {
+    CeItem ce;
+    const float* w;
+};
+struct CeWeightedGroup {
+    CeWeightedItem item[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void ce_loss_weighted_group_kernel(const CeWeightedGroup g, int nc) {
+    const CeWeightedItem& wi = g.item[blockIdx.x];
+    const CeItem& it = wi.ce;
+    __shared__ double part[256], partw[256];
+    if (!wi.w) {
+        ce_item_mean(it, nc, part);
+        return;
+    }
+    double acc = 0.0, accw = 0.0;
+    for (int b = threadIdx.x; b < it.B; b += 256) {
+        const float* row = it.logits + (int64_t)b * nc;
+        float mx = row[0];
+        for (int c = 1; c < nc; ++c) mx = fmaxf(mx, row[c]);
+        double s = 0.0;
+        for (int c = 0; c < nc; ++c) s += exp((double)row[c] - (double)mx);
+        const long long lab = it.labels[b];
+        const bool ok = lab >= 0 && lab < nc;
+        const double lse = (double)mx + log(s);
+        const double wb = ok ? (double)wi.w[lab] : __builtin_nan("");
+        acc += wb * (lse - (double)row[ok ? lab : 0]);
+        accw += wb;
+    }
+    part[threadIdx.x] = acc;
+    partw[threadIdx.x] = accw;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+            part[threadIdx.x] += part[threadIdx.x + w];
+            partw[threadIdx.x] += partw[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    const double wsum = partw[0];
+    if (threadIdx.x == 0) it.loss[0] = (float)(part[0] / wsum);
+    if (!it.dlogits) return;
+    for (int b = threadIdx.x; b < it.B; b += 256) {
+        const float* row = it.logits + (int64_t)b * nc;
+        float mx = row[0];
+        for (int c = 1; c < nc; ++c) mx = fmaxf(mx, row[c]);
+        double s = 0.0;
+        for (int c = 0; c < nc; ++c) s += exp((double)row[c] - (double)mx);
+        const long long lab = it.labels[b];
+        const bool ok = lab >= 0 && lab < nc;
+        const double wb = ok ? (double)wi.w[lab] : __builtin_nan("");
+        for (int c = 0; c < nc; ++c) {
+            const double p = exp((double)row[c] - (double)mx) / s;
+            it.dlogits[(int64_t)b * nc + c] = (float)(wb * (c == lab ? p - 1.0 : p) / wsum);
+        }
+    }
 }
 
 // Adam and the packing of the parameter blob.  A segment is one parameter tensor (ADAM_PLAIN, ADAM_CONV) or the
@@ -1486,8 +1552,11 @@ struct AdamGroup {
 };
 static_assert(sizeof(AdamGroup) <= 3584, "the descriptors must fit the kernel argument segment");
 
-__device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, const AdamRep& r) {
-    const double gd = g;
+// SCALED: the gradient is g * scale (clipping by the norm, grad_norm_* below), the product rounded once in double; a
+// scale of exactly 1 leaves g, so the update is the unscaled one bit for bit.
+template <bool SCALED>
+__device__ __forceinline__ float adam_one(float p, float g, float& m, float& v, const AdamRep& r, double scale) {
+    const double gd = SCALED ? __dmul_rn((double)g, scale) : (double)g;
     const double md = r.b1 * (double)m + (1.0 - r.b1) * gd;
     const double vd = r.b2 * (double)v + (1.0 - r.b2) * gd * gd;
     m = (float)md;
@@ -1521,7 +1590,8 @@ __device__ __forceinline__ int conv_blob_index(int q, int cin, int taps) {
     return (co * taps + tap) * cin + ci;
 }
 
-__global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) {
+template <bool SCALED>
+__device__ __forceinline__ void adam_group_body(const AdamGroup& G, double scale) {
     const AdamRep& r = G.rep[blockIdx.y];
     int s = 0;
     while (s + 1 < G.nseg && (int)blockIdx.x >= G.seg[s + 1].block0) ++s;
@@ -1537,12 +1607,12 @@ __global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) {
         for (int q = q0; q < min(q0 + 4, sg.n); ++q) {
             if (!skip_a) {
                 float m = a.m[q], v = a.v[q];
-                a.p[q] = adam_one(a.p[q], gblob ? gblob[q] : a.g[q], m, v, r);
+                a.p[q] = adam_one<SCALED>(a.p[q], gblob ? gblob[q] : a.g[q], m, v, r, scale);
                 a.m[q] = m; a.v[q] = v;
             }
             if (!skip_b) {
                 float m = b.m[q], v = b.v[q];
-                b.p[q] = adam_one(b.p[q], gblob ? gblob[q] : b.g[q], m, v, r);
+                b.p[q] = adam_one<SCALED>(b.p[q], gblob ? gblob[q] : b.g[q], m, v, r, scale);
                 b.m[q] = m; b.v[q] = v;
             }
         }
@@ -1565,7 +1635,7 @@ __global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {           // constant indices after unrolling: the vectors stay in registers
             float mj = m[j], vj = v[j];
-            p[j] = adam_one(p[j], g[j], mj, vj, r);
+            p[j] = adam_one<SCALED>(p[j], g[j], mj, vj, r, scale);
             m[j] = mj; v[j] = vj;
         }
         *reinterpret_cast<f32x4*>(t.p + q0) = p;
@@ -1576,8 +1646,96 @@ __global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) {
     for (int q = q0; q < min(q0 + 4, sg.n); ++q) {            // tail of a segment, or tensors off the 16-byte grid
         const int bi = conv ? conv_blob_index(q, sg.cin, sg.taps) : q;
         float m = t.m[q], v = t.v[q];
-        t.p[q] = adam_one(t.p[q], t.g ? t.g[q] : gblob[bi], m, v, r);
+        t.p[q] = adam_one<SCALED>(t.p[q], t.g ? t.g[q] : gblob[bi], m, v, r, scale);
         t.m[q] = m; t.v[q] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void adam_group_kernel(const AdamGroup G) { adam_group_body<false>(G, 1.0); }
+
+// one device float per replica (NULL: 1), read by every thread of the replica's workgroups
+struct AdamScales {
+    const float* scale[RSAF_CNNLSTM_GROUP_MAX];
+};
+
+__global__ __launch_bounds__(256) void adam_scaled_group_kernel(const AdamGroup G, const AdamScales S) {
+    const float* sp = S.scale[blockIdx.y];
+    adam_group_body<true>(G, sp ? (double)sp[0] : 1.0);
+}
+
+// The 2-norm of a replica's gradient as clip_grad_norm_ takes it: over the PARAMETERS that the step updates.  The walk
+// is adam_group_kernel's (same segments, same workgroups, the parameter's index space), so a conv kernel is read through
+// the same permutation, the padding between segments is never read, and a bias segment of the blob counts once per live
+// parameter of its pair.  Every workgroup sums the squares of its <= 1024 floats in double (a float squared is exact
+// there) through a fixed tree and writes ONE partial; grad_norm_finish_kernel sums a replica's partials in a fixed order.
+// No atomics: the result depends on the gradients alone, not on K, on the replica's place in the group or on scheduling.
+struct NormRep {
+    const float* grads;                         // gradient blob or NULL (gradients by the table's fourth row)
+    const unsigned long long* table;            // [4][P] device pointers when grads is NULL (only the fourth row is read)
+    unsigned long long skip;
+    double max_norm;
+    double* partials;                           // [blocks]
+    float *norm_out, *scale_out;
+};
+struct NormGroup {
+    AdamSeg seg[ADAM_MAX_SEGS];
+    NormRep rep[RSAF_CNNLSTM_GROUP_MAX];
+    int nseg, P, blocks;
+};
+static_assert(sizeof(NormGroup) <= 3584, "the descriptors must fit the kernel argument segment");
+
+__device__ __forceinline__ double block_sum_256(double x, double* part) {
+    part[threadIdx.x] = x;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+__global__ __launch_bounds__(256) void grad_norm_partial_kernel(const NormGroup G) {
+    const NormRep& r = G.rep[blockIdx.y];
+    __shared__ double part[256];
+    int s = 0;
+    while (s + 1 < G.nseg && (int)blockIdx.x >= G.seg[s + 1].block0) ++s;
+    const AdamSeg sg = G.seg[s];
+    const bool bias = sg.kind == ADAM_BIAS;
+    const bool live_a = !((r.skip >> sg.pa) & 1), live_b = bias && !((r.skip >> sg.pb) & 1);
+    const int q0 = (((int)blockIdx.x - sg.block0) * 256 + (int)threadIdx.x) * 4;
+    double acc = 0.0;
+    if (live_a || live_b) {
+        const float* gblob = r.grads ? r.grads + sg.blob_off : nullptr;
+        const float* ga = gblob || !live_a ? nullptr : reinterpret_cast<const float*>(r.table[3 * G.P + sg.pa]);
+        const float* gb = gblob || !live_b ? nullptr : reinterpret_cast<const float*>(r.table[3 * G.P + sg.pb]);
+        const bool conv = sg.kind == ADAM_CONV;
+        for (int q = q0; q < min(q0 + 4, sg.n); ++q) {
+            const int bi = conv ? conv_blob_index(q, sg.cin, sg.taps) : q;
+            if (live_a) {
+                const double g = gblob ? gblob[bi] : ga[q];
+                acc += g * g;
+            }
+            if (live_b) {
+                const double g = gblob ? gblob[bi] : gb[q];
+                acc += g * g;
+            }
+        }
+    }
+    const double total = block_sum_256(acc, part);
+    if (threadIdx.x == 0) r.partials[blockIdx.x] = total;
+}
+
+// grid K: norm = sqrt(sum of the partials), scale = min(1, max_norm / (norm + 1e-6)), both rounded to float once
+__global__ __launch_bounds__(256) void grad_norm_finish_kernel(const NormGroup G) {
+    const NormRep& r = G.rep[blockIdx.x];
+    __shared__ double part[256];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < G.blocks; i += 256) acc += r.partials[i];
+    const double total = block_sum_256(acc, part);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(total), ratio = r.max_norm / (norm + 1e-6);
+        r.norm_out[0] = (float)norm;
+        r.scale_out[0] = (float)(ratio < 1.0 || ratio != ratio ? ratio : 1.0);      // a NaN norm gives a NaN scale, as torch's clamp does
     }
 }
 
@@ -1660,6 +1818,23 @@ static int make_adam_segs(const Dims& d, AdamSeg* segs, int* nseg, int64_t* bloc
     return P;
 }
 
+// the byte ranges that the items of one call write; add() refuses a range that overlaps an earlier one, naming both
+struct WriteRanges {
+    struct Range { const char* p; int64_t bytes; int item; const char* what; };
+    Range r[RSAF_CNNLSTM_GROUP_MAX * 3];
+    int n = 0;
+    int add(const void* p, int64_t bytes, int item, const char* what, const char* who) {
+        if (!p) return RSAF_OK;
+        const char* c = static_cast<const char*>(p);
+        for (int i = 0; i < n; ++i)
+            if (c < r[i].p + r[i].bytes && r[i].p < c + bytes)
+                return fail(RSAF_ERR_ARG, who, item, (std::string("`") + what + "` overlaps `" + r[i].what + "` of item " +
+                                                      std::to_string(r[i].item)).c_str());
+        r[n++] = Range{c, bytes, item, what};
+        return RSAF_OK;
+    }
+};
+
 struct BnRunItem {
     const float* stats;
     float* mean[5];
@@ -1679,6 +1854,37 @@ __global__ __launch_bounds__(256) void bn_running_group_kernel(const BnRunGroup 
     const float keep = (float)(1.0 - it.momentum[i]), am = (float)it.momentum[i], av = (float)(it.momentum[i] * it.unbias[i]);
     it.mean[i][c] = __fmaf_rn(am, it.stats[(i * 3 + 0) * C + c], __fmul_rn(it.mean[i][c], keep));
     it.var[i][c] = __fmaf_rn(av, it.stats[(i * 3 + 1) * C + c], __fmul_rn(it.var[i][c], keep));
+}
+
+// the checks of the Adam entries and the descriptors of their launch; ItemT: rsaf_cnnlstm_adam_item or its scaled twin
+template <typename ItemT>
+static int adam_prepare(const Dims& d, const ItemT* items_host, int K, const char* who, AdamGroup* G, int64_t* blocks, int64_t* total) {
+    TRY(check_dims(d));
+    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    if (!items_host) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    *total = make_playout(d).total;
+    if (!(*total <= 0x3fffffffLL && d.D <= 0xffffff)) return fail(RSAF_ERR_ARG, who, -1, "parameter blob too large");
+    G->P = make_adam_segs(d, G->seg, &G->nseg, blocks);
+    if (!(G->P <= 64 && *blocks <= 0x7fffffffLL)) return fail(RSAF_ERR_ARG, who, -1, "too many parameters");
+    for (int k = 0; k < K; ++k) {
+        const ItemT& it = items_host[k];
+        if (!it.table) return fail(RSAF_ERR_ARG, who, k, "NULL pointer");
+        if (reinterpret_cast<uintptr_t>(it.grads) & 15) return fail(RSAF_ERR_ARG, who, k, "grads must be 16-byte aligned");
+        if (!(it.step >= 1)) return fail(RSAF_ERR_ARG, who, k, "step counts from 1");
+        if (!(it.beta1 >= 0.0 && it.beta1 < 1.0 && it.beta2 >= 0.0 && it.beta2 < 1.0 && it.eps >= 0.0 && it.lr >= 0.0))
+            return fail(RSAF_ERR_ARG, who, k, "needs 0 <= beta < 1, eps >= 0, lr >= 0");
+        for (int j = 0; j < k; ++j)
+            if (items_host[j].table == it.table)
+                return fail(RSAF_ERR_ARG, who, k, ("shares its table with item " + std::to_string(j)).c_str());
+        AdamRep& r = G->rep[k];
+        r.grads = it.grads;
+        r.table = reinterpret_cast<const unsigned long long*>(it.table);
+        r.skip = it.skip;
+        r.b1 = it.beta1; r.b2 = it.beta2; r.eps = it.eps;
+        r.step_size = it.lr / (1.0 - std::pow(it.beta1, (double)it.step));
+        r.inv_sqrt_bc2 = 1.0 / std::sqrt(1.0 - std::pow(it.beta2, (double)it.step));
+    }
+    return RSAF_OK;
 }
 
 }  // namespace cnntrain
@@ -1806,6 +2012,30 @@ int rsaf_ce_loss_group(const rsaf_ce_loss_item* items_host, int K, int num_class
     return RSAF_OK;
 }
 
+int rsaf_ce_loss_weighted_group(const rsaf_ce_loss_weighted_item* items_host, int K, int num_classes, rsaf_stream_t stream) {
+    RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
+    RSAF_CHECK_ARG(items_host, "items_host is NULL");
+    RSAF_CHECK_ARG(num_classes >= 2, "num_classes must be >= 2");
+    CeWeightedGroup g{};
+    WriteRanges writes;
+    double bytes = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const rsaf_ce_loss_weighted_item& it = items_host[k];
+        if (!(it.B >= 1 && (int64_t)it.B * num_classes <= 0x3fffffffLL)) return fail(RSAF_ERR_ARG, __func__, k, "batch must be >= 1 and B * num_classes < 2^30");
+        if (!(it.logits && it.labels && it.loss_out)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        TRY(writes.add(it.loss_out, 4, k, "loss_out", __func__));
+        TRY(writes.add(it.dlogits_out, (int64_t)it.B * num_classes * 4, k, "dlogits_out", __func__));
+        g.item[k] = CeWeightedItem{CeItem{it.logits, reinterpret_cast<const long long*>(it.labels), it.loss_out, it.dlogits_out, it.B},
+                                   it.class_weight};
+        bytes += (double)it.B * (num_classes * (it.dlogits_out ? 8 : 4) + 8) + (it.class_weight ? num_classes * 4.0 : 0.0);
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_ce", s, 0.0, bytes);
+    hipLaunchKernelGGL(ce_loss_weighted_group_kernel, dim3(K), dim3(256), 0, s, g, num_classes);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
 int rsaf_cnnlstm_adam_param_count(int input_dim, int channels, int hidden, int num_classes, int lstm_layers) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
     if (check_dims(d) != RSAF_OK) return -1;
@@ -1815,36 +2045,75 @@ int rsaf_cnnlstm_adam_param_count(int input_dim, int channels, int hidden, int n
 int rsaf_cnnlstm_adam_group(const rsaf_cnnlstm_adam_item* items_host, int K, int input_dim, int channels, int hidden,
                             int num_classes, int lstm_layers, rsaf_stream_t stream) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    AdamGroup G{};
+    int64_t blocks = 0, total = 0;
+    TRY(adam_prepare(d, items_host, K, __func__, &G, &blocks, &total));
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_adam", s, 0.0, (double)K * total * 4 * 7);
+    hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_cnnlstm_adam_scaled_group(const rsaf_cnnlstm_adam_scaled_item* items_host, int K, int input_dim, int channels, int hidden,
+                                   int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    AdamGroup G{};
+    int64_t blocks = 0, total = 0;
+    TRY(adam_prepare(d, items_host, K, __func__, &G, &blocks, &total));
+    AdamScales S{};
+    for (int k = 0; k < K; ++k) S.scale[k] = items_host[k].grad_scale;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_adam", s, 0.0, (double)K * total * 4 * 7);
+    hipLaunchKernelGGL(adam_scaled_group_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G, S);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int64_t rsaf_cnnlstm_grad_norm_partials(int input_dim, int channels, int hidden, int num_classes, int lstm_layers) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
+    if (check_dims(d) != RSAF_OK) return -1;
+    AdamSeg segs[ADAM_MAX_SEGS];
+    int nseg = 0;
+    int64_t blocks = 0;
+    make_adam_segs(d, segs, &nseg, &blocks);
+    return blocks;
+}
+
+int rsaf_cnnlstm_grad_norm_group(const rsaf_cnnlstm_grad_norm_item* items_host, int K, int input_dim, int channels, int hidden,
+                                 int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
     TRY(check_dims(d));
     RSAF_CHECK_ARG(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "K must be in [1, 16] (rsaf_cnnlstm_train_group_max)");
     RSAF_CHECK_ARG(items_host, "items_host is NULL");
     const int64_t total = make_playout(d).total;
     RSAF_CHECK_ARG(total <= 0x3fffffffLL && d.D <= 0xffffff, "parameter blob too large");
-    AdamGroup G{};
+    NormGroup G{};
     int64_t blocks = 0;
     G.P = make_adam_segs(d, G.seg, &G.nseg, &blocks);
     RSAF_CHECK_ARG(G.P <= 64 && blocks <= 0x7fffffffLL, "too many parameters");
+    G.blocks = (int)blocks;
+    WriteRanges writes;
     for (int k = 0; k < K; ++k) {
-        const rsaf_cnnlstm_adam_item& it = items_host[k];
-        if (!it.table) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        const rsaf_cnnlstm_grad_norm_item& it = items_host[k];
+        if (!(it.grads || it.table)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer: needs a gradient blob or a table with a fourth row");
+        if (!(it.partials && it.norm_out && it.scale_out)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
         if (reinterpret_cast<uintptr_t>(it.grads) & 15) return fail(RSAF_ERR_ARG, __func__, k, "grads must be 16-byte aligned");
-        if (!(it.step >= 1)) return fail(RSAF_ERR_ARG, __func__, k, "step counts from 1");
-        if (!(it.beta1 >= 0.0 && it.beta1 < 1.0 && it.beta2 >= 0.0 && it.beta2 < 1.0 && it.eps >= 0.0 && it.lr >= 0.0))
-            return fail(RSAF_ERR_ARG, __func__, k, "needs 0 <= beta < 1, eps >= 0, lr >= 0");
-        for (int j = 0; j < k; ++j)
-            if (items_host[j].table == it.table)
-                return fail(RSAF_ERR_ARG, __func__, k, ("shares its table with item " + std::to_string(j)).c_str());
-        AdamRep& r = G.rep[k];
-        r.grads = it.grads;
-        r.table = reinterpret_cast<const unsigned long long*>(it.table);
-        r.skip = it.skip;
-        r.b1 = it.beta1; r.b2 = it.beta2; r.eps = it.eps;
-        r.step_size = it.lr / (1.0 - std::pow(it.beta1, (double)it.step));
-        r.inv_sqrt_bc2 = 1.0 / std::sqrt(1.0 - std::pow(it.beta2, (double)it.step));
+        if (!(it.max_norm > 0.0)) return fail(RSAF_ERR_ARG, __func__, k, "max_norm must be > 0 and not NaN (+inf: no clipping)");
+        if (reinterpret_cast<uintptr_t>(it.partials) & 7) return fail(RSAF_ERR_ARG, __func__, k, "partials must be 8-byte aligned");
+        if (it.partials_count < blocks)
+            return fail(RSAF_ERR_WORKSPACE, __func__, k, "partials is shorter than rsaf_cnnlstm_grad_norm_partials() doubles");
+        TRY(writes.add(it.partials, blocks * 8, k, "partials", __func__));
+        TRY(writes.add(it.norm_out, 4, k, "norm_out", __func__));
+        TRY(writes.add(it.scale_out, 4, k, "scale_out", __func__));
+        G.rep[k] = NormRep{it.grads, reinterpret_cast<const unsigned long long*>(it.table), it.skip, it.max_norm, it.partials,
+                           it.norm_out, it.scale_out};
     }
     hipStream_t s = (hipStream_t)stream;
-    ProfScope prof("train_adam", s, 0.0, (double)K * total * 4 * 7);
-    hipLaunchKernelGGL(adam_group_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G);
+    ProfScope prof("train_grad_norm", s, 0.0, (double)K * (total * 4 + blocks * 16));
+    hipLaunchKernelGGL(grad_norm_partial_kernel, dim3((unsigned)blocks, K), dim3(256), 0, s, G);
+    RSAF_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(K), dim3(256), 0, s, G);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
