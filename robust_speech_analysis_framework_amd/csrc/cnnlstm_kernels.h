@@ -1,5 +1,5 @@
 // Kernels of the CNN-LSTM classifier shared by the inference path (cnnlstm.hip) and the training step
-// (cnnlstm_train.hip).
+// (cnnlstm_train.hip; its loss and optimizer side is cnnlstm_optim.hip and uses none of these).
 #pragma once
 #include "rsaf_common.h"
 

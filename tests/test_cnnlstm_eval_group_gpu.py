@@ -14,8 +14,10 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from weights import synth_input, synth_state_dict  # noqa: E402
+from cnnlstm_support import same  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -55,15 +57,6 @@ def build(D, C, H, seed, act, p_rate=0.5, p_block=0.2, layers=2, num_classes=2):
 def inputs(D, shapes, seed):
     import torch
     return [torch.from_numpy(synth_input(B, T, D, seed + k)).to("cuda") for k, (B, T) in enumerate(shapes)]
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if not np.array_equal(a, b):
-        d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-        raise AssertionError(f"{what}: {int((a != b).sum())} of {a.size} values differ, max |diff| {d.max():.3e} "
-                             f"(largest magnitude {np.abs(b).max():.3e})")
 
 
 def singles(models, xs):

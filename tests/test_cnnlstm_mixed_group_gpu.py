@@ -21,8 +21,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from weights import synth_input, synth_state_dict  # noqa: E402
+from cnnlstm_support import same  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -61,15 +63,6 @@ def labels(shapes, seed):
     import torch
     return [torch.from_numpy(np.random.Generator(np.random.PCG64(seed + k)).integers(0, NC, B)).to("cuda")
             for k, (B, _) in enumerate(shapes)]
-
-
-def same(a, b, what):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if not np.array_equal(a, b):
-        d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-        raise AssertionError(f"{what}: {int((a != b).sum())} of {a.size} values differ, max |diff| {d.max():.3e} "
-                             f"(largest magnitude {np.abs(b).max():.3e})")
 
 
 def host(t):

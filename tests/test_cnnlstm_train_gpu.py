@@ -11,15 +11,15 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 from weights import sample_tensor, synth_input, synth_state_dict  # noqa: E402
+from cnnlstm_support import RTOL, ZERO_GRAD, check_grads, device_masks  # noqa: E402
 
 from oracle import cnnlstm_train_oracle as to
 
 pytestmark = pytest.mark.gpu
 
-RTOL = 1e-4
-ZERO_GRAD = ("conv1.bias", "conv2.bias", "shortcut.0.bias", "attention_weights.bias")    # mathematically zero
 GOLDEN = sorted(glob.glob(os.path.join(HERE, "golden", "cnnlstm_train_*.npz")))
 
 
@@ -37,13 +37,6 @@ def build(D, C, H, seed, act, p_rate=0.0, p_block=0.0):
     return m.to("cuda").train(), sd
 
 
-def device_masks(mk):
-    import torch
-    t = lambda a: torch.from_numpy(a).to("cuda")                                  # noqa: E731
-    lst = [t(mk[k]) for k in sorted(k for k in mk if k.startswith("lstm"))]
-    return {"res_block1": t(mk["res_block1"]), "res_block2": t(mk["res_block2"]), "lstm": lst, "fc": t(mk["fc"])}
-
-
 def step(m, x, labels):
     import torch
     m.zero_grad()
@@ -52,22 +45,6 @@ def step(m, x, labels):
     loss.backward()
     torch.cuda.synchronize()
     return out.detach().cpu().numpy(), loss.item(), {k: p.grad.detach().cpu().numpy() for k, p in m.named_parameters()}
-
-
-def check_grads(got, want, scale_floor=1e-7):
-    worst = ("", 0.0)
-    for k, g in want.items():
-        a = got[k].astype(np.float64)
-        assert a.shape == g.shape, k
-        if k.endswith(ZERO_GRAD):
-            # rounding noise on both sides; bound it by the scale of the neighbouring weight gradient
-            assert np.abs(a).max() < 1e-3 * max(np.abs(want[k.replace("bias", "weight")]).max(), 1e-6), (k, np.abs(a).max())
-            continue
-        err = np.abs(a - g).max() / max(np.abs(g).max(), scale_floor)
-        if err > worst[1]:
-            worst = (k, err)
-        assert err < RTOL, (k, err)
-    return worst
 
 
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p)[14:-4] for p in GOLDEN])
