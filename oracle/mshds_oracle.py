@@ -10,7 +10,7 @@ cross-correlation pitch, path finder, HNR) and the Praat manual pages "Sound: To
 "Sound: To Pitch (ac)...", "Sound: To Harmonicity (cc)...", "Sound: To Spectrogram...",
 "Spectrum: Get centre of gravity / central moment...".  Free choices are documented inline.
 
-Built so far (the rest of the 25 features is NaN, as in ``csrc/mshds.hip``):
+Built so far (the rest of the 25 features is NaN, as in the ``csrc/mshds*.hip`` kernels):
   a2 ``_speechrate``, a9 ``_measureFormants``, a3 ``_pitch_values``, a4 ``_extract_pitch``, a5 ``_extract_intensity``, a6 ``_extract_harmonicity``,
   a10 ``_extract_Spectral_Moments``, a7 ``_extract_Slope_Tilt``, a8 ``_extract_CPP``.
 Arithmetic: float64 on the float32 samples (Praat computes in double).

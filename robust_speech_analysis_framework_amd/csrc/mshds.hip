@@ -1,7 +1,7 @@
 // Praat-style analyses behind the MSHDS features, float64 kernels for gfx950.
 //
-// Replaces the parselmouth/Praat calls of src/mshds_extractor.py (all ten helpers; the cepstral part lives in
-// mshds_cpp.hip):
+// Replaces the parselmouth/Praat calls of src/mshds_extractor.py (all ten helpers; formants, pulses and Ltas live in
+// mshds_voice.hip, the cepstral part in mshds_cpp.hip, what the three files share in mshds_common.h):
 //   _speechrate (:11-125), _pitch_values (:127-162), _extract_pitch (:164-183), _extract_intensity (:185-205),
 //   _extract_harmonicity (:207-225), _extract_Slope_Tilt (:227-251), _measureFormants (:303-338),
 //   _extract_Spectral_Moments (:340-376).
@@ -12,42 +12,26 @@
 // kernels (MI355X: 78 TFLOP/s fp64, vector and matrix alike); discrete decisions (voicing, path) then agree with
 // the oracle.
 //
-// Mapping: one 256-thread workgroup per analysis frame for the pitch kernel (frame staged in LDS, correlation on
-// v_mfma_f64_16x16x4_f64, candidates refined by Brent's method on a Chebyshev form of the sinc interpolation or,
-// where the depth is clipped, on wave-cooperative sinc sums), one wave per frame for intensity, one wave per clip
-// for the path finder and the per-clip statistics, one wave per voiced stretch for the pulse walker.
+// Mapping: ONE WAVE per frame for the pitch correlations (wave_fft.h: 512 / 1 024 / 2 048 complex points in registers),
+// except the 4 096-point cross-correlation, which takes a 256-thread workgroup per 16 frames (Stockham FFT in LDS); the
+// normalised correlation rows go through the caller's workspace.  One wave per frame for the candidate lists; the
+// refinement runs in its own kernels: Chebyshev coefficients per cell on the fp64 matrix pipe where the array ends clip
+// the depth, then Brent's search with one candidate per lane.  One wave per frame for intensity and the 1 024-point
+// spectrogram slice, one wave per clip for the path finder, the speech rate and the per-clip statistics.  Pitch host
+// side: one PitchPlan per call (checks + geometry, no HIP call), one function per launch family.
 #include <algorithm>
 #include <map>
 #include <mutex>
 #include <vector>
 
-#include "praat_interp.h"
-#include "rsaf_common.h"
-#include "wave_fft.h"
-
-// Frame times sit exactly on half-sample positions, where Praat's nearest/low index rounding is
-// decided by the last bit: evaluate t1 + f*dt etc. as separately rounded IEEE operations (no FMA
-// contraction), exactly like the float64 host arithmetic of the oracle.
-#pragma clang fp contract(off)
+#include "mshds_common.h"      // FMA contraction is off from there on
 
 namespace rsaf {
 namespace mshds {
 
-constexpr double DXS = 1.0 / 16000.0;
-constexpr double PI = 3.14159265358979323846;
 constexpr int MAXC = 16;            // candidate slots per frame (max_candidates <= 15)
 constexpr int MAX_MAXIMA = 96;      // local maxima considered per frame (in ascending lag order)
-constexpr double GOLD = 0.38196601125010515180;   // (3 - sqrt 5) / 2
 
-struct ClipInfo {       // one entry per clip of a launch (host-built)
-    int64_t sample_off;
-    int64_t frame_off;  // first frame of this clip in the per-launch frame buffers
-    double t1;          // time of the first frame
-    int n_samples;
-    int n_frames;
-    double x1;          // time of the first sample (0.5 dx for a sound read from a 16 kHz file; Praat's centred grid after Sound_resample)
-    double xmax;        // end of the sound's time domain [0, xmax] (n dx for a file; the ORIGINAL duration after Sound_resample)
-};
 
 struct PitchParams {
     double dt, min_pitch, ceiling, voicing_thr, octave_cost, dt_window;
@@ -59,18 +43,6 @@ struct PitchParams {
     double voicing_thr2;    // >= 0: also emit the candidate lists for this (lower) voicing threshold into out2
     int debug_stop;         // profiling aid (env RSAF_PITCH_STOP): leave the frame kernel after phase k; 0 = run all
 };
-
-// Sampled_xToLowIndex / xToNearestIndex / xToHighIndex of the sound (0-based), x1 = time of its first sample
-// (Praat rounds the 1-based real index (x - x1) / dx + 1; the + 1.0 stays a separately rounded operation: fp contract is off)
-__device__ __forceinline__ int64_t low_index(double t, double x1) { return (int64_t)floor((t - x1) / DXS + 1.0) - 1; }
-__device__ __forceinline__ int64_t nearest_index(double t, double x1) { return (int64_t)floor(((t - x1) / DXS + 1.0) + 0.5) - 1; }
-__device__ __forceinline__ int64_t high_index(double t, double x1) { return (int64_t)ceil((t - x1) / DXS + 1.0) - 1; }
-
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-    return v;
-}
 
 // ---- per-clip mean and global peak |x - mean| ------------------------------------------------------
 __global__ __launch_bounds__(256) void clip_peak_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
@@ -162,182 +134,6 @@ __global__ __launch_bounds__(256) void intensity_kernel(const float* __restrict_
         const double v = sx / sw / 4.0e-10;
         out[c.frame_off + f] = v < 1e-30 ? -300.0 : 10.0 * log10(v);
     }
-}
-
-// cos(x) for x in [0, pi] (all arguments of the sinc window are): fold to [0, pi/2] and evaluate the
-// degree-18 Taylor polynomial in x^2 (remainder (pi/2)^20/20! = 3.4e-15).  The library cos/sincos cost
-// ~1k cycles each in fp64 and dominated this kernel; this is ~12 FMAs.
-__device__ __forceinline__ double cos_0_pi(double x) {
-    const bool hi = x > 0.5 * PI;
-    const double y = hi ? PI - x : x;
-    const double z = y * y;
-    double p = -1.0 / 6402373705728000.0;              // -1/18!
-    p = p * z + 1.0 / 20922789888000.0;                // 1/16!
-    p = p * z - 1.0 / 87178291200.0;                   // -1/14!
-    p = p * z + 1.0 / 479001600.0;                     // 1/12!
-    p = p * z - 1.0 / 3628800.0;                       // -1/10!
-    p = p * z + 1.0 / 40320.0;                         // 1/8!
-    p = p * z - 1.0 / 720.0;                           // -1/6!
-    p = p * z + 1.0 / 24.0;
-    p = p * z - 0.5;
-    p = p * z + 1.0;
-    return hi ? -p : p;
-}
-__device__ __forceinline__ double sin_0_pi(double x) { return cos_0_pi(fabs(0.5 * PI - x)); }
-
-// 1/d for d > 0: hardware reciprocal estimate + two Newton steps (full double accuracy, ~5 ops instead
-// of the ~15-op IEEE division sequence)
-__device__ __forceinline__ double fast_rcp(double d) {
-    double r = __builtin_amdgcn_rcp(d);
-    r = r * (2.0 - d * r);
-    r = r * (2.0 - d * r);
-    return r;
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {      // l must be wave-uniform
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
-// Sum over each aligned group of G lanes, result in every lane of the group.  The 16-lane part is four DPP
-// steps (xor 1, xor 2, half-row mirror, row mirror: VALU latency, no LDS crossbar); rows are then combined
-// through scalar registers.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
-    return __hiloint2double(hi, lo);
-}
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-    v += dpp_f64<0xB1>(v);      // quad_perm [1,0,3,2]
-    v += dpp_f64<0x4E>(v);      // quad_perm [2,3,0,1]
-    v += dpp_f64<0x141>(v);     // row_half_mirror
-    v += dpp_f64<0x140>(v);     // row_mirror
-    if (G == 16) return v;
-    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-    if (G == 64) return (r0 + r1) + (r2 + r3);
-    return (threadIdx.x & 32) ? r2 + r3 : r0 + r1;
-}
-
-// maximum over the wave in every lane, same DPP / readlane structure (a ds_bpermute butterfly costs six LDS-crossbar
-// round trips per reduction: in the pitch frame kernels, three reductions per frame, that was a third of the time in
-// front of the correlation)
-__device__ __forceinline__ double wave_max_dpp(double v) {
-    v = fmax(v, dpp_f64<0xB1>(v));
-    v = fmax(v, dpp_f64<0x4E>(v));
-    v = fmax(v, dpp_f64<0x141>(v));
-    v = fmax(v, dpp_f64<0x140>(v));
-    const double r0 = readlane_f64(v, 0), r1 = readlane_f64(v, 16), r2 = readlane_f64(v, 32), r3 = readlane_f64(v, 48);
-    return fmax(fmax(r0, r1), fmax(r2, r3));
-}
-
-// ---- sinc interpolation of an LDS array by a G-lane group (Praat NUM_interpolate_sinc) -----------------
-// y: n samples (0-based); x: 0-based real position; only indices in [nz_lo, nz_hi] can be non-zero.
-// Every lane of the wave must call this (the 64/G groups of a wave evaluate different x).
-// RECUR: the raised-cosine window angle advances by a fixed step per term, so each lane rotates
-// (cos, sin) by the group stride instead of evaluating the polynomial per term (pays for long kernels).
-template <int G, bool RECUR>
-__device__ double sinc_group(const double* __restrict__ y, int n, double x, int depth, int nz_lo, int nz_hi, int lg) {
-    const double x1 = x + 1.0;
-    const int midleft = (int)floor(x1), midright = midleft + 1;
-    const bool special = (x1 > n) | (x1 < 1) | (x1 == (double)midleft);
-    int si = x1 > n ? n - 1 : (x1 < 1 ? 0 : midleft - 1);
-    si = si < 0 ? 0 : (si > n - 1 ? n - 1 : si);
-    int d = depth;
-    if (d > midright - 1) d = midright - 1;
-    if (d > n - midleft) d = n - midleft;
-    if (d < 0 || special) d = 0;
-    const int left = midright - d, right = midleft + d;
-    double acc = 0.0;
-    const double a0l = PI * (x1 - midleft);               // in (0, pi) unless special
-    const double hs = special ? 0.0 : 0.5 * sin_0_pi(a0l); // sin(pi - a) = sin(a): same for both halves
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        // left half: 1-based ix = midleft - k; right half: ix = midright + k; k = 0..d-1.  The window
-        // angle (a0 + pi k) / den stays in (0, pi).  [kmin, kmax) drops the all-zero parts of y.
-        const double a0 = half == 0 ? a0l : PI * (midright - x1);
-        const double iden = fast_rcp(half == 0 ? x1 - left + 1.0 : right - x1 + 1.0);
-        int kmin, kmax = d;
-        if (half == 0) {
-            kmin = midleft - 1 - nz_hi;
-            if (midleft - kmax < nz_lo) kmax = midleft - nz_lo;
-        } else {
-            kmin = nz_lo - midright + 1;
-            if (midright + kmax - 2 > nz_hi) kmax = nz_hi - midright + 2;
-        }
-        kmin = kmin < 0 ? 0 : kmin;
-        const int k0 = kmin + lg;
-        // G is even: every term of a lane has the sign of its first one, (-1)^k0 hs is applied once behind the loop
-        double part = 0.0;
-        if (RECUR) {
-            const double th = (a0 + PI * k0) * iden, st = (PI * G) * iden;   // st < pi whenever a lane has 2+ terms
-            double c = cos_0_pi(fmin(th, PI)), sn = sin_0_pi(fmin(th, PI));
-            const double C = cos_0_pi(fmin(st, PI)), S = sin_0_pi(fmin(st, PI));
-            for (int k = k0; k < kmax; k += G) {
-                const int idx = half == 0 ? midleft - k - 1 : midright + k - 1;
-                const double a = a0 + PI * k;
-                part += y[idx] * (fast_rcp(a) * (1.0 + c));
-                const double c2 = c * C - sn * S;
-                sn = sn * C + c * S;
-                c = c2;
-            }
-        } else {
-            for (int k = k0; k < kmax; k += G) {
-                const int idx = half == 0 ? midleft - k - 1 : midright + k - 1;
-                const double a = a0 + PI * k;
-                part += y[idx] * (fast_rcp(a) * (1.0 + cos_0_pi(a * iden)));
-            }
-        }
-        acc += ((k0 & 1) ? -hs : hs) * part;
-    }
-    acc = group_sum<G>(acc);
-    return special ? y[si] : acc;
-}
-
-// Praat NUMimproveMaximum (sinc): Brent's minimiser in the netlib fminbr form on -sinc over [ix-1, ix+1],
-// tolerance sqrt(eps)*|x| + tol/3 on the 1-based position, <= 60 iterations.  One G-lane group per
-// candidate; `live` = this group holds a real candidate (others just keep the wave's shuffles uniform).
-template <int G, bool RECUR>
-__device__ void improve_max_group(const double* __restrict__ y, int n, double ix0, int depth, int nz_lo, int nz_hi,
-                                  int lg, bool live, double& xm, double& ym) {
-    const double SQRT_EPS = 1.4901161193847656e-08, TOL3 = 1e-10 / 3.0;
-    double a = ix0 + 1.0 - 1.0, b = ix0 + 1.0 + 1.0;     // 1-based bracket
-    double v = a + GOLD * (b - a);
-    double fv = -sinc_group<G, RECUR>(y, n, v - 1.0, depth, nz_lo, nz_hi, lg);
-    double x = v, w = v, fx = fv, fw = fv;
-    bool active = live;
-    for (int it = 0; it < 60; ++it) {
-        const double rng = b - a, mid = 0.5 * (a + b);
-        const double tol_act = SQRT_EPS * fabs(x) + TOL3;
-        if (fabs(x - mid) + 0.5 * rng <= 2.0 * tol_act) active = false;
-        if (!__any(active)) break;
-        double step = GOLD * (x < mid ? b - x : a - x);
-        if (fabs(x - w) >= tol_act) {
-            const double t = (x - w) * (fx - fv);
-            double q = (x - v) * (fx - fw);
-            double p = (x - v) * q - (x - w) * t;
-            q = 2.0 * (q - t);
-            if (q > 0.0) p = -p; else q = -q;
-            if (fabs(p) < fabs(step * q) && p > q * (a - x + 2.0 * tol_act) && p < q * (b - x - 2.0 * tol_act))
-                step = p / q;
-        }
-        if (fabs(step) < tol_act) step = step > 0.0 ? tol_act : -tol_act;
-        const double tt = x + step;
-        const double ft = -sinc_group<G, RECUR>(y, n, tt - 1.0, depth, nz_lo, nz_hi, lg);
-        if (active) {
-            if (ft <= fx) {
-                if (tt < x) b = x; else a = x;
-                v = w; w = x; x = tt;
-                fv = fw; fw = fx; fx = ft;
-            } else {
-                if (tt < x) a = tt; else b = tt;
-                if (ft <= fw || w == x) { v = w; w = tt; fv = fw; fw = ft; }
-                else if (ft <= fv || v == x || v == w) { v = tt; fv = ft; }
-            }
-        }
-    }
-    xm = x - 1.0;
-    ym = -fx;
 }
 
 // ---- pitch candidates per frame (AC: Hanning-windowed autocorrelation; CC: forward cross-correlation) --
@@ -466,7 +262,6 @@ __device__ void refine_candidates(const RefineArgs& A, int tid, int nthreads) {
 // A complex transform of M points as a Stockham autosort FFT (radix 4, a final radix 2 when M is not a power of 4):
 // natural order in and out, ping-pong between two LDS buffers, 256 threads.  Twiddles W_N^k = exp(-2 pi i k / N),
 // k < N / 2, come from a table built on the host in double precision.
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ double2_t cmul(double2_t a, double2_t b) {
     return double2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
@@ -2502,932 +2297,6 @@ __global__ __launch_bounds__(64) void speechrate_kernel(const double* __restrict
     o[4] = n_pauses > 0 ? (original_dur - phonation) / n_pauses : 0.0;
 }
 
-// ---- 16 kHz -> 10 kHz resampling (Sound_resample (10000, 500) at the head of To Formant (burg)) -----------------
-// Input: the clip after Praat's FFT low-pass (rsaf_praat_lowpass_batch).  out[m] = sum_k x[base + k] * W[phase][k + D]:
-// the ratio 5/8 gives 5 distinct fractional offsets, whose NUM_interpolate_sinc weights at full depth D the host
-// tabulates in float64.
-struct ResampleInfo {        // per clip (host-built), 48 bytes
-    int64_t sample_off;      // into wav
-    int64_t out_off;         // into the 10 kHz buffer
-    double pos0;             // real input index of output sample 0
-    double x1o;              // time of output sample 0
-    int n_in, n_out;
-    int table;               // index of this clip's weight table (one per distinct pos0)
-    int pad;
-};
-
-// 320-thread workgroup = 5 phases x 256 consecutive q: wave r owns phase r, so its weight row is wave-uniform and comes
-// through the scalar cache into SGPRs (no LDS traffic for the weights); a lane owns 4 consecutive q, whose tap windows
-// are 8 samples apart: every sample it reads from the LDS tile feeds 4 FMAs (taps k, k - 8, k - 16, k - 24 of its four
-// outputs), which balances the LDS read rate against the fp64 FMA rate.  Lanes are 32 samples apart in the tile; a
-// 33/32 skew puts the 8-byte reads of a half wave on distinct banks.  The tables hold NUM_interpolate_sinc's weights at
-// full depth for the five fractional positions of the 8 : 5 grid, rows zero-padded to `wstride` doubles; outputs whose
-// depth Praat clips (within `depth` input samples of either end) are recomputed by resample_edge_kernel.
-constexpr int RS_QL = 4;                  // consecutive q per lane
-constexpr int RS_QT = 64 * RS_QL;         // q per workgroup
-__global__ __launch_bounds__(320) void resample_kernel(const double* __restrict__ lp, const ResampleInfo* __restrict__ ri,
-                                                       const double* __restrict__ tables, int wstride,
-                                                       const int* __restrict__ phase_base, int depth,
-                                                       double* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const ResampleInfo c = ri[blockIdx.y];
-    const int q0 = blockIdx.x * RS_QT;
-    if (5 * q0 >= c.n_out) return;
-    const int taps = 2 * depth + 1;
-    double* xs = reinterpret_cast<double*>(smem_raw);                 // input tile
-    const int tid = threadIdx.x;
-    const int* pb = phase_base + c.table * 5;
-    int bmin = pb[0], bmax = pb[0];
-    for (int r = 1; r < 5; ++r) { bmin = min(bmin, pb[r]); bmax = max(bmax, pb[r]); }
-    const int lo = 8 * q0 + bmin - depth;                             // first input index of the tile
-    const int nkb = (taps + 8 * (RS_QL - 1) + 7) / 8;                 // tap blocks of 8; the rows are zero beyond `taps`
-    const int span = 8 * RS_QL * 63 + (bmax - bmin) + 8 * nkb;        // every index the tap loop reads
-    const double* x = lp + c.sample_off;
-    for (int i = tid; i < span; i += 320) {
-        const int j = lo + i;
-        xs[i + (i >> 5)] = (j >= 0 && j < c.n_in) ? x[j] : 0.0;
-    }
-    __syncthreads();
-    const int r = __builtin_amdgcn_readfirstlane(tid >> 6), ql = tid & 63;
-    const double* __restrict__ w = tables + ((int64_t)c.table * 5 + r) * wstride;   // wave-uniform
-    const int i0 = 8 * RS_QL * ql + pb[r] - bmin;                     // tile index of tap 0 of the lane's first output
-    double acc[RS_QL] = {0.0, 0.0, 0.0, 0.0};
-    double wq[RS_QL][8];                                              // weights k = 8 (kb - j) + t of output j
-#pragma unroll
-    for (int j = 0; j < RS_QL; ++j)
-#pragma unroll
-        for (int t = 0; t < 8; ++t) wq[j][t] = 0.0;
-    for (int kb = 0; kb < nkb; ++kb) {
-#pragma unroll
-        for (int j = RS_QL - 1; j > 0; --j)
-#pragma unroll
-            for (int t = 0; t < 8; ++t) wq[j][t] = wq[j - 1][t];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) wq[0][t] = w[8 * kb + t];
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            const int i = i0 + 8 * kb + t;
-            const double xv = xs[i + (i >> 5)];
-#pragma unroll
-            for (int j = 0; j < RS_QL; ++j) acc[j] = fma(xv, wq[j][t], acc[j]);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < RS_QL; ++j) {
-        const int m = 5 * (q0 + RS_QL * ql + j) + r;
-        if (m < c.n_out) out[c.out_off + m] = acc[j];
-    }
-}
-
-// the first and last `n_edge` output samples of every clip by the general routine when their depth is clipped (or the
-// position falls outside the sound)
-__global__ __launch_bounds__(256) void resample_edge_kernel(const double* __restrict__ lp, const ResampleInfo* __restrict__ ri,
-                                                            int depth, int n_edge, double ratio_in_out, double* __restrict__ out) {
-    const ResampleInfo c = ri[blockIdx.y];
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= 2 * n_edge) return;
-    const int m = e < n_edge ? e : c.n_out - 1 - (e - n_edge);
-    if (m < 0 || m >= c.n_out) return;
-    const double x = c.pos0 + (double)m * ratio_in_out + 1.0;         // Praat's 1-based real index
-    const int64_t midleft = (int64_t)floor(x);
-    const bool full = x >= 1.0 && x <= (double)c.n_in && midleft >= depth && (int64_t)c.n_in - midleft >= depth;
-    if (full) return;
-    out[c.out_off + m] = praat_interpolate_sinc(lp + c.sample_off, (int64_t)c.n_in, x, depth);
-}
-
-// ---- Formant (burg): one wave per frame -----------------------------------------------------------------------
-// (wave sums / maxima on DPP + v_readlane, root broadcasts on v_readlane: the ds_bpermute forms - ~50 LDS-crossbar round
-// trips per Aberth iteration, 24 per Burg order - were most of the 34 000 cycles a frame took)
-// Gaussian-windowed 50 ms frame of the pre-emphasised 10 kHz signal -> Burg LPC (order 10) -> roots by
-// Aberth-Ehrlich iteration (all ten simultaneously, lanes 0..9) + Newton polish -> reflect into the unit
-// circle -> (frequency, bandwidth) of the roots in the upper half plane, ascending, at most 5.
-constexpr int FB_ORDER = 10;
-struct FormantFrame { double f[5]; double b[5]; };
-
-// A wave takes FB_GROUP consecutive frames: the Burg recursion runs frame by frame with all 64 lanes on the frame's
-// samples; the root finding - ten lanes per polynomial - then runs for the FB_GROUP polynomials at once (lane = 10 g + root),
-// so that the most expensive phase (~650 instructions per Aberth iteration, 10-15 iterations) is paid once per 6 frames
-// instead of once per frame with 54 idle lanes.
-constexpr int FB_GROUP = 6;
-__global__ __launch_bounds__(256) void formant_kernel(const double* __restrict__ y10, const ResampleInfo* __restrict__ ri,
-                                                      const ClipInfo* __restrict__ ci, const double* __restrict__ win,
-                                                      int nsw, double dt, double dxo, double preemph,
-                                                      FormantFrame* __restrict__ out) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    __shared__ double s_cf[4][FB_GROUP][FB_ORDER + 1];
-    __shared__ double2 s_z[4][64];
-    __shared__ double s_fq[4][64];
-    __shared__ int s_okf[4][FB_GROUP];
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const ClipInfo c = ci[blockIdx.y];
-    const int fbase = (blockIdx.x * 4 + wv) * FB_GROUP;
-    if (fbase >= c.n_frames) return;
-    const ResampleInfo r = ri[blockIdx.y];
-    double* b1 = reinterpret_cast<double*>(smem_raw) + (size_t)wv * 2 * (nsw + 2);
-    double* b2 = b1 + (nsw + 2);
-    const double* y = y10 + r.out_off;
-    const int n = r.n_out;
-    const double x1o = r.x1o;
-    const double qn = __longlong_as_double(0x7ff8000000000000LL);
-    auto wsync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const int ng = min(FB_GROUP, c.n_frames - fbase);
-#pragma unroll 1
-    for (int g = 0; g < ng; ++g) {
-        const int f = fbase + g;
-        const double t = c.t1 + f * dt;
-        const int left = (int)floor((t - x1o) / dxo);
-        const int half = nsw / 2;
-        int start = left + 1 - half, end = left + half;
-        start = start < 0 ? 0 : start;
-        end = end > n - 1 ? n - 1 : end;
-        const int len = end - start + 1;
-        // pre-emphasised, windowed frame into b1[1..len] (Burg's 1-based arrays); also the max intensity
-        double mxi = 0.0, p = 0.0;
-        for (int j0 = lane; j0 < len; j0 += 4 * 64) {                     // twelve loads in flight (see clip_peak_kernel)
-            double ya[4], yb[4], wq[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 64 * u < len ? j0 + 64 * u : len - 1, i = start + j;
-                ya[u] = y[i];
-                yb[u] = y[i > 0 ? i - 1 : 0];
-                wq[u] = win[j];
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 64 * u, i = start + j;
-                if (j < len) {
-                    const double v = (i > 0) ? ya[u] - preemph * yb[u] : ya[u];
-                    mxi = fmax(mxi, v * v);
-                    const double xv = v * wq[u];
-                    b1[j + 1] = xv;
-                    p += xv * xv;
-                }
-            }
-        }
-        mxi = wave_max_dpp(mxi);
-        p = group_sum<64>(p);
-        bool ok = !(len < FB_ORDER + 2 || mxi == 0.0 || p <= 0.0);
-        wsync();
-        double a[FB_ORDER + 1], aa[FB_ORDER + 1];
-#pragma unroll
-        for (int i = 0; i <= FB_ORDER; ++i) { a[i] = 0.0; aa[i] = 0.0; }
-        if (ok) {
-            // NUMburg.  x = b1 copy: b2[j] = x[j+1] for j = 1..len-1, b1[j] = x[j] for j = 1..len-1
-            for (int j = 1 + lane; j <= len - 1; j += 64) b2[j] = b1[j + 1];
-            wsync();
-            for (int i = 1; i <= FB_ORDER; ++i) {
-                double num = 0.0, den = 0.0;
-                for (int j = 1 + lane; j <= len - i; j += 64) { const double u = b1[j], v = b2[j]; num += u * v; den += u * u + v * v; }
-                num = group_sum<64>(num);
-                den = group_sum<64>(den);
-                if (den <= 0.0) { ok = false; break; }
-                a[i] = 2.0 * num / den;
-                for (int j = 1; j < i; ++j) a[j] = aa[j] - a[i] * aa[i - j];
-                if (i < FB_ORDER) {
-                    for (int j = 1; j <= i; ++j) aa[j] = a[j];
-                    const double k = aa[i];
-                    // b1[j] -= k*b2[j]; b2[j] = b2[j+1] - k*b1[j+1] (old b1) for j = 1..len-i-1
-                    for (int j0 = 1; j0 <= len - i - 1; j0 += 64) {
-                        const int j = j0 + lane;
-                        double nb1 = 0.0, nb2 = 0.0;
-                        const bool on = j <= len - i - 1;
-                        if (on) { nb1 = b1[j] - k * b2[j]; nb2 = b2[j + 1] - k * b1[j + 1]; }
-                        __builtin_amdgcn_wave_barrier();
-                        if (on) { b1[j] = nb1; b2[j] = nb2; }
-                        wsync();
-                    }
-                }
-            }
-        }
-        // polynomial z^10 - a1 z^9 - ... - a10 ; cf[k] = coefficient of z^(10-k)
-        if (lane == 0) {
-            s_okf[wv][g] = ok ? 1 : 0;
-            s_cf[wv][g][0] = 1.0;
-#pragma unroll
-            for (int k = 1; k <= FB_ORDER; ++k) s_cf[wv][g][k] = -a[k];
-        }
-        wsync();
-    }
-    // ---- roots of the ng polynomials at once: lane = 10 g + root ----
-    const int g = lane / FB_ORDER, li = lane - g * FB_ORDER;
-    const bool mine = g < ng;
-    const int gg = mine ? g : 0;
-    const bool okf = mine && s_okf[wv][gg] != 0;
-    double cf[FB_ORDER + 1];
-#pragma unroll
-    for (int k = 0; k <= FB_ORDER; ++k) cf[k] = s_cf[wv][gg][k];
-    // Aberth-Ehrlich: start on a circle of radius 0.9
-    double zr = 0.0, zi = 0.0;
-    { double sn, cs; sincos(2.0 * PI * (li + 0.35) / FB_ORDER, &sn, &cs); zr = 0.9 * cs; zi = 0.9 * sn; }
-    for (int it = 0; it < 80; ++it) {
-        // p(z), p'(z) by Horner
-        double pr = cf[0], pi_ = 0.0, dr = 0.0, di = 0.0;
-#pragma unroll
-        for (int k = 1; k <= FB_ORDER; ++k) {
-            const double ndr = dr * zr - di * zi + pr, ndi = dr * zi + di * zr + pi_;
-            dr = ndr; di = ndi;
-            const double npr = pr * zr - pi_ * zi + cf[k], npi = pr * zi + pi_ * zr;
-            pr = npr; pi_ = npi;
-        }
-        // w = p/p'
-        const double dd = dr * dr + di * di;
-        double wr_ = 0.0, wi_ = 0.0;
-        if (dd > 0.0) { const double rd = fast_rcp(dd); wr_ = (pr * dr + pi_ * di) * rd; wi_ = (pi_ * dr - pr * di) * rd; }
-        // s = sum_{j != i} 1/(z_i - z_j) over the roots of the same polynomial
-        s_z[wv][lane] = make_double2(zr, zi);
-        wsync();
-        double sr = 0.0, si = 0.0;
-#pragma unroll
-        for (int j = 0; j < FB_ORDER; ++j) {
-            const double2 oz = s_z[wv][gg * FB_ORDER + j];
-            const double ex = zr - oz.x, ey = zi - oz.y;
-            const double ee = ex * ex + ey * ey;
-            if (j != li && ee > 0.0) { const double re = fast_rcp(ee); sr += ex * re; si -= ey * re; }
-        }
-        wsync();
-        // delta = w / (1 - w*s)
-        const double qr = 1.0 - (wr_ * sr - wi_ * si), qi = -(wr_ * si + wi_ * sr);
-        const double qq = qr * qr + qi * qi;
-        double er = wr_, ei = wi_;
-        if (qq > 0.0) { const double rq = fast_rcp(qq); er = (wr_ * qr + wi_ * qi) * rq; ei = (wi_ * qr - wr_ * qi) * rq; }
-        zr -= er; zi -= ei;
-        const double step = okf ? fabs(er) + fabs(ei) : 0.0;
-        if (wave_max_dpp(step) < 1e-11) break;               // the three Newton steps below square this down to rounding
-    }
-    for (int it = 0; it < 3; ++it) {                              // Newton polish on the original polynomial
-        double pr = cf[0], pi_ = 0.0, dr = 0.0, di = 0.0;
-#pragma unroll
-        for (int k = 1; k <= FB_ORDER; ++k) {
-            const double ndr = dr * zr - di * zi + pr, ndi = dr * zi + di * zr + pi_;
-            dr = ndr; di = ndi;
-            const double npr = pr * zr - pi_ * zi + cf[k], npi = pr * zi + pi_ * zr;
-            pr = npr; pi_ = npi;
-        }
-        const double dd = dr * dr + di * di;
-        if (dd > 0.0) { zr -= (pr * dr + pi_ * di) / dd; zi -= (pi_ * dr - pr * di) / dd; }
-    }
-    // fix into the unit circle, keep the upper half plane, convert
-    const double nyq = 0.5 / dxo;
-    double mag2 = zr * zr + zi * zi;
-    if (mag2 > 1.0) { zr /= mag2; zi /= mag2; mag2 = zr * zr + zi * zi; }   // z -> 1/conj(z)
-    double fq = fabs(atan2(zi, zr)) * nyq / PI;
-    const double bw = -log(mag2) * nyq / PI;
-    const bool keep = okf && zi >= 0.0 && fq >= 50.0 && fq <= nyq - 50.0;
-    if (!keep) fq = 1e300;
-    // rank among the kept roots of the same frame (stable by root index), write the first five
-    s_fq[wv][lane] = fq;
-    wsync();
-    int rank = 0;
-#pragma unroll
-    for (int j = 0; j < FB_ORDER; ++j) {
-        const double of = s_fq[wv][gg * FB_ORDER + j];
-        rank += (of < fq) || (of == fq && j < li);
-    }
-    // the five lowest of each frame through LDS, so that one lane writes each output slot
-    s_z[wv][lane] = make_double2(qn, qn);
-    wsync();
-    if (keep && rank < 5) s_z[wv][gg * FB_ORDER + rank] = make_double2(fq, bw);
-    wsync();
-    if (mine && li < 5) {
-        FormantFrame* o = out + c.frame_off + fbase + gg;
-        const double2 v = s_z[wv][gg * FB_ORDER + li];
-        o->f[li] = v.x;
-        o->b[li] = v.y;
-    }
-}
-
-// ---- glottal pulses: Sound & Pitch: To PointProcess (cc), one wave per clip ----------------------------------
-__device__ double pitch_value_at(const double* __restrict__ f, int n, double t1, double dt, double ceiling, double t) {
-    const double qn = __longlong_as_double(0x7ff8000000000000LL);
-    if (n <= 0) return qn;
-    const double ireal = (t - t1) / dt;
-    const int64_t ileft = (int64_t)floor(ireal);
-    double phase = ireal - (double)ileft;
-    int64_t inear, ifar;
-    if (phase < 0.5) { inear = ileft; ifar = ileft + 1; } else { inear = ileft + 1; ifar = ileft; phase = 1.0 - phase; }
-    if (inear < 0 || inear >= n) return qn;
-    const double fn = f[inear];
-    if (!(fn > 0.0 && fn < ceiling)) return qn;
-    if (ifar < 0 || ifar >= n) return fn;
-    const double ff = f[ifar];
-    if (!(ff > 0.0 && ff < ceiling)) return fn;
-    return fn + phase * (ff - fn);
-}
-
-// Sound_findMaximumCorrelation with the shifts spread over the lanes; returns corr, *tout, *peak (uniform).
-// The samples come from a wave-private LDS window that SLIDES with the walk: the fixed window and the union of the
-// shifted windows of one pulse span ~2.5 periods, the window holds PULSE_LDS samples, so it is refilled from global
-// memory once per ~10-20 pulses (in the walking direction) instead of twice per pulse; every lane then reads the fixed
-// window as a broadcast and its own shifted window with unit stride.  `win0` = sample index of the window's first
-// entry (INT64_MIN: empty), kept by the caller across pulses; dir = -1 / +1: the walk goes left / right.
-constexpr int PULSE_LDS = 3072;
-constexpr int PULSE_FW = 128;         // pitch frames of the walker's sliding window
-__device__ double max_correlation_wave(const float* __restrict__ x, int n, double x1, double t1, double window, double tmin2,
-                                       double tmax2, int lane, double* tout, double* peak, float* pwin, int64_t* win0, int dir) {
-    const double half = 0.5 * window;
-    const int64_t ileft1 = nearest_index(t1 - half, x1);
-    const int64_t iright1 = nearest_index(t1 + half, x1);
-    const int64_t l2min = low_index(tmin2 - half, x1);
-    const int64_t l2max = high_index(tmax2 - half, x1);
-    double best = -1.0, r1 = 0.0, r2 = 0.0, r3 = 0.0, r1b = 0.0, r3b = 0.0, ir = 0.0, pk = 0.0;
-    const int wlen = (int)(iright1 - ileft1 + 1);
-    const int slen = (int)(l2max - l2min) + wlen;
-    const int64_t ulo = ileft1 < l2min ? ileft1 : l2min;                      // union of both ranges
-    const int64_t uhi = (ileft1 + wlen > l2min + slen ? ileft1 + wlen : l2min + slen);
-    const bool staged = wlen > 0 && slen > 0 && uhi - ulo <= PULSE_LDS;
-    if (staged && (*win0 == INT64_MIN || ulo < *win0 || uhi > *win0 + PULSE_LDS)) {
-        // refill: the needed span at the trailing end of the window, the rest ahead in the walking direction
-        const int64_t w0 = dir < 0 ? uhi - PULSE_LDS : ulo;
-        __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < PULSE_LDS; i += 64) { const int64_t j = w0 + i; pwin[i] = (j >= 0 && j < n) ? x[j] : 0.0f; }
-        *win0 = w0;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    const float* ps1 = pwin + (staged ? (int)(ileft1 - *win0) : 0);
-    const float* ps2 = pwin + (staged ? (int)(l2min - *win0) : 0);
-    // Interior case (every sample of both windows lies inside the sound: all pulses but the ones at the very ends of a
-    // clip): no pair is skipped, so the sum of squares of the fixed window is one number, the one of the shifted window
-    // slides (norm2(s + 1) = norm2(s) - a[s]^2 + a[s + wlen]^2: one scan over the 64 shifts of a batch), and the local
-    // peak is only needed for the one step that detects the maximum.  The loop over the window then carries the cross
-    // product alone: 2 LDS reads, 2 conversions and 1 FMA per sample instead of 3 FMAs, a maximum and an absolute value more.
-    const bool interior = staged && ulo >= 0 && uhi <= n;
-    double n1_all = 0.0;
-    if (interior) {
-        for (int i = lane; i < wlen; i += 64) { const double a = ps1[i]; n1_all = fma(a, a, n1_all); }
-        n1_all = group_sum<64>(n1_all);
-    }
-    for (int64_t b = l2min; b <= l2max; b += 64) {
-        const int64_t ileft2 = b + lane;
-        double norm1 = 0.0, norm2 = 0.0, prod = 0.0, lp = 0.0;
-        if (interior) {
-            const int ob = (int)(b - l2min);                       // window offset of the batch's first shift
-            double n20 = 0.0;                                      // sum of squares of shift ob
-            for (int i = lane; i < wlen; i += 64) { const double a = ps2[ob + i]; n20 = fma(a, a, n20); }
-            n20 = group_sum<64>(n20);
-            const bool in = ileft2 <= l2max;
-            const int o2 = ob + lane;
-            // d_t = a[t + wlen]^2 - a[t]^2 for shift t -> t + 1 (reads stay inside the union: the last lane that matters is cnt - 1)
-            double dsc = 0.0;
-            if (in && ileft2 < l2max) { const double lo_ = ps2[o2], hi_ = ps2[o2 + wlen]; dsc = hi_ * hi_ - lo_ * lo_; }
-            double incl = dsc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
-            norm1 = n1_all;
-            norm2 = n20 + (incl - dsc);                            // exclusive prefix of the differences
-            // The sliding sum is exact for 16-bit PCM (the squares add exactly); on resampled or float clips it can cancel
-            // when the energy drops sharply inside the batch.  A lane whose sum has lost its digits takes the direct sum.
-            if (in && !(norm2 > 1e-9 * n20)) {
-                double d2 = 0.0;
-                for (int i = 0; i < wlen; ++i) { const double a = ps2[o2 + i]; d2 = fma(a, a, d2); }
-                norm2 = d2;
-            }
-            if (in) {
-                double p0 = 0.0, p1 = 0.0;
-                int i = 0;
-                for (; i + 1 < wlen; i += 2) {
-                    p0 = fma((double)ps1[i], (double)ps2[o2 + i], p0);
-                    p1 = fma((double)ps1[i + 1], (double)ps2[o2 + i + 1], p1);
-                }
-                if (i < wlen) p0 = fma((double)ps1[i], (double)ps2[o2 + i], p0);
-                prod = p0 + p1;
-            }
-        } else if (ileft2 <= l2max) {
-            if (staged) {
-                const int o2 = (int)(ileft2 - l2min);
-                // Praat skips pairs outside the sound: the pairs inside are one index range, worked out once per lag
-                int64_t lo = -ileft1 > -ileft2 ? -ileft1 : -ileft2, hi = n - ileft1 < n - ileft2 ? n - ileft1 : n - ileft2;
-                lo = lo < 0 ? 0 : lo;
-                hi = hi > wlen ? wlen : hi;
-                for (int i = (int)lo; i < (int)hi; ++i) {
-                    const double a1 = ps1[i], a2 = ps2[o2 + i];
-                    norm1 += a1 * a1; norm2 += a2 * a2; prod += a1 * a2;
-                    lp = fmax(lp, fabs(a2));
-                }
-            } else {
-                for (int64_t i1 = ileft1, i2 = ileft2; i1 <= iright1; ++i1, ++i2) {
-                    if (i1 < 0 || i1 >= n || i2 < 0 || i2 >= n) continue;
-                    const double a1 = x[i1], a2 = x[i2];
-                    norm1 += a1 * a1; norm2 += a2 * a2; prod += a1 * a2;
-                    lp = fmax(lp, fabs(a2));
-                }
-            }
-        }
-        const double rr = prod != 0.0 ? prod / sqrt(norm1 * norm2) : 0.0;
-        const int cnt = (int)((l2max - b + 1) < 64 ? (l2max - b + 1) : 64);
-        // Praat's scan (r1 = r2; r2 = r3; r3 = r[k]; a strictly better r2 that is >= both neighbours wins, the local peak
-        // taken at the step that detects it) for the 64 shifts at once: lane k holds step k's (r1, r2, r3) = (r[k-2], r[k-1],
-        // r[k]) (r2, r3 carry the two last values across batches, zeros in front of the first shift), the winner is the FIRST
-        // lane whose r2 equals the maximum over the qualifying lanes, taken only if it beats the best so far
-        const double up1 = __shfl_up(rr, 1, 64), up2 = __shfl_up(rr, 2, 64);
-        const double s2 = lane == 0 ? r3 : up1;
-        const double s1 = lane == 0 ? r2 : (lane == 1 ? r3 : up2);
-        const bool ok = lane < cnt && s2 >= s1 && s2 >= rr;
-        const double m = wave_max_dpp(ok ? s2 : -INFINITY);
-        if (m > best) {
-            const int kw = __ffsll((long long)__ballot(ok && s2 == m)) - 1;
-            best = m;
-            r1b = readlane_f64(s1, kw); r3b = readlane_f64(rr, kw);
-            if (interior) {                                        // local peak of the detecting step's shifted window
-                const int ok_ = (int)(b - l2min) + kw;
-                double mx = 0.0;
-                for (int i = lane; i < wlen; i += 64) mx = fmax(mx, fabs((double)ps2[ok_ + i]));
-                pk = wave_max_dpp(mx);
-            } else {
-                pk = readlane_f64(lp, kw);
-            }
-            ir = (double)(b + kw - 1);
-        }
-        const double last = readlane_f64(rr, cnt - 1);
-        r2 = cnt >= 2 ? readlane_f64(rr, cnt - 2) : r3;
-        r3 = last;
-    }
-    (void)r1;
-    *peak = pk;
-    *tout = t1;
-    if (best > -1.0) {
-        const double d2r = 2.0 * best - r1b - r3b;
-        if (d2r != 0.0) { const double dr = 0.5 * (r3b - r1b); best += 0.5 * dr * dr / d2r; ir += dr / d2r; }
-        *tout = t1 + (ir - (double)ileft1) * DXS;
-    }
-    return best;
-}
-
-__device__ double find_extremum_wave(const float* __restrict__ x, int n, double x1, double tmin, double tmax, int lane) {
-    int64_t imin = low_index(tmin, x1), imax = high_index(tmax, x1);
-    imin = imin < 0 ? 0 : imin;
-    imax = imax > n - 1 ? n - 1 : imax;
-    const int cnt = (int)(imax - imin + 1);
-    if (cnt <= 0) return 0.5 * (tmin + tmax);
-    double ie;
-    if (cnt == 1) ie = 1.0;
-    else if (cnt == 2) {
-        const double a = fabs((double)x[imin]), b = fabs((double)x[imin + 1]);
-        ie = a > b ? 1.0 : (a < b ? 2.0 : 1.5);
-    } else {
-        // first minimum / first maximum (strict comparisons in index order) via (value, index) reductions
-        double mn = INFINITY, mx = -INFINITY;
-        int jmn = 0x7fffffff, jmx = 0x7fffffff;
-        for (int j = lane; j < cnt; j += 64) {
-            const double v = x[imin + j];
-            if (v < mn) { mn = v; jmn = j; }
-            if (v > mx) { mx = v; jmx = j; }
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double omn = __shfl_xor(mn, o, 64), omx = __shfl_xor(mx, o, 64);
-            const int ojmn = __shfl_xor(jmn, o, 64), ojmx = __shfl_xor(jmx, o, 64);
-            if (omn < mn || (omn == mn && ojmn < jmn)) { mn = omn; jmn = ojmn; }
-            if (omx > mx || (omx == mx && ojmx < jmx)) { mx = omx; jmx = ojmx; }
-        }
-        if (mn == mx) ie = 0.5 * (cnt + 1.0);
-        else {
-            const int j = fabs(mn) > fabs(mx) ? jmn : jmx;
-            if (j == 0) ie = 1.0;
-            else if (j == cnt - 1) ie = (double)cnt;
-            else {
-                const double vm = x[imin + j], vl = x[imin + j - 1], vr = x[imin + j + 1];
-                ie = (j + 1) + 0.5 * (vr - vl) / (2.0 * vm - vl - vr);
-            }
-        }
-    }
-    return x1 + ((double)imin + ie - 1.0) * DXS;
-}
-
-// ---- Sound & Pitch: To PointProcess (cc) -------------------------------------------------------------------
-// Praat walks the voiced stretches one after the other; inside a stretch the pulses are found one by one (each
-// search starts at the previous pulse), but the stretches only interact through `added_right` (the last pulse
-// added while walking right), which merely vetoes left-going pulses of later stretches.  So: (1) one wave per
-// clip lists the stretches, (2) one wave per stretch walks it and records its pulses with their veto margins,
-// (3) one wave per clip applies the vetoes in order and writes the pulses in ascending time.
-struct Stretch { int il, irr, off, pad; };      // frame range, first slot of the stretch in the per-clip scratch
-
-__device__ __forceinline__ bool voiced_at(const double* f, int nF, double ceiling, int i) {
-    return i >= 0 && i < nF && f[i] > 0.0 && f[i] < ceiling;
-}
-
-// 256 threads: all four waves scan the samples for the absolute peak (a single wave took 7 500 dependent-ish rounds over a
-// 30 s clip: most of this kernel's 3.2 ms), wave 0 then lists the stretches.
-__global__ __launch_bounds__(256) void pulse_stretches_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ pci,
-                                                              const double* __restrict__ sel_freq, double pdt, double ceiling,
-                                                              Stretch* __restrict__ st, int max_st, int* __restrict__ n_st,
-                                                              double* __restrict__ abs_peak) {
-    __shared__ float s_pk[4];
-    const ClipInfo c = pci[blockIdx.x];
-    const int lane = threadIdx.x & 63, nF = c.n_frames;
-    {   // Vector_getAbsoluteExtremum of the whole sound (no mean subtraction, unlike the pitch analysis)
-        const float* x = wav + c.sample_off;
-        float gp = 0.0f;                                      // |x| of float samples: exact in float
-        const int n4 = c.n_samples >> 2;
-        const bool al = (reinterpret_cast<uintptr_t>(x) & 15) == 0;   // 16-byte loads when the clip's first sample is 16-byte aligned
-                                                                      // (the address itself: `wav` may be any float*, e.g. a sliced view)
-        if (al) {
-            const float4* x4 = reinterpret_cast<const float4*>(x);
-            for (int i = threadIdx.x; i < n4; i += 256) {
-                const float4 v = x4[i];
-                gp = fmaxf(fmaxf(gp, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-            }
-            for (int i = 4 * n4 + threadIdx.x; i < c.n_samples; i += 256) gp = fmaxf(gp, fabsf(x[i]));
-        } else {
-            for (int i = threadIdx.x; i < c.n_samples; i += 256) gp = fmaxf(gp, fabsf(x[i]));
-        }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) gp = fmaxf(gp, __shfl_xor(gp, o, 64));
-        if (lane == 0) s_pk[threadIdx.x >> 6] = gp;
-        __syncthreads();
-        if (threadIdx.x == 0) abs_peak[blockIdx.x] = (double)fmaxf(fmaxf(s_pk[0], s_pk[1]), fmaxf(s_pk[2], s_pk[3]));
-        if (threadIdx.x >= 64) return;
-    }
-    const double* f = sel_freq + c.frame_off;
-    Stretch* S = st + (int64_t)blockIdx.x * max_st;
-    int count = 0;
-    for (int base = 0; base < nF; base += 64) {
-        const int i = base + lane;
-        const bool v = voiced_at(f, nF, ceiling, i);
-        const bool start = v && !voiced_at(f, nF, ceiling, i - 1), end = v && !voiced_at(f, nF, ceiling, i + 1);
-        const unsigned long long ms = __ballot(start);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (start) { const int k = count + __popcll(ms & below); if (k < max_st) S[k].il = i; }
-        if (end) {
-            // the stretch that ends here is the last one started at or before this frame
-            const int k = count + __popcll(ms & (below | (1ull << lane))) - 1;
-            if (k >= 0 && k < max_st) S[k].irr = i;
-        }
-        count += __popcll(ms);
-    }
-    count = count < max_st ? count : max_st;
-    __threadfence_block();
-    // scratch slots: a stretch of n frames holds at most n*pdt*ceiling/0.8 + 3 pulses on either side
-    int run = 0;
-    for (int base = 0; base < count; base += 64) {
-        const int k = base + lane;
-        int cap = 0;
-        if (k < count) cap = (int)((double)(S[k].irr - S[k].il + 1) * pdt * ceiling * 1.25) + 4;
-        int inc = cap;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int t2 = __shfl_up(inc, o, 64); if (lane >= o) inc += t2; }
-        if (k < count) { S[k].off = run + inc - cap; S[k].pad = cap; }
-        run += __shfl(inc, 63, 64);
-    }
-    if (lane == 0) n_st[blockIdx.x] = count;
-}
-
-// scratch per clip: left[slot] = (time, veto margin 0.8/f0) in walking order (entry 0 = the middle pulse),
-// right[slot] = time; counts[stretch] = (n_left, n_right)
-__global__ __launch_bounds__(256) void pulse_walk_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ pci,
-                                                         const double* __restrict__ sel_freq, double pdt, double ceiling,
-                                                         const double* __restrict__ abs_peak, const Stretch* __restrict__ st,
-                                                         int max_st, const int* __restrict__ n_st, double2* __restrict__ left,
-                                                         double* __restrict__ right, int cap_slots, int2* __restrict__ counts) {
-    __shared__ float s_ps[4][PULSE_LDS];
-    __shared__ double s_fw[4][PULSE_FW];                       // sliding window of the pitch track (the walk reads it once per pulse)
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int clip = blockIdx.y, k = blockIdx.x * 4 + wv;
-    if (k >= n_st[clip]) return;
-    float* pwin = s_ps[wv];
-    int64_t win0 = INT64_MIN;
-    const ClipInfo c = pci[clip];
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples, nF = c.n_frames;
-    const double* f = sel_freq + c.frame_off;
-    const Stretch S = st[(int64_t)clip * max_st + k];
-    double2* L = left + (int64_t)clip * cap_slots + S.off;
-    double* R = right + (int64_t)clip * cap_slots + S.off;
-    const int cap = S.pad;
-    double* fw = s_fw[wv];
-    int fw0 = -(1 << 30);                                     // frame index of fw[0]; far away = empty
-    // Pitch "Get value at time" (pitch_value_at) on the LDS window: the two frames around t, refilled when the walk leaves it
-    auto f0_at = [&](double t, int dir) -> double {
-        const double qn = __longlong_as_double(0x7ff8000000000000LL);
-        if (nF <= 0) return qn;
-        const double ireal = (t - c.t1) / pdt;
-        const int64_t ileft = (int64_t)floor(ireal);
-        double phase = ireal - (double)ileft;
-        int64_t inear, ifar;
-        if (phase < 0.5) { inear = ileft; ifar = ileft + 1; } else { inear = ileft + 1; ifar = ileft; phase = 1.0 - phase; }
-        if (inear < 0 || inear >= nF) return qn;
-        const int64_t lo = ileft, hi = ileft + 1;              // both frames (either may lie outside the track: read as 0)
-        if (lo < fw0 || hi >= fw0 + PULSE_FW) {
-            const int64_t w0 = dir < 0 ? hi - (PULSE_FW - 1) : lo;
-            __builtin_amdgcn_wave_barrier();
-            for (int i = lane; i < PULSE_FW; i += 64) { const int64_t j = w0 + i; fw[i] = (j >= 0 && j < nF) ? f[j] : 0.0; }
-            fw0 = (int)w0;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        const double fn = fw[inear - fw0];
-        if (!(fn > 0.0 && fn < ceiling)) return qn;
-        if (ifar < 0 || ifar >= nF) return fn;
-        const double ff = fw[ifar - fw0];
-        if (!(ff > 0.0 && ff < ceiling)) return fn;
-        return fn + phase * (ff - fn);
-    };
-    const double duration = c.xmax;                          // Pitch_getVoicedIntervalAfter works on the Pitch's domain = the sound's
-    const double gp = abs_peak[clip];
-    int nl = 0, nr = 0;
-    double tleft = c.t1 + S.il * pdt - 0.5 * pdt, tright = c.t1 + S.irr * pdt + 0.5 * pdt;
-    bool skip = tleft >= duration - 0.5 * pdt;               // Praat stops here; every later stretch starts even later
-    tleft = tleft < 0.0 ? 0.0 : tleft;
-    tright = tright > duration ? duration : tright;
-    const double tmid = 0.5 * (tleft + tright);
-    const double f0mid = pitch_value_at(f, nF, c.t1, pdt, ceiling, tmid);
-    if (!(f0mid == f0mid)) skip = true;
-    if (!skip) {
-        double tmax = find_extremum_wave(x, n, c.x1, tmid - 0.5 / f0mid, tmid + 0.5 / f0mid, lane);
-        if (lane == 0) L[0] = make_double2(tmax, 0.0);
-        nl = 1;
-        const double tsave = tmax;
-        for (int g2 = 0; g2 < 200000; ++g2) {                      // to the left
-            const double f0 = f0_at(tmax, -1);
-            if (!(f0 == f0)) break;
-            double peak, tout;
-            const double corr = max_correlation_wave(x, n, c.x1, tmax, 1.0 / f0, tmax - 1.25 / f0, tmax - 0.8 / f0, lane, &tout, &peak, pwin, &win0, -1);
-            tmax = tout;
-            if (corr == -1.0) tmax -= 1.0 / f0;
-            if (tmax < tleft) {
-                if (corr > 0.7 && peak > 0.023333 * gp && nl < cap) { if (lane == 0) L[nl] = make_double2(tmax, 0.8 / f0); ++nl; }
-                break;
-            }
-            if (corr > 0.3 && (peak == 0.0 || peak > 0.01 * gp) && nl < cap) { if (lane == 0) L[nl] = make_double2(tmax, 0.8 / f0); ++nl; }
-        }
-        tmax = tsave;
-        for (int g2 = 0; g2 < 200000; ++g2) {                      // to the right
-            const double f0 = f0_at(tmax, +1);
-            if (!(f0 == f0)) break;
-            double peak, tout;
-            const double corr = max_correlation_wave(x, n, c.x1, tmax, 1.0 / f0, tmax + 0.8 / f0, tmax + 1.25 / f0, lane, &tout, &peak, pwin, &win0, +1);
-            tmax = tout;
-            if (corr == -1.0) tmax += 1.0 / f0;
-            if (tmax > tright) {
-                if (corr > 0.7 && peak > 0.023333 * gp && nr < cap) { if (lane == 0) R[nr] = tmax; ++nr; }
-                break;
-            }
-            if (corr > 0.3 && (peak == 0.0 || peak > 0.01 * gp) && nr < cap) { if (lane == 0) R[nr] = tmax; ++nr; }
-        }
-    }
-    if (lane == 0) counts[(int64_t)clip * max_st + k] = make_int2(nl, nr);
-}
-
-__global__ __launch_bounds__(64) void pulse_merge_kernel(const Stretch* __restrict__ st, int max_st, const int* __restrict__ n_st,
-                                                         const double2* __restrict__ left, const double* __restrict__ right,
-                                                         int cap_slots, const int2* __restrict__ counts,
-                                                         double* __restrict__ pulses, int max_pulses, int* __restrict__ n_pulses) {
-    const int clip = blockIdx.x, lane = threadIdx.x;
-    const int ns = n_st[clip];
-    double* pts = pulses + (int64_t)clip * max_pulses;
-    int np_ = 0;
-    double added_right = -1e308;
-    for (int k = 0; k < ns; ++k) {
-        const Stretch S = st[(int64_t)clip * max_st + k];
-        const int2 cn = counts[(int64_t)clip * max_st + k];
-        const double2* L = left + (int64_t)clip * cap_slots + S.off;
-        const double* R = right + (int64_t)clip * cap_slots + S.off;
-        if (cn.x <= 0) continue;
-        // left-going pulses in ascending time = walking order reversed; entry 0 (the middle pulse) is never vetoed
-        for (int base = cn.x - 1; base >= 1; base -= 64) {
-            const int i = base - lane;
-            bool keep = false;
-            double t = 0.0;
-            if (i >= 1) { const double2 e = L[i]; t = e.x; keep = t - added_right > e.y; }
-            const unsigned long long m = __ballot(keep);
-            const int pos = np_ + __popcll(m & ((1ull << lane) - 1ull));
-            if (keep && pos < max_pulses) pts[pos] = t;
-            np_ += __popcll(m);
-        }
-        if (np_ < max_pulses && lane == 0) pts[np_] = L[0].x;
-        ++np_;
-        for (int base = 0; base < cn.y; base += 64) {
-            const int i = base + lane;
-            if (i < cn.y && np_ + i < max_pulses) pts[np_ + i] = R[i];
-        }
-        if (cn.y > 0) added_right = R[cn.y - 1];
-        np_ += cn.y;
-    }
-    if (lane == 0) n_pulses[clip] = np_ < max_pulses ? np_ : max_pulses;
-}
-
-// ---- Ltas (pitch-corrected) -> "Get slope" and robust tilt (src/mshds_extractor.py:227-251) ---------------
-// One workgroup per clip; every wave takes every fourth pulse.  A pulse whose two neighbouring intervals are
-// plausible periods contributes the energy spectrum of the one period around it: a DFT of exactly that many
-// samples (lane = frequency bin, rotation recurrence over the samples), binned into 100 Hz bands.
-// Per-wave band sums are combined in a fixed order, so the result does not depend on scheduling.
-constexpr int LTAS_NB = 50;            // maximum frequency 5000 Hz / bandwidth 100 Hz
-constexpr double LTAS_BW = 100.0;
-constexpr int LTAS_MAXN = 1024;        // samples of one period that fit the LDS staging (longest period 20 ms = 320)
-
-__device__ double ltas_mean_rect(const double* z, int nx, double x1, double dx, double xmin, double xmax) {
-    const double qn = __longlong_as_double(0x7ff8000000000000LL);
-    xmin = fmax(xmin, x1 - 0.5 * dx);
-    xmax = fmin(xmax, x1 + (nx - 0.5) * dx);
-    if (!(xmin < xmax)) return qn;
-    const double rimin = (xmin - x1) / dx + 1.0, rimax = (xmax - x1) / dx + 1.0;
-    double total = 0.0, rng = 0.0;
-    if (rimax >= 0.5 && rimin < nx + 0.5) {
-        const int imin = rimin < 0.5 ? 0 : (int)floor(rimin + 0.5);
-        const int imax = rimax >= nx + 0.5 ? nx + 1 : (int)floor(rimax + 0.5);
-        for (int i = imin + 1; i < imax; ++i) { rng += 1.0; total += z[i - 1]; }
-        if (imin == imax) {
-            if (imin >= 1 && imin <= nx) { const double ph = rimax - rimin; rng += ph; total += ph * z[imin - 1]; }
-        } else {
-            if (imin >= 1) { const double ph = imin - rimin + 0.5; rng += ph; total += ph * z[imin - 1]; }
-            if (imax <= nx) { const double ph = rimax - imax + 0.5; rng += ph; total += ph * z[imax - 1]; }
-        }
-    }
-    return rng > 0.0 ? total / rng : qn;
-}
-
-__global__ __launch_bounds__(256) void ltas_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
-                                                   const double* __restrict__ pulses, int max_pulses,
-                                                   const int* __restrict__ n_pulses, double shortest, double longest,
-                                                   double max_factor, double* __restrict__ out) {
-    __shared__ double s_energy[4][LTAS_NB], s_count[4][LTAS_NB], s_z[LTAS_NB], s_slopes[LTAS_NB];
-    __shared__ float s_x[4][LTAS_MAXN];
-    __shared__ int s_periods[4], s_fail[4];
-    const ClipInfo c = ci[blockIdx.x];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples;
-    const double* pts = pulses + (int64_t)blockIdx.x * max_pulses;
-    const int np_ = n_pulses[blockIdx.x];
-    const double qn = __longlong_as_double(0x7ff8000000000000LL);
-    for (int b = lane; b < LTAS_NB; b += 64) { s_energy[wv][b] = 0.0; s_count[wv][b] = 0.0; }
-    int periods = 0, fail = 0;
-    for (int ip = 1 + wv; ip < np_ - 1; ip += 4) {
-        const double tl = pts[ip - 1], tm = pts[ip], tr = pts[ip + 1];
-        const double left = tm - tl, right = tr - tm;
-        const double factor = left > right ? left / right : right / left;
-        if (!(left >= shortest && left <= longest && right >= shortest && right <= longest && factor <= max_factor)) continue;
-        const double t1 = tm - 0.5 * left, t2 = tm + 0.5 * right;
-        const int64_t ix1 = (int64_t)ceil((t1 - c.x1) / DXS), ix2 = (int64_t)floor((t2 - c.x1) / DXS);   // Sound_extractPart
-        if (ix2 < ix1 || ix2 - ix1 + 1 > LTAS_MAXN) { fail = 1; continue; }   // Praat: "no samples" aborts the analysis
-        const int m = (int)(ix2 - ix1 + 1);
-        for (int j = lane; j < m; j += 64) { const int64_t i = ix1 + j; s_x[wv][j] = (i >= 0 && i < n) ? x[i] : 0.0f; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        const double sdx = 1.0 / (DXS * m);
-        const int nfreq = m / 2 + 1;
-        // bins k = 1 .. nfreq-1 whose band ceil(k*sdx/100) is within 1..50 (k = 0 falls into band 0)
-        for (int kb = 1; kb < nfreq; kb += 64) {
-            const int k = kb + lane;
-            const double freq = k * sdx;
-            int band = (int)ceil(freq / LTAS_BW);
-            const bool on = k < nfreq && band >= 1 && band <= LTAS_NB;
-            double e = 0.0;
-            if (__any(on)) {
-                // sum_j x_j exp(-2 pi i k j / m): rotate (c, s) by the bin's angle, which lies in (0, pi]
-                const double th = 2.0 * PI * (double)(k < nfreq ? k : 0) / (double)m;
-                const double C = cos_0_pi(th), S = sin_0_pi(th);
-                double cr = 1.0, sr = 0.0, re = 0.0, im = 0.0;
-                for (int j = 0; j < m; ++j) {
-                    const double v = s_x[wv][j];
-                    re += v * cr; im -= v * sr;
-                    const double c2 = cr * C - sr * S;
-                    sr = sr * C + cr * S;
-                    cr = c2;
-                }
-                re *= DXS; im *= DXS;
-                e = (re * re + im * im) * 2.0 * sdx;
-            }
-            if (!on) { band = -1 - lane; e = 0.0; }
-            // bands are non-decreasing in k: the first lane of a run adds the whole run (<= 4 bins per band)
-            const int bprev = __shfl_up(band, 1, 64);
-            const bool head = on && (lane == 0 || bprev != band);
-            double sum = e, cnt = 1.0;
-#pragma unroll
-            for (int d = 1; d <= 7; ++d) {
-                const int bn = __shfl_down(band, d, 64);
-                const double en = __shfl_down(e, d, 64);
-                if (lane + d < 64 && bn == band) { sum += en; cnt += 1.0; }
-            }
-            // a run can continue in the next 64-bin round: LDS accumulation below handles that (same wave, ordered)
-            if (head) { s_energy[wv][band - 1] += sum; s_count[wv][band - 1] += cnt; }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        }
-        ++periods;
-    }
-    if (lane == 0) { s_periods[wv] = periods; s_fail[wv] = fail; }
-    __syncthreads();
-    if (tid == 0) {
-        const int total_periods = s_periods[0] + s_periods[1] + s_periods[2] + s_periods[3];
-        const int failed = s_fail[0] | s_fail[1] | s_fail[2] | s_fail[3];
-        double slope = qn, tilt = qn;
-        if (np_ - 2 >= 1 && total_periods >= 1 && !failed) {
-            double total = 0.0;
-            for (int b = 0; b < LTAS_NB; ++b) {
-                s_energy[0][b] = (s_energy[0][b] + s_energy[1][b]) + (s_energy[2][b] + s_energy[3][b]);
-                s_count[0][b] = (s_count[0][b] + s_count[1][b]) + (s_count[2][b] + s_count[3][b]);
-                total += s_count[0][b];
-            }
-            const double duration = c.xmax;                      // PointProcess_Sound_to_Ltas divides by sound->xmax - sound->xmin
-            bool any = false;
-            for (int b = 0; b < LTAS_NB; ++b) {
-                if (s_count[0][b] > 0.0) {
-                    const double mean_e = s_energy[0][b] / s_count[0][b];
-                    s_z[b] = 10.0 * log10(mean_e * (total / LTAS_NB) / LTAS_BW / duration / 4.0e-10);
-                    any = true;
-                } else {
-                    s_z[b] = qn;
-                }
-            }
-            if (any) {
-                for (int b = 0; b < LTAS_NB; ++b) s_slopes[b] = s_z[b];     // defined values before filling
-                for (int b = 0; b < LTAS_NB; ++b) {
-                    if (s_slopes[b] == s_slopes[b]) continue;
-                    int bl = b - 1, br = b + 1;
-                    while (bl >= 0 && !(s_slopes[bl] == s_slopes[bl])) --bl;
-                    while (br < LTAS_NB && !(s_slopes[br] == s_slopes[br])) ++br;
-                    if (bl < 0) s_z[b] = s_slopes[br];
-                    else if (br >= LTAS_NB) s_z[b] = s_slopes[bl];
-                    else s_z[b] = ((br - b) * s_slopes[bl] + (b - bl) * s_slopes[br]) / (double)(br - bl);
-                }
-                const double x1 = 0.5 * LTAS_BW;
-                const double low = ltas_mean_rect(s_z, LTAS_NB, x1, LTAS_BW, 50.0, 1000.0);
-                const double high = ltas_mean_rect(s_z, LTAS_NB, x1, LTAS_BW, 1000.0, 4000.0);
-                slope = high - low;
-                // Theil's incomplete method over the bands centred in [100, 5000] Hz
-                int imin = 1 + (int)ceil((100.0 - x1) / LTAS_BW), imax = 1 + (int)floor((5000.0 - x1) / LTAS_BW);
-                imin = imin < 1 ? 1 : imin;
-                imax = imax > LTAS_NB ? LTAS_NB : imax;
-                const int cntp = imax - imin + 1, nc = cntp / 2, n2 = (cntp & 1) ? nc + 1 : nc;
-                for (int i = 0; i < nc; ++i) {
-                    const double xa = x1 + (imin - 1 + i) * LTAS_BW, xb = x1 + (imin - 1 + n2 + i) * LTAS_BW;
-                    s_slopes[i] = (s_z[imin - 1 + n2 + i] - s_z[imin - 1 + i]) / (xb - xa);
-                }
-                for (int i = 1; i < nc; ++i) {                              // insertion sort (<= 24 values)
-                    const double v = s_slopes[i];
-                    int j = i - 1;
-                    while (j >= 0 && s_slopes[j] > v) { s_slopes[j + 1] = s_slopes[j]; --j; }
-                    s_slopes[j + 1] = v;
-                }
-                if (nc >= 1) {                                              // NUMquantile(0.5)
-                    if (nc == 1) tilt = s_slopes[0];
-                    else {
-                        const double place = 0.5 * nc + 0.5;
-                        int lf = (int)floor(place);
-                        lf = lf < 1 ? 1 : (lf > nc - 1 ? nc - 1 : lf);
-                        tilt = s_slopes[lf] == s_slopes[lf - 1] ? s_slopes[lf - 1]
-                                                                  : s_slopes[lf - 1] + (place - lf) * (s_slopes[lf] - s_slopes[lf - 1]);
-                    }
-                } else {
-                    slope = qn;                                             // the tilt report fails -> both NaN (:250-251)
-                }
-            }
-        }
-        out[2 * blockIdx.x] = slope;
-        out[2 * blockIdx.x + 1] = tilt;
-    }
-}
-
-// ---- _measureFormants statistics: F1, B1, F2, B2 linearly interpolated at every pulse ------------------------
-__global__ __launch_bounds__(64) void formant_stats_kernel(const FormantFrame* __restrict__ ff, const ClipInfo* __restrict__ fci,
-                                                           double fdt, const double* __restrict__ pulses, int max_pulses,
-                                                           const int* __restrict__ n_pulses, double* __restrict__ out) {
-    const ClipInfo c = fci[blockIdx.x];
-    const int lane = threadIdx.x, np_ = n_pulses[blockIdx.x], nF = c.n_frames;
-    const FormantFrame* F = ff + c.frame_off;
-    const double* pts = pulses + (int64_t)blockIdx.x * max_pulses;
-    const double qn = __longlong_as_double(0x7ff8000000000000LL);
-    double cnt[4] = {0, 0, 0, 0}, sum[4] = {0, 0, 0, 0};
-    auto value = [&](int k, double t) -> double {      // k: 0 F1, 1 B1, 2 F2, 3 B2
-        if (nF <= 0) return qn;
-        const double ireal = (t - c.t1) / fdt;
-        const int64_t ileft = (int64_t)floor(ireal);
-        double phase = ireal - (double)ileft;
-        int64_t inear, ifar;
-        if (phase < 0.5) { inear = ileft; ifar = ileft + 1; } else { inear = ileft + 1; ifar = ileft; phase = 1.0 - phase; }
-        if (inear < 0 || inear >= nF) return qn;
-        const int fi = k >> 1;
-        const double vn = (k & 1) ? F[inear].b[fi] : F[inear].f[fi];
-        if (!(vn == vn)) return qn;
-        if (ifar < 0 || ifar >= nF) return vn;
-        const double vf = (k & 1) ? F[ifar].b[fi] : F[ifar].f[fi];
-        if (!(vf == vf)) return vn;
-        return vn + phase * (vf - vn);
-    };
-    for (int i = lane; i < np_; i += 64)
-        for (int k = 0; k < 4; ++k) { const double v = value(k, pts[i]); if (v == v) { cnt[k] += 1; sum[k] += v; } }
-    double mean[4];
-    for (int k = 0; k < 4; ++k) { cnt[k] = wave_sum_f64(cnt[k]); sum[k] = wave_sum_f64(sum[k]); mean[k] = cnt[k] > 0 ? sum[k] / cnt[k] : qn; }
-    double sq[4] = {0, 0, 0, 0};
-    for (int i = lane; i < np_; i += 64)
-        for (int k = 0; k < 4; ++k) { const double v = value(k, pts[i]); if (v == v) { const double d = v - mean[k]; sq[k] += d * d; } }
-    for (int k = 0; k < 4; ++k) sq[k] = wave_sum_f64(sq[k]);
-    if (lane == 0)
-        for (int k = 0; k < 4; ++k) {
-            out[blockIdx.x * 8 + 2 * k] = mean[k];
-            out[blockIdx.x * 8 + 2 * k + 1] = cnt[k] > 1 ? sqrt(sq[k] / (cnt[k] - 1)) : qn;
-        }
-}
-
 }  // namespace mshds
 }  // namespace rsaf
 
@@ -3467,6 +2336,10 @@ int rsaf_mshds_intensity(const float* wav, const void* clip_info, int n_clips, i
     return RSAF_OK;
 }
 
+}  // extern "C"
+
+// ---- the pitch analysis on the host (C++ linkage: its launch helpers are templates) ---------------------------------
+
 // W_N^k = exp(-2 pi i k / N), k < N / 2, in double precision (host libm), one table per (device, N), kept for the
 // life of the process (the pitch correlation kernels)
 static int fft_twiddles(int N, const double** out) {
@@ -3493,34 +2366,90 @@ static int fft_twiddles(int N, const double** out) {
     return RSAF_OK;
 }
 
-// second_*: optional outputs of the same analysis with another voicing threshold (h2_voicing_thr >= 0): the frame
-// kernel shares the correlation and the refinement, the path finder runs once per threshold
+// one PitchPlan per call (checks + geometry), then one function per launch family
+
+// the 18 doubles of params_host (include/rsaf.h; filled by mshds.py MshdsEngine.pitch)
+enum PitchSlot {
+    PS_DT, PS_MIN_PITCH, PS_CEILING, PS_VOICING_THR, PS_OCTAVE_COST, PS_SILENCE_THR, PS_OCTAVE_JUMP, PS_VUV,
+    PS_NSAMP_WINDOW, PS_NSAMP_PERIOD, PS_MIN_LAG, PS_MAX_LAG, PS_BRENT_IXMAX, PS_MAX_CAND, PS_REFINE_DEPTH, PS_IS_CC,
+    PS_DT_WINDOW,
+    PS_TABLE_MODE,      // 0: shared Chebyshev table only, 1: + the tables of the clipped depths, 2: one table per cell
+};
+
+// lags 0 .. L of a stored correlation row: max_lag of a cross-correlation, brent_ixmax of an autocorrelation
+static int pitch_row_lags(const double* h) { return (int)h[PS_IS_CC] ? (int)h[PS_MAX_LAG] : (int)h[PS_BRENT_IXMAX]; }
+
 // workspace per frame: the correlation row, the coefficient blocks of two candidate lists, the frame record
 static inline int64_t pitch_ws_bytes_per_frame(int rstride) {
     return (int64_t)rstride * (int64_t)sizeof(double) + 2 * (int64_t)PC_DOUBLES * (int64_t)sizeof(double) + (int64_t)HDR_INTS * (int64_t)sizeof(int);
 }
 
-static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int max_frames, const double* gpeak,
-                      const double* window, const double* window_r, const double* params_host, void* frame_out,
-                      unsigned char* psi, int* end_state, double* sel_freq, double* sel_strength, double* stats_out,
-                      double voicing_thr2, void* frame_out2, unsigned char* psi2, int* end_state2, double* sel_freq2,
-                      double* sel_strength2, double* stats_out2, const double* sinc_cheb, void* workspace,
-                      int64_t workspace_bytes, rsaf_stream_t stream) {
+struct PitchCall {      // what the two entries share
+    const float* wav;
+    const ClipInfo* ci;
+    int n_clips, max_frames;
+    const double* gpeak;
+    const double *window, *window_r, *sinc_cheb;
+    double* workspace;
+    int64_t workspace_bytes;
+    hipStream_t stream;
+};
+
+// the outputs of one voicing threshold.  A dual call has two: the frame kernels share the correlation and the
+// refinement, the path finder runs once per threshold
+struct PitchOutputs {
+    FrameOut* frame_out;
+    unsigned char* psi;
+    int* end_state;
+    double *sel_freq, *sel_strength, *stats;
+    bool complete() const { return frame_out && psi && end_state && sel_freq && sel_strength && stats; }
+};
+
+struct PitchPlan {
+    PitchParams P;
+    double silence_thr, octave_jump, vuv;   // the path finder's costs
+    bool dual;
+    int seg_len, Lr, rstride;               // samples a frame reads; lags 0 .. Lr of a row; doubles per row (+ the relative intensity)
+    int ncc, log2m, log2n;                  // CC: complex FFT length; AC: nfft = 2^(log2m + 1); CC: ncc = 2^log2n before padding
+    // correlation mode: one wave per frame with S = 64 wave_r complex points (AC: 8 / 16 / 32, CC: 16 / 32), or
+    // wave_r = 0: the 4 096-point cross-correlation on the workgroup kernel pitch_cc_kernel<12>
+    int wave_r;
+    size_t lds_corr, lds_cand, lds_cell;    // workgroup correlation kernel, candidate kernel, per-cell coefficient kernel
+    int cell_b_lo, cell_n_b, cell_ntap_pad; // per-cell tables (mshds.sinc_cell_tables): cells b_lo .. b_lo + n_b - 1, padded taps
+    bool defer;                             // refinement in its own kernels (false: RSAF_PITCH_INKERNEL, the tests' A/B reference)
+    bool grouped;                           // ... with the coefficients built per cell by pitch_cell_coef_kernel
+    const double* cheb;                     // table of the candidate kernel's Chebyshev form; nullptr: direct sinc sums
+    int group;                              // clips per pass through the workspace
+    double corr_flops, corr_lds;            // ProfScope models of the correlation kernel, per frame
+};
+
+// grid of pitch_cell_coef_kernel over `gframes` frames: a workgroup per (cell, chunk of frames), the chunks dealt in eights
+constexpr int CELL_CHUNK_FRAMES = 4096;
+static int64_t cell_workgroups(const PitchPlan& pl, int64_t gframes, int* n_chunks_out) {
+    const int64_t n_chunks = (gframes + CELL_CHUNK_FRAMES - 1) / CELL_CHUNK_FRAMES;
+    if (n_chunks_out) *n_chunks_out = (int)n_chunks;
+    return 8 * (int64_t)pl.cell_n_b * ((n_chunks + 7) / 8);
+}
+
+// Every argument check and the geometry of a call; makes no HIP call. n_clips == 0 leaves the plan unset (nothing to run).
+static int pitch_plan(const PitchCall& c, const double* h, const PitchOutputs& o1, const PitchOutputs& o2,
+                      double voicing_thr2, PitchPlan* plan) {
+    PitchPlan& pl = *plan;
+    PitchParams& P = pl.P;
+    const int n_clips = c.n_clips, max_frames = c.max_frames;
     RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_frames >= 0, "bad clip/frame count");
     if (n_clips == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(wav && clip_info && gpeak && params_host && frame_out && psi && end_state && sel_freq &&
-                   sel_strength && stats_out, "NULL pointer");
-    const bool dual = voicing_thr2 >= 0.0;
-    RSAF_CHECK_ARG(!dual || (frame_out2 && psi2 && end_state2 && sel_freq2 && sel_strength2 && stats_out2),
-                   "NULL pointer (second threshold outputs)");
-    const double* h = params_host;
-    PitchParams P;
-    P.dt = h[0]; P.min_pitch = h[1]; P.ceiling = h[2]; P.voicing_thr = h[3]; P.octave_cost = h[4];
-    const double silence_thr = h[5], octave_jump = h[6], vuv = h[7];
-    P.nsamp_window = (int)h[8]; P.nsamp_period = (int)h[9]; P.min_lag = (int)h[10]; P.max_lag = (int)h[11];
-    P.brent_ixmax = (int)h[12]; P.max_cand = (int)h[13]; P.refine_depth = (int)h[14]; P.is_cc = (int)h[15];
-    P.dt_window = h[16];
-    const int table_mode = (int)h[17];            // 0: shared table only, 1: + the tables of the clipped depths, 2: one table per cell
+    RSAF_CHECK_ARG(c.wav && c.ci && c.gpeak && h && o1.complete(), "NULL pointer");
+    const bool dual = pl.dual = voicing_thr2 >= 0.0;
+    RSAF_CHECK_ARG(!dual || o2.complete(), "NULL pointer (second threshold outputs)");
+    P.dt = h[PS_DT]; P.min_pitch = h[PS_MIN_PITCH]; P.ceiling = h[PS_CEILING]; P.voicing_thr = h[PS_VOICING_THR];
+    P.octave_cost = h[PS_OCTAVE_COST];
+    pl.silence_thr = h[PS_SILENCE_THR]; pl.octave_jump = h[PS_OCTAVE_JUMP]; pl.vuv = h[PS_VUV];
+    P.nsamp_window = (int)h[PS_NSAMP_WINDOW]; P.nsamp_period = (int)h[PS_NSAMP_PERIOD];
+    P.min_lag = (int)h[PS_MIN_LAG]; P.max_lag = (int)h[PS_MAX_LAG]; P.brent_ixmax = (int)h[PS_BRENT_IXMAX];
+    P.max_cand = (int)h[PS_MAX_CAND]; P.refine_depth = (int)h[PS_REFINE_DEPTH]; P.is_cc = (int)h[PS_IS_CC];
+    P.dt_window = h[PS_DT_WINDOW];
+    const int table_mode = (int)h[PS_TABLE_MODE];
     P.cheb_clipped = table_mode == 1 ? 1 : 0;
     P.voicing_thr2 = dual ? voicing_thr2 : -1.0;
     { const char* e = getenv("RSAF_PITCH_STOP"); P.debug_stop = e ? atoi(e) : 0; }
@@ -3528,226 +2457,266 @@ static int pitch_impl(const float* wav, const void* clip_info, int n_clips, int 
     P.half_period = P.nsamp_period / 2 + 1;
     RSAF_CHECK_ARG(P.max_cand >= 2 && P.max_cand <= MAXC - 1, "max_candidates must be in [2, 15]");
     RSAF_CHECK_ARG(P.nsamp_window >= 4 && P.brent_ixmax >= 2 && P.max_lag >= 2, "window too short");
-    RSAF_CHECK_ARG(P.is_cc || (window && window_r), "AC needs the window tables");
+    RSAF_CHECK_ARG(P.is_cc || (c.window && c.window_r), "AC needs the window tables");
     RSAF_CHECK_ARG((P.is_cc ? P.max_lag : P.brent_ixmax) <= 1023, "more than 1023 lags (pitch floor below ~16 Hz) is not supported");
     P.nfft = 1;                                                    // Praat: while (nsampFFT < nsamp_window * (1 + 0.5)) nsampFFT *= 2
     while ((double)P.nfft < (double)P.nsamp_window * 1.5) P.nfft *= 2;
     if (P.nfft < 16) P.nfft = 16;
     RSAF_CHECK_ARG(P.is_cc || P.nsamp_window + P.brent_ixmax <= P.nfft, "brent_ixmax must not exceed half the analysis window");
-    const int seg_len = P.is_cc ? P.nsamp_window + P.max_lag + 1 : P.nsamp_window;
-    const int Lr = P.is_cc ? P.max_lag : P.brent_ixmax;
-    const int rstride = Lr + 2;                                    // r[0..L] + the frame's relative intensity
+    const int seg_len = pl.seg_len = P.is_cc ? P.nsamp_window + P.max_lag + 1 : P.nsamp_window;
+    const int Lr = pl.Lr = pitch_row_lags(h);
+    pl.rstride = Lr + 2;                                           // r[0..L] + the frame's relative intensity
     int ncc = 64;                                                  // CC: complex FFT length, >= nw + max_lag + 1
     while (ncc < seg_len) ncc *= 2;
     RSAF_CHECK_ARG(!P.is_cc || ncc <= 4096, "cross-correlation window + lag range longer than 4 095 samples is not supported");
     RSAF_CHECK_ARG(P.is_cc || P.nfft <= 4096, "autocorrelation window longer than 2 730 samples is not supported");
     // the workgroup cross-correlation kernel: two complex buffers + sumy2 + scratch
-    const size_t lds_corr = P.is_cc ? (size_t)ncc * 2 * 2 * sizeof(double) + (size_t)(((Lr + 2) & ~1) + 32) * sizeof(double) : 0;
-    // in-kernel refinement (the form before the refinement kernels existed): the A/B reference of the tests
-    const bool defer = getenv("RSAF_PITCH_INKERNEL") == nullptr;
-    const bool grouped = defer && table_mode == 2 && !dual && P.is_cc && sinc_cheb != nullptr;
+    pl.lds_corr = P.is_cc ? (size_t)ncc * 2 * 2 * sizeof(double) + (size_t)(((Lr + 2) & ~1) + 32) * sizeof(double) : 0;
+    pl.defer = getenv("RSAF_PITCH_INKERNEL") == nullptr;
+    pl.grouped = pl.defer && table_mode == 2 && !dual && P.is_cc && c.sinc_cheb != nullptr;
     int r_lo_h, r_hi_h;                                            // (as in the kernel: the depth-30 estimates' reach in grouped mode)
-    pitch_r_range(P.brent_ixmax, Lr, P.min_lag, P.max_lag, grouped ? 30 : P.refine_depth, &r_lo_h, &r_hi_h);
-    const size_t lds_cand = (size_t)(((r_hi_h - r_lo_h + 2) & ~1) + 3 * MAX_MAXIMA + 6 * MAXC + MAXC * 2 * NCH) * sizeof(double) +
-                            (size_t)(MAX_MAXIMA + 2 * MAXC + 4) * sizeof(int);
-    RSAF_CHECK_ARG(lds_corr <= 150 * 1024 && lds_cand <= 150 * 1024, "analysis window too long for LDS");
+    pitch_r_range(P.brent_ixmax, Lr, P.min_lag, P.max_lag, pl.grouped ? 30 : P.refine_depth, &r_lo_h, &r_hi_h);
+    pl.lds_cand = (size_t)(((r_hi_h - r_lo_h + 2) & ~1) + 3 * MAX_MAXIMA + 6 * MAXC + MAXC * 2 * NCH) * sizeof(double) +
+                  (size_t)(MAX_MAXIMA + 2 * MAXC + 4) * sizeof(int);
+    RSAF_CHECK_ARG(pl.lds_corr <= 150 * 1024 && pl.lds_cand <= 150 * 1024, "analysis window too long for LDS");
     // the correlation rows of a group of clips live in the caller's workspace between the kernels, and behind them what the
     // candidate kernel leaves for the refinement kernels: per frame the coefficient blocks of two lists and a 128-byte record
-    const int64_t row_bytes_per_clip = (int64_t)max_frames * pitch_ws_bytes_per_frame(rstride);
-    RSAF_CHECK_ARG(max_frames == 0 || (workspace && workspace_bytes >= row_bytes_per_clip),
+    const int64_t row_bytes_per_clip = (int64_t)max_frames * pitch_ws_bytes_per_frame(pl.rstride);
+    RSAF_CHECK_ARG(max_frames == 0 || (c.workspace && c.workspace_bytes >= row_bytes_per_clip),
                    "workspace too small (rsaf_mshds_pitch_workspace_bytes)");
-    int group = max_frames == 0 ? n_clips : (int)std::min<int64_t>(n_clips, workspace_bytes / std::max<int64_t>(row_bytes_per_clip, 1));
+    int group = max_frames == 0 ? n_clips : (int)std::min<int64_t>(n_clips, c.workspace_bytes / std::max<int64_t>(row_bytes_per_clip, 1));
     if (max_frames > 0) group = (int)std::min<int64_t>(group, ((int64_t)1 << 26) / max_frames > 0 ? ((int64_t)1 << 26) / max_frames : 1);   // frame index in 27 bits (cell queue)
+    pl.group = group;
     RSAF_CHECK_ARG(table_mode != 2 || (!dual && P.is_cc), "per-cell tables serve single-threshold cross-correlation analyses only");
-    hipStream_t s = (hipStream_t)stream;
-    int log2m = 0;
-    while ((2 << log2m) < P.nfft) ++log2m;                           // nfft = 2 M = 2^(log2m + 1)
-    int log2n = 0;
-    while ((1 << log2n) < ncc) ++log2n;
+    pl.log2m = 0;
+    while ((2 << pl.log2m) < P.nfft) ++pl.log2m;                   // nfft = 2 M = 2^(log2m + 1)
+    pl.log2n = 0;
+    while ((1 << pl.log2n) < ncc) ++pl.log2n;
     // transform lengths of 512 .. 2048 complex points run one wave per frame: every autocorrelation (nfft <= 4096) and
     // every cross-correlation but the 4 096-point one, which takes the workgroup kernel pitch_cc_kernel<12>.
     // A shorter transform is zero-padded up to the smallest wave size: the correlation is linear as long as the lags stay
     // below (transform length - window), so a longer transform returns the same values (autocorrelation: 512 complex =
     // 1024 real points; cross-correlation: 1024 points, whose transform back has the 512 the wave kernel needs).
     int wave_r = 0;
-    if (!P.is_cc) wave_r = log2m <= 9 ? 8 : 1 << (log2m - 6);
-    else if (log2n <= 11) wave_r = log2n <= 10 ? 16 : 32;
+    if (!P.is_cc) wave_r = pl.log2m <= 9 ? 8 : 1 << (pl.log2m - 6);
+    else if (pl.log2n <= 11) wave_r = pl.log2n <= 10 ? 16 : 32;
     if (wave_r && !P.is_cc) P.nfft = 128 * wave_r;                  // 2 S real points
     if (wave_r && P.is_cc) ncc = 64 * wave_r;
-    if (!wave_r)                                                    // 128 KB of LDS and more
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cc_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_corr));
-    const double* twiddles = nullptr;
-    const double* twiddles2 = nullptr;
-    if (!P.is_cc) {
-        const int rc = fft_twiddles(P.nfft, &twiddles);
-        if (rc != RSAF_OK) return rc;
-    } else {
-        int rc = fft_twiddles(2 * ncc, &twiddles);                  // W_2N^k: the N-point complex transform
-        if (rc != RSAF_OK) return rc;
-        rc = fft_twiddles(ncc, &twiddles2);                         // W_N^k: the N/2-point transform and the spectrum pass
-        if (rc != RSAF_OK) return rc;
-    }
-    if (lds_cand > 48 * 1024)
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)lds_cand));
+    pl.wave_r = wave_r;
+    pl.ncc = ncc;
     // the Chebyshev form needs the full depth on both sides of every cell a candidate can use
-    const double* cheb = table_mode == 2 ? nullptr : sinc_cheb;
+    pl.cheb = table_mode == 2 ? nullptr : c.sinc_cheb;
     const int cell_lag_lo = P.min_lag > 2 ? P.min_lag : 2;
     const int cell_lag_hi = std::min(P.max_lag - 1, P.brent_ixmax - 1);
-    {
-        const int lag_lo = cell_lag_lo, lag_hi = cell_lag_hi;
-        const bool unclipped = P.brent_ixmax + lag_lo - 1 >= P.refine_depth && lag_hi + 2 + P.refine_depth <= P.brent_ixmax;
-        P.cheb_all_full = unclipped ? 1 : 0;
-        if (cheb == nullptr) P.cheb_clipped = 0;
-        // clipped analyses keep the Chebyshev form only with the per-depth tables behind the shared one
-        if (!unclipped && !P.cheb_clipped) cheb = nullptr;
-    }
+    const bool unclipped = P.brent_ixmax + cell_lag_lo - 1 >= P.refine_depth && cell_lag_hi + 2 + P.refine_depth <= P.brent_ixmax;
+    P.cheb_all_full = unclipped ? 1 : 0;
+    if (pl.cheb == nullptr) P.cheb_clipped = 0;
+    // clipped analyses keep the Chebyshev form only with the per-depth tables behind the shared one
+    if (!unclipped && !P.cheb_clipped) pl.cheb = nullptr;
     // per-cell tables (mshds.sinc_cell_tables): cells b_lo .. b_hi, the lags 0 .. L (r is symmetric: the two taps that meet
     // a lag are summed in the table) padded to a multiple of four
-    const int cell_b_lo = P.brent_ixmax + cell_lag_lo - 1, cell_n_b = cell_lag_hi - cell_lag_lo + 2;
-    const int cell_ntap_pad = (Lr + 1 + 3) & ~3;
-    const size_t lds_cell = (size_t)cell_ntap_pad * NCH * sizeof(double) + 4 * CELL_Q * sizeof(unsigned);
-    if (grouped) {
-        RSAF_CHECK_ARG(cell_n_b >= 1 && lds_cell <= 150 * 1024, "per-cell tables: lag range too long for LDS");
-        if (lds_cell > 48 * 1024)
-            RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cell_coef_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)lds_cell));
+    pl.cell_b_lo = P.brent_ixmax + cell_lag_lo - 1;
+    pl.cell_n_b = cell_lag_hi - cell_lag_lo + 2;
+    pl.cell_ntap_pad = (Lr + 1 + 3) & ~3;
+    pl.lds_cell = (size_t)pl.cell_ntap_pad * NCH * sizeof(double) + 4 * CELL_Q * sizeof(unsigned);
+    if (pl.grouped) {
+        RSAF_CHECK_ARG(pl.cell_n_b >= 1 && pl.lds_cell <= 150 * 1024, "per-cell tables: lag range too long for LDS");
+        if (max_frames > 0 && P.debug_stop == 0)                   // the largest grid of the call: that of a full group
+            RSAF_CHECK_ARG(cell_workgroups(pl, (int64_t)group * max_frames, nullptr) <= 0x7fffffffLL,
+                           "per-cell tables: too many workgroups");
     }
-    if (max_frames > 0) {
-        // algorithmic flops of the correlation kernels, counted for equal-length clips (an upper bound for ragged batches);
-        // the candidate kernel's work is not counted
-        // AC: two complex FFTs of M = nfft / 2 points (5 M log2 M flops each) and the spectrum pass (~30 flops per point)
-        const double Mfft = 0.5 * (double)P.nfft;
-        const double ac_flops = 2.0 * 5.0 * Mfft * log2(Mfft) + 30.0 * Mfft;
-        // CC: one complex FFT of ncc points, one of ncc / 2, the spectrum pass (~40 flops per point) and the prefix sums
-        const double cc_flops = 5.0 * ncc * log2((double)ncc) + 2.5 * ncc * log2(0.5 * ncc) + 40.0 * 0.5 * ncc + 4.0 * seg_len;
-        // LDS bytes a frame moves through the FFT kernel (every pass reads and writes its N complex doubles: log4 stages of
-        // each transform, the staging pass and the spectrum pass): the kernel's own roofline is the LDS, not the FLOPs
-        // (one wave per frame, wave_fft.h: two exchanges per transform, each writing and reading the S complex doubles, and the
-        // paired spectrum step: 160 S bytes per autocorrelation frame, 120 S + the running sums per cross-correlation frame)
-        const double ac_lds = 160.0 * Mfft;
-        const double cc_lds = wave_r ? 120.0 * ncc + 16.0 * Lr
-                                     : 16.0 * ncc * (ceil(log2((double)ncc) / 2.0) + 2.0) * 2.0 + 16.0 * 0.5 * ncc * (ceil(log2(0.5 * ncc) / 2.0) + 1.0) * 2.0;
-        for (int c0 = 0; c0 < n_clips; c0 += group) {
-            const int nc = std::min(group, n_clips - c0);
-            const ClipInfo* cig = (const ClipInfo*)clip_info + c0;
-            {
-            // family "mshds_pitch_{ac,cc}_fft": the correlation kernel alone (FLOPs = its FFTs, bytes = its LDS traffic)
-            ProfScope prof(P.is_cc ? "mshds_pitch_cc_fft" : "mshds_pitch_ac_fft", s,
-                           (P.is_cc ? cc_flops : ac_flops) * (double)max_frames * (double)nc,
-                           (P.is_cc ? cc_lds : ac_lds) * (double)max_frames * (double)nc);
-            if (wave_r) {
-                // one wave per frame (wave_fft.h): S = 64 R complex points
-                const dim3 grid((max_frames + WF_FRAMES - 1) / WF_FRAMES, nc);
-                const double2_t* twz = reinterpret_cast<const double2_t*>(P.is_cc ? twiddles2 : twiddles);
-                if (P.is_cc) {
-                    const size_t lds_w = (size_t)((wave_r == 16 ? wfft::Plan<16>::LDS_DOUBLES : wfft::Plan<32>::LDS_DOUBLES) + ((Lr + 3) & ~1)) * sizeof(double);
-                    if (wave_r == 16)
-                        hipLaunchKernelGGL(pitch_cc_wave_kernel<16>, grid, dim3(64), lds_w, s, wav, cig, gpeak + c0, P, twz,
-                                           (double*)workspace, rstride, max_frames);
-                    else
-                        hipLaunchKernelGGL(pitch_cc_wave_kernel<32>, grid, dim3(64), lds_w, s, wav, cig, gpeak + c0, P, twz,
-                                           (double*)workspace, rstride, max_frames);
-                } else {
-#define RSAF_ACW_CASE(RR)                                                                                             \
-    case RR:                                                                                                          \
-        hipLaunchKernelGGL(pitch_ac_wave_kernel<RR>, grid, dim3(64), (size_t)wfft::Plan<RR>::LDS_DOUBLES * sizeof(double), s, wav, \
-                           cig, gpeak + c0, window, window_r, P, twz, (double*)workspace, rstride, max_frames);        \
-        break;
-                    switch (wave_r) { RSAF_ACW_CASE(8) RSAF_ACW_CASE(16) RSAF_ACW_CASE(32) default: break; }
-#undef RSAF_ACW_CASE
-                }
-            } else {
-                // 4 096-point cross-correlation: the workgroup kernel
-                hipLaunchKernelGGL(pitch_cc_kernel<12>, dim3((max_frames + CC_FRAMES_PER_WG - 1) / CC_FRAMES_PER_WG, nc),
-                                   dim3(256), lds_corr, s, wav, cig, gpeak + c0, P,
-                                   reinterpret_cast<const double2_t*>(twiddles), reinterpret_cast<const double2_t*>(twiddles2),
-                                   (double*)workspace, rstride, max_frames);
-            }
-            RSAF_CHECK_HIP(hipGetLastError());
-            }
-            // family "mshds_pitch_cand": maxima, candidate lists, Brent refinement.  Work model: every frame's normalised
-            // correlation row comes back from the HBM workspace ((Lr + 2) doubles); on the Chebyshev path the coefficient build
-            // of the frame's candidates runs on the fp64 matrix pipe: ceil(2 depth / 4) tap groups x 2 column tiles of
-            // v_mfma_f64_16x16x4_f64 (2 048 flops each).  The Brent iterations themselves (a dozen polynomial evaluations per
-            // candidate) and the direct path's sinc sums are not counted.
-            const double cand_rows = (double)max_frames * (double)nc;
-            // workspace of the group: rows | coefficients of list A | of list B | frame records
-            const int64_t gframes = (int64_t)nc * max_frames;
-            double* pc_a = (double*)workspace + gframes * rstride;
-            double* pc_b = pc_a + gframes * PC_DOUBLES;
-            int* hdr = reinterpret_cast<int*>(pc_b + gframes * PC_DOUBLES);
-            DeferArgs DA{defer ? hdr : nullptr, defer ? pc_a : nullptr, defer ? pc_b : nullptr, grouped ? 1 : 0};
-            {
-            ProfScope prof(grouped ? "mshds_pitch_cand_lists" : cheb ? "mshds_pitch_cand_cheb" : "mshds_pitch_cand_direct", s,
-                           cheb ? cand_rows * 2048.0 * 2.0 * ceil(2.0 * P.refine_depth / 4.0) : 0.0,
-                           cand_rows * (double)(Lr + 2) * 8.0);
-            hipLaunchKernelGGL(pitch_cand_kernel, dim3(max_frames, nc), dim3(CT), lds_cand, s, cig, gpeak + c0, P,
-                               (const double*)workspace, rstride, max_frames, (FrameOut*)frame_out,
-                               dual ? (FrameOut*)frame_out2 : (FrameOut*)nullptr, cheb, DA);
-            RSAF_CHECK_HIP(hipGetLastError());
-            }
-            if (defer && P.debug_stop == 0) {
-                if (grouped) {
-                    // one table per cell on the fp64 matrix pipe: <= 28 cells per frame x (2 L + 1) taps x 16 coefficients
-                    constexpr int chunk_frames = 4096;               // frames per workgroup
-                    const int64_t n_chunks = (gframes + chunk_frames - 1) / chunk_frames;
-                    const int64_t n_wg = 8 * (int64_t)cell_n_b * ((n_chunks + 7) / 8);
-                    RSAF_CHECK_ARG(n_wg <= 0x7fffffffLL, "per-cell tables: too many workgroups");
-                    ProfScope prof("mshds_pitch_cand_cells", s, cand_rows * 28.0 * 2.0 * cell_ntap_pad * NCH,   // <= 28 cells per frame
-                                   cand_rows * 28.0 * (double)(Lr + 1) * 8.0);
-                    hipLaunchKernelGGL(pitch_cell_coef_kernel, dim3((unsigned)n_wg), dim3(256), lds_cell, s, cig, nc, max_frames,
-                                       (const int*)hdr, (const double*)workspace, rstride, Lr, P.brent_ixmax, sinc_cheb,
-                                       cell_b_lo, cell_n_b, cell_ntap_pad, chunk_frames, (int)n_chunks, pc_a);
-                    RSAF_CHECK_HIP(hipGetLastError());
-                }
-                const bool low_is_second = dual && P.voicing_thr2 < P.voicing_thr;
-                FrameOut* oa = low_is_second ? (FrameOut*)frame_out2 : (FrameOut*)frame_out;
-                FrameOut* ob = !dual ? (FrameOut*)nullptr : low_is_second ? (FrameOut*)frame_out : (FrameOut*)frame_out2;
-                ProfScope prof("mshds_pitch_cand_brent", s, 0.0, cand_rows * 15.0 * 2.0 * NCH * 8.0);
-                hipLaunchKernelGGL(pitch_brent_kernel, dim3((max_frames + BR_FRAMES - 1) / BR_FRAMES, nc), dim3(64), 0, s, cig, (const int*)hdr,
-                                   (const double*)pc_a, (const double*)pc_b, max_frames, P.brent_ixmax, oa, ob);
-                RSAF_CHECK_HIP(hipGetLastError());
-            }
-        }
-    }
-    for (int pass = 0; pass < (dual ? 2 : 1); ++pass) {
-        const FrameOut* fo = (const FrameOut*)(pass ? frame_out2 : frame_out);
-        unsigned char* ps = pass ? psi2 : psi;
-        int* es = pass ? end_state2 : end_state;
-        double* sf = pass ? sel_freq2 : sel_freq;
-        double* ss = pass ? sel_strength2 : sel_strength;
-        const double vt = pass ? voicing_thr2 : P.voicing_thr;
-        {
-            ProfScope prof("mshds_pitch_path", s, 0.0, 0.0);
-            hipLaunchKernelGGL(path_kernel, dim3(n_clips), dim3(64), 0, s, fo, (const ClipInfo*)clip_info, P.dt, silence_thr,
-                               vt, P.octave_cost, octave_jump, vuv, P.ceiling, ps, es);
-            RSAF_CHECK_HIP(hipGetLastError());
-            hipLaunchKernelGGL(backtrack_kernel, dim3(n_clips), dim3(256), 0, s, fo, (const ClipInfo*)clip_info, ps, es, sf, ss);
-            RSAF_CHECK_HIP(hipGetLastError());
-        }
-        hipLaunchKernelGGL(pitch_stats_kernel, dim3(n_clips), dim3(64), 0, s, sf, (const ClipInfo*)clip_info, P.ceiling,
-                           pass ? stats_out2 : stats_out);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
+    // algorithmic flops of the correlation kernels, counted for equal-length clips (an upper bound for ragged batches);
+    // the candidate kernel's work is not counted
+    // AC: two complex FFTs of M = nfft / 2 points (5 M log2 M flops each) and the spectrum pass (~30 flops per point)
+    const double Mfft = 0.5 * (double)P.nfft;
+    const double ac_flops = 2.0 * 5.0 * Mfft * log2(Mfft) + 30.0 * Mfft;
+    // CC: one complex FFT of ncc points, one of ncc / 2, the spectrum pass (~40 flops per point) and the prefix sums
+    const double cc_flops = 5.0 * ncc * log2((double)ncc) + 2.5 * ncc * log2(0.5 * ncc) + 40.0 * 0.5 * ncc + 4.0 * seg_len;
+    // LDS bytes a frame moves through the FFT kernel (every pass reads and writes its N complex doubles: log4 stages of
+    // each transform, the staging pass and the spectrum pass): the kernel's own roofline is the LDS, not the FLOPs
+    // (one wave per frame, wave_fft.h: two exchanges per transform, each writing and reading the S complex doubles, and the
+    // paired spectrum step: 160 S bytes per autocorrelation frame, 120 S + the running sums per cross-correlation frame)
+    const double ac_lds = 160.0 * Mfft;
+    const double cc_lds = wave_r ? 120.0 * ncc + 16.0 * Lr
+                                 : 16.0 * ncc * (ceil(log2((double)ncc) / 2.0) + 2.0) * 2.0 + 16.0 * 0.5 * ncc * (ceil(log2(0.5 * ncc) / 2.0) + 1.0) * 2.0;
+    pl.corr_flops = P.is_cc ? cc_flops : ac_flops;
+    pl.corr_lds = P.is_cc ? cc_lds : ac_lds;
     return RSAF_OK;
 }
+
+// what has to happen once per call ahead of the launches: the kernels' LDS limits and the twiddle tables
+// tw: AC: W_nfft^k;  CC: W_2N^k, the N-point complex transform of the workgroup kernel
+// tw2: CC: W_N^k, the N/2-point transform and the spectrum pass
+static int pitch_prepare(const PitchPlan& pl, const double2_t** tw_out, const double2_t** tw2_out) {
+    if (!pl.wave_r)                                                 // 128 KB of LDS and more
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cc_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_corr));
+    const double *tw = nullptr, *tw2 = nullptr;
+    int rc = fft_twiddles(pl.P.is_cc ? 2 * pl.ncc : pl.P.nfft, &tw);
+    if (rc == RSAF_OK && pl.P.is_cc) rc = fft_twiddles(pl.ncc, &tw2);
+    if (rc != RSAF_OK) return rc;
+    *tw_out = reinterpret_cast<const double2_t*>(tw);
+    *tw2_out = reinterpret_cast<const double2_t*>(tw2);
+    if (pl.lds_cand > 48 * 1024)
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)pl.lds_cand));
+    if (pl.grouped && pl.lds_cell > 48 * 1024)
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cell_coef_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)pl.lds_cell));
+    return RSAF_OK;
+}
+
+// the clips of one pass through the workspace, which holds: rows | coefficients of list A | of list B | frame records
+struct PitchGroup {
+    const ClipInfo* ci;
+    const double* gpeak;
+    int nc;
+    double *pc_a, *pc_b;
+    int* hdr;
+};
+
+static PitchGroup pitch_group(const PitchCall& c, const PitchPlan& pl, int c0) {
+    PitchGroup g;
+    g.ci = c.ci + c0;
+    g.gpeak = c.gpeak + c0;
+    g.nc = std::min(pl.group, c.n_clips - c0);
+    const int64_t gframes = (int64_t)g.nc * c.max_frames;
+    g.pc_a = c.workspace + gframes * pl.rstride;
+    g.pc_b = g.pc_a + gframes * PC_DOUBLES;
+    g.hdr = reinterpret_cast<int*>(g.pc_b + gframes * PC_DOUBLES);
+    return g;
+}
+
+template <int R>
+static void launch_ac_wave(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, dim3 grid, const double2_t* tw) {
+    hipLaunchKernelGGL(pitch_ac_wave_kernel<R>, grid, dim3(64), (size_t)wfft::Plan<R>::LDS_DOUBLES * sizeof(double), c.stream,
+                       c.wav, g.ci, g.gpeak, c.window, c.window_r, pl.P, tw, c.workspace, pl.rstride, c.max_frames);
+}
+
+template <int R>
+static void launch_cc_wave(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, dim3 grid, const double2_t* tw2) {
+    const size_t lds_w = (size_t)(wfft::Plan<R>::LDS_DOUBLES + ((pl.Lr + 3) & ~1)) * sizeof(double);
+    hipLaunchKernelGGL(pitch_cc_wave_kernel<R>, grid, dim3(64), lds_w, c.stream, c.wav, g.ci, g.gpeak, pl.P, tw2,
+                       c.workspace, pl.rstride, c.max_frames);
+}
+
+// family "mshds_pitch_{ac,cc}_fft": the correlation kernel alone (FLOPs = its FFTs, bytes = its LDS traffic)
+static int launch_correlation(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, const double2_t* tw, const double2_t* tw2) {
+    ProfScope prof(pl.P.is_cc ? "mshds_pitch_cc_fft" : "mshds_pitch_ac_fft", c.stream,
+                   pl.corr_flops * (double)c.max_frames * (double)g.nc, pl.corr_lds * (double)c.max_frames * (double)g.nc);
+    const dim3 wave_grid((c.max_frames + WF_FRAMES - 1) / WF_FRAMES, g.nc);      // one wave per frame (wave_fft.h)
+    if (!pl.wave_r)         // 4 096-point cross-correlation: the workgroup kernel
+        hipLaunchKernelGGL(pitch_cc_kernel<12>, dim3((c.max_frames + CC_FRAMES_PER_WG - 1) / CC_FRAMES_PER_WG, g.nc), dim3(256),
+                           pl.lds_corr, c.stream, c.wav, g.ci, g.gpeak, pl.P, tw, tw2, c.workspace, pl.rstride, c.max_frames);
+    else if (pl.P.is_cc)
+        switch (pl.wave_r) {
+            case 16: launch_cc_wave<16>(c, pl, g, wave_grid, tw2); break;
+            case 32: launch_cc_wave<32>(c, pl, g, wave_grid, tw2); break;
+        }
+    else
+        switch (pl.wave_r) {
+            case 8: launch_ac_wave<8>(c, pl, g, wave_grid, tw); break;
+            case 16: launch_ac_wave<16>(c, pl, g, wave_grid, tw); break;
+            case 32: launch_ac_wave<32>(c, pl, g, wave_grid, tw); break;
+        }
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// family "mshds_pitch_cand": maxima, candidate lists, Brent refinement.  Work model: every frame's normalised
+// correlation row comes back from the HBM workspace ((Lr + 2) doubles); on the Chebyshev path the coefficient build
+// of the frame's candidates runs on the fp64 matrix pipe: ceil(2 depth / 4) tap groups x 2 column tiles of
+// v_mfma_f64_16x16x4_f64 (2 048 flops each).  The Brent iterations themselves (a dozen polynomial evaluations per
+// candidate) and the direct path's sinc sums are not counted.
+static int launch_candidates(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, FrameOut* out, FrameOut* out2) {
+    const double rows = (double)c.max_frames * (double)g.nc;     // frames as the ProfScope models count them
+    const DeferArgs DA{pl.defer ? g.hdr : nullptr, pl.defer ? g.pc_a : nullptr, pl.defer ? g.pc_b : nullptr, pl.grouped ? 1 : 0};
+    ProfScope prof(pl.grouped ? "mshds_pitch_cand_lists" : pl.cheb ? "mshds_pitch_cand_cheb" : "mshds_pitch_cand_direct", c.stream,
+                   pl.cheb ? rows * 2048.0 * 2.0 * ceil(2.0 * pl.P.refine_depth / 4.0) : 0.0,
+                   rows * (double)(pl.Lr + 2) * 8.0);
+    hipLaunchKernelGGL(pitch_cand_kernel, dim3(c.max_frames, g.nc), dim3(CT), pl.lds_cand, c.stream, g.ci, g.gpeak, pl.P,
+                       (const double*)c.workspace, pl.rstride, c.max_frames, out, out2, pl.cheb, DA);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// the deferred refinement: per-cell coefficients where the plan says so, then Brent's search with one candidate per lane
+static int launch_refinement(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, FrameOut* out, FrameOut* out2) {
+    const double rows = (double)c.max_frames * (double)g.nc;
+    if (pl.grouped) {
+        // one table per cell on the fp64 matrix pipe: <= 28 cells per frame x (2 L + 1) taps x 16 coefficients
+        int n_chunks;
+        const int64_t n_wg = cell_workgroups(pl, (int64_t)g.nc * c.max_frames, &n_chunks);
+        ProfScope prof("mshds_pitch_cand_cells", c.stream, rows * 28.0 * 2.0 * pl.cell_ntap_pad * NCH,   // <= 28 cells per frame
+                       rows * 28.0 * (double)(pl.Lr + 1) * 8.0);
+        hipLaunchKernelGGL(pitch_cell_coef_kernel, dim3((unsigned)n_wg), dim3(256), pl.lds_cell, c.stream, g.ci, g.nc, c.max_frames,
+                           (const int*)g.hdr, (const double*)c.workspace, pl.rstride, pl.Lr, pl.P.brent_ixmax, c.sinc_cheb,
+                           pl.cell_b_lo, pl.cell_n_b, pl.cell_ntap_pad, CELL_CHUNK_FRAMES, n_chunks, g.pc_a);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    // list A is the one of the lower voicing threshold
+    const bool low_is_second = pl.dual && pl.P.voicing_thr2 < pl.P.voicing_thr;
+    FrameOut* oa = low_is_second ? out2 : out;
+    FrameOut* ob = low_is_second ? out : out2;
+    ProfScope prof("mshds_pitch_cand_brent", c.stream, 0.0, rows * 15.0 * 2.0 * NCH * 8.0);
+    hipLaunchKernelGGL(pitch_brent_kernel, dim3((c.max_frames + BR_FRAMES - 1) / BR_FRAMES, g.nc), dim3(64), 0, c.stream, g.ci,
+                       (const int*)g.hdr, (const double*)g.pc_a, (const double*)g.pc_b, c.max_frames, pl.P.brent_ixmax, oa, ob);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// path finder, backtrack and statistics of one voicing threshold, all clips of the call
+static int launch_paths(const PitchCall& c, const PitchPlan& pl, const PitchOutputs& o, double voicing_thr) {
+    const PitchParams& P = pl.P;
+    {
+        ProfScope prof("mshds_pitch_path", c.stream, 0.0, 0.0);
+        hipLaunchKernelGGL(path_kernel, dim3(c.n_clips), dim3(64), 0, c.stream, (const FrameOut*)o.frame_out, c.ci, P.dt,
+                           pl.silence_thr, voicing_thr, P.octave_cost, pl.octave_jump, pl.vuv, P.ceiling, o.psi, o.end_state);
+        RSAF_CHECK_HIP(hipGetLastError());
+        hipLaunchKernelGGL(backtrack_kernel, dim3(c.n_clips), dim3(256), 0, c.stream, (const FrameOut*)o.frame_out, c.ci, o.psi,
+                           o.end_state, o.sel_freq, o.sel_strength);
+        RSAF_CHECK_HIP(hipGetLastError());
+    }
+    hipLaunchKernelGGL(pitch_stats_kernel, dim3(c.n_clips), dim3(64), 0, c.stream, o.sel_freq, c.ci, P.ceiling, o.stats);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// o2 / voicing_thr2 >= 0: the same analysis for a second voicing threshold (rsaf_mshds_pitch_dual)
+static int pitch_run(const PitchCall& c, const double* params_host, const PitchOutputs& o1, const PitchOutputs& o2,
+                     double voicing_thr2) {
+    PitchPlan pl;
+    int rc = pitch_plan(c, params_host, o1, o2, voicing_thr2, &pl);
+    if (rc != RSAF_OK || c.n_clips == 0) return rc;
+    const double2_t *tw, *tw2;
+    if ((rc = pitch_prepare(pl, &tw, &tw2)) != RSAF_OK) return rc;
+    FrameOut* out2 = pl.dual ? o2.frame_out : nullptr;
+    for (int c0 = 0; c.max_frames > 0 && c0 < c.n_clips; c0 += pl.group) {
+        const PitchGroup g = pitch_group(c, pl, c0);
+        if ((rc = launch_correlation(c, pl, g, tw, tw2)) != RSAF_OK) return rc;
+        if ((rc = launch_candidates(c, pl, g, o1.frame_out, out2)) != RSAF_OK) return rc;
+        if (pl.defer && pl.P.debug_stop == 0 && (rc = launch_refinement(c, pl, g, o1.frame_out, out2)) != RSAF_OK) return rc;
+    }
+    if ((rc = launch_paths(c, pl, o1, pl.P.voicing_thr)) != RSAF_OK) return rc;
+    return pl.dual ? launch_paths(c, pl, o2, voicing_thr2) : RSAF_OK;
+}
+
+extern "C" {
 
 // bytes of correlation rows per clip (max_frames rows of max_lag + 2 doubles); the analysis runs the clips in groups of
 // floor(workspace_bytes / this), so any multiple >= 1 works and n_clips multiples avoid the grouping
 int64_t rsaf_mshds_pitch_workspace_bytes_per_clip(int max_frames, const double* params_host /* 18 doubles */) {
     if (!params_host || max_frames < 0) return -1;
-    const int Lr = (int)params_host[15] ? (int)params_host[11] : (int)params_host[12];
-    return (int64_t)max_frames * pitch_ws_bytes_per_frame(Lr + 2);
+    return (int64_t)max_frames * pitch_ws_bytes_per_frame(pitch_row_lags(params_host) + 2);
 }
 
 int rsaf_mshds_pitch(const float* wav, const void* clip_info, int n_clips, int max_frames, const double* gpeak,
                      const double* window, const double* window_r, const double* params_host /* 18 doubles */,
                      void* frame_out, unsigned char* psi, int* end_state, double* sel_freq, double* sel_strength, double* stats_out,
                      const double* sinc_cheb, void* workspace, int64_t workspace_bytes, rsaf_stream_t stream) {
-    return pitch_impl(wav, clip_info, n_clips, max_frames, gpeak, window, window_r, params_host, frame_out, psi, end_state,
-                      sel_freq, sel_strength, stats_out, -1.0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, sinc_cheb,
-                      workspace, workspace_bytes, stream);
+    const PitchCall call{wav, (const ClipInfo*)clip_info, n_clips, max_frames, gpeak, window, window_r, sinc_cheb,
+                         (double*)workspace, workspace_bytes, (hipStream_t)stream};
+    return pitch_run(call, params_host, PitchOutputs{(FrameOut*)frame_out, psi, end_state, sel_freq, sel_strength, stats_out},
+                     PitchOutputs{}, -1.0);
 }
 
 int rsaf_mshds_pitch_dual(const float* wav, const void* clip_info, int n_clips, int max_frames, const double* gpeak,
@@ -3757,10 +2726,13 @@ int rsaf_mshds_pitch_dual(const float* wav, const void* clip_info, int n_clips, 
                           double* sel_freq2, double* sel_strength2, double* stats_out2, const double* sinc_cheb,
                           void* workspace, int64_t workspace_bytes, rsaf_stream_t stream) {
     RSAF_CHECK_ARG(voicing_threshold2 >= 0.0, "second voicing threshold must be >= 0");
-    return pitch_impl(wav, clip_info, n_clips, max_frames, gpeak, window, window_r, params_host, frame_out, psi, end_state,
-                      sel_freq, sel_strength, stats_out, voicing_threshold2, frame_out2, psi2, end_state2, sel_freq2,
-                      sel_strength2, stats_out2, sinc_cheb, workspace, workspace_bytes, stream);
+    const PitchCall call{wav, (const ClipInfo*)clip_info, n_clips, max_frames, gpeak, window, window_r, sinc_cheb,
+                         (double*)workspace, workspace_bytes, (hipStream_t)stream};
+    return pitch_run(call, params_host, PitchOutputs{(FrameOut*)frame_out, psi, end_state, sel_freq, sel_strength, stats_out},
+                     PitchOutputs{(FrameOut*)frame_out2, psi2, end_state2, sel_freq2, sel_strength2, stats_out2},
+                     voicing_threshold2);
 }
+
 
 // peaks of an n-frame contour: at most n/2; the LDS form keeps SR_MAX_PEAKS of them (a smooth 16 ms contour of at most
 // ~8 500 frames has far fewer), the global-memory form of long clips sizes the lists exactly
@@ -3792,125 +2764,6 @@ int rsaf_mshds_speechrate(const double* intensity_db, const void* clip_info, int
     hipLaunchKernelGGL(speechrate_kernel, dim3(n_clips), dim3(64), lds, s, intensity_db, (const ClipInfo*)clip_info,
                        intensity_dt, sel_freq, (const ClipInfo*)pitch_clip_info, pitch_dt, pitch_ceiling, workspace,
                        rsaf_mshds_speechrate_workspace_doubles(max_frames), max_frames, peak_cap, in_global ? 1 : 0, out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-int rsaf_mshds_resample10k_table_stride(int depth) { return (2 * depth + 1 + 8 * (RS_QL - 1) + 7) / 8 * 8 + 8; }
-
-int rsaf_mshds_resample10k(const double* lowpassed, const void* resample_info, int n_clips, int max_out, const double* tables,
-                           int table_stride, const int* phase_base, int depth, double* out, rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_out >= 0 && depth >= 3, "bad argument");
-    if (n_clips == 0 || max_out == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(lowpassed && resample_info && tables && phase_base && out, "NULL pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const int taps = 2 * depth + 1;
-    RSAF_CHECK_ARG(table_stride >= rsaf_mshds_resample10k_table_stride(depth), "weight rows shorter than rsaf_mshds_resample10k_table_stride");
-    const int span = 8 * (RS_QT - 1) + 8 + taps + 8 * RS_QL + 8;       // phase bases differ by < 8; the tap loop runs past `taps`
-    const size_t lds = (size_t)(span + span / 32 + 2) * sizeof(double);
-    RSAF_CHECK_ARG(lds <= 150 * 1024, "resampler depth too large for LDS");
-    if (lds > 48 * 1024)
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)resample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ProfScope prof("mshds_resample10k", s, 0.0, 0.0);
-    const int nq = (max_out + 4) / 5;
-    hipLaunchKernelGGL(resample_kernel, dim3((nq + RS_QT - 1) / RS_QT, n_clips), dim3(320), lds, s, lowpassed,
-                       (const ResampleInfo*)resample_info, tables, table_stride, phase_base, depth, out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    const int n_edge = (int)((double)(depth + 2) * 0.625) + 3;         // output samples within depth + 2 input samples of an end
-    hipLaunchKernelGGL(resample_edge_kernel, dim3((2 * n_edge + 255) / 256, n_clips), dim3(256), 0, s, lowpassed,
-                       (const ResampleInfo*)resample_info, depth, n_edge, 1.6, out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-int rsaf_mshds_formants(const double* y10, const void* resample_info, const void* clip_info, int n_clips, int max_frames,
-                        const double* window, int nsamp_window, double time_step, double dx_out, double preemph_factor,
-                        void* frames_out, rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_frames >= 0 && nsamp_window >= 16, "bad argument");
-    if (n_clips == 0 || max_frames == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(y10 && resample_info && clip_info && window && frames_out, "NULL pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = (size_t)4 * 2 * (nsamp_window + 2) * sizeof(double);
-    RSAF_CHECK_ARG(lds <= 150 * 1024, "formant window too long");
-    if (lds > 48 * 1024)
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)formant_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ProfScope prof("mshds_formant_frames", s, 0.0, 0.0);
-    hipLaunchKernelGGL(formant_kernel, dim3((max_frames + 4 * FB_GROUP - 1) / (4 * FB_GROUP), n_clips), dim3(256), lds, s, y10,
-                       (const ResampleInfo*)resample_info, (const ClipInfo*)clip_info, window, nsamp_window, time_step,
-                       dx_out, preemph_factor, (FormantFrame*)frames_out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// scratch of rsaf_mshds_pulses: stretch table + per-stretch counts + left (time, margin) + right (time) slots
-static void pulses_layout(int n_clips, int max_frames, int max_samples, double pitch_dt, double ceiling, int* max_st,
-                          int* cap_slots, int64_t* total) {
-    *max_st = max_frames / 2 + 2;
-    *cap_slots = (int)((double)max_frames * pitch_dt * ceiling * 1.25) + 4 * *max_st + 16;
-    (void)max_samples;
-    *total = (int64_t)n_clips * ((int64_t)*max_st * (sizeof(Stretch) + sizeof(int2)) + sizeof(int) * 2 + sizeof(double) +
-                                 (int64_t)*cap_slots * (sizeof(double2) + sizeof(double))) + 256;
-}
-
-int64_t rsaf_mshds_pulses_workspace_bytes(int n_clips, int max_frames, double pitch_dt, double pitch_ceiling) {
-    int ms, cs;
-    int64_t total;
-    pulses_layout(n_clips, max_frames, 0, pitch_dt, pitch_ceiling, &ms, &cs, &total);
-    return total;
-}
-
-int rsaf_mshds_pulses(const float* wav, const void* pitch_clip_info, int n_clips, int max_frames, const double* sel_freq,
-                      double pitch_dt, double pitch_ceiling, void* workspace, int64_t workspace_bytes, double* pulses,
-                      int max_pulses, int* n_pulses, rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_pulses >= 1 && max_frames >= 0, "bad argument");
-    if (n_clips == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(wav && pitch_clip_info && sel_freq && workspace && pulses && n_pulses, "NULL pointer");
-    int max_st, cap_slots;
-    int64_t need;
-    pulses_layout(n_clips, max_frames, 0, pitch_dt, pitch_ceiling, &max_st, &cap_slots, &need);
-    RSAF_CHECK_ARG(workspace_bytes >= need, "workspace too small (rsaf_mshds_pulses_workspace_bytes)");
-    char* w = (char*)workspace;
-    double2* left = (double2*)w;              w += (int64_t)n_clips * cap_slots * sizeof(double2);
-    double* right = (double*)w;               w += (int64_t)n_clips * cap_slots * sizeof(double);
-    double* abs_peak = (double*)w;            w += (int64_t)n_clips * sizeof(double);
-    Stretch* st = (Stretch*)w;                w += (int64_t)n_clips * max_st * sizeof(Stretch);
-    int2* counts = (int2*)w;                  w += (int64_t)n_clips * max_st * sizeof(int2);
-    int* n_st = (int*)w;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof("mshds_pulses", s, 0.0, 0.0);
-    hipLaunchKernelGGL(pulse_stretches_kernel, dim3(n_clips), dim3(256), 0, s, wav, (const ClipInfo*)pitch_clip_info, sel_freq,
-                       pitch_dt, pitch_ceiling, st, max_st, n_st, abs_peak);
-    RSAF_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pulse_walk_kernel, dim3((max_st + 3) / 4, n_clips), dim3(256), 0, s, wav, (const ClipInfo*)pitch_clip_info,
-                       sel_freq, pitch_dt, pitch_ceiling, abs_peak, st, max_st, n_st, left, right, cap_slots, counts);
-    RSAF_CHECK_HIP(hipGetLastError());
-    hipLaunchKernelGGL(pulse_merge_kernel, dim3(n_clips), dim3(64), 0, s, st, max_st, n_st, left, right, cap_slots, counts, pulses,
-                       max_pulses, n_pulses);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-int rsaf_mshds_ltas_slope_tilt(const float* wav, const void* clip_info, int n_clips, const double* pulses,
-                               int max_pulses, const int* n_pulses, double shortest_period, double longest_period,
-                               double max_period_factor, double* out, rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(n_clips >= 0 && max_pulses >= 0, "bad clip/pulse count");
-    if (n_clips == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(wav && clip_info && pulses && n_pulses && out, "NULL pointer");
-    RSAF_CHECK_ARG(longest_period * 16000.0 + 2.0 <= LTAS_MAXN, "longest period does not fit the LDS staging");
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof("mshds_ltas", s, 0.0, 0.0);
-    hipLaunchKernelGGL(ltas_kernel, dim3(n_clips), dim3(256), 0, s, wav, (const ClipInfo*)clip_info, pulses, max_pulses,
-                       n_pulses, shortest_period, longest_period, max_period_factor, out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-int rsaf_mshds_formant_stats(const void* frames, const void* clip_info, int n_clips, double time_step, const double* pulses,
-                             int max_pulses, const int* n_pulses, double* out, rsaf_stream_t stream) {
-    if (n_clips <= 0) return RSAF_OK;
-    RSAF_CHECK_ARG(frames && clip_info && pulses && n_pulses && out, "NULL pointer");
-    hipLaunchKernelGGL(formant_stats_kernel, dim3(n_clips), dim3(64), 0, (hipStream_t)stream, (const FormantFrame*)frames,
-                       (const ClipInfo*)clip_info, time_step, pulses, max_pulses, n_pulses, out);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }

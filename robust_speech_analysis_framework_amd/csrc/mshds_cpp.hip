@@ -19,14 +19,15 @@
 #include "praat_lowpass.h"
 #include "rsaf_common.h"
 #include "wave_fft.h"
-
-#pragma clang fp contract(off)
+// the four above are compiled with contraction on; from this header's pragma on, nothing is contracted
+#include "mshds_common.h"
 
 namespace rsaf {
 namespace mshds_cpp {
 
-constexpr double DXS = 1.0 / 16000.0;
-constexpr double PI = 3.14159265358979323846;
+using mshds::ClipInfo;
+using mshds::DXS;
+using mshds::PI;
 constexpr double FS_OUT = 10000.0;
 constexpr double DXO = 1.0 / FS_OUT;
 constexpr int DEPTH = 50;                 // Sound_resample precision of Sound_to_PowerCepstrogram
@@ -35,16 +36,6 @@ constexpr double DQ = 1.0e-4;             // quefrency step = 1 / FS_OUT
 constexpr int NFFT_MAX = 1024;            // 0.1 s window at 10 kHz = 1000 samples
 constexpr int NQ_MAX = NFFT_MAX / 2 + 1;  // 513
 constexpr int SEG_DOUBLES = 15;
-
-struct ClipInfo {      // same 48-byte rows as csrc/mshds.hip
-    int64_t sample_off;
-    int64_t frame_off;
-    double t1;
-    int n_samples;
-    int n_frames;
-    double x1;         // time of the first sample
-    double xmax;       // end of the sound's time domain
-};
 
 // one voiced interval (all fields double so that the table is one plain array)
 struct Seg {

@@ -2,11 +2,11 @@
 
 The reference runs ~10 Praat analyses per file through parselmouth, one file at a time, with Python
 loops per pulse / per frame (``src/mshds_extractor.py:11-376``).  Here the analyses of a whole batch
-run as float64 HIP kernels (``csrc/mshds.hip``); the host only builds the frame grids (Praat's
+run as float64 HIP kernels (``csrc/mshds.hip``, ``csrc/mshds_voice.hip``); the host only builds the frame grids (Praat's
 ``Sampled_shortTermAnalysis`` arithmetic), the window tables, and routes each clip to the
 speaker-adapted pitch range that ``_pitch_values`` chooses (``:127-162``).
 
-All 25 columns are computed on the device (``csrc/mshds.hip``, ``csrc/mshds_cpp.hip``); there is no CPU
+All 25 columns are computed on the device (``csrc/mshds.hip``, ``mshds_voice.hip``, ``mshds_cpp.hip``); there is no CPU
 fallback.  A helper that fails in the reference gives NaN for its columns there (``except: return nan``);
 the kernels reproduce those cases (too-short clips, no voiced frames, no periods) as NaN as well.
 """
@@ -261,6 +261,17 @@ class MshdsEngine:
                                       for a in builder())
         return self._tables[key]
 
+    def _pitch_outputs(self, tf, n):
+        """The six outputs of one voicing threshold, in the argument order of rsaf_mshds_pitch / rsaf_mshds_pitch_dual."""
+        import torch
+        dev = self.device
+        return {"frame_out": torch.empty(tf * self.fo_doubles, dtype=torch.float64, device=dev),
+                "psi": torch.empty(tf * 16, dtype=torch.uint8, device=dev),
+                "end_state": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+                "sel_freq": torch.zeros(tf, dtype=torch.float64, device=dev),
+                "sel_strength": torch.zeros(tf, dtype=torch.float64, device=dev),
+                "stats": torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)}
+
     # ---- one pitch analysis over a set of clips ----
     def pitch(self, wav, sample_offs, lengths, gpeak, *, time_step, floor, ceiling, max_candidates=15,
               silence_threshold=0.03, voicing_threshold=0.45, octave_cost=0.01, octave_jump_cost=0.35,
@@ -277,12 +288,7 @@ class MshdsEngine:
         ci_d = _dev(ci, dev)
         win, wr = self._table(("pitch", g.nsamp_window, is_cc), g.tables)
         tf = max(total, 1)
-        frame_out = torch.empty(tf * self.fo_doubles, dtype=torch.float64, device=dev)
-        psi = torch.empty(tf * 16, dtype=torch.uint8, device=dev)
-        end_state = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
-        sel_f = torch.zeros(tf, dtype=torch.float64, device=dev)
-        sel_s = torch.zeros(tf, dtype=torch.float64, device=dev)
-        stats = torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)
+        first = self._pitch_outputs(tf, n)
         # cross-correlation passes can have candidates whose interpolation depth the array ends clip: the per-depth tables
         # ride behind the shared one when they are small (depth 70: 618 KB; depth 700 would be 63 MB: direct evaluation)
         clipped_tables = bool(is_cc) and int(refine_depth) <= CHEB_CLIP_MAX_DEPTH
@@ -301,13 +307,7 @@ class MshdsEngine:
                                    g.dt_window, table_mode)
         second = None
         if voicing_threshold2 is not None:
-            second = {"geom": g, "ci": ci, "ci_dev": ci_d, "total_frames": total, "max_frames": mx,
-                      "frame_out": torch.empty(tf * self.fo_doubles, dtype=torch.float64, device=dev),
-                      "psi": torch.empty(tf * 16, dtype=torch.uint8, device=dev),
-                      "end_state": torch.empty(max(n, 1), dtype=torch.int32, device=dev),
-                      "sel_freq": torch.zeros(tf, dtype=torch.float64, device=dev),
-                      "sel_strength": torch.zeros(tf, dtype=torch.float64, device=dev),
-                      "stats": torch.empty((max(n, 1), 8), dtype=torch.float64, device=dev)}
+            second = {"geom": g, "ci": ci, "ci_dev": ci_d, "total_frames": total, "max_frames": mx, **self._pitch_outputs(tf, n)}
         wp = _lib.ptr(win) if win is not None else None
         wrp = _lib.ptr(wr) if wr is not None else None
         if cheb is None:
@@ -318,29 +318,27 @@ class MshdsEngine:
         per_clip = int(lib.rsaf_mshds_pitch_workspace_bytes_per_clip(mx, params)) if n else 0
         ws_bytes = max(per_clip * max(1, min(n, int(self.pitch_ws_cap_bytes // max(per_clip, 1)))), 8)
         ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        def ptrs(o):
+            return [_lib.ptr(o[k]) for k in first]
         if n and g.half_window >= 2:
             if second is None:
                 _lib.check(lib.rsaf_mshds_pitch(
-                    _lib.ptr(wav), _lib.ptr(ci_d), n, mx, _lib.ptr(gpeak), wp, wrp, params,
-                    _lib.ptr(frame_out), _lib.ptr(psi), _lib.ptr(end_state), _lib.ptr(sel_f), _lib.ptr(sel_s),
-                    _lib.ptr(stats), chp, _lib.ptr(ws), ws_bytes, _lib.stream_ptr(stream)), "rsaf_mshds_pitch")
+                    _lib.ptr(wav), _lib.ptr(ci_d), n, mx, _lib.ptr(gpeak), wp, wrp, params, *ptrs(first),
+                    chp, _lib.ptr(ws), ws_bytes, _lib.stream_ptr(stream)), "rsaf_mshds_pitch")
             else:
                 _lib.check(lib.rsaf_mshds_pitch_dual(
-                    _lib.ptr(wav), _lib.ptr(ci_d), n, mx, _lib.ptr(gpeak), wp, wrp, params,
-                    _lib.ptr(frame_out), _lib.ptr(psi), _lib.ptr(end_state), _lib.ptr(sel_f), _lib.ptr(sel_s),
-                    _lib.ptr(stats), float(voicing_threshold2), _lib.ptr(second["frame_out"]), _lib.ptr(second["psi"]),
-                    _lib.ptr(second["end_state"]), _lib.ptr(second["sel_freq"]), _lib.ptr(second["sel_strength"]),
-                    _lib.ptr(second["stats"]), chp, _lib.ptr(ws), ws_bytes, _lib.stream_ptr(stream)), "rsaf_mshds_pitch_dual")
+                    _lib.ptr(wav), _lib.ptr(ci_d), n, mx, _lib.ptr(gpeak), wp, wrp, params, *ptrs(first),
+                    float(voicing_threshold2), *ptrs(second), chp, _lib.ptr(ws), ws_bytes, _lib.stream_ptr(stream)),
+                    "rsaf_mshds_pitch_dual")
         else:
-            stats.fill_(float("nan"))
-            stats[:, 0] = 0
-            if second is not None:
-                second["stats"].fill_(float("nan"))
-                second["stats"][:, 0] = 0
+            for o in (first, second) if second is not None else (first,):
+                o["stats"].fill_(float("nan"))
+                o["stats"][:, 0] = 0
         if second is not None:
             second["stats"] = second["stats"][:n]
-        return {"geom": g, "ci": ci, "ci_dev": ci_d, "sel_freq": sel_f, "sel_strength": sel_s, "stats": stats[:n],
-                "frame_out": frame_out, "total_frames": total, "max_frames": mx, "second": second}
+        return {"geom": g, "ci": ci, "ci_dev": ci_d, "sel_freq": first["sel_freq"], "sel_strength": first["sel_strength"],
+                "stats": first["stats"][:n], "frame_out": first["frame_out"], "total_frames": total, "max_frames": mx,
+                "second": second}
 
     def intensity(self, wav, sample_offs, lengths, minimum_pitch, time_step, subtract_mean=True, stream=None, dom=None):
         import torch

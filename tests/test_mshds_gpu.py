@@ -157,12 +157,12 @@ def test_pitch_ac_few_candidates_replacement_rule(eng):
     assert np.array_equal(got > 0, p.frequency() > 0) and _rel(got, p.frequency()) < 1e-7
 
 
-def test_harmonicity_cc_mean(eng):
+def _check_harmonicity_cc_mean(eng, floors):
     import torch
     clips = [synth.synth_clip(120, 1.2), synth.synth_clip(121, 1.6)]
     wav, offs, lens = _pack(clips)
     gp = eng.clip_peaks(wav, offs, lens)
-    for floor in (100.0, 60.0):
+    for floor in floors:
         cc = eng.pitch(wav, offs, lens, gp, time_step=0.005, floor=floor, ceiling=8000.0, max_candidates=15,
                        silence_threshold=0.1, voicing_threshold=0.0, octave_cost=0.0, octave_jump_cost=0.0,
                        voiced_unvoiced_cost=0.0, periods=4.5, is_cc=True, refine_depth=700)
@@ -171,6 +171,15 @@ def test_harmonicity_cc_mean(eng):
         for i, c in enumerate(clips):
             ref = mo.extract_harmonicity(c, floor, None, 0.005)
             assert abs(h[i].item() - ref) < 1e-6 * max(1.0, abs(ref)), (floor, i, h[i].item(), ref)
+
+
+def test_harmonicity_cc_mean(eng):
+    _check_harmonicity_cc_mean(eng, (100.0, 60.0))     # one wave per frame: 1 024 and 2 048 complex points
+
+
+def test_harmonicity_cc_mean_workgroup_kernel(eng):
+    # window + lags = 2 200 samples: the 4 096-point transform, which only the workgroup kernel pitch_cc_kernel<12> runs
+    _check_harmonicity_cc_mean(eng, (40.0,))
 
 
 def test_spectral_moments_gated_by_pitch(eng):
