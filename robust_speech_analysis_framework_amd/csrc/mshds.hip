@@ -1,48 +1,23 @@
-// Praat-style analyses behind the MSHDS features, float64 kernels for gfx950.
+// Praat-style contour analyses behind the MSHDS features, float64 kernels for gfx950.
 //
-// Replaces the parselmouth/Praat calls of src/mshds_extractor.py (all ten helpers; formants, pulses and Ltas live in
-// mshds_voice.hip, the cepstral part in mshds_cpp.hip, what the three files share in mshds_common.h):
-//   _speechrate (:11-125), _pitch_values (:127-162), _extract_pitch (:164-183), _extract_intensity (:185-205),
-//   _extract_harmonicity (:207-225), _extract_Slope_Tilt (:227-251), _measureFormants (:303-338),
-//   _extract_Spectral_Moments (:340-376).
-// Algorithms: Boersma (1993) autocorrelation / cross-correlation pitch with sinc-interpolated candidates and the
-// Viterbi path finder; Praat's intensity (Kaiser-weighted mean square), Gaussian-window spectrogram + spectral
-// moments, cc pulse walker, pitch-corrected Ltas, Burg formants, de Jong & Wempe syllable nuclei.  Semantics =
+// Replaces these parselmouth/Praat calls of src/mshds_extractor.py: _speechrate (:11-125), _extract_intensity (:185-205),
+// the mean of _extract_harmonicity (:207-225) and _extract_Spectral_Moments (:340-376).  The pitch analysis they read
+// lives in mshds_pitch.hip, formants, pulses and Ltas in mshds_voice.hip, the cepstral part in mshds_cpp.hip, what the
+// files share in mshds_common.h.
+// Algorithms: Praat's intensity (Kaiser-weighted mean square), Gaussian-window spectrogram + spectral moments gated by
+// pitch definedness, the harmonics-to-noise mean over a cc pitch track, de Jong & Wempe syllable nuclei.  Semantics =
 // oracle/mshds_oracle.py (parity unpinned: Praat itself is not available).  Praat computes in double, so do these
-// kernels (MI355X: 78 TFLOP/s fp64, vector and matrix alike); discrete decisions (voicing, path) then agree with
-// the oracle.
+// kernels.
 //
-// Mapping: ONE WAVE per frame for the pitch correlations (wave_fft.h: 512 / 1 024 / 2 048 complex points in registers),
-// except the 4 096-point cross-correlation, which takes a 256-thread workgroup per 16 frames (Stockham FFT in LDS); the
-// normalised correlation rows go through the caller's workspace.  One wave per frame for the candidate lists; the
-// refinement runs in its own kernels: Chebyshev coefficients per cell on the fp64 matrix pipe where the array ends clip
-// the depth, then Brent's search with one candidate per lane.  One wave per frame for intensity and the 1 024-point
-// spectrogram slice, one wave per clip for the path finder, the speech rate and the per-clip statistics.  Pitch host
-// side: one PitchPlan per call (checks + geometry, no HIP call), one function per launch family.
+// Mapping: one workgroup per clip for the global peak, one wave per frame for intensity and the 1 024-point spectrogram
+// slice (a workgroup per frame for other transform lengths), one wave per clip for the speech rate and the per-clip
+// statistics.
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <vector>
 
 #include "mshds_common.h"      // FMA contraction is off from there on
 
 namespace rsaf {
 namespace mshds {
-
-constexpr int MAXC = 16;            // candidate slots per frame (max_candidates <= 15)
-constexpr int MAX_MAXIMA = 96;      // local maxima considered per frame (in ascending lag order)
-
-
-struct PitchParams {
-    double dt, min_pitch, ceiling, voicing_thr, octave_cost, dt_window;
-    int cheb_all_full;      // no candidate of this analysis can have its interpolation depth clipped by the array ends
-    int cheb_clipped;       // the Chebyshev table is followed by the tables of the clipped depths 1 .. refine_depth - 1
-    int nsamp_window, half_window, nsamp_period, half_period, min_lag, max_lag, brent_ixmax, max_cand;
-    int refine_depth, is_cc;
-    int nfft;               // AC: FFT length, the smallest power of two >= 1.5 nsamp_window (Praat's nsampFFT)
-    double voicing_thr2;    // >= 0: also emit the candidate lists for this (lower) voicing threshold into out2
-    int debug_stop;         // profiling aid (env RSAF_PITCH_STOP): leave the frame kernel after phase k; 0 = run all
-};
 
 // ---- per-clip mean and global peak |x - mean| ------------------------------------------------------
 __global__ __launch_bounds__(256) void clip_peak_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
@@ -133,1637 +108,6 @@ __global__ __launch_bounds__(256) void intensity_kernel(const float* __restrict_
     if (lane == 0) {
         const double v = sx / sw / 4.0e-10;
         out[c.frame_off + f] = v < 1e-30 ? -300.0 : 10.0 * log10(v);
-    }
-}
-
-// ---- pitch candidates per frame (AC: Hanning-windowed autocorrelation; CC: forward cross-correlation) --
-// dynamic LDS: seg[seg_len] doubles, r[2*brent_ixmax+1] doubles
-struct FrameOut {     // per frame, written contiguously: intensity, ncand, freq[MAXC], strength[MAXC]
-    double intensity;
-    double ncand;
-    double freq[MAXC];
-    double strength[MAXC];
-};
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-// stored half-width of the candidate kernel's correlation array (see pitch_cand_kernel)
-// [lo, hi] = the lags the candidate kernel can touch: the candidates' lags widened by the interpolation depth, never
-// beyond 2 L + 2 (zeros past the non-zero range |lag| <= L that a tap loop may still multiply) nor the array itself
-__host__ __device__ inline void pitch_r_range(int rc, int L, int min_lag, int max_lag, int depth, int* lo, int* hi) {
-    const int w = 2 * L + 2, span = w < rc ? w : rc;
-    const int lag_lo = min_lag > 2 ? min_lag : 2;
-    int lag_hi = max_lag - 1;
-    if (lag_hi > rc - 1) lag_hi = rc - 1;
-    const int d = depth > 30 ? depth : 30;
-    int a = lag_lo - d - 3, b = lag_hi + d + 3;
-    *lo = a < -span ? -span : a;
-    *hi = b > span ? span : b;
-}
-// ---- sinc interpolation as a polynomial in the fractional position -----------------------------------------
-// Between two samples the depth-d interpolation is S(b + frac) = sum_o W_o(frac) y[b + o], o = -(d-1) .. d, and
-// every weight W_o is a smooth function of frac in [0, 1] alone (as long as the depth is not clipped by the
-// array ends).  With the degree-15 Chebyshev coefficients of the weights tabulated once on the host
-// (cheb[o + d - 1][j]), the 16 coefficients of S on a cell cost one pass over the taps, after which every Brent
-// evaluation is a 16-term Clenshaw recurrence instead of 2d reciprocal-and-cosine terms.  The fit error
-// (< 1e-12) is below the rounding of the direct formula near integer positions.
-constexpr int NCH = 16;
-
-__device__ __forceinline__ double cheb_eval(const double* __restrict__ c, double frac) {
-    const double t = 2.0 * frac - 1.0, t2 = 2.0 * t;
-    double b1 = 0.0, b2 = 0.0;
-#pragma unroll
-    for (int j = NCH - 1; j >= 1; --j) { const double b0 = fma(t2, b1, c[j] - b2); b2 = b1; b1 = b0; }
-    return fma(t, b1, c[0] - b2);
-}
-
-// Praat NUMimproveMaximum (sinc) on the two cells around the 0-based integer position x0; P = [2][NCH] coefficients
-// (cell 0 = [x0-1, x0], cell 1 = [x0, x0+1]).  One lane per candidate; the loop runs while any lane is active.
-// The 2 x 16 coefficients of the lane's candidate stay in registers for the whole search: an evaluation is then a
-// per-coefficient select and ONE dependent multiply-add per Clenshaw step (the subtraction c_j - b_{j+2} does not wait
-// for b_{j+1}); reading the cell's row from LDS per evaluation put a memory round trip in front of every chain.
-__device__ void improve_max_cheb(const double* __restrict__ Pc, int x0, bool live, double& xm, double& ym) {
-    const double SQRT_EPS = 1.4901161193847656e-08, TOL3 = 1e-10 / 3.0;
-    const double ix1 = (double)x0 + 1.0;                    // 1-based like Praat
-    double c0[NCH], c1[NCH];
-#pragma unroll
-    for (int j = 0; j < NCH; ++j) { c0[j] = Pc[j]; c1[j] = Pc[NCH + j]; }
-    auto f = [&](double v1) {                               // v1: 1-based position in [ix1-1, ix1+1]
-        double fl = floor(v1);
-        double cell = fl - (ix1 - 1.0);
-        cell = cell < 0.0 ? 0.0 : (cell > 1.0 ? 1.0 : cell);
-        const double frac = v1 - (ix1 - 1.0 + cell);
-        const bool hi = cell > 0.5;
-        const double t = 2.0 * frac - 1.0, t2 = 2.0 * t;
-        double b1 = 0.0, b2 = 0.0;
-#pragma unroll
-        for (int j = NCH - 1; j >= 1; --j) { const double b0 = fma(t2, b1, (hi ? c1[j] : c0[j]) - b2); b2 = b1; b1 = b0; }
-        return -fma(t, b1, (hi ? c1[0] : c0[0]) - b2);
-    };
-    double a = ix1 - 1.0, b = ix1 + 1.0;
-    double v = a + GOLD * (b - a);
-    double fv = f(v);
-    double x = v, w = v, fx = fv, fw = fv;
-    bool active = live;
-    for (int it = 0; it < 60; ++it) {
-        const double rng = b - a, mid = 0.5 * (a + b);
-        const double tol_act = SQRT_EPS * fabs(x) + TOL3;
-        if (fabs(x - mid) + 0.5 * rng <= 2.0 * tol_act) active = false;
-        if (!__any(active)) break;
-        double step = GOLD * (x < mid ? b - x : a - x);
-        if (fabs(x - w) >= tol_act) {
-            const double t = (x - w) * (fx - fv);
-            double q = (x - v) * (fx - fw);
-            double p = (x - v) * q - (x - w) * t;
-            q = 2.0 * (q - t);
-            if (q > 0.0) p = -p; else q = -q;
-            if (fabs(p) < fabs(step * q) && p > q * (a - x + 2.0 * tol_act) && p < q * (b - x - 2.0 * tol_act))
-                step = p / q;
-        }
-        if (fabs(step) < tol_act) step = step > 0.0 ? tol_act : -tol_act;
-        const double tt = x + step;
-        const double ft = f(tt);
-        if (active) {
-            if (ft <= fx) {
-                if (tt < x) b = x; else a = x;
-                v = w; w = x; x = tt;
-                fv = fw; fw = fx; fx = ft;
-            } else {
-                if (tt < x) a = tt; else b = tt;
-                if (ft <= fw || w == x) { v = w; w = tt; fv = fw; fw = ft; }
-                else if (ft <= fv || v == x || v == w) { v = tt; fv = ft; }
-            }
-        }
-    }
-    xm = x - 1.0;
-    ym = -fx;
-}
-
-struct RefineArgs {
-    const double* r; int RN, RC, depth, nz_lo, nz_hi, ncand;
-    const int* place; double* cf; double* cs;
-};
-// refine every kept candidate: maximise the sinc-interpolated correlation, 256/G candidates per round
-template <int G, bool RECUR>
-__device__ void refine_candidates(const RefineArgs& A, int tid, int nthreads) {
-    const int lane = tid & 63, lg = lane & (G - 1), gidx = (tid >> 6) * (64 / G) + lane / G;
-    __syncthreads();
-    for (int kb = 1; kb < A.ncand; kb += nthreads / G) {
-        const int k = kb + gidx;
-        const bool live = k < A.ncand;
-        double xm, ym;
-        improve_max_group<G, RECUR>(A.r, A.RN, (double)(A.place[live ? k : 1] + A.RC), A.depth, A.nz_lo, A.nz_hi, lg,
-                                    live, xm, ym);
-        if (ym > 1.0) ym = 1.0 / ym;
-        if (live && lg == 0) { A.cf[k] = 1.0 / DXS / (xm - A.RC); A.cs[k] = ym; }
-    }
-}
-
-// ---- Stockham FFT of the workgroup cross-correlation kernel -------------------------------------------------------
-// A complex transform of M points as a Stockham autosort FFT (radix 4, a final radix 2 when M is not a power of 4):
-// natural order in and out, ping-pong between two LDS buffers, 256 threads.  Twiddles W_N^k = exp(-2 pi i k / N),
-// k < N / 2, come from a table built on the host in double precision.
-
-__device__ __forceinline__ double2_t cmul(double2_t a, double2_t b) {
-    return double2_t{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x};
-}
-__device__ __forceinline__ double2_t tw_at(const double2_t* __restrict__ tw, int t, int M) {   // W_N^t, 0 <= t < N
-    const bool neg = t >= M;
-    const double2_t w = tw[neg ? t - M : t];
-    return neg ? double2_t{-w.x, -w.y} : w;
-}
-
-// The transform length is a template parameter: the stages unroll, and for M <= 1024 every twiddle a thread needs
-// (a function of the stage and the thread only) is fetched ONCE, in front of the frame's first pass over the samples, and
-// kept in registers; the table loads (L2 latency) no longer sit between the barriers of every stage.
-template <int LOG2M>
-struct FftPlan {
-    static constexpr int M = 1 << LOG2M, N = 2 * M;
-    static constexpr int N4 = LOG2M / 2;                    // radix-4 stages
-    static constexpr bool HAS2 = (LOG2M & 1) != 0;          // one radix-2 stage behind them
-    static constexpr int T4 = M / 4, T2 = M / 2;
-    static constexpr int BPT4 = T4 > 256 ? T4 / 256 : 1, BPT2 = T2 > 256 ? T2 / 256 : 1;
-    static constexpr bool PRE = LOG2M <= 11;                // twiddles in registers
-    static constexpr int NTW4 = PRE && N4 > 1 ? (N4 - 1) * BPT4 * 3 : 1, NTW2 = PRE && HAS2 ? BPT2 : 1;
-};
-
-template <int LOG2M>
-struct FftTw {
-    double2_t w4[FftPlan<LOG2M>::NTW4];
-    double2_t w2[FftPlan<LOG2M>::NTW2];
-};
-
-template <int LOG2M>
-__device__ __forceinline__ void fft_load_twiddles(FftTw<LOG2M>& R, const double2_t* __restrict__ tw, int tid) {
-    using PL = FftPlan<LOG2M>;
-    if (!PL::PRE) return;
-#pragma unroll
-    for (int st = 1; st < PL::N4; ++st) {
-        const int Ns = 1 << (2 * st), step = PL::N / (Ns * 4);
-#pragma unroll
-        for (int bq = 0; bq < PL::BPT4; ++bq) {
-            const int j = tid + 256 * bq, t1 = (j & (Ns - 1)) * step;
-#pragma unroll
-            for (int r = 1; r <= 3; ++r) R.w4[((st - 1) * PL::BPT4 + bq) * 3 + r - 1] = tw_at(tw, (r * t1) & (PL::N - 1), PL::M);
-        }
-    }
-    if (PL::HAS2) {
-        const int Ns = 1 << (2 * PL::N4), step = PL::N / (Ns * 2);
-#pragma unroll
-        for (int bq = 0; bq < PL::BPT2; ++bq) R.w2[bq] = tw_at(tw, ((tid + 256 * bq) & (Ns - 1)) * step, PL::M);
-    }
-}
-
-// Between the first two radix-4 stages element e lives at slot fsw(e) (low two bits XOR-ed with bits 3-4): stage 0 writes
-// elements 4 j + r from lane j, a 64-byte lane stride = 4-way bank conflict for the 16-byte stores of 8 consecutive lanes
-// (PMC on the former workgroup autocorrelation kernel: 30 % of the LDS-active cycles were conflict cycles, the LDS busy 65 %);
-// swizzled, the 8 lanes hit 8 different slots of the 128-byte bank row, and the unit-stride reads of stage 1 stay
-// conflict-free (the permutation stays inside aligned blocks of 4 slots).  Every other pass sees the natural order.
-__device__ __forceinline__ int fsw(int e) { return e ^ ((e >> 3) & 3); }
-
-// forward complex FFT of M points from `a` (result in the returned buffer, `a` or `b`); every stage ends at a barrier
-template <int LOG2M>
-__device__ __forceinline__ double2_t* fft_stockham(double2_t* a, double2_t* b, const FftTw<LOG2M>& R,
-                                                   const double2_t* __restrict__ tw, int tid) {
-    using PL = FftPlan<LOG2M>;
-    constexpr int M = PL::M, N = PL::N, T4 = PL::T4, T2 = PL::T2;
-    double2_t* src = a;
-    double2_t* dst = b;
-#pragma unroll
-    for (int st = 0; st < PL::N4; ++st) {
-        const int Ns = 1 << (2 * st), step = N / (Ns * 4);
-#pragma unroll
-        for (int bq = 0; bq < PL::BPT4; ++bq) {
-            const int j = tid + 256 * bq;
-            if (T4 >= 256 || j < T4) {
-                const int k = j & (Ns - 1);
-                const bool rs = st == 1;                                  // stage 0 stored swizzled
-                double2_t v0 = src[rs ? fsw(j) : j], v1 = src[rs ? fsw(j + T4) : j + T4], v2 = src[rs ? fsw(j + 2 * T4) : j + 2 * T4],
-                          v3 = src[rs ? fsw(j + 3 * T4) : j + 3 * T4];
-                if (st > 0) {
-                    if (PL::PRE) {
-                        const int o = ((st - 1) * PL::BPT4 + bq) * 3;
-                        v1 = cmul(v1, R.w4[o]);
-                        v2 = cmul(v2, R.w4[o + 1]);
-                        v3 = cmul(v3, R.w4[o + 2]);
-                    } else {
-                        const int t1 = k * step;
-                        v1 = cmul(v1, tw_at(tw, t1, M));
-                        v2 = cmul(v2, tw_at(tw, 2 * t1, M));
-                        v3 = cmul(v3, tw_at(tw, 3 * t1, M));
-                    }
-                }
-                const double2_t a0 = v0 + v2, a1 = v0 - v2, a2 = v1 + v3;
-                const double2_t d = v1 - v3;
-                const double2_t a3 = double2_t{d.y, -d.x};             // (v1 - v3) * (-i)
-                const int j0 = ((j - k) << 2) + k;
-                const bool ws = st == 0 && PL::N4 >= 2;
-                dst[ws ? fsw(j0) : j0] = a0 + a2;
-                dst[ws ? fsw(j0 + Ns) : j0 + Ns] = a1 + a3;
-                dst[ws ? fsw(j0 + 2 * Ns) : j0 + 2 * Ns] = a0 - a2;
-                dst[ws ? fsw(j0 + 3 * Ns) : j0 + 3 * Ns] = a1 - a3;
-            }
-        }
-        __syncthreads();
-        double2_t* t_ = src; src = dst; dst = t_;
-    }
-    if (PL::HAS2) {                                                     // one radix-2 stage left (M = 2 * 4^a)
-        const int Ns = 1 << (2 * PL::N4), step = N / (Ns * 2);
-#pragma unroll
-        for (int bq = 0; bq < PL::BPT2; ++bq) {
-            const int j = tid + 256 * bq;
-            if (T2 >= 256 || j < T2) {
-                const int k = j & (Ns - 1);
-                const double2_t v0 = src[j];
-                const double2_t v1 = cmul(src[j + T2], PL::PRE ? R.w2[bq] : tw_at(tw, k * step, M));
-                const int j0 = ((j - k) << 1) + k;
-                dst[j0] = v0 + v1;
-                dst[j0 + Ns] = v0 - v1;
-            }
-        }
-        __syncthreads();
-        double2_t* t_ = src; src = dst; dst = t_;
-    }
-    return src;
-}
-
-// ---- CC: forward cross-correlation by FFT ----------------------------------------------------------------------
-// r(l) = sum_{j < nw} seg[j] seg[j + l], l = 0 .. L, is the linear cross-correlation of a = seg[0, nw) with b = seg[0, nw + L]:
-// both are real, so ONE complex FFT of N >= nw + L + 1 points on z = a + i b gives A[k] = (Z[k] + conj Z[N-k]) / 2 and
-// B[k] = (Z[k] - conj Z[N-k]) / 2i; C = conj(A) B is the spectrum of the correlation, Hermitian, and goes back through a
-// complex FFT of N / 2 points like the autocorrelation kernel's second transform.  (On the fp64 matrix pipe the direct sum
-// cost 0.6 M multiply-adds per frame at the 60 Hz floor; this is 0.17 M flops.)  Normalisation as before: r / sqrt(sumx2 sumy2(l))
-// with sumy2 from a block prefix sum of the squares, taken before the transforms reuse the buffers.
-constexpr int CC_FRAMES_PER_WG = 16;
-
-template <int LOG2N>
-__global__ __launch_bounds__(256) void pitch_cc_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
-                                                       const double* __restrict__ gpeak, const PitchParams P,
-                                                       const double2_t* __restrict__ tw1, const double2_t* __restrict__ tw2,
-                                                       double* __restrict__ rbuf, int rstride, int max_frames) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const ClipInfo c = ci[blockIdx.y];
-    if ((int)blockIdx.x * CC_FRAMES_PER_WG >= c.n_frames) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    constexpr int N = 1 << LOG2N, M = N >> 1;               // complex transform lengths: N forward, M back
-    const int nw = P.nsamp_window, L = P.max_lag;
-    const int seg_len = nw + L + 1;
-    FftTw<LOG2N> twa;                                       // tw1 = W_2N^k (k < N): twiddles of the N-point transform
-    FftTw<LOG2N - 1> twb;                                   // tw2 = W_N^k (k < M): the M-point transform and the spectrum pass
-    fft_load_twiddles<LOG2N>(twa, tw1, tid);
-    fft_load_twiddles<LOG2N - 1>(twb, tw2, tid);
-    constexpr int NPK = (M / 2) / 256 + 1;                  // spectrum pass: k = tid + 256 i <= M / 2
-    double2_t twp[NPK];
-#pragma unroll
-    for (int i = 0; i < NPK; ++i) twp[i] = tw2[tid + 256 * i <= M / 2 ? tid + 256 * i : 0];
-    double2_t* za = reinterpret_cast<double2_t*>(smem_raw);  // [N]
-    double2_t* zb = za + N;                                  // [N]
-    double* s_sy = reinterpret_cast<double*>(zb + N);        // [L + 1] sumy2(l)
-    double* s_red = s_sy + ((L + 2) & ~1);                   // [8]
-    double* s_val = s_red + 8;                               // [4]
-    double* s_scan = s_val + 4;                              // [16] wave totals of the four 256-lag chunks of the scan
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples;
-    const double gp = gpeak[blockIdx.y];
-    for (int f = blockIdx.x * CC_FRAMES_PER_WG; f < (int)(blockIdx.x + 1) * CC_FRAMES_PER_WG && f < c.n_frames; ++f) {
-    double* rb = rbuf + ((int64_t)blockIdx.y * max_frames + f) * rstride;   // r[0..L], then the intensity
-    const double t = c.t1 + f * P.dt;
-    const int64_t left = low_index(t, c.x1), right = left + 1;
-    // local mean over one longest period to each side (divisor 2*nsamp_period as in Praat)
-    {
-        int64_t s0 = right - P.nsamp_period, s1 = left + P.nsamp_period;
-        s0 = s0 < 0 ? 0 : (s0 > n - 1 ? n - 1 : s0);
-        s1 = s1 < 0 ? 0 : (s1 > n - 1 ? n - 1 : s1);
-        double s = 0.0;
-        for (int64_t i = s0 + tid; i <= s1; i += 256) s += (double)x[i];
-        s = group_sum<64>(s);
-        if (lane == 0) s_red[wv] = s;
-    }
-    __syncthreads();
-    const double local_mean = (s_red[0] + s_red[1] + s_red[2] + s_red[3]) / (2.0 * P.nsamp_period);
-    int loc_max_lag;
-    {
-        // Praat: startTime = t - 0.5 * (1 / minimumPitch + dt_window), dt_window = periods / minimumPitch
-        const double start_time = t - 0.5 * (1.0 / P.min_pitch + P.dt_window);
-        int64_t start = low_index(start_time, c.x1);
-        if (start < 0) start = 0;
-        int64_t span = L + nw;
-        if (span > n - start) span = n - start;
-        loc_max_lag = (int)(span - nw);
-        // one pass: z = a + i b, the local peak (|b| over half a longest period around the window centre) and sumx2 = sum a^2
-        int pa = P.half_window - P.half_period, pb = P.half_window + P.half_period;
-        pa = pa < 0 ? 0 : pa;
-        pb = pb > nw ? nw : pb;
-        double m = 0.0, sx = 0.0;
-        const float* xs = x + start;                          // start >= 0
-        const int avail = (int)((n - start) < (int64_t)seg_len ? (n - start) : (int64_t)seg_len);   // samples of seg inside the sound
-#pragma unroll 4
-        for (int j = tid; j < N; j += 256) {
-            const double v = j < avail ? ((double)xs[j] - local_mean) : 0.0;
-            za[j] = double2_t{j < nw ? v : 0.0, v};          // z = a + i b
-            if (j >= pa && j < pb) m = fmax(m, fabs(v));
-            if (j < nw) sx += v * v;
-        }
-        m = wave_max_dpp(m);
-        sx = group_sum<64>(sx);
-        if (lane == 0) { s_val[wv] = m; s_red[4 + wv] = sx; }
-    }
-    __syncthreads();
-    const double local_peak = fmax(fmax(s_val[0], s_val[1]), fmax(s_val[2], s_val[3]));
-    const double intensity = gp > 0.0 ? (local_peak > gp ? 1.0 : local_peak / gp) : 0.0;
-    const double sumx2 = (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]);
-    // sumy2(l) = sum_{j=l}^{l+nw-1} b_j^2 = sumx2 + sum_{i<l} (b_{i+nw}^2 - b_i^2): an inclusive scan over the L lags
-    {
-        constexpr int NQ = 4;                                 // L <= 1023
-        double inc[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = tid + 256 * q;                      // term i feeds sumy2(i + 1)
-            double d = 0.0;
-            if (i < L) { const double u = za[i + nw].y, w0 = za[i].y; d = u * u - w0 * w0; }
-            double sc = d;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const double t2 = __shfl_up(sc, o, 64); if (lane >= o) sc += t2; }
-            inc[q] = sc;
-            if (lane == 63) s_scan[4 * q + wv] = sc;
-        }
-        __syncthreads();
-        if (tid == 0) s_sy[0] = sumx2;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const int i = tid + 256 * q;
-            if (i < L) {
-                double off = 0.0;
-                for (int z = 0; z < 4 * q + wv; ++z) off += s_scan[z];
-                s_sy[i + 1] = sumx2 + (off + inc[q]);
-            }
-        }
-    }
-    if (P.debug_stop == 1) continue;
-
-    double2_t* Z = fft_stockham<LOG2N>(za, zb, twa, tw1, tid);
-    double2_t* Y = Z == za ? zb : za;
-    // C[k] = conj(A[k]) B[k]; Y[k] = (C[k] + conj C[M-k]) + i conj(W_N^k) (C[k] - conj C[M-k]), stored conjugated
-    auto spec = [&](int k) {                                 // C[k] for 0 <= k <= M
-        const double2_t zk = Z[k], zn = Z[(N - k) & (N - 1)];
-        const double2_t A = double2_t{0.5 * (zk.x + zn.x), 0.5 * (zk.y - zn.y)};
-        const double2_t Bm = double2_t{0.5 * (zk.y + zn.y), -0.5 * (zk.x - zn.x)};   // (Z[k] - conj Z[N-k]) / 2i
-        return double2_t{A.x * Bm.x + A.y * Bm.y, A.x * Bm.y - A.y * Bm.x};          // conj(A) * B
-    };
-#pragma unroll
-    for (int i = 0; i < NPK; ++i) {
-        const int k = tid + 256 * i;
-        if (k > M / 2) continue;
-        const double2_t ck = spec(k), cm = spec(M - k);
-        const double2_t w = twp[i];                          // W_N^k
-        {   // Y[k]
-            const double2_t su = double2_t{ck.x + cm.x, ck.y - cm.y}, di = double2_t{ck.x - cm.x, ck.y + cm.y};
-            // i conj(w) di = i (w.x - i w.y)(di.x + i di.y) = (w.y di.x - w.x di.y) ... real: -(w.x di.y - w.y di.x)?  expand:
-            // conj(w) di = (w.x di.x + w.y di.y) + i (w.x di.y - w.y di.x);  times i: -(w.x di.y - w.y di.x) + i (w.x di.x + w.y di.y)
-            const double2_t yy = double2_t{su.x - (w.x * di.y - w.y * di.x), su.y + (w.x * di.x + w.y * di.y)};
-            Y[k] = double2_t{yy.x, -yy.y};
-        }
-        if (k != 0 && k != M - k) {   // Y[M - k]: roles swapped, W_N^(M-k) = -conj(W_N^k), so conj(W_N^(M-k)) = -w
-            const double2_t su = double2_t{cm.x + ck.x, cm.y - ck.y}, di = double2_t{cm.x - ck.x, cm.y + ck.y};
-            // i * (-w) * di = -i (w.x + i w.y)(di.x + i di.y) = (w.x di.y + w.y di.x) - i (w.x di.x - w.y di.y)
-            const double2_t yy = double2_t{su.x + (w.x * di.y + w.y * di.x), su.y - (w.x * di.x - w.y * di.y)};
-            Y[M - k] = double2_t{yy.x, -yy.y};
-        }
-    }
-    __syncthreads();
-    const double* r = reinterpret_cast<const double*>(fft_stockham<LOG2N - 1>(Y, Y == za ? zb : za, twb, tw2, tid));
-    if (P.debug_stop == 2) continue;
-    // r[2 j] = Re, r[2 j + 1] = -Im of the (conjugated) output, times N
-    if (tid == 0) { rb[0] = 1.0; rb[L + 1] = intensity; }
-    const double inv_n = 1.0 / (double)N;
-    for (int l = 1 + tid; l <= L; l += 256) {
-        const double v = ((l & 1) ? -r[l] : r[l]) * inv_n;
-        const double den = sumx2 * s_sy[l];
-        rb[l] = (l <= loc_max_lag && den > 0.0) ? v / sqrt(den) : 0.0;
-    }
-    __syncthreads();                                        // the next frame overwrites the buffers
-    }
-}
-
-// ---- the two correlation kernels with ONE WAVE per frame (csrc/wave_fft.h) --------------------------------------
-// Transform lengths up to 2048 complex points (every analysis of the MSHDS feature scripts at 16 kHz; shorter transforms
-// are zero-padded up to 512 / 1024 points, which returns the same linear correlation) run here: the frame lives in the registers of one wavefront from the sample loads to the normalised correlation row.  The local
-// mean, the window, the local peak and sum x^2 are taken on the registers the transform starts from (wave reductions by
-// DPP, no LDS round trip, no workgroup barrier anywhere), the spectrum step evaluates every conjugate pair once, and only
-// the lags the candidate kernel reads are normalised and stored.  A wave takes WF_FRAMES consecutive frames so that its
-// five base twiddles are fetched once.
-constexpr int WF_FRAMES = 8;
-
-__device__ __forceinline__ wfft::cplx ld_tw(const double2_t* __restrict__ tw, int i) {
-    const double2_t w = tw[i];
-    return wfft::cplx{w.x, w.y};
-}
-// 1 / sqrt(d) for d > 0: hardware estimate + two Newton steps
-__device__ __forceinline__ double fast_rsqrt(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-    y = y * (1.5 - 0.5 * d * y * y);
-    y = y * (1.5 - 0.5 * d * y * y);
-    return y;
-}
-// inclusive prefix sum over the 64 lanes: four row_shr steps inside the rows of 16, the row totals through v_readlane
-__device__ __forceinline__ double wave_scan_incl(double v, int lane) {
-    v += dpp_f64<0x111>(v);
-    v += dpp_f64<0x112>(v);
-    v += dpp_f64<0x114>(v);
-    v += dpp_f64<0x118>(v);
-    const double t0 = readlane_f64(v, 15), t1 = readlane_f64(v, 31), t2 = readlane_f64(v, 47);
-    const int row = lane >> 4;
-    return v + (row == 0 ? 0.0 : (row == 1 ? t0 : (row == 2 ? t0 + t1 : (t0 + t1) + t2)));
-}
-
-// AC: Praat's Sound_to_Pitch (ac) transforms the windowed frame with an FFT of nsampFFT >= 1.5 nsamp_window points, squares
-// the spectrum and transforms back; so does pitch_ac_wave_kernel, in fp64: about 2.5 N log2 N flops per transform against
-// 2 nw L for the direct sum (nine times fewer at nw = 960, L = 512).  The real transform of N points is a complex transform
-// of S = N / 2 points on z[j] = x[2 j] + i x[2 j + 1] (the zero-padded frame), a pass that separates X[k], squares it and
-// packs the even spectrum P back into S complex points, and a second complex transform whose output is r[2 j] + i r[2 j + 1].
-template <int R>
-__global__ __launch_bounds__(64, R == 32 ? 2 : (R == 16 ? 3 : 4)) void pitch_ac_wave_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
-                                                           const double* __restrict__ gpeak, const double* __restrict__ win,
-                                                           const double* __restrict__ wr, const PitchParams P,
-                                                           const double2_t* __restrict__ tw, double* __restrict__ rbuf,
-                                                           int rstride, int max_frames) {
-    using namespace wfft;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* lds = reinterpret_cast<double*>(smem_raw);
-    const ClipInfo c = ci[blockIdx.y];
-    const int f0 = blockIdx.x * WF_FRAMES;
-    if (f0 >= c.n_frames) return;
-    const int lane_ = threadIdx.x;
-    constexpr int S = 64 * R, N = 2 * S, L2 = 64 / R;        // tw = W_N^k, k < S
-    const int nw = P.nsamp_window, L = P.brent_ixmax;
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples;
-    const double gp = gpeak[blockIdx.y];
-    LdsMem mem{lds};
-    const int f1 = f0 + WF_FRAMES < c.n_frames ? f0 + WF_FRAMES : c.n_frames;
-    int pa = P.half_window - P.half_period, pb = P.half_window + P.half_period;
-    pa = pa < 0 ? 0 : pa;
-    pb = pb > nw ? nw : pb;
-#pragma unroll 1
-    for (int f = f0; f < f1; ++f) {
-        // Everything below that depends only on the lane (addresses, range predicates, the powers of the base twiddles) is
-        // loop-invariant, and hoisted out of the frame loop it costs more registers than the frame itself: the lane index and
-        // the base twiddles pass through an empty asm so that they count as redefined per frame.
-        int lane = lane_;
-        asm volatile("" : "+v"(lane));
-        // base twiddles (three 16-byte loads per frame, L1): W_S^lane = W_N^(2 lane), W_64^(lane % L2), W_N^lane
-        cplx w_s = ld_tw(tw, 2 * lane), w_b = ld_tw(tw, (lane % L2) * (N / 64));
-        double* rb = rbuf + ((int64_t)blockIdx.y * max_frames + f) * rstride;   // r[0..L], then the intensity
-        const double t = c.t1 + f * P.dt;
-        const int left = (int)low_index(t, c.x1), right = left + 1;
-        // The raw samples first, as the S complex points z[k] = x[2 k] + i x[2 k + 1], k = lane + 64 m: every load of the frame is
-        // in flight at once.  (A separate pass for the local mean in front of them made the frame wait for memory twice.)
-        const int start = right - P.half_window;
-        const bool inside = start >= 0 && start + nw <= n;        // the window lies inside the sound
-        // (Loads are unconditional, on clamped indices, and what lies outside the window is zeroed afterwards: a load inside a
-        // branch is waited for inside that branch, and the frame would cross the memory latency once per register.)
-        cplx v[R];
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            const int j = 128 * m + 2 * lane;
-            int i0 = start + j, i1 = i0 + 1;
-            i0 = i0 < 0 ? 0 : (i0 > n - 1 ? n - 1 : i0);
-            i1 = i1 < 0 ? 0 : (i1 > n - 1 ? n - 1 : i1);
-            v[m] = cplx{(double)x[i0], (double)x[i1]};
-        }
-        // local mean over one longest period to each side (divisor 2*nsamp_period as in Praat): from the registers when the
-        // window holds that range (always, for windows of two periods and more away from the ends of the sound)
-        double local_mean;
-        {
-            int s0 = right - P.nsamp_period, s1 = left + P.nsamp_period;
-            s0 = s0 < 0 ? 0 : (s0 > n - 1 ? n - 1 : s0);
-            s1 = s1 < 0 ? 0 : (s1 > n - 1 ? n - 1 : s1);
-            double sm = 0.0;
-            if (inside && s0 >= start && s1 < start + nw) {
-                const int a0 = s0 - start, a1 = s1 - start;
-#pragma unroll
-                for (int m = 0; m < R; ++m) {
-                    const int jb = 128 * m, j = jb + 2 * lane;
-                    if (jb + 127 >= a0 && jb <= a1) {
-                        if (j >= a0 && j <= a1) sm += v[m].x;
-                        if (j + 1 >= a0 && j + 1 <= a1) sm += v[m].y;
-                    }
-                }
-            } else {
-                for (int i = s0 + lane; i <= s1; i += 256) {      // four loads in flight
-                    const float q0 = x[i], q1 = i + 64 <= s1 ? x[i + 64] : 0.f, q2 = i + 128 <= s1 ? x[i + 128] : 0.f,
-                                q3 = i + 192 <= s1 ? x[i + 192] : 0.f;
-                    sm += ((double)q0 + (double)q1) + ((double)q2 + (double)q3);
-                }
-            }
-            local_mean = group_sum<64>(sm) / (2.0 * P.nsamp_period);
-        }
-        // the windowed frame; the local peak over half a longest period around the window centre
-        constexpr int WCH = R == 32 ? 8 : 4;
-        double pk = 0.0;
-#pragma unroll
-        for (int mc = 0; mc < R; mc += WCH) {                     // WCH registers' window loads in flight
-            double2_t w2[WCH];
-#pragma unroll
-            for (int u = 0; u < WCH; ++u) {
-                const int j = 128 * (mc + u) + 2 * lane;
-                w2[u] = *reinterpret_cast<const double2_t*>(win + (j < nw ? j : nw - 2));      // nw is even
-            }
-#pragma unroll
-            for (int u = 0; u < WCH; ++u) {
-                const int m = mc + u, jb = 128 * m, j = jb + 2 * lane;
-                const bool on = j < nw;
-                const double e0 = on ? (v[m].x - local_mean) * w2[u].x : 0.0, e1 = on ? (v[m].y - local_mean) * w2[u].y : 0.0;
-                if (jb + 127 >= pa && jb < pb) {                  // uniform
-                    if (j >= pa && j < pb) pk = fmax(pk, fabs(e0));
-                    if (j + 1 >= pa && j + 1 < pb) pk = fmax(pk, fabs(e1));
-                }
-                v[m] = cplx{e0, e1};
-            }
-            asm volatile("" ::: "memory");
-        }
-        const double local_peak = wave_max_dpp(pk);
-        const double intensity = gp > 0.0 ? (local_peak > gp ? 1.0 : local_peak / gp) : 0.0;
-        if (P.debug_stop == 1) continue;
-        // transform, |X|^2 repacked (conjugated), transform: r[2 k] = Re, r[2 k + 1] = -Im of element k
-        wave_fft<R>(v, lds, lane, w_s, w_b);
-        {
-            ac_spec_store<R>(v, mem, lane);
-            wave_sync();
-            const cplx y_half = ac_spec_pairs<R>(v, mem, lane, ld_tw(tw, lane));
-            wave_sync();
-            ac_spec_load<R>(v, mem, lane, y_half);
-            wave_sync();
-        }
-        // (the powers of the base twiddles are recomputed: kept from the first transform they would cost 120 registers)
-        asm volatile("" : "+v"(lane));
-        w_s = ld_tw(tw, 2 * lane);
-        w_b = ld_tw(tw, (lane % L2) * (N / 64));
-        wave_fft<R>(v, lds, lane, w_s, w_b);
-        if (P.debug_stop == 2) continue;
-        const double r0 = readlane_f64(v[0].x, 0);
-        if (lane == 0) { rb[0] = 1.0; rb[L + 1] = intensity; }
-        double wa[8], wb[8];                                      // L <= 1023: lags 2 (lane + 64 m), m < 8; loads first
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int l0 = 2 * (lane + 64 * m);
-            wa[m] = wr[l0 < L ? l0 : L];
-            wb[m] = wr[l0 + 1 < L ? l0 + 1 : L];
-        }
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int l0 = 2 * (lane + 64 * m);
-            if (128 * m > L) break;                               // uniform
-            if (l0 >= 1 && l0 <= L) rb[l0] = r0 > 0.0 ? v[m].x * fast_rcp(r0 * wa[m]) : 0.0;
-            if (l0 + 1 <= L) rb[l0 + 1] = r0 > 0.0 ? -v[m].y * fast_rcp(r0 * wb[m]) : 0.0;
-        }
-    }
-}
-
-template <int R>
-__global__ __launch_bounds__(64, R == 32 ? 2 : 3) void pitch_cc_wave_kernel(const float* __restrict__ wav, const ClipInfo* __restrict__ ci,
-                                                           const double* __restrict__ gpeak, const PitchParams P,
-                                                           const double2_t* __restrict__ tw, double* __restrict__ rbuf,
-                                                           int rstride, int max_frames) {
-    using namespace wfft;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* lds = reinterpret_cast<double*>(smem_raw);
-    double* s_sy = lds + Plan<R>::LDS_DOUBLES;                 // [L + 1] sumy2(l)
-    const ClipInfo c = ci[blockIdx.y];
-    const int f0 = blockIdx.x * WF_FRAMES;
-    if (f0 >= c.n_frames) return;
-    const int lane_ = threadIdx.x;
-    constexpr int S = 64 * R, H = R / 2, L2 = 64 / R, L2H = 64 / H;   // tw = W_S^k, k < S / 2; transforms of S, then S / 2 points
-    const int nw = P.nsamp_window, L = P.max_lag;
-    const int seg_len = nw + L + 1;
-    const float* x = wav + c.sample_off;
-    const int n = c.n_samples;
-    const double gp = gpeak[blockIdx.y];
-    LdsMem mem{lds};
-    const int f1 = f0 + WF_FRAMES < c.n_frames ? f0 + WF_FRAMES : c.n_frames;
-    int pa = P.half_window - P.half_period, pb = P.half_window + P.half_period;
-    pa = pa < 0 ? 0 : pa;
-    pb = pb > nw ? nw : pb;
-#pragma unroll 1
-    for (int f = f0; f < f1; ++f) {
-        int lane = lane_;                                          // redefined per frame: see pitch_ac_wave_kernel
-        asm volatile("" : "+v"(lane));
-        double* rb = rbuf + ((int64_t)blockIdx.y * max_frames + f) * rstride;   // r[0..L], then the intensity
-        const double t = c.t1 + f * P.dt;
-        const int left = (int)low_index(t, c.x1), right = left + 1;
-        // Praat: startTime = t - 0.5 * (1 / minimumPitch + dt_window), dt_window = periods / minimumPitch
-        const double start_time = t - 0.5 * (1.0 / P.min_pitch + P.dt_window);
-        int64_t start64 = low_index(start_time, c.x1);
-        if (start64 < 0) start64 = 0;
-        const int start = (int)start64;
-        int span = L + nw;
-        if (span > n - start) span = n - start;
-        const int loc_max_lag = span - nw;
-        const int avail = n - start < seg_len ? n - start : seg_len;      // samples of the segment inside the sound
-        // every load of the frame first: the raw segment b[j], j = lane + 64 m, and the samples nw behind the first L of them
-        // (for the running sum below)
-        // (unconditional loads on clamped indices, zeroed afterwards: see pitch_ac_wave_kernel)
-        cplx v[R];
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            int gi = start + lane + 64 * m;
-            gi = gi > n - 1 ? n - 1 : gi;
-            v[m] = cplx{0.0, (double)x[gi]};
-        }
-        float tail[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {                             // L <= 1023
-            int gi = start + lane + 64 * q + nw;
-            gi = gi > n - 1 ? n - 1 : gi;
-            tail[q] = x[gi];
-        }
-        // local mean over one longest period to each side (divisor 2*nsamp_period as in Praat), from the registers when the
-        // segment holds that range
-        double local_mean;
-        {
-            int s0 = right - P.nsamp_period, s1 = left + P.nsamp_period;
-            s0 = s0 < 0 ? 0 : (s0 > n - 1 ? n - 1 : s0);
-            s1 = s1 < 0 ? 0 : (s1 > n - 1 ? n - 1 : s1);
-            double sm = 0.0;
-            if (s0 >= start && s1 < start + avail) {
-                const int a0 = s0 - start, a1 = s1 - start;
-#pragma unroll
-                for (int m = 0; m < R; ++m) {
-                    const int jb = 64 * m, j = jb + lane;
-                    if (jb + 63 >= a0 && jb <= a1 && j >= a0 && j <= a1) sm += v[m].y;
-                }
-            } else {
-                for (int i = s0 + lane; i <= s1; i += 256) {      // four loads in flight
-                    const float q0 = x[i], q1 = i + 64 <= s1 ? x[i + 64] : 0.f, q2 = i + 128 <= s1 ? x[i + 128] : 0.f,
-                                q3 = i + 192 <= s1 ? x[i + 192] : 0.f;
-                    sm += ((double)q0 + (double)q1) + ((double)q2 + (double)q3);
-                }
-            }
-            local_mean = group_sum<64>(sm) / (2.0 * P.nsamp_period);
-        }
-        // z = a + i b: b = the segment minus the mean, a = its first nw samples; the local peak and sumx2 = sum a^2 on the way
-        double pk = 0.0, sx = 0.0;
-#pragma unroll
-        for (int m = 0; m < R; ++m) {
-            const int jb = 64 * m, j = jb + lane;
-            double e = 0.0, a = 0.0;
-            if (j < avail) e = v[m].y - local_mean;
-            if (j < nw) a = e;
-            if (jb + 63 >= pa && jb < pb && j >= pa && j < pb) pk = fmax(pk, fabs(e));
-            sx = fma(a, a, sx);
-            v[m] = cplx{a, e};
-        }
-        const double local_peak = wave_max_dpp(pk);
-        const double intensity = gp > 0.0 ? (local_peak > gp ? 1.0 : local_peak / gp) : 0.0;
-        const double sumx2 = group_sum<64>(sx);
-        // sumy2(l) = sum_{j=l}^{l+nw-1} b_j^2 = sumx2 + sum_{i<l} (b_{i+nw}^2 - b_i^2): a running sum over the L lags, 64 at a time
-        {
-            double carry = 0.0;
-            if (lane == 0) s_sy[0] = sumx2;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (64 * q >= L) break;                            // uniform
-                const int i = lane + 64 * q;
-                double d = 0.0;
-                if (i < L) {
-                    const double u = i + nw < avail ? (double)tail[q] - local_mean : 0.0, w0 = v[q].y;
-                    d = u * u - w0 * w0;
-                }
-                const double sc = wave_scan_incl(d, lane);
-                if (i < L) s_sy[i + 1] = sumx2 + (carry + sc);
-                carry += readlane_f64(sc, 63);
-            }
-        }
-        if (P.debug_stop == 1) continue;
-        const cplx w_s1 = ld_tw(tw, lane);                        // W_S^lane; W_64^(lane % L2) = W_S^(R (lane % L2))
-        wave_fft<R>(v, lds, lane, w_s1, ld_tw(tw, (lane % L2) * R));
-        // C = conj(A) B repacked into the S / 2 points of the transform back (wave_fft.h)
-        cplx y[H];
-        cc_spec_store<R>(v, mem, lane);
-        wave_sync();
-        const cplx y_half = cc_spec_pairs<R>(v, y, mem, lane, w_s1);
-        wave_sync();
-        cc_spec_load<R>(y, mem, lane, y_half);
-        wave_sync();
-        wave_fft<H>(y, lds, lane, ld_tw(tw, 2 * lane), ld_tw(tw, (lane % L2H) * R));   // W_(S/2)^lane, W_64^(lane % (2 L2))
-        if (P.debug_stop == 2) continue;
-        // r[2 k] = Re, r[2 k + 1] = -Im of element k, times S; normalised by sqrt(sumx2 sumy2(l))
-        if (lane == 0) { rb[0] = 1.0; rb[L + 1] = intensity; }
-        const double inv_n = 1.0 / (double)S;
-        constexpr int MO = H < 8 ? H : 8;                         // L <= 1023: lags 2 (lane + 64 m), m < 8
-        double ya[MO], yb[MO];
-#pragma unroll
-        for (int m = 0; m < MO; ++m) {
-            const int l0 = 2 * (lane + 64 * m);
-            ya[m] = s_sy[l0 < L ? l0 : L];
-            yb[m] = s_sy[l0 + 1 < L ? l0 + 1 : L];
-        }
-#pragma unroll
-        for (int m = 0; m < MO; ++m) {
-            const int l0 = 2 * (lane + 64 * m);
-            if (128 * m > L) break;                               // uniform
-            if (l0 >= 1 && l0 <= L) {
-                const double den = sumx2 * ya[m];
-                rb[l0] = (l0 <= loc_max_lag && den > 0.0) ? (y[m].x * inv_n) * fast_rsqrt(den) : 0.0;
-            }
-            if (l0 + 1 <= L) {
-                const double den = sumx2 * yb[m];
-                rb[l0 + 1] = (l0 + 1 <= loc_max_lag && den > 0.0) ? (-y[m].y * inv_n) * fast_rsqrt(den) : 0.0;
-            }
-        }
-        wave_sync();                                              // the next frame rewrites s_sy
-    }
-}
-
-// Kernel 2 of 2: one wave per frame.  Reads the frame's normalised correlation row, finds the local maxima,
-// estimates them (parabola + sinc 30), builds the candidate list(s) with Praat's replacement rule and refines
-// every kept candidate with Brent's method.  All phases are single-wave, so nothing waits at a workgroup barrier
-// and ~10 frames are resident per CU.
-constexpr int CT = 64;          // threads of the candidate kernel
-// Deferred refinement.  The Brent search of a frame keeps at most 15 of a wave's 64 lanes busy on a chain of dependent
-// float64 operations, and the coefficient build of a cell whose depth the array ends clip needs that cell's own table.
-// With `hdr` given the candidate kernel therefore stops at the candidate lists: it leaves a 128-byte record per frame
-// (flags, list lengths, the lists' lags) and - unless the cells' coefficients are built per cell by
-// pitch_cell_coef_kernel (`grouped`) - the Chebyshev coefficients of the candidates' cells in the workspace;
-// pitch_brent_kernel then refines one candidate per lane (the candidates of sixteen frames packed into a wave).
-constexpr int HDR_INTS = 32;                    // [0] flags, [1] length of list A, [2] of list B, [4..11] lags of A (16 x u16),
-                                                // [12..19] lags of B, [20..23] for every slot of B: the slot of A with the same lag
-constexpr int PC_DOUBLES = MAXC * 2 * NCH;      // per frame and list: [slot][cell][coefficient]
-constexpr int HDR_A_DEFER = 1, HDR_B_DEFER = 2, HDR_B_COPY = 4;
-struct DeferArgs {
-    int* hdr;            // nullptr: everything in the candidate kernel (the form before round 4, kept as the A/B reference)
-    double* pc_a;        // coefficients of the list that is refined first (the lower voicing threshold of a dual pass)
-    double* pc_b;        // coefficients of the other list of a dual pass (only written when it holds a lag the first lacks)
-    int grouped;         // 1: pitch_cell_coef_kernel builds pc_a
-};
-__global__ __launch_bounds__(64) void pitch_cand_kernel(const ClipInfo* __restrict__ ci, const double* __restrict__ gpeak,
-                                                        const PitchParams P, const double* __restrict__ rbuf, int rstride,
-                                                        int max_frames, FrameOut* __restrict__ out,
-                                                        FrameOut* __restrict__ out2, const double* __restrict__ cheb,
-                                                        const DeferArgs DA) {
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    const ClipInfo c = ci[blockIdx.y];
-    const int f = blockIdx.x;
-    if (f >= c.n_frames) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = 0;
-    const int L = P.is_cc ? P.max_lag : P.brent_ixmax;
-    const int RC = P.brent_ixmax;                   // centre index of r
-    const int RN = 2 * P.brent_ixmax + 1;
-    // r is Praat's symmetric array of 2 ixmax + 1 lags, but only |lag| <= L is non-zero and nothing reads beyond
-    // the candidates' lags widened by the interpolation depth (and never past 2 L + 1): only that range is stored,
-    // through a base pointer shifted so that the indices stay Praat's
-    // (with the per-cell coefficient kernel behind it, this kernel reads no further than its depth-30 first estimates)
-    int r_lo, r_hi;
-    pitch_r_range(RC, L, P.min_lag, P.max_lag, (DA.hdr && DA.grouped) ? 30 : P.refine_depth, &r_lo, &r_hi);
-    double* r_store = reinterpret_cast<double*>(smem_raw);
-    double* r = r_store - (RC + r_lo);
-    double* s_mfreq = r_store + ((r_hi - r_lo + 2) & ~1);   // [MAX_MAXIMA]
-    double* s_mstr = s_mfreq + MAX_MAXIMA;          // [MAX_MAXIMA]
-    double* s_mloc = s_mstr + MAX_MAXIMA;           // [MAX_MAXIMA] strength - octave cost (Praat's "local strength")
-    double* s_cf = s_mloc + MAX_MAXIMA;             // [MAXC]
-    double* s_cs = s_cf + MAXC;                     // [MAXC]
-    double* s_cloc = s_cs + MAXC;                   // [MAXC]
-    int* s_maxlag = reinterpret_cast<int*>(s_cloc + MAXC);   // [MAX_MAXIMA]
-    int* s_place = s_maxlag + MAX_MAXIMA;           // [MAXC]
-    int* s_place2 = s_place + MAXC;                 // [MAXC]  second (lower-threshold) list
-    int* s_cnt = s_place2 + MAXC;                   // [0] = nmax, [1] = ncand, [2] = ncand2, [3] = missing
-    double* s_cf2 = reinterpret_cast<double*>(s_cnt + 4);   // [MAXC]
-    double* s_cs2 = s_cf2 + MAXC;                   // [MAXC]
-    double* s_cloc2 = s_cs2 + MAXC;                 // [MAXC]
-    double* s_part = s_cloc2 + MAXC;                // [MAXC][2][NCH] Chebyshev coefficients of the candidates' cells
-#define s_nmax s_cnt[0]
-#define s_ncand s_cnt[1]
-
-    FrameOut* o = out + c.frame_off + f;
-#define RSAF_PITCH_DBG_STOP(k)                                                                       \
-    if (P.debug_stop == (k)) {                                                                       \
-        if (tid == 0) { o->intensity = 0.0; o->ncand = 1.0; }                                        \
-        if (tid < MAXC) { o->freq[tid] = 0.0; o->strength[tid] = 0.0; }                              \
-        return;                                                                                      \
-    }
-    RSAF_PITCH_DBG_STOP(1)
-    RSAF_PITCH_DBG_STOP(2)
-    const double* rb = rbuf + ((int64_t)blockIdx.y * max_frames + f) * rstride;
-    const double intensity = rb[L + 1];
-    const double gp = gpeak[blockIdx.y];
-    // the row r[0..L] mirrored into Praat's symmetric array: ten loads in flight (unconditional, on clamped lags) before
-    // the first store - one load per loop turn crossed the memory latency ten to fifteen times per frame
-    for (int j0 = RC + r_lo + tid; j0 <= RC + r_hi; j0 += 10 * CT) {
-        double v[10];
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-            const int j = j0 + u * CT;
-            const int l = j >= RC ? j - RC : RC - j;
-            v[u] = rb[l <= L ? l : L];
-        }
-#pragma unroll
-        for (int u = 0; u < 10; ++u) {
-            const int j = j0 + u * CT;
-            const int l = j >= RC ? j - RC : RC - j;
-            if (j <= RC + r_hi) r[j] = l <= L ? v[u] : 0.0;
-        }
-    }
-    if (tid == 0) s_nmax = 0;
-    __syncthreads();
-    // ---- local maxima in ascending lag order (wave 0, ballot + prefix) ----
-    const bool dual = out2 != nullptr && P.voicing_thr2 >= 0.0;
-    const double thr_low = dual && P.voicing_thr2 < P.voicing_thr ? P.voicing_thr2 : P.voicing_thr;
-    const int lag_lo = P.min_lag > 2 ? P.min_lag : 2;
-    int lag_hi = P.max_lag - 1;
-    if (lag_hi > P.brent_ixmax - 1) lag_hi = P.brent_ixmax - 1;
-    if (wv == 0) {
-        int count = 0;
-        for (int base = lag_lo; base <= lag_hi; base += 64) {
-            const int l = base + lane;
-            bool ok = false;
-            if (l <= lag_hi) {
-                const double v = r[RC + l];
-                ok = (v > 0.5 * thr_low) && (v > r[RC + l - 1]) && (v >= r[RC + l + 1]);
-            }
-            const unsigned long long m = __ballot(ok);
-            const int pos = count + __popcll(m & ((1ull << lane) - 1ull));
-            if (ok && pos < MAX_MAXIMA) s_maxlag[pos] = l;
-            count += __popcll(m);
-        }
-        if (lane == 0) s_nmax = count < MAX_MAXIMA ? count : MAX_MAXIMA;
-    }
-    __syncthreads();
-    RSAF_PITCH_DBG_STOP(3)
-    const int nmax = s_nmax;
-    const int nz_lo = RC - L, nz_hi = RC + L;
-    // ---- first estimate of every maximum: parabolic position, sinc(30) strength (16 maxima per round) ----
-    const int l16 = lane & 15, gidx = lane >> 4;
-    for (int mb = 0; mb < nmax; mb += CT / 16) {
-        const int m = mb + gidx;
-        const bool live = m < nmax;
-        const int l = s_maxlag[live ? m : 0];
-        const double y0 = r[RC + l - 1], y1 = r[RC + l], y2 = r[RC + l + 1];
-        const double dr = 0.5 * (y2 - y0), d2r = 2.0 * y1 - y0 - y2;
-        const double fm = 1.0 / DXS / (l + dr / d2r);
-        double st = sinc_group<16, false>(r, RN, RC + 1.0 / DXS / fm, 30, nz_lo, nz_hi, l16);
-        if (st > 1.0) st = 1.0 / st;
-        if (live && l16 == 0) { s_mfreq[m] = fm; s_mstr[m] = st; s_mloc[m] = st - P.octave_cost * log2(P.min_pitch / fm); }
-    }
-    __syncthreads();
-    RSAF_PITCH_DBG_STOP(4)
-    // ---- candidate list with replacement of the weakest (sequential in the maxima as in Praat, cooperative per step) ----
-    // The maxima were collected for the lower of the two voicing thresholds; each list takes the maxima whose
-    // correlation exceeds half its own threshold, in ascending lag order.  Lane z owns slot z of the list (its local
-    // strength and the index of its maximum); lanes also hold the maxima's local strengths (lane l: maxima l and l + 64),
-    // so the walk over the maxima reads them by v_readlane and the "weakest slot" is one wave reduction, redone only
-    // after a replacement.  (The one-thread form re-read 14 slots from LDS per maximum: with the harmonicity pass'
-    // threshold of 0 and up to 96 maxima that serial chain was a fifth of its frame time.)
-    const double mloc0 = lane < nmax ? s_mloc[lane] : 0.0, mloc1 = lane + 64 < nmax ? s_mloc[lane + 64] : 0.0;
-    const double mr0 = lane < nmax ? r[RC + s_maxlag[lane]] : -1.0, mr1 = lane + 64 < nmax ? r[RC + s_maxlag[lane + 64]] : -1.0;
-    auto build_list = [&](double vthr, double* cf, double* cs, double* cloc, int* place_lag, int* ncand_out) {
-        unsigned long long todo0 = __ballot(mr0 > 0.5 * vthr), todo1 = __ballot(mr1 > 0.5 * vthr);
-        double my_loc = 0.0;
-        int my_m = -1, nc = 1;
-        double weakest = 2.0;
-        int wplace = 0;
-        bool known = false;                                   // weakest / wplace describe the current slots
-        for (int half = 0; half < 2; ++half) {
-            unsigned long long todo = half ? todo1 : todo0;
-            while (todo) {
-                const int bit = __ffsll((long long)todo) - 1;
-                todo &= todo - 1;
-                const int m = 64 * half + bit;
-                const double loc_m = readlane_f64(half ? mloc1 : mloc0, bit);
-                int place;
-                if (nc < P.max_cand) {
-                    place = nc++;
-                } else {
-                    if (!known) {                             // first minimum over slots 1 .. max_cand - 1 (Praat: strict <)
-                        const double v = (lane >= 1 && lane < P.max_cand) ? my_loc : INFINITY;
-                        double mn = v;
-#pragma unroll
-                        for (int o = 32; o >= 1; o >>= 1) mn = fmin(mn, __shfl_xor(mn, o, 64));
-                        if (mn < 2.0) { weakest = mn; wplace = __ffsll((long long)__ballot(v == mn)) - 1; }
-                        else { weakest = 2.0; wplace = 0; }
-                        known = true;
-                    }
-                    place = loc_m <= weakest ? 0 : wplace;
-                }
-                if (place) {
-                    if (lane == place) { my_loc = loc_m; my_m = m; }
-                    known = false;
-                }
-            }
-        }
-        if (lane < MAXC) {
-            const bool on = lane >= 1 && lane < nc && my_m >= 0;
-            cf[lane] = on ? s_mfreq[my_m] : 0.0;
-            cs[lane] = on ? s_mstr[my_m] : 0.0;
-            cloc[lane] = on ? my_loc : 0.0;
-            place_lag[lane] = on ? s_maxlag[my_m] : 0;
-        }
-        if (lane == 0) *ncand_out = nc;
-    };
-    build_list(P.voicing_thr, s_cf, s_cs, s_cloc, s_place, &s_cnt[1]);
-    if (dual) build_list(P.voicing_thr2, s_cf2, s_cs2, s_cloc2, s_place2, &s_cnt[2]);
-    __syncthreads();
-    const int ncand = s_cnt[1];
-    RSAF_PITCH_DBG_STOP(5)
-    // ---- refine every kept candidate: maximise the sinc-interpolated correlation (16 at a time) ----
-    // With every path cost zero (harmonicity pass) the path finder picks the strongest candidate of each
-    // frame on its own, so a candidate far below the best first-pass strength can never be selected and
-    // is left unrefined (the depth-30 and refined strengths differ by far less than the margin).
-    // Lanes per candidate follow the candidate count (uniform per frame): few candidates (the usual AC case)
-    // get a whole wave each, a full list gets 16 lanes each, so one or two rounds cover every frame.
-    const int64_t wframe = (int64_t)blockIdx.y * max_frames + f;          // the frame's index in the workspace arrays
-    // returns true when the list's refinement is left to pitch_brent_kernel
-    auto refine_list = [&](int nc, const int* place_lag, double* cf, double* cs, double* pc_out) -> bool {
-        if (DA.hdr && DA.grouped) return true;                           // per-cell tables: nothing to build here
-        // Depth of the sinc interpolation on a cell whose left sample is b (0-based): Praat clips it to the samples that
-        // exist on either side, min(depth, b + 1, n - b - 1), for BOTH halves of the kernel.  A frame whose cells all
-        // have the full depth takes the shared table on the matrix pipe; a clipped cell (cc passes: lags within `depth` of
-        // the end of the array) has its own table per depth (host-built, depths 3 .. depth - 1; 618 KB at depth 70) and
-        // its 16 coefficients cost 2 d_c x 16 multiply-adds on the vector ALU - against ~15 Brent evaluations of the
-        // 2 d_c-term sum with a reciprocal and a cosine per term in the direct form.  Depths below 3 (nearest / linear /
-        // cubic in NUM_interpolate_sinc) and analyses without per-depth tables (depth 700: 140 tables of 41 KB would not
-        // stay in L2) keep the direct form.
-        bool use_cheb = cheb != nullptr;
-        int n_clip_cols = 0;
-        // lane k holds candidate k (k < 16: one DPP row): the scans over the candidates below are one LDS read per lane and
-        // row reductions, not loops of dependent LDS reads
-        const bool cand_lane = lane >= 1 && lane < nc;
-        const int my_b0 = (cand_lane ? place_lag[lane] : 0) + RC - 1;
-        auto row_min = [](int v) {
-            v = min(v, __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, false));
-            v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, false));
-            v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, false));
-            v = min(v, __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, false));
-            return __builtin_amdgcn_readlane(v, 0);
-        };
-        if (use_cheb && !P.cheb_all_full) {
-            int dc0 = P.refine_depth, dc1 = P.refine_depth;
-            dc0 = dc0 < my_b0 + 1 ? dc0 : my_b0 + 1;
-            dc0 = dc0 < RN - my_b0 - 1 ? dc0 : RN - my_b0 - 1;
-            dc1 = dc1 < my_b0 + 2 ? dc1 : my_b0 + 2;
-            dc1 = dc1 < RN - my_b0 - 2 ? dc1 : RN - my_b0 - 2;
-            n_clip_cols = __popcll(__ballot(cand_lane && dc0 < P.refine_depth)) + __popcll(__ballot(cand_lane && dc1 < P.refine_depth));
-            const int dmin = row_min(cand_lane ? min(dc0, dc1) : P.refine_depth);
-            if (n_clip_cols > 0 && (!P.cheb_clipped || dmin < 3)) use_cheb = false;
-        }
-        if (use_cheb) {
-            // Chebyshev coefficients of both cells of every candidate on the fp64 matrix pipe:
-            //   P[j][(k, cell)] = sum_o cheb[o][j] * r[b_k + cell + o]      (16 coefficients x up to 30 columns x 2 d taps)
-            // as v_mfma_f64_16x16x4: A[m = j][kk] = cheb[o + kk][j] (a lane's table load is the A operand as it is),
-            // B[kk][n] = r[base_n + o + kk] with a per-lane base (column n = 2 (k - 1) + cell), one or two column tiles.
-            // The vector-ALU form of this sum (8 FMAs and 8 LDS reads per table element and round of four candidates)
-            // was 35-70 % of the harmonicity pass' frame time.
-            double* s_P = s_part;                                    // [MAXC][2][NCH], the partial sums are dead by now
-            const int d = P.refine_depth;
-            const int kq = lane >> 4, nn = lane & 15;
-            const int ncol = 2 * (nc - 1), tiles = (ncol + 15) >> 4;
-            if (nc > 1 && ncol <= 12 && n_clip_cols == 0) {
-                // Few candidates (the autocorrelation passes keep two or three): v_mfma_f64_4x4x4_4b instead - four independent
-                // 4 x 4 x 4 blocks in 16 cycles where the 16 x 16 x 4 instruction takes 64 with 4-12 of its 16 columns in use.
-                // Block = (lane % 16) / 4 holds coefficients 4 blk .. 4 blk + 3 (A[blk][i][k] in lane 16 k + 4 blk + i: the same table
-                // element as the wide instruction's A operand), every block gets the same B (B[blk][k][j] in lane 16 k + 4 blk + j:
-                // tap k of column j = lane % 4), D[blk][i][j] comes back in lane 16 i + 4 blk + j (tools/micro/mfma_f64_4x4_probe.hip).
-                const int bmin = row_min(cand_lane ? my_b0 : 0x7fffffff), bmax = -row_min(cand_lane ? -my_b0 : 0x7fffffff);
-                const int groups = (ncol + 3) >> 2;
-                int rb4[3];
-                bool cf4[3];
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const int n = 4 * g + (lane & 3), k = 1 + (n >> 1);
-                    rb4[g] = place_lag[k < nc ? k : 1] + RC - 1 + (n & 1);
-                    cf4[g] = n < ncol;                                   // (no clipped cell in this frame: they keep the wide path)
-                }
-                int o_lo = nz_lo - (bmax + 1), o_hi = nz_hi - bmin;
-                o_lo = o_lo < -(d - 1) ? -(d - 1) : o_lo;
-                o_hi = o_hi > d ? d : o_hi;
-                double a4[3] = {0.0, 0.0, 0.0};
-                const double* ctab = cheb + (int64_t)(d - 1) * NCH + nn;
-                int o = o_lo;
-                for (; o + 31 <= o_hi; o += 32) {
-                    double cw[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) cw[u] = ctab[(int64_t)(o + 4 * u + kq) * NCH];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int oo = o + 4 * u + kq;
-                        a4[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw[u], cf4[0] ? r[rb4[0] + oo] : 0.0, a4[0], 0, 0, 0);
-                        if (groups > 1) a4[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw[u], cf4[1] ? r[rb4[1] + oo] : 0.0, a4[1], 0, 0, 0);
-                        if (groups > 2) a4[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw[u], cf4[2] ? r[rb4[2] + oo] : 0.0, a4[2], 0, 0, 0);
-                    }
-                }
-                for (; o <= o_hi; o += 4) {
-                    const int oo = o + kq, oc = oo <= o_hi ? oo : o_hi;          // taps past o_hi contribute zero
-                    const double cw = oo <= o_hi ? ctab[(int64_t)oc * NCH] : 0.0;
-                    a4[0] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw, cf4[0] ? r[rb4[0] + oc] : 0.0, a4[0], 0, 0, 0);
-                    if (groups > 1) a4[1] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw, cf4[1] ? r[rb4[1] + oc] : 0.0, a4[1], 0, 0, 0);
-                    if (groups > 2) a4[2] = __builtin_amdgcn_mfma_f64_4x4x4f64(cw, cf4[2] ? r[rb4[2] + oc] : 0.0, a4[2], 0, 0, 0);
-                }
-                const int coef = (nn & 12) + kq;                             // 4 blk + i
-#pragma unroll
-                for (int g = 0; g < 3; ++g) {
-                    const int n = 4 * g + (lane & 3), k = 1 + (n >> 1);
-                    if (g < groups && n < ncol) s_P[(k * 2 + (n & 1)) * NCH + coef] = a4[g];
-                }
-            } else if (nc > 1) {
-                const int bmin = row_min(cand_lane ? my_b0 : 0x7fffffff), bmax = -row_min(cand_lane ? -my_b0 : 0x7fffffff);
-                int rbase[2];
-                bool colfull[2];                                      // clipped cells are rebuilt below: their B operand is zero here
-#pragma unroll
-                for (int T = 0; T < 2; ++T) {
-                    const int n = 16 * T + nn, k = 1 + (n >> 1);
-                    rbase[T] = place_lag[k < nc ? k : 1] + RC - 1 + (n & 1);   // 0-based left sample of the cell
-                    colfull[T] = n_clip_cols == 0 || (rbase[T] + 1 >= d && RN - rbase[T] - 1 >= d);
-                }
-                // r is zero outside [nz_lo, nz_hi]: taps that reach no candidate's non-zero range are skipped
-                int o_lo = nz_lo - (bmax + 1), o_hi = nz_hi - bmin;
-                o_lo = o_lo < -(d - 1) ? -(d - 1) : o_lo;
-                o_hi = o_hi > d ? d : o_hi;
-                double4_t acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = acc0;
-                const double* ctab = cheb + (int64_t)(d - 1) * NCH + nn;
-                // eight table loads (L2-resident, ~500 cycles each) are issued together before they are consumed
-                int o = o_lo;
-                for (; o + 31 <= o_hi; o += 32) {
-                    double cw[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) cw[u] = ctab[(int64_t)(o + 4 * u + kq) * NCH];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        const int oo = o + 4 * u + kq;
-                        acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(cw[u], colfull[0] ? r[rbase[0] + oo] : 0.0, acc0, 0, 0, 0);
-                        if (tiles > 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(cw[u], colfull[1] ? r[rbase[1] + oo] : 0.0, acc1, 0, 0, 0);
-                    }
-                }
-                for (; o <= o_hi; o += 4) {
-                    const int oo = o + kq, oc = oo <= o_hi ? oo : o_hi;          // taps past o_hi contribute zero
-                    const double cw = oo <= o_hi ? ctab[(int64_t)oc * NCH] : 0.0;
-                    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(cw, colfull[0] ? r[rbase[0] + oc] : 0.0, acc0, 0, 0, 0);
-                    if (tiles > 1) acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(cw, colfull[1] ? r[rbase[1] + oc] : 0.0, acc1, 0, 0, 0);
-                }
-                // D layout: lane (kq, nn), register v -> row j = kq + 4 v, column nn
-#pragma unroll
-                for (int T = 0; T < 2; ++T) {
-                    const int n = 16 * T + nn, k = 1 + (n >> 1);
-                    if (T < tiles && k < nc) {
-#pragma unroll
-                        for (int v = 0; v < 4; ++v) s_P[(k * 2 + (n & 1)) * NCH + kq + 4 * v] = T == 0 ? acc0[v] : acc1[v];
-                    }
-                }
-                if (n_clip_cols > 0) {
-                    // clipped cells: coefficient j = sum over the 2 d_c taps of the depth's own table; lane = (tap phase, j)
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                    const double* clip_tabs = cheb + (int64_t)2 * d * NCH;        // tables of depths 1 .. d - 1, depth e at 16 e (e - 1)
-                    const int jj = lane & 15, ph = lane >> 4;
-                    for (int col = 0; col < ncol; ++col) {
-                        const int k = 1 + (col >> 1), b = place_lag[k] + RC - 1 + (col & 1);
-                        int dc = d;
-                        dc = dc < b + 1 ? dc : b + 1;
-                        dc = dc < RN - b - 1 ? dc : RN - b - 1;
-                        if (dc >= d) continue;                           // uniform
-                        const double* tab = clip_tabs + (int64_t)NCH * dc * (dc - 1) + jj;
-                        double acc = 0.0;
-                        int o = -(dc - 1) + ph;
-                        for (; o + 12 <= dc; o += 16) {                   // four table loads in flight
-                            double tw4[4];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) tw4[u] = tab[(int64_t)(o + 4 * u + dc - 1) * NCH];
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) acc = fma(tw4[u], r[b + o + 4 * u], acc);
-                        }
-                        for (; o <= dc; o += 4) acc = fma(tab[(int64_t)(o + dc - 1) * NCH], r[b + o], acc);
-                        acc += __shfl_xor(acc, 16, 64);
-                        acc += __shfl_xor(acc, 32, 64);
-                        if (ph == 0) s_P[(k * 2 + (col & 1)) * NCH + jj] = acc;
-                    }
-                }
-            }
-            __syncthreads();
-            if (P.debug_stop == 6) return true;
-            if (DA.hdr) {                                            // the coefficients travel to pitch_brent_kernel
-                for (int i = 2 * NCH + tid; i < nc * 2 * NCH; i += CT) pc_out[i] = s_P[i];
-                __syncthreads();
-                return true;
-            }
-            if (tid < 64) {                                          // nc <= 16: one lane per candidate
-                const int k = 1 + tid;
-                const bool live = k < nc;
-                double xm, ym;
-                improve_max_cheb(s_P + (live ? k : 1) * 2 * NCH, place_lag[live ? k : 1] + RC, live, xm, ym);
-                if (ym > 1.0) ym = 1.0 / ym;
-                if (live) { cf[k] = 1.0 / DXS / (xm - RC); cs[k] = ym; }
-            }
-            __syncthreads();
-            return false;
-        }
-        const int nref = nc - 1;
-        const int span = P.refine_depth < 2 * L ? P.refine_depth : 2 * L;    // longest half kernel
-        RefineArgs A{r, RN, RC, P.refine_depth, nz_lo, nz_hi, nc, place_lag, cf, cs};
-        if (nref <= 4) { if (span >= 6 * 64) refine_candidates<64, true>(A, tid, CT); else refine_candidates<64, false>(A, tid, CT); }
-        else if (nref <= 8) { if (span >= 6 * 32) refine_candidates<32, true>(A, tid, CT); else refine_candidates<32, false>(A, tid, CT); }
-        else { if (span >= 6 * 16) refine_candidates<16, true>(A, tid, CT); else refine_candidates<16, false>(A, tid, CT); }
-        __syncthreads();
-        return false;
-    };
-    int* hdr = DA.hdr ? DA.hdr + wframe * HDR_INTS : nullptr;
-    int flags = 0;
-    if (!dual) {
-        if (refine_list(ncand, s_place, s_cf, s_cs, DA.pc_a ? DA.pc_a + wframe * PC_DOUBLES : nullptr)) flags = HDR_A_DEFER;
-        if (hdr) {
-            if (tid < MAXC) reinterpret_cast<unsigned short*>(hdr + 4)[tid] = (unsigned short)s_place[tid];
-            if (tid == 0) { hdr[0] = gp > 0.0 ? flags : 0; hdr[1] = ncand; hdr[2] = 0; }
-        }
-    } else {
-        // refine the lower-threshold list (normally a superset), copy the shared candidates by lag, and only
-        // when a candidate of the primary list is missing from it (both lists overflowed) refine that list too
-        const int ncand2 = s_cnt[2];
-        const bool low_is_second = P.voicing_thr2 < P.voicing_thr;
-        int* pl_a = low_is_second ? s_place2 : s_place;   double* cf_a = low_is_second ? s_cf2 : s_cf;   double* cs_a = low_is_second ? s_cs2 : s_cs;
-        int* pl_b = low_is_second ? s_place : s_place2;   double* cf_b = low_is_second ? s_cf : s_cf2;   double* cs_b = low_is_second ? s_cs : s_cs2;
-        const int nc_a = low_is_second ? ncand2 : ncand, nc_b = low_is_second ? ncand : ncand2;
-        const bool def_a = refine_list(nc_a, pl_a, cf_a, cs_a, DA.pc_a ? DA.pc_a + wframe * PC_DOUBLES : nullptr);
-        if (def_a) flags |= HDR_A_DEFER;
-        if (tid == 0) s_cnt[3] = 0;
-        __syncthreads();
-        int hit = 0;
-        {
-            const int pa_reg = tid < MAXC ? pl_a[tid] : 0;             // lane z holds the lag of candidate z of the refined list
-            const int mine = (tid >= 1 && tid < nc_b) ? pl_b[tid] : -1;
-            for (int z = 1; z < nc_a; ++z) if (__builtin_amdgcn_readlane(pa_reg, z) == mine) hit = z;   // v_readlane: no LDS round trip per z
-            if (tid >= 1 && tid < nc_b) {
-                if (hit) { if (!def_a) { cf_b[tid] = cf_a[hit]; cs_b[tid] = cs_a[hit]; } } else atomicAdd(&s_cnt[3], 1);
-            }
-        }
-        __syncthreads();
-        if (s_cnt[3] > 0) {
-            // restore the first estimates of the list (entries copied above hold refined values) and refine it whole
-            if (tid >= 1 && tid < nc_b) {
-                for (int m = 0; m < nmax; ++m) if (s_maxlag[m] == pl_b[tid]) { cf_b[tid] = s_mfreq[m]; cs_b[tid] = s_mstr[m]; }
-            }
-            __syncthreads();
-            if (refine_list(nc_b, pl_b, cf_b, cs_b, DA.pc_b ? DA.pc_b + wframe * PC_DOUBLES : nullptr)) flags |= HDR_B_DEFER;
-        } else if (def_a) {
-            flags |= HDR_B_COPY;
-        }
-        if (hdr) {
-            if (tid < MAXC) {
-                reinterpret_cast<unsigned short*>(hdr + 4)[tid] = (unsigned short)pl_a[tid];
-                reinterpret_cast<unsigned short*>(hdr + 12)[tid] = (unsigned short)pl_b[tid];
-                reinterpret_cast<unsigned char*>(hdr + 20)[tid] = (unsigned char)hit;
-            }
-            if (tid == 0) { hdr[0] = gp > 0.0 ? flags : 0; hdr[1] = nc_a; hdr[2] = nc_b; }
-        }
-        if (tid == 0) {
-            FrameOut* o2 = out2 + c.frame_off + f;
-            o2->intensity = intensity;
-            o2->ncand = gp > 0.0 ? (double)ncand2 : 1.0;
-        }
-        if (tid < MAXC) {
-            FrameOut* o2 = out2 + c.frame_off + f;
-            const bool on = tid < ncand2 && gp > 0.0;
-            o2->freq[tid] = on ? s_cf2[tid] : 0.0;
-            o2->strength[tid] = on ? s_cs2[tid] : 0.0;
-        }
-    }
-    if (tid == 0) {
-        o->intensity = intensity;
-        o->ncand = gp > 0.0 ? (double)ncand : 1.0;
-    }
-    if (tid < MAXC) {
-        const bool on = tid < ncand && gp > 0.0;
-        o->freq[tid] = on ? s_cf[tid] : 0.0;
-        o->strength[tid] = on ? s_cs[tid] : 0.0;
-    }
-}
-
-// ---- deferred refinement, part 1: Chebyshev coefficients per CELL (analyses whose depth the array ends clip) ----------
-// A cell is the interval between two samples of Praat's symmetric correlation array (index b = its left sample); the
-// depth of the sinc interpolation on it is min(depth, b + 1, RN - b - 1) (NUM_interpolate_sinc), so in an analysis whose
-// array is shorter than lag + depth every cell has its own depth and with it its own weight table - which the frame-wise
-// kernel can only answer with the direct sum (a reciprocal and a cosine per tap and evaluation: 19.6 ms per 64 clips in the
-// harmonicity pass at a 100 Hz floor, against 7-9 ms where one table serves every cell).  The table depends on b alone,
-// only the taps that meet the non-zero lags |lag| <= L of r matter, and r[-lag] = r[lag] lets the table carry the sum of the
-// two taps that meet a lag; in those terms
-//     P_b[j][cell] = sum_m tab_b[m][j] * r_cell[m],        m = 0 .. L,
-// i.e. one GEMM per b over all the cells of the batch that sit on b: a workgroup owns (b, a chunk of frames), keeps tab_b
-// in LDS, scans the chunk's candidate lags for its two matches per frame (cell 0 of the candidate at lag b - RC + 1,
-// cell 1 of the one at lag b - RC), and runs 16 cells at a time through v_mfma_f64_16x16x4 (A = the table from LDS,
-// B = the cells' correlation rows from the workspace).  The host builds the tables (mshds.sinc_cell_tables).
-// Workgroup id -> (b, chunk): all b of a chunk run on ONE XCD (ids are dealt round-robin to the 8 XCDs), so the chunk's rows
-// - read 28 times over, by every cell of every candidate - stay in that XCD's L2.
-constexpr int CELL_Q = 192;          // queue slots per wave (at most 15 left over + 128 new per scan step)
-__global__ __launch_bounds__(256) void pitch_cell_coef_kernel(const ClipInfo* __restrict__ ci, int n_clips, int max_frames,
-                                                              const int* __restrict__ hdr, const double* __restrict__ rbuf,
-                                                              int rstride, int L, int RC, const double* __restrict__ tabs,
-                                                              int b_lo, int n_b, int ntap_pad, int chunk_frames, int n_chunks,
-                                                              double* __restrict__ pc) {
-    using namespace wfft;
-    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    double* tab = reinterpret_cast<double*>(smem_raw);                               // [ntap_pad][NCH]
-    unsigned* qall = reinterpret_cast<unsigned*>(tab + (size_t)ntap_pad * NCH);      // [4][CELL_Q]
-    const int64_t wid = blockIdx.x;
-    const int64_t q = wid >> 3;
-    const int bi = (int)(q % n_b);
-    const int64_t chunk = (q / n_b) * 8 + (wid & 7);
-    if (chunk >= n_chunks) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned* qb = qall + wv * CELL_Q;
-    const int b = b_lo + bi;
-    const int lag0 = b - RC + 1, lag1 = b - RC;                // the lags whose cell 0 / cell 1 is this b
-    const int64_t total = (int64_t)n_clips * max_frames;
-    const int per_wave = chunk_frames / 4;
-    const int64_t g_begin = chunk * chunk_frames + (int64_t)wv * per_wave;
-    const int64_t g_end = g_begin + per_wave < total ? g_begin + per_wave : total;
-    const int nn = lane & 15, kq = lane >> 4;
-    // a lane's frame record: flags, list length, the 16 lags (zeros for a frame that does not exist or has nothing deferred)
-    struct Rec { int nc; int lw[8]; };
-    auto load_rec = [&](int64_t g) {
-        Rec r;
-        r.nc = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) r.lw[i] = 0;
-        if (g < g_end) {
-            const int clip = (int)(g / max_frames), fr = (int)(g - (int64_t)clip * max_frames);
-            if (fr < ci[clip].n_frames) {
-                const int* h = hdr + g * HDR_INTS;
-                const int flags = h[0], nc = h[1];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) r.lw[i] = h[4 + i];
-                r.nc = (flags & HDR_A_DEFER) ? nc : 0;
-            }
-        }
-        return r;
-    };
-    Rec rec = load_rec(g_begin + lane);                        // in flight while the table arrives
-    {
-        // the cell's table -> LDS, sixteen bytes per lane and load, eight loads in flight
-        const double2_t* src = reinterpret_cast<const double2_t*>(tabs + (int64_t)bi * ntap_pad * NCH);
-        double2_t* dst = reinterpret_cast<double2_t*>(tab);
-        const int n2 = ntap_pad * NCH / 2;
-        for (int i0 = tid; i0 < n2; i0 += 8 * 256) {
-            double2_t v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) v[u] = src[i0 + 256 * u < n2 ? i0 + 256 * u : n2 - 1];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (i0 + 256 * u < n2) dst[i0 + 256 * u] = v[u];
-        }
-    }
-    __syncthreads();
-    int count = 0;
-    // sixteen cells through the matrix pipe: eight tap groups per batch, the next batch's operands (rows from L2, table from
-    // LDS) are requested before the current batch's eight dependent MFMAs are issued
-    auto run_tile = [&](int off, int n) {                      // queue entries off .. off + n - 1 (n <= 16)
-        const unsigned e = qb[off + (nn < n ? nn : 0)];
-        const int64_t g = e >> 5;
-        const int k = (e >> 1) & 15, c = e & 1;
-        const double* rb = rbuf + g * rstride;
-        double4_t acc = {0.0, 0.0, 0.0, 0.0};
-        double av[2][8], bv[2][8];
-        auto fetch = [&](int t0, double (&a8)[8], double (&b8)[8]) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int t = t0 + 4 * u + kq;                 // the lag
-                const int tc = t < ntap_pad ? t : ntap_pad - 1;
-                b8[u] = rb[tc <= L ? tc : L];                  // lags beyond L only meet the zero rows that pad the table
-                a8[u] = t < ntap_pad ? tab[tc * NCH + nn] : 0.0;
-            }
-        };
-        fetch(0, av[0], bv[0]);
-        for (int t0 = 0; t0 < ntap_pad; t0 += 64) {
-            if (t0 + 32 < ntap_pad) fetch(t0 + 32, av[1], bv[1]);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[0][u], bv[0][u], acc, 0, 0, 0);
-            if (t0 + 32 >= ntap_pad) break;
-            if (t0 + 64 < ntap_pad) fetch(t0 + 64, av[0], bv[0]);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av[1][u], bv[1][u], acc, 0, 0, 0);
-        }
-        if (nn < n) {                                          // D: lane (kq, nn), register v -> coefficient kq + 4 v of cell nn
-            double* dst = pc + (g * MAXC + k) * (2 * NCH) + c * NCH;
-#pragma unroll
-            for (int v = 0; v < 4; ++v) dst[kq + 4 * v] = acc[v];
-        }
-    };
-    for (int64_t g0 = g_begin; g0 < g_end; g0 += 64) {
-        const int64_t g = g0 + lane;
-        int m0 = 0, m1 = 0;
-#pragma unroll
-        for (int k = 1; k < MAXC; ++k) {                       // a list holds a lag once: at most one match per cell side
-            const int lg = (rec.lw[k >> 1] >> (16 * (k & 1))) & 0xffff;
-            if (k < rec.nc && lg == lag0) m0 = k;
-            if (k < rec.nc && lg == lag1) m1 = k;
-        }
-        rec = load_rec(g + 64);                                // the next step's records travel while this step's tiles run
-        const unsigned long long b0 = __ballot(m0 != 0), b1 = __ballot(m1 != 0);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        if (m0) qb[count + __popcll(b0 & below)] = ((unsigned)g << 5) | ((unsigned)m0 << 1);
-        count += __popcll(b0);
-        if (m1) qb[count + __popcll(b1 & below)] = ((unsigned)g << 5) | ((unsigned)m1 << 1) | 1u;
-        count += __popcll(b1);
-        wave_sync();
-        int done = 0;
-        for (; count - done >= 16; done += 16) run_tile(done, 16);
-        const int left = count - done;                         // < 16 entries move to the front
-        const unsigned rest = lane < left ? qb[done + lane] : 0u;
-        wave_sync();
-        if (lane < left) qb[lane] = rest;
-        count = left;
-        wave_sync();
-    }
-    if (count > 0) run_tile(0, count);
-}
-
-// ---- deferred refinement, part 2: Brent's search, one candidate per lane ----------------------------------------------
-// A wave takes BR_FRAMES consecutive frames of a clip and packs their deferred candidates (list A, then - where the second
-// list of a dual pass has to be refined on its own - list B) into its lanes: an autocorrelation pass keeps two or three
-// candidates per frame, so a frame-per-16-lanes mapping would leave four lanes in five idle through every iteration.
-// A candidate of list A also writes the slots of list B that hold the same lag (HDR_B_COPY: the second threshold's list).
-constexpr int BR_FRAMES = 16;
-__global__ __launch_bounds__(64) void pitch_brent_kernel(const ClipInfo* __restrict__ ci, const int* __restrict__ hdr,
-                                                         const double* __restrict__ pc_a, const double* __restrict__ pc_b,
-                                                         int max_frames, int RC, FrameOut* __restrict__ out_a,
-                                                         FrameOut* __restrict__ out_b) {
-    const ClipInfo c = ci[blockIdx.y];
-    const int f0 = blockIdx.x * BR_FRAMES;
-    if (f0 >= c.n_frames) return;
-    const int lane = threadIdx.x;
-    const int64_t g0 = (int64_t)blockIdx.y * max_frames + f0;
-    int cnt_a = 0, cnt_b = 0;
-    if (lane < BR_FRAMES && f0 + lane < c.n_frames) {
-        const int* h = hdr + (g0 + lane) * HDR_INTS;
-        const int flags = h[0];
-        if (flags & HDR_A_DEFER) cnt_a = h[1] > 1 ? h[1] - 1 : 0;
-        if (flags & HDR_B_DEFER) cnt_b = h[2] > 1 ? h[2] - 1 : 0;
-    }
-    const int tot = cnt_a + cnt_b;
-    int incl = tot;
-#pragma unroll
-    for (int o = 1; o < BR_FRAMES; o <<= 1) { const int up = __shfl_up(incl, o, 64); if (lane >= o) incl += up; }
-    const int excl = incl - tot;
-    const int T = __builtin_amdgcn_readlane(incl, BR_FRAMES - 1);
-    for (int q0 = 0; q0 < T; q0 += 64) {
-        const int q = q0 + lane;
-        const bool live = q < T;
-        int j = 0;                                            // the last frame whose first candidate is at or before q
-#pragma unroll
-        for (int jj = 1; jj < BR_FRAMES; ++jj) if (__builtin_amdgcn_readlane(excl, jj) <= q) j = jj;
-        if (!live) j = 0;
-        const int r = q - __shfl(excl, j, 64), na = __shfl(cnt_a, j, 64);
-        const bool is_b = live && r >= na;
-        const int slot = live ? (is_b ? r - na : r) + 1 : 1;
-        const int64_t g = g0 + j;
-        const int* h = hdr + g * HDR_INTS;
-        const int lag = reinterpret_cast<const unsigned short*>(h + (is_b ? 12 : 4))[slot];
-        const double* Pc = (is_b ? pc_b : pc_a) + (g * MAXC + slot) * (2 * NCH);
-        double xm, ym;
-        improve_max_cheb(Pc, lag + RC, live, xm, ym);
-        if (ym > 1.0) ym = 1.0 / ym;
-        const double fq = 1.0 / DXS / (xm - RC);
-        if (live) {
-            FrameOut* o = (is_b ? out_b : out_a) + c.frame_off + f0 + j;
-            o->freq[slot] = fq;
-            o->strength[slot] = ym;
-            if (!is_b && out_b != nullptr && (h[0] & HDR_B_COPY)) {
-                const int nc_b = h[2];
-                FrameOut* o2 = out_b + c.frame_off + f0 + j;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned hw = (unsigned)h[20 + w];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int t = 4 * w + u;
-                        if (t >= 1 && t < nc_b && (int)((hw >> (8 * u)) & 0xff) == slot) { o2->freq[t] = fq; o2->strength[t] = ym; }
-                    }
-                }
-            }
-        }
-    }
-}
-
-// ---- Viterbi path finder: one wave per clip (lane = candidate of the current frame) -------------------
-constexpr int PATH_CH = 32;          // frames whose own costs are computed at once (lane-parallel) ahead of the dependent steps
-constexpr int PATH_RING = 4 * PATH_CH;   // frames of the LDS ring: the chunk being written lies >= 2 chunks behind the frames being read
-
-__global__ __launch_bounds__(64) void path_kernel(const FrameOut* __restrict__ fr, const ClipInfo* __restrict__ ci,
-                                                  double dt, double silence_thr, double voicing_thr, double octave_cost,
-                                                  double octave_jump_cost, double vuv_cost, double ceiling,
-                                                  unsigned char* __restrict__ psi, int* __restrict__ end_state) {
-    // ring of PATH_RING frames: a frame's own costs at [(f mod PATH_RING) * MAXC + candidate]
-    __shared__ double s_delta[PATH_RING * MAXC], s_logf[PATH_RING * MAXC];
-    __shared__ unsigned char s_flag[PATH_RING * MAXC];       // bit 0: voiceless, bit 1: valid
-    __shared__ double s_cur[2][MAXC];                        // path costs of the previous frame (double-buffered by frame parity)
-    __shared__ __attribute__((aligned(16))) unsigned char s_psi[PATH_CH * MAXC];   // back pointers of the current chunk
-    const ClipInfo c = ci[blockIdx.x];
-    const int lane = threadIdx.x;
-    const int nF = c.n_frames;
-    if (nF <= 0) return;
-    const FrameOut* F = fr + c.frame_off;
-    unsigned char* P = psi + c.frame_off * MAXC;
-    const double corr = 0.01 / dt;
-    const double ojc = octave_jump_cost * corr, vuc = vuv_cost * corr;
-    // The loop-carried chain is the vector of path costs alone.  (1) A frame's own costs (two log2 per candidate) do not
-    // depend on the path: they are computed for PATH_CH frames at a time with every lane busy, one chunk ahead, into an LDS
-    // ring; the global loads of the chunk after that are in flight while the dependent steps run.  (2) A step is the
-    // 16 x 16 table of transitions: lane (j, q) = (lane >> 2, lane & 3) evaluates predecessors q, q + 4, q + 8, q + 12 of
-    // candidate j (four independent evaluations), the quad combines them in two exchange steps (first maximum: ties go
-    // to the lower predecessor, as Praat's strict > in ascending order does), lane (j, 0) publishes the new cost through
-    // LDS.  One LDS round trip per frame instead of up to 15 dependent v_readlane rounds.
-    auto clampn = [](double nc) { const int v = (int)nc; return v < 0 ? 0 : (v > MAXC ? MAXC : v); };
-    constexpr int PPLN = PATH_CH * MAXC / 64;                  // (frame, candidate) pairs per lane
-    constexpr int RING = PATH_RING;
-    double lfq[PPLN], lst[PPLN], lnc[PPLN], lin[PPLN];
-    auto fetch = [&](int f0) {                                // frames [f0, f0 + PATH_CH) -> registers
-#pragma unroll
-        for (int u = 0; u < PPLN; ++u) {
-            const int pr = lane + 64 * u, fi = f0 + (pr >> 4), cd = pr & (MAXC - 1);
-            const int f = fi < nF ? fi : nF - 1;
-            lfq[u] = F[f].freq[cd]; lst[u] = F[f].strength[cd]; lnc[u] = F[f].ncand; lin[u] = F[f].intensity;
-        }
-    };
-    auto derive_to = [&](int f0) {                            // registers -> ring slots of frames [f0, f0 + PATH_CH)
-        const int base = (f0 % RING) * MAXC;
-#pragma unroll
-        for (int u = 0; u < PPLN; ++u) {
-            const int pr = lane + 64 * u, cd = pr & (MAXC - 1);
-            const bool valid = cd < clampn(lnc[u]);
-            const bool vl = !(lfq[u] > 0.0 && lfq[u] < ceiling);
-            double unv = silence_thr <= 0.0 ? 0.0 : 2.0 - lin[u] / (silence_thr / (1.0 + voicing_thr));
-            unv = voicing_thr + fmax(0.0, unv);
-            s_delta[base + pr] = valid ? (vl ? unv : lst[u] - octave_cost * log2(ceiling / lfq[u])) : -1e300;
-            s_logf[base + pr] = vl ? 0.0 : log2(lfq[u]);
-            s_flag[base + pr] = (unsigned char)((vl ? 1 : 0) | (valid ? 2 : 0));
-        }
-    };
-    // one wave per workgroup: wavefront-scope fences order the LDS traffic without draining the global stores (a
-    // workgroup-scope release waits for vmcnt(0): with a global store per step that was most of the step)
-    auto lds_sync = [] {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
-    const int j = lane >> 2, q = lane & 3;
-    fetch(0);
-    derive_to(0);
-    fetch(PATH_CH);
-    lds_sync();
-    if (q == 0) { s_cur[0][j] = s_delta[j]; s_psi[j] = 0; }   // frame 0: the path cost is the frame's own cost
-    double cur = s_delta[j];
-    for (int f0 = 0; f0 < nF; f0 += PATH_CH) {
-        if (f0 + PATH_CH < nF) {                               // the next chunk's costs, then the loads of the one after it
-            derive_to(f0 + PATH_CH);
-            fetch(f0 + 2 * PATH_CH);
-        }
-        lds_sync();
-        const int fend = f0 + PATH_CH < nF ? f0 + PATH_CH : nF;
-#pragma unroll 1
-        for (int f = f0 > 0 ? f0 : 1; f < fend; ++f) {
-            const int me = (f % RING) * MAXC + j, pb = ((f - 1) % RING) * MAXC;
-            const double delta = s_delta[me], logf = s_logf[me];
-            const int fl = s_flag[me], vl = fl & 1, valid = (fl >> 1) & 1;
-            const double* pcur = s_cur[(f - 1) & 1];
-            double best = -INFINITY;
-            int place = 0;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int c1 = q + 4 * u;
-                const double pc = pcur[c1], pl = s_logf[pb + c1];
-                const int pf = s_flag[pb + c1], pv = pf & 1, pval = (pf >> 1) & 1;
-                const double tc = (pv && vl) ? 0.0 : ((pv || vl) ? vuc : ojc * fabs(pl - logf));
-                const double v = pval ? pc - tc + delta : -INFINITY;
-                if (v > best) { best = v; place = c1; }
-            }
-            {                                                  // the quad's maximum (two DPP quad permutes: VALU latency, no
-                double ov = dpp_f64<0xB1>(best);               // LDS crossbar); ties: the lower predecessor
-                int op = __builtin_amdgcn_update_dpp(0, place, 0xB1, 0xf, 0xf, false);
-                if (ov > best || (ov == best && op < place)) { best = ov; place = op; }
-                ov = dpp_f64<0x4E>(best);
-                op = __builtin_amdgcn_update_dpp(0, place, 0x4E, 0xf, 0xf, false);
-                if (ov > best || (ov == best && op < place)) { best = ov; place = op; }
-            }
-            if (best == -INFINITY) place = 0;                  // no valid predecessor: Praat leaves place at its initial 0
-            if (!valid) best = -1e300;
-            cur = best;
-            if (q == 0) { s_cur[f & 1][j] = best; s_psi[(f - f0) * MAXC + j] = (unsigned char)place; }
-            lds_sync();
-        }
-        // the chunk's back pointers leave as 16-byte rows
-        if (lane < fend - f0)
-            reinterpret_cast<uint4*>(P + (int64_t)f0 * MAXC)[lane] = reinterpret_cast<const uint4*>(s_psi)[lane];
-        lds_sync();
-    }
-    // best end state: first maximum
-    double bv = q == 0 ? cur : -INFINITY;
-    int bi = j;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    if (lane == 0) end_state[blockIdx.x] = bi;
-}
-
-// backtrack in its own launch: the kernel boundary makes the psi stores of path_kernel visible.
-// The back-pointer walk is a dependent chain of byte loads (state of frame f-1 = psi[f][state of frame f]).  The table
-// is staged in LDS chunk by chunk (from the last frame backwards); inside a chunk the chain is cut into 256 segments:
-// (1) every thread walks its segment for all 16 possible entry states at once (16 independent chains: the segment's
-// map entry -> exit), (2) one thread threads the true state through the 256 maps, (3) every thread walks its segment
-// again from its true entry state and records the states, (4) all threads gather the selected values.
-// 2 x 12 + 256 dependent LDS reads per 3 072 frames instead of 3 072.
-constexpr int BT_CHUNK = 3072;
-__global__ __launch_bounds__(256) void backtrack_kernel(const FrameOut* __restrict__ fr, const ClipInfo* __restrict__ ci,
-                                                        const unsigned char* __restrict__ psi,
-                                                        const int* __restrict__ end_state, double* __restrict__ sel_freq,
-                                                        double* __restrict__ sel_strength) {
-    __shared__ __attribute__((aligned(16))) unsigned char s_psi[BT_CHUNK * MAXC];
-    __shared__ unsigned char s_state[BT_CHUNK];
-    __shared__ unsigned char s_map[256 * MAXC];
-    __shared__ unsigned char s_entry[256];
-    __shared__ int s_carry;
-    const ClipInfo c = ci[blockIdx.x];
-    if (c.n_frames <= 0) return;
-    const int tid = threadIdx.x;
-    const FrameOut* F = fr + c.frame_off;
-    const unsigned char* P = psi + c.frame_off * MAXC;
-    if (tid == 0) s_carry = end_state[blockIdx.x];
-    for (int hi = c.n_frames; hi > 0; hi -= BT_CHUNK) {        // frames [lo, hi)
-        const int lo = hi > BT_CHUNK ? hi - BT_CHUNK : 0, cnt = hi - lo;
-        const uint4* src = reinterpret_cast<const uint4*>(P + (int64_t)lo * MAXC);   // MAXC == 16 bytes per frame
-        uint4* dst = reinterpret_cast<uint4*>(s_psi);
-        for (int i = tid; i < cnt; i += 256) dst[i] = src[i];
-        __syncthreads();
-        const int SL = (cnt + 255) / 256, nseg = (cnt + SL - 1) / SL;
-        const int fb = tid * SL, ft = min(fb + SL, cnt) - 1;   // this thread's frames [fb, ft] of the chunk (top = ft)
-        if (tid < nseg) {
-            unsigned char x[MAXC];
-#pragma unroll
-            for (int e = 0; e < MAXC; ++e) x[e] = (unsigned char)e;
-            for (int f = ft; f >= fb; --f) {
-                if (lo + f > 0) {
-#pragma unroll
-                    for (int e = 0; e < MAXC; ++e) x[e] = s_psi[f * MAXC + x[e]];
-                }
-            }
-#pragma unroll
-            for (int e = 0; e < MAXC; ++e) s_map[tid * MAXC + e] = x[e];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int st = s_carry;                                   // state of frame hi-1
-            for (int t = nseg - 1; t >= 0; --t) { s_entry[t] = (unsigned char)st; st = s_map[t * MAXC + st]; }
-            s_carry = st;                                       // state of frame lo-1
-        }
-        __syncthreads();
-        if (tid < nseg) {
-            int st = s_entry[tid];
-            for (int f = ft; f >= fb; --f) {
-                s_state[f] = (unsigned char)st;
-                if (lo + f > 0) st = s_psi[f * MAXC + st];
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < cnt; i += 256) {
-            const int st = s_state[i];
-            sel_freq[c.frame_off + lo + i] = F[lo + i].freq[st];
-            sel_strength[c.frame_off + lo + i] = F[lo + i].strength[st];
-        }
-        __syncthreads();
-    }
-}
-
-// ---- per-clip statistics of a selected pitch track ------------------------------------------------------
-// out[clip][8]: 0 n_nonzero, 1 mean(nonzero), 2 std(nonzero, population), 3 mean after |z|<=2 filter,
-//               4 n_voiced (0<f<ceiling), 5 mean Hz, 6 sd semitones (n-1), 7 count after filter
-__global__ __launch_bounds__(64) void pitch_stats_kernel(const double* __restrict__ sel_freq, const ClipInfo* __restrict__ ci,
-                                                         double ceiling, double* __restrict__ out) {
-    const ClipInfo c = ci[blockIdx.x];
-    const int lane = threadIdx.x;
-    const double* f = sel_freq + c.frame_off;
-    double n0 = 0, s0 = 0, nv = 0, sv = 0, sst = 0;
-    for (int i = lane; i < c.n_frames; i += 64) {
-        const double v = f[i];
-        if (v != 0.0) { n0 += 1; s0 += v; }
-        if (v > 0.0 && v < ceiling) { nv += 1; sv += v; sst += 12.0 * log2(v / 100.0); }
-    }
-    n0 = wave_sum_f64(n0); s0 = wave_sum_f64(s0); nv = wave_sum_f64(nv); sv = wave_sum_f64(sv); sst = wave_sum_f64(sst);
-    const double m0 = n0 > 0 ? s0 / n0 : 0.0, mst = nv > 0 ? sst / nv : 0.0;
-    double q0 = 0, qst = 0;
-    for (int i = lane; i < c.n_frames; i += 64) {
-        const double v = f[i];
-        if (v != 0.0) q0 += (v - m0) * (v - m0);
-        if (v > 0.0 && v < ceiling) { const double d = 12.0 * log2(v / 100.0) - mst; qst += d * d; }
-    }
-    q0 = wave_sum_f64(q0); qst = wave_sum_f64(qst);
-    const double sd0 = n0 > 0 ? sqrt(q0 / n0) : 0.0;
-    double nf = 0, sf = 0;
-    for (int i = lane; i < c.n_frames; i += 64) {
-        const double v = f[i];
-        if (v != 0.0 && fabs((v - m0) / sd0) <= 2.0) { nf += 1; sf += v; }
-    }
-    nf = wave_sum_f64(nf); sf = wave_sum_f64(sf);
-    if (lane == 0) {
-        double* o = out + (int64_t)blockIdx.x * 8;
-        const double qn = __longlong_as_double(0x7ff8000000000000LL);
-        o[0] = n0; o[1] = m0; o[2] = sd0; o[3] = nf > 0 ? sf / nf : qn;
-        o[4] = nv; o[5] = nv > 0 ? sv / nv : qn; o[6] = nv > 1 ? sqrt(qst / (nv - 1)) : qn; o[7] = nf;
     }
 }
 
@@ -2305,8 +649,6 @@ using namespace rsaf::mshds;
 
 extern "C" {
 
-int rsaf_mshds_frameout_doubles(void) { return (int)(sizeof(FrameOut) / sizeof(double)); }
-
 int rsaf_mshds_clip_peak(const float* wav, const void* clip_info, int n_clips, double* gpeak, rsaf_stream_t stream) {
     RSAF_CHECK_ARG(n_clips >= 0, "negative n_clips");
     if (n_clips == 0) return RSAF_OK;
@@ -2335,404 +677,6 @@ int rsaf_mshds_intensity(const float* wav, const void* clip_info, int n_clips, i
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
-
-}  // extern "C"
-
-// ---- the pitch analysis on the host (C++ linkage: its launch helpers are templates) ---------------------------------
-
-// W_N^k = exp(-2 pi i k / N), k < N / 2, in double precision (host libm), one table per (device, N), kept for the
-// life of the process (the pitch correlation kernels)
-static int fft_twiddles(int N, const double** out) {
-    static std::mutex mu;
-    static std::map<std::pair<int, int>, double*> cache;
-    int dev = 0;
-    RSAF_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(mu);
-    auto it = cache.find({dev, N});
-    if (it == cache.end()) {
-        std::vector<double> h((size_t)N);                          // N / 2 complex numbers
-        for (int k = 0; k < N / 2; ++k) {
-            const double a = 2.0 * M_PI * (double)k / (double)N;
-            h[2 * k] = cos(a);
-            h[2 * k + 1] = -sin(a);
-        }
-        if (N >= 4) { h[2 * (N / 4)] = 0.0; h[2 * (N / 4) + 1] = -1.0; }      // exactly -i
-        double* d = nullptr;
-        RSAF_CHECK_HIP(hipMalloc(&d, (size_t)N * sizeof(double)));
-        RSAF_CHECK_HIP(hipMemcpy(d, h.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice));
-        it = cache.emplace(std::make_pair(dev, N), d).first;
-    }
-    *out = it->second;
-    return RSAF_OK;
-}
-
-// one PitchPlan per call (checks + geometry), then one function per launch family
-
-// the 18 doubles of params_host (include/rsaf.h; filled by mshds.py MshdsEngine.pitch)
-enum PitchSlot {
-    PS_DT, PS_MIN_PITCH, PS_CEILING, PS_VOICING_THR, PS_OCTAVE_COST, PS_SILENCE_THR, PS_OCTAVE_JUMP, PS_VUV,
-    PS_NSAMP_WINDOW, PS_NSAMP_PERIOD, PS_MIN_LAG, PS_MAX_LAG, PS_BRENT_IXMAX, PS_MAX_CAND, PS_REFINE_DEPTH, PS_IS_CC,
-    PS_DT_WINDOW,
-    PS_TABLE_MODE,      // 0: shared Chebyshev table only, 1: + the tables of the clipped depths, 2: one table per cell
-};
-
-// lags 0 .. L of a stored correlation row: max_lag of a cross-correlation, brent_ixmax of an autocorrelation
-static int pitch_row_lags(const double* h) { return (int)h[PS_IS_CC] ? (int)h[PS_MAX_LAG] : (int)h[PS_BRENT_IXMAX]; }
-
-// workspace per frame: the correlation row, the coefficient blocks of two candidate lists, the frame record
-static inline int64_t pitch_ws_bytes_per_frame(int rstride) {
-    return (int64_t)rstride * (int64_t)sizeof(double) + 2 * (int64_t)PC_DOUBLES * (int64_t)sizeof(double) + (int64_t)HDR_INTS * (int64_t)sizeof(int);
-}
-
-struct PitchCall {      // what the two entries share
-    const float* wav;
-    const ClipInfo* ci;
-    int n_clips, max_frames;
-    const double* gpeak;
-    const double *window, *window_r, *sinc_cheb;
-    double* workspace;
-    int64_t workspace_bytes;
-    hipStream_t stream;
-};
-
-// the outputs of one voicing threshold.  A dual call has two: the frame kernels share the correlation and the
-// refinement, the path finder runs once per threshold
-struct PitchOutputs {
-    FrameOut* frame_out;
-    unsigned char* psi;
-    int* end_state;
-    double *sel_freq, *sel_strength, *stats;
-    bool complete() const { return frame_out && psi && end_state && sel_freq && sel_strength && stats; }
-};
-
-struct PitchPlan {
-    PitchParams P;
-    double silence_thr, octave_jump, vuv;   // the path finder's costs
-    bool dual;
-    int seg_len, Lr, rstride;               // samples a frame reads; lags 0 .. Lr of a row; doubles per row (+ the relative intensity)
-    int ncc, log2m, log2n;                  // CC: complex FFT length; AC: nfft = 2^(log2m + 1); CC: ncc = 2^log2n before padding
-    // correlation mode: one wave per frame with S = 64 wave_r complex points (AC: 8 / 16 / 32, CC: 16 / 32), or
-    // wave_r = 0: the 4 096-point cross-correlation on the workgroup kernel pitch_cc_kernel<12>
-    int wave_r;
-    size_t lds_corr, lds_cand, lds_cell;    // workgroup correlation kernel, candidate kernel, per-cell coefficient kernel
-    int cell_b_lo, cell_n_b, cell_ntap_pad; // per-cell tables (mshds.sinc_cell_tables): cells b_lo .. b_lo + n_b - 1, padded taps
-    bool defer;                             // refinement in its own kernels (false: RSAF_PITCH_INKERNEL, the tests' A/B reference)
-    bool grouped;                           // ... with the coefficients built per cell by pitch_cell_coef_kernel
-    const double* cheb;                     // table of the candidate kernel's Chebyshev form; nullptr: direct sinc sums
-    int group;                              // clips per pass through the workspace
-    double corr_flops, corr_lds;            // ProfScope models of the correlation kernel, per frame
-};
-
-// grid of pitch_cell_coef_kernel over `gframes` frames: a workgroup per (cell, chunk of frames), the chunks dealt in eights
-constexpr int CELL_CHUNK_FRAMES = 4096;
-static int64_t cell_workgroups(const PitchPlan& pl, int64_t gframes, int* n_chunks_out) {
-    const int64_t n_chunks = (gframes + CELL_CHUNK_FRAMES - 1) / CELL_CHUNK_FRAMES;
-    if (n_chunks_out) *n_chunks_out = (int)n_chunks;
-    return 8 * (int64_t)pl.cell_n_b * ((n_chunks + 7) / 8);
-}
-
-// Every argument check and the geometry of a call; makes no HIP call. n_clips == 0 leaves the plan unset (nothing to run).
-static int pitch_plan(const PitchCall& c, const double* h, const PitchOutputs& o1, const PitchOutputs& o2,
-                      double voicing_thr2, PitchPlan* plan) {
-    PitchPlan& pl = *plan;
-    PitchParams& P = pl.P;
-    const int n_clips = c.n_clips, max_frames = c.max_frames;
-    RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_frames >= 0, "bad clip/frame count");
-    if (n_clips == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(c.wav && c.ci && c.gpeak && h && o1.complete(), "NULL pointer");
-    const bool dual = pl.dual = voicing_thr2 >= 0.0;
-    RSAF_CHECK_ARG(!dual || o2.complete(), "NULL pointer (second threshold outputs)");
-    P.dt = h[PS_DT]; P.min_pitch = h[PS_MIN_PITCH]; P.ceiling = h[PS_CEILING]; P.voicing_thr = h[PS_VOICING_THR];
-    P.octave_cost = h[PS_OCTAVE_COST];
-    pl.silence_thr = h[PS_SILENCE_THR]; pl.octave_jump = h[PS_OCTAVE_JUMP]; pl.vuv = h[PS_VUV];
-    P.nsamp_window = (int)h[PS_NSAMP_WINDOW]; P.nsamp_period = (int)h[PS_NSAMP_PERIOD];
-    P.min_lag = (int)h[PS_MIN_LAG]; P.max_lag = (int)h[PS_MAX_LAG]; P.brent_ixmax = (int)h[PS_BRENT_IXMAX];
-    P.max_cand = (int)h[PS_MAX_CAND]; P.refine_depth = (int)h[PS_REFINE_DEPTH]; P.is_cc = (int)h[PS_IS_CC];
-    P.dt_window = h[PS_DT_WINDOW];
-    const int table_mode = (int)h[PS_TABLE_MODE];
-    P.cheb_clipped = table_mode == 1 ? 1 : 0;
-    P.voicing_thr2 = dual ? voicing_thr2 : -1.0;
-    { const char* e = getenv("RSAF_PITCH_STOP"); P.debug_stop = e ? atoi(e) : 0; }
-    P.half_window = P.nsamp_window / 2;
-    P.half_period = P.nsamp_period / 2 + 1;
-    RSAF_CHECK_ARG(P.max_cand >= 2 && P.max_cand <= MAXC - 1, "max_candidates must be in [2, 15]");
-    RSAF_CHECK_ARG(P.nsamp_window >= 4 && P.brent_ixmax >= 2 && P.max_lag >= 2, "window too short");
-    RSAF_CHECK_ARG(P.is_cc || (c.window && c.window_r), "AC needs the window tables");
-    RSAF_CHECK_ARG((P.is_cc ? P.max_lag : P.brent_ixmax) <= 1023, "more than 1023 lags (pitch floor below ~16 Hz) is not supported");
-    P.nfft = 1;                                                    // Praat: while (nsampFFT < nsamp_window * (1 + 0.5)) nsampFFT *= 2
-    while ((double)P.nfft < (double)P.nsamp_window * 1.5) P.nfft *= 2;
-    if (P.nfft < 16) P.nfft = 16;
-    RSAF_CHECK_ARG(P.is_cc || P.nsamp_window + P.brent_ixmax <= P.nfft, "brent_ixmax must not exceed half the analysis window");
-    const int seg_len = pl.seg_len = P.is_cc ? P.nsamp_window + P.max_lag + 1 : P.nsamp_window;
-    const int Lr = pl.Lr = pitch_row_lags(h);
-    pl.rstride = Lr + 2;                                           // r[0..L] + the frame's relative intensity
-    int ncc = 64;                                                  // CC: complex FFT length, >= nw + max_lag + 1
-    while (ncc < seg_len) ncc *= 2;
-    RSAF_CHECK_ARG(!P.is_cc || ncc <= 4096, "cross-correlation window + lag range longer than 4 095 samples is not supported");
-    RSAF_CHECK_ARG(P.is_cc || P.nfft <= 4096, "autocorrelation window longer than 2 730 samples is not supported");
-    // the workgroup cross-correlation kernel: two complex buffers + sumy2 + scratch
-    pl.lds_corr = P.is_cc ? (size_t)ncc * 2 * 2 * sizeof(double) + (size_t)(((Lr + 2) & ~1) + 32) * sizeof(double) : 0;
-    pl.defer = getenv("RSAF_PITCH_INKERNEL") == nullptr;
-    pl.grouped = pl.defer && table_mode == 2 && !dual && P.is_cc && c.sinc_cheb != nullptr;
-    int r_lo_h, r_hi_h;                                            // (as in the kernel: the depth-30 estimates' reach in grouped mode)
-    pitch_r_range(P.brent_ixmax, Lr, P.min_lag, P.max_lag, pl.grouped ? 30 : P.refine_depth, &r_lo_h, &r_hi_h);
-    pl.lds_cand = (size_t)(((r_hi_h - r_lo_h + 2) & ~1) + 3 * MAX_MAXIMA + 6 * MAXC + MAXC * 2 * NCH) * sizeof(double) +
-                  (size_t)(MAX_MAXIMA + 2 * MAXC + 4) * sizeof(int);
-    RSAF_CHECK_ARG(pl.lds_corr <= 150 * 1024 && pl.lds_cand <= 150 * 1024, "analysis window too long for LDS");
-    // the correlation rows of a group of clips live in the caller's workspace between the kernels, and behind them what the
-    // candidate kernel leaves for the refinement kernels: per frame the coefficient blocks of two lists and a 128-byte record
-    const int64_t row_bytes_per_clip = (int64_t)max_frames * pitch_ws_bytes_per_frame(pl.rstride);
-    RSAF_CHECK_ARG(max_frames == 0 || (c.workspace && c.workspace_bytes >= row_bytes_per_clip),
-                   "workspace too small (rsaf_mshds_pitch_workspace_bytes)");
-    int group = max_frames == 0 ? n_clips : (int)std::min<int64_t>(n_clips, c.workspace_bytes / std::max<int64_t>(row_bytes_per_clip, 1));
-    if (max_frames > 0) group = (int)std::min<int64_t>(group, ((int64_t)1 << 26) / max_frames > 0 ? ((int64_t)1 << 26) / max_frames : 1);   // frame index in 27 bits (cell queue)
-    pl.group = group;
-    RSAF_CHECK_ARG(table_mode != 2 || (!dual && P.is_cc), "per-cell tables serve single-threshold cross-correlation analyses only");
-    pl.log2m = 0;
-    while ((2 << pl.log2m) < P.nfft) ++pl.log2m;                   // nfft = 2 M = 2^(log2m + 1)
-    pl.log2n = 0;
-    while ((1 << pl.log2n) < ncc) ++pl.log2n;
-    // transform lengths of 512 .. 2048 complex points run one wave per frame: every autocorrelation (nfft <= 4096) and
-    // every cross-correlation but the 4 096-point one, which takes the workgroup kernel pitch_cc_kernel<12>.
-    // A shorter transform is zero-padded up to the smallest wave size: the correlation is linear as long as the lags stay
-    // below (transform length - window), so a longer transform returns the same values (autocorrelation: 512 complex =
-    // 1024 real points; cross-correlation: 1024 points, whose transform back has the 512 the wave kernel needs).
-    int wave_r = 0;
-    if (!P.is_cc) wave_r = pl.log2m <= 9 ? 8 : 1 << (pl.log2m - 6);
-    else if (pl.log2n <= 11) wave_r = pl.log2n <= 10 ? 16 : 32;
-    if (wave_r && !P.is_cc) P.nfft = 128 * wave_r;                  // 2 S real points
-    if (wave_r && P.is_cc) ncc = 64 * wave_r;
-    pl.wave_r = wave_r;
-    pl.ncc = ncc;
-    // the Chebyshev form needs the full depth on both sides of every cell a candidate can use
-    pl.cheb = table_mode == 2 ? nullptr : c.sinc_cheb;
-    const int cell_lag_lo = P.min_lag > 2 ? P.min_lag : 2;
-    const int cell_lag_hi = std::min(P.max_lag - 1, P.brent_ixmax - 1);
-    const bool unclipped = P.brent_ixmax + cell_lag_lo - 1 >= P.refine_depth && cell_lag_hi + 2 + P.refine_depth <= P.brent_ixmax;
-    P.cheb_all_full = unclipped ? 1 : 0;
-    if (pl.cheb == nullptr) P.cheb_clipped = 0;
-    // clipped analyses keep the Chebyshev form only with the per-depth tables behind the shared one
-    if (!unclipped && !P.cheb_clipped) pl.cheb = nullptr;
-    // per-cell tables (mshds.sinc_cell_tables): cells b_lo .. b_hi, the lags 0 .. L (r is symmetric: the two taps that meet
-    // a lag are summed in the table) padded to a multiple of four
-    pl.cell_b_lo = P.brent_ixmax + cell_lag_lo - 1;
-    pl.cell_n_b = cell_lag_hi - cell_lag_lo + 2;
-    pl.cell_ntap_pad = (Lr + 1 + 3) & ~3;
-    pl.lds_cell = (size_t)pl.cell_ntap_pad * NCH * sizeof(double) + 4 * CELL_Q * sizeof(unsigned);
-    if (pl.grouped) {
-        RSAF_CHECK_ARG(pl.cell_n_b >= 1 && pl.lds_cell <= 150 * 1024, "per-cell tables: lag range too long for LDS");
-        if (max_frames > 0 && P.debug_stop == 0)                   // the largest grid of the call: that of a full group
-            RSAF_CHECK_ARG(cell_workgroups(pl, (int64_t)group * max_frames, nullptr) <= 0x7fffffffLL,
-                           "per-cell tables: too many workgroups");
-    }
-    // algorithmic flops of the correlation kernels, counted for equal-length clips (an upper bound for ragged batches);
-    // the candidate kernel's work is not counted
-    // AC: two complex FFTs of M = nfft / 2 points (5 M log2 M flops each) and the spectrum pass (~30 flops per point)
-    const double Mfft = 0.5 * (double)P.nfft;
-    const double ac_flops = 2.0 * 5.0 * Mfft * log2(Mfft) + 30.0 * Mfft;
-    // CC: one complex FFT of ncc points, one of ncc / 2, the spectrum pass (~40 flops per point) and the prefix sums
-    const double cc_flops = 5.0 * ncc * log2((double)ncc) + 2.5 * ncc * log2(0.5 * ncc) + 40.0 * 0.5 * ncc + 4.0 * seg_len;
-    // LDS bytes a frame moves through the FFT kernel (every pass reads and writes its N complex doubles: log4 stages of
-    // each transform, the staging pass and the spectrum pass): the kernel's own roofline is the LDS, not the FLOPs
-    // (one wave per frame, wave_fft.h: two exchanges per transform, each writing and reading the S complex doubles, and the
-    // paired spectrum step: 160 S bytes per autocorrelation frame, 120 S + the running sums per cross-correlation frame)
-    const double ac_lds = 160.0 * Mfft;
-    const double cc_lds = wave_r ? 120.0 * ncc + 16.0 * Lr
-                                 : 16.0 * ncc * (ceil(log2((double)ncc) / 2.0) + 2.0) * 2.0 + 16.0 * 0.5 * ncc * (ceil(log2(0.5 * ncc) / 2.0) + 1.0) * 2.0;
-    pl.corr_flops = P.is_cc ? cc_flops : ac_flops;
-    pl.corr_lds = P.is_cc ? cc_lds : ac_lds;
-    return RSAF_OK;
-}
-
-// what has to happen once per call ahead of the launches: the kernels' LDS limits and the twiddle tables
-// tw: AC: W_nfft^k;  CC: W_2N^k, the N-point complex transform of the workgroup kernel
-// tw2: CC: W_N^k, the N/2-point transform and the spectrum pass
-static int pitch_prepare(const PitchPlan& pl, const double2_t** tw_out, const double2_t** tw2_out) {
-    if (!pl.wave_r)                                                 // 128 KB of LDS and more
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cc_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_corr));
-    const double *tw = nullptr, *tw2 = nullptr;
-    int rc = fft_twiddles(pl.P.is_cc ? 2 * pl.ncc : pl.P.nfft, &tw);
-    if (rc == RSAF_OK && pl.P.is_cc) rc = fft_twiddles(pl.ncc, &tw2);
-    if (rc != RSAF_OK) return rc;
-    *tw_out = reinterpret_cast<const double2_t*>(tw);
-    *tw2_out = reinterpret_cast<const double2_t*>(tw2);
-    if (pl.lds_cand > 48 * 1024)
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cand_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)pl.lds_cand));
-    if (pl.grouped && pl.lds_cell > 48 * 1024)
-        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)pitch_cell_coef_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)pl.lds_cell));
-    return RSAF_OK;
-}
-
-// the clips of one pass through the workspace, which holds: rows | coefficients of list A | of list B | frame records
-struct PitchGroup {
-    const ClipInfo* ci;
-    const double* gpeak;
-    int nc;
-    double *pc_a, *pc_b;
-    int* hdr;
-};
-
-static PitchGroup pitch_group(const PitchCall& c, const PitchPlan& pl, int c0) {
-    PitchGroup g;
-    g.ci = c.ci + c0;
-    g.gpeak = c.gpeak + c0;
-    g.nc = std::min(pl.group, c.n_clips - c0);
-    const int64_t gframes = (int64_t)g.nc * c.max_frames;
-    g.pc_a = c.workspace + gframes * pl.rstride;
-    g.pc_b = g.pc_a + gframes * PC_DOUBLES;
-    g.hdr = reinterpret_cast<int*>(g.pc_b + gframes * PC_DOUBLES);
-    return g;
-}
-
-template <int R>
-static void launch_ac_wave(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, dim3 grid, const double2_t* tw) {
-    hipLaunchKernelGGL(pitch_ac_wave_kernel<R>, grid, dim3(64), (size_t)wfft::Plan<R>::LDS_DOUBLES * sizeof(double), c.stream,
-                       c.wav, g.ci, g.gpeak, c.window, c.window_r, pl.P, tw, c.workspace, pl.rstride, c.max_frames);
-}
-
-template <int R>
-static void launch_cc_wave(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, dim3 grid, const double2_t* tw2) {
-    const size_t lds_w = (size_t)(wfft::Plan<R>::LDS_DOUBLES + ((pl.Lr + 3) & ~1)) * sizeof(double);
-    hipLaunchKernelGGL(pitch_cc_wave_kernel<R>, grid, dim3(64), lds_w, c.stream, c.wav, g.ci, g.gpeak, pl.P, tw2,
-                       c.workspace, pl.rstride, c.max_frames);
-}
-
-// family "mshds_pitch_{ac,cc}_fft": the correlation kernel alone (FLOPs = its FFTs, bytes = its LDS traffic)
-static int launch_correlation(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, const double2_t* tw, const double2_t* tw2) {
-    ProfScope prof(pl.P.is_cc ? "mshds_pitch_cc_fft" : "mshds_pitch_ac_fft", c.stream,
-                   pl.corr_flops * (double)c.max_frames * (double)g.nc, pl.corr_lds * (double)c.max_frames * (double)g.nc);
-    const dim3 wave_grid((c.max_frames + WF_FRAMES - 1) / WF_FRAMES, g.nc);      // one wave per frame (wave_fft.h)
-    if (!pl.wave_r)         // 4 096-point cross-correlation: the workgroup kernel
-        hipLaunchKernelGGL(pitch_cc_kernel<12>, dim3((c.max_frames + CC_FRAMES_PER_WG - 1) / CC_FRAMES_PER_WG, g.nc), dim3(256),
-                           pl.lds_corr, c.stream, c.wav, g.ci, g.gpeak, pl.P, tw, tw2, c.workspace, pl.rstride, c.max_frames);
-    else if (pl.P.is_cc)
-        switch (pl.wave_r) {
-            case 16: launch_cc_wave<16>(c, pl, g, wave_grid, tw2); break;
-            case 32: launch_cc_wave<32>(c, pl, g, wave_grid, tw2); break;
-        }
-    else
-        switch (pl.wave_r) {
-            case 8: launch_ac_wave<8>(c, pl, g, wave_grid, tw); break;
-            case 16: launch_ac_wave<16>(c, pl, g, wave_grid, tw); break;
-            case 32: launch_ac_wave<32>(c, pl, g, wave_grid, tw); break;
-        }
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// family "mshds_pitch_cand": maxima, candidate lists, Brent refinement.  Work model: every frame's normalised
-// correlation row comes back from the HBM workspace ((Lr + 2) doubles); on the Chebyshev path the coefficient build
-// of the frame's candidates runs on the fp64 matrix pipe: ceil(2 depth / 4) tap groups x 2 column tiles of
-// v_mfma_f64_16x16x4_f64 (2 048 flops each).  The Brent iterations themselves (a dozen polynomial evaluations per
-// candidate) and the direct path's sinc sums are not counted.
-static int launch_candidates(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, FrameOut* out, FrameOut* out2) {
-    const double rows = (double)c.max_frames * (double)g.nc;     // frames as the ProfScope models count them
-    const DeferArgs DA{pl.defer ? g.hdr : nullptr, pl.defer ? g.pc_a : nullptr, pl.defer ? g.pc_b : nullptr, pl.grouped ? 1 : 0};
-    ProfScope prof(pl.grouped ? "mshds_pitch_cand_lists" : pl.cheb ? "mshds_pitch_cand_cheb" : "mshds_pitch_cand_direct", c.stream,
-                   pl.cheb ? rows * 2048.0 * 2.0 * ceil(2.0 * pl.P.refine_depth / 4.0) : 0.0,
-                   rows * (double)(pl.Lr + 2) * 8.0);
-    hipLaunchKernelGGL(pitch_cand_kernel, dim3(c.max_frames, g.nc), dim3(CT), pl.lds_cand, c.stream, g.ci, g.gpeak, pl.P,
-                       (const double*)c.workspace, pl.rstride, c.max_frames, out, out2, pl.cheb, DA);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// the deferred refinement: per-cell coefficients where the plan says so, then Brent's search with one candidate per lane
-static int launch_refinement(const PitchCall& c, const PitchPlan& pl, const PitchGroup& g, FrameOut* out, FrameOut* out2) {
-    const double rows = (double)c.max_frames * (double)g.nc;
-    if (pl.grouped) {
-        // one table per cell on the fp64 matrix pipe: <= 28 cells per frame x (2 L + 1) taps x 16 coefficients
-        int n_chunks;
-        const int64_t n_wg = cell_workgroups(pl, (int64_t)g.nc * c.max_frames, &n_chunks);
-        ProfScope prof("mshds_pitch_cand_cells", c.stream, rows * 28.0 * 2.0 * pl.cell_ntap_pad * NCH,   // <= 28 cells per frame
-                       rows * 28.0 * (double)(pl.Lr + 1) * 8.0);
-        hipLaunchKernelGGL(pitch_cell_coef_kernel, dim3((unsigned)n_wg), dim3(256), pl.lds_cell, c.stream, g.ci, g.nc, c.max_frames,
-                           (const int*)g.hdr, (const double*)c.workspace, pl.rstride, pl.Lr, pl.P.brent_ixmax, c.sinc_cheb,
-                           pl.cell_b_lo, pl.cell_n_b, pl.cell_ntap_pad, CELL_CHUNK_FRAMES, n_chunks, g.pc_a);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    // list A is the one of the lower voicing threshold
-    const bool low_is_second = pl.dual && pl.P.voicing_thr2 < pl.P.voicing_thr;
-    FrameOut* oa = low_is_second ? out2 : out;
-    FrameOut* ob = low_is_second ? out : out2;
-    ProfScope prof("mshds_pitch_cand_brent", c.stream, 0.0, rows * 15.0 * 2.0 * NCH * 8.0);
-    hipLaunchKernelGGL(pitch_brent_kernel, dim3((c.max_frames + BR_FRAMES - 1) / BR_FRAMES, g.nc), dim3(64), 0, c.stream, g.ci,
-                       (const int*)g.hdr, (const double*)g.pc_a, (const double*)g.pc_b, c.max_frames, pl.P.brent_ixmax, oa, ob);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// path finder, backtrack and statistics of one voicing threshold, all clips of the call
-static int launch_paths(const PitchCall& c, const PitchPlan& pl, const PitchOutputs& o, double voicing_thr) {
-    const PitchParams& P = pl.P;
-    {
-        ProfScope prof("mshds_pitch_path", c.stream, 0.0, 0.0);
-        hipLaunchKernelGGL(path_kernel, dim3(c.n_clips), dim3(64), 0, c.stream, (const FrameOut*)o.frame_out, c.ci, P.dt,
-                           pl.silence_thr, voicing_thr, P.octave_cost, pl.octave_jump, pl.vuv, P.ceiling, o.psi, o.end_state);
-        RSAF_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(backtrack_kernel, dim3(c.n_clips), dim3(256), 0, c.stream, (const FrameOut*)o.frame_out, c.ci, o.psi,
-                           o.end_state, o.sel_freq, o.sel_strength);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(pitch_stats_kernel, dim3(c.n_clips), dim3(64), 0, c.stream, o.sel_freq, c.ci, P.ceiling, o.stats);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// o2 / voicing_thr2 >= 0: the same analysis for a second voicing threshold (rsaf_mshds_pitch_dual)
-static int pitch_run(const PitchCall& c, const double* params_host, const PitchOutputs& o1, const PitchOutputs& o2,
-                     double voicing_thr2) {
-    PitchPlan pl;
-    int rc = pitch_plan(c, params_host, o1, o2, voicing_thr2, &pl);
-    if (rc != RSAF_OK || c.n_clips == 0) return rc;
-    const double2_t *tw, *tw2;
-    if ((rc = pitch_prepare(pl, &tw, &tw2)) != RSAF_OK) return rc;
-    FrameOut* out2 = pl.dual ? o2.frame_out : nullptr;
-    for (int c0 = 0; c.max_frames > 0 && c0 < c.n_clips; c0 += pl.group) {
-        const PitchGroup g = pitch_group(c, pl, c0);
-        if ((rc = launch_correlation(c, pl, g, tw, tw2)) != RSAF_OK) return rc;
-        if ((rc = launch_candidates(c, pl, g, o1.frame_out, out2)) != RSAF_OK) return rc;
-        if (pl.defer && pl.P.debug_stop == 0 && (rc = launch_refinement(c, pl, g, o1.frame_out, out2)) != RSAF_OK) return rc;
-    }
-    if ((rc = launch_paths(c, pl, o1, pl.P.voicing_thr)) != RSAF_OK) return rc;
-    return pl.dual ? launch_paths(c, pl, o2, voicing_thr2) : RSAF_OK;
-}
-
-extern "C" {
-
-// bytes of correlation rows per clip (max_frames rows of max_lag + 2 doubles); the analysis runs the clips in groups of
-// floor(workspace_bytes / this), so any multiple >= 1 works and n_clips multiples avoid the grouping
-int64_t rsaf_mshds_pitch_workspace_bytes_per_clip(int max_frames, const double* params_host /* 18 doubles */) {
-    if (!params_host || max_frames < 0) return -1;
-    return (int64_t)max_frames * pitch_ws_bytes_per_frame(pitch_row_lags(params_host) + 2);
-}
-
-int rsaf_mshds_pitch(const float* wav, const void* clip_info, int n_clips, int max_frames, const double* gpeak,
-                     const double* window, const double* window_r, const double* params_host /* 18 doubles */,
-                     void* frame_out, unsigned char* psi, int* end_state, double* sel_freq, double* sel_strength, double* stats_out,
-                     const double* sinc_cheb, void* workspace, int64_t workspace_bytes, rsaf_stream_t stream) {
-    const PitchCall call{wav, (const ClipInfo*)clip_info, n_clips, max_frames, gpeak, window, window_r, sinc_cheb,
-                         (double*)workspace, workspace_bytes, (hipStream_t)stream};
-    return pitch_run(call, params_host, PitchOutputs{(FrameOut*)frame_out, psi, end_state, sel_freq, sel_strength, stats_out},
-                     PitchOutputs{}, -1.0);
-}
-
-int rsaf_mshds_pitch_dual(const float* wav, const void* clip_info, int n_clips, int max_frames, const double* gpeak,
-                          const double* window, const double* window_r, const double* params_host /* 18 doubles */,
-                          void* frame_out, unsigned char* psi, int* end_state, double* sel_freq, double* sel_strength,
-                          double* stats_out, double voicing_threshold2, void* frame_out2, unsigned char* psi2, int* end_state2,
-                          double* sel_freq2, double* sel_strength2, double* stats_out2, const double* sinc_cheb,
-                          void* workspace, int64_t workspace_bytes, rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(voicing_threshold2 >= 0.0, "second voicing threshold must be >= 0");
-    const PitchCall call{wav, (const ClipInfo*)clip_info, n_clips, max_frames, gpeak, window, window_r, sinc_cheb,
-                         (double*)workspace, workspace_bytes, (hipStream_t)stream};
-    return pitch_run(call, params_host, PitchOutputs{(FrameOut*)frame_out, psi, end_state, sel_freq, sel_strength, stats_out},
-                     PitchOutputs{(FrameOut*)frame_out2, psi2, end_state2, sel_freq2, sel_strength2, stats_out2},
-                     voicing_threshold2);
-}
-
 
 // peaks of an n-frame contour: at most n/2; the LDS form keeps SR_MAX_PEAKS of them (a smooth 16 ms contour of at most
 // ~8 500 frames has far fewer), the global-memory form of long clips sizes the lists exactly

@@ -1,5 +1,6 @@
-// What more than one MSHDS translation unit uses (mshds.hip, mshds_voice.hip, mshds_cpp.hip): the
-// clip table rows, Praat's sample-index rounding, and the wave / lane-group helpers of the sinc interpolation.
+// What more than one MSHDS translation unit uses (mshds.hip, mshds_pitch.hip, mshds_voice.hip, mshds_cpp.hip): the
+// clip table rows, Praat's sample-index rounding, the wave / lane-group helpers of the sinc interpolation, and Brent's
+// search for a maximum (pitch candidates, syllable nuclei).
 // Every MSHDS .hip includes this header before any code of its own: the three headers below are compiled with FMA
 // contraction on, everything after the pragma (the rest of this header and the including file) with it off.
 #pragma once
@@ -173,16 +174,16 @@ __device__ double sinc_group(const double* __restrict__ y, int n, double x, int 
     return special ? y[si] : acc;
 }
 
-// Praat NUMimproveMaximum (sinc): Brent's minimiser in the netlib fminbr form on -sinc over [ix-1, ix+1],
-// tolerance sqrt(eps)*|x| + tol/3 on the 1-based position, <= 60 iterations.  One G-lane group per
-// candidate; `live` = this group holds a real candidate (others just keep the wave's shuffles uniform).
-template <int G, bool RECUR>
-__device__ void improve_max_group(const double* __restrict__ y, int n, double ix0, int depth, int nz_lo, int nz_hi,
-                                  int lg, bool live, double& xm, double& ym) {
+// Praat NUMimproveMaximum: Brent's minimiser in the netlib fminbr form on f (= minus the interpolated curve, a function
+// of the 1-based position) over [ix1 - 1, ix1 + 1], tolerance sqrt(eps)*|x| + tol/3 on the position, <= 60 iterations.
+// Every lane of the wave evaluates f in every iteration (f may exchange data between lanes); `live` = this lane holds a
+// real candidate, and the loop runs while any lane's candidate is still active.  Returns the 0-based position and the maximum.
+template <class F>
+__device__ __forceinline__ void brent_maximise(F f, double ix1, bool live, double& xm, double& ym) {
     const double SQRT_EPS = 1.4901161193847656e-08, TOL3 = 1e-10 / 3.0;
-    double a = ix0 + 1.0 - 1.0, b = ix0 + 1.0 + 1.0;     // 1-based bracket
+    double a = ix1 - 1.0, b = ix1 + 1.0;
     double v = a + GOLD * (b - a);
-    double fv = -sinc_group<G, RECUR>(y, n, v - 1.0, depth, nz_lo, nz_hi, lg);
+    double fv = f(v);
     double x = v, w = v, fx = fv, fw = fv;
     bool active = live;
     for (int it = 0; it < 60; ++it) {
@@ -202,7 +203,7 @@ __device__ void improve_max_group(const double* __restrict__ y, int n, double ix
         }
         if (fabs(step) < tol_act) step = step > 0.0 ? tol_act : -tol_act;
         const double tt = x + step;
-        const double ft = -sinc_group<G, RECUR>(y, n, tt - 1.0, depth, nz_lo, nz_hi, lg);
+        const double ft = f(tt);
         if (active) {
             if (ft <= fx) {
                 if (tt < x) b = x; else a = x;
@@ -217,6 +218,15 @@ __device__ void improve_max_group(const double* __restrict__ y, int n, double ix
     }
     xm = x - 1.0;
     ym = -fx;
+}
+
+// ... on the sinc interpolation of an LDS array around the 0-based position ix0.  One G-lane group per candidate;
+// `live` = this group holds a real candidate (others just keep the wave's shuffles uniform).
+template <int G, bool RECUR>
+__device__ void improve_max_group(const double* __restrict__ y, int n, double ix0, int depth, int nz_lo, int nz_hi,
+                                  int lg, bool live, double& xm, double& ym) {
+    brent_maximise([&](double v1) { return -sinc_group<G, RECUR>(y, n, v1 - 1.0, depth, nz_lo, nz_hi, lg); }, ix0 + 1.0,
+                   live, xm, ym);
 }
 
 }  // namespace mshds
