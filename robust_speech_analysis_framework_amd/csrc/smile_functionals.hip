@@ -13,6 +13,7 @@
 //
 // Semantics = oracle/smile_oracle.py (sma3 / delta2 with edge replication, population moments).
 #include "rsaf_common.h"
+#include "smile_layout.h"
 
 #pragma clang fp contract(off)
 
@@ -101,10 +102,13 @@ __global__ __launch_bounds__(256) void smile_functionals_kernel(const double* __
     const int T = (int)(frame_off[clip + 1] - fo);
 
     // column placement (cCsvSink order: lld, lld_de, lld2, lld2_de, lld3, lld3_de)
+    // (a level of n rows takes 2 n NFUNC columns, so the level that begins at row lo begins at column 2 lo NFUNC)
+    constexpr int L0 = LLD_LEVEL_BEGIN[0], L1 = LLD_LEVEL_BEGIN[1], L2 = LLD_LEVEL_BEGIN[2];
+    static_assert(L0 == 0 && LLD_LEVEL_END[0] == L1 && LLD_LEVEL_END[1] == L2 && LLD_LEVEL_END[2] == NLLD, "the levels tile the rows");
     int lo, nlev, base;
-    if (li < 16) { lo = 0; nlev = 16; base = 0; }
-    else if (li < 22) { lo = 16; nlev = 6; base = 16 * 24; }
-    else { lo = 22; nlev = 16; base = 22 * 24; }
+    if (li < L1) { lo = L0; nlev = L1 - L0; base = L0 * 2 * NFUNC; }
+    else if (li < L2) { lo = L1; nlev = L2 - L1; base = L1 * 2 * NFUNC; }
+    else { lo = L2; nlev = NLLD - L2; base = L2 * 2 * NFUNC; }
     double* o_s = out + (int64_t)clip * RSAF_SMILE_NFEAT + base + (li - lo) * NFUNC;
     double* o_d = o_s + nlev * NFUNC;
 

@@ -35,6 +35,7 @@
 #include <vector>
 
 #include "rsaf_common.h"
+#include "smile_layout.h"
 
 namespace rsaf {
 namespace smile {
@@ -53,38 +54,6 @@ constexpr double I0 = 1e-6;
 constexpr double SHS_MINPITCH = 52.0, SHS_MAXPITCH = 620.0;
 constexpr double LN2 = 0.69314718055994530942;
 
-constexpr int RUNW = 16;                 // frames per wave
-constexpr int NSUM = 23;                 // doubles a frame leaves for the end-of-run pass (slots 0 .. 22)
-constexpr int RED_D = 8 * 65;            // doubles of the 8-sums-at-a-time reduction scratch
-
-template <int LOG2N>
-struct Geo {
-    static constexpr int NFFT = 1 << LOG2N;
-    static constexpr int NC = NFFT / 2;              // complex points of the packed-real transform
-    static constexpr int NB = NC + 1;                // magnitude bins
-    static constexpr int PPL = NC / 64;              // bins per lane (2, 4, 8, 16)
-    static constexpr int NBP = NC + 8;               // padded length of the per-bin tables
-    // LDS of one wave, in doubles.  Round 4: the octave spectrum no longer has a buffer of its own - it lives in the second half
-    // of the dead FFT buffer plus a zero pad behind it, the spline moments take the first half once the enhanced spectrum is
-    // consumed, and the two magnitude arrays swap roles from frame to frame (this frame's magnitudes ARE the next frame's
-    // "previous" ones: no copy; the smoothed and the summation spectrum go to the array the flux has finished with):
-    // 15.6 -> 12.7 KB per wave at 16 kHz, i.e. 12 instead of 10 waves per CU.
-    // The 2 048-point instance (44.1 / 48 kHz) is trimmed to the last double: 40 928 bytes per wave = FOUR waves per CU instead
-    // of three (its arrays need NC + 1 entries and the FFT buffer exactly 2 NC; the shorter instances keep the padding the
-    // reduction scratch in the FFT buffer relies on).
-    static constexpr bool TRIM = LOG2N >= 11;
-    static constexpr int Z_D = 2 * NC + (TRIM ? 0 : 8);   // FFT buffer (c64[NC]); later the enhanced spectrum / spline moments | octave spectrum
-    static constexpr int ARR = NC + (TRIM ? 2 : 8);       // one per-bin array (NB = NC + 1 entries)
-    static constexpr int PAD_D = ((NC * 5) / 8 + 8 + 7) & ~7;   // zeros behind the octave spectrum: longer than the largest harmonic shift (< 0.62 NC)
-    static constexpr int S_D = (Z_D - ARR) + PAD_D;  // the octave spectrum's room: NB bins + the pad
-    static_assert(S_D >= NB + (NC * 5) / 8 + 1, "octave spectrum + pad must fit");
-    static constexpr int MELCAP = NC / 4;            // cap of the longest side of a triangular mel band, in bins
-    static constexpr bool RED_IN_Z = Z_D >= RED_D;   // the reduction scratch lives in the FFT buffer when it fits
-    static constexpr int OFF_S = ARR, OFF_P0 = Z_D + PAD_D, OFF_P1 = OFF_P0 + ARR, OFF_STASH = OFF_P1 + ARR;
-    static constexpr int OFF_RED = RED_IN_Z ? 0 : OFF_STASH + RUNW * NSUM;
-    static constexpr int WAVE_D = OFF_STASH + RUNW * NSUM + (RED_IN_Z ? 0 : RED_D);
-};
-
 // ---- constant tables (host-computed in double, one blob per (device, sample rate)) -------------------
 template <int LOG2N>
 struct __attribute__((aligned(16))) Tables {
@@ -92,14 +61,12 @@ struct __attribute__((aligned(16))) Tables {
     c64 tw[G::NC + G::NC / 2];        // exp(-2 pi i k / NFFT), k < 3 NC / 2: the packed-real unpack uses k <= NC, the
                                       // complex stages exp(-2 pi i m / NC) = tw[2 m], m < 3 NC / 4
     double ham[G::NFFT];              // Hamming window, zero beyond the frame
-    double lo_wt[G::NBP];             // HTK lower-channel weight per bin (0 where unused)
     double sharp[G::NBP];             // bark(f) * g(bark) per bin
     double tb[G::NBP];                // octave-scale target i: fractional position inside source interval klo[i]
     double audw[G::NBP];              // auditory weighting of target i
     double sp_g[G::NBP];              // tridiagonal (1, 4, 1) elimination factors, 0 at bin 0
     int klo[G::NBP];
     double dct[NMEL * 16];            // DCT-II rows 1..12 with the lifter folded in, transposed: [band j][coefficient k] (16 per row)
-    int seg_start[32];                // bins with lower channel c are [seg_start[c], seg_start[c+1]), c = 0..26
     double mel_w[G::MELCAP * 64];     // lane 2 c + side = one side of triangular band c: weight of its i-th bin at [i * 64 + lane]
     int mel_b0[64];                   // ... first bin of that side
     int mel_len, mel_pad[3];          // bins of the longest side
@@ -136,6 +103,7 @@ static void build_tables(Tables<LOG2N>& t, int fs, int frame, int hop) {
     double cf[NMEL + 2];
     for (int c = 0; c < NMEL + 2; ++c) cf[c] = lo + (hi - lo) * c / (NMEL + 1);
     std::vector<int> lo_chan(G::NB, -1);
+    std::vector<double> lo_wt(G::NB, 0.0);                          // HTK lower-channel weight per bin (0 where unused)
     for (int b = 0; b < G::NB; ++b) {
         const double f = b * df;
         if (f < 20.0 || f > fhi) continue;
@@ -143,24 +111,25 @@ static void build_tables(Tables<LOG2N>& t, int fs, int frame, int hop) {
         int c = 0;
         while (c < NMEL && cf[c + 1] <= m) ++c;
         lo_chan[b] = c;
-        t.lo_wt[b] = (cf[c + 1] - m) / (cf[c + 1] - cf[c]);
+        lo_wt[b] = (cf[c + 1] - m) / (cf[c + 1] - cf[c]);
     }
+    int seg_start[NMEL + 2];                                        // bins with lower channel c are [seg_start[c], seg_start[c + 1]), c = 0..26
     int b = 0;
     while (b < G::NB && lo_chan[b] < 0) ++b;
     for (int c = 0; c <= NMEL + 1; ++c) {
         while (b < G::NB && lo_chan[b] >= 0 && lo_chan[b] < c) ++b;
-        t.seg_start[c] = b;
+        seg_start[c] = b;
     }
     // band c (0-based) = rising side (bins whose lower channel is c, weight 1 - lo_wt) + falling side (lower channel c + 1,
     // weight lo_wt); lane 2 c + side walks its side, the weights transposed so that a step of all lanes is one coalesced load
     t.mel_len = 0;
     for (int L = 0; L < 2 * NMEL; ++L) {
         const int seg = (L >> 1) + (L & 1);
-        const int b0 = t.seg_start[seg], b1 = t.seg_start[seg + 1];
+        const int b0 = seg_start[seg], b1 = seg_start[seg + 1];
         t.mel_b0[L] = b0;
         t.mel_len = std::max(t.mel_len, b1 - b0);
         for (int bb = b0; bb < b1 && bb - b0 < G::MELCAP; ++bb)
-            t.mel_w[(bb - b0) * 64 + L] = (L & 1) ? t.lo_wt[bb] : 1.0 - t.lo_wt[bb];
+            t.mel_w[(bb - b0) * 64 + L] = (L & 1) ? lo_wt[bb] : 1.0 - lo_wt[bb];
     }
     t.mel_len = (t.mel_len + 7) & ~7;                               // the kernel walks the sides 8 bins at a time (zero weights behind a side)
     if (t.mel_len > G::MELCAP) t.mel_len = -1;                      // get_tables refuses
@@ -473,6 +442,154 @@ __device__ __forceinline__ void fft_mag(c64* Z, const Tables<LOG2N>* __restrict_
     lds_fence();
 }
 
+// ---- one frame, phase by phase (the phases and their numbers are those of tools/smile_phase.py) -------------------------
+// Phases 7, 9 and 10 and the end-of-run pass are functions; phases 1 - 6 and 8 stand inline in the run loop of the kernel, each
+// under its phase comment: as functions they change the kernel's code (profiles/r17/smile_kernels_asm.txt has the figures).
+//
+// The wave's LDS.  Every view of it is WaveLds<LOG2N>::region(wave_lds()): a constant offset from the LDS base.  (A view
+// kept in a struct member instead is a different kernel to the compiler: four registers more in the 2 048-point instance.)
+__device__ __forceinline__ double* wave_lds() {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    return smem;
+}
+
+// What the phase functions of a frame share: who the frame is, the tables, the outputs.  Their LDS regions they name
+// themselves, by lifetime: WaveLds<LOG2N>::region(wave_lds()), smile_layout.h.
+template <int LOG2N>
+struct FrameCtx {
+    const Tables<LOG2N>* __restrict__ T;
+    int lane;                            // per frame a fresh copy, see the run loop
+    int tr, fr;                          // frame of the run, frame of the clip
+    int64_t fg, total_frames;            // frame of the batch: column of lld, row of cand and octave_dbg
+    double df;
+    double* __restrict__ lld;
+    double* __restrict__ cand;
+    double* __restrict__ octave_dbg;
+};
+
+// phase 7: the spline at the octave-scale targets, negatives reset, auditory weighting -> the octave spectrum
+template <int LOG2N>
+__device__ __forceinline__ void phase_octave_axis(const FrameCtx<LOG2N>& fc) {
+    using L = WaveLds<LOG2N>;
+    constexpr int NC = Geo<LOG2N>::NC, NB = Geo<LOG2N>::NB, PPL = Geo<LOG2N>::PPL;
+    const Tables<LOG2N>* __restrict__ T = fc.T;
+    const int lane = fc.lane;
+    const int64_t fg = fc.fg;
+    const double* A2 = L::prev_frame(wave_lds(), fc.tr);
+    const double* MM = L::moments(wave_lds());
+    double* SS = L::octave(wave_lds());
+    double* octave_dbg = fc.octave_dbg;
+#pragma unroll 1
+    for (int j = 0; j <= PPL; ++j) {
+        const int i = lane + 64 * j;
+        if (i > NC) break;
+        const int kl = T->klo[i];
+        const double b = T->tb[i], aa = 1.0 - b;
+        const double y = aa * A2[kl] + b * A2[kl + 1] + (aa * aa * aa - aa) * MM[kl] + (b * b * b - b) * MM[kl + 1];
+        const double s = fmax(y, 0.0) * T->audw[i];
+        SS[i] = s;
+        if (octave_dbg) octave_dbg[fg * NB + i] = s;
+    }
+    lds_fence();
+}
+
+// phase 9: peaks (y2 > y1 and y2 >= y3) with parabolic refinement, inside 52..620 Hz, positive score: compacted into the
+// peak list (the octave spectrum is dead; at most NC / 2 peaks, the zeros behind it stay zero); returns their number
+template <int LOG2N>
+__device__ __forceinline__ int phase_peak_list(const FrameCtx<LOG2N>& fc) {
+    using L = WaveLds<LOG2N>;
+    constexpr int NC = Geo<LOG2N>::NC, PPL = Geo<LOG2N>::PPL;
+    const Tables<LOG2N>* __restrict__ T = fc.T;
+    const int lane = fc.lane;
+    const double* HH = L::prev_frame(wave_lds(), fc.tr);
+    double* L_sc = L::peak_score(wave_lds());
+    double* L_f = L::peak_freq(wave_lds());
+    int npk = 0;
+#pragma unroll 1
+    for (int j = 0; j <= PPL; ++j) {
+        const int i = lane + 64 * j;
+        bool ok = false;
+        double sc = 0.0, fq = 0.0;
+        if (i >= 1 && i <= NC - 1) {
+            const double y1 = HH[i - 1], y2 = HH[i], y3 = HH[i + 1];
+            if (y2 > y1 && y2 >= y3) {
+                const double den = (y1 - 2.0 * y2) + y3;
+                const double dx = 0.5 * (y1 - y3) / den;
+                sc = y2 - 0.125 * (y1 - y3) * (y1 - y3) / den;
+                fq = exp2(T->fmin_l2 + ((double)i + dx) * T->dl2);
+                ok = fq >= SHS_MINPITCH && fq <= SHS_MAXPITCH && sc > 0.0;
+            }
+        }
+        const unsigned long long m = __ballot(ok);
+        if (ok) {
+            const int p = npk + __popcll(m & ((1ull << lane) - 1ull));
+            L_sc[p] = sc;
+            L_f[p] = fq;
+        }
+        npk += __popcll(m);
+    }
+    lds_fence();
+    return npk;
+}
+
+// phase 10: rank = number of peaks with a higher score (ties: the lower index, i.e. the earlier list entry, first); the
+// NCAND best become the frame's candidates (f0, voicing)
+template <int LOG2N>
+__device__ __forceinline__ void phase_rank(const FrameCtx<LOG2N>& fc, int npk, double hmean) {
+    using L = WaveLds<LOG2N>;
+    const int lane = fc.lane;
+    const double* L_sc = L::peak_score(wave_lds());
+    const double* L_f = L::peak_freq(wave_lds());
+    double* cd = fc.cand + fc.fg * (NCAND * 2);
+    if (lane < NCAND && lane >= npk) { cd[2 * lane] = 0.0; cd[2 * lane + 1] = 0.0; }
+    for (int p0 = 0; p0 < npk; p0 += 64) {
+        const int p = p0 + lane;
+        const double mine = p < npk ? L_sc[p] : 0.0;
+        int rank = 0;
+        for (int q = 0; q < npk; ++q) {
+            const double o = L_sc[q];
+            rank += (o > mine || (o == mine && q < p)) ? 1 : 0;
+        }
+        if (p < npk && rank < NCAND) {
+            cd[2 * rank] = L_f[p];
+            cd[2 * rank + 1] = fmax(0.0, 1.0 - hmean / mine);
+        }
+    }
+    lds_fence();
+}
+
+// end of the run: this lane finishes frame fg from the sums in st (everything that is a scalar function of a frame's sums)
+template <int LOG2N>
+__device__ __forceinline__ void finish_frame(const Tables<LOG2N>* __restrict__ T, const double* st, int frame,
+                                             double* __restrict__ lld, int64_t total_frames, int64_t fg) {
+    constexpr int NB = Geo<LOG2N>::NB;
+    const double N = (double)frame, NBd = (double)NB;
+    auto out = [&](LldRow row, double val) { lld[(int64_t)row * total_frames + fg] = val; };
+    const double tot = st[SUM_TOTAL], safe = tot > 0.0 ? tot : 1.0;
+    out(LLD_RMS_ENERGY, sqrt(st[SUM_W2] / N));                           // cEnergy on winframe
+    out(LLD_ZCR, st[SUM_ZC] / N);                                        // cMZcr on the raw frame
+    const double inten = (st[SUM_HAM_W2] / T->ham_sum) / I0;
+    out(LLD_INTENSITY, inten);
+    out(LLD_LOUDNESS, pow(inten, 0.3));
+    out(LLD_BAND_250_650, st[SUM_BAND1]);
+    out(LLD_BAND_1000_4000, st[SUM_BAND2]);
+    out(LLD_ROLLOFF_25, st[SUM_ROLLOFF + 0]); out(LLD_ROLLOFF_50, st[SUM_ROLLOFF + 1]);
+    out(LLD_ROLLOFF_75, st[SUM_ROLLOFF + 2]); out(LLD_ROLLOFF_90, st[SUM_ROLLOFF + 3]);
+    out(LLD_FLUX, sqrt(st[SUM_FLUX] / NBd));                             // 0 for the first frame of a clip
+    out(LLD_CENTROID, st[SUM_P_F] / safe);
+    out(LLD_ENTROPY, tot > 0.0 ? log2(tot) - (st[SUM_P_LN_P] / LN2) / tot : 0.0);   // -sum p log2 p, p = P / total
+    const double var = st[SUM_M2] / safe, vs = var > 0.0 ? var : 1.0;
+    out(LLD_VARIANCE, var);
+    out(LLD_SKEWNESS, (st[SUM_M3] / safe) / (vs * sqrt(vs)));
+    out(LLD_KURTOSIS, (st[SUM_M4] / safe) / (vs * vs));
+    out(LLD_SLOPE, (NBd * st[SUM_P_F] - T->slope_sf * tot) / T->slope_den);   // of the power spectrum over frequency
+    out(LLD_SHARPNESS, st[SUM_SHARP] / safe);                            // psychoacoustic sharpness
+    out(LLD_HARMONICITY, st[SUM_HARM] / (st[SUM_MAG] > 0.0 ? st[SUM_MAG] : 1.0));   // harmonicity proxy
+    // flatness = geometric / arithmetic mean of the power spectrum; a frame of zeros has the limit value 1
+    out(LLD_FLATNESS, tot > 0.0 ? exp(st[SUM_LN_P] / NBd) / fmax(tot / NBd, 1e-30) : 1.0);
+}
+
+// ---- the kernel: prologue (twiddles, the frame in front of the run, the zeros), the run loop over the phases, the finaliser ----
 template <int LOG2N>
 __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const float* __restrict__ wav, const int64_t* __restrict__ clip_off,
                                                        const int64_t* __restrict__ frame_off, int64_t total_frames,
@@ -481,8 +598,7 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
                                                        const Tables<LOG2N>* __restrict__ T, int stop) {
     using G = Geo<LOG2N>;
     constexpr int NC = G::NC, NB = G::NB, PPL = G::PPL;
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int lane_ = threadIdx.x;
+    const int lane_ = threadIdx.x;       // the run loop works on a per-frame copy of it (`lane` there); outside the loop `lane` is this
     const int lane = lane_;
     const int clip = blockIdx.y;
     const int64_t fo = frame_off[clip];
@@ -494,15 +610,12 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
     const int frame = T->frame, hop = T->hop;
     const double df = T->df;
 
-    c64* Z = reinterpret_cast<c64*>(smem);
-    double* ZD = smem;                                   // the FFT buffer as arrays of doubles once the transform is done
-    double* SS = smem + G::OFF_S;                        // second half of the FFT buffer + the zero pad
-    double* STASH = smem + G::OFF_STASH;
-    double* RED = smem + G::OFF_RED;
+    using L = WaveLds<LOG2N>;                        // regions and lifetimes: smile_layout.h
+    c64* Z = L::template fft<c64>(wave_lds());
+    double* SS = L::octave(wave_lds());
+    double* RED = L::red(wave_lds());
 
-    // frame-invariant per-lane constants kept in registers for the run: the FFT twiddles.  (The Hamming window values are
-    // re-read per frame and the lane index is redefined per frame through an empty asm: with every lane-only expression
-    // hoisted out of the run loop the 512-point instance needed 247 registers - two waves per SIMD - against 166 now.)
+    // frame-invariant per-lane constants kept in registers for the run: the FFT twiddles
     FftTw<LOG2N> W;
     W.load(T, lane);
     double hm[2 * PPL];
@@ -511,19 +624,24 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
     if (f0 > 0) {                                        // magnitudes of the frame in front of the run (for the flux): the "previous" array of frame 0
         double a, b, c;
         frame_to_z<LOG2N>(xclip + (int64_t)(f0 - 1) * hop, hm, frame, Z, lane, a, b, c);
-        fft_mag<LOG2N>(Z, T, W, lane, smem + G::OFF_P1);
+        fft_mag<LOG2N>(Z, T, W, lane, L::prev_frame(wave_lds(), 0));
     }
     // the zero pad behind the octave spectrum: outside the FFT buffer and the reduction scratch, written once
     for (int i = G::Z_D - G::OFF_S + lane; i < G::S_D; i += 64) SS[i] = 0.0;
 
 #pragma unroll 1
     for (int tr = 0; tr < n_run; ++tr) {
+        // The lane index is redefined per frame through an empty asm, and the Hamming values are read again per frame (the
+        // same loads as in front of the loop): with every lane-only expression hoisted out of the run loop the 512-point
+        // instance needed 247 registers - two waves per SIMD - against 166 now.
         int lane = lane_;
         asm volatile("" : "+v"(lane));
         const int fr = f0 + tr;
         const int64_t fg = fo + fr;
-        double* MAG = smem + ((tr & 1) ? G::OFF_P1 : G::OFF_P0);      // this frame's magnitudes (the next frame's previous ones)
-        double* MAGP = smem + ((tr & 1) ? G::OFF_P0 : G::OFF_P1);     // the previous frame's; from the enhancement on: free
+        const FrameCtx<LOG2N> fc{T, lane, tr, fr, fg, total_frames, df, lld, cand, octave_dbg};
+        double* MAG = L::this_frame(wave_lds(), tr);                  // this frame's magnitudes (the next frame's previous ones)
+        double* MAGP = L::prev_frame(wave_lds(), tr);                 // the previous frame's; from the enhancement on: free
+        // ---- phase 1: window + FFT + magnitudes ----
         double s_w2, s_hw2, s_zc;
         double hm[2 * PPL];
 #pragma unroll
@@ -532,7 +650,7 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
         fft_mag<LOG2N>(Z, T, W, lane, MAG);
         if (stop == 1) continue;                         // profiling aid (env RSAF_SMILE_STOP): leave the frame after phase k
 
-        // ---- cSpectral partial sums over the lane's bins (power spectrum; Androids.conf:258-280) ----
+        // ---- phase 2: cSpectral partial sums over the lane's bins (power spectrum; Androids.conf:258-280) ----
         double v[8], w[8];
         {
             double tot = 0, pf = 0, sm = 0, b1 = 0, b2 = 0, sh = 0, fx = 0, sl = 0, pl = 0, hrm = 0;
@@ -553,14 +671,16 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
                 if (P > 0.0) pl += P * lp;                       // P ln P (P < 1e-30 contributes < 1e-28: below every tolerance)
                 if (k >= 1 && k < NC) hrm += fmax(m - 0.5 * (MAG[k - 1] + MAG[k + 1]), 0.0);
             }
-            v[0] = s_w2; v[1] = s_hw2; v[2] = s_zc; v[3] = tot; v[4] = pf; v[5] = sm; v[6] = b1; v[7] = b2;
-            w[0] = sh; w[1] = fx; w[2] = sl; w[3] = pl; w[4] = hrm; w[5] = 0; w[6] = 0; w[7] = 0;
+            v[SUM_W2 & 7] = s_w2; v[SUM_HAM_W2 & 7] = s_hw2; v[SUM_ZC & 7] = s_zc; v[SUM_TOTAL & 7] = tot;
+            v[SUM_P_F & 7] = pf; v[SUM_MAG & 7] = sm; v[SUM_BAND1 & 7] = b1; v[SUM_BAND2 & 7] = b2;
+            w[SUM_SHARP & 7] = sh; w[SUM_FLUX & 7] = fx; w[SUM_LN_P & 7] = sl; w[SUM_P_LN_P & 7] = pl; w[SUM_HARM & 7] = hrm;
+            w[SUM_B_PAD5 & 7] = 0; w[SUM_B_PAD6 & 7] = 0; w[SUM_B_PAD7 & 7] = 0;
         }
         const double r1 = reduce8(v, RED, lane);
         const double r2 = reduce8(w, RED, lane);
-        double* st = STASH + tr * NSUM;
-        if ((lane & 7) == 0) { st[lane >> 3] = r1; st[8 + (lane >> 3)] = r2; }
-        const double tot = shfl_f64(r1, 24), pfs = shfl_f64(r1, 32);
+        double* st = L::stash(wave_lds(), tr);
+        if ((lane & 7) == 0) { st[SUM_GROUP_A + (lane >> 3)] = r1; st[SUM_GROUP_B + (lane >> 3)] = r2; }
+        const double tot = shfl_f64(r1, 8 * (SUM_TOTAL & 7)), pfs = shfl_f64(r1, 8 * (SUM_P_F & 7));   // every lane of group q holds total q
         const double safe = tot > 0.0 ? tot : 1.0;
         const double cen = pfs / safe;
         {   // central moments about the centroid
@@ -572,13 +692,15 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
                 const double mk = MAG[k], P = mk * mk, d = (double)k * df - cen, d2 = d * d;
                 m2 += d2 * P; m3 += d2 * d * P; m4 += d2 * d2 * P;
             }
-            v[0] = m2; v[1] = m3; v[2] = m4; v[3] = 0; v[4] = 0; v[5] = 0; v[6] = 0; v[7] = 0;
+            v[SUM_M2 & 7] = m2; v[SUM_M3 & 7] = m3; v[SUM_M4 & 7] = m4;
+#pragma unroll
+            for (int q = SUM_ROLLOFF - SUM_GROUP_C; q < 8; ++q) v[q] = 0;          // the group is eight wide
         }
         const double r3 = reduce8(v, RED, lane);
-        if ((lane & 7) == 0 && lane < 24) st[16 + (lane >> 3)] = r3;
+        if ((lane & 7) == 0 && lane < 8 * (SUM_ROLLOFF - SUM_GROUP_C)) st[SUM_GROUP_C + (lane >> 3)] = r3;
         if (stop == 2) continue;
 
-        // ---- roll-off points: first bin whose inclusive cumulative power reaches p * total (lane-blocked prefix sums) ----
+        // ---- phase 3: roll-off points: first bin whose inclusive cumulative power reaches p * total (lane-blocked prefix sums) ----
         {
             double c[PPL];
             double run = 0.0;
@@ -597,12 +719,12 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
                 for (int j = PPL - 1; j >= 0; --j) if (excl + c[j] >= th) first = PPL * lane + j;
                 first = wave_min_int(first);
                 if (first == 0x7fffffff) first = NC;               // only the last bin is left
-                if (lane == 0) st[19 + q] = (double)first * df;
+                if (lane == 0) st[SUM_ROLLOFF + q] = (double)first * df;
             }
         }
 
         if (stop == 3) continue;
-        // ---- cMelspec + cMfcc (Androids.conf:101-115): lane 2 c + side = one side of triangular band c ----
+        // ---- phase 4: cMelspec + cMfcc (Androids.conf:101-115): lane 2 c + side = one side of triangular band c ----
         {
             double s = 0.0;
             {
@@ -623,16 +745,16 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
                 double acc = 0.0;
 #pragma unroll
                 for (int jj = 0; jj < NMEL; ++jj) acc += T->dct[jj * 16 + lane] * SS[jj];
-                lld[(int64_t)(1 + lane) * total_frames + fg] = acc;
+                lld[(int64_t)(LLD_MFCC1 + lane) * total_frames + fg] = acc;
             }
             lds_fence();
         }
 
         if (stop == 4) continue;
-        // ---- cSpecScale (Androids.conf:142-160): peak enhancement + (1,2,1) smoothing on the linear spectrum ----
+        // ---- phase 5: cSpecScale (Androids.conf:142-160): peak enhancement + (1,2,1) smoothing on the linear spectrum ----
         // (MAG stays as it is: it is the next frame's MAGP)
-        double* A1 = ZD;                                   // enhanced spectrum   (FFT buffer, first half)
-        double* MM = ZD;                                   // spline moments      (the same half, once the smoothing has consumed A1)
+        double* A1 = L::enhanced(wave_lds());                         // enhanced spectrum   (FFT buffer, first half)
+        double* MM = L::moments(wave_lds());                          // spline moments      (the same half, once the smoothing has consumed A1)
         {
             // local maxima (a[i] > a[i-1] and a[i] >= a[i+1]; the ends count when larger than their one neighbour) as bit
             // masks of 64 bins; "within 2 bins of a maximum" is then shift arithmetic on the scalar unit
@@ -683,7 +805,7 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
         }
         if (stop == 5) continue;
         double* A2 = MAGP;
-        {   // natural cubic spline through the bins: tridiag(1, 4, 1) m = second differences, m_0 = m_NC = 0.
+        {   // phase 6: natural cubic spline through the bins: tridiag(1, 4, 1) m = second differences, m_0 = m_NC = 0.
             // Lane-blocked Thomas algorithm: the forward and the backward recurrence are affine maps x -> A x + B per bin;
             // a lane composes its PPL bins, a wave scan composes the lanes, the carry then re-runs the lane's bins.
             double g[PPL], r[PPL], dp[PPL];
@@ -723,22 +845,9 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
             lds_fence();
         }
         if (stop == 6) continue;
-        // spline at the octave-scale targets, negatives reset, auditory weighting -> S
-#pragma unroll 1
-        for (int j = 0; j <= PPL; ++j) {
-            const int i = lane + 64 * j;
-            if (i > NC) break;
-            const int kl = T->klo[i];
-            const double b = T->tb[i], aa = 1.0 - b;
-            const double y = aa * A2[kl] + b * A2[kl + 1] + (aa * aa * aa - aa) * MM[kl] + (b * b * b - b) * MM[kl + 1];
-            const double s = fmax(y, 0.0) * T->audw[i];
-            SS[i] = s;
-            if (octave_dbg) octave_dbg[fg * NB + i] = s;
-        }
-        lds_fence();
-
+        phase_octave_axis(fc);
         if (stop == 7) continue;
-        // ---- cPitchShs (Androids.conf:162-186): sub-harmonic summation, peaks, the 6 best candidates ----
+        // ---- phase 8: cPitchShs (Androids.conf:162-186): sub-harmonic summation (phases 9, 10: peaks, the 6 best candidates) ----
         double* HH = MAGP;                                  // A2 is dead (spline and evaluation are done): the summation spectrum
         double hsum = 0.0;
 #pragma unroll 1
@@ -755,103 +864,45 @@ __global__ __launch_bounds__(64, LOG2N <= 9 ? 3 : 2) void smile_lld_kernel(const
         const double hmean = wave_sum_all(hsum) / (double)NB;
         lds_fence();
         if (stop == 8) continue;
-        // peaks (y2 > y1 and y2 >= y3) with parabolic refinement, inside 52..620 Hz, positive score: compacted into a list
-        double* L_sc = SS;                                  // S is dead: list of (score, f0); at most NC / 2 peaks, the pad stays zero
-        double* L_f = SS + NC / 2;
-        int npk = 0;
-#pragma unroll 1
-        for (int j = 0; j <= PPL; ++j) {
-            const int i = lane + 64 * j;
-            bool ok = false;
-            double sc = 0.0, fq = 0.0;
-            if (i >= 1 && i <= NC - 1) {
-                const double y1 = HH[i - 1], y2 = HH[i], y3 = HH[i + 1];
-                if (y2 > y1 && y2 >= y3) {
-                    const double den = (y1 - 2.0 * y2) + y3;
-                    const double dx = 0.5 * (y1 - y3) / den;
-                    sc = y2 - 0.125 * (y1 - y3) * (y1 - y3) / den;
-                    fq = exp2(T->fmin_l2 + ((double)i + dx) * T->dl2);
-                    ok = fq >= SHS_MINPITCH && fq <= SHS_MAXPITCH && sc > 0.0;
-                }
-            }
-            const unsigned long long m = __ballot(ok);
-            if (ok) {
-                const int p = npk + __popcll(m & ((1ull << lane) - 1ull));
-                L_sc[p] = sc;
-                L_f[p] = fq;
-            }
-            npk += __popcll(m);
-        }
-        lds_fence();
+        const int npk = phase_peak_list(fc);
         if (stop == 9) continue;
-        // rank = number of peaks with a higher score (ties: the lower index, i.e. the earlier list entry, first)
-        double* cd = cand + fg * (NCAND * 2);
-        if (lane < NCAND && lane >= npk) { cd[2 * lane] = 0.0; cd[2 * lane + 1] = 0.0; }
-        for (int p0 = 0; p0 < npk; p0 += 64) {
-            const int p = p0 + lane;
-            const double mine = p < npk ? L_sc[p] : 0.0;
-            int rank = 0;
-            for (int q = 0; q < npk; ++q) {
-                const double o = L_sc[q];
-                rank += (o > mine || (o == mine && q < p)) ? 1 : 0;
-            }
-            if (p < npk && rank < NCAND) {
-                cd[2 * rank] = L_f[p];
-                cd[2 * rank + 1] = fmax(0.0, 1.0 - hmean / mine);
-            }
-        }
-        lds_fence();
+        phase_rank(fc, npk, hmean);
     }
 
-    // ---- end of the run: lane t finishes frame f0 + t from its sums ----
-    if (lane < n_run) {
-        const double* st = STASH + lane * NSUM;
-        const int64_t fg = fo + f0 + lane;
-        const double N = (double)frame, NBd = (double)NB;
-        auto out = [&](int row, double val) { lld[(int64_t)row * total_frames + fg] = val; };
-        const double tot = st[3], safe = tot > 0.0 ? tot : 1.0;
-        out(0, sqrt(st[0] / N));                                             // pcm_RMSenergy (cEnergy on winframe)
-        out(13, st[2] / N);                                                  // pcm_zcr (cMZcr on the raw frame)
-        const double inten = (st[1] / T->ham_sum) / I0;
-        out(16, inten);                                                      // pcm_intensity
-        out(17, pow(inten, 0.3));                                            // pcm_loudness
-        out(22, st[6]);
-        out(23, st[7]);
-        out(24, st[19]); out(25, st[20]); out(26, st[21]); out(27, st[22]);  // roll-off 25 / 50 / 75 / 90 %
-        out(28, sqrt(st[9] / NBd));                                          // flux (0 for the first frame of a clip)
-        out(29, st[4] / safe);                                               // centroid
-        out(30, tot > 0.0 ? log2(tot) - (st[11] / LN2) / tot : 0.0);         // entropy = -sum p log2 p, p = P / total
-        const double var = st[16] / safe, vs = var > 0.0 ? var : 1.0;
-        out(31, var);
-        out(32, (st[17] / safe) / (vs * sqrt(vs)));
-        out(33, (st[18] / safe) / (vs * vs));
-        out(34, (NBd * st[4] - T->slope_sf * tot) / T->slope_den);           // slope of the power spectrum over frequency
-        out(35, st[8] / safe);                                               // psychoacoustic sharpness
-        out(36, st[12] / (st[5] > 0.0 ? st[5] : 1.0));                       // harmonicity proxy
-        // flatness = geometric / arithmetic mean of the power spectrum; a frame of zeros has the limit value 1
-        out(37, tot > 0.0 ? exp(st[10] / NBd) / fmax(tot / NBd, 1e-30) : 1.0);
-    }
+    // end of the run: lane t finishes frame f0 + t from its sums
+    if (lane < n_run) finish_frame<LOG2N>(T, L::stash(wave_lds(), lane), frame, lld, total_frames, fo + f0 + lane);
 }
 
+// one launch: the batch as rsaf_smile_lld_batch received it, plus the geometry of its sample rate
+struct LldCall {
+    const float* wav;
+    const int64_t* clip_off;
+    const int64_t* frame_off;
+    int n_clips;
+    int64_t max_clip_frames, total_frames;
+    int fs, frame, hop;
+    double* lld;
+    double* cand;
+    double* octave_dbg;
+};
+
 template <int LOG2N>
-static int launch(const float* wav, const int64_t* clip_off, const int64_t* frame_off, int n_clips,
-                  int64_t max_clip_frames, int64_t total_frames, int fs, int frame, int hop, double* lld, double* cand,
-                  double* octave_dbg, hipStream_t s) {
+static int launch(const LldCall& c, hipStream_t s) {
     using G = Geo<LOG2N>;
     const Tables<LOG2N>* tab = nullptr;
-    int rc = get_tables<LOG2N>(fs, frame, hop, &tab);
+    int rc = get_tables<LOG2N>(c.fs, c.frame, c.hop, &tab);
     if (rc != RSAF_OK) return rc;
-    const int64_t runs = (max_clip_frames + RUNW - 1) / RUNW;
+    const int64_t runs = (c.max_clip_frames + RUNW - 1) / RUNW;
     RSAF_CHECK_ARG(runs <= 0x7fffffffLL, "clip too long");
-    constexpr size_t lds = (size_t)G::WAVE_D * sizeof(double);
+    constexpr size_t lds = G::bytes();
     static_assert(lds <= 64 * 1024, "one wave's buffers must fit the default dynamic LDS limit");
     static_assert(LOG2N < 11 || lds <= 40 * 1024, "the 2 048-point instance must leave room for four waves per CU");
     // algorithmic bytes: every sample read once (4 B) + the LLD rows written (38 * 8 B per frame)
     ProfScope prof("smile_lld", s, 0.0, 0.0);
-    dim3 grid((unsigned)runs, (unsigned)n_clips);
+    dim3 grid((unsigned)runs, (unsigned)c.n_clips);
     static const int stop = [] { const char* e = getenv("RSAF_SMILE_STOP"); return e ? atoi(e) : 0; }();
-    hipLaunchKernelGGL(smile_lld_kernel<LOG2N>, grid, dim3(64), lds, s, wav, clip_off, frame_off, total_frames, lld, cand,
-                       octave_dbg, tab, stop);
+    hipLaunchKernelGGL(smile_lld_kernel<LOG2N>, grid, dim3(64), lds, s, c.wav, c.clip_off, c.frame_off, c.total_frames, c.lld,
+                       c.cand, c.octave_dbg, tab, stop);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
@@ -896,11 +947,13 @@ int rsaf_smile_lld_batch(const float* wav, const int64_t* clip_off, const int64_
     if (n_clips == 0 || total_frames == 0 || max_clip_frames == 0) return RSAF_OK;
     RSAF_CHECK_ARG(wav && clip_off && frame_off && lld && cand, "NULL pointer");
     hipStream_t s = (hipStream_t)stream;
+    const LldCall call{wav, clip_off, frame_off, n_clips, max_clip_frames, total_frames, sample_rate, frame, hop,
+                       lld, cand, octave_spectrum};
     switch (l2) {
-        case 8: return launch<8>(wav, clip_off, frame_off, n_clips, max_clip_frames, total_frames, sample_rate, frame, hop, lld, cand, octave_spectrum, s);
-        case 9: return launch<9>(wav, clip_off, frame_off, n_clips, max_clip_frames, total_frames, sample_rate, frame, hop, lld, cand, octave_spectrum, s);
-        case 10: return launch<10>(wav, clip_off, frame_off, n_clips, max_clip_frames, total_frames, sample_rate, frame, hop, lld, cand, octave_spectrum, s);
-        default: return launch<11>(wav, clip_off, frame_off, n_clips, max_clip_frames, total_frames, sample_rate, frame, hop, lld, cand, octave_spectrum, s);
+        case 8: return launch<8>(call, s);
+        case 9: return launch<9>(call, s);
+        case 10: return launch<10>(call, s);
+        default: return launch<11>(call, s);
     }
 }
 

@@ -21,6 +21,7 @@
 #include <cmath>
 
 #include "rsaf_common.h"
+#include "smile_layout.h"
 
 namespace rsaf {
 namespace smile {
@@ -161,9 +162,9 @@ __global__ __launch_bounds__(64) void smile_viterbi_kernel(const double* __restr
     __threadfence();
     __builtin_amdgcn_wave_barrier();
     // fixed-lag decisions, one lane per frame, then the energy gate (cValbasedSelector on pcm_RMSenergy)
-    const double* rms = lld + fo;
-    double* f0row = lld + (int64_t)14 * total_frames + fo;
-    double* vrow = lld + (int64_t)15 * total_frames + fo;
+    const double* rms = lld + (int64_t)LLD_RMS_ENERGY * total_frames + fo;
+    double* f0row = lld + (int64_t)LLD_F0_FINAL * total_frames + fo;
+    double* vrow = lld + (int64_t)LLD_VOICING * total_frames + fo;
     for (int t = lane; t < T; t += 64) {
         const int e = min(t + BUFLEN - 1, T - 1);
         int s = bk[(int64_t)e * 8 + 7];
@@ -218,11 +219,11 @@ __global__ __launch_bounds__(64) void smile_jitter_kernel(const float* __restric
     const int T = (int)(frame_off[clip + 1] - fo);
     if (T <= 0) return;
     const float* src = wav + s0;
-    const double* f0row = lld + (int64_t)14 * total_frames + fo;
-    double* o_jl = lld + (int64_t)18 * total_frames + fo;
-    double* o_jd = lld + (int64_t)19 * total_frames + fo;
-    double* o_sh = lld + (int64_t)20 * total_frames + fo;
-    double* o_hn = lld + (int64_t)21 * total_frames + fo;
+    const double* f0row = lld + (int64_t)LLD_F0_FINAL * total_frames + fo;
+    double* o_jl = lld + (int64_t)LLD_JITTER_LOCAL * total_frames + fo;
+    double* o_jd = lld + (int64_t)LLD_JITTER_DDP * total_frames + fo;
+    double* o_sh = lld + (int64_t)LLD_SHIMMER_LOCAL * total_frames + fo;
+    double* o_hn = lld + (int64_t)LLD_LOG_HNR * total_frames + fo;
 
     int run_id = 0;
     bool carry = false;                                    // frame base-1 voiced

@@ -12,8 +12,16 @@ from oracle import smile_oracle as so
 # decision (peak enhancement, candidate ranking, Viterbi path, jitter lags, roll-off bins, maxPos / minPos) must coincide.
 TOL = 1e-4
 TIGHT = 1e-9                   # what float64-vs-float64 actually delivers (different FFT / summation orders)
-ROLLOFF_ROWS = (24, 25, 26, 27)
-PITCH_ROWS = (14, 15, 18, 19, 20, 21)
+
+
+def _row(name):
+    return so.LLD_NAMES.index(name)
+
+
+ROLLOFF_ROWS = tuple(_row(f"pcm_fftMag_spectralRollOff{p}.0") for p in (25, 50, 75, 90))
+F0, VOICING, JITTER_LOCAL, LOG_HNR = _row("F0final"), _row("voicingFinalUnclipped"), _row("jitterLocal"), _row("logHNR")
+JITTER_ROWS = (JITTER_LOCAL, _row("jitterDDP"), _row("shimmerLocal"), LOG_HNR)
+PITCH_ROWS = (F0, VOICING) + JITTER_ROWS
 
 
 def _clips(seconds_list, first=0):
@@ -64,7 +72,7 @@ def _check_rows(gpu, ref, P):
     """All 38 rows, end to end against the float64 oracle: values at TIGHT (<< north_star's 1e-4), roll-off bins and the
     voiced / unvoiced pattern exact."""
     assert not np.isnan(gpu).any()
-    assert np.array_equal(gpu[14] > 0, ref[14] > 0)                    # the Viterbi path's voicing decisions
+    assert np.array_equal(gpu[F0] > 0, ref[F0] > 0)                    # the Viterbi path's voicing decisions
     for i in range(so.NLLD):
         scale = np.max(np.abs(ref[i])) + 1e-30
         err = np.abs(gpu[i] - ref[i])
@@ -95,12 +103,12 @@ def _check_pitch_chain(clips, p, g, octv, cand, P, min_voiced=0.05):
         c3 = np.concatenate([got_c, (got_c[:, :, :1] > 0).astype(np.float64)], axis=2)
         F, V = so.viterbi_smooth(c3)                                                     # (c) Viterbi + energy gate
         F, V = so.energy_gate(F, V, g[0, sl])
-        assert np.array_equal(g[14, sl], F) and np.array_equal(g[15, sl], V)             # same path, same candidates: bit-equal
-        J = so.jitter_shimmer(c, g[14, sl], P)                                           # (d) cPitchJitter
-        for r, row in enumerate((18, 19, 20, 21)):
+        assert np.array_equal(g[F0, sl], F) and np.array_equal(g[VOICING, sl], V)             # same path, same candidates: bit-equal
+        J = so.jitter_shimmer(c, g[F0, sl], P)                                           # (d) cPitchJitter
+        for r, row in enumerate(JITTER_ROWS):
             sc = np.abs(J[r]).max() + 1e-30
             assert np.abs(g[row, sl] - J[r]).max() / sc <= TIGHT, so.LLD_NAMES[row]
-        voiced_total += int((g[14, sl] > 0).sum())
+        voiced_total += int((g[F0, sl] > 0).sum())
         off += nf
     assert voiced_total >= min_voiced * sum(p.frames)               # the chain was actually exercised
 
@@ -124,7 +132,7 @@ def test_lld_parity_30s_clip(rsaf_lib):
     ref = np.concatenate([so.lld(c) for c in clips], axis=1)
     _check_pitch_chain(clips, p, g, octv, cand, P)
     _check_rows(g, ref, P)                                             # all 38 rows end to end, 30 s voiced clip included
-    assert (ref[14, 2998:] > 0).mean() > 0.3
+    assert (ref[F0, 2998:] > 0).mean() > 0.3
 
 
 @pytest.mark.parametrize("fs", [8000, 22050, 44100, 48000])
@@ -141,6 +149,29 @@ def test_native_sample_rates(rsaf_lib, fs):
     _check_rows(g, ref, P)
 
 
+def _run_boundary_cases():
+    """(fs, samples): clips whose LAST run of 16 frames is full (16 frames), or holds ONE frame whose flux needs the frame
+    in front of the run (17 frames; 33: the same at the third run); at 8 and 48 kHz the 256- and 2 048-point instances
+    take the one-frame path."""
+    cases = [(16000, 2800), (16000, 2960), (16000, 5520)]
+    for fs in (8000, 48000):
+        P = so.Params(fs)
+        cases.append((fs, P.frame + 16 * P.hop))
+    return cases
+
+
+@pytest.mark.parametrize("fs,n", _run_boundary_cases())
+def test_run_boundaries(rsaf_lib, fs, n):
+    P = so.Params(fs)
+    clip = voiced_clip(30 + fs % 11, 1.0, fs=fs)[:n]
+    assert len(clip) == n
+    p, g, _, _ = _run_gpu([clip], fs=fs)
+    assert p.frames == [P.n_frames(n)] and p.frames[0] in (16, 17, 33)
+    ref = so.lld(clip, P)
+    assert g.shape == ref.shape
+    _check_rows(g, ref, P)
+
+
 def test_known_answers_through_the_kernels(rsaf_lib):
     """Harmonic tone -> F0final at the tone (within the shift quantisation of the summation), voiced, jitter ~ 0;
     silence and white noise -> unvoiced, zeros."""
@@ -151,11 +182,11 @@ def test_known_answers_through_the_kernels(rsaf_lib):
     noise = (0.05 * np.random.default_rng(0).standard_normal(fs)).astype(np.float32)
     p, g, _, _ = _run_gpu([tone, np.zeros(fs // 2, np.float32), noise])
     a, b, c = p.frames
-    F = g[14, :a]
+    F = g[F0, :a]
     assert (F > 0).mean() > 0.95 and 0.0 <= (np.median(F[F > 0]) - 250.0) / 250.0 < 0.025
-    assert np.median(g[15, :a]) > 0.7 and np.median(g[18, :a]) < 1e-3 and np.median(g[21, :a]) > 5.0
+    assert np.median(g[VOICING, :a]) > 0.7 and np.median(g[JITTER_LOCAL, :a]) < 1e-3 and np.median(g[LOG_HNR, :a]) > 5.0
     assert np.all(g[list(PITCH_ROWS), a:a + b] == 0.0)               # silence: gated by the energy selector
-    assert (g[14, a + b:] > 0).mean() < 0.05                          # noise: (almost) never voiced
+    assert (g[F0, a + b:] > 0).mean() < 0.05                          # noise: (almost) never voiced
 
 
 def test_empty_and_too_short_inputs(rsaf_lib):
