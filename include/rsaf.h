@@ -550,13 +550,34 @@ int rsaf_w2v2_forward_ragged(const float* wav, const int64_t* chunk_start, const
  *                             rel_attn_embed[bucket(d)][h] for |d| < RSAF_W2V2_REL_SPAN; the kernels clamp d to that range,
  *                             which is exact when max_bucket_distance < RSAF_W2V2_REL_SPAN (bucket() is constant beyond it).
  *                             The packer builds it with transformers' sequence of torch operations
- * The gates take rows x heads floats of workspace per call.                                                             */
+ * The gates take rows x heads floats of workspace per call.
+ *
+ * data2vec-audio is one more variant: Wav2Vec2's forward with another positional embedding.
+ *   RSAF_W2V2_POS_CONV_STACK   the positional embedding is a stack of D grouped convolutions instead of one weight-normed
+ *                              convolution: p_0 = x (the projected features of one window), and for i = 0..D-1
+ *                                  p_{i+1} = GELU( LN( conv1d_i(p_i) ) ),      h = encoder.layer_norm(x + p_D)
+ *                              conv1d_i: hidden -> hidden channels in pos_groups groups, pos_kernel taps (1..64, odd or even),
+ *                              zero padding pos_kernel / 2 on both sides of the WINDOW and, for an even kernel, the last
+ *                              output frame dropped: frame t reads frames t - K/2 .. t - K/2 + K - 1.  With bias, without
+ *                              weight norm.  LN: LayerNorm over the hidden channels of a frame WITHOUT weight or bias, eps
+ *                              1e-5 whatever layer_norm_eps is (nn.LayerNorm's default).  The depth D (1..15) travels in
+ *                              bits 12..15 of flags (D << RSAF_W2V2_POS_DEPTH_SHIFT).  RSAF_ERR_ARG before any launch: the
+ *                              flag without depth bits, depth bits without the flag, the flag without
+ *                              RSAF_W2V2_LAYER_FEAT_NORM, or with RSAF_W2V2_PRE_LN, RSAF_W2V2_REL_POS_BIAS or
+ *                              RSAF_W2V2_NO_FEAT_PROJ_LN
+ * Weight blob: layer 0's kernel ([hidden][tap * cg + ci], cg = hidden / pos_groups: the layout of the single convolution)
+ * and bias sit in the pos_conv_w / pos_conv_b slots; layers 1..D-1 are appended after every segment above, and
+ * rsaf_w2v2_weight_offsets_ex lists them last, {weight, bias} per layer.  The workspace grows by the fp16 planes and row
+ * scales of those D - 1 kernels; the stack's rows live in buffers the single convolution uses.                       */
 #define RSAF_W2V2_LAYER_FEAT_NORM 1
 #define RSAF_W2V2_CONV_BIAS 2
 #define RSAF_W2V2_PRE_LN 4
 #define RSAF_W2V2_NO_INPUT_NORM 8
 #define RSAF_W2V2_NO_FEAT_PROJ_LN 32 /* (bit 16 stays an unknown bit: RSAF_ERR_ARG, as callers of ABI 7 were promised) */
 #define RSAF_W2V2_REL_POS_BIAS 64
+#define RSAF_W2V2_POS_CONV_STACK 256 /* (bit 128 stays an unknown bit) */
+#define RSAF_W2V2_POS_DEPTH_SHIFT 12
+#define RSAF_W2V2_POS_DEPTH_MASK 0xF000
 #define RSAF_W2V2_REL_SPAN 1024
 int64_t rsaf_w2v2_weight_floats_ex(int conv_dim, int hidden, int layers, int heads, int intermediate, int pos_kernel,
                                    int pos_groups, int flags);

@@ -11,6 +11,7 @@
 // power-of-two scales, three MFMA products per term):
 //   conv1..6  : channels-last activations make a k-tap/stride-2 conv a GEMM with lda = 2*C, K = k*C
 //   pos-conv  : activations regrouped to [chunk][group][T+K-1 (zero padded)][C/G], one batched GEMM
+//               (data2vec-audio, RSAF_W2V2_POS_CONV_STACK: a stack of convolution + LayerNorm + GELU layers, posstack_* below)
 //   attention : S = QK^T/sqrt(d) and O = PV as (chunk, head)-batched GEMMs on the packed qkv buffer
 // conv0 (Cin = 1) + GroupNorm + GELU is recomputed in two passes (stats, apply) instead of
 // materialising the un-normalised 15 999 x 512 activation; LayerNorm / softmax are one wave per row.
@@ -27,13 +28,17 @@ namespace w2v2 {
 // flags: the forward variants of the _ex entry points (include/rsaf.h)
 constexpr int F_LAYER_FEAT_NORM = RSAF_W2V2_LAYER_FEAT_NORM, F_CONV_BIAS = RSAF_W2V2_CONV_BIAS, F_PRE_LN = RSAF_W2V2_PRE_LN,
               F_NO_INPUT_NORM = RSAF_W2V2_NO_INPUT_NORM, F_NO_FEAT_PROJ_LN = RSAF_W2V2_NO_FEAT_PROJ_LN,
-              F_REL_POS_BIAS = RSAF_W2V2_REL_POS_BIAS, F_ALL = 15 | F_NO_FEAT_PROJ_LN | F_REL_POS_BIAS;
+              F_REL_POS_BIAS = RSAF_W2V2_REL_POS_BIAS, F_POS_CONV_STACK = RSAF_W2V2_POS_CONV_STACK,
+              F_POS_DEPTH_MASK = RSAF_W2V2_POS_DEPTH_MASK,
+              F_ALL = 15 | F_NO_FEAT_PROJ_LN | F_REL_POS_BIAS | F_POS_CONV_STACK | F_POS_DEPTH_MASK;
 constexpr int REL_SPAN = RSAF_W2V2_REL_SPAN, REL_TAB = 2 * REL_SPAN - 1;    // the distance table of a head: |k - q| < REL_SPAN
 
 struct Cfg {
     int C, Hd, L, NH, I, PK, PG;
     float eps;
     int flags = 0;
+    // POS_CONV_STACK: convolutions of the positional stack (0: the single weight-normed convolution)
+    int pos_depth() const { return (flags & F_POS_CONV_STACK) ? (flags & F_POS_DEPTH_MASK) >> RSAF_W2V2_POS_DEPTH_SHIFT : 0; }
 };
 
 static inline int64_t pad4(int64_t n) { return (n + 3) & ~int64_t(3); }
@@ -51,6 +56,7 @@ struct Layout {
     // REL_POS_BIAS: per layer the gate's two summed weight rows ga / gb [hd], {ba, bb} and gru_rel_pos_const [NH]; the table
     std::vector<int64_t> ga, gb, gbias, gconst;
     int64_t reltab = -1;             // [NH][REL_TAB]
+    std::vector<int64_t> stackw, stackb;   // POS_CONV_STACK: kernel and bias of the stack's layers 1..D-1 (layer 0: posw / posb)
     int64_t total;
 };
 
@@ -83,6 +89,9 @@ static Layout make_layout(const Cfg& c) {
         }
         L.reltab = take((int64_t)c.NH * REL_TAB);
     }
+    for (int i = 1; i < c.pos_depth(); ++i) {
+        L.stackw.push_back(take((int64_t)c.Hd * c.PK * cg)); L.stackb.push_back(take(c.Hd));
+    }
     L.total = o;
     return L;
 }
@@ -94,9 +103,18 @@ static int check_cfg(const Cfg& c) {
     RSAF_CHECK_ARG(c.I >= 16 && c.I % 16 == 0, "intermediate_size must be a multiple of 16");
     RSAF_CHECK_ARG(c.L >= 1 && c.L <= 64, "num_hidden_layers out of range");
     RSAF_CHECK_ARG(c.NH >= 1 && c.Hd % c.NH == 0 && (c.Hd / c.NH) % 4 == 0, "head_dim must be a multiple of 4");
-    RSAF_CHECK_ARG(c.PG >= 1 && c.Hd % c.PG == 0 && (c.Hd / c.PG) % 4 == 0 && c.PK >= 2 && c.PK % 2 == 0,
-                   "positional conv: channels/group multiple of 4, even kernel");
     RSAF_CHECK_ARG((c.flags & ~F_ALL) == 0, "unknown RSAF_W2V2_* flag bits");
+    RSAF_CHECK_ARG(c.PG >= 1 && c.Hd % c.PG == 0 && (c.Hd / c.PG) % 4 == 0, "positional conv: channels/group multiple of 4");
+    if (c.flags & F_POS_CONV_STACK) {
+        RSAF_CHECK_ARG(c.flags & F_POS_DEPTH_MASK, "RSAF_W2V2_POS_CONV_STACK needs its depth in flags bits 12..15");
+        RSAF_CHECK_ARG(c.PK >= 1 && c.PK <= 64, "positional conv stack: kernel must lie in 1..64");
+        RSAF_CHECK_ARG(!(c.flags & (F_PRE_LN | F_REL_POS_BIAS | F_NO_FEAT_PROJ_LN)),
+                       "RSAF_W2V2_POS_CONV_STACK with PRE_LN, REL_POS_BIAS or NO_FEAT_PROJ_LN is not built");
+        RSAF_CHECK_ARG(c.flags & F_LAYER_FEAT_NORM, "RSAF_W2V2_POS_CONV_STACK needs RSAF_W2V2_LAYER_FEAT_NORM");
+    } else {
+        RSAF_CHECK_ARG(!(c.flags & F_POS_DEPTH_MASK), "depth bits without RSAF_W2V2_POS_CONV_STACK");
+        RSAF_CHECK_ARG(c.PK >= 2 && c.PK % 2 == 0, "positional conv: even kernel");
+    }
     RSAF_CHECK_ARG(!((c.flags & F_NO_FEAT_PROJ_LN) && (c.flags & F_LAYER_FEAT_NORM)),
                    "RSAF_W2V2_NO_FEAT_PROJ_LN with RSAF_W2V2_LAYER_FEAT_NORM is not built");
     return RSAF_OK;
@@ -125,6 +143,7 @@ struct Workspace {
     int64_t conv_scale, conv_amax, pos_scale, fp_amax, wlen, win_norm, s_lnfp, s_x, s_ffn, s_att, s_qkv;
     int64_t cb_max;                                      // CONV_BIAS: max |bias| of conv1..5 (appended after the tables)
     int64_t gate;                                        // REL_POS_BIAS: the bias gates [rows][NH] of the current layer (appended)
+    std::vector<int64_t> wp_stack, ws_stack;             // POS_CONV_STACK on the matrix pipe: planes and row scales of layers 1..D-1 (appended)
     int64_t t_Tw, t_row0, t_ztab, t_rowwin;              // window tables (int32 / int64 views of the float workspace)
     int64_t t_coff, t_crow;                              // packed conv row spaces of the current group (see packed_in_rows)
 };
@@ -135,6 +154,8 @@ constexpr int CONV_GROUP = 512;      // windows per pass of the feature encoder 
 static inline int conv_group(int n) { return n < CONV_GROUP ? n : CONV_GROUP; }                  // window slots of a feature-encoder pass
 static inline bool fused_attention(const Cfg& c, int Tt) { return c.Hd / c.NH == 64 && Tt <= 256; }   // else three launches and the score buffer
 static inline bool posconv_on_f16x3(const Cfg& c) { return (c.Hd / c.PG) % 16 == 0; }             // else the exact-fp32 GEMM
+// the positional stack's MFMA kernel holds a group's channels of a row tile in LDS: group widths of 16, 32, 48 and 64
+static inline bool posstack_on_mfma(const Cfg& c) { return c.pos_depth() > 0 && (c.Hd / c.PG) % 16 == 0 && c.Hd / c.PG <= 64; }
 
 static inline int64_t planes_floats(int64_t n) { return pad4(n); }
 
@@ -245,6 +266,10 @@ static Workspace make_ws(const Cfg& c, const Rag& R) {
     w.t_coff = take((int64_t)7 * (G + 1)); w.t_crow = take(2 * packed_tab_base(G, T, 7));
     w.cb_max = (c.flags & F_CONV_BIAS) ? take(8) : -1;
     w.gate = (c.flags & F_REL_POS_BIAS) ? take(rows * c.NH) : -1;
+    if (posstack_on_mfma(c))
+        for (int i = 1; i < c.pos_depth(); ++i) {
+            w.wp_stack.push_back(take(planes_floats((int64_t)c.Hd * c.PK * (c.Hd / c.PG)))); w.ws_stack.push_back(take(c.Hd));
+        }
     w.total = o;
     return w;
 }
@@ -1350,6 +1375,190 @@ __global__ __launch_bounds__(512, 1) void posconv_f16x3_kernel(const unsigned sh
     }
 }
 
+// ---- positional convolution STACK (RSAF_W2V2_POS_CONV_STACK: data2vec-audio) ---------------------------------------------------
+// D layers of p <- GELU(LN(conv(p))): grouped convolution of PK taps with bias, LayerNorm over all Hd channels of a frame
+// without weight or bias (eps 1e-5), GELU.  The LayerNorm couples the groups of a frame, so a layer is two launches:
+//   posstack_conv_kernel  one workgroup = PS_ROWS frames of one (window, group): the pre-LN values (+ bias) as fp32 rows
+//   posstack_rows_kernel  one wave per frame: LayerNorm + GELU over the Hd channels, out as the fp16 plane pair the next
+//                         layer's convolution multiplies (or, after the last layer, as fp32 rows for encoder.layer_norm)
+// The planes are plain packed rows [rows][Hd]; the convolution zero-fills the frames outside [0, T_w) of ITS window while it
+// copies its row tile (+ PK - 1 halo rows) into LDS, so no halo ever reads a neighbouring window's rows and a ragged call
+// computes what the per-window calls compute.  From layer 1 on |p| <= sqrt(Hd - 1) (GELU of a normalised row), so the A
+// planes' power-of-two scale is a constant of the geometry; layer 0 reads x under the window's scale (W.fp_amax).
+// The convolution is the f16x3 arithmetic of posconv_f16x3_kernel (a_l b_h + a_h b_l + a_h b_h on v_mfma_f32_16x16x32_f16, fp32
+// accumulation), with the same LDS image layout ([plane][cg / 16 panels][rows][16], 16-byte halves swizzled by (row >> 3) & 1)
+// and the same weight panels; PK cg / 16 may be odd (19 x 3 = 57 units of 16 k): the last MFMA's upper half multiplies zeros.
+// Four waves x 64 rows; a wave reads its weight fragments from global memory (panel layout: 512 contiguous bytes per 16 lanes),
+// one step ahead of the MFMAs that consume them.
+constexpr int PS_ROWS = 256;                     // output frames per workgroup (4 waves x 4 row tiles of 16)
+static int posstack_rows_alloc(int PK) { return PS_ROWS + PK - 1; }
+static size_t posstack_lds_bytes(int cg, int PK) { return (size_t)2 * cg * posstack_rows_alloc(PK) * sizeof(unsigned short); }
+
+template <int NT>
+__global__ __launch_bounds__(256) void posstack_conv_kernel(const unsigned short* __restrict__ ap, int64_t a_plane,
+                                                            const unsigned short* __restrict__ wp, int64_t b_plane, int Hd,
+                                                            const float* __restrict__ a_scale, float a_scale_const,
+                                                            const float* __restrict__ b_scale, const float* __restrict__ bias,
+                                                            const int* __restrict__ Tw, const int64_t* __restrict__ row0,
+                                                            float* __restrict__ pre, int PK, int tiles, int rows_alloc) {
+    extern __shared__ __attribute__((aligned(16))) unsigned short ps_sm[];
+    constexpr int cg = 16 * NT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int w = blockIdx.x / tiles, tile = blockIdx.x - w * tiles, g = blockIdx.y;
+    const int Tv = Tw[w], t0 = tile * PS_ROWS;
+    if (t0 >= Tv) return;                                                  // the whole workgroup: a window shorter than the longest
+    const int64_t r0 = row0[w];
+    const int a_panel = rows_alloc * 16;                                   // elements per (plane, panel)
+    // the tile's image: LDS row lr = frame t0 - PK / 2 + lr of THIS window, zeros outside [0, T_w)
+    {
+        constexpr int chunks = 2 * NT;                                     // 16-byte pieces of a row's cg channels
+        const int total = 2 * rows_alloc * chunks;
+        for (int i = tid; i < total; i += 256) {
+            const int ch = i % chunks, r = i / chunks;
+            const int pl = r / rows_alloc, lr = r - pl * rows_alloc;
+            const int t = t0 - PK / 2 + lr;
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (t >= 0 && t < Tv) v = *reinterpret_cast<const uint4*>(ap + pl * a_plane + (r0 + t) * Hd + g * cg + ch * 8);
+            *reinterpret_cast<uint4*>(ps_sm + (pl * NT + (ch >> 1)) * a_panel + lr * 16 + (((ch & 1) ^ ((lr >> 3) & 1)) << 3)) = v;
+        }
+    }
+    __syncthreads();
+    const int nunits = PK * NT, nsteps = (nunits + 1) / 2;                 // a unit = 16 k of one tap; a step = one MFMA depth of 32
+    const int r16 = lane & 15, q = lane >> 4, hlf = q & 1, upair = q >> 1;
+    const int m_base = wave * 64;
+    pc_f32x4 acc[4][NT];
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = pc_f32x4{0.f, 0.f, 0.f, 0.f};
+    struct BFrag { pc_f16x8 h[NT], l[NT]; };
+    const pc_f16x8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
+    // this lane's unit of step j (the upper half of an odd count's last step has none: its weights read as zeros)
+    auto fetch_b = [&](int j, BFrag& B) {
+        const int unit = 2 * j + upair;
+        const bool ok = unit < nunits;
+        const unsigned short* src = wp + ((int64_t)(ok ? unit : 0) * Hd + g * cg + r16) * 16 + hlf * 8;
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+            B.h[nt] = ok ? *reinterpret_cast<const pc_f16x8*>(src + nt * 256) : zero8;
+            B.l[nt] = ok ? *reinterpret_cast<const pc_f16x8*>(src + b_plane + nt * 256) : zero8;
+        }
+    };
+    auto mfmas = [&](int j, const BFrag& B) {
+        const int unit = 2 * j + upair;
+        const int u = unit < nunits ? unit : 0;
+        const int tap = u / NT, panel = u - tap * NT;
+        pc_f16x8 ah[4], al[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            const int row = m_base + 16 * mt + r16 + tap;
+            const int off = panel * a_panel + row * 16 + ((hlf ^ ((row >> 3) & 1)) << 3);
+            ah[mt] = *reinterpret_cast<const pc_f16x8*>(ps_sm + off);
+            al[mt] = *reinterpret_cast<const pc_f16x8*>(ps_sm + NT * a_panel + off);
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al[mt], B.h[nt], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], B.l[nt], acc[mt][nt], 0, 0, 0);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], B.h[nt], acc[mt][nt], 0, 0, 0);
+    };
+    BFrag B0, B1;
+    fetch_b(0, B0);
+    for (int j = 0; j < nsteps; j += 2) {
+        if (j + 1 < nsteps) fetch_b(j + 1, B1);
+        mfmas(j, B0);
+        if (j + 1 < nsteps) {
+            if (j + 2 < nsteps) fetch_b(j + 2, B0);
+            mfmas(j + 1, B1);
+        }
+    }
+    // epilogue: lane (q, r16), register v = row 4 q + v, column r16 of a 16 x 16 tile: the pre-LN value, scales undone, + bias
+    const float sa_inv = pow2_inverse(a_scale ? a_scale[w] : a_scale_const);
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) {
+        const int col = g * cg + 16 * nt + r16;
+        const float inv = sa_inv * pow2_inverse(b_scale[col]);
+        const float bs = bias[col];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int m = t0 + m_base + 16 * mt + 4 * q + v;
+                if (m < Tv) pre[(r0 + m) * Hd + col] = acc[mt][nt][v] * inv + bs;
+            }
+    }
+}
+
+// One wave per frame of D <= 1024 channels.  MODE 0: the row as it is (layer 0's input x) -> planes under its window's scale
+// (from the largest |x| of the window, which also goes to win_scale).  MODE 1: LayerNorm without weight or bias (eps 1e-5)
+// + GELU -> planes under the constant scale.  MODE 2: the same -> fp32 rows of `out` (which may be `src`: the wave holds the row).
+template <int MODE>
+__global__ __launch_bounds__(256) void posstack_rows_kernel(const float* src, int64_t rows, int D, const int* __restrict__ rowwin,
+                                                            const unsigned* __restrict__ amax, float* __restrict__ win_scale,
+                                                            float const_scale, unsigned short* __restrict__ planes, int64_t plane,
+                                                            float* out) {
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int D4 = D >> 2;
+    const float4* x4 = reinterpret_cast<const float4*>(src + row * D);
+    float4 v[4];
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = lane + 64 * i;
+        v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < D4) { v[i] = x4[idx]; s += (v[i].x + v[i].y) + (v[i].z + v[i].w); }
+    }
+    float sc = const_scale;
+    if constexpr (MODE == 0) {
+        const int w = rowwin[row];
+        sc = f16x2_scale_for_bound(__uint_as_float(amax[w]));
+        if (lane == 0) win_scale[w] = sc;                                  // every row of the window writes the same value
+    } else {
+        const float mean = wave_sum(s) / D;
+        float qq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int idx = lane + 64 * i;
+            if (idx < D4) {
+                const float a = v[i].x - mean, b = v[i].y - mean, c = v[i].z - mean, d = v[i].w - mean;
+                qq += (a * a + b * b) + (c * c + d * d);
+            }
+        }
+        const float rstd = 1.0f / sqrtf(wave_sum(qq) / D + 1e-5f);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const gelu_f32x2 e0 = gelu_pair(gelu_f32x2{(v[i].x - mean) * rstd, (v[i].y - mean) * rstd});
+            const gelu_f32x2 e1 = gelu_pair(gelu_f32x2{(v[i].z - mean) * rstd, (v[i].w - mean) * rstd});
+            v[i] = make_float4(e0.x, e0.y, e1.x, e1.y);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = lane + 64 * i;
+        if (idx >= D4) continue;
+        if constexpr (MODE == 2) {
+            reinterpret_cast<float4*>(out + row * D)[idx] = v[i];
+        } else {
+            const float yy[4] = {v[i].x * sc, v[i].y * sc, v[i].z * sc, v[i].w * sc};
+            unsigned short hh[4], ll[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) split2_w(yy[k], hh[k], ll[k]);
+            unsigned short* pp = planes + row * D + 4 * idx;
+            *reinterpret_cast<uint2*>(pp) = make_uint2(hh[0] | ((unsigned)hh[1] << 16), hh[2] | ((unsigned)hh[3] << 16));
+            *reinterpret_cast<uint2*>(pp + plane) = make_uint2(ll[0] | ((unsigned)ll[1] << 16), ll[2] | ((unsigned)ll[3] << 16));
+        }
+    }
+}
+
 // a step of a sequence that ends at the first error
 #define RSAF_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
@@ -1632,8 +1841,13 @@ struct Forward {
         for (int i = 0; i < 6; ++i)
             RSAF_TRY(split_wp(L.conv[i], C, KERN[i + 1] * C, W.wp_conv[i], W.ws_conv[i], wstat_conv(i)));
         RSAF_TRY(split_wp(L.fpw, Hd, C, W.wp_fp, W.ws_fp, WSTAT_FP));
-        if (posconv_on_f16x3(c)) {                           // [G cg][PK cg] as panels of Hd rows
+        if (c.pos_depth() ? posstack_on_mfma(c) : posconv_on_f16x3(c)) {   // [G cg][PK cg] as panels of Hd rows
             RSAF_TRY(split_wp(L.posw, Hd, c.PK * (Hd / c.PG), W.wp_pos, W.ws_pos, WSTAT_POS));
+        }
+        for (size_t i = 0; i < W.wp_stack.size(); ++i) {     // POS_CONV_STACK: the stack's layers 1..D-1 (no bound reads their statistics)
+            const int K = c.PK * (Hd / c.PG);
+            RSAF_TRY(launch_f16x2_row_scales(Wt + L.stackw[i], Hd, K, K, ws + W.ws_stack[i], nullptr, nullptr, s));
+            RSAF_TRY(launch_split_f16x2(Wt + L.stackw[i], Hd, K, K, ws + W.ws_stack[i], 1, planes_at(W.wp_stack[i]), (int64_t)Hd * K, 1, s));
         }
         for (int l = 0; l < c.L; ++l) {
             const LayerOff& lo = L.layers[l];
@@ -1796,6 +2010,76 @@ struct Forward {
         }
         if (pre_ln) return ln_to_qkv(x, ws + W.y, Wt + L.layers[0].ln1g, Wt + L.layers[0].ln1b, gate_rows(), 0, true, x);
         return ln_to_qkv(x, ws + W.y, Wt + L.elng, Wt + L.elnb, x, 0, true);
+    }
+    // 5 (POS_CONV_STACK). p_0 = x, p_{i+1} = GELU(LN(conv_i(p_i))), i = 0..D-1 (LN without weight or bias, eps 1e-5), then
+    //    x = LN(x + p_D) as above.  The pre-LN rows of every layer go through W.y, which ends up holding p_D; the planes
+    //    between the layers live in W.xg (rows x Hd elements per plane: no padding rows, the kernel pads per window)
+    int positional_conv_stack() {
+        const int D = c.pos_depth(), cg = Hd / c.PG;
+        {
+            ProfScope prof("w2v2_posconv_stack", s, 2.0 * (double)D * rows * cg * (double)c.PK * cg * c.PG, (double)D * rows * Hd * 16.0);
+            RSAF_TRY(posstack_on_mfma(c) ? posstack_mfma(D) : posstack_fp32(D));
+        }
+        return ln_to_qkv(x, ws + W.y, Wt + L.elng, Wt + L.elnb, x, 0, true);
+    }
+    template <int MODE>
+    int posstack_rows(const float* src, float* dst) {
+        hipLaunchKernelGGL(posstack_rows_kernel<MODE>, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, src, rows, Hd, rowwin,
+                           bits_at(W.fp_amax), ws + W.pos_scale, f16x2_scale_for_bound(sqrtf((float)Hd)), planes_at(W.xg), rows * Hd, dst);
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+    template <int NT>
+    int posstack_conv_launch(int i) {
+        const int cg = Hd / c.PG, tiles = (Tt + PS_ROWS - 1) / PS_ROWS;
+        const size_t lds = posstack_lds_bytes(cg, c.PK);
+        RSAF_CHECK_ARG((int64_t)n * tiles <= 0x7fffffffLL, "too many row tiles");
+        RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)posstack_conv_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((posstack_conv_kernel<NT>), dim3((unsigned)(n * tiles), (unsigned)c.PG), dim3(256), lds, s,
+                           reinterpret_cast<const unsigned short*>(planes_at(W.xg)), rows * Hd,
+                           reinterpret_cast<const unsigned short*>(planes_at(i ? W.wp_stack[i - 1] : W.wp_pos)), (int64_t)Hd * c.PK * cg, Hd,
+                           i ? nullptr : ws + W.pos_scale, f16x2_scale_for_bound(sqrtf((float)Hd)), ws + (i ? W.ws_stack[i - 1] : W.ws_pos),
+                           Wt + (i ? L.stackb[i - 1] : L.posb), Tw + (int64_t)6 * n, row0, ws + W.y, c.PK, tiles, posstack_rows_alloc(c.PK));
+        RSAF_CHECK_HIP(hipGetLastError());
+        return RSAF_OK;
+    }
+    int posstack_mfma(int D) {
+        RSAF_TRY(posstack_rows<0>(x, nullptr));
+        for (int i = 0; i < D; ++i) {
+            switch (Hd / c.PG / 16) {
+                case 1: RSAF_TRY(posstack_conv_launch<1>(i)); break;
+                case 2: RSAF_TRY(posstack_conv_launch<2>(i)); break;
+                case 3: RSAF_TRY(posstack_conv_launch<3>(i)); break;
+                default: RSAF_TRY(posstack_conv_launch<4>(i)); break;
+            }
+            RSAF_TRY(i + 1 < D ? posstack_rows<1>(ws + W.y, nullptr) : posstack_rows<2>(ws + W.y, ws + W.y));
+        }
+        return RSAF_OK;
+    }
+    // other group widths (test geometries): regroup + the exact-fp32 GEMM per run of equal windows, rows normalised in place
+    int posstack_fp32(int D) {
+        const int cg = Hd / c.PG;
+        for (int i = 0; i < D; ++i) {
+            for (const auto& tg : R.tgroups) {
+                const int nw = tg.second - tg.first, Tq = R.T6[tg.first], TTq = Tq + c.PK - 1;
+                const int64_t r0 = R.row0[tg.first];
+                const int64_t t4 = (int64_t)nw * TTq * (Hd / 4);
+                hipLaunchKernelGGL(regroup_kernel, dim3((unsigned)std::min<int64_t>((t4 + 255) / 256, 4096)), dim3(256), 0, s,
+                                   reinterpret_cast<const float4*>((i ? ws + W.y : x) + r0 * Hd), reinterpret_cast<float4*>(ws + W.xg),
+                                   nw, Tq, Hd / 4, c.PG, c.PK);
+                RSAF_CHECK_HIP(hipGetLastError());
+                GemmParams p = gemm_params_plain(ws + W.xg, Wt + (i ? L.stackw[i - 1] : L.posw), ws + W.y + r0 * Hd, Tq, cg, c.PK * cg, cg,
+                                                 (int64_t)c.PK * cg, Hd);
+                p.nz = nw * c.PG; p.nz2 = c.PG;
+                p.sA1 = (int64_t)c.PG * TTq * cg; p.sA2 = (int64_t)TTq * cg;
+                p.sB1 = 0; p.sB2 = (int64_t)cg * c.PK * cg;
+                p.sC1 = (int64_t)Tq * Hd; p.sC2 = cg;
+                p.bias = Wt + (i ? L.stackb[i - 1] : L.posb); p.sBias2 = cg; p.act = ACT_NONE;
+                RSAF_TRY(launch_gemm_f32(p, s, "w2v2_posstack_gemm_f32"));
+            }
+            RSAF_TRY(posstack_rows<2>(ws + W.y, ws + W.y));
+        }
+        return RSAF_OK;
     }
     // the regrouped sequence as k16 panels of T_w + PK - 1 rows per (window, group): tap k = one row down
     int posconv_regroup_planes() {
@@ -2054,7 +2338,7 @@ static int forward_impl(const float* wav, const int64_t* chunk_start, const int*
     RSAF_TRY(f.weight_planes());
     RSAF_TRY(f.feature_encoder());
     RSAF_TRY(f.feature_projection());
-    RSAF_TRY(f.positional_conv());
+    RSAF_TRY(c.pos_depth() ? f.positional_conv_stack() : f.positional_conv());
     for (int l = 0; l < c.L; ++l)
         RSAF_TRY(f.encoder_layer(l));
     return RSAF_OK;
@@ -2120,6 +2404,8 @@ int rsaf_w2v2_weight_offsets_ex(int conv_dim, int hidden, int layers, int heads,
             for (int64_t o : {L.ga[l], L.gb[l], L.gbias[l], L.gconst[l]}) v.push_back(o);
         v.push_back(L.reltab);
     }
+    // POS_CONV_STACK: {kernel, bias} of the stack's layers 1..D-1
+    for (size_t i = 0; i < L.stackw.size(); ++i) { v.push_back(L.stackw[i]); v.push_back(L.stackb[i]); }
     RSAF_CHECK_ARG(cap >= (int)v.size(), "offsets_host too small");
     for (size_t i = 0; i < v.size(); ++i) offsets_host[i] = v[i];
     *n_host = (int)v.size();

@@ -51,12 +51,12 @@ def layer_selection(output_layers, num_layers=None):
 
 def _cfg_args(cfg: W2V2Config):
     return (cfg.conv_dim[0], cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads,
-            cfg.intermediate_size, cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups)
+            cfg.intermediate_size, cfg.pos_kernel, cfg.num_conv_pos_embedding_groups)
 
 
 def weight_offsets(cfg: W2V2Config):
     lib = _lib.load()
-    cap = 32 + 21 + 16 * cfg.num_hidden_layers + 1
+    cap = 32 + 21 + 16 * cfg.num_hidden_layers + 1 + 2 * 15
     buf = (C.c_int64 * cap)()
     n = C.c_int(0)
     _lib.check(lib.rsaf_w2v2_weight_offsets_ex(*_cfg_args(cfg), cfg.flags, buf, cap, C.byref(n)), "rsaf_w2v2_weight_offsets_ex")
@@ -65,8 +65,8 @@ def weight_offsets(cfg: W2V2Config):
 
 def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
     """HF-keyed state_dict -> the float32 blob of ``rsaf_w2v2_forward_ragged_ex`` (weight norm folded,
-    conv kernels tap-major, q/k/v fused; conv biases, conv LayerNorms, WavLM's summed gate rows and its distance table
-    appended per ``cfg.flags``)."""
+    conv kernels tap-major, q/k/v fused; conv biases, conv LayerNorms, WavLM's summed gate rows and its distance table,
+    data2vec-audio's positional stack from its second layer on appended per ``cfg.flags``)."""
     cfg.validate()
     offs, total = weight_offsets(cfg)
     blob = np.zeros(total, dtype=np.float32)
@@ -91,11 +91,15 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
     else:                                                    # NO_FEAT_PROJ_LN: the two slots stay, unused
         put(np.zeros(cfg.conv_dim[-1])); put(np.zeros(cfg.conv_dim[-1]))
     put(g("feature_projection.projection.weight")); put(g("feature_projection.projection.bias"))
-    wg = g("encoder.pos_conv_embed.conv.parametrizations.weight.original0")      # [1,1,K]
-    wv = g("encoder.pos_conv_embed.conv.parametrizations.weight.original1")      # [H, H/G, K]
-    w = wg * wv / np.sqrt((wv * wv).sum(axis=(0, 1), keepdims=True))             # weight_norm(dim=2)
+    stack = cfg.model_type == "data2vec-audio"               # layer 0 of its positional stack takes the single conv's slots
+    if stack:
+        w = g("encoder.pos_conv_embed.layers.0.conv.weight")                     # [H, H/G, K], no weight norm
+    else:
+        wg = g("encoder.pos_conv_embed.conv.parametrizations.weight.original0")  # [1,1,K]
+        wv = g("encoder.pos_conv_embed.conv.parametrizations.weight.original1")  # [H, H/G, K]
+        w = wg * wv / np.sqrt((wv * wv).sum(axis=(0, 1), keepdims=True))         # weight_norm(dim=2)
     put(np.ascontiguousarray(w.transpose(0, 2, 1)).reshape(w.shape[0], -1))      # [H][tap*cg + ci] = [G][cg][...]
-    put(g("encoder.pos_conv_embed.conv.bias"))
+    put(g("encoder.pos_conv_embed.layers.0.conv.bias" if stack else "encoder.pos_conv_embed.conv.bias"))
     put(g("encoder.layer_norm.weight")); put(g("encoder.layer_norm.bias"))
     for l in range(cfg.num_hidden_layers):
         p = f"encoder.layers.{l}."
@@ -121,6 +125,11 @@ def pack_weights(cfg: W2V2Config, sd: dict) -> np.ndarray:
             put(np.array([b[:4].sum(), b[4:].sum()]))
             put(g(p + "gru_rel_pos_const"))
         put(relative_position_table(cfg, sd["encoder.layers.0.attention.rel_attn_embed.weight"]))
+    if stack:                                                # layers 1..D-1, tap-major like layer 0
+        for i in range(1, cfg.num_conv_pos_embeddings):
+            w = g(f"encoder.pos_conv_embed.layers.{i}.conv.weight")
+            put(np.ascontiguousarray(w.transpose(0, 2, 1)).reshape(w.shape[0], -1))
+            put(g(f"encoder.pos_conv_embed.layers.{i}.conv.bias"))
     assert next(it, None) is None, "weight layout has segments pack_weights does not fill"
     return blob
 

@@ -11,8 +11,11 @@ large checkpoints' variants run too: ``feat_extract_norm="layer"``, ``conv_bias=
 
 Two sibling families run on the same forward (``model_type`` in config.json): HuBERT, which is Wav2Vec2's arithmetic with
 an optional feature-projection LayerNorm (``feat_proj_layer_norm``), and WavLM, whose attention adds a gated relative
-position bias to the scores (``num_buckets``, ``max_bucket_distance``).  Any other ``model_type`` is refused by name: a
-checkpoint whose keys merely contain Wav2Vec2's would otherwise run without the terms it adds.
+position bias to the scores (``num_buckets``, ``max_bucket_distance``).  A third, ``data2vec-audio``, is Wav2Vec2 with the
+layer-norm feature encoder, the post-LN encoder and another positional embedding: a stack of ``num_conv_pos_embeddings``
+(the DEPTH, HF's naming) grouped convolutions of ``conv_pos_kernel_size`` taps, each followed by a parameter-free LayerNorm
+and a GELU (``POS_CONV_STACK``).  Any other ``model_type`` is refused by name: a checkpoint whose keys merely contain
+Wav2Vec2's would otherwise run without the terms it adds.
 """
 from __future__ import annotations
 
@@ -24,9 +27,11 @@ import numpy as np
 
 # forward variants of rsaf_w2v2_forward_ragged_ex (include/rsaf.h)
 LAYER_FEAT_NORM, CONV_BIAS, PRE_LN, NO_INPUT_NORM, NO_FEAT_PROJ_LN, REL_POS_BIAS = 1, 2, 4, 8, 32, 64
+POS_CONV_STACK, POS_DEPTH_SHIFT = 256, 12         # data2vec-audio: the stack's depth (1..15) travels in flags bits 12..15
 MAX_HIDDEN = 1024                  # LayerNorm runs one wave per row
 REL_SPAN = 1024                    # RSAF_W2V2_REL_SPAN: the packed distance table covers |k - q| < REL_SPAN, clamped beyond
-MODEL_TYPES = ("wav2vec2", "hubert", "wavlm")
+MODEL_TYPES = ("wav2vec2", "hubert", "wavlm", "data2vec-audio")
+D2V = "data2vec-audio"
 
 
 @dataclass
@@ -45,10 +50,12 @@ class W2V2Config:
     conv_bias: bool = False
     do_stable_layer_norm: bool = False         # pre-LN encoder
     do_normalize: bool = True                  # preprocessor_config.json: zero-mean / unit-variance windows
-    model_type: str = "wav2vec2"               # "wav2vec2", "hubert" or "wavlm"
+    model_type: str = "wav2vec2"               # "wav2vec2", "hubert", "wavlm" or "data2vec-audio"
     feat_proj_layer_norm: bool = True          # hubert: False = no LayerNorm before the feature projection
     num_buckets: int = 320                     # wavlm: rows of rel_attn_embed
     max_bucket_distance: int = 800             # wavlm: bucket() is constant from this distance on
+    conv_pos_kernel_size: int = 19             # data2vec-audio: taps of every convolution of the positional stack, whose
+                                               # depth is num_conv_pos_embeddings (other families: the taps of their one conv)
     extras: dict = field(default_factory=dict)
 
     @property
@@ -60,7 +67,13 @@ class W2V2Config:
         """The RSAF_W2V2_* bits of this architecture (0 for base-960h's)."""
         return ((LAYER_FEAT_NORM if self.feat_extract_norm == "layer" else 0) | (CONV_BIAS if self.conv_bias else 0)
                 | (PRE_LN if self.do_stable_layer_norm else 0) | (0 if self.do_normalize else NO_INPUT_NORM)
-                | (0 if self.feat_proj_layer_norm else NO_FEAT_PROJ_LN) | (REL_POS_BIAS if self.model_type == "wavlm" else 0))
+                | (0 if self.feat_proj_layer_norm else NO_FEAT_PROJ_LN) | (REL_POS_BIAS if self.model_type == "wavlm" else 0)
+                | ((POS_CONV_STACK | self.num_conv_pos_embeddings << POS_DEPTH_SHIFT) if self.model_type == D2V else 0))
+
+    @property
+    def pos_kernel(self) -> int:
+        """Taps of a positional convolution (the ``pos_kernel`` argument of the C entry points)."""
+        return self.conv_pos_kernel_size if self.model_type == D2V else self.num_conv_pos_embeddings
 
     def frames(self, n_samples: int) -> int:
         """Feature-encoder output length (transformers ``_get_feat_extract_output_lengths``)."""
@@ -97,8 +110,17 @@ class W2V2Config:
                 raise ValueError(f"max_bucket_distance={self.max_bucket_distance} must lie in (num_buckets / 4, {REL_SPAN}): "
                                  f"the packed distance table covers |k - q| < {REL_SPAN}")
         g = self.num_conv_pos_embedding_groups
-        if self.hidden_size % g or (self.hidden_size // g) % 4 or self.num_conv_pos_embeddings % 2:
-            raise ValueError("pos-conv: channels per group must be a multiple of 4, kernel even")
+        if self.hidden_size % g or (self.hidden_size // g) % 4:
+            raise ValueError("pos-conv: channels per group must be a multiple of 4")
+        if self.model_type == D2V:
+            if not 1 <= self.num_conv_pos_embeddings <= 15 or not 1 <= self.conv_pos_kernel_size <= 64:
+                raise ValueError(f"{D2V}: num_conv_pos_embeddings (the stack's depth) must lie in 1..15 and "
+                                 "conv_pos_kernel_size in 1..64")
+            if self.feat_extract_norm != "layer" or self.do_stable_layer_norm or not self.feat_proj_layer_norm:
+                raise ValueError(f"{D2V} is the layer-norm feature encoder with the post-LN encoder and the feature-projection "
+                                 "LayerNorm (feat_extract_norm='layer', do_stable_layer_norm=False, feat_proj_layer_norm=True)")
+        elif self.num_conv_pos_embeddings % 2:
+            raise ValueError("pos-conv: kernel even")
 
     @staticmethod
     def from_hf_dict(d: dict, do_normalize: bool = True) -> "W2V2Config":
@@ -117,18 +139,31 @@ class W2V2Config:
         elif model_type == "wavlm":
             family["num_buckets"] = int(d.get("num_buckets", 320))
             family["max_bucket_distance"] = int(d.get("max_bucket_distance", 800))
+        elif model_type == D2V:
+            # its positional embedding is a stack: num_conv_pos_embeddings convolutions of conv_pos_kernel_size taps.  A
+            # Wav2Vec2 config relabelled data2vec-audio has neither the key nor a depth this build runs
+            if "conv_pos_kernel_size" not in d:
+                raise ValueError(f"config.json: model_type={D2V!r} needs conv_pos_kernel_size (the taps of its positional stack)")
+            if not 1 <= int(d["num_conv_pos_embeddings"]) <= 15:
+                raise ValueError(f"config.json: model_type={D2V!r}: num_conv_pos_embeddings={d['num_conv_pos_embeddings']!r} is "
+                                 "the depth of the positional stack and must lie in 1..15")
+            if not 1 <= int(d["conv_pos_kernel_size"]) <= 64:
+                raise ValueError(f"config.json: model_type={D2V!r}: conv_pos_kernel_size={d['conv_pos_kernel_size']!r} must lie "
+                                 "in 1..64")
+            family["conv_pos_kernel_size"] = int(d["conv_pos_kernel_size"])
+        tag = f"model_type={D2V!r}: " if model_type == D2V else ""
         for key, want in (("feat_extract_activation", "gelu"), ("hidden_act", "gelu")):
             if d.get(key, want) != want:
-                raise ValueError(f"config.json: {key}={d.get(key)!r} is not supported (need {want!r})")
-        if d.get("feat_extract_norm", "group") not in ("group", "layer"):
+                raise ValueError(f"config.json: {tag}{key}={d.get(key)!r} is not supported (need {want!r})")
+        if model_type != D2V and d.get("feat_extract_norm", "group") not in ("group", "layer"):
             raise ValueError(f"config.json: feat_extract_norm={d.get('feat_extract_norm')!r} is not supported "
                              "(need 'group' or 'layer')")
         if d.get("add_adapter") or d.get("adapter_attn_dim"):
-            raise ValueError("config.json: adapters (add_adapter / adapter_attn_dim) are not supported")
+            raise ValueError(f"config.json: {tag}adapters (add_adapter / adapter_attn_dim) are not supported")
         for key in ("hidden_size", "conv_dim"):
             v = max(d[key]) if isinstance(d.get(key), list) else d.get(key, 0)
             if v > MAX_HIDDEN:
-                raise ValueError(f"config.json: {key}={d[key]!r} is above {MAX_HIDDEN}, which this build does not support "
+                raise ValueError(f"config.json: {tag}{key}={d[key]!r} is above {MAX_HIDDEN}, which this build does not support "
                                  "(LayerNorm runs one wave per row; XLS-R 1B / 2B are out of scope)")
         return W2V2Config(conv_dim=tuple(d["conv_dim"]), conv_kernel=tuple(d["conv_kernel"]),
                           conv_stride=tuple(d["conv_stride"]), hidden_size=d["hidden_size"],
@@ -137,13 +172,16 @@ class W2V2Config:
                           num_conv_pos_embeddings=d["num_conv_pos_embeddings"],
                           num_conv_pos_embedding_groups=d["num_conv_pos_embedding_groups"],
                           layer_norm_eps=d.get("layer_norm_eps", 1e-5),
-                          feat_extract_norm=d.get("feat_extract_norm", "group"), conv_bias=bool(d.get("conv_bias", False)),
-                          do_stable_layer_norm=bool(d.get("do_stable_layer_norm", False)), do_normalize=bool(do_normalize),
-                          model_type=model_type, **family)
+                          # transformers' Data2VecAudioModel ignores both switches: always layer norm + post-LN
+                          feat_extract_norm="layer" if model_type == D2V else d.get("feat_extract_norm", "group"),
+                          conv_bias=bool(d.get("conv_bias", False)),
+                          do_stable_layer_norm=model_type != D2V and bool(d.get("do_stable_layer_norm", False)),
+                          do_normalize=bool(do_normalize), model_type=model_type, **family)
 
 
 def hf_shapes(cfg: W2V2Config) -> dict:
-    """state_dict keys/shapes of ``transformers.Wav2Vec2Model`` (``HubertModel``, ``WavLMModel``) for this geometry."""
+    """state_dict keys/shapes of ``transformers.Wav2Vec2Model`` (``HubertModel``, ``WavLMModel``, ``Data2VecAudioModel``) for
+    this geometry."""
     sh = {}
     cin = 1
     for i, (c, k) in enumerate(zip(cfg.conv_dim, cfg.conv_kernel)):
@@ -167,9 +205,10 @@ def hf_shapes(cfg: W2V2Config) -> dict:
     sh["feature_projection.projection.weight"] = (Hd, Cc)
     sh["feature_projection.projection.bias"] = (Hd,)
     K, G = cfg.num_conv_pos_embeddings, cfg.num_conv_pos_embedding_groups
-    sh["encoder.pos_conv_embed.conv.bias"] = (Hd,)
-    sh["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (1, 1, K)
-    sh["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = (Hd, Hd // G, K)
+    if cfg.model_type != D2V:
+        sh["encoder.pos_conv_embed.conv.bias"] = (Hd,)
+        sh["encoder.pos_conv_embed.conv.parametrizations.weight.original0"] = (1, 1, K)
+        sh["encoder.pos_conv_embed.conv.parametrizations.weight.original1"] = (Hd, Hd // G, K)
     sh["encoder.layer_norm.weight"] = (Hd,)
     sh["encoder.layer_norm.bias"] = (Hd,)
     for l in range(cfg.num_hidden_layers):
@@ -193,6 +232,11 @@ def hf_shapes(cfg: W2V2Config) -> dict:
             sh[p + "gru_rel_pos_linear.weight"] = (8, cfg.head_dim)
             sh[p + "gru_rel_pos_linear.bias"] = (8,)
         sh["encoder.layers.0.attention.rel_attn_embed.weight"] = (cfg.num_buckets, cfg.num_attention_heads)
+    # data2vec-audio's positional stack comes last too (K = the depth here)
+    if cfg.model_type == D2V:
+        for i in range(K):
+            sh[f"encoder.pos_conv_embed.layers.{i}.conv.weight"] = (Hd, Hd // G, cfg.conv_pos_kernel_size)
+            sh[f"encoder.pos_conv_embed.layers.{i}.conv.bias"] = (Hd,)
     return sh
 
 
@@ -244,12 +288,12 @@ def random_state_dict(cfg: W2V2Config, seed: int = 0) -> dict:
 
 
 def _strip_prefix(sd: dict) -> dict:
-    """base-960h is a Wav2Vec2ForCTC checkpoint: keys carry a ``wav2vec2.`` prefix (``hubert.`` / ``wavlm.`` in those
+    """base-960h is a Wav2Vec2ForCTC checkpoint: keys carry a ``wav2vec2.`` prefix (``hubert.`` / ``wavlm.`` / ``data2vec_audio.`` in those
     families' CTC and classification checkpoints); ``lm_head`` is unused.  The heads of Wav2Vec2ForPreTraining checkpoints
     (XLSR-53, XLS-R: ``quantizer``, ``project_q``, ``project_hid``) are unused too."""
     out = {}
     for k, v in sd.items():
-        for prefix in ("wav2vec2.", "hubert.", "wavlm."):
+        for prefix in ("wav2vec2.", "hubert.", "wavlm.", "data2vec_audio."):
             if k.startswith(prefix):
                 k = k[len(prefix):]
                 break
@@ -307,6 +351,8 @@ def save_local_model(model_dir: str, cfg: W2V2Config, sd: dict):
         d.update(model_type="hubert", feat_proj_layer_norm=bool(cfg.feat_proj_layer_norm))
     elif cfg.model_type == "wavlm":
         d.update(model_type="wavlm", num_buckets=cfg.num_buckets, max_bucket_distance=cfg.max_bucket_distance)
+    elif cfg.model_type == D2V:                              # num_conv_pos_embeddings above is the stack's depth
+        d.update(model_type=D2V, conv_pos_kernel_size=cfg.conv_pos_kernel_size)
     with open(os.path.join(model_dir, "config.json"), "w") as f:
         json.dump(d, f)
     if not cfg.do_normalize:

@@ -1,9 +1,13 @@
-"""Rate of the Wav2Vec2 stage per architecture: Wav2Vec2 base and large stable-layer-norm, WavLM base, HuBERT base.
+"""Rate of the Wav2Vec2 stage per architecture: Wav2Vec2 base and large stable-layer-norm, WavLM base, HuBERT base,
+data2vec-audio base (beside ``base_layer_norm``, the Wav2Vec2 geometry it differs from in the positional stage alone).
 
 Times ``W2V2Engine.extract_packed`` on 64 x 30 s synthetic clips (the reference's 5 s / 4 s window plan: 448 windows)
 with seeded random weights, and prints audio seconds per second for each architecture.  The architectures alternate
 within every repetition (one process, one device), so a drift of the device hits all of them alike; ratios are taken
 per repetition.
+
+After the timed repetitions one more pass per architecture runs under the library's profiler and reports the
+positional stage's families (``w2v2_posconv_stack``, ``w2v2_posconv_gemm``, ``w2v2_regroup``) in milliseconds per pass.
 
     python tools/w2v2_variant_rate.py [--models base,wavlm_base] [--clips 64] [--seconds 30] [--reps 10] [--out FILE]
 """
@@ -19,7 +23,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from robust_speech_analysis_framework_amd import synth  # noqa: E402
+from robust_speech_analysis_framework_amd import _lib, synth  # noqa: E402
 from robust_speech_analysis_framework_amd.w2v2 import W2V2Engine  # noqa: E402
 from robust_speech_analysis_framework_amd.w2v2_config import W2V2Config, random_state_dict  # noqa: E402
 
@@ -34,7 +38,11 @@ MODELS = {
     "large_stable_ln": W2V2Config(**LARGE),
     "wavlm_base": W2V2Config(**BASE, model_type="wavlm"),
     "hubert_base": W2V2Config(**BASE, model_type="hubert", feat_proj_layer_norm=False),
+    "base_layer_norm": W2V2Config(**BASE, feat_extract_norm="layer"),
+    "data2vec_base": W2V2Config(**BASE, model_type="data2vec-audio", feat_extract_norm="layer", num_conv_pos_embeddings=5,
+                                conv_pos_kernel_size=19, num_conv_pos_embedding_groups=16),
 }
+POS_FAMILIES = ("w2v2_posconv_stack", "w2v2_posconv_gemm", "w2v2_regroup")
 
 
 def main():
@@ -66,15 +74,24 @@ def main():
             engines[n].extract_packed(wav, offs, lengths)
             torch.cuda.synchronize()
             times[n].append(time.perf_counter() - t0)
+    pos_ms = {}
+    for n in names:                                        # one profiled pass each: the positional stage's kernel families
+        _lib.prof_begin()
+        engines[n].extract_packed(wav, offs, lengths)
+        torch.cuda.synchronize()
+        prof = _lib.prof_end()
+        pos_ms[n] = {k: prof[k]["ms"] for k in POS_FAMILIES if k in prof}
     res = {"device": torch.cuda.get_device_name(0), "clips": a.clips, "seconds": a.seconds, "reps": a.reps, "order": "alternating"}
     for n in names:
         cfg, t = MODELS[n], np.array(times[n])
         med = float(np.median(t))
         res[n] = {"model_type": cfg.model_type, "flags": cfg.flags, "hidden": cfg.hidden_size, "layers": cfg.num_hidden_layers,
                   "frames": frames[n], "median_s": med, "min_s": float(t.min()), "max_s": float(t.max()), "audio_s": audio,
-                  "audio_s_per_s": audio / med, "times_s": [float(v) for v in t]}
+                  "audio_s_per_s": audio / med, "times_s": [float(v) for v in t], "positional_stage_ms": pos_ms[n]}
         print(f"{n:16s} {cfg.model_type:8s} flags {cfg.flags:3d}  {audio:.0f} audio-s in {med * 1e3:.1f} ms (median of {a.reps}, "
               f"{t.min() * 1e3:.1f} .. {t.max() * 1e3:.1f})  -> {audio / med:.0f} audio-s/s", flush=True)
+        print(f"{'':16s} positional stage, one profiled pass: "
+              + ", ".join(f"{k} {v:.3f} ms" for k, v in pos_ms[n].items()), flush=True)
     for n in names[1:]:                                    # time ratio to the first model, per repetition
         r = np.array(times[n]) / np.array(times[names[0]])
         res[f"{n}_over_{names[0]}_time"] = {"median": float(np.median(r)), "min": float(r.min()), "max": float(r.max())}
