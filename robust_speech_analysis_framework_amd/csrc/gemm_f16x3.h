@@ -1,8 +1,38 @@
 // fp32-accurate GEMM on the fp16 matrix pipe of gfx950 from two-way operand splits (see gemm_f16x3.hip).
 #pragma once
+#if defined(__HIPCC__)
 #include "gemm_f32.h"
+#define H3_HD __host__ __device__ inline
+#else                                                        // a plain C++ host replay: the parameters and the walks alone
+#include <cstdint>
+#define H3_HD inline
+#endif
 
 namespace rsaf {
+
+// n / d for 0 <= n < 2^31 as (n * mul) >> shift: with l = ceil(log2 d), mul = ceil(2^(31 + l) / d) < 2^32 and
+// shift = 31 + l, 2^shift <= mul d <= 2^shift + 2^l, which makes the quotient exact for every 31-bit n (Granlund and
+// Montgomery 1994, theorem 4.2).  One 32 x 32 -> 64-bit product and a shift: scalar instructions on the device.
+struct H3Div { unsigned mul; int shift; };
+inline H3Div h3_div_make(int d) {
+    int l = 0;
+    while ((1LL << l) < d) ++l;
+    const uint64_t two = 1ULL << (31 + l);
+    H3Div r;
+    r.mul = (unsigned)((two + (uint64_t)d - 1) / (uint64_t)d);
+    r.shift = 31 + l;
+    return r;
+}
+H3_HD int h3_div(int n, H3Div r) { return (int)(((uint64_t)(unsigned)n * r.mul) >> r.shift); }
+// the reciprocal checked where a wrong one would show first: the ends of [0, nmax] and around the multiples of d next to them
+inline bool h3_div_check(H3Div r, int d, int nmax) {
+    if (d <= 0 || nmax < 0 || (uint64_t)r.mul * (uint64_t)d < (1ULL << r.shift)) return false;
+    const int64_t top = (int64_t)(nmax / d) * d;
+    const int64_t at[] = {0, 1, d - 1, d, (int64_t)d + 1, 2LL * d - 1, top - 1, top, top + d - 1, nmax - 1, nmax};
+    for (int64_t n : at)
+        if (n >= 0 && n <= nmax && h3_div((int)n, r) != (int)(n / d)) return false;
+    return true;
+}
 
 // C[z][m][n] = act( alpha * sum_k A[z][m][k] * B[n][k] + bias[n] + R[z][m][n] ).
 // Every operand is two fp16 planes (hi, lo) of the fp32 value TIMES A POWER OF TWO chosen per row (or per batch), so
@@ -51,10 +81,75 @@ struct GemmH3Params {
     int b_panel_rows;
     // A as a padded panel image shared by the taps of a convolution: a_panel with R = a_panel_rows rows per panel (batches
     // allowed: sA = rows between the batches' first rows x 16), and, with a_tap_panels = P > 0, K = taps x P panels where
-    // k-tile kt reads panel kt % P one row further down per tap kt / P (a_tap_inv is filled in by the launcher)
+    // k-tile kt reads panel kt % P one row further down per tap kt / P (walked by h3_kstep_next below; a_tap_inv, the
+    // reciprocal of the kernel's earlier kt / P, is no longer read)
     int a_panel_rows, a_tap_panels, a_tap_inv;
+    // The tile grid of the launch and the reciprocals of its walk (h3_tile_at), filled in and checked by the launcher
+    // (h3_grid_fill) for the tile configuration it chose: callers leave them zero.
+    int tiles_m, tiles_n, nwg;
+    H3Div inv_nwg, inv_nz2, inv_per_group, inv_gsz, inv_gsz_last;
 };
 
+// ---- the walk of the persistent workgroups over the tiles (kernel and host replay: tests/host/gemm_tilewalk_replay.cpp) ----
+// Tile t -> batch z = t / nwg and, inside the batch, the XCD-aware bijective remap of the index, then group_m row-tiles x
+// all column-tiles walked column by column.  Tile indices are below 2^31 (the launcher rejects more), every division is a
+// multiplication by a reciprocal the launcher made: no 64-bit division on the device.
+struct H3Tile { int z, z1, z2, tm, tn; };                    // batch (z = z1 * nz2 + z2), row-tile and column-tile
+H3_HD H3Tile h3_tile_at(const GemmH3Params& p, int t) {
+    H3Tile T;
+    T.z = h3_div(t, p.inv_nwg);
+    const int orig = t - T.z * p.nwg;
+    T.z1 = h3_div(T.z, p.inv_nz2);                           // (window, group) of a grouped convolution; nz2 <= 1: z1 = z
+    T.z2 = T.z - T.z1 * (p.nz2 > 1 ? p.nz2 : 1);
+    const int xcd = orig & 7, q8 = p.nwg >> 3, r8 = p.nwg & 7;
+    const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+    const int per_group = p.group_m * p.tiles_n;
+    const int grp = h3_div(wg, p.inv_per_group);
+    const int first_m = grp * p.group_m;
+    const bool full = p.tiles_m - first_m >= p.group_m;      // only the last group can be short: tiles_m % group_m row-tiles
+    const int gsz = full ? p.group_m : p.tiles_m - first_m;
+    const int in_grp = wg - grp * per_group;
+    T.tn = h3_div(in_grp, full ? p.inv_gsz : p.inv_gsz_last);
+    T.tm = first_m + (in_grp - T.tn * gsz);
+    return T;
+}
+// Fills the grid fields of p for tiles of bm x bn (M, N, nz, nz2, group_m set) and checks every reciprocal at the ends of
+// its range; false: more than 2^31 - 1 tiles, or a reciprocal that does not divide.
+inline bool h3_grid_fill(GemmH3Params& p, int bm, int bn) {
+    const int64_t tn = (p.N + bn - 1) / bn, tm = (p.M + bm - 1) / bm;
+    if (tn <= 0 || tm <= 0 || p.nz <= 0 || p.group_m <= 0 || tn * tm * p.nz > 0x7fffffffLL || p.group_m * tn > 0x7fffffffLL) return false;
+    p.tiles_m = (int)tm; p.tiles_n = (int)tn; p.nwg = (int)(tm * tn);
+    const int nz2 = p.nz2 > 1 ? p.nz2 : 1, per_group = (int)(p.group_m * tn);
+    const int last = p.tiles_m % p.group_m ? p.tiles_m % p.group_m : p.group_m;
+    p.inv_nwg = h3_div_make(p.nwg); p.inv_nz2 = h3_div_make(nz2); p.inv_per_group = h3_div_make(per_group);
+    p.inv_gsz = h3_div_make(p.group_m); p.inv_gsz_last = h3_div_make(last);
+    return h3_div_check(p.inv_nwg, p.nwg, (int)(tm * tn * p.nz - 1)) && h3_div_check(p.inv_nz2, nz2, p.nz - 1) &&
+           h3_div_check(p.inv_per_group, per_group, p.nwg - 1) && h3_div_check(p.inv_gsz, p.group_m, per_group - 1) &&
+           h3_div_check(p.inv_gsz_last, last, per_group - 1);
+}
+
+// ---- the walk of a DMA source over the k-tiles -----------------------------------------------------------------------
+// Offset of k-tile KT of an operand whose k-tiles lie `kstride` apart.  A convolution over a padded panel image
+// (tap_panels = P > 0: K = taps x P panels) walks the P channel panels of a tap and then moves ONE ROW (16 elements) down
+// for the next tap: offset (KT % P) kstride + (KT / P) 16.  The kernel never forms KT * kstride: it keeps the offset (inside
+// a pointer) and the panel counter and advances both once per k-tile; the choice between the two steps is a select.
+// `unit` scales the steps (1: elements, 2: bytes of fp16).
+struct H3KStep { int64_t step, jump; int wrap; };
+H3_HD H3KStep h3_kstep(int64_t kstride, int tap_panels, int unit) {
+    H3KStep s;
+    s.step = kstride * unit;
+    s.jump = tap_panels > 0 ? (16 - (int64_t)(tap_panels - 1) * kstride) * unit : s.step;
+    s.wrap = tap_panels > 0 ? tap_panels : 0x7fffffff;       // (no taps: the counter never wraps)
+    return s;
+}
+// the step from the k-tile whose panel counter is pc to the next one, and the counter's advance
+H3_HD int64_t h3_kstep_next(const H3KStep& s, int& pc) {
+    const bool w = pc + 1 == s.wrap;
+    pc = w ? 0 : pc + 1;
+    return w ? s.jump : s.step;
+}
+
+#if defined(__HIPCC__)
 int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag);
 
 // Per-row statistics of a row-major fp32 matrix [rows][K] (ld elements between rows): scale[r] = the power of two that puts
@@ -72,7 +167,7 @@ int launch_scale_from_bound(const unsigned* amax_bits, int64_t n, const float* f
 
 // ---- device helpers shared with the producers that write plane operands (w2v2.hip) -------------------------------------
 // the power of two s with bound * s in [2^14, 2^15) (bound > 0, finite); 1 for bound == 0
-__host__ __device__ inline float f16x2_scale_for_bound(float bound) {
+H3_HD float f16x2_scale_for_bound(float bound) {
     union { float f; unsigned u; } v;
     v.f = bound;
     const int e = (int)((v.u >> 23) & 0xff);             // biased exponent: bound in [2^(e-127), 2^(e-126))
@@ -83,14 +178,13 @@ __host__ __device__ inline float f16x2_scale_for_bound(float bound) {
     return v.f;
 }
 // 1 / s of a power of two, exactly
-__host__ __device__ inline float pow2_inverse(float s) {
+H3_HD float pow2_inverse(float s) {
     union { float f; unsigned u; } v;
     v.f = s;
     v.u = 0x7F000000u - v.u;
     return v.f;
 }
 
-#if defined(__HIPCC__)
 // GELU(x) = x / 2 (1 + erf(x / sqrt 2)) of TWO values at once on the packed-fp32 instructions (v_pk_fma_f32 / v_pk_mul_f32: one
 // instruction, two elements).  erf: the two-interval form of the single-precision libm routines (|a| <= 0.9277: a + a P(a^2);
 // beyond: 1 - exp2(Q(|a|)), log2(e) folded into Q's coefficients so that the exponential is the bare v_exp_f32), both intervals

@@ -24,8 +24,12 @@
 // 256 x 256 x 16 block tile, 8 waves of 128 x 64 (4 x 2 MFMA tiles, 24 MFMAs per k-tile and wave), one workgroup per
 // CU; k-tiles travel global -> LDS by DMA (global_load_lds, 16 B per lane), three stages of 32 KB, two k-tiles in
 // flight; the two 16-byte chunks of a 32-byte row are swapped on the SOURCE side for rows with (row >> 3) & 1 so that
-// the ds_read_b128 fragment reads are conflict-free; the two waves of a SIMD run half a k-tile apart.
+// the ds_read_b128 fragment reads are conflict-free; the two waves of a SIMD run half a k-tile apart.  Nothing that is
+// invariant is computed per k-tile or between two tiles: the DMA sources are running pointers, the steady-state loop of
+// each wave group is one basic block, and a workgroup finds its next tile while it waits for the current one's first
+// k-tiles (the walks are in gemm_f16x3.h, replayed on the host by tests/host/gemm_tilewalk_replay.cpp).
 #include <algorithm>
+#include <type_traits>
 
 #include "gemm_f16x3.h"
 
@@ -89,111 +93,108 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
     constexpr int A_PLANE = CFG::A_PLANE, B_PLANE = CFG::B_PLANE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), l31 = lane & 31, h = lane >> 5;
-    const int tiles_n = (p.N + BN - 1) / BN, tiles_m = (p.M + BM - 1) / BM;
-    const int nwg = tiles_n * tiles_m;
-    const int64_t total_tiles = (int64_t)nwg * p.nz;
+    const unsigned total_tiles = (unsigned)p.nwg * (unsigned)p.nz;      // < 2^31 (launcher)
     const int wm0 = (wave / CFG::WN) * (32 * TM), wn0 = (wave % CFG::WN) * (32 * TN);
 
-    // Persistent workgroups: workgroup b walks tiles b, b + gridDim.x, ...  Tile t -> batch z = t / nwg and, inside the batch,
-    // the XCD-aware bijective remap of the index, then GROUP_M row-tiles x all column-tiles walked column by column.
-    struct Tile { int m0, n0, Mz; int64_t z, z1, z2, coff; };
-    auto tile_at = [&](int64_t t) {
-        Tile T;
-        T.z = t / nwg;
-        const int orig = (int)(t - T.z * nwg);
-        T.z1 = p.nz2 > 1 ? T.z / p.nz2 : T.z;
-        T.z2 = p.nz2 > 1 ? T.z % p.nz2 : 0;                              // (window, group) of a grouped convolution
-        T.Mz = p.ztab ? (int)p.ztab[2 * T.z1] : p.M;                     // rows of this batch (ragged windows)
-        T.coff = p.ztab ? p.ztab[2 * T.z1 + 1] : -1;
-        const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
-        const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
-        const int GROUP_M = p.group_m;
-        const int per_group = GROUP_M * tiles_n;
-        const int grp = wg / per_group;
-        const int first_m = grp * GROUP_M;
-        const int gsz = (tiles_m - first_m) < GROUP_M ? (tiles_m - first_m) : GROUP_M;
-        const int in_grp = wg - grp * per_group;
-        T.m0 = (first_m + in_grp % gsz) * BM;
-        T.n0 = (in_grp / gsz) * BN;
-        return T;
-    };
+    // Persistent workgroups: workgroup b walks tiles b, b + gridDim.x, ... in the order of h3_tile_at (gemm_f16x3.h).
+    // A tile as the kernel keeps it: where it is, the rows of its batch, and the element offsets of its A and B origins.
+    struct Tile { int m0, n0, Mz, z, z1, z2; int64_t coff, aoff, boff; unsigned t; bool valid; };
     // the first tile at or after t (stride gridDim.x) that has rows: tiles past a short batch's rows are skipped
-    auto next_valid = [&](int64_t t, Tile& T) {
+    auto next_valid = [&](unsigned t) {
+        Tile T;
+        T.valid = false;
         for (; t < total_tiles; t += gridDim.x) {
-            T = tile_at(t);
-            if (T.m0 < T.Mz) return t;
+            const H3Tile W = h3_tile_at(p, (int)t);
+            T.m0 = W.tm * BM; T.n0 = W.tn * BN; T.z = W.z; T.z1 = W.z1; T.z2 = W.z2;
+            T.Mz = p.ztab ? (int)p.ztab[2 * W.z1] : p.M;                 // rows of this batch (ragged windows)
+            if (T.m0 < T.Mz) {
+                T.coff = p.ztab ? p.ztab[2 * W.z1 + 1] : -1;
+                T.aoff = W.z1 * p.sA + W.z2 * p.sA2 + (int64_t)T.m0 * (p.a_panel ? 16 : p.lda);
+                T.boff = W.z2 * p.sB2 + (int64_t)T.n0 * (p.b_panel ? 16 : p.ldb);
+                T.t = t; T.valid = true;
+                break;
+            }
         }
-        return (int64_t)-1;
+        return T;
     };
 
     // DMA: one wave-instruction moves 32 rows of one plane (1 KiB).  Instruction j of an operand covers rows 32 j ..;
-    // the A_INSTR + B_INSTR instructions of a plane pair are dealt round-robin to the waves.
+    // the A_INSTR + B_INSTR instructions of a plane pair are dealt round-robin to the waves: slot i of a wave is instruction
+    // wave + NW i, an A instruction for i < A_SLOTS and a B instruction behind that (the last slot may be empty).
     // lane -> row 32 j + (lane >> 1), LDS chunk lane & 1 <- global chunk (lane & 1) ^ ((row >> 3) & 1)
     constexpr int NI = CFG::A_INSTR + CFG::B_INSTR;
     constexpr int IPW = (NI + NW - 1) / NW;                               // instructions (x NPL planes) per wave and k-tile
-    const unsigned short* sbase[IPW];                                    // wave-uniform: operand + tile origin (SGPR pair)
+    constexpr int A_SLOTS = CFG::A_INSTR / NW;
+    constexpr int LAST_LIVE = NI - NW * (IPW - 1);                        // waves whose last slot holds an instruction
+    static_assert(CFG::A_INSTR % NW == 0, "a slot is an A or a B instruction for every wave alike");
+    static_assert(LAST_LIVE == NW || LAST_LIVE <= NW / 2, "the waves of group B have the same number of DMA instructions");
+    const bool last_live = LAST_LIVE == NW || wave < LAST_LIVE;           // (wave-uniform; a constant for the 256 x 256 tile)
+#define H3_LIVE(i) ((i) < IPW - 1 || last_live)
+    // Per DMA instruction a wave-uniform 64-bit source pointer (SGPR pair) that RUNS: it points at the k-tile this wave
+    // fetches next and advances by a loop-invariant step per k-tile (h3_kstep_next: the k-stride, or in tap-panel mode the
+    // jump to the next tap when the panel counter wraps; a select).  The two prefetch DMAs of a tile set it up.
+    const char* src[IPW][NPL];
     unsigned voff[IPW];                                                   // per lane: ((row in tile) * ld + chunk) * 2 bytes
-    int64_t pstride[IPW], kstride[IPW];
     int ldsoff[IPW];
-    bool live[IPW];
+    int pc = 0;                                                           // panel counter of the k-tile the A pointers are at
+    const H3KStep a_step = h3_kstep(p.a_panel ? (int64_t)(p.a_panel_rows > 0 ? p.a_panel_rows : p.M) * 16 : 16, p.a_tap_panels, 2);
+    const int64_t b_step = 2 * (p.b_panel ? (int64_t)(p.b_panel_rows > 0 ? p.b_panel_rows : p.N) * 16 : 16);
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
-        const int j = wave + NW * i;
-        live[i] = j < NI;
-        const bool isA = j < CFG::A_INSTR;
-        const int jj = isA ? j : j - CFG::A_INSTR;
-        pstride[i] = isA ? p.a_plane : p.b_plane;
-        kstride[i] = isA ? (p.a_panel ? (int64_t)(p.a_panel_rows > 0 ? p.a_panel_rows : p.M) * 16 : 16) : (p.b_panel ? (int64_t)(p.b_panel_rows > 0 ? p.b_panel_rows : p.N) * 16 : 16);
-        ldsoff[i] = isA ? jj * 512 : NPL * A_PLANE + jj * 512;
+        const int jj = i < A_SLOTS ? wave + NW * i : wave + NW * i - CFG::A_INSTR;
+        ldsoff[i] = i < A_SLOTS ? jj * 512 : NPL * A_PLANE + jj * 512;
     }
-    auto set_tile = [&](const Tile& T) {                                  // DMA sources of a tile
+    auto set_tile = [&](const Tile& T) {                                  // DMA sources of a tile's k-tile 0
+        pc = 0;
 #pragma unroll
         for (int i = 0; i < IPW; ++i) {
-            const int j = wave + NW * i;
-            const bool isA = j < CFG::A_INSTR;
-            const int jj = isA ? j : j - CFG::A_INSTR;
+            const bool isA = i < A_SLOTS;
+            const int jj = isA ? wave + NW * i : wave + NW * i - CFG::A_INSTR;
             const int row = 32 * jj + (lane >> 1);
             const int dch = (lane & 1) ^ ((row >> 3) & 1);
-            if (isA) {
-                const int rr = (T.m0 + row < T.Mz) ? row : T.Mz - 1 - T.m0;   // rows past M re-read the last row
-                const int64_t rs = p.a_panel ? 16 : p.lda;                // row stride (elements)
-                sbase[i] = p.A + T.z1 * p.sA + T.z2 * p.sA2 + (int64_t)T.m0 * rs;
-                voff[i] = 2u * ((unsigned)rr * (unsigned)rs + 8u * dch);
-            } else {
-                const int rr = (T.n0 + row < p.N) ? row : p.N - 1 - T.n0;
-                const int64_t rs = p.b_panel ? 16 : p.ldb;
-                sbase[i] = p.B + T.z2 * p.sB2 + (int64_t)T.n0 * rs;
-                voff[i] = 2u * ((unsigned)rr * (unsigned)rs + 8u * dch);
-            }
+            const int rr = isA ? ((T.m0 + row < T.Mz) ? row : T.Mz - 1 - T.m0)     // rows past M re-read the last row
+                               : ((T.n0 + row < p.N) ? row : p.N - 1 - T.n0);
+            const int64_t rs = isA ? (p.a_panel ? 16 : p.lda) : (p.b_panel ? 16 : p.ldb);   // row stride (elements)
+            voff[i] = 2u * ((unsigned)rr * (unsigned)rs + 8u * dch);
+            const unsigned short* base = isA ? p.A + T.aoff : p.B + T.boff;
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl)
+                src[i][pl] = reinterpret_cast<const char*>(base + pl * (isA ? p.a_plane : p.b_plane));
         }
     };
-    const int nk = p.K / BK;
-    // element offset of k-tile KT of instruction i's operand.  A convolution over a padded panel image (a_tap_panels = P > 0:
-    // K = taps x P panels) walks the P channel panels of a tap and then moves ONE ROW down for the next tap: the rows of
-    // consecutive taps overlap, the image holds every activation once.  tap = KT / P by a host-checked reciprocal.
-    auto koff = [&](int i, int KT) -> int64_t {
-        if (p.a_tap_panels > 0 && (wave + NW * i) < CFG::A_INSTR) {
-            const int tap = (int)(((unsigned)KT * (unsigned)p.a_tap_inv) >> 16);
-            return (int64_t)(KT - tap * p.a_tap_panels) * kstride[i] + (int64_t)tap * 16;
-        }
-        return (int64_t)KT * kstride[i];
-    };
-
-#define H3_DMA(KT, ST)                                                                                          \
+    // this wave's share of the k-tile its pointers are at, into the stage at element offset ST of the LDS image
+#define H3_DMA(ST)                                                                                              \
     do {                                                                                                        \
         _Pragma("unroll") for (int i = 0; i < IPW; ++i) {                                                       \
-            if (live[i]) {                                                                                      \
-                const bool isA_ = (wave + NW * i) < CFG::A_INSTR;                                               \
+            if (H3_LIVE(i)) {                                                                                   \
                 _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl)                                              \
-                    __builtin_amdgcn_global_load_lds(H3_ADDR(sbase[i] + (pl * pstride[i] + koff(i, (KT))), voff[i]), \
-                        (lds_ptr3)(smem3 + (ST) * STAGE + ldsoff[i] + pl * (isA_ ? A_PLANE : B_PLANE)), 16, 0, 0); \
+                    __builtin_amdgcn_global_load_lds(H3_ADDR(src[i][pl], voff[i]),                              \
+                        (lds_ptr3)(smem3 + (ST) + ldsoff[i] + pl * (i < A_SLOTS ? A_PLANE : B_PLANE)), 16, 0, 0); \
             }                                                                                                   \
         }                                                                                                       \
     } while (0)
+    // ... and on to the next k-tile: scalar adds only
+#define H3_ADVANCE()                                                                                            \
+    do {                                                                                                        \
+        const int64_t a_inc_ = h3_kstep_next(a_step, pc);                                                       \
+        _Pragma("unroll") for (int i = 0; i < IPW; ++i)                                                         \
+            _Pragma("unroll") for (int pl = 0; pl < NPL; ++pl) src[i][pl] += i < A_SLOTS ? a_inc_ : b_step;     \
+    } while (0)
+    const int nk = p.K / BK;
+    // a tile's first two k-tiles, into stages 0 and 1; the pointers end at k-tile 2, where both wave groups refill from
+    auto prefetch = [&](const Tile& T) {
+        set_tile(T);
+        H3_DMA(0);
+        if (nk > 1) {
+            H3_ADVANCE();
+            H3_DMA(STAGE);
+            H3_ADVANCE();
+        }
+    };
 
     static_assert(NST == 3 && TM % 2 == 0, "the staggered loop needs three stages and an even number of m-tiles");
     const int grpB = wave >= NW / 2 ? 1 : 0;
-    constexpr int NDMA = NPL * IPW;                          // DMA instructions of this wave per k-tile
+    constexpr int NDMA_B = NPL * (LAST_LIVE == NW ? IPW : IPW - 1);   // DMA instructions per k-tile of a wave of group B
     constexpr int HM = TM / 2;
     constexpr int PATCH_LD = 36;                             // floats per patch row (16-byte aligned rows, 2-way write conflicts)
     float* patch = reinterpret_cast<float*>(smem3 + (CFG::PATCH_IN_STAGE2 ? 2 : NST) * STAGE) + wave * (32 * PATCH_LD);
@@ -222,8 +223,8 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
                     e0[u] = p.a_scale[rt.x];
                     e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[rt.x] : 1.0f;
                 } else {
-                    e0[u] = p.a_scale[T.z1 * p.a_scale_zs + (int64_t)row * p.a_scale_ms];
-                    e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[T.z1 * p.c_scale_zs + (int64_t)row * p.c_scale_ms] : 1.0f;
+                    e0[u] = p.a_scale[(int64_t)T.z1 * p.a_scale_zs + (int64_t)row * p.a_scale_ms];
+                    e1[u] = (OUT_PLANES && p.Cp) ? p.c_scale[(int64_t)T.z1 * p.c_scale_zs + (int64_t)row * p.c_scale_ms] : 1.0f;
                 }
             } else if (i < BM + BN) {
                 const int col = T.n0 + i - BM;
@@ -232,15 +233,16 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
             }
         }
     };
-    Tile cur;
-    int64_t t_cur = next_valid(blockIdx.x, cur);
-    if (t_cur < 0) return;                                   // (workgroup-uniform)
+    Tile cur = next_valid(blockIdx.x);
+    if (!cur.valid) return;                                  // (workgroup-uniform)
     load_epi(cur);
-    set_tile(cur);
-    H3_DMA(0, 0);
-    if (nk > 1) H3_DMA(1, 1);
+    prefetch(cur);
 
     while (true) {
+    // The NEXT tile of this workgroup, found now: the divisions of the walk and the skip over the tiles of short batches
+    // are scalar work that sits under the wait for the first k-tiles, not between this tile's last MFMA and the next
+    // tile's first DMA.
+    const Tile nxt = next_valid(cur.t + gridDim.x);
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -249,25 +251,22 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
-    // Main loop: ONE instruction stream, two barriers per k-tile, the two waves of every SIMD half a k-tile apart
-    // (waves NW/2 .. NW-1 pass one extra barrier in front of the loop and the others one behind it: barriers match by
-    // count).  A wave issues its DMA instructions at the head of its first half, behind the B-fragment reads of the new
-    // k-tile; group A (slot 2 kt) fetches k-tile kt + 1 into the stage of k-tile kt - 2 and waits for it in front of its
-    // next top barrier; group B (slot 2 kt + 1) fetches k-tile kt + 2 into the stage of k-tile kt - 1 and waits for it
-    // in front of the middle barrier of its k-tile kt + 1 (counted: its next DMA instructions stay in flight).
-    // Everything this wave has in flight - its share of k-tiles 0 and 1 and, from the second tile on, the previous
-    // epilogue's stores (loads and stores share the counter and do not retire in order with each other) - has landed:
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (grpB) __builtin_amdgcn_s_barrier();
-    int st = 0;                                              // stage of k-tile kt
-    for (int kt = 0; kt < nk; ++kt) {
-        if (!grpB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A: its share of k-tile kt (issued one k-tile ago)
+    // Main loop: two barriers per k-tile, the two waves of every SIMD half a k-tile apart (waves NW/2 .. NW-1, group B,
+    // pass one extra barrier in front of their k-tiles and the others, group A, one behind theirs: barriers match by count).
+    // A wave issues its DMA instructions in its first half, behind the top barrier that frees their stage; group A fetches
+    // k-tile kt + 1 into the stage of k-tile kt - 2 and waits for it in front of its next top barrier; group B fetches
+    // k-tile kt + 2 into the stage of k-tile kt - 1 and waits for it in front of the middle barrier of its k-tile kt + 1
+    // (counted: its next DMA instructions stay in flight).  Both groups fetch k-tiles 2 .. nk - 1 in turn, from the same
+    // running pointers: group A in its k-tiles 1 .. nk - 2, group B in its k-tiles 0 .. nk - 3.  The k-tiles that fetch and
+    // those that do not are separate instances of one body (REFILL), per group (GRPB): inside the loops nothing is tested
+    // but the trip count, the waits are immediates, and the three stage offsets rotate through three scalars.
+    int s0 = 0, s1 = STAGE, s2 = 2 * STAGE;                  // element offsets of the stages of k-tiles kt, kt + 1, kt + 2
+    auto ktile = [&](auto refill_c, auto grpb_c) __attribute__((always_inline)) {
+        constexpr bool REFILL = decltype(refill_c)::value, GRPB = decltype(grpb_c)::value;
+        if (!GRPB) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // A: its share of this k-tile (issued one k-tile ago)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        const int rkt = kt + 1 + grpB;
-        const bool refill = rkt < nk && (grpB || kt >= 1);
-        const int rst = (st + 1 + grpB) % NST;
-        const unsigned short* img = smem3 + st * STAGE;
+        const unsigned short* img = smem3 + s0;
         f16x8 bf[TN][NPL];
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {
@@ -276,18 +275,9 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
 #pragma unroll
             for (int pl = 0; pl < NPL; ++pl) bf[nt][pl] = *reinterpret_cast<const f16x8*>(&img[NPL * A_PLANE + pl * B_PLANE + off]);
         }
-        if (refill) {
-#pragma unroll
-            for (int d = 0; d < NDMA; ++d) {
-                const int i = d / NPL, pl = d % NPL;
-                if (live[i]) {
-                    const bool isA_ = (wave + NW * i) < CFG::A_INSTR;
-                    __builtin_amdgcn_sched_barrier(0);
-                    __builtin_amdgcn_global_load_lds(H3_ADDR(sbase[i] + (pl * pstride[i] + koff(i, rkt)), voff[i]),
-                        (lds_ptr3)(smem3 + rst * STAGE + ldsoff[i] + pl * (isA_ ? A_PLANE : B_PLANE)), 16, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
+        if (REFILL) {
+            H3_DMA(GRPB ? s2 : s1);
+            H3_ADVANCE();
         }
         f16x8 afp[NPL];                                      // A fragments of m-tile HM, fetched in the first half
 #pragma unroll
@@ -317,18 +307,30 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
                 acc[mt][nt] = c;
             }
             if (mt == HM - 1) {
-                if (grpB) {                                  // (the count is this wave's own: the last instruction slot may be empty)
-                    if (!refill) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                    else if (live[IPW - 1]) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPL * IPW) : "memory");
-                    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NPL * (IPW - 1) > 0 ? NPL * (IPW - 1) : 0) : "memory");
-                }
+                // B: its share of the next k-tile has landed; what it issued in this k-tile (NDMA_B instructions) stays in flight
+                if (GRPB) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(REFILL ? NDMA_B : 0) : "memory");
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
         }
-        st = st == NST - 1 ? 0 : st + 1;
+        const int s_ = s0; s0 = s1; s1 = s2; s2 = s_;
+    };
+    constexpr std::true_type YES{};
+    constexpr std::false_type NO{};
+    // Everything this wave has in flight - its share of k-tiles 0 and 1 and, from the second tile on, the previous
+    // epilogue's stores (loads and stores share the counter and do not retire in order with each other) - has landed:
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!grpB) {
+        ktile(NO, NO);                                       // k-tile 0: k-tile 1 is already on its way
+        for (int kt = 1; kt < nk - 1; ++kt) ktile(YES, NO);
+        if (nk > 1) ktile(NO, NO);
+        __builtin_amdgcn_s_barrier();
+    } else {
+        __builtin_amdgcn_s_barrier();
+        for (int kt = 0; kt < nk - 2; ++kt) ktile(YES, YES);
+        if (nk > 1) ktile(NO, YES);
+        ktile(NO, YES);
     }
-    if (!grpB) __builtin_amdgcn_s_barrier();
 
     // ---- epilogue ----
     // MFMA layout: lane l31 = column, register e -> row (e & 3) + 8 (e >> 2) + 4 h of a 32 x 32 tile.  Each tile is
@@ -348,7 +350,7 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
     float4 r4[4];                                        // residual of the sub-tile in hand (fp32 output only: CW = 4)
     auto load_r = [&](int mt, int nt) {
         const int tn = done.n0 + wn0 + nt * 32, tm = done.m0 + wm0 + mt * 32;
-        const float* Rt = p.R + done.z * p.sR + (int64_t)tm * p.ldr + tn + c4;
+        const float* Rt = p.R + (int64_t)done.z * p.sR + (int64_t)tm * p.ldr + tn + c4;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const bool ok = (tn + c4) < p.N && (tm + 8 * q + lr) < done.Mz;
@@ -365,12 +367,10 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
 
     // ---- next tile: its first two k-tiles travel while this tile's epilogue runs ----
     __syncthreads();                                     // every wave is done reading the stages; the tables are filed
-    t_cur = next_valid(t_cur + gridDim.x, cur);
-    if (t_cur >= 0) {
-        set_tile(cur);
+    cur = nxt;                                           // (found at the head of this tile)
+    if (cur.valid) {
+        prefetch(cur);
         load_epi(cur);
-        H3_DMA(0, 0);
-        if (nk > 1) H3_DMA(1, 1);
     }
 
     {
@@ -493,9 +493,11 @@ __global__ __launch_bounds__(CFG::THREADS, CFG::WGS * CFG::THREADS / 256) void g
         }
     }
     }
-    if (t_cur < 0) break;
+    if (!cur.valid) break;
     }
 #undef H3_DMA
+#undef H3_ADVANCE
+#undef H3_LIVE
 }
 
 // ---- operand preparation ------------------------------------------------------------------------------------------
@@ -638,8 +640,8 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
     do {                                                                                                                \
         RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)gemm_f16x3_kernel<CFG, ACT, F32, PL, HR, ##__VA_ARGS__>,         \
                                            hipFuncAttributeMaxDynamicSharedMemorySize, CFG::LDS_BYTES));                 \
-        const int64_t tiles = (int64_t)((p.N + CFG::BN - 1) / CFG::BN) * ((p.M + CFG::BM - 1) / CFG::BM) * p.nz;        \
-        RSAF_CHECK_ARG(tiles <= 0x7fffffffLL, "too many tiles");                                                        \
+        RSAF_CHECK_ARG(h3_grid_fill(pp, CFG::BM, CFG::BN), "too many tiles");                                           \
+        const int64_t tiles = (int64_t)pp.nwg * pp.nz;                                                                  \
         hipLaunchKernelGGL((gemm_f16x3_kernel<CFG, ACT, F32, PL, HR, ##__VA_ARGS__>),                                    \
                            dim3((unsigned)std::min<int64_t>(tiles, persistent_wgs)), dim3(CFG::THREADS), CFG::LDS_BYTES, stream, pp); \
     } while (0)
@@ -657,11 +659,6 @@ int launch_gemm_f16x3(const GemmH3Params& p, hipStream_t stream, const char* tag
     } while (0)
     GemmH3Params pp = p;
     if (pp.group_m <= 0) pp.group_m = 2;
-    if (pp.a_tap_panels > 0) {                               // kt / P as (kt * inv) >> 16, checked for every k-tile of this launch
-        pp.a_tap_inv = 65536 / pp.a_tap_panels + 1;
-        for (int kt = 0; kt < pp.K / 16; ++kt)
-            RSAF_CHECK_ARG((int)(((unsigned)kt * (unsigned)pp.a_tap_inv) >> 16) == kt / pp.a_tap_panels, "a_tap_panels: K too long for the reciprocal");
-    }
     // persistent workgroups, one per CU
     int persistent_wgs = 256;
     {
