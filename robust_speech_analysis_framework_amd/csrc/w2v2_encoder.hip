@@ -1,6 +1,7 @@
 // Wav2Vec2 forward, encoder: LayerNorm (ln), attention (fused on the fp16 matrix pipe, or three launches), WavLM's bias gate
 // and the encoder layers; the kernels, then the Forward phases that launch them.
 #include "w2v2_forward.h"
+#include "attn_softmax.h"
 
 namespace rsaf {
 namespace w2v2 {
@@ -191,12 +192,17 @@ typedef const __attribute__((address_space(1))) void* attn_glb_ptr;
 //     of the sum over keys; no conversion work in this kernel except for the probabilities;
 //   * K blocks of 128 keys x 64 halfs x 2 planes (32 KB) by LDS-DMA, 16-byte chunks XOR-swizzled on the source address
 //     (chunk ^ ((row >> 1) & 7): the ds_read_b128 fragment reads of 16 consecutive rows cover all 64 banks);
-//   * the score tile's register layout is the A operand of P V (element j of lane half h = key 16 s + 8 (j >> 2) + 4 h + (j & 3)),
-//     P = p * 2^14 split into hi + lo; the V fragment (B operand, the same key order) comes out of row-major V by two
-//     ds_read_b64_tr_b16 (4 keys x 16 columns per 16-lane group, delivered column-major), V chunks swizzled by
-//     ((row >> 1) & 1) << 2 so that the four rows of a transposed read sit on disjoint banks;
-//   * O = acc 2^-14 is already in the window's scale: it leaves as the plane pair of the out-projection's A operand.
+//   * the score tile's register layout is an operand of the second product (element j of lane half h = key 16 s + 8 (j >> 2)
+//     + 4 h + (j & 3)), P = e * 2^14 split into hi + lo, e = exp(s - max) un-normalised (attn_softmax.h: the maximum on the
+//     raw accumulators, one fma into a base-2 argument, the bare v_exp_f32, a three-instruction split of two elements); the V
+//     fragment (the same key order) comes out of row-major V by two ds_read_b64_tr_b16 (4 keys x 16 columns per 16-lane
+//     group, delivered column-major), V chunks swizzled by ((row >> 1) & 1) << 2 so that the four rows of a transposed
+//     read sit on disjoint banks; the fragments of a step are requested one step ahead (counted lgkmcnt);
+//   * the second product is O^T = V^T P^T (V the A operand): the query stays on the lane, so acc / sum is in-lane, already
+//     in the window's scale, and leaves as the plane pair of the out-projection's A operand in 16-byte stores.
 // Matrix cycles: 192 MFMAs of 32 cycles per wave against 512 of 64 on the fp32 pipe.
+// The grid is one-dimensional: attn::wg_slot gives the two query halves of a (window, head) ids 8 apart, so that they run on
+// one XCD at the same time and K / V come from HBM once (they were fetched twice: 6.9 GB per launch of 2 000 windows).
 // RELPOS (WavLM, REL_POS_BIAS): score(q, key) += gate[q][head] * tab[head][key - q].  The head's table over |key - q| <= 255
 // (511 floats of reltab, 2 KB of static LDS beside the 64 KB of K / V blocks: still two workgroups per CU) is staged once per
 // workgroup; a lane loads its query's gate once and reads tab at (255 - q) + key: the keys of a lane are compile-time
@@ -204,6 +210,75 @@ typedef const __attribute__((address_space(1))) void* attn_glb_ptr;
 // of the two trailing arguments and keeps its code.
 using ah8 = __attribute__((ext_vector_type(8))) _Float16;
 typedef short atr4 __attribute__((__vector_size__(4 * sizeof(short))));
+typedef short atr8 __attribute__((__vector_size__(8 * sizeof(short))));
+typedef unsigned au4 __attribute__((ext_vector_type(4)));
+
+// max(a, b, c): one v_max3_f32
+__device__ __forceinline__ float attn_max3(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
+// lanes 32-63 of a change places with lanes 0-31 of b
+__device__ __forceinline__ void attn_swap32(unsigned& a, unsigned& b) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+}
+
+// The transposed V fragments of one P V step (16 keys x 32 columns, both planes): [hi keys 0-7 | hi keys 8-15 | lo | lo] of
+// the lane's address `a` plus immediates.  The reads stay asm (hipcc 7.2 has no builtin for them) and volatile, which keeps
+// them in program order among themselves and behind the barrier that publishes the staged block; they carry no memory
+// clobber, so the vector work of the next probabilities is free to move across them.  Their results are not valid before
+// attn_v_wait has passed them through: the wait is counted, LEFT = the reads issued after these four (LDS returns in order).
+template <int OFF>
+__device__ __forceinline__ void attn_v_issue(unsigned a, atr4 (&f)[4]) {
+    constexpr int LO = attn::V_LO, ROWS8 = attn::V_ROWS8;                       // bytes: to the lo plane, to 8 keys further
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f[0]) : "v"(a), "n"(OFF));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f[1]) : "v"(a), "n"(OFF + ROWS8));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f[2]) : "v"(a), "n"(OFF + LO));
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f[3]) : "v"(a), "n"(OFF + LO + ROWS8));
+}
+template <int LEFT>
+__device__ __forceinline__ void attn_v_wait(atr4 (&f)[4]) {
+    asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]) : "n"(LEFT));
+}
+
+// One of the 16 steps of a 128-key block B of O^T += V^T P^T: STEP = 4 t4 + 2 s2 + ct is key tile t4 (32 keys), k-step s2 (16
+// keys: elements 8 s2 .. 8 s2 + 7 of the score tile) and column tile ct (32 of the 64 columns).  The probabilities of a k-step
+// are made in front of its first column tile; the fragments of step STEP + 1 are requested before this step waits for its own.
+template <int B, int STEP>
+__device__ __forceinline__ void attn_pv_step(const af32x16 (&sc)[8], float m, float c2, unsigned va, float& sum0, float& sum1,
+                                             unsigned (&ph)[4], unsigned (&pl)[4], atr4 (&vf)[2][4], af32x16& o0, af32x16& o1) {
+    constexpr int t4 = STEP >> 2, s2 = (STEP >> 1) & 1, ct = STEP & 1, kt = 4 * B + t4;
+    if constexpr (ct == 0) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float e0 = attn::exp2_bare(attn::exp2_arg(sc[kt][8 * s2 + 2 * w], m, c2));
+            const float e1 = attn::exp2_bare(attn::exp2_arg(sc[kt][8 * s2 + 2 * w + 1], m, c2));
+            sum0 += e0;
+            sum1 += e1;
+            // (v_ldexp_f32: as multiplies the compiler pairs them into packed-fp32 instructions plus the moves that line their
+            // operands up, which cost more beside MFMAs than they save)
+            attn::split2(__builtin_ldexpf(e0, attn::P_SHIFT), __builtin_ldexpf(e1, attn::P_SHIFT), ph[w], pl[w]);
+        }
+    }
+    if constexpr (STEP + 1 < 16) attn_v_issue<attn::v_step_bytes(STEP + 1)>(((STEP + 1) & 1) ? va ^ 64u : va, vf[(STEP + 1) & 1]);
+    attn_v_wait<(STEP + 1 < 16) ? 4 : 0>(vf[STEP & 1]);
+    // (whole-vector moves: rebuilding the fragments element by element from the 4-element results,
+    // `vh[j] = bit_cast(th0[j])`, came out of hipcc 7.2 as a broadcast of element 0)
+    const ah8 vh = __builtin_bit_cast(ah8, __builtin_shufflevector(vf[STEP & 1][0], vf[STEP & 1][1], 0, 1, 2, 3, 4, 5, 6, 7));
+    const ah8 vl = __builtin_bit_cast(ah8, __builtin_shufflevector(vf[STEP & 1][2], vf[STEP & 1][3], 0, 1, 2, 3, 4, 5, 6, 7));
+    const ah8 p_hi = __builtin_bit_cast(ah8, au4{ph[0], ph[1], ph[2], ph[3]});
+    const ah8 p_lo = __builtin_bit_cast(ah8, au4{pl[0], pl[1], pl[2], pl[3]});
+    af32x16& o = ct == 0 ? o0 : o1;
+    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, p_lo, o, 0, 0, 0);
+    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, p_hi, o, 0, 0, 0);
+    o = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, p_hi, o, 0, 0, 0);
+}
+template <int B, int... STEP>
+__device__ __forceinline__ void attn_pv_block(std::integer_sequence<int, STEP...>, const af32x16 (&sc)[8], float m, float c2, unsigned va,
+                                              float& sum0, float& sum1, unsigned (&ph)[4], unsigned (&pl)[4], atr4 (&vf)[2][4],
+                                              af32x16& o0, af32x16& o1) {
+    attn_v_issue<attn::v_step_bytes(0)>(va, vf[0]);
+    (attn_pv_step<B, STEP>(sc, m, c2, va, sum0, sum1, ph, pl, vf, o0, o1), ...);
+}
 
 template <bool RELPOS>
 __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short* __restrict__ qkvp, int64_t in_plane,
@@ -211,18 +286,21 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short
                                                             int64_t n_rows, const int* __restrict__ Tw,
                                                             const int64_t* __restrict__ row0, int NH, int Hd, float scale,
                                                             const float* __restrict__ row_scale,
-                                                            const float* __restrict__ gate, const float* __restrict__ reltab) {
+                                                            const float* __restrict__ gate, const float* __restrict__ reltab,
+                                                            int64_t pairs, int halves) {
     constexpr int HD = AttnLds::HD, KB = AttnLds::KB, PLANE = AttnLds::PLANE;    // one staged block: 2 planes x 16 KB (halfs)
     extern __shared__ __attribute__((aligned(1024))) unsigned short kvh[];      // two blocks
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
-    const int win = blockIdx.x / NH, head = blockIdx.x - win * NH;
+    const attn::WgSlot slot = attn::wg_slot(blockIdx.x, halves);                 // (window x head, query half)
+    if (slot.pair >= pairs) return;                                             // padding of the last group of 16 ids
+    const int win = (int)(slot.pair / NH), head = (int)(slot.pair - (int64_t)win * NH), qhalf = slot.half;
     const int T = Tw[win];
-    if (blockIdx.y * 128 >= T) return;                                          // (workgroup-uniform)
+    if (qhalf * 128 >= T) return;                                               // (workgroup-uniform)
     const int64_t wrow0 = row0[win];
     const int64_t ld = 3 * (int64_t)Hd;                                         // halfs per row of a plane
     const unsigned short* base = qkvp + wrow0 * ld + (int64_t)head * HD;       // q of this window and head, plane 0
-    const int q0 = blockIdx.y * 128 + wv * 32;
+    const int q0 = qhalf * 128 + wv * 32;
     const int nblk = (T + KB - 1) / KB;                                         // 1 or 2 key blocks
     const float sw = row_scale[wrow0];                                          // the window's power of two
     const float sinv = pow2_inverse(sw);
@@ -231,7 +309,7 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short
     if constexpr (RELPOS) {
         __shared__ float tabs[512];
         for (int i = tid; i < 511; i += 256) tabs[i] = reltab[(int64_t)head * REL_TAB + (REL_SPAN - 256) + i];   // d = i - 255
-        const int q = blockIdx.y * 128 + wv * 32 + l31;                         // <= 255 (published by the first drain())
+        const int q = qhalf * 128 + wv * 32 + l31;                               // <= 255 (published by the first drain())
         qgate = gate[(wrow0 + (q < T ? q : T - 1)) * NH + head];
         qtab = tabs + (255 - q);
     }
@@ -300,121 +378,98 @@ __global__ __launch_bounds__(256, 2) void attn_f16x3_kernel(const unsigned short
         }
     }
     // V0 now sits in buf1 (one key block) or buf0 (two key blocks)
-    // ---- softmax over the keys of this lane's query: key = 32 kt + (e & 3) + 8 (e >> 2) + 4 h ----
+    // ---- softmax over the keys of this lane's query: key = 32 kt + (e & 3) + 8 (e >> 2) + 4 h (attn_softmax.h) ----
+    // Pass 1, the row maximum: on the raw accumulators (sscale > 0 commutes with the max; RELPOS: on the biased scores, which
+    // replace them), two elements per v_max3_f32.  Only a tile that reaches beyond T holds keys to mask: a wave-uniform test.
     const float sscale = scale * sinv * sinv;                                   // q and k both carry s_w
-    float m = -INFINITY;
+    const float c2 = RELPOS ? attn::LOG2E : attn::exp2_scale(sscale);
+    float m0 = -INFINITY, m1 = -INFINITY;
 #pragma unroll
-    for (int kt = 0; kt < 8; ++kt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int key = 32 * kt + (e & 3) + 8 * (e >> 2) + 4 * h;
-            float v;
+    for (int kt = 0; kt < 8; ++kt) {
+        if (kt < 4 * nblk) {                                                    // (wave-uniform)
             if constexpr (RELPOS) {                                             // (the table read is unconditional: in bounds for every key)
-                const float sv = fmaf(qgate, qtab[key], sc[kt][e] * sscale);
-                v = key < T ? sv : -INFINITY;
-            } else {
-                v = key < T ? sc[kt][e] * sscale : -INFINITY;
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    sc[kt][e] = fmaf(qgate, qtab[32 * kt + (e & 3) + 8 * (e >> 2) + 4 * h], sc[kt][e] * sscale);
             }
-            sc[kt][e] = v;
-            m = fmaxf(m, v);
+            if (32 * kt + 32 > T) {
+                asm volatile("; tile with keys to mask");                       // (keeps the branch: as selects this costs every tile two instructions per score)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    if (4 * h >= T - (32 * kt + (e & 3) + 8 * (e >> 2))) sc[kt][e] = -INFINITY;   // key >= T
+            }
+#pragma unroll
+            for (int e = 0; e < 16; e += 4) {
+                m0 = attn_max3(m0, sc[kt][e], sc[kt][e + 1]);
+                m1 = attn_max3(m1, sc[kt][e + 2], sc[kt][e + 3]);
+            }
         }
+    }
+    float m = fmaxf(m0, m1);
     m = fmaxf(m, __shfl_xor(m, 32, 64));
-    float sum = 0.0f;
-#pragma unroll
-    for (int kt = 0; kt < 8; ++kt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const float ev = expf(sc[kt][e] - m);                               // exp(-inf) = 0 for the padded keys
-            sc[kt][e] = ev;
-            sum += ev;
-        }
-    sum += __shfl_xor(sum, 32, 64);
-    const float inv = 16384.0f / sum;                                           // probabilities travel as p * 2^14 (hi + lo)
 
-    // ---- O = P V ----
+    // ---- O^T = V^T P^T, P = 2^((s - m) c2) 2^14 formed tile by tile in front of the MFMAs that consume it ----
+    // (V^T is the A operand, P^T the B operand: the fragments are the ones P V would take, the operands change places, and
+    // the accumulator comes out with the QUERY on the lane, as the scores do: the row sum and its reciprocal stay in-lane, and
+    // a lane's registers hold four consecutive columns of its query's output row.)
     af32x16 o0, o1;
 #pragma unroll
     for (int e = 0; e < 16; ++e) { o0[e] = 0.0f; o1[e] = 0.0f; }
-    // transposed-read addressing: 16-lane group gq covers columns 16 (gq & 1) .. + 15 of a column tile and the 4 keys of lane
-    // half h = gq >> 1; lane 4 q + p of the group supplies row q, columns 4 p .. 4 p + 3
-    const int gq = lane >> 4, li = lane & 15, tq = li >> 2, tp = li & 3;
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-        if (b < nblk) {
-            // V block b: V0 is where the score phase left it, V1 goes to the other buffer while V0 is multiplied
-            unsigned short* v0buf = nblk == 1 ? buf1 : buf0;
-            const unsigned short* cur = b == 0 ? v0buf : (v0buf == buf0 ? buf1 : buf0);
-            if (b == 0 && nblk > 1) stage(2 * Hd, KB, v0buf == buf0 ? buf1 : buf0, true);
-#pragma unroll
-            for (int t4 = 0; t4 < 4; ++t4) {
-                const int kt = 4 * b + t4;
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    ah8 ph, pl;                                                 // A operand: this lane's query, keys of k-step s2
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const float pn = sc[kt][8 * s2 + j] * inv;
-                        const _Float16 hi = (_Float16)pn;
-                        ph[j] = hi;
-                        pl[j] = (_Float16)(pn - (float)hi);
-                    }
-#pragma unroll
-                    for (int ct = 0; ct < 2; ++ct) {
-                        // (volatile asm with a memory clobber: the reads stay behind the barrier that publishes the staged
-                        // block, the wait for the four results is explicit and tied to them)
-                        atr4 th0, th1, tl0, tl1;
-                        {
-                            const int rowa = 32 * t4 + 16 * s2 + 4 * (gq >> 1) + tq, rowb = rowa + 8;      // keys within the staged block
-                            const int cha = (4 * ct + 2 * (gq & 1) + (tp >> 1)) ^ (((rowa >> 1) & 1) << 2);
-                            const int chb = (4 * ct + 2 * (gq & 1) + (tp >> 1)) ^ (((rowb >> 1) & 1) << 2);
-                            const unsigned a0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short*)(cur + rowa * HD + 8 * cha + 4 * (tp & 1));
-                            const unsigned a1 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short*)(cur + rowb * HD + 8 * chb + 4 * (tp & 1));
-                            asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(th0) : "v"(a0) : "memory");
-                            asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(th1) : "v"(a1) : "memory");
-                            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(tl0) : "v"(a0), "n"(2 * PLANE) : "memory");
-                            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(tl1) : "v"(a1), "n"(2 * PLANE) : "memory");
-                            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(th0), "+v"(th1), "+v"(tl0), "+v"(tl1) : : "memory");
-                        }
-                        // (whole-vector moves: rebuilding the fragments element by element from the 4-element results,
-                        // `vh[j] = bit_cast(th0[j])`, came out of hipcc 7.2 as a broadcast of element 0)
-                        typedef short atr8 __attribute__((__vector_size__(8 * sizeof(short))));
-                        const ah8 vh = __builtin_bit_cast(ah8, __builtin_shufflevector(th0, th1, 0, 1, 2, 3, 4, 5, 6, 7));
-                        const ah8 vl = __builtin_bit_cast(ah8, __builtin_shufflevector(tl0, tl1, 0, 1, 2, 3, 4, 5, 6, 7));
-                        if (ct == 0) {
-                            o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh, o0, 0, 0, 0);
-                            o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl, o0, 0, 0, 0);
-                            o0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o0, 0, 0, 0);
-                        } else {
-                            o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, vh, o1, 0, 0, 0);
-                            o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vl, o1, 0, 0, 0);
-                            o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, vh, o1, 0, 0, 0);
-                        }
-                    }
-                }
-            }
-            if (b == 0 && nblk > 1) drain();
-        }
+    float sum0 = 0.0f, sum1 = 0.0f;
+    // transposed-read addressing (attn_softmax.h): the step, the + 8 keys, the plane and the column tile (chunk bit 2:
+    // address ^ 64) are immediates on ONE lane address per block
+    static_assert(attn::V_HD == HD && attn::V_KB == KB, "attn_softmax.h restates the staged block");
+    const unsigned vlane = (unsigned)attn::v_lane_bytes(lane);
+    unsigned short* v0buf = nblk == 1 ? buf1 : buf0;
+    unsigned short* v1buf = nblk == 1 ? buf0 : buf1;
+    unsigned ph[4], pl[4];
+    atr4 vf[2][4];
+    {
+        // V block 0 is where the score phase left it; V1 goes to the other buffer while V0 is multiplied
+        if (nblk > 1) stage(2 * Hd, KB, v1buf, true);
+        const unsigned va = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short*)v0buf + vlane;
+        attn_pv_block<0>(std::make_integer_sequence<int, 16>{}, sc, m, c2, va, sum0, sum1, ph, pl, vf, o0, o1);
     }
-    // C layout: column = lane & 31 (d), row = (e & 3) + 8 (e >> 2) + 4 h (query within the wave's 32).  acc * 2^-14 = o * s_w:
-    // already the out-projection's A operand in the window's scale (|o| <= max |v| of the window, and v * s_w < 2^15).
-    // k16 panels of n_rows rows (gemm_f16x3.h): column head * 64 + 32 u + l31 -> panel 4 head + 2 u + (l31 >> 4), k = l31 & 15
+    if (nblk > 1) {
+        drain();
+        const unsigned va = (unsigned)(uintptr_t)(__attribute__((address_space(3))) const unsigned short*)v1buf + vlane;
+        attn_pv_block<1>(std::make_integer_sequence<int, 16>{}, sc, m, c2, va, sum0, sum1, ph, pl, vf, o0, o1);
+    }
+    float sum = sum0 + sum1;
+    sum += __shfl_xor(sum, 32, 64);
+    const float rinv = 1.0f / (sum * attn::P_SCALE);                            // the normalisation, and the 2^14 of P taken back
+
+    // C layout of O^T: column = lane & 31 (query within the wave's 32), row = (e & 3) + 8 (e >> 2) + 4 h (d within the column
+    // tile).  acc / sum = o * s_w: already the out-projection's A operand in the window's scale (|o| <= max |v| of the window,
+    // and v * s_w < 2^15).  k16 panels of n_rows rows (gemm_f16x3.h): column head * 64 + d -> panel 4 head + (d >> 4),
+    // k = d & 15.  Registers 8 gp .. 8 gp + 7 of tile ct are k = 4 h + {0..3} and 8 + 4 h + {0..3} of panel 2 ct + gp: the
+    // two halves of the wave exchange one of the two groups (v_permlane32_swap), after which lane h holds k = 8 h .. 8 h + 7,
+    // 16 bytes per plane, and a wave instruction writes 32 rows x 32 bytes = 1 KB of a panel without a gap.
+    const int q = q0 + l31;
     const int64_t panel_sz = n_rows * 16;
-    unsigned short* op = planes + ((int64_t)(head * 4) + (l31 >> 4)) * panel_sz + wrow0 * 16 + (l31 & 15);
+    unsigned short* op = planes + (int64_t)(head * 4) * panel_sz + (wrow0 + q) * 16 + attn::store_k0(lane);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int q = q0 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        if (q < T) {
-            unsigned short* d0 = op + (int64_t)q * 16;
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const float x = (u == 0 ? o0[e] : o1[e]) * (1.0f / 16384.0f);
-                unsigned short a2, b2;
-                split2_w(x, a2, b2);
-                d0[2 * u * panel_sz] = a2;
-                d0[plane_stride + 2 * u * panel_sz] = b2;
+        for (int gp = 0; gp < 2; ++gp) {
+            unsigned hi[4], lo[4];                                              // [k = 4 h ..: 2 words][k = 8 + 4 h ..: 2 words]
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const int e = 8 * gp + 2 * w;
+                attn::split2((ct == 0 ? o0[e] : o1[e]) * rinv, (ct == 0 ? o0[e + 1] : o1[e + 1]) * rinv, hi[w], lo[w]);
+            }
+            // lower half keeps k 0..3 and takes k 4..7 from the upper one, which takes k 8..11 and keeps k 12..15
+#pragma unroll
+            for (int w = 0; w < 2; ++w) {
+                attn_swap32(hi[w], hi[w + 2]);
+                attn_swap32(lo[w], lo[w + 2]);
+            }
+            if (q < T) {
+                unsigned short* d0 = op + (int64_t)attn::store_panel(ct, gp) * panel_sz;
+                *reinterpret_cast<uint4*>(d0) = uint4{hi[0], hi[1], hi[2], hi[3]};
+                *reinterpret_cast<uint4*>(d0 + plane_stride) = uint4{lo[0], lo[1], lo[2], lo[3]};
             }
         }
-    }
 }
 
 // one power of two per window for the q / k / v projection's plane output: the bound of the window's rows,
@@ -607,9 +662,11 @@ int Forward::attention_fused() {
     for (const auto& tg : R.tgroups) att_flops += 4.0 * (tg.second - tg.first) * c.NH * (double)R.T6[tg.first] * R.T6[tg.first] * hd;
     ProfScope prof("w2v2_attn_fused", s, att_flops, 0.0);
     RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)attn_f16x3_kernel<RP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)AttnLds::bytes()));
-    hipLaunchKernelGGL(attn_f16x3_kernel<RP>, dim3((unsigned)(n * c.NH), (unsigned)((Tt + 127) / 128)), dim3(256), AttnLds::bytes(), s,
+    const int64_t pairs = (int64_t)n * c.NH;                                    // (window, head); one workgroup per query half of each
+    const int halves = (Tt + 127) / 128;
+    hipLaunchKernelGGL(attn_f16x3_kernel<RP>, dim3((unsigned)attn::grid_size(pairs, halves)), dim3(256), AttnLds::bytes(), s,
                        planes_at(W.qkv), rows * 3 * Hd, planes_at(W.attp), rows * Hd, rows, Tw + (int64_t)6 * n, row0, c.NH, Hd, scale,
-                       ws + W.s_qkv, gate(), reltab());
+                       ws + W.s_qkv, gate(), reltab(), pairs, halves);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
