@@ -7,80 +7,23 @@
 //      BN folded into the weights at load time, k=3 padding handled in the A-tile loader)
 //   -> max_pool1d(2) -> res_block2 (identity shortcut)
 //   -> 2-layer bidirectional LSTM: input projections for all time steps as one GEMM per layer
-//      (N = 8H: both directions), then a persistent recurrent kernel
+//      (N = 8H: both directions), then a persistent recurrent kernel (cnnlstm_lstm.hip)
 //   -> attention pooling (online softmax over time) + dropout(identity) + Linear -> logits[B,2]
 //
-// Recurrent kernel: one workgroup = 16 batch rows of one direction for all T' steps (rows are
-// independent, so there is no inter-workgroup traffic).  H/16 waves; wave w owns hidden units
-// 16w..16w+15 for all four gates, and keeps its slice of W_hh permanently in registers as
-// v_mfma_f32_16x16x4_f32 B-fragments (H registers per lane).  Per step: the accumulators start from
-// the prefetched input projection, h_{t-1} is read from LDS as the A operand, the gate nonlinearity
-// and cell update are lane-local (all four gates of a (row, unit) pair land in the same lane and
-// register index), h_t goes to LDS (double-buffered, one barrier per step) and to HBM.
+// This file: the CNN front (exact fp32, and the fp16-split path with its split / scale kernels), the attention head, the
+// phases of a forward (Fwd, run_forward) and the entry points.  The weight blob and the workspace are laid out in
+// cnnlstm_layout.h.
 #include <algorithm>
 #include <cstdlib>
 #include <string>
 
+#include "cnnlstm_host.h"
 #include "cnnlstm_kernels.h"
 #include "gemm_f32.h"
 #include "gemm_f16x3.h"
 
 namespace rsaf {
 namespace cnnlstm {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-struct Dims {
-    int D, C, H, NC, L, act;
-};
-
-static inline int64_t pad4(int64_t n) { return (n + 3) & ~int64_t(3); }
-
-// ---- weight blob layout (floats); every segment starts 16-byte aligned -----------------------
-struct Layout {
-    int64_t w1, b1, wsc, bsc, w2, b2, w3, b3, w4, b4;
-    int64_t wih[4], bih[4], whh[4];
-    int64_t watt, batt, wfc, bfc, total;
-};
-
-static Layout make_layout(const Dims& d) {
-    Layout L{};
-    int64_t o = 0;
-    auto take = [&](int64_t n) { int64_t s = o; o += pad4(n); return s; };
-    L.w1 = take((int64_t)d.C * 3 * d.D);
-    L.b1 = take(d.C);
-    if (d.D != d.C) { L.wsc = take((int64_t)d.C * d.D); L.bsc = take(d.C); } else { L.wsc = L.bsc = -1; }
-    L.w2 = take((int64_t)d.C * 3 * d.C); L.b2 = take(d.C);
-    L.w3 = take((int64_t)d.C * 3 * d.C); L.b3 = take(d.C);
-    L.w4 = take((int64_t)d.C * 3 * d.C); L.b4 = take(d.C);
-    for (int l = 0; l < d.L; ++l) {
-        const int in = l == 0 ? d.C : 2 * d.H;
-        L.wih[l] = take((int64_t)8 * d.H * in);
-        L.bih[l] = take(8 * d.H);
-        L.whh[l] = take((int64_t)2 * 4 * d.H * d.H);
-    }
-    L.watt = take(2 * d.H); L.batt = take(1);
-    L.wfc = take((int64_t)d.NC * 2 * d.H); L.bfc = take(d.NC);
-    L.total = o;
-    return L;
-}
-
-// what is wrong with the dims, or NULL
-static const char* dims_problem(const Dims& d) {
-    if (!(d.D > 0 && d.D % 4 == 0)) return "input_dim must be a positive multiple of 4";
-    if (!(d.C > 0 && d.C % 4 == 0)) return "cnn_out_channels must be a positive multiple of 4";
-    if (!(d.H == 64 || d.H == 128)) return "lstm_hidden_dim must be 64 or 128 (reference search space)";
-    if (!(d.NC >= 1 && d.NC <= 16)) return "num_classes must be in [1, 16]";
-    if (!(d.L >= 1 && d.L <= 4)) return "lstm_layers must be in [1, 4]";
-    if (!(d.act == ACT_GELU || d.act == ACT_SILU)) return "activation must be gelu (1) or silu (2)";
-    return nullptr;
-}
-
-static int check_dims(const Dims& d) {
-    const char* problem = dims_problem(d);
-    RSAF_CHECK_ARG(!problem, problem);
-    return RSAF_OK;
-}
 
 // ---- max_pool1d(kernel_size=2) over time, channels-last ----------------------------------------
 __global__ __launch_bounds__(256) void pool2_kernel(const float4* __restrict__ x, float4* __restrict__ y,
@@ -95,263 +38,6 @@ __global__ __launch_bounds__(256) void pool2_kernel(const float4* __restrict__ x
         const float4 d = x[(b * T + 2 * t + 1) * C4 + c];
         y[i] = make_float4(fmaxf(a.x, d.x), fmaxf(a.y, d.y), fmaxf(a.z, d.z), fmaxf(a.w, d.w));
     }
-}
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// ---- persistent bidirectional LSTM recurrence ------------------------------------------------------
-// SAVE (training): the post-activation gates overwrite the input projection in place (the lane that read an element
-// is the lane that rewrites it, one step after the read of the next step was issued) and the cell state is kept.
-template <int H, bool SAVE>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_rec_kernel(const float* xproj, const float* __restrict__ whh,
-                                                               float* __restrict__ hout, float* gates_save,
-                                                               float* __restrict__ c_save, int B, int T) {
-    constexpr int LDH = H + 4;
-    constexpr int KG = H / 16;                   // k-groups of 16 (4 MFMA k-steps each)
-    __shared__ __attribute__((aligned(16))) float hbuf[2][16][LDH];
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int w = tid >> 6;
-    const int col = lane & 15;
-    const int q = lane >> 4;
-    const int dir = blockIdx.y;
-    const int b0 = blockIdx.x * 16;
-    const int unit = 16 * w + col;
-
-    // W_hh slice as B fragments: element (g, j) of gate gt holds W[gt*H + unit][16g + 4q + j]
-    float breg[4][KG * 4];
-    const float* wd = whh + (int64_t)dir * 4 * H * H;
-#pragma unroll
-    for (int gt = 0; gt < 4; ++gt)
-#pragma unroll
-        for (int g = 0; g < KG; ++g) {
-            const float4 v = *reinterpret_cast<const float4*>(wd + (int64_t)(gt * H + unit) * H + 16 * g + 4 * q);
-            breg[gt][4 * g + 0] = v.x; breg[gt][4 * g + 1] = v.y;
-            breg[gt][4 * g + 2] = v.z; breg[gt][4 * g + 3] = v.w;
-        }
-    for (int i = tid; i < 2 * 16 * LDH; i += H / 16 * 64) (&hbuf[0][0][0])[i] = 0.0f;
-
-    // rows of this lane in the C/D map: q*4 + r, clamped to the last batch row (copies replicate it bit for bit)
-    int64_t xoff[4], hoff[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + q * 4 + r;
-        const int bc = b < B ? b : B - 1;
-        xoff[r] = (int64_t)bc * T * 8 * H + dir * 4 * H + unit;
-        hoff[r] = (int64_t)bc * T * 2 * H + dir * H + unit;
-    }
-    float cst[4] = {0.f, 0.f, 0.f, 0.f};
-    float xin[4][4];
-    {
-        const int t = dir ? T - 1 : 0;
-#pragma unroll
-        for (int gt = 0; gt < 4; ++gt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xin[gt][r] = xproj[xoff[r] + (int64_t)t * 8 * H + gt * H];
-    }
-    vmem_drain();
-    __syncthreads();
-
-    int cur = 0;
-    for (int s = 0; s < T; ++s) {
-        const int t = dir ? T - 1 - s : s;
-        f32x4 acc[4];
-#pragma unroll
-        for (int gt = 0; gt < 4; ++gt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[gt][r] = xin[gt][r];
-        {                                          // prefetch the next step's input projection (the last step reloads
-            const int tn = s + 1 < T ? (dir ? t - 1 : t + 1) : t;      // its own: the loop body stays branch-free)
-#pragma unroll
-            for (int gt = 0; gt < 4; ++gt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) xin[gt][r] = xproj[xoff[r] + (int64_t)tn * 8 * H + gt * H];
-        }
-#pragma unroll
-        for (int g = 0; g < KG; ++g) {
-            const float4 a4 = *reinterpret_cast<const float4*>(&hbuf[cur][col][16 * g + 4 * q]);
-            const float a[4] = {a4.x, a4.y, a4.z, a4.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int gt = 0; gt < 4; ++gt)
-                    acc[gt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], breg[gt][4 * g + j], acc[gt], 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float ig = sigmoidf_(acc[0][r]);
-            const float fg = sigmoidf_(acc[1][r]);
-            const float gg = tanhf(acc[2][r]);
-            const float og = sigmoidf_(acc[3][r]);
-            cst[r] = fg * cst[r] + ig * gg;
-            const float hv = og * tanhf(cst[r]);
-            hbuf[cur ^ 1][q * 4 + r][unit] = hv;
-            // rows past B are clamped to row B-1 and replicate it bit for bit: their stores rewrite the same values, and
-            // leaving them unconditional keeps the loop branch-free (exact vmcnt bookkeeping, no store drain per step)
-            hout[hoff[r] + (int64_t)t * 2 * H] = hv;
-            if (SAVE) {
-                float* gs = gates_save + xoff[r] + (int64_t)t * 8 * H;
-                gs[0] = ig; gs[H] = fg; gs[2 * H] = gg; gs[3 * H] = og;
-                c_save[hoff[r] + (int64_t)t * 2 * H] = cst[r];
-            }
-        }
-        lds_barrier();
-        cur ^= 1;
-    }
-}
-
-// ---- the same recurrence for small batches: 4 batch rows per workgroup -------------------------------------
-// With a handful of sequences (the reference trains with batches of 4 and 8, src/dl_cv_strategies.py:234,265) the
-// 16-row tile above wastes 3/4 of its MFMA work and leaves the step time at 16 rows' worth.  Here a workgroup owns 4
-// rows of one direction and uses v_mfma_f32_4x4x1_16B_f32 (16 independent 4x4 outer products per instruction): row i
-// of every block is batch row i, the 64 (block, j) columns of wave w are the four gates of hidden units 16w..16w+15
-// (column c = 16*gate + u).  W_hh stays register-resident (H registers per lane: the lane's column over all k), h
-// is broadcast from LDS.  The gate pre-activations of one (row, unit) land in four lanes (one per gate); they are
-// exchanged through a wave-private LDS tile so that lane (q, u) updates cell (row q, unit u).
-// The body is shared by the one-recurrence kernel and the group kernel below: `dir` and `tile` (the 4-row tile of the
-// batch) are what blockIdx.y / blockIdx.x are to the former.
-// HALVES = 2 (the mixed group kernel, H = 64): the workgroup is two such bodies side by side, threads [0, 16 H) and
-// [16 H, 32 H), each on its own half of the LDS buffers; `dir` is then the half's own direction.  Both halves take the
-// same B and T, so they meet at every barrier.
-template <int H, bool SAVE, int HALVES = 1>
-__device__ __forceinline__ void lstm_rec4_body(const float* xproj, const float* __restrict__ whh,
-                                               float* __restrict__ hout, float* gates_save,
-                                               float* __restrict__ c_save, int B, int T, int dir, int tile) {
-    constexpr int LDH = H + 4;
-    constexpr int NW = H / 16;
-    __shared__ __attribute__((aligned(16))) float hbuf_all[HALVES][2][4][LDH];
-    __shared__ float gx_all[HALVES][NW][4][80];     // [wave][row][16*gate + u], row stride 80: conflict-free both ways
-    const int half = HALVES == 1 ? 0 : (int)threadIdx.x / (NW * 64);
-    auto& hbuf = hbuf_all[half];
-    auto& gx = gx_all[half];
-    const int tid = HALVES == 1 ? (int)threadIdx.x : (int)threadIdx.x - half * (NW * 64), lane = tid & 63, w = tid >> 6;
-    const int gq = lane >> 4, u = lane & 15;        // as a column: gate gq of unit u; as a cell owner: row gq of unit u
-    const int b0 = tile * 4;
-    const int unit = 16 * w + u;
-
-    float breg[H];
-    {
-        const float* wr = whh + (int64_t)dir * 4 * H * H + (int64_t)(gq * H + unit) * H;
-#pragma unroll
-        for (int k = 0; k < H; k += 4) {
-            const float4 v = *reinterpret_cast<const float4*>(wr + k);
-            breg[k] = v.x; breg[k + 1] = v.y; breg[k + 2] = v.z; breg[k + 3] = v.w;
-        }
-    }
-    for (int i = tid; i < 2 * 4 * LDH; i += NW * 64) (&hbuf[0][0][0])[i] = 0.0f;
-
-    // as a column: input projections of rows 0..3; as a cell owner: outputs of row gq
-    int64_t xoff[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int bc = min(b0 + r, B - 1);
-        xoff[r] = (int64_t)bc * T * 8 * H + dir * 4 * H + gq * H + unit;
-    }
-    const int bo = min(b0 + gq, B - 1);
-    const int64_t hoff = (int64_t)bo * T * 2 * H + dir * H + unit;
-    const int64_t goff = (int64_t)bo * T * 8 * H + dir * 4 * H + unit;
-    const int arow = lane & 3;                      // A operand: lane 4*blk + i carries batch row i
-    const float ya = gq == 2 ? 2.0f : 1.0f, yb = gq == 2 ? -2.0f : -1.0f, yc = gq == 2 ? -1.0f : 0.0f;
-    float cst = 0.f;
-    float xin[4];
-    {
-        const int t = dir ? T - 1 : 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xin[r] = xproj[xoff[r] + (int64_t)t * 8 * H];
-    }
-    vmem_drain();
-    __syncthreads();
-
-    int cur = 0;
-    for (int s = 0; s < T; ++s) {
-        const int t = dir ? T - 1 - s : s;
-        f32x4 acc[4];
-        acc[0] = f32x4{xin[0], xin[1], xin[2], xin[3]};
-#pragma unroll
-        for (int a = 1; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-        {
-            const int tn = s + 1 < T ? (dir ? t - 1 : t + 1) : t;      // branch-free: the last step reloads its own row
-#pragma unroll
-            for (int r = 0; r < 4; ++r) xin[r] = xproj[xoff[r] + (int64_t)tn * 8 * H];
-        }
-        // h in batches of 8 float4 (32 k), the next batch in flight while this one feeds the matrix pipe
-        float4 ab[2][8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ab[0][j] = *reinterpret_cast<const float4*>(&hbuf[cur][arow][4 * j]);
-#pragma unroll
-        for (int kb = 0; kb < H / 32; ++kb) {
-            if (kb + 1 < H / 32) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    ab[(kb + 1) & 1][j] = *reinterpret_cast<const float4*>(&hbuf[cur][arow][32 * (kb + 1) + 4 * j]);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 a4 = ab[kb & 1][j];
-                const int k = 32 * kb + 4 * j;
-                acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.x, breg[k + 0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.y, breg[k + 1], acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.z, breg[k + 2], acc[2], 0, 0, 0);
-                acc[3] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.w, breg[k + 3], acc[3], 0, 0, 0);
-            }
-        }
-        // gate nonlinearity in the column's lane (one gate type per lane: y = ya / (1 + exp(yb * x)) + yc is the
-        // logistic function for i, f, o and tanh for g), then the 4x4 exchange through the wave's LDS tile
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float pre = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
-            gx[w][r][lane] = ya * __builtin_amdgcn_rcpf(1.0f + __expf(yb * pre)) + yc;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const float ig = gx[w][gq][u], fg = gx[w][gq][16 + u], gg = gx[w][gq][32 + u], og = gx[w][gq][48 + u];
-        cst = fg * cst + ig * gg;
-        const float hv = og * (2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * cst)) - 1.0f);
-        hbuf[cur ^ 1][gq][unit] = hv;
-        hout[hoff + (int64_t)t * 2 * H] = hv;          // rows past B replicate row B-1 (see lstm_rec_kernel)
-        if (SAVE) {
-            float* gs = gates_save + goff + (int64_t)t * 8 * H;
-            gs[0] = ig; gs[H] = fg; gs[2 * H] = gg; gs[3 * H] = og;
-            c_save[hoff + (int64_t)t * 2 * H] = cst;
-        }
-        lds_barrier();
-        cur ^= 1;
-    }
-}
-
-template <int H, bool SAVE>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_kernel(const float* xproj, const float* __restrict__ whh,
-                                                                float* __restrict__ hout, float* gates_save,
-                                                                float* __restrict__ c_save, int B, int T) {
-    lstm_rec4_body<H, SAVE>(xproj, whh, hout, gates_save, c_save, B, T, blockIdx.y, blockIdx.x);
-}
-
-// Several independent recurrences (same H; own weights, own B and T) in one launch: grid (max tiles, 2, K), blockIdx.z
-// selects the descriptor.  The descriptors are kernel arguments (wave-uniform: they load through scalar registers), so
-// a launch needs no device table and no copy.  A workgroup whose tile lies beyond its recurrence's batch leaves before
-// it touches LDS or a barrier; the others loop over their own T.
-template <int H, bool SAVE>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_rec4_group_kernel(const LstmRecGroup g) {
-    const LstmRecItem& it = g.item[blockIdx.z];
-    if ((int)blockIdx.x * 4 >= it.B) return;
-    lstm_rec4_body<H, SAVE>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, blockIdx.y, blockIdx.x);
-}
-
-// Recurrences of different H in one launch (LstmRecMixedItem, cnnlstm_kernels.h): grid (max tiles, 2, K), 512 threads.  Every
-// exit below is taken by the whole workgroup (the descriptor and the block index are uniform) and comes before the first
-// LDS access or barrier; a workgroup that enters a body runs all eight waves through every barrier of its loop.
-template <bool SAVE>
-__global__ __launch_bounds__(512) void lstm_rec4_group_mixed_kernel(const LstmRecMixedGroup g) {
-    const LstmRecMixedItem& m = g.item[blockIdx.z];
-    const LstmRecItem& it = m.rec;
-    if ((int)blockIdx.x * 4 >= it.B) return;
-    if (m.H == 128) {
-        lstm_rec4_body<128, SAVE>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, blockIdx.y, blockIdx.x);
-        return;
-    }
-    if (blockIdx.y != 0) return;                       // H = 64: the blockIdx.y == 0 workgroup runs both directions
-    const int dir = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
-    lstm_rec4_body<64, SAVE, 2>(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, dir, blockIdx.x);
 }
 
 // ---- attention pooling (softmax over time) + final Linear -----------------------------------------
@@ -445,98 +131,21 @@ __global__ __launch_bounds__(256) void attnpool_fc_group_mixed_kernel(const Attn
 
 }  // namespace cnnlstm
 
-int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* gates_save, float* c_save, int B, int T,
-                    int H, hipStream_t s) {
-    using namespace cnnlstm;
-    RSAF_CHECK_ARG(H == 64 || H == 128, "lstm_hidden_dim must be 64 or 128");
-    RSAF_CHECK_ARG((gates_save == nullptr) == (c_save == nullptr), "gates_save and c_save go together");
-    ProfScope prof("lstm_recurrent", s, 2.0 * B * T * 2.0 * 4 * H * H, 0.0);
-    // 4-row workgroups while they still fit the chip about twice over; the 16-row tile beyond (same pipe time for 4x the rows)
-    const bool small = B <= lstm_small_max();
-    dim3 grid(small ? (B + 3) / 4 : (B + 15) / 16, 2);
-#define RSAF_LSTM_LAUNCH(KERNEL, HH, SV) \
-    hipLaunchKernelGGL((KERNEL<HH, SV>), grid, dim3(HH / 16 * 64), 0, s, xproj, whh, hout, gates_save, c_save, B, T)
-    if (small) {
-        if (gates_save) { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec4_kernel, 128, true); else RSAF_LSTM_LAUNCH(lstm_rec4_kernel, 64, true); }
-        else { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec4_kernel, 128, false); else RSAF_LSTM_LAUNCH(lstm_rec4_kernel, 64, false); }
-    } else {
-        if (gates_save) { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec_kernel, 128, true); else RSAF_LSTM_LAUNCH(lstm_rec_kernel, 64, true); }
-        else { if (H == 128) RSAF_LSTM_LAUNCH(lstm_rec_kernel, 128, false); else RSAF_LSTM_LAUNCH(lstm_rec_kernel, 64, false); }
-    }
-#undef RSAF_LSTM_LAUNCH
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
+void launch_pool2(const float* x, float* y, int B, int T, int Tp, int C, int blocks, hipStream_t s) {
+    hipLaunchKernelGGL(cnnlstm::pool2_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(x),
+                       reinterpret_cast<float4*>(y), B, T, Tp, C / 4);
 }
 
-int lstm_small_max() {
-    static const int v = [] { const char* e = getenv("RSAF_LSTM_SMALL_MAX"); return e ? atoi(e) : 1024; }();
-    return v;
-}
-
-int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s) {
-    using namespace cnnlstm;
-    RSAF_CHECK_ARG(H == 64 || H == 128, "lstm_hidden_dim must be 64 or 128");
-    RSAF_CHECK_ARG(items && K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "a group holds 1 to 16 recurrences");
-    LstmRecGroup g{};
-    const bool save = items[0].gates_save != nullptr;
-    int tiles = 0;
-    double flops = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const LstmRecItem& it = items[k];
-        RSAF_CHECK_ARG(it.B >= 1 && it.B <= lstm_small_max() && it.T >= 1, "a grouped recurrence runs on the 4-row tiles");
-        RSAF_CHECK_ARG((it.gates_save != nullptr) == save && (it.c_save != nullptr) == save,
-                       "gates_save and c_save go together, for all recurrences of a group or for none");
-        g.item[k] = it;
-        tiles = std::max(tiles, (it.B + 3) / 4);
-        flops += 2.0 * it.B * it.T * 2.0 * 4 * H * H;
-    }
-    ProfScope prof("lstm_recurrent", s, flops, 0.0);
-    dim3 grid(tiles, 2, K);
-#define RSAF_LSTM_LAUNCH(HH, SV) hipLaunchKernelGGL((lstm_rec4_group_kernel<HH, SV>), grid, dim3(HH / 16 * 64), 0, s, g)
-    if (save) { if (H == 128) RSAF_LSTM_LAUNCH(128, true); else RSAF_LSTM_LAUNCH(64, true); }
-    else { if (H == 128) RSAF_LSTM_LAUNCH(128, false); else RSAF_LSTM_LAUNCH(64, false); }
-#undef RSAF_LSTM_LAUNCH
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-int launch_lstm_rec_group_mixed(const LstmRecMixedItem* items, int K, hipStream_t s) {
-    using namespace cnnlstm;
-    RSAF_CHECK_ARG(items && K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX, "a group holds 1 to 16 recurrences");
-    LstmRecMixedGroup g{};
-    const bool save = items[0].rec.gates_save != nullptr;
-    int tiles = 0;
-    double flops = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const LstmRecItem& it = items[k].rec;
-        const int H = items[k].H;
-        RSAF_CHECK_ARG(H == 64 || H == 128, "lstm_hidden_dim must be 64 or 128");
-        RSAF_CHECK_ARG(it.B >= 1 && it.B <= lstm_small_max() && it.T >= 1, "a grouped recurrence runs on the 4-row tiles");
-        RSAF_CHECK_ARG((it.gates_save != nullptr) == save && (it.c_save != nullptr) == save,
-                       "gates_save and c_save go together, for all recurrences of a group or for none");
-        g.item[k] = items[k];
-        tiles = std::max(tiles, (it.B + 3) / 4);
-        flops += 2.0 * it.B * it.T * 2.0 * 4 * H * H;
-    }
-    ProfScope prof("lstm_recurrent", s, flops, 0.0);
-    dim3 grid(tiles, 2, K);
-    if (save) hipLaunchKernelGGL(lstm_rec4_group_mixed_kernel<true>, grid, dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(lstm_rec4_group_mixed_kernel<false>, grid, dim3(512), 0, s, g);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-namespace cnnlstm {
-
-static int conv3(const float* x, const float* wk, const float* bias, const float* R, int64_t ldr, int64_t sR,
-                 float* y, int B, int T, int Cin, int Cout, int act, hipStream_t s) {
+int conv3(const float* x, const float* wk, const float* bias, const float* R, int64_t ldr, int64_t sR, float* y, int B, int T,
+          int Cin, int Cout, int act, hipStream_t s, const char* tag) {
     GemmParams p = gemm_params_plain(x - Cin, wk, y, T, Cout, 3 * Cin, Cin, 3 * Cin, Cout);
     p.bias = bias; p.R = R; p.ldr = ldr; p.sR1 = sR;
     p.nz = B; p.nz2 = 1; p.sA1 = (int64_t)T * Cin; p.sC1 = (int64_t)T * Cout;
     p.a_pad_k = Cin; p.act = act;
-    return launch_gemm_f32(p, s, "cnn_conv_gemm");
+    return launch_gemm_f32(p, s, tag);
 }
 
+namespace cnnlstm {
 
 static int tap_copy(float* dst, const float* src, int64_t n, hipStream_t s) {
     if (dst) RSAF_CHECK_HIP(hipMemcpyAsync(dst, src, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -688,41 +297,6 @@ __global__ __launch_bounds__(256) void zero_pad_rows_kernel(unsigned short* __re
     }
 }
 
-// widths the fp16-split GEMM takes (K and N multiples of 16); anything else (test geometries) stays on the exact-fp32 MFMA
-static bool use_f16x3(int input_dim, int channels) {
-    return input_dim % 16 == 0 && channels % 16 == 0;
-}
-
-struct F16Ws {          // float offsets into the workspace behind the fp32 buffers
-    int64_t xp, c1p, poolp, c3p, c4p, hp, wp[5], ws[5], wih_p[4], wih_s[4], stat, amax, scale, one, total;
-};
-constexpr int CNN_NSTAT = 5 + 5 + 4;     // weight matrices w1 wsc w2 w3 w4, their biases, wih[l]
-constexpr int CNN_NAMAX = 6, CNN_NSCALE = 6;
-
-static F16Ws make_f16_ws(const Dims& d, int B, int T) {
-    F16Ws w{};
-    int64_t o = 0;
-    auto take = [&](int64_t k) { int64_t s = o; o += pad4(k); return s; };
-    const int Tp = T / 2;
-    w.xp = take((int64_t)B * (T + 2) * d.D);
-    w.c1p = take((int64_t)B * (T + 2) * d.C);
-    w.poolp = take((int64_t)B * (Tp + 2) * d.C);
-    w.c3p = take((int64_t)B * (Tp + 2) * d.C);
-    w.c4p = take((int64_t)B * Tp * d.C);
-    w.hp = take((int64_t)B * Tp * 2 * d.H);
-    const int64_t wsz[5] = {(int64_t)d.C * 3 * d.D, (int64_t)d.C * d.D, (int64_t)d.C * 3 * d.C, (int64_t)d.C * 3 * d.C, (int64_t)d.C * 3 * d.C};
-    for (int i = 0; i < 5; ++i) { w.wp[i] = take(wsz[i]); w.ws[i] = take(d.C); }
-    for (int l = 0; l < d.L; ++l) { w.wih_p[l] = take((int64_t)8 * d.H * (l == 0 ? d.C : 2 * d.H)); w.wih_s[l] = take(8 * d.H); }
-    w.stat = take(2 * CNN_NSTAT);
-    w.amax = take((int64_t)CNN_NAMAX * B);
-    w.scale = take((int64_t)CNN_NSCALE * B);
-    w.one = take(4);
-    w.total = o;
-    return w;
-}
-
-#define TRY(expr) do { int _rc = (expr); if (_rc) return _rc; } while (0)
-
 // ---- one forward, cut at its recurrences into phases -------------------------------------------------------------------
 //   prep_weights (f16x3 path: the weights as plane pairs, once per distinct blob) | front (CNN + layer-0 input projection)
 //   | per layer: recurrence, inproj of the next layer | head.
@@ -735,7 +309,8 @@ struct Fwd {
     const float* W;
     float* logits;
     float *res1_out, *res2_out, *lstm_out, *pooled_out;     // stage taps (rsaf_cnnlstm_forward_stages), else NULL
-    float *bufA, *bufB, *bufC, *xproj, *seq0, *seq1;        // fp32 buffers of the workspace
+    float *bufA, *bufB, *bufC, *xproj, *seq0, *seq1;        // fp32 buffers of the workspace (InferWs)
+    int64_t ws_floats;                                      // what the forward uses of it
     // f16x3 path: own activation planes, amax and scale | the weight planes, row scales, statistics and `one`, which live
     // in this item's workspace (prep) or in that of the first item of the group that carries the same `weights`
     bool f16, prep;
@@ -745,15 +320,7 @@ struct Fwd {
     float* lout;                    // output buffer of the next recurrence
 };
 
-enum { AX = 0, ASC = 1, AC1 = 2, AC2 = 3, AC3 = 4, AC4 = 5 };   // amax [6][B]: x, shortcut, conv1, conv2, conv3, conv4
-enum { SX = 0, SC1 = 1, SPOOL = 2, SC3 = 3, SC4 = 4 };          // scale [6][B]: x, conv1, pooled, conv3, conv4, (spare)
-
 static uint16_t* planes_at(float* base, int64_t off) { return reinterpret_cast<uint16_t*>(base + off); }
-
-static int fail(int code, const char* who, int idx, const std::string& msg) {
-    set_error(std::string(who) + ": " + (idx >= 0 ? "item " + std::to_string(idx) + ": " : std::string()) + msg);
-    return code;
-}
 
 // argument checks of one forward (idx < 0: the single entries, whose messages carry no item) and its buffers; `short_code`:
 // what a workspace below the item's need returns
@@ -763,35 +330,53 @@ static int check_item(const Dims& d, const float* x, int B, int T, const float* 
     if (!(T >= 2)) return fail(RSAF_ERR_ARG, who, idx, "sequence length must be >= 2 (max_pool1d(2) of the reference needs it)");
     if (!((int64_t)B * (T / 2) <= 0x7fffffffLL)) return fail(RSAF_ERR_ARG, who, idx, "B*T too large");
     if (!(x && weights && workspace && logits)) return fail(RSAF_ERR_ARG, who, idx, "NULL pointer");
-    if (workspace_bytes < rsaf_cnnlstm_workspace_bytes(B, T, d.D, d.C, d.H, d.L)) return fail(short_code, who, idx, short_code == RSAF_ERR_WORKSPACE ? "workspace too small" : "workspace too small for this item's architecture");
+    const InferWs w = make_infer_ws(d, B, T);
+    if (workspace_bytes < w.total * (int64_t)sizeof(float)) return fail(short_code, who, idx, short_code == RSAF_ERR_WORKSPACE ? "workspace too small" : "workspace too small for this item's architecture");
     *f = Fwd{};
     f->d = d; f->L = make_layout(d);
     f->x = x; f->B = B; f->T = T; f->W = weights; f->logits = logits;
-    const int Tp = T / 2;
     float* ws = static_cast<float*>(workspace);
-    const int64_t conv = pad4((int64_t)B * T * d.C);
-    f->bufA = ws;
-    f->bufB = ws + conv;
-    f->bufC = ws + 2 * conv;
-    f->xproj = ws + 3 * conv;
-    f->seq0 = f->xproj + pad4((int64_t)B * Tp * 8 * d.H);
-    f->seq1 = f->seq0 + pad4((int64_t)B * Tp * 2 * d.H);
-    f->f16 = use_f16x3(d.D, d.C);
+    f->bufA = ws + w.bufA; f->bufB = ws + w.bufB; f->bufC = ws + w.bufC;
+    f->xproj = ws + w.xproj; f->seq0 = ws + w.seq0; f->seq1 = ws + w.seq1;
+    f->ws_floats = w.total;
+    f->f16 = w.f16;
     if (f->f16) {
-        f->f16base = f->seq1 + pad4((int64_t)B * Tp * 2 * d.H);
-        f->F = make_f16_ws(d, B, T);
+        f->f16base = ws + w.f16base;
+        f->F = w.F;
         f->prep = true; f->wbase = f->f16base; f->WF = f->F;
     }
     return RSAF_OK;
 }
 
-static bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
-    const char *p = static_cast<const char*>(a), *q = static_cast<const char*>(b);
-    return p < q + nb && q < p + na;
+// no two items of a group overlapping in what the forward writes, and items that share `weights` sharing an architecture
+static int check_overlaps(const rsaf_cnnlstm_forward_item* items, const Fwd* fs, int K, const char* who) {
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const rsaf_cnnlstm_forward_item &a = items[j], &b = items[k];
+            const int NC = fs[k].d.NC;
+            const char* what = overlap(static_cast<const float*>(a.workspace), fs[j].ws_floats, static_cast<const float*>(b.workspace),
+                                       fs[k].ws_floats) ? "workspace"
+                               : overlap(a.logits, (int64_t)a.B * NC, b.logits, (int64_t)b.B * NC) ? "logits" : nullptr;
+            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
+            const Dims &p = fs[j].d, &q = fs[k].d;
+            if (a.weights == b.weights && !(p.C == q.C && p.H == q.H && p.act == q.act))
+                return fail(RSAF_ERR_ARG, who, k, "shares `weights` with item " + std::to_string(j) + " but not its architecture");
+        }
+    return RSAF_OK;
 }
 
-// weights -> plane pairs in k16 panels with their row scales; statistics {max row norm, max |element|}: matrix i at slot i,
-// its bias at slot 5 + i, wih[l] at slot 10 + l.  A pure function of the blob.
+// weight preparation once per distinct blob: later items read the planes, scales and statistics of the first one
+static void share_weight_prep(Fwd* fs, int K) {
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j)
+            if (fs[k].f16 && fs[j].prep && fs[j].W == fs[k].W) {
+                fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
+                break;
+            }
+}
+
+// weights -> plane pairs in k16 panels with their row scales; statistics {max row norm, max |element|} at the slots stat_w,
+// stat_b and stat_wih of cnnlstm_layout.h.  A pure function of the blob.
 static int prep_weights(const Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
     const int D = d.D, C = d.C, H = d.H;
     const float* W = f.W;
@@ -804,13 +389,13 @@ static int prep_weights(const Fwd& f, const Dims& d, const Layout& L, hipStream_
     const int wk[5] = {3 * D, D, 3 * C, 3 * C, 3 * C};
     for (int i = 0; i < 5; ++i) {
         if (woff[i] < 0) continue;                                          // no 1x1 shortcut when D == C
-        TRY(launch_f16x2_row_scales(W + woff[i], C, wk[i], wk[i], base + F.ws[i], nullptr, stat + 2 * i, s));
+        TRY(launch_f16x2_row_scales(W + woff[i], C, wk[i], wk[i], base + F.ws[i], nullptr, stat + 2 * stat_w(i), s));
         TRY(launch_split_f16x2(W + woff[i], C, wk[i], wk[i], base + F.ws[i], 1, planes_at(base, F.wp[i]), (int64_t)C * wk[i], 1, s));
-        TRY(launch_f16x2_row_scales(W + boff[i], 1, C, C, one, nullptr, stat + 2 * (5 + i), s));
+        TRY(launch_f16x2_row_scales(W + boff[i], 1, C, C, one, nullptr, stat + 2 * stat_b(i), s));
     }
     for (int l = 0; l < d.L; ++l) {
         const int in = l == 0 ? C : 2 * H;
-        TRY(launch_f16x2_row_scales(W + L.wih[l], 8 * H, in, in, base + F.wih_s[l], nullptr, stat + 2 * (10 + l), s));
+        TRY(launch_f16x2_row_scales(W + L.wih[l], 8 * H, in, in, base + F.wih_s[l], nullptr, stat + 2 * stat_wih(l), s));
         TRY(launch_split_f16x2(W + L.wih[l], 8 * H, in, in, base + F.wih_s[l], 1, planes_at(base, F.wih_p[l]), (int64_t)8 * H * in, 1, s));
     }
     RSAF_CHECK_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(one), 0x46800000, 1, s));   // 16384.0f: |h| < 1 for every LSTM output
@@ -846,6 +431,22 @@ static int inproj(Fwd& f, const Dims& d, const Layout& L, int l, hipStream_t s) 
     return launch_gemm_f16x3(p, s, "lstm_inproj_gemm");
 }
 
+// one residual block with both convolutions on the exact-fp32 MFMA GEMM (src/models.py:64-76): h = act(conv3(x)) -> bufA,
+// the 1x1 shortcut -> bufB (wsc == NULL: the identity, x itself), y = act(conv3(h) + shortcut)
+static int resblock_f32(const float* x, int B, int T, int D, int C, int act, const float* w1, const float* b1, const float* wsc,
+                        const float* bsc, const float* w2, const float* b2, float* bufA, float* bufB, float* y, hipStream_t s) {
+    TRY(conv3(x, w1, b1, nullptr, 0, 0, bufA, B, T, D, C, act, s, "cnn_conv_gemm"));
+    const float* sc = x;
+    int64_t ldsc = D;
+    if (wsc) {
+        GemmParams p = gemm_params_plain(x, wsc, bufB, T, C, D, D, D, C);
+        p.bias = bsc; p.nz = B; p.sA1 = (int64_t)T * D; p.sC1 = (int64_t)T * C;
+        TRY(launch_gemm_f32(p, s, "cnn_conv_gemm"));
+        sc = bufB; ldsc = C;
+    }
+    return conv3(bufA, w2, b2, sc, ldsc, (int64_t)T * ldsc, y, B, T, C, C, act, s, "cnn_conv_gemm");
+}
+
 // the two residual blocks on the exact-fp32 MFMA GEMM
 static int front_f32(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
     const int B = f.B, T = f.T, D = d.D, C = d.C, Tp = T / 2;
@@ -853,29 +454,20 @@ static int front_f32(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
     const float* W = f.W;
     float *bufA = f.bufA, *bufB = f.bufB, *bufC = f.bufC;
     // res_block1 (src/models.py:64-76, :175)
-    TRY(conv3(x, W + L.w1, W + L.b1, nullptr, 0, 0, bufA, B, T, D, C, d.act, s));
-    const float* sc = x;
-    int64_t ldsc = D;
-    if (D != C) {
-        GemmParams p = gemm_params_plain(x, W + L.wsc, bufB, T, C, D, D, D, C);
-        p.bias = W + L.bsc; p.nz = B; p.sA1 = (int64_t)T * D; p.sC1 = (int64_t)T * C;
-        TRY(launch_gemm_f32(p, s, "cnn_conv_gemm"));
-        sc = bufB; ldsc = C;
-    }
-    TRY(conv3(bufA, W + L.w2, W + L.b2, sc, ldsc, (int64_t)T * ldsc, bufC, B, T, C, C, d.act, s));
+    TRY(resblock_f32(x, B, T, D, C, d.act, W + L.w1, W + L.b1, D != C ? W + L.wsc : nullptr, D != C ? W + L.bsc : nullptr, W + L.w2,
+                     W + L.b2, bufA, bufB, bufC, s));
     TRY(tap_copy(f.res1_out, bufC, (int64_t)B * T * C, s));
     // max_pool1d(2) (:177)
     {
         const int64_t n4 = (int64_t)B * Tp * (C / 4);
         const int blocks = (int)std::min<int64_t>((n4 + 255) / 256, 256 * 16);
         ProfScope prof("cnn_pool2", s, 0.0, (double)B * T * C * 4 * 1.5);
-        hipLaunchKernelGGL(pool2_kernel, dim3(blocks), dim3(256), 0, s, reinterpret_cast<const float4*>(bufC),
-                           reinterpret_cast<float4*>(bufA), B, T, Tp, C / 4);
+        launch_pool2(bufC, bufA, B, T, Tp, C, blocks, s);
         RSAF_CHECK_HIP(hipGetLastError());
     }
     // res_block2, identity shortcut (:178)
-    TRY(conv3(bufA, W + L.w3, W + L.b3, nullptr, 0, 0, bufB, B, Tp, C, C, d.act, s));
-    TRY(conv3(bufB, W + L.w4, W + L.b4, bufA, C, (int64_t)Tp * C, bufC, B, Tp, C, C, d.act, s));
+    TRY(conv3(bufA, W + L.w3, W + L.b3, nullptr, 0, 0, bufB, B, Tp, C, C, d.act, s, "cnn_conv_gemm"));
+    TRY(conv3(bufB, W + L.w4, W + L.b4, bufA, C, (int64_t)Tp * C, bufC, B, Tp, C, C, d.act, s, "cnn_conv_gemm"));
     return tap_copy(f.res2_out, bufC, (int64_t)B * Tp * C, s);
 }
 
@@ -889,7 +481,7 @@ static int front_f16x3(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
     const F16Ws& F = f.F;
     const F16Ws& WF = f.WF;
     auto planes = [&](int64_t off) { return planes_at(f16base, off); };
-    const unsigned* stat = reinterpret_cast<const unsigned*>(f.wbase + WF.stat);   // [CNN_NSTAT][2], see prep_weights
+    const unsigned* stat = reinterpret_cast<const unsigned*>(f.wbase + WF.stat);   // [CNN_NSTAT][2], slots stat_w / stat_b
     unsigned* amax = reinterpret_cast<unsigned*>(f16base + F.amax);
     float* scale = f16base + F.scale;
     RSAF_CHECK_HIP(hipMemsetAsync(amax, 0, sizeof(unsigned) * CNN_NAMAX * B, s));
@@ -945,18 +537,18 @@ static int front_f16x3(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
         RSAF_CHECK_HIP(hipGetLastError());
     }
     // res_block1 (src/models.py:64-76, :175): conv1 -> planes, shortcut -> fp32, conv2 (+ shortcut) -> fp32
-    cnn_scale(AX, -1, 0, 5, sqrtf((float)(3 * D)) * 1.00001f, SC1);
+    cnn_scale(AX, -1, stat_w(W1), stat_b(W1), sqrtf((float)(3 * D)) * 1.00001f, SC1);
     hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(64), dim3(256), 0, s, planes(F.c1p), pl_c, B, T, C / 8);
     a_panels = x_panels ? D / 16 : 0;
-    TRY(gemm(planes(F.xp), pl_x, T + 2, 0, D, SX, 0, T, C, 3 * D, nullptr, planes(F.c1p), pl_c, T + 2, 1, SC1, W + L.b1, nullptr,
+    TRY(gemm(planes(F.xp), pl_x, T + 2, 0, D, SX, W1, T, C, 3 * D, nullptr, planes(F.c1p), pl_c, T + 2, 1, SC1, W + L.b1, nullptr,
              d.act, AC1, "cnn_conv_gemm"));
     const float* sc = x;
     if (D != C) {
-        TRY(gemm(planes(F.xp), pl_x, T + 2, 1, D, SX, 1, T, C, D, bufB, nullptr, 0, 0, 0, -1, W + L.bsc, nullptr, ACT_NONE, ASC, "cnn_conv_gemm"));
+        TRY(gemm(planes(F.xp), pl_x, T + 2, 1, D, SX, WSC, T, C, D, bufB, nullptr, 0, 0, 0, -1, W + L.bsc, nullptr, ACT_NONE, ASC, "cnn_conv_gemm"));
         sc = bufB;
     }
     a_panels = 0;
-    TRY(gemm(planes(F.c1p), pl_c, T + 2, 0, C, SC1, 2, T, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b2, sc, d.act, AC2, "cnn_conv_gemm"));
+    TRY(gemm(planes(F.c1p), pl_c, T + 2, 0, C, SC1, W2, T, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b2, sc, d.act, AC2, "cnn_conv_gemm"));
     TRY(tap_copy(f.res1_out, bufC, (int64_t)B * T * C, s));
     // max_pool1d(2) (:177): pooled fp32 rows (the residual of res_block2) + padded planes; max |pooled| <= max |conv2 output|
     cnn_scale(AC2, -1, -1, -1, 1.0f, SPOOL);
@@ -969,11 +561,11 @@ static int front_f16x3(Fwd& f, const Dims& d, const Layout& L, hipStream_t s) {
         RSAF_CHECK_HIP(hipGetLastError());
     }
     // res_block2, identity shortcut (:178)
-    cnn_scale(AC2, -1, 3, 8, sqrtf((float)(3 * C)) * 1.00001f, SC3);
+    cnn_scale(AC2, -1, stat_w(W3), stat_b(W3), sqrtf((float)(3 * C)) * 1.00001f, SC3);
     hipLaunchKernelGGL(zero_pad_rows_kernel, dim3(64), dim3(256), 0, s, planes(F.c3p), pl_p, B, Tp, C / 8);
-    TRY(gemm(planes(F.poolp), pl_p, Tp + 2, 0, C, SPOOL, 3, Tp, C, 3 * C, nullptr, planes(F.c3p), pl_p, Tp + 2, 1, SC3, W + L.b3, nullptr,
+    TRY(gemm(planes(F.poolp), pl_p, Tp + 2, 0, C, SPOOL, W3, Tp, C, 3 * C, nullptr, planes(F.c3p), pl_p, Tp + 2, 1, SC3, W + L.b3, nullptr,
              d.act, AC3, "cnn_conv_gemm"));
-    TRY(gemm(planes(F.c3p), pl_p, Tp + 2, 0, C, SC3, 4, Tp, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b4, bufA, d.act, AC4, "cnn_conv_gemm"));
+    TRY(gemm(planes(F.c3p), pl_p, Tp + 2, 0, C, SC3, W4, Tp, C, 3 * C, bufC, nullptr, 0, 0, 0, -1, W + L.b4, bufA, d.act, AC4, "cnn_conv_gemm"));
     TRY(tap_copy(f.res2_out, bufC, (int64_t)B * Tp * C, s));
     // conv4's output as the plane pair of the first input projection, under the exact maximum of every sequence
     cnn_scale(AC4, -1, -1, -1, 1.0f, SC4);
@@ -1002,10 +594,17 @@ static AttnPoolItem head_item(const Fwd& f, const Layout& L) {
     return AttnPoolItem{f.lin, f.W + L.watt, f.W + L.batt, f.W + L.wfc, f.W + L.bfc, f.logits, f.pooled_out, f.B, f.T / 2};
 }
 
+static void launch_attnpool(const AttnPoolItem& it, int H, int NC, hipStream_t s) {      // wfc == NULL: pooling only
+    if (H == 128)
+        hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
+                           it.pooled_out, it.T, NC);
+    else
+        hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
+                           it.pooled_out, it.T, NC);
+}
+
 // attention pooling + fc (:187-191): one launch per forward (SINGLE), one for the heads of all of them (GROUPED: one
 // architecture; MIXED: an architecture per item)
-enum { SINGLE = 0, GROUPED = 1, MIXED = 2 };
-
 static int head(const Fwd* fs, int K, int mode, hipStream_t s) {
     const int NC = fs[0].d.NC;
     if (mode == SINGLE) {
@@ -1013,12 +612,7 @@ static int head(const Fwd* fs, int K, int mode, hipStream_t s) {
             const int H = fs[k].d.H;
             const AttnPoolItem it = head_item(fs[k], fs[k].L);
             ProfScope prof("attnpool_fc", s, 0.0, (double)it.B * it.T * 2 * H * 4);
-            if (H == 128)
-                hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
-                                   it.pooled_out, it.T, NC);
-            else
-                hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(it.B), dim3(256), 0, s, it.seq, it.watt, it.batt, it.wfc, it.bfc, it.logits,
-                                   it.pooled_out, it.T, NC);
+            launch_attnpool(it, H, NC, s);
             RSAF_CHECK_HIP(hipGetLastError());
         }
         return RSAF_OK;
@@ -1042,7 +636,8 @@ static int head(const Fwd* fs, int K, int mode, hipStream_t s) {
 }
 
 // GROUPED / MIXED: one launch per layer carries the recurrences of all items whose batch runs on the 4-row kernel (an item
-// above lstm_small_max() has its recurrence launched on its own), and one launch the heads; SINGLE: one launch per item.
+// above lstm_small_max() has its recurrence launched on its own: launch_lstm_rec_layer), and one launch the heads; SINGLE:
+// one launch per item.
 // Every item carries its own dims and layout; only a MIXED call has items that differ in them (never in D, NC or L).
 static int run_forward(Fwd* fs, int K, int mode, hipStream_t s) {
     const int layers = fs[0].d.L;
@@ -1050,19 +645,9 @@ static int run_forward(Fwd* fs, int K, int mode, hipStream_t s) {
         if (fs[k].f16 && fs[k].prep) TRY(prep_weights(fs[k], fs[k].d, fs[k].L, s));
     for (int k = 0; k < K; ++k) TRY(front(fs[k], fs[k].d, fs[k].L, s));
     for (int l = 0; l < layers; ++l) {
-        LstmRecMixedItem small[RSAF_CNNLSTM_GROUP_MAX];
-        int n_small = 0;
-        for (int k = 0; k < K; ++k) {
-            const LstmRecItem it = rec_item(fs[k], fs[k].d, fs[k].L, l);
-            if (mode != SINGLE && it.B <= lstm_small_max()) small[n_small++] = LstmRecMixedItem{it, fs[k].d.H};
-            else TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, nullptr, nullptr, it.B, it.T, fs[k].d.H, s));
-        }
-        if (n_small && mode == MIXED) TRY(launch_lstm_rec_group_mixed(small, n_small, s));
-        else if (n_small) {
-            LstmRecItem same[RSAF_CNNLSTM_GROUP_MAX];
-            for (int k = 0; k < n_small; ++k) same[k] = small[k].rec;
-            TRY(launch_lstm_rec_group(same, n_small, fs[0].d.H, s));
-        }
+        LstmRecMixedItem recs[RSAF_CNNLSTM_GROUP_MAX];
+        for (int k = 0; k < K; ++k) recs[k] = LstmRecMixedItem{rec_item(fs[k], fs[k].d, fs[k].L, l), fs[k].d.H};
+        TRY(launch_lstm_rec_layer(recs, K, mode, false, s));
         for (int k = 0; k < K; ++k) {
             Fwd& f = fs[k];
             f.lin = f.lout;
@@ -1084,14 +669,14 @@ extern "C" {
 
 int64_t rsaf_cnnlstm_weight_floats(int input_dim, int channels, int hidden, int num_classes, int lstm_layers) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
-    if (check_dims(d) != RSAF_OK) return -1;
+    if (check_dims(d, 0) != RSAF_OK) return -1;
     return make_layout(d).total;
 }
 
 int rsaf_cnnlstm_weight_offsets(int input_dim, int channels, int hidden, int num_classes, int lstm_layers,
                                 int64_t* offsets_host, int cap, int* n_host) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, ACT_SILU};
-    int rc = check_dims(d);
+    int rc = check_dims(d, 0);
     if (rc != RSAF_OK) return rc;
     RSAF_CHECK_ARG(offsets_host && n_host, "NULL output");
     const Layout L = make_layout(d);
@@ -1109,23 +694,15 @@ int rsaf_cnnlstm_weight_offsets(int input_dim, int channels, int hidden, int num
 
 int64_t rsaf_cnnlstm_workspace_bytes(int B, int T, int input_dim, int channels, int hidden, int lstm_layers) {
     if (B <= 0 || T < 2) return -1;
-    const int64_t Tp = T / 2;
-    const int64_t conv = pad4((int64_t)B * T * channels);
-    const int64_t xp = pad4((int64_t)B * Tp * 8 * hidden);
-    const int64_t sq = pad4((int64_t)B * Tp * 2 * hidden);
-    int64_t f16 = 0;                                     // plane pairs, scales and statistics of the fp16-split GEMM path
-    if (use_f16x3(input_dim, channels)) {
-        Dims d{input_dim, channels, hidden, 2, lstm_layers, ACT_SILU};
-        f16 = make_f16_ws(d, B, T).total;
-    }
-    return (3 * conv + xp + 2 * sq + f16) * (int64_t)sizeof(float);
+    const Dims d{input_dim, channels, hidden, 2, lstm_layers, ACT_SILU};
+    return make_infer_ws(d, B, T).total * (int64_t)sizeof(float);
 }
 
 static int forward_single(const char* who, const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
                           int lstm_layers, int act, const float* weights, void* workspace, int64_t workspace_bytes, float* logits,
                           float* res1_out, float* res2_out, float* lstm_out, float* pooled_out, rsaf_stream_t stream) {
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
-    TRY(check_dims(d));
+    TRY(check_dims(d, 0));
     if (B == 0) return RSAF_OK;
     Fwd f;
     TRY(check_item(d, x, B, T, weights, workspace, workspace_bytes, logits, who, -1, &f));
@@ -1153,32 +730,17 @@ int rsaf_cnnlstm_forward_group(const rsaf_cnnlstm_forward_item* items_host, int 
     const char* who = __func__;
     Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
     Fwd fs[RSAF_CNNLSTM_GROUP_MAX];
-    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (RSAF_CNNLSTM_GROUP_MAX)");
-    if (!items_host) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    TRY(check_group_args(K, items_host, who, "RSAF_CNNLSTM_GROUP_MAX"));
     // widths the layouts cannot be computed for are refused here; the full check of the dims follows the item checks (it is
     // the same for every item, and the item checks name the item)
-    if (!(input_dim > 0 && channels > 0 && hidden > 0 && lstm_layers >= 1 && lstm_layers <= 4)) return check_dims(d);
+    if (!(input_dim > 0 && channels > 0 && hidden > 0 && lstm_layers >= 1 && lstm_layers <= 4)) return check_dims(d, 0);
     for (int k = 0; k < K; ++k) {
         const rsaf_cnnlstm_forward_item& it = items_host[k];
         TRY(check_item(d, it.x, it.B, it.T, it.weights, it.workspace, it.workspace_bytes, it.logits, who, k, &fs[k]));
     }
-    for (int k = 1; k < K; ++k)
-        for (int j = 0; j < k; ++j) {
-            const rsaf_cnnlstm_forward_item &a = items_host[j], &b = items_host[k];
-            const char* what =
-                overlap(a.workspace, rsaf_cnnlstm_workspace_bytes(a.B, a.T, d.D, d.C, d.H, d.L), b.workspace,
-                        rsaf_cnnlstm_workspace_bytes(b.B, b.T, d.D, d.C, d.H, d.L)) ? "workspace"
-                : overlap(a.logits, (int64_t)a.B * d.NC * 4, b.logits, (int64_t)b.B * d.NC * 4) ? "logits" : nullptr;
-            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
-        }
-    TRY(check_dims(d));
-    // weight preparation once per distinct blob: later items read the planes, scales and statistics of the first one
-    for (int k = 1; k < K; ++k)
-        for (int j = 0; j < k; ++j)
-            if (fs[k].f16 && fs[j].prep && fs[j].W == fs[k].W) {
-                fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
-                break;
-            }
+    TRY(check_overlaps(items_host, fs, K, who));
+    TRY(check_dims(d, 0));
+    share_weight_prep(fs, K);
     return run_forward(fs, K, GROUPED, (hipStream_t)stream);
 }
 
@@ -1186,34 +748,16 @@ int rsaf_cnnlstm_forward_group_mixed(const rsaf_cnnlstm_forward_item* items_host
                                      int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
     const char* who = __func__;
     Fwd fs[RSAF_CNNLSTM_GROUP_MAX];
-    if (!(K >= 1 && K <= RSAF_CNNLSTM_GROUP_MAX)) return fail(RSAF_ERR_ARG, who, -1, "K must be in [1, 16] (RSAF_CNNLSTM_GROUP_MAX)");
-    if (!items_host) return fail(RSAF_ERR_ARG, who, -1, "items_host is NULL");
+    TRY(check_group_args(K, items_host, who, "RSAF_CNNLSTM_GROUP_MAX"));
     if (!arch_host) return fail(RSAF_ERR_ARG, who, -1, "arch_host is NULL");
-    int64_t bytes[RSAF_CNNLSTM_GROUP_MAX];
     for (int k = 0; k < K; ++k) {
         const rsaf_cnnlstm_forward_item& it = items_host[k];
         const Dims d{input_dim, arch_host[k].channels, arch_host[k].hidden, num_classes, lstm_layers, arch_host[k].act};
-        if (const char* problem = dims_problem(d)) return fail(RSAF_ERR_ARG, who, k, problem);
+        if (const char* problem = dims_problem(d, 0)) return fail(RSAF_ERR_ARG, who, k, problem);
         TRY(check_item(d, it.x, it.B, it.T, it.weights, it.workspace, it.workspace_bytes, it.logits, who, k, &fs[k], RSAF_ERR_ARG));
-        bytes[k] = rsaf_cnnlstm_workspace_bytes(it.B, it.T, d.D, d.C, d.H, d.L);
     }
-    for (int k = 1; k < K; ++k)
-        for (int j = 0; j < k; ++j) {
-            const rsaf_cnnlstm_forward_item &a = items_host[j], &b = items_host[k];
-            const char* what = overlap(a.workspace, bytes[j], b.workspace, bytes[k]) ? "workspace"
-                               : overlap(a.logits, (int64_t)a.B * num_classes * 4, b.logits, (int64_t)b.B * num_classes * 4) ? "logits" : nullptr;
-            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
-            const rsaf_cnnlstm_arch &p = arch_host[j], &q = arch_host[k];
-            if (a.weights == b.weights && !(p.channels == q.channels && p.hidden == q.hidden && p.act == q.act))
-                return fail(RSAF_ERR_ARG, who, k, "shares `weights` with item " + std::to_string(j) + " but not its architecture");
-        }
-    // weight preparation once per distinct blob, as in rsaf_cnnlstm_forward_group
-    for (int k = 1; k < K; ++k)
-        for (int j = 0; j < k; ++j)
-            if (fs[k].f16 && fs[j].prep && fs[j].W == fs[k].W) {
-                fs[k].prep = false; fs[k].wbase = fs[j].wbase; fs[k].WF = fs[j].WF;
-                break;
-            }
+    TRY(check_overlaps(items_host, fs, K, who));
+    share_weight_prep(fs, K);
     return run_forward(fs, K, MIXED, (hipStream_t)stream);
 }
 
@@ -1243,18 +787,7 @@ int rsaf_cnn_resblock_forward(const float* x, int B, int T, int in_channels, int
     const int D = in_channels, C = out_channels;
     float* bufA = static_cast<float*>(workspace);
     float* bufB = bufA + pad4((int64_t)B * T * C);
-    int rc = conv3(x, w1, b1, nullptr, 0, 0, bufA, B, T, D, C, act, s);
-    if (rc) return rc;
-    const float* sc = x;
-    int64_t ldsc = D;
-    if (wsc) {
-        GemmParams p = gemm_params_plain(x, wsc, bufB, T, C, D, D, D, C);
-        p.bias = bsc; p.nz = B; p.sA1 = (int64_t)T * D; p.sC1 = (int64_t)T * C;
-        rc = launch_gemm_f32(p, s, "cnn_conv_gemm");
-        if (rc) return rc;
-        sc = bufB; ldsc = C;
-    }
-    return conv3(bufA, w2, b2, sc, ldsc, (int64_t)T * ldsc, y, B, T, C, C, act, s);
+    return resblock_f32(x, B, T, D, C, act, w1, b1, wsc, bsc, w2, b2, bufA, bufB, y, s);
 }
 
 int rsaf_attnpool_forward(const float* seq, int B, int T, int features, const float* watt, const float* batt,
@@ -1265,12 +798,7 @@ int rsaf_attnpool_forward(const float* seq, int B, int T, int features, const fl
     RSAF_CHECK_ARG(seq && watt && batt && pooled, "NULL pointer");
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof("attnpool_fc", s, 0.0, (double)B * T * features * 4);
-    if (features == 256)
-        hipLaunchKernelGGL(attnpool_fc_kernel<4>, dim3(B), dim3(256), 0, s, seq, watt, batt,
-                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, pooled, T, 0);
-    else
-        hipLaunchKernelGGL(attnpool_fc_kernel<2>, dim3(B), dim3(256), 0, s, seq, watt, batt,
-                           (const float*)nullptr, (const float*)nullptr, (float*)nullptr, pooled, T, 0);
+    launch_attnpool(AttnPoolItem{seq, watt, batt, nullptr, nullptr, nullptr, pooled, B, T}, features / 2, 0, s);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }

@@ -1,5 +1,6 @@
-// Kernels of the CNN-LSTM classifier shared by the inference path (cnnlstm.hip) and the training step
-// (cnnlstm_train.hip; its loss and optimizer side is cnnlstm_optim.hip and uses none of these).
+// What the inference path (cnnlstm.hip) and the training step (cnnlstm_train.hip) of the CNN-LSTM classifier call in each
+// other's files and in cnnlstm_lstm.hip, which holds every recurrence kernel: a kernel is launched only from the file that
+// defines it (the loss and optimizer side, cnnlstm_optim.hip, uses none of these).
 #pragma once
 #include "rsaf_common.h"
 
@@ -7,13 +8,10 @@ namespace rsaf {
 
 // Persistent bidirectional LSTM recurrence over xproj[B][T][2][4H] (input projections + bias, gate order i,f,g,o)
 // with whh[2][4H][H]; hout[B][T][2H].  With gates_save/c_save (training) the post-activation gates are stored in the
-// xproj layout (gates_save may alias xproj) and the cell states in the hout layout.
-int launch_lstm_rec(const float* xproj, const float* whh, float* hout, float* gates_save, float* c_save, int B, int T,
-                    int H, hipStream_t s);
-
-// The same for up to RSAF_CNNLSTM_GROUP_MAX independent recurrences of one H (own weights, own B and T) in ONE launch of the
-// 4-row kernel: every B must be <= lstm_small_max(), and all of them save gates / cell states or none does.  The
-// descriptors travel by value in the kernel arguments.
+// xproj layout (gates_save may alias xproj) and the cell states in the hout layout.  Up to RSAF_CNNLSTM_GROUP_MAX independent
+// recurrences (own weights, own B and T) run in ONE launch of the 4-row kernel: every B at or under the threshold, and all
+// of them save gates / cell states or none does.  The descriptors travel by value in the kernel arguments; a mixed group
+// (replicas of different architecture) carries an H per recurrence.
 struct LstmRecItem {
     const float* xproj;
     const float* whh;
@@ -22,28 +20,39 @@ struct LstmRecItem {
     float* c_save;
     int B, T;
 };
-struct LstmRecGroup {
-    LstmRecItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-int launch_lstm_rec_group(const LstmRecItem* items, int K, int H, hipStream_t s);
+struct LstmRecGroup { LstmRecItem item[RSAF_CNNLSTM_GROUP_MAX]; };
+struct LstmRecMixedItem { LstmRecItem rec; int H; };
+struct LstmRecMixedGroup { LstmRecMixedItem item[RSAF_CNNLSTM_GROUP_MAX]; };
 
-// The same for recurrences of different H (mixed groups: replicas of different architecture) in ONE launch of 512-thread
-// workgroups.  An H = 128 item runs as above, grid.y its direction.  The workgroup of an H = 64 item runs BOTH directions of
-// its tile, waves 0-3 direction 0 and waves 4-7 direction 1, each half on LDS buffers of its own: the halves loop over the
-// same T, so all eight waves meet at every barrier, and the grid.y == 1 workgroups of such an item leave whole.  No
-// workgroup ever has some of its waves returned while others wait at a barrier.
-struct LstmRecMixedItem {
-    LstmRecItem rec;
-    int H;
+// The BPTT recurrences in the same forms.  `gates`: the saved post-activation gates, overwritten with the pre-activation gate
+// gradients; cst: the saved cell states; dh: the gradient w.r.t. the layer's output.
+struct LstmBwdItem {
+    float* gates;
+    const float* cst;
+    const float* dh;
+    const float* whh;
+    int B, T;
 };
-struct LstmRecMixedGroup {
-    LstmRecMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-int launch_lstm_rec_group_mixed(const LstmRecMixedItem* items, int K, hipStream_t s);
+struct LstmBwdGroup { LstmBwdItem item[RSAF_CNNLSTM_GROUP_MAX]; };
+struct LstmBwdMixedItem { LstmBwdItem rec; int H; };
+struct LstmBwdMixedGroup { LstmBwdMixedItem item[RSAF_CNNLSTM_GROUP_MAX]; };
 
-// Attention pooling + classifier (the head of the inference forward) of up to RSAF_CNNLSTM_GROUP_MAX independent forwards of
-// one H and one num_classes in ONE launch; the descriptors travel by value in the kernel arguments.  seq [B][T][2H];
-// pooled_out may be NULL.
+// One layer's recurrences of the K forwards / replicas of an entry.  SINGLE: one launch each.  GROUPED (one H), MIXED (an H
+// per item): one launch carries those whose batch runs on the 4-row kernel, behind the own launches of the items above
+// the threshold (RSAF_LSTM_SMALL_MAX).  all_or_none (the training GROUPED entries): any batch above it makes the layer SINGLE for all.
+enum { SINGLE = 0, GROUPED = 1, MIXED = 2 };
+int launch_lstm_rec_layer(const LstmRecMixedItem* items, int K, int mode, bool all_or_none, hipStream_t s);
+int launch_lstm_bwd_layer(const LstmBwdMixedItem* items, int K, int mode, bool all_or_none, hipStream_t s);
+
+// max_pool1d(2) over time, channels-last (cnnlstm.hip); grid, profiler scope and the launch error are the caller's
+void launch_pool2(const float* x, float* y, int B, int T, int Tp, int C, int blocks, hipStream_t s);
+
+// k = 3 / pad = 1 convolution over channels-last sequences on the exact-fp32 GEMM (cnnlstm.hip): y = act(conv(x) + bias + R)
+int conv3(const float* x, const float* wk, const float* bias, const float* R, int64_t ldr, int64_t sR, float* y, int B, int T,
+          int Cin, int Cout, int act, hipStream_t s, const char* tag);
+
+// Attention pooling + classifier, the head of the inference forward, with group forms like the recurrences' (cnnlstm.hip).
+// seq [B][T][2H]; pooled_out may be NULL.
 struct AttnPoolItem {
     const float* seq;
     const float* watt;
@@ -54,20 +63,9 @@ struct AttnPoolItem {
     float* pooled_out;
     int B, T;
 };
-struct AttnPoolGroup {
-    AttnPoolItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-// the heads of forwards of different H (one num_classes) in ONE launch
-struct AttnPoolMixedItem {
-    AttnPoolItem head;
-    int H;
-};
-struct AttnPoolMixedGroup {
-    AttnPoolMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-
-// Largest batch that runs on the 4-row recurrence kernels (environment RSAF_LSTM_SMALL_MAX, read once; default 1 024).
-int lstm_small_max();
+struct AttnPoolGroup { AttnPoolItem item[RSAF_CNNLSTM_GROUP_MAX]; };
+struct AttnPoolMixedItem { AttnPoolItem head; int H; };
+struct AttnPoolMixedGroup { AttnPoolMixedItem item[RSAF_CNNLSTM_GROUP_MAX]; };
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains the vector-memory counter, i.e. waits for
 // the write acknowledgements of the per-step global stores of the recurrences - a few hundred cycles on every time step

@@ -4,7 +4,7 @@
 // the kernel arguments, as the group recurrence kernels take theirs.
 #include <cmath>
 
-#include "cnnlstm_train_layout.h"
+#include "cnnlstm_host.h"
 
 namespace rsaf {
 namespace cnntrain {

@@ -12,89 +12,17 @@
 //   weight grad  dW[M][taps*N] = sum_rows dy[row][M]^T x[row+tap][N]: both operands are transposed into [.][rows]
 //              images (tap shift and sequence boundaries applied while transposing), then an NT GEMM split
 //              along rows into `S` partial products that a second kernel sums in a fixed order (deterministic).
-// The two recurrences are persistent kernels: the forward one of cnnlstm.hip (saving gates and cell states) and
-// lstm_bwd_kernel below (W_hh register-resident as MFMA B fragments with k = gate row, dgates staged in LDS).
+// The two recurrences are the persistent kernels of cnnlstm_lstm.hip: the forward one (saving gates and cell states) and the
+// BPTT one.  This file: the training CNN, head and BatchNorm kernels and the phases of a step; the parameter blob, the saved
+// activations and the scratch are laid out in cnnlstm_layout.h.
 #include <algorithm>
 
+#include "cnnlstm_host.h"
 #include "cnnlstm_kernels.h"
-#include "cnnlstm_train_layout.h"
 #include "gemm_f32.h"
 
 namespace rsaf {
 namespace cnntrain {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-// ---- saved activations -----------------------------------------------------------------------------------
-struct SLayout {
-    int64_t stat;                 // [5][3][C]: mean, biased var, rstd of bn1, shortcut bn, bn2, (block 2) bn1, bn2
-    int64_t y1, ysc, a1d, y2, z1, p, y3, a3d, y4, z2, r2;
-    int64_t gates[4], cst[4], hout[4], hdrop[4];
-    int64_t prob, ctx, total;
-};
-
-static SLayout make_slayout(const Dims& d, int B, int T) {
-    SLayout S{};
-    const int64_t Tp = T / 2, n1 = pad4((int64_t)B * T * d.C), n2 = pad4((int64_t)B * Tp * d.C);
-    int64_t o = 0;
-    auto take = [&](int64_t n) { int64_t s = o; o += pad4(n); return s; };
-    S.stat = take(5 * 3 * d.C);
-    S.y1 = take(n1); S.ysc = d.D != d.C ? take(n1) : -1; S.a1d = take(n1); S.y2 = take(n1); S.z1 = take(n1);
-    S.p = take(n2); S.y3 = take(n2); S.a3d = take(n2); S.y4 = take(n2); S.z2 = take(n2); S.r2 = take(n2);
-    for (int l = 0; l < d.L; ++l) {
-        S.gates[l] = take((int64_t)B * Tp * 8 * d.H);
-        S.cst[l] = take((int64_t)B * Tp * 2 * d.H);
-        S.hout[l] = take((int64_t)B * Tp * 2 * d.H);
-        S.hdrop[l] = l < d.L - 1 ? take((int64_t)B * Tp * 2 * d.H) : -1;
-    }
-    S.prob = take((int64_t)B * Tp); S.ctx = take((int64_t)B * 2 * d.H);
-    S.total = o;
-    return S;
-}
-
-// split of the row dimension of a weight-gradient GEMM
-struct Split { int64_t kc, s, kp; };
-static Split make_split(int64_t rows) {
-    int64_t kc = 1024;
-    while ((rows + kc - 1) / kc > 4096) kc *= 2;
-    Split sp; sp.kc = kc; sp.s = std::max<int64_t>((rows + kc - 1) / kc, 1); sp.kp = sp.s * kc;
-    return sp;
-}
-
-// scratch (floats) shared by forward and backward
-struct WLayout {
-    int64_t bufA, bufB, bufC;           // [B*T][max(C, 2H)] activations / gradients
-    int64_t t1, t2;                     // transposed images [Mmax][kp], [Nmax][kp]
-    int64_t part;                       // split-K partial products
-    int64_t red;                        // column-reduction partials
-    int64_t wflip;                      // tap-flipped transposed conv weights [C][3][C]
-    int64_t small;                      // dctx, dp, per-row partials
-    int64_t total;
-};
-
-static const int RED_PARTS = 256;
-
-static WLayout make_wlayout(const Dims& d, int B, int T) {
-    WLayout W{};
-    const int64_t Tp = T / 2;
-    const int64_t wide = std::max<int64_t>(d.C, 2 * d.H);
-    const int64_t rows = (int64_t)B * T;
-    const Split sp = make_split(rows);
-    int64_t o = 0;
-    auto take = [&](int64_t n) { int64_t s = o; o += pad4(n); return s; };
-    const int64_t nb = std::max<int64_t>((int64_t)B * T * d.C, (int64_t)B * Tp * wide);
-    W.bufA = take(nb); W.bufB = take(nb); W.bufC = take(nb);
-    const int64_t Mmax = std::max<int64_t>(d.C, 8 * d.H);
-    const int64_t Nmax = std::max<int64_t>(std::max<int64_t>(3 * d.D, 3 * d.C), 2 * d.H);
-    W.t1 = take(Mmax * sp.kp); W.t2 = take(Nmax * sp.kp);
-    int64_t mn = std::max<int64_t>((int64_t)d.C * 3 * std::max(d.D, d.C), (int64_t)8 * d.H * std::max(d.C, 2 * d.H));
-    W.part = take(sp.s * mn);
-    W.red = take((int64_t)RED_PARTS * 2 * std::max<int64_t>(d.C, 8 * d.H) * 2);     // doubles
-    W.wflip = take((int64_t)d.C * 3 * d.C);
-    W.small = take(2112 + (int64_t)B * (4 * d.H + 8) + (int64_t)B * Tp + 64);   // BN sums [2][<=1024] | dctx | dwatt, dbatt partials | dp
-    W.total = o;
-    return W;
-}
 
 // ---- activation and its derivative ----------------------------------------------------------------------------
 __device__ __forceinline__ float act_f(float v, int act) {
@@ -279,20 +207,6 @@ __global__ __launch_bounds__(256) void add_kernel(const float4* __restrict__ a, 
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
         const float4 x = a[i], k = b[i];
         out[i] = make_float4(x.x + k.x, x.y + k.y, x.z + k.z, x.w + k.w);
-    }
-}
-
-// max_pool1d(2), channels-last
-__global__ __launch_bounds__(256) void pool2_kernel(const float4* __restrict__ x, float4* __restrict__ y, int B, int T, int Tp, int C4) {
-    const int64_t n = (int64_t)B * Tp * C4;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int c = (int)(i % C4);
-        const int64_t bt = i / C4;
-        const int t = (int)(bt % Tp);
-        const int64_t b = bt / Tp;
-        const float4 a = x[(b * T + 2 * t) * C4 + c];
-        const float4 d = x[(b * T + 2 * t + 1) * C4 + c];
-        y[i] = make_float4(fmaxf(a.x, d.x), fmaxf(a.y, d.y), fmaxf(a.z, d.z), fmaxf(a.w, d.w));
     }
 }
 
@@ -517,274 +431,8 @@ __global__ __launch_bounds__(ATT_WAVES * 64) void attn_bwd_kernel(const float* _
     }
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
-// ---- persistent LSTM backward recurrence (BPTT) ---------------------------------------------------------------------
-// One workgroup = 16 batch rows of one direction; wave w owns hidden units 16w..16w+15.  Walks the time steps in the
-// reverse of the forward order.  Per step, lane-local: dh = dh_out + dh_rec, gate/cell derivatives from the saved
-// post-activation gates and cell states; the pre-activation gate gradients overwrite the saved gates (they are the
-// operand of the weight / input gradients afterwards) and go to LDS as the MFMA A operand of
-//     dh_rec[row][unit] = sum_k dgates[row][k] * W_hh[k][unit],   k over the 4H gate rows,
-// with W_hh register-resident as B fragments (H registers per lane).
-template <int H>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd_kernel(float* gates, const float* __restrict__ cst,
-                                                               const float* __restrict__ dh_out, const float* __restrict__ whh,
-                                                               int B, int T) {
-    constexpr int LDG = 4 * H + 4;
-    constexpr int KG = 4 * H / 16;                  // k-groups of 16 gate rows
-    extern __shared__ __attribute__((aligned(16))) float dgbuf[];     // [2][16][LDG]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, col = lane & 15, q = lane >> 4;
-    const int dir = blockIdx.y, b0 = blockIdx.x * 16, unit = 16 * w + col;
-
-    // B fragments: breg[4g + j] = W_hh[dir][16g + 4q + j][unit]
-    float breg[KG * 4];
-    const float* wd = whh + (int64_t)dir * 4 * H * H;
-#pragma unroll
-    for (int g = 0; g < KG; ++g)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) breg[4 * g + j] = wd[(int64_t)(16 * g + 4 * q + j) * H + unit];
-    for (int i = tid; i < 2 * 16 * LDG; i += H / 16 * 64) dgbuf[i] = 0.0f;
-
-    int brow[4];
-    int64_t goff[4], hoff[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int b = b0 + q * 4 + r;
-        brow[r] = b < B;
-        const int bc = b < B ? b : B - 1;
-        goff[r] = (int64_t)bc * T * 8 * H + dir * 4 * H + unit;
-        hoff[r] = (int64_t)bc * T * 2 * H + dir * H + unit;
-    }
-    float dcc[4] = {0.f, 0.f, 0.f, 0.f};            // dL/dc carried to the previous forward step
-    f32x4 acc[4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-    __syncthreads();
-
-    int cur = 0;
-    for (int s = 0; s < T; ++s) {
-        const int t = dir ? s : T - 1 - s;           // reverse of the forward order
-        const int tprev = dir ? t + 1 : t - 1;       // the step the forward pass ran just before t
-        const bool first = dir ? (t == T - 1) : (t == 0);
-        float* dgw = dgbuf + (cur ^ 1) * 16 * LDG;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const float* gp = gates + goff[r] + (int64_t)t * 8 * H;
-            const float ig = gp[0], fg = gp[H], gg = gp[2 * H], og = gp[3 * H];
-            const float c = cst[hoff[r] + (int64_t)t * 2 * H];
-            const float cpl = cst[hoff[r] + (int64_t)(first ? t : tprev) * 2 * H];
-            const float cp = first ? 0.f : cpl;
-            const float dh = dh_out[hoff[r] + (int64_t)t * 2 * H] + (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
-            const float tc = tanhf(c);
-            const float dc = dcc[r] + dh * og * (1.0f - tc * tc);
-            const float d_o = dh * tc * og * (1.0f - og);
-            const float d_i = dc * gg * ig * (1.0f - ig);
-            const float d_f = dc * cp * fg * (1.0f - fg);
-            const float d_g = dc * ig * (1.0f - gg * gg);
-            dcc[r] = dc * fg;
-            const int row = q * 4 + r;
-            dgw[row * LDG + unit] = d_i; dgw[row * LDG + H + unit] = d_f;
-            dgw[row * LDG + 2 * H + unit] = d_g; dgw[row * LDG + 3 * H + unit] = d_o;
-            // rows past B are clamped copies of row B-1: they must NOT store here, because this loop reads the gates of
-            // step t row by row and a copy in an earlier register row would overwrite them before the real row reads
-            if (brow[r]) {
-                float* go = gates + goff[r] + (int64_t)t * 8 * H;
-                go[0] = d_i; go[H] = d_f; go[2 * H] = d_g; go[3 * H] = d_o;
-            }
-        }
-        lds_barrier();
-        cur ^= 1;
-        const float* dgr = dgbuf + cur * 16 * LDG;
-#pragma unroll
-        for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int g = 0; g < KG; ++g) {
-            const float4 a4 = *reinterpret_cast<const float4*>(&dgr[col * LDG + 16 * g + 4 * q]);
-            acc[g & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.x, breg[4 * g + 0], acc[g & 3], 0, 0, 0);
-            acc[g & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.y, breg[4 * g + 1], acc[g & 3], 0, 0, 0);
-            acc[g & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.z, breg[4 * g + 2], acc[g & 3], 0, 0, 0);
-            acc[g & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4.w, breg[4 * g + 3], acc[g & 3], 0, 0, 0);
-        }
-    }
-}
-
-// ---- the same backward recurrence for small batches: 4 batch rows per workgroup ---------------------------------------
-// Wave w owns hidden units 16w..16w+15; lane (q, u) = (lane / 16, lane % 16) owns cell (row q, unit 16w + u): lane-local
-// gate / cell derivatives, dgates to HBM (in place) and to LDS (double-buffered: one LDS-only barrier per step).
-// dh_rec = dgates . W_hh with v_mfma_f32_4x4x1_16B_f32 (row i of every block = batch row i): the 16 blocks of an
-// instruction are 4 gates x 4 groups of 4 units, i.e. lane (g, u) contracts the H rows of gate g against unit u (its
-// W_hh column slice is register-resident, H registers) and a two-step butterfly over the gate lanes completes the sum
-// in a fixed order.  No partial products through LDS.
-// The body is shared by the one-recurrence kernel and the group kernels below (`dir`, `tile`: direction and 4-row tile).
-// HALVES = 2 (the mixed group kernel, H = 64): two such bodies side by side in one workgroup, threads [0, 16 H) and
-// [16 H, 32 H), each on its own half of the LDS buffer and with its own `dir`, as lstm_rec4_body (cnnlstm.hip) does it.
-template <int H, int HALVES = 1>
-__device__ __forceinline__ void lstm_bwd4_body(float* gates, const float* __restrict__ cst, const float* __restrict__ dh_out,
-                                               const float* __restrict__ whh, int B, int T, int dir, int tile) {
-    constexpr int NW = H / 16;
-    constexpr int LDG = 4 * H + 20;                 // row stride = 20 banks (mod 32): the four rows of a fragment read and the
-                                                    // 16-lane row groups of the cell owners' writes land on distinct banks
-    __shared__ __attribute__((aligned(16))) float dg_all[HALVES][2][4][LDG];
-    const int half = HALVES == 1 ? 0 : (int)threadIdx.x / (NW * 64);
-    auto& dg = dg_all[half];
-    const int tid = HALVES == 1 ? (int)threadIdx.x : (int)threadIdx.x - half * (NW * 64), lane = tid & 63, w = tid >> 6;
-    const int q = lane >> 4, u = lane & 15;
-    const int b0 = tile * 4;
-    const int unit = 16 * w + u;
-    const int arow = lane & 3;
-
-    // breg[m] = W_hh[dir][q*H + m][unit]   (q as the gate of this lane's blocks)
-    float breg[H];
-    {
-        const float* wd = whh + (int64_t)dir * 4 * H * H + (int64_t)(q * H) * H + unit;
-#pragma unroll
-        for (int m = 0; m < H; ++m) breg[m] = wd[(int64_t)m * H];
-    }
-    const int bo = min(b0 + q, B - 1);              // rows past B replicate row B-1 bit for bit (see lstm_rec_kernel)
-    const int64_t goff = (int64_t)bo * T * 8 * H + dir * 4 * H + unit;
-    const int64_t hoff = (int64_t)bo * T * 2 * H + dir * H + unit;
-    float dcc = 0.f, dh_rec = 0.f;
-    float ig, fg, gg, og, cc, dho;                  // operands of the current step (prefetched)
-    {
-        const int t = dir ? 0 : T - 1;
-        const float* gp = gates + goff + (int64_t)t * 8 * H;
-        ig = gp[0]; fg = gp[H]; gg = gp[2 * H]; og = gp[3 * H];
-        cc = cst[hoff + (int64_t)t * 2 * H];
-        dho = dh_out[hoff + (int64_t)t * 2 * H];
-    }
-    vmem_drain();
-    int cur = 0;
-    for (int s = 0; s < T; ++s) {
-        const int t = dir ? s : T - 1 - s;           // reverse of the forward order
-        const int tprev = dir ? t + 1 : t - 1;       // the step the forward pass ran just before t == the next step here
-        const bool last = s + 1 == T;
-        // next step's operands (branch-free: the last step reloads its own and zeroes c_prev)
-        const int tl = last ? t : tprev;
-        const float* gp = gates + goff + (int64_t)tl * 8 * H;
-        const float nig = gp[0], nfg = gp[H], ngg = gp[2 * H], nog = gp[3 * H];
-        const float ncl = cst[hoff + (int64_t)tl * 2 * H];
-        const float ncc = last ? 0.f : ncl;
-        const float ndho = dh_out[hoff + (int64_t)tl * 2 * H];
-
-        const float dh = dho + dh_rec;
-        const float tc = 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * cc)) - 1.0f;
-        const float dc = dcc + dh * og * (1.0f - tc * tc);
-        const float d_o = dh * tc * og * (1.0f - og);
-        const float d_i = dc * gg * ig * (1.0f - ig);
-        const float d_f = dc * ncc * fg * (1.0f - fg);           // c of the previous forward step (0 at the first)
-        const float d_g = dc * ig * (1.0f - gg * gg);
-        dcc = dc * fg;
-        float* dgw = &dg[cur][q][0];
-        dgw[unit] = d_i; dgw[H + unit] = d_f; dgw[2 * H + unit] = d_g; dgw[3 * H + unit] = d_o;
-        {
-            float* go = gates + goff + (int64_t)t * 8 * H;
-            go[0] = d_i; go[H] = d_f; go[2 * H] = d_g; go[3 * H] = d_o;
-        }
-        lds_barrier();
-        // A operand: lane 4*blk + i carries batch row i; the block's gate is this lane's q
-        const float* dgr = &dg[cur][arow][q * H];
-        f32x4 acc[4];
-#pragma unroll
-        for (int a = 0; a < 4; ++a) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
-        float4 ab[2][8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) ab[0][j] = *reinterpret_cast<const float4*>(dgr + 4 * j);
-#pragma unroll
-        for (int kb = 0; kb < H / 32; ++kb) {
-            if (kb + 1 < H / 32) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) ab[(kb + 1) & 1][j] = *reinterpret_cast<const float4*>(dgr + 32 * (kb + 1) + 4 * j);
-            }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float4 a4 = ab[kb & 1][j];
-                const int m = 32 * kb + 4 * j;
-                acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.x, breg[m + 0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.y, breg[m + 1], acc[1], 0, 0, 0);
-                acc[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.z, breg[m + 2], acc[2], 0, 0, 0);
-                acc[3] = __builtin_amdgcn_mfma_f32_4x4x1f32(a4.w, breg[m + 3], acc[3], 0, 0, 0);
-            }
-        }
-        // lane (g, u), register r: sum over the rows of gate g for (batch row r, unit u).  Butterfly over g; lane (q, u)
-        // keeps batch row q.
-        float pr[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
-            v += __shfl_xor(v, 16, 64);
-            v += __shfl_xor(v, 32, 64);
-            pr[r] = v;
-        }
-        dh_rec = q == 0 ? pr[0] : q == 1 ? pr[1] : q == 2 ? pr[2] : pr[3];
-        cur ^= 1;
-        ig = nig; fg = nfg; gg = ngg; og = nog; cc = ncc; dho = ndho;
-    }
-}
-
-template <int H>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_kernel(float* gates, const float* __restrict__ cst,
-                                                                const float* __restrict__ dh_out, const float* __restrict__ whh,
-                                                                int B, int T) {
-    lstm_bwd4_body<H>(gates, cst, dh_out, whh, B, T, blockIdx.y, blockIdx.x);
-}
-
-// The BPTT recurrences of several independent replicas in one launch, as lstm_rec4_group_kernel (cnnlstm.hip) does for the
-// forward ones: grid (max tiles, 2, K), descriptors by value in the kernel arguments, a workgroup beyond its replica's
-// batch leaves before it touches LDS or a barrier.
-struct LstmBwdItem {
-    float* gates;
-    const float* cst;
-    const float* dh;
-    const float* whh;
-    int B, T;
-};
-struct LstmBwdGroup {
-    LstmBwdItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-
-template <int H>
-__global__ __launch_bounds__(H / 16 * 64) void lstm_bwd4_group_kernel(const LstmBwdGroup g) {
-    const LstmBwdItem& it = g.item[blockIdx.z];
-    if ((int)blockIdx.x * 4 >= it.B) return;
-    lstm_bwd4_body<H>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, blockIdx.y, blockIdx.x);
-}
-
-// BPTT recurrences of different H in one launch, as lstm_rec4_group_mixed_kernel (cnnlstm.hip) runs the forward ones: 512
-// threads; an H = 128 item takes grid.y as its direction, the grid.y == 0 workgroup of an H = 64 item runs both directions
-// (waves 0-3 and 4-7, same T, own LDS halves) and its grid.y == 1 workgroup leaves whole.  Every exit is taken by the whole
-// workgroup before the first LDS access or barrier; a workgroup that enters a body runs all eight waves through every barrier.
-struct LstmBwdMixedItem {
-    LstmBwdItem rec;
-    int H;
-};
-struct LstmBwdMixedGroup {
-    LstmBwdMixedItem item[RSAF_CNNLSTM_GROUP_MAX];
-};
-
-__global__ __launch_bounds__(512) void lstm_bwd4_group_mixed_kernel(const LstmBwdMixedGroup g) {
-    const LstmBwdMixedItem& m = g.item[blockIdx.z];
-    const LstmBwdItem& it = m.rec;
-    if ((int)blockIdx.x * 4 >= it.B) return;
-    if (m.H == 128) {
-        lstm_bwd4_body<128>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, blockIdx.y, blockIdx.x);
-        return;
-    }
-    if (blockIdx.y != 0) return;
-    const int dir = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);
-    lstm_bwd4_body<64, 2>(it.gates, it.cst, it.dh, it.whh, it.B, it.T, dir, blockIdx.x);
-}
-
 // ---- host-side helpers ------------------------------------------------------------------------------------------
 static inline int ew_blocks(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 256 * 32)); }
-
-static int conv3(const float* x, const float* wk, const float* bias, float* y, int B, int T, int Cin, int Cout, hipStream_t s,
-                 const char* tag) {
-    GemmParams p = gemm_params_plain(x - Cin, wk, y, T, Cout, 3 * Cin, Cin, 3 * Cin, Cout);
-    p.bias = bias;
-    p.nz = B; p.nz2 = 1; p.sA1 = (int64_t)T * Cin; p.sC1 = (int64_t)T * Cout;
-    p.a_pad_k = Cin;
-    return launch_gemm_f32(p, s, tag);
-}
 
 struct Ctx {
     Dims d;
@@ -824,7 +472,7 @@ static int bn_backward(const Ctx& c, const float* dout, const float* mask, bool 
     const int C = c.d.C;
     const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(RED_PARTS, rows / 128));
     double* partial = reinterpret_cast<double*>(c.ws + c.W.red);
-    float* sums = c.ws + c.W.small;                      // [2][C] (C <= 1024 fits: small >= 64 + ...)
+    float* sums = c.ws + c.W.bn_sums;                    // [2][C]
     {
         ProfScope prof("train_bn_reduce", c.s, 0.0, (double)rows * C * 8);
         if (pre)
@@ -865,17 +513,13 @@ static int wgrad(const Ctx& c, const float* dy, int64_t ld_dy, int M, const floa
     float* t1 = c.ws + c.W.t1;
     float* t2 = c.ws + c.W.t2;
     float* part = c.ws + c.W.part;
-    int rc = transpose_shift(c, dy, ld_dy, M, B, T, 0, t1, sp.kp);
-    if (rc) return rc;
-    for (int j = 0; j < taps; ++j) {
-        rc = transpose_shift(c, xin, ld_x, N, B, T, taps == 1 ? shift0 : j - taps / 2, t2 + (int64_t)j * N * sp.kp, sp.kp);
-        if (rc) return rc;
-    }
+    TRY(transpose_shift(c, dy, ld_dy, M, B, T, 0, t1, sp.kp));
+    for (int j = 0; j < taps; ++j)
+        TRY(transpose_shift(c, xin, ld_x, N, B, T, taps == 1 ? shift0 : j - taps / 2, t2 + (int64_t)j * N * sp.kp, sp.kp));
     const int NN = taps * N;
     GemmParams p = gemm_params_plain(t1, t2, sp.s == 1 ? out : part, M, NN, (int)sp.kc, sp.kp, sp.kp, NN);
     p.nz = (int)sp.s; p.nz2 = 1; p.sA1 = sp.kc; p.sB1 = sp.kc; p.sC1 = (int64_t)M * NN;
-    rc = launch_gemm_f32(p, c.s, "train_wgrad_gemm");
-    if (rc) return rc;
+    TRY(launch_gemm_f32(p, c.s, "train_wgrad_gemm"));
     if (sp.s > 1) {
         const int64_t n = (int64_t)M * NN;
         ProfScope prof("train_elementwise", c.s, 0.0, (double)n * sp.s * 4);
@@ -894,59 +538,7 @@ static int conv3_dgrad(const Ctx& c, const float* dy, const float* w, float* dx,
         hipLaunchKernelGGL(flip_taps_kernel, dim3(ew_blocks(n)), dim3(256), 0, c.s, w, wf, Cout, Cin);
         RSAF_CHECK_HIP(hipGetLastError());
     }
-    return conv3(dy, wf, nullptr, dx, B, T, Cout, Cin, c.s, "train_dgrad_gemm");
-}
-
-static int launch_lstm_bwd(float* gates, const float* cst, const float* dh, const float* whh, int B, int T, int H, hipStream_t s) {
-    ProfScope prof("lstm_bwd_recurrent", s, 2.0 * B * T * 2.0 * 4 * H * H, 0.0);
-    if (B <= lstm_small_max()) {
-        dim3 grid((B + 3) / 4, 2);
-        if (H == 128) hipLaunchKernelGGL(lstm_bwd4_kernel<128>, grid, dim3(512), 0, s, gates, cst, dh, whh, B, T);
-        else hipLaunchKernelGGL(lstm_bwd4_kernel<64>, grid, dim3(256), 0, s, gates, cst, dh, whh, B, T);
-    } else {
-        dim3 grid((B + 15) / 16, 2);
-        const size_t lds = (size_t)2 * 16 * (4 * H + 4) * sizeof(float);
-        if (H == 128)
-            RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)lstm_bwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        if (H == 128) hipLaunchKernelGGL(lstm_bwd_kernel<128>, grid, dim3(512), lds, s, gates, cst, dh, whh, B, T);
-        else hipLaunchKernelGGL(lstm_bwd_kernel<64>, grid, dim3(256), lds, s, gates, cst, dh, whh, B, T);
-    }
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// every B <= lstm_small_max() (the caller's choice of path)
-static int launch_lstm_bwd_group(const LstmBwdItem* items, int K, int H, hipStream_t s) {
-    LstmBwdGroup g{};
-    int tiles = 0;
-    double flops = 0.0;
-    for (int k = 0; k < K; ++k) {
-        g.item[k] = items[k];
-        tiles = std::max(tiles, (items[k].B + 3) / 4);
-        flops += 2.0 * items[k].B * items[k].T * 2.0 * 4 * H * H;
-    }
-    ProfScope prof("lstm_bwd_recurrent", s, flops, 0.0);
-    dim3 grid(tiles, 2, K);
-    if (H == 128) hipLaunchKernelGGL(lstm_bwd4_group_kernel<128>, grid, dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(lstm_bwd4_group_kernel<64>, grid, dim3(256), 0, s, g);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
-}
-
-// every B <= lstm_small_max(), every H 64 or 128 (the caller's checks)
-static int launch_lstm_bwd_group_mixed(const LstmBwdMixedItem* items, int K, hipStream_t s) {
-    LstmBwdMixedGroup g{};
-    int tiles = 0;
-    double flops = 0.0;
-    for (int k = 0; k < K; ++k) {
-        g.item[k] = items[k];
-        tiles = std::max(tiles, (items[k].rec.B + 3) / 4);
-        flops += 2.0 * items[k].rec.B * items[k].rec.T * 2.0 * 4 * items[k].H * items[k].H;
-    }
-    ProfScope prof("lstm_bwd_recurrent", s, flops, 0.0);
-    hipLaunchKernelGGL(lstm_bwd4_group_mixed_kernel, dim3(tiles, 2, K), dim3(512), 0, s, g);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
+    return conv3(dy, wf, nullptr, nullptr, 0, 0, dx, B, T, Cout, Cin, ACT_NONE, c.s, "train_dgrad_gemm");
 }
 
 // ---- one replica's step, cut at its recurrences into phases -----------------------------------------------------------
@@ -996,7 +588,7 @@ static int check_overlaps(const rsaf_cnnlstm_train_item* items, int K, bool back
                                : overlap(a.scratch, reps[j].WL.total, b.scratch, reps[k].WL.total) ? "scratch"
                                : !backward && overlap(a.logits, (int64_t)a.B * NC, b.logits, (int64_t)b.B * NC) ? "logits"
                                : backward && overlap(a.grads, reps[j].L.total, b.grads, reps[k].L.total) ? "grads" : nullptr;
-            if (what) return fail(RSAF_ERR_ARG, who, k, (std::string("shares `") + what + "` with item " + std::to_string(j)).c_str());
+            if (what) return fail(RSAF_ERR_ARG, who, k, std::string("shares `") + what + "` with item " + std::to_string(j));
         }
     return RSAF_OK;
 }
@@ -1016,7 +608,7 @@ static int check_group_mixed(const rsaf_cnnlstm_train_item* items, const rsaf_cn
     if (!arch) return fail(RSAF_ERR_ARG, who, -1, "arch_host is NULL");
     for (int k = 0; k < K; ++k) {
         const Dims d{input_dim, arch[k].channels, arch[k].hidden, num_classes, lstm_layers, arch[k].act};
-        if (const char* problem = dims_problem(d)) return fail(RSAF_ERR_ARG, who, k, problem);
+        if (const char* problem = dims_problem(d, TRAIN_C_MAX)) return fail(RSAF_ERR_ARG, who, k, problem);
         TRY(check_item(d, items[k], backward, s, who, k, &reps[k], RSAF_ERR_ARG));
     }
     return check_overlaps(items, K, backward, who, reps);
@@ -1045,7 +637,7 @@ static int fwd_cnn(Replica& r, const PLayout& L) {
     float* r1 = r.it.scratch + r.WL.bufA;
 
     // ---- res_block1 (src/models.py:64-76) --------------------------------------------------------------------
-    TRY(conv3(x, P + L.c1.w, P + L.c1.b, saved + S.y1, B, T, D, C, s, "train_conv_gemm"));
+    TRY(conv3(x, P + L.c1.w, P + L.c1.b, nullptr, 0, 0, saved + S.y1, B, T, D, C, ACT_NONE, s, "train_conv_gemm"));
     TRY(bn_stats(c, saved + S.y1, rows, stat(0)));
     {
         ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 12);
@@ -1059,7 +651,7 @@ static int fwd_cnn(Replica& r, const PLayout& L) {
         TRY(launch_gemm_f32(p, s, "train_conv_gemm"));
         TRY(bn_stats(c, saved + S.ysc, rows, stat(1)));
     }
-    TRY(conv3(saved + S.a1d, P + L.c2.w, P + L.c2.b, saved + S.y2, B, T, C, C, s, "train_conv_gemm"));
+    TRY(conv3(saved + S.a1d, P + L.c2.w, P + L.c2.b, nullptr, 0, 0, saved + S.y2, B, T, C, C, ACT_NONE, s, "train_conv_gemm"));
     TRY(bn_stats(c, saved + S.y2, rows, stat(2)));
     {
         ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 16);
@@ -1070,11 +662,10 @@ static int fwd_cnn(Replica& r, const PLayout& L) {
     // ---- max_pool1d(2) (:177) -----------------------------------------------------------------------------------
     {
         ProfScope prof("train_elementwise", s, 0.0, (double)rows * C * 6);
-        hipLaunchKernelGGL(pool2_kernel, dim3(ew_blocks(rows2 * C / 4)), dim3(256), 0, s, reinterpret_cast<const float4*>(r1),
-                           reinterpret_cast<float4*>(saved + S.p), B, T, Tp, C / 4);
+        launch_pool2(r1, saved + S.p, B, T, Tp, C, ew_blocks(rows2 * C / 4), s);
     }
     // ---- res_block2, identity shortcut (:178) ----------------------------------------------------------------------
-    TRY(conv3(saved + S.p, P + L.c3.w, P + L.c3.b, saved + S.y3, B, Tp, C, C, s, "train_conv_gemm"));
+    TRY(conv3(saved + S.p, P + L.c3.w, P + L.c3.b, nullptr, 0, 0, saved + S.y3, B, Tp, C, C, ACT_NONE, s, "train_conv_gemm"));
     TRY(bn_stats(c, saved + S.y3, rows2, stat(3)));
     {
         ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 12);
@@ -1082,7 +673,7 @@ static int fwd_cnn(Replica& r, const PLayout& L) {
                            stat(3), P + L.c3.g, P + L.c3.be, reinterpret_cast<const float4*>(r.it.mask_block2),
                            reinterpret_cast<float4*>(saved + S.a3d), act, rows2 * C / 4, C);
     }
-    TRY(conv3(saved + S.a3d, P + L.c4.w, P + L.c4.b, saved + S.y4, B, Tp, C, C, s, "train_conv_gemm"));
+    TRY(conv3(saved + S.a3d, P + L.c4.w, P + L.c4.b, nullptr, 0, 0, saved + S.y4, B, Tp, C, C, ACT_NONE, s, "train_conv_gemm"));
     TRY(bn_stats(c, saved + S.y4, rows2, stat(4)));
     {
         ProfScope prof("train_elementwise", s, 0.0, (double)rows2 * C * 16);
@@ -1155,11 +746,10 @@ static int bwd_head(Replica& r, const PLayout& L) {
     const float* P = r.it.params;
     float* G = r.it.grads;
     float* saved = r.it.saved;
-    float* small = r.it.scratch + r.WL.small;
-    float* dctx = small + 2 * 1024 + 64;               // after the BN `sums` area
-    float* dwatt_part = dctx + (int64_t)B * F;
-    float* dbatt_part = dwatt_part + (int64_t)B * F;
-    float* dp_scr = dbatt_part + B + 4;
+    float* dctx = r.it.scratch + r.WL.dctx;
+    float* dwatt_part = r.it.scratch + r.WL.dwatt_part;
+    float* dbatt_part = r.it.scratch + r.WL.dbatt_part;
+    float* dp_scr = r.it.scratch + r.WL.dp;
     const float* seq_top = saved + S.hout[d.L - 1];
     float* dseq = r.it.scratch + r.WL.bufA;             // [rows2][2H]
     {
@@ -1293,28 +883,17 @@ static int bwd_blocks(Replica& r, const PLayout& L) {
 // GROUPED (one architecture): one launch carries the recurrences of all replicas (4-row kernels; needs every batch at or
 // under the threshold, else all run per replica).  MIXED (an architecture per replica): one launch carries those at or under
 // the threshold, and a replica above it has its recurrence launched on its own.  SINGLE: one launch per replica through the
-// one-recurrence launchers.  Every replica carries its own dims (c.d) and layouts.
-enum { SINGLE = 0, GROUPED = 1, MIXED = 2 };
+// one-recurrence launchers (launch_lstm_rec_layer / launch_lstm_bwd_layer, all_or_none).  Every replica carries its own dims
+// (c.d) and layouts.
 
 static int run_forward(Replica* reps, int K, int mode) {
     hipStream_t s = reps[0].c.s;
     const int layers = reps[0].c.d.L;
-    if (mode == GROUPED)
-        for (int k = 0; k < K; ++k)
-            if (reps[k].it.B > lstm_small_max()) mode = SINGLE;
     for (int k = 0; k < K; ++k) TRY(fwd_cnn(reps[k], reps[k].L));
     for (int l = 0; l < layers; ++l) {
-        LstmRecItem same[RSAF_CNNLSTM_GROUP_MAX];
-        LstmRecMixedItem mixed[RSAF_CNNLSTM_GROUP_MAX];
-        int n = 0;
-        for (int k = 0; k < K; ++k) {
-            const LstmRecItem it = fwd_rec_item(reps[k], reps[k].L, l);
-            if (mode == SINGLE || it.B > lstm_small_max())
-                TRY(launch_lstm_rec(it.xproj, it.whh, it.hout, it.gates_save, it.c_save, it.B, it.T, reps[k].c.d.H, s));
-            else { same[n] = it; mixed[n++] = LstmRecMixedItem{it, reps[k].c.d.H}; }
-        }
-        if (n && mode == MIXED) TRY(launch_lstm_rec_group_mixed(mixed, n, s));
-        else if (n) TRY(launch_lstm_rec_group(same, n, reps[0].c.d.H, s));
+        LstmRecMixedItem recs[RSAF_CNNLSTM_GROUP_MAX];
+        for (int k = 0; k < K; ++k) recs[k] = LstmRecMixedItem{fwd_rec_item(reps[k], reps[k].L, l), reps[k].c.d.H};
+        TRY(launch_lstm_rec_layer(recs, K, mode, true, s));
         for (int k = 0; k < K; ++k) TRY(fwd_after_rec(reps[k], reps[k].L, l));
     }
     for (int k = 0; k < K; ++k) TRY(fwd_head(reps[k], reps[k].L));
@@ -1324,22 +903,11 @@ static int run_forward(Replica* reps, int K, int mode) {
 static int run_backward(Replica* reps, int K, int mode) {
     hipStream_t s = reps[0].c.s;
     const int layers = reps[0].c.d.L;
-    if (mode == GROUPED)
-        for (int k = 0; k < K; ++k)
-            if (reps[k].it.B > lstm_small_max()) mode = SINGLE;
     for (int k = 0; k < K; ++k) TRY(bwd_head(reps[k], reps[k].L));
     for (int l = layers - 1; l >= 0; --l) {              // LSTM layers, top down
-        LstmBwdItem same[RSAF_CNNLSTM_GROUP_MAX];
-        LstmBwdMixedItem mixed[RSAF_CNNLSTM_GROUP_MAX];
-        int n = 0;
-        for (int k = 0; k < K; ++k) {
-            const LstmBwdItem it = bwd_rec_item(reps[k], reps[k].L, l);
-            if (mode == SINGLE || it.B > lstm_small_max())
-                TRY(launch_lstm_bwd(it.gates, it.cst, it.dh, it.whh, it.B, it.T, reps[k].c.d.H, s));
-            else { same[n] = it; mixed[n++] = LstmBwdMixedItem{it, reps[k].c.d.H}; }
-        }
-        if (n && mode == MIXED) TRY(launch_lstm_bwd_group_mixed(mixed, n, s));
-        else if (n) TRY(launch_lstm_bwd_group(same, n, reps[0].c.d.H, s));
+        LstmBwdMixedItem recs[RSAF_CNNLSTM_GROUP_MAX];
+        for (int k = 0; k < K; ++k) recs[k] = LstmBwdMixedItem{bwd_rec_item(reps[k], reps[k].L, l), reps[k].c.d.H};
+        TRY(launch_lstm_bwd_layer(recs, K, mode, true, s));
         for (int k = 0; k < K; ++k) TRY(bwd_after_rec(reps[k], reps[k].L, l));
     }
     for (int k = 0; k < K; ++k) TRY(bwd_blocks(reps[k], reps[k].L));

@@ -1,7 +1,7 @@
 """Geometry table of the CNN-LSTM entry points and the builders of its cases, shared by tests/test_cnnlstm_geometry.py
 (no GPU) and tests/test_cnnlstm_geometry_gpu.py.
 
-``check_dims`` (csrc/cnnlstm.hip, csrc/cnnlstm_train_layout.h) accepts every input_dim and cnn_out_channels that is a multiple
+``check_dims`` (csrc/cnnlstm_host.h over ``dims_problem`` of csrc/cnnlstm_layout.h) accepts every input_dim and cnn_out_channels that is a multiple
 of 4, lstm_hidden_dim 64 or 128, 1 to 16 classes and 1 to 4 LSTM layers; the code branches on exactly these dimensions
 (fp16-split or exact-fp32 convolutions, panel image of the input, the tile configuration of the GEMM, the 32 / 64 / 256
 channel blocks of the training helpers, the ``max(...)`` sizes of the training scratch).  Each row is the smallest shape

@@ -2,8 +2,8 @@
 train_replicas_lockstep against K single steps through CNNLSTM.forward (bit for bit) and against the training oracle.
 
 Exact equality is the bar between the group and the single path: both run the same device code in the same order per
-replica (the recurrence kernels share one body) and every reduction of the step has a fixed partition (header comment of
-cnnlstm_train.hip; the sums of the loss and the gradient norm: the fixed tree of cnnlstm_optim.hip), so a difference is a bug, not rounding.  Against the float64 oracle the bar is the project's 1e-4
+replica (the recurrence kernels of cnnlstm_lstm.hip share one body) and every reduction of the step has a fixed partition (header
+comment of cnnlstm_train.hip; the sums of the loss and the gradient norm: the fixed tree of cnnlstm_optim.hip), so a difference is a bug, not rounding.  Against the float64 oracle the bar is the project's 1e-4
 relative to each tensor's largest magnitude (tests/test_cnnlstm_train_gpu.py)."""
 import copy
 import os
