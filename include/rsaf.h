@@ -713,7 +713,8 @@ int rsaf_mshds_ltas_slope_tilt(const float* wav, const void* clip_info, int n_cl
  * low-pass of the extracted part over its own power of two, NUM_interpolate_sinc), "To PowerCepstrogram" 60 0.002 5000 50,
  * "Get CPPS" no 0.01 0.001 60 330 0.05 parabolic 0.001 0 Straight Robust.
  * Replaces src/mshds_extractor.py:272-297.  Workspaces (caller-owned, per clip): seg_table
- * [max_seg][rsaf_mshds_cpp_seg_doubles()] doubles, hdr [4] ints, resampled [cap_res], cepstrogram
+ * [max_seg][rsaf_mshds_cpp_seg_doubles()] doubles, hdr [4] ints = {intervals, 1 if the clip failed, frames in all,
+ * resampled samples in all} (csrc/mshds_cpp_layout.h: Seg, ClipHdr), resampled [cap_res], cepstrogram
  * [cap_frames][513], cpp_frames [cap_frames] doubles, lp_work [cap_work] complex doubles (cap_work >= longest clip +
  * 2000 max_seg covers every case); lowpassed: float64 scratch for the samples wav[lp_origin ...] of the clips of this
  * call (sample s of the batch at lowpassed[s - lp_origin]); lg_max = log2 of the first power of two >= longest clip +

@@ -9,6 +9,7 @@
 // power cepstrum per frame (two 1024-point fp64 FFTs in LDS), smoothed CPP per frame (moving averages,
 // two bitonic sorts for Theil's line, parabolic peak), reduction per interval and clip.
 // The arithmetic is fp64 and nothing is contracted to FMA where Praat's rounding decides an integer.
+// Layouts, constants and the arithmetic both forms of a per-frame kernel share: mshds_cpp_layout.h (also compiled on the host).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,42 +22,14 @@
 #include "wave_fft.h"
 // the four above are compiled with contraction on; from this header's pragma on, nothing is contracted
 #include "mshds_common.h"
+#include "mshds_cpp_layout.h"
 
 namespace rsaf {
 namespace mshds_cpp {
 
 using mshds::ClipInfo;
-using mshds::DXS;
 using mshds::PI;
-constexpr double FS_OUT = 10000.0;
-constexpr double DXO = 1.0 / FS_OUT;
-constexpr int DEPTH = 50;                 // Sound_resample precision of Sound_to_PowerCepstrogram
-constexpr double DT = 0.002;              // cepstrogram time step
-constexpr double DQ = 1.0e-4;             // quefrency step = 1 / FS_OUT
-constexpr int NFFT_MAX = 1024;            // 0.1 s window at 10 kHz = 1000 samples
-constexpr int NQ_MAX = NFFT_MAX / 2 + 1;  // 513
-constexpr int SEG_DOUBLES = 15;
-
-// one voiced interval (all fields double so that the table is one plain array)
-struct Seg {
-    double ix1, m_in, m_out, res_off, frame_off, nf, x1_seg, x1o, window, t1, nx, nfft;
-    double work_off, item_off, lg;   // low-pass transform: first complex number, first work item, log2 of its length
-};
-static_assert(sizeof(Seg) == SEG_DOUBLES * sizeof(double), "Seg layout");
-
-// "%.6f" and back ("Down to Table" prints the interval times with 6 decimals, the reference parses them again).
-// printf rounds the exact binary value; interval ends clipped to the sound's end are multiples of 62.5 us, i.e.
-// sit within one ulp of a decimal tie, so the product t * 1e6 must not be rounded before the decision: the FMA
-// recovers its rounding error exactly.
-__device__ __forceinline__ double round6(double t) {
-    const double p = t * 1.0e6;
-    const double e = fma(t, 1.0e6, -p);                  // t * 1e6 == p + e exactly
-    double q = floor(p);
-    double f = (p - q) + e;                              // fractional part of the exact product
-    if (f < 0.0) { q -= 1.0; f += 1.0; }
-    const bool up = f > 0.5 || (f == 0.5 && fmod(q, 2.0) != 0.0);
-    return (up ? q + 1.0 : q) / 1.0e6;
-}
+static_assert(DXS == mshds::DXS && ANTI_TURN_AROUND == resample::ANTI_TURN_AROUND, "mshds_cpp_layout.h restates these");
 
 // work items (workgroups) of one pass of an interval's low-pass transform of 2^lg samples: the larger of the column and row pass
 __host__ __device__ inline int lp_items(int lg) {
@@ -66,7 +39,7 @@ __host__ __device__ inline int lp_items(int lg) {
 }
 
 // ---- 1. voiced intervals -> segment table -----------------------------------------------------------------
-// hdr[clip] = {n_seg, fail, total_frames, total_resampled}
+// one wave per clip; leaves the clip's rows of the segment table and its ClipHdr
 __global__ __launch_bounds__(64) void segments_kernel(const ClipInfo* __restrict__ ci, const double* __restrict__ pulses,
                                                       int max_pulses, const int* __restrict__ n_pulses, double max_period,
                                                       double mean_period, double pitch_floor, Seg* __restrict__ segs,
@@ -92,43 +65,27 @@ __global__ __launch_bounds__(64) void segments_kernel(const ClipInfo* __restrict
         begin_voiceless = end_voiced;
         const double tmin = round6(begin_voiced), tmax = round6(end_voiced);
         if (tmin >= tmax) return;                                            // :284
-        const int64_t ix1 = (int64_t)ceil((tmin - c.x1) / DXS), ix2 = (int64_t)floor((tmax - c.x1) / DXS);
-        const double dur = tmax - tmin;
-        const int64_t m_out = (int64_t)floor(dur * FS_OUT + 0.5);
-        if (ix2 < ix1 || m_out < 1) { fail = 1; return; }                    // Praat raises outside the inner try -> NaN
-        const int64_t m_in = ix2 - ix1 + 1;
-        double window = 2.0 * 3.0 / pitch_floor;
-        const double my_duration = DXS * (double)m_in;
-        if (window > my_duration) window = my_duration;
-        const int64_t nf = (int64_t)floor((my_duration - window) / DT) + 1;
-        const double x1_seg = c.x1 + (double)ix1 * DXS - tmin;
-        const double mid = x1_seg - 0.5 * DXS + 0.5 * my_duration;
-        const double t1 = mid - 0.5 * (double)nf * DT + 0.5 * DT;
-        const int64_t nx = (int64_t)floor(window * FS_OUT + 0.5);
-        int nfft = 2;
-        while (nfft < nx) nfft *= 2;
-        int lg = 11;                                                         // Sound_resample: first power of two >= n + 2000
-        while (((int64_t)1 << lg) < m_in + 2 * resample::ANTI_TURN_AROUND) ++lg;
-        const int64_t work_len = (int64_t)1 << (lg - 1);
-        if (nseg >= max_seg || res_off + m_out > cap_res || frame_off + nf > cap_frames || nx > NFFT_MAX || nx < 1 || nf < 1 ||
-            lg > lg_max || work_off + work_len > cap_work) {
+        SegGeom g;
+        if (!seg_geometry(tmin, tmax, c.x1, pitch_floor, &g)) { fail = 1; return; }
+        const int64_t work_len = g.work_len();
+        if (nseg >= max_seg || res_off + g.m_out > cap_res || frame_off + g.nf > cap_frames || g.exceeds(lg_max) ||
+            work_off + work_len > cap_work) {
             fail = 1;
             return;
         }
         if (lane == 0) {
             Seg s;
-            s.ix1 = (double)ix1; s.m_in = (double)m_in; s.m_out = (double)m_out; s.res_off = (double)res_off;
-            s.frame_off = (double)frame_off; s.nf = (double)nf; s.x1_seg = x1_seg;
-            s.x1o = 0.5 * (dur - (double)(m_out - 1) * DXO);
-            s.window = window; s.t1 = t1; s.nx = (double)nx; s.nfft = (double)nfft;
-            s.work_off = (double)work_off; s.item_off = (double)item_off; s.lg = (double)lg;
+            s.ix1 = (double)g.ix1; s.m_in = (double)g.m_in; s.m_out = (double)g.m_out; s.res_off = (double)res_off;
+            s.frame_off = (double)frame_off; s.nf = (double)g.nf; s.x1_seg = g.x1_seg; s.x1o = g.x1o();
+            s.window = g.window; s.t1 = g.t1; s.nx = (double)g.nx; s.nfft = (double)g.nfft;
+            s.work_off = (double)work_off; s.item_off = (double)item_off; s.lg = (double)g.lg;
             out[nseg] = s;
         }
         ++nseg;
-        res_off += m_out;
-        frame_off += nf;
+        res_off += g.m_out;
+        frame_off += g.nf;
         work_off += work_len;
-        item_off += lp_items(lg);
+        item_off += lp_items(g.lg);
     };
     for (int base = 0; base < np_; base += 64) {
         const int i = base + lane;
@@ -143,22 +100,22 @@ __global__ __launch_bounds__(64) void segments_kernel(const ClipInfo* __restrict
     }
     if (np_ > 0) emit(cur_start, np_ - 1);
     if (lane == 0) {
-        hdr[4 * blockIdx.x + 0] = nseg;
-        hdr[4 * blockIdx.x + 1] = fail;
-        hdr[4 * blockIdx.x + 2] = (int)frame_off;
-        hdr[4 * blockIdx.x + 3] = (int)res_off;
+        ClipHdr* h = ClipHdr::at(hdr, blockIdx.x);
+        h->n_seg = nseg;
+        h->fail = fail;
+        h->total_frames = (int)frame_off;
+        h->total_resampled = (int)res_off;
     }
 }
 
-// index of the segment that owns element g of a prefix-summed range (OFF = index of the offset field in Seg)
-template <int OFF>
-__device__ __forceinline__ int find_seg(const Seg* __restrict__ s, int nseg, int g) {
-    int lo = 0, hi = nseg - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((int)reinterpret_cast<const double*>(s + mid)[OFF] <= g) lo = mid; else hi = mid - 1;
-    }
-    return lo;
+// the segment table of one clip, as every later kernel reads it
+struct ClipSegs {
+    int nseg;
+    const Seg* S;
+    __device__ __forceinline__ Seg of_frame(int f) const { return S[find_seg<&Seg::frame_off>(S, nseg, f)]; }
+};
+__device__ __forceinline__ ClipSegs clip_segs(const Seg* __restrict__ segs, int max_seg, const int* __restrict__ hdr, int clip) {
+    return ClipSegs{ClipHdr::at(hdr, clip)->n_seg, segs + (int64_t)clip * max_seg};
 }
 
 // ---- 2. 16 kHz -> 10 kHz of every interval: Sound_resample (10000, 50) --------------------------------------
@@ -175,13 +132,12 @@ __global__ __launch_bounds__(256) void seg_lowpass_kernel(const float* __restric
                                                           int lg_lo, int lg_hi, resample::LpTables T) {
     extern __shared__ resample::c64 lp_lds[];
     const int clip = blockIdx.y;
-    const int nseg = hdr[4 * clip];
+    const auto [nseg, S] = clip_segs(segs, max_seg, hdr, clip);
     if (nseg <= 0) return;
-    const Seg* S = segs + (int64_t)clip * max_seg;
     const ClipInfo c = ci[clip];
     const int total = (int)S[nseg - 1].item_off + lp_items((int)S[nseg - 1].lg);
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
-        const Seg s = S[find_seg<13>(S, nseg, w)];
+        const Seg s = S[find_seg<&Seg::item_off>(S, nseg, w)];
         if ((int)s.lg < lg_lo || (int)s.lg > lg_hi) continue;               // the other launch's class (same for the whole workgroup)
         resample::LpSig sg;
         sg.in_off = c.sample_off + (int64_t)s.ix1;
@@ -205,8 +161,7 @@ __global__ __launch_bounds__(1024) void seg_lowpass_lds_kernel(const float* __re
                                                                resample::LpTables T) {
     extern __shared__ resample::c64 lp_lds[];
     const int clip = blockIdx.y;
-    const int nseg = hdr[4 * clip];
-    const Seg* S = segs + (int64_t)clip * max_seg;
+    const auto [nseg, S] = clip_segs(segs, max_seg, hdr, clip);
     const ClipInfo c = ci[clip];
     for (int k = blockIdx.x; k < nseg; k += gridDim.x) {
         const Seg s = S[k];
@@ -223,8 +178,6 @@ __global__ __launch_bounds__(1024) void seg_lowpass_lds_kernel(const float* __re
 // intervals and phases whose fraction lies within 1e-6 of an integer take Praat's formula term by term as before
 // (`RSAF_CPP_POLYPHASE=0`: everything does).  Against the term-by-term form the sums differ by rounding only (the weights
 // are those of the phase's first output: positions 8 samples apart differ by ~1e-11 in the fraction).
-constexpr int RS_TAPS = 2 * DEPTH;                    // 100
-constexpr int RS_WIN = 512;                            // input window of a workgroup: 255 * 1.6 + 100 samples
 __global__ __launch_bounds__(256) void resample_kernel(const double* __restrict__ lowpassed, int64_t lp_origin,
                                                        const ClipInfo* __restrict__ ci, const Seg* __restrict__ segs, int max_seg,
                                                        const int* __restrict__ hdr, int cap_res, double* __restrict__ res,
@@ -233,14 +186,14 @@ __global__ __launch_bounds__(256) void resample_kernel(const double* __restrict_
     __shared__ double s_in[RS_WIN];
     __shared__ int s_si0;
     const int clip = blockIdx.y;
-    const int nseg = hdr[4 * clip], total = hdr[4 * clip + 3];
+    const auto [nseg, S] = clip_segs(segs, max_seg, hdr, clip);
+    const int total = ClipHdr::at(hdr, clip)->total_resampled;
     const int tid = threadIdx.x;
     const int g0 = blockIdx.x * 256;
     if (g0 >= total || nseg <= 0) return;               // workgroup-uniform
     const int g = g0 + tid;
     const bool live = g < total;
-    const Seg* S = segs + (int64_t)clip * max_seg;
-    const int si = find_seg<3>(S, nseg, live ? g : total - 1);
+    const int si = find_seg<&Seg::res_off>(S, nseg, live ? g : total - 1);
     const Seg s = S[si];
     const ClipInfo c = ci[clip];
     const double* y = lowpassed + (c.sample_off - lp_origin) + (int64_t)s.ix1;   // the extracted part, low-passed
@@ -334,12 +287,26 @@ __device__ __forceinline__ int bitrev(int i, int log2n) { return log2n ? (int)(_
 
 // Real-input FFT of n = 2m points from an m-point complex FFT of z[j] = x[2j] + i x[2j+1] (already transformed in `a`):
 // X[k] = E + W_n^k O,  E = (Z[k] + conj Z[m-k]) / 2,  O = -i (Z[k] - conj Z[m-k]) / 2,  k = 0..m  (Z[m] = Z[0]).
+// E and O of the pair (zk, zc) = (Z[k], Z[m - k])
+struct EvenOdd { double er, ei, orr, oi; };
+template <class Z>
+__device__ __forceinline__ EvenOdd real_even_odd(const Z& zk, const Z& zc) {
+    return EvenOdd{0.5 * (zk.x + zc.x), 0.5 * (zk.y - zc.y), 0.5 * (zk.y + zc.y), -0.5 * (zk.x - zc.x)};
+}
+// The pair's two bins at once, as the one-wave kernel evaluates them: sum = X[k] = E + T, diff = conj X[m - k] = E - T with
+// the product T = W^k O formed first.  real_fft_bin below adds the product's two terms to E one after the other,
+// (E + w.x O.re) - w.y O.im: another rounding, so the workgroup form keeps its own line and the two are not folded.
+template <class Z>
+__device__ __forceinline__ void real_split(const Z& zk, const Z& zc, const Z& w, Z* sum, Z* diff) {
+    const EvenOdd p = real_even_odd(zk, zc);
+    const double tr = w.x * p.orr - w.y * p.oi, ti = w.x * p.oi + w.y * p.orr;
+    *sum = Z{p.er + tr, p.ei + ti};
+    *diff = Z{p.er - tr, ti - p.ei};
+}
 __device__ __forceinline__ double2 real_fft_bin(const double2* a, int m, int k, const double2* __restrict__ tw, int twstep) {
-    const double2 zk = a[k == m ? 0 : k], zc = a[k == 0 ? 0 : m - k];
-    const double er = 0.5 * (zk.x + zc.x), ei = 0.5 * (zk.y - zc.y);
-    const double orr = 0.5 * (zk.y + zc.y), oi = -0.5 * (zk.x - zc.x);
+    const EvenOdd p = real_even_odd(a[k == m ? 0 : k], a[k == 0 ? 0 : m - k]);
     const double2 w = k == m ? make_double2(-1.0, 0.0) : tw[k * twstep];
-    return make_double2(er + w.x * orr - w.y * oi, ei + w.x * oi + w.y * orr);
+    return make_double2(p.er + w.x * p.orr - w.y * p.oi, p.ei + w.x * p.oi + w.y * p.orr);
 }
 
 // Frames of intervals shorter than the 0.1 s window (transform lengths below 1024): the one-wave kernel below lists them,
@@ -357,17 +324,14 @@ __global__ __launch_bounds__(256) void cepstrum_kernel(const Seg* __restrict__ s
     for (int item = blockIdx.x; item < count; item += gridDim.x) {
     __syncthreads();                                    // the previous frame's readers of a / xs / s_red are done
     const int clip = list[2 * item], f = list[2 * item + 1];
-    const int nseg = hdr[4 * clip];
-    const Seg* S = segs + (int64_t)clip * max_seg;
-    const Seg s = S[find_seg<4>(S, nseg, f)];
+    const Seg s = clip_segs(segs, max_seg, hdr, clip).of_frame(f);
     const int fl = f - (int)s.frame_off;
     const int nx = (int)s.nx, nfft = (int)s.nfft, m_out = (int)s.m_out;
     int log2n = 0;
     while ((1 << log2n) < nfft) ++log2n;
     const int m = nfft >> 1, log2m = log2n - 1, twstep = NFFT_MAX / nfft;
     const double* y = res + (int64_t)clip * cap_res + (int64_t)s.res_off;
-    const double t = s.t1 + (double)fl * DT;
-    const int64_t idx0 = (int64_t)floor((t - 0.5 * s.window - s.x1o) / DXO + 0.5);   // Sampled_xToNearestIndex, 0-based
+    const int64_t idx0 = frame_first_index<int64_t>(s, fl);
     // gather with the pre-emphasis y[j] - a y[j-1] (the first sample of the sound is kept), frame mean
     double loc[4];
     double sum = 0.0;
@@ -386,23 +350,10 @@ __global__ __launch_bounds__(256) void cepstrum_kernel(const Seg* __restrict__ s
     if (lane == 0) s_red[wv] = sum;
     __syncthreads();
     const double mean = ((s_red[0] + s_red[1]) + (s_red[2] + s_red[3])) / (double)nx;
-    const double imid = 0.5 * (nx + 1), edge = exp(-12.0);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int i = tid + 256 * r;
-        if (i < nfft) {
-            double v = 0.0;
-            if (i < nx) {
-                double w;
-                if (nx == 1000) w = win1000[i];
-                else {
-                    const double d = (double)(i + 1) - imid;
-                    w = (exp(-48.0 * (d * d) / (double)((nx + 1) * (nx + 1))) - edge) / (1.0 - edge);
-                }
-                v = (loc[r] - mean) * w;
-            }
-            xs[i] = v;
-        }
+        if (i < nfft) xs[i] = i < nx ? (loc[r] - mean) * (nx == 1000 ? win1000[i] : gauss_window(i, nx)) : 0.0;
     }
     __syncthreads();
     // both transforms have real input (the second one even as well): one complex FFT of half the length each
@@ -436,8 +387,26 @@ __global__ __launch_bounds__(256) void cepstrum_kernel(const Seg* __restrict__ s
 // transforms are 512-point complex transforms in registers (wave_fft.h, 8 points per lane), the conjugate pairs (k, 512 - k)
 // of the real-input split are evaluated once each by the lane that holds k < 256, the ln-power half spectrum goes through
 // LDS once to become the even sequence of the second transform.  No workgroup barrier; CEP_FRAMES frames per wave.
-constexpr int CEP_FRAMES = 4;
 constexpr int CEP_LDS_DOUBLES = wfft::Plan<8>::LDS_DOUBLES + 516;
+
+// What both one-wave kernels start with: the clip's segment table and the frames [f0, f1) that workgroup blockIdx.x takes
+// (per_wave frames each); false: none.
+__device__ __forceinline__ bool wave_frames(const Seg* __restrict__ segs, int max_seg, const int* __restrict__ hdr, int clip,
+                                            int per_wave, ClipSegs* cs, int* f0, int* f1) {
+    *cs = clip_segs(segs, max_seg, hdr, clip);
+    if (cs->nseg <= 0) return false;
+    const int nframes = ClipHdr::at(hdr, clip)->total_frames;
+    *f0 = blockIdx.x * per_wave;
+    if (*f0 >= nframes) return false;
+    *f1 = *f0 + per_wave < nframes ? *f0 + per_wave : nframes;
+    return true;
+}
+// a frame the one-wave kernel leaves to the workgroup kernel (short interval, or every frame when forced): lane 0 lists it
+__device__ __forceinline__ bool listed_instead(const Seg& s, int force_list, int lane, const FrameList& list, int clip, int f) {
+    if ((int)s.nfft == NFFT_MAX && !force_list) return false;
+    if (lane == 0) list.push(clip, f);
+    return true;
+}
 
 __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restrict__ segs, int max_seg, const int* __restrict__ hdr,
                                                               const double* __restrict__ res, int cap_res, int cap_frames,
@@ -449,32 +418,22 @@ __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restr
     double* lp = lds + Plan<8>::LDS_DOUBLES;            // ln-power half spectrum, bins 0 .. 512
     constexpr int R = 8, S = 512, H = 4;
     const int clip = blockIdx.y;
-    const int nseg = hdr[4 * clip];
-    if (nseg <= 0) return;
-    const int nframes = hdr[4 * clip + 2];
-    const int f0 = blockIdx.x * CEP_FRAMES;
-    if (f0 >= nframes) return;
-    const Seg* SG = segs + (int64_t)clip * max_seg;
+    ClipSegs cs;
+    int f0, f1;
+    if (!wave_frames(segs, max_seg, hdr, clip, CEP_FRAMES, &cs, &f0, &f1)) return;
+    const FrameList flist(list, list_count, list_cap);
     const int lane_ = threadIdx.x;
     LdsMem mem{lds};
-    const int f1 = f0 + CEP_FRAMES < nframes ? f0 + CEP_FRAMES : nframes;
 #pragma unroll 1
     for (int f = f0; f < f1; ++f) {
         int lane = lane_;                               // redefined per frame (keeps lane-only expressions out of the loop preheader)
         asm volatile("" : "+v"(lane));
-        const Seg s = SG[find_seg<4>(SG, nseg, f)];
-        if ((int)s.nfft != 1024 || force_list) {                      // a short interval: the workgroup kernel takes the frame
-            if (lane == 0) {
-                const int at = atomicAdd(list_count, 1);
-                if (at < list_cap) { list[2 * at] = clip; list[2 * at + 1] = f; }
-            }
-            continue;
-        }
+        const Seg s = cs.of_frame(f);
+        if (listed_instead(s, force_list, lane, flist, clip, f)) continue;
         const int fl = f - (int)s.frame_off;
         const int nx = (int)s.nx, m_out = (int)s.m_out;
         const double* y = res + (int64_t)clip * cap_res + (int64_t)s.res_off;
-        const double t = s.t1 + (double)fl * DT;
-        const int idx0 = (int)floor((t - 0.5 * s.window - s.x1o) / DXO + 0.5);   // Sampled_xToNearestIndex, 0-based
+        const int idx0 = frame_first_index<int>(s, fl);
         // gather with the pre-emphasis y[j] - a y[j-1] (the first sample of the sound is kept): element k = lane + 64 m of
         // the packed frame holds samples 2 k and 2 k + 1.  Loads are unconditional on clamped indices.
         cplx v[R];
@@ -493,7 +452,7 @@ __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restr
             sum += e0 + e1;
         }
         const double mean = wave_sum_f64(sum) / (double)nx;
-        const double imid = 0.5 * (nx + 1), edge = exp(-12.0);
+        const GaussWindow gw(nx);
 #pragma unroll
         for (int m = 0; m < R; ++m) {
             const int i0 = 2 * (lane + 64 * m);
@@ -502,9 +461,8 @@ __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restr
                 w0 = win1000[i0 < 999 ? i0 : 999];
                 w1 = win1000[i0 + 1 < 999 ? i0 + 1 : 999];
             } else {
-                const double d0 = (double)(i0 + 1) - imid, d1 = (double)(i0 + 2) - imid, q = (double)((nx + 1) * (nx + 1));
-                w0 = (exp(-48.0 * (d0 * d0) / q) - edge) / (1.0 - edge);
-                w1 = (exp(-48.0 * (d1 * d1) / q) - edge) / (1.0 - edge);
+                w0 = gw.at(i0);
+                w1 = gw.at(i0 + 1);
             }
             v[m] = cplx{i0 < nx ? (v[m].x - mean) * w0 : 0.0, i0 + 1 < nx ? (v[m].y - mean) * w1 : 0.0};
         }
@@ -519,10 +477,9 @@ __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restr
             const int pp = k ? S / 2 - k : 0;
             cplx zc{mem.ld(pp), mem.ld(S / 2 + pp)};
             if (m == 0) zc = cplx{lane == 0 ? v[0].x : zc.x, lane == 0 ? v[0].y : zc.y};
-            const cplx zk = v[m], w = mul_w64(wl, m * 4);                       // W_1024^(64 m) = W_64^(4 m)
-            const double er = 0.5 * (zk.x + zc.x), ei = 0.5 * (zk.y - zc.y), orr = 0.5 * (zk.y + zc.y), oi = -0.5 * (zk.x - zc.x);
-            const double tr = w.x * orr - w.y * oi, ti = w.x * oi + w.y * orr;
-            const double ar = (er + tr) * DXO, ai = (ei + ti) * DXO, br = (er - tr) * DXO, bi = (ti - ei) * DXO;
+            cplx xa, xb;
+            real_split(v[m], zc, mul_w64(wl, m * 4), &xa, &xb);                 // W_1024^(64 m) = W_64^(4 m)
+            const double ar = xa.x * DXO, ai = xa.y * DXO, br = xb.x * DXO, bi = xb.y * DXO;
             lp[k] = log(ar * ar + ai * ai + 1e-300);
             lp[S - k] = log(br * br + bi * bi + 1e-300);                        // k = 0: bin 512 = Re Z[0] - Im Z[0]
         }
@@ -549,10 +506,9 @@ __global__ __launch_bounds__(64, 4) void cepstrum_wave_kernel(const Seg* __restr
             const int pp = k ? S / 2 - k : 0;
             cplx zc{mem.ld(pp), mem.ld(S / 2 + pp)};
             if (m == 0) zc = cplx{lane == 0 ? v[0].x : zc.x, lane == 0 ? v[0].y : zc.y};
-            const cplx zk = v[m], w = mul_w64(wl, m * 4);
-            const double er = 0.5 * (zk.x + zc.x), orr = 0.5 * (zk.y + zc.y), oi = -0.5 * (zk.x - zc.x);
-            const double tr = w.x * orr - w.y * oi;
-            const double ca = (er + tr) * sdx, cb = (er - tr) * sdx;
+            cplx xa, xb;
+            real_split(v[m], zc, mul_w64(wl, m * 4), &xa, &xb);                 // the cepstrum is real: only the real parts
+            const double ca = xa.x * sdx, cb = xb.x * sdx;
             o[k] = ca * ca;
             o[S - k] = cb * cb;
         }
@@ -642,6 +598,35 @@ __device__ double quantile_half(const double* a, int n) {     // Praat NUMquanti
     return a[left - 1] + (place - left) * (a[left] - a[left - 1]);
 }
 
+// Vector_getMaximumAndX (parabolic) over the bins [imin, imax]: the end points first, then the local maxima in ascending
+// order, a later candidate wins only if strictly greater -> every thread keeps its best candidate with the order in
+// which the sequential search would have met it, and candidates are merged by (value, order).
+struct PeakCand {
+    double best = -INFINITY, bx = 0.0;
+    int bord = 0x7fffffff;
+    __device__ __forceinline__ void set(double value, double x, int order) { best = value; bx = x; bord = order; }
+    __device__ __forceinline__ bool loses_to(double ov, int oo) const { return ov > best || (ov == best && oo < bord); }
+    // the two end points: bin imin is the start value, bin imax replaces it only if strictly greater
+    __device__ __forceinline__ void end_points(int t, const double* db, int imin, int imax) {
+        if (t == 0) set(db[imin], (double)imin, 0);
+        if (t == 1 && db[imax] > db[imin]) set(db[imax], (double)imax, 1);
+    }
+    // bin i, a local maximum (dc > dl && dc >= dr) with the neighbours dl, dr: the parabola's vertex is the candidate
+    __device__ __forceinline__ void vertex(double dl, double dc, double dr, int i) {
+        const double dy = 0.5 * (dr - dl), d2y = 2.0 * dc - dl - dr;
+        const double v = dc + 0.5 * dy * dy / d2y;
+        if (v > best) set(v, (double)i + dy / d2y, 2 + i);
+    }
+    __device__ __forceinline__ void wave_reduce() {
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const double ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64);
+            const int oo = __shfl_xor(bord, o, 64);
+            if (loses_to(ov, oo)) set(ov, ox, oo);
+        }
+    }
+};
+
 __global__ __launch_bounds__(256) void cpp_frame_kernel(const Seg* __restrict__ segs, int max_seg, const int* __restrict__ hdr,
                                                         const double* __restrict__ ceps, int cap_frames, int n_time,
                                                         int n_quef, double pitch_floor, double pitch_ceiling,
@@ -656,19 +641,12 @@ __global__ __launch_bounds__(256) void cpp_frame_kernel(const Seg* __restrict__ 
     for (int item = blockIdx.x; item < count; item += gridDim.x) {
     __syncthreads();                                    // the previous frame's readers of the shared arrays are done
     const int clip = list[2 * item], f = list[2 * item + 1];
-    const int nseg = hdr[4 * clip];
-    const Seg* S = segs + (int64_t)clip * max_seg;
-    const Seg s = S[find_seg<4>(S, nseg, f)];
+    const Seg s = clip_segs(segs, max_seg, hdr, clip).of_frame(f);
     const int fl = f - (int)s.frame_off, nf = (int)s.nf, nfft = (int)s.nfft, nq = nfft / 2 + 1;
     const double* Z = ceps + ((int64_t)clip * cap_frames + (int64_t)s.frame_off) * NQ_MAX;   // frames of this interval
-    // moving average over time (VECsmoothByMovingAverage: [i - w/2, i + w/2], one less on the right for even w)
+    // moving average over time
     int lo = fl, hi = fl;
-    if (n_time > 1) {
-        lo = fl - n_time / 2;
-        hi = fl + n_time / 2 - ((n_time & 1) == 0 ? 1 : 0);
-        lo = lo < 0 ? 0 : lo;
-        hi = hi > nf - 1 ? nf - 1 : hi;
-    }
+    if (n_time > 1) moving_average_range(fl, n_time, nf, &lo, &hi);
     for (int q = tid; q < nq; q += 256) {
         double v = 0.0;
         for (int j = lo; j <= hi; ++j) v += Z[(int64_t)j * NQ_MAX + q];
@@ -679,9 +657,8 @@ __global__ __launch_bounds__(256) void cpp_frame_kernel(const Seg* __restrict__ 
     for (int q = tid; q < nq; q += 256) {
         double v = zt[q];
         if (n_quef > 1) {
-            int a = q - n_quef / 2, b = q + n_quef / 2 - ((n_quef & 1) == 0 ? 1 : 0);
-            a = a < 0 ? 0 : a;
-            b = b > nq - 1 ? nq - 1 : b;
+            int a, b;
+            moving_average_range(q, n_quef, nq, &a, &b);
             v = 0.0;
             for (int j = a; j <= b; ++j) v += zt[j];
             v /= (double)(b - a + 1);
@@ -690,7 +667,7 @@ __global__ __launch_bounds__(256) void cpp_frame_kernel(const Seg* __restrict__ 
     }
     __syncthreads();
     // Theil's incomplete method over all nq points: slope = median of the nc half-distance slopes ...
-    const int nc = nq / 2, n2 = (nq & 1) ? nc + 1 : nc;
+    const int nc = theil_n(nq).nc, n2 = theil_n(nq).n2;
     int p2 = 1;
     while (p2 < nc) p2 <<= 1;
     for (int i = tid; i < p2; i += 256)
@@ -711,51 +688,31 @@ __global__ __launch_bounds__(256) void cpp_frame_kernel(const Seg* __restrict__ 
         __syncthreads();
         sort_lds(srt, hn, tid);
         const double e = db[nq - 1] - slope * ((double)(nq - 1) * DQ);
-        const double lo_v = srt[hn / 2 - 1], hi_v = srt[hn / 2];  // the middle of the union is the median of (lo, e, hi)
-        icpt = e <= lo_v ? lo_v : (e >= hi_v ? hi_v : e);
+        icpt = median3_clamp(e, srt[hn / 2 - 1], srt[hn / 2]);    // the middle of the union is the median of (lo, e, hi)
     } else {
         for (int i = tid; i < p2; i += 256) srt[i] = i < nq ? db[i] - slope * ((double)i * DQ) : INFINITY;
         __syncthreads();
         sort_lds(srt, p2, tid);
         icpt = quantile_half(srt, nq);
     }
-    // Vector_getMaximumAndX (parabolic) over [1/ceiling, 1/floor]: end points first, then the local maxima in
-    // ascending order, a later candidate wins only if strictly greater -> (value, order) reduction
+    // the peak over [1/ceiling, 1/floor]
     const double qlo = 1.0 / pitch_ceiling, qhi = 1.0 / pitch_floor;
-    int imin = (int)ceil(qlo / DQ), imax = (int)floor(qhi / DQ);
-    imax = imax > nq - 1 ? nq - 1 : imax;
-    double best = -INFINITY, bx = 0.0;
-    int bord = 0x7fffffff;
+    int imin, imax;
+    peak_bounds(qlo, qhi, nq, &imin, &imax);
+    PeakCand pk;
     if (imax >= imin) {
-        if (tid == 0) { best = db[imin]; bx = (double)imin; bord = 0; }
-        if (tid == 1 && db[imax] > db[imin]) { best = db[imax]; bx = (double)imax; bord = 1; }
+        pk.end_points(tid, db, imin, imax);
         const int a = imin < 1 ? 1 : imin, b = imax > nq - 2 ? nq - 2 : imax;
-        for (int i = a + tid; i <= b; i += 256) {
-            if (db[i] > db[i - 1] && db[i] >= db[i + 1]) {
-                const double dy = 0.5 * (db[i + 1] - db[i - 1]), d2y = 2.0 * db[i] - db[i - 1] - db[i + 1];
-                const double v = db[i] + 0.5 * dy * dy / d2y;
-                if (v > best) { best = v; bx = (double)i + dy / d2y; bord = 2 + i; }
-            }
-        }
+        for (int i = a + tid; i <= b; i += 256)
+            if (db[i] > db[i - 1] && db[i] >= db[i + 1]) pk.vertex(db[i - 1], db[i], db[i + 1], i);
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-        const double ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64);
-        const int oo = __shfl_xor(bord, o, 64);
-        if (ov > best || (ov == best && oo < bord)) { best = ov; bx = ox; bord = oo; }
-    }
-    if (lane == 0) { s_val[wv] = best; s_xq[wv] = bx; s_ord[wv] = bord; }
+    pk.wave_reduce();
+    if (lane == 0) { s_val[wv] = pk.best; s_xq[wv] = pk.bx; s_ord[wv] = pk.bord; }
     __syncthreads();
     if (tid == 0) {
         for (int w = 1; w < 4; ++w)
-            if (s_val[w] > best || (s_val[w] == best && s_ord[w] < bord)) { best = s_val[w]; bx = s_xq[w]; bord = s_ord[w]; }
-        double out = __longlong_as_double(0x7ff8000000000000LL);
-        if (imax >= imin) {
-            double qpeak = bx * DQ;
-            qpeak = qpeak < qlo ? qlo : (qpeak > qhi ? qhi : qpeak);
-            out = best - (slope * qpeak + icpt);
-        }
-        cpp_out[(int64_t)clip * cap_frames + f] = out;
+            if (pk.loses_to(s_val[w], s_ord[w])) pk.set(s_val[w], s_xq[w], s_ord[w]);
+        cpp_out[(int64_t)clip * cap_frames + f] = cpp_value(pk.best, pk.bx, slope, icpt, qlo, qhi, imax >= imin);
     }
     }
 }
@@ -808,8 +765,6 @@ __device__ __forceinline__ void wave_select_pair(const double (&x)[E], int t, do
     b = mn;
 }
 
-constexpr int CPPF_FRAMES = 4;
-
 __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __restrict__ segs, int max_seg, const int* __restrict__ hdr,
                                                                const double* __restrict__ ceps, int cap_frames, int n_time,
                                                                int n_quef, double pitch_floor, double pitch_ceiling,
@@ -817,38 +772,25 @@ __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __rest
                                                                int* __restrict__ list_count, int list_cap, int force_list) {
     __shared__ double sq[NQ_MAX + 7];                    // smoothed power per bin, then dB per bin
     constexpr int NQ = NQ_MAX;                           // 513
+    constexpr TheilN TH = theil_n(NQ);                   // 256 slopes between the bins i and 257 + i
     const int clip = blockIdx.y;
-    const int nseg = hdr[4 * clip];
-    if (nseg <= 0) return;
-    const int nframes = hdr[4 * clip + 2];
-    const int f0 = blockIdx.x * CPPF_FRAMES;
-    if (f0 >= nframes) return;
-    const Seg* SG = segs + (int64_t)clip * max_seg;
+    ClipSegs cs;
+    int f0, f1;
+    if (!wave_frames(segs, max_seg, hdr, clip, CPPF_FRAMES, &cs, &f0, &f1)) return;
+    const FrameList flist(list, list_count, list_cap);
     const int lane_ = threadIdx.x;
-    const int f1 = f0 + CPPF_FRAMES < nframes ? f0 + CPPF_FRAMES : nframes;
     const double qlo = 1.0 / pitch_ceiling, qhi = 1.0 / pitch_floor;
 #pragma unroll 1
     for (int f = f0; f < f1; ++f) {
         int lane = lane_;
         asm volatile("" : "+v"(lane));
-        const Seg s = SG[find_seg<4>(SG, nseg, f)];
-        if ((int)s.nfft != 1024 || force_list) {                      // a short interval: the workgroup kernel takes the frame
-            if (lane == 0) {
-                const int at = atomicAdd(list_count, 1);
-                if (at < list_cap) { list[2 * at] = clip; list[2 * at + 1] = f; }
-            }
-            continue;
-        }
+        const Seg s = cs.of_frame(f);
+        if (listed_instead(s, force_list, lane, flist, clip, f)) continue;
         const int fl = f - (int)s.frame_off, nf = (int)s.nf;
         const double* Z = ceps + ((int64_t)clip * cap_frames + (int64_t)s.frame_off) * NQ_MAX;   // frames of this interval
-        // moving average over time (VECsmoothByMovingAverage: [i - w/2, i + w/2], one less on the right for even w)
+        // moving average over time
         int lo = fl, hi = fl;
-        if (n_time > 1) {
-            lo = fl - n_time / 2;
-            hi = fl + n_time / 2 - ((n_time & 1) == 0 ? 1 : 0);
-            lo = lo < 0 ? 0 : lo;
-            hi = hi > nf - 1 ? nf - 1 : hi;
-        }
+        if (n_time > 1) moving_average_range(fl, n_time, nf, &lo, &hi);
         const int q0 = 8 * lane;
         double zt[9];
 #pragma unroll
@@ -883,10 +825,8 @@ __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __rest
             }
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
-                const int q = q0 + e;
-                int a = q - 5, b = q + 4;
-                a = a < 0 ? 0 : a;
-                b = b > NQ - 1 ? NQ - 1 : b;
+                int a, b;
+                moving_average_range(q0 + e, 10, NQ, &a, &b);
                 double v = 0.0;
 #pragma unroll
                 for (int i = 0; i < 10; ++i) v += w[e + i];   // entries outside [0, 512] are 0.0: the sum is the one over [a, b]
@@ -899,9 +839,8 @@ __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __rest
                 const int q = q0 + e < NQ ? q0 + e : NQ - 1;
                 double v = sq[q];
                 if (n_quef > 1) {
-                    int a = q - n_quef / 2, b = q + n_quef / 2 - ((n_quef & 1) == 0 ? 1 : 0);
-                    a = a < 0 ? 0 : a;
-                    b = b > NQ - 1 ? NQ - 1 : b;
+                    int a, b;
+                    moving_average_range(q, n_quef, NQ, &a, &b);
                     v = 0.0;
                     for (int j = a; j <= b; ++j) v += sq[j];
                     v /= (double)(b - a + 1);
@@ -919,10 +858,10 @@ __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __rest
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int i = 4 * lane + e;
-            sl[e] = (sq[257 + i] - sq[i]) / ((double)(257 + i) * DQ - (double)i * DQ);
+            sl[e] = (sq[TH.n2 + i] - sq[i]) / ((double)(TH.n2 + i) * DQ - (double)i * DQ);
         }
         double m0, m1;
-        wave_select_pair<4>(sl, 127, m0, m1);                                   // NUMquantile(0.5) of 256: place 128.5
+        wave_select_pair<4>(sl, TH.nc / 2 - 1, m0, m1);                         // NUMquantile(0.5) of 256: place 128.5
         const double slope = m1 == m0 ? m0 : m0 + 0.5 * (m1 - m0);
         // ... intercept = median of the 513 residual offsets: the ranks 255 and 256 of the first 512 bracket it
         double rs[8];
@@ -931,44 +870,24 @@ __global__ __launch_bounds__(64, 4) void cpp_frame_wave_kernel(const Seg* __rest
         double lo_v, hi_v;
         wave_select_pair<8>(rs, 255, lo_v, hi_v);
         const double e512 = sq[NQ - 1] - slope * ((double)(NQ - 1) * DQ);
-        const double icpt = e512 <= lo_v ? lo_v : (e512 >= hi_v ? hi_v : e512);
-        // Vector_getMaximumAndX (parabolic) over [1/ceiling, 1/floor]: end points first, then the local maxima in
-        // ascending order, a later candidate wins only if strictly greater -> (value, order) reduction
-        int imin = (int)ceil(qlo / DQ), imax = (int)floor(qhi / DQ);
-        imax = imax > NQ - 1 ? NQ - 1 : imax;
-        double best = -INFINITY, bx = 0.0;
-        int bord = 0x7fffffff;
+        const double icpt = median3_clamp(e512, lo_v, hi_v);
+        // the peak over [1/ceiling, 1/floor]
+        int imin, imax;
+        peak_bounds(qlo, qhi, NQ, &imin, &imax);
+        PeakCand pk;
         if (imax >= imin) {
-            if (lane == 0) { best = sq[imin]; bx = (double)imin; bord = 0; }
-            if (lane == 1 && sq[imax] > sq[imin]) { best = sq[imax]; bx = (double)imax; bord = 1; }
+            pk.end_points(lane, sq, imin, imax);
             const int a = imin < 1 ? 1 : imin, b = imax > NQ - 2 ? NQ - 2 : imax;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int i = q0 + e;
                 const int il = i >= 1 ? i - 1 : 0, ir = i + 1 <= NQ - 1 ? i + 1 : NQ - 1;
                 const double dl = sq[il], dc = db[e], dr = sq[ir];
-                if (i >= a && i <= b && dc > dl && dc >= dr) {
-                    const double dy = 0.5 * (dr - dl), d2y = 2.0 * dc - dl - dr;
-                    const double v = dc + 0.5 * dy * dy / d2y;
-                    if (v > best) { best = v; bx = (double)i + dy / d2y; bord = 2 + i; }
-                }
+                if (i >= a && i <= b && dc > dl && dc >= dr) pk.vertex(dl, dc, dr, i);
             }
         }
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            const double ov = __shfl_xor(best, o, 64), ox = __shfl_xor(bx, o, 64);
-            const int oo = __shfl_xor(bord, o, 64);
-            if (ov > best || (ov == best && oo < bord)) { best = ov; bx = ox; bord = oo; }
-        }
-        if (lane == 0) {
-            double out = __longlong_as_double(0x7ff8000000000000LL);
-            if (imax >= imin) {
-                double qpeak = bx * DQ;
-                qpeak = qpeak < qlo ? qlo : (qpeak > qhi ? qhi : qpeak);
-                out = best - (slope * qpeak + icpt);
-            }
-            cpp_out[(int64_t)clip * cap_frames + f] = out;
-        }
+        pk.wave_reduce();
+        if (lane == 0) cpp_out[(int64_t)clip * cap_frames + f] = cpp_value(pk.best, pk.bx, slope, icpt, qlo, qhi, imax >= imin);
         wfft::wave_sync();                              // the next frame rewrites sq
     }
 }
@@ -979,8 +898,8 @@ __global__ __launch_bounds__(256) void reduce_kernel(const Seg* __restrict__ seg
                                                      double* __restrict__ out) {
     __shared__ double s_red[4];
     const int clip = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int nseg = hdr[4 * clip], fail = hdr[4 * clip + 1];
-    const Seg* S = segs + (int64_t)clip * max_seg;
+    const auto [nseg, S] = clip_segs(segs, max_seg, hdr, clip);
+    const int fail = ClipHdr::at(hdr, clip)->fail;
     const double* F = cpp_frames + (int64_t)clip * cap_frames;
     double total = 0.0;
     int kept = 0;
@@ -1004,6 +923,172 @@ __global__ __launch_bounds__(256) void reduce_kernel(const Seg* __restrict__ seg
 using namespace rsaf;
 using namespace rsaf::mshds_cpp;
 
+namespace {
+
+// errors of every function below carry the name of the entry point
+#define CPP_CHECK_ARG(cond, msg)                                                    \
+    do {                                                                            \
+        if (!(cond)) {                                                              \
+            ::rsaf::set_error(std::string("rsaf_mshds_cpp: ") + (msg));             \
+            return RSAF_ERR_ARG;                                                    \
+        }                                                                           \
+    } while (0)
+#define CPP_CHECK_HIP(expr)                                                         \
+    do {                                                                            \
+        hipError_t _e = (expr);                                                     \
+        if (_e != hipSuccess) {                                                     \
+            ::rsaf::set_error(std::string("rsaf_mshds_cpp: " #expr " -> ") + hipGetErrorString(_e)); \
+            return RSAF_ERR_HIP;                                                    \
+        }                                                                           \
+    } while (0)
+
+constexpr int LG_LDS = 14;           // longest low-pass transform held whole in LDS: 2^13 complex numbers = 128 KB
+
+// One call: the operands as the kernels take them and what cpp_plan derives from them.
+struct CppCall {
+    const float* wav;
+    const ClipInfo* ci;
+    int n_clips;
+    const double* pulses;
+    int max_pulses;
+    const int* n_pulses;
+    const double* window1000;
+    const double2* twiddle1024;
+    int max_seg, cap_res, cap_frames;
+    Seg* segs;
+    int* hdr;
+    double *resampled, *cepstrogram, *cpp_frames, *lowpassed;
+    int64_t lp_origin;
+    resample::c64* lp_work;
+    int64_t cap_work;
+    int lg_max;
+    double* out;
+    hipStream_t stream;
+    // derived
+    FrameList list{nullptr, nullptr, 0};   // in lp_work, once the intervals are resampled
+    int force_list = 0;                    // RSAF_CPP_WAVE; bit 0: cepstrum through the list, bit 1: smoothed-CPP frames through the list
+    int polyphase = 1;                     // RSAF_CPP_POLYPHASE
+    int lg_whole = 0;                      // intervals up to 2^lg_whole samples: seg_lowpass_lds_kernel with lds_whole bytes
+    size_t lds_whole = 0;
+    int lg_pass_lo = 0, lg_pass_hi = -1;   // longer ones (none when lo > hi): the three passes with lds_pass bytes
+    size_t lds_pass = 0;
+};
+
+// Every argument check of a call, the two environment switches and the geometry of its launches; makes no HIP call.
+int cpp_plan(CppCall& c) {
+    CPP_CHECK_ARG(c.n_clips >= 0 && c.n_clips <= 65535 && c.max_pulses >= 0, "bad clip/pulse count");
+    if (c.n_clips == 0) return RSAF_OK;
+    CPP_CHECK_ARG(c.wav && c.ci && c.pulses && c.n_pulses && c.window1000 && c.twiddle1024 && c.segs && c.hdr && c.resampled &&
+                  c.cepstrogram && c.cpp_frames && c.lowpassed && c.lp_work && c.out, "NULL pointer");
+    CPP_CHECK_ARG(c.max_seg >= 1 && c.cap_res >= 1 && c.cap_frames >= 1 && c.cap_frames <= 65535 * 32 && c.cap_work >= 1024 &&
+                  c.lg_max >= 11 && c.lg_max <= resample::LP_LG_MAX, "bad capacities");
+    c.list = FrameList(c.lp_work, c.n_clips, c.cap_work);
+    CPP_CHECK_ARG(c.list.holds((int64_t)c.n_clips * c.cap_frames), "frame list smaller than the frame count");
+    const char* pe = getenv("RSAF_CPP_POLYPHASE");
+    c.polyphase = (pe && pe[0] == '0') ? 0 : 1;
+    // RSAF_CPP_WAVE: "0" = both per-frame kernels in their workgroup form, "c" = only the cepstrum by one wave per frame
+    const char* we = getenv("RSAF_CPP_WAVE");
+    c.force_list = !we ? 0 : (we[0] == '0' ? 3 : (we[0] == 'c' ? 2 : 0));
+    c.lg_whole = std::min(LG_LDS, c.lg_max);
+    c.lds_whole = ((size_t)1 << (c.lg_whole - 1)) * sizeof(resample::c64);
+    if (c.lg_max > LG_LDS) {
+        c.lg_pass_lo = LG_LDS + 1;
+        c.lg_pass_hi = c.lg_max;
+        for (int lg = c.lg_pass_lo; lg <= c.lg_pass_hi; ++lg) {
+            const resample::LpGeom g = resample::lp_geom(lg);
+            c.lds_pass = std::max(c.lds_pass, std::max(((size_t)g.C << g.log1), ((size_t)2 << g.log2)) * sizeof(resample::c64));
+        }
+    }
+    return RSAF_OK;
+}
+
+int launch_segments(const CppCall& c) {
+    hipLaunchKernelGGL(segments_kernel, dim3(c.n_clips), dim3(64), 0, c.stream, c.ci, c.pulses, c.max_pulses, c.n_pulses, 0.02, 0.1,
+                       60.0, c.segs, c.max_seg, c.cap_res, c.cap_frames, c.cap_work, c.lg_max, c.hdr);
+    CPP_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// Praat's FFT low-pass of every interval: the short ones whole in LDS, the long ones by the three passes over lp_work
+int launch_lowpass(const CppCall& c) {
+    resample::LpTables T;
+    const int rc = resample::lp_tables((int64_t)1 << c.lg_max, &T);
+    if (rc != RSAF_OK) return rc;
+    T.lg_max = c.lg_max;
+    if (c.lds_whole > 48 * 1024)
+        CPP_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.lds_whole));
+    hipLaunchKernelGGL(seg_lowpass_lds_kernel, dim3(32, c.n_clips), dim3(1024), c.lds_whole, c.stream, c.wav, c.ci, c.segs, c.max_seg,
+                       c.hdr, c.lowpassed, c.lp_origin, c.lg_whole, T);
+    if (c.lg_pass_lo > c.lg_pass_hi) return RSAF_OK;
+    const size_t lds = c.lds_pass;
+    if (lds > 48 * 1024) {
+        CPP_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CPP_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CPP_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    const dim3 grid(64, c.n_clips);                                      // workgroups that walk the items of a clip
+#define CPP_LOWPASS_PASS(P)                                                                                                      \
+    hipLaunchKernelGGL(seg_lowpass_kernel<P>, grid, dim3(256), lds, c.stream, c.wav, c.ci, c.segs, c.max_seg, c.hdr, c.lp_work,  \
+                       c.cap_work, c.lowpassed, c.lp_origin, c.lg_pass_lo, c.lg_pass_hi, T)
+    CPP_LOWPASS_PASS(0);
+    CPP_LOWPASS_PASS(1);
+    CPP_LOWPASS_PASS(2);
+#undef CPP_LOWPASS_PASS
+    return RSAF_OK;
+}
+
+int launch_resample(const CppCall& c) {
+    hipLaunchKernelGGL(resample_kernel, dim3((c.cap_res + 255) / 256, c.n_clips), dim3(256), 0, c.stream, (const double*)c.lowpassed,
+                       c.lp_origin, c.ci, c.segs, c.max_seg, c.hdr, c.cap_res, c.resampled, c.polyphase);
+    CPP_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// frames with the full 1024-point transform: one wave each; the others are listed and taken by the workgroup kernel
+int launch_cepstra(const CppCall& c) {
+    const FrameList& l = c.list;
+    CPP_CHECK_HIP(hipMemsetAsync(l.count, 0, sizeof(int), c.stream));
+    const double pre = exp(-2.0 * PI * 50.0 * DXO);
+    hipLaunchKernelGGL(cepstrum_wave_kernel, dim3((c.cap_frames + CEP_FRAMES - 1) / CEP_FRAMES, c.n_clips), dim3(64), 0, c.stream,
+                       c.segs, c.max_seg, c.hdr, c.resampled, c.cap_res, c.cap_frames, c.window1000, c.twiddle1024, pre, c.cepstrogram,
+                       l.entries, l.count, l.cap, c.force_list & 1);
+    CPP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cepstrum_kernel, dim3(2048), dim3(256), 0, c.stream, c.segs, c.max_seg, c.hdr, c.resampled, c.cap_res,
+                       c.cap_frames, c.window1000, c.twiddle1024, pre, c.cepstrogram, l.entries, l.count, l.cap);
+    CPP_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+// "Get CPPS" 0.01 s, 0.001 s, 60 - 330 Hz per frame, the same split between the two kernel forms
+int launch_frames(const CppCall& c) {
+    const FrameList& l = c.list;
+    const int n_time = (int)floor(0.01 / DT), n_quef = (int)floor(0.001 / DQ);
+    CPP_CHECK_HIP(hipMemsetAsync(l.count, 0, sizeof(int), c.stream));
+    hipLaunchKernelGGL(cpp_frame_wave_kernel, dim3((c.cap_frames + CPPF_FRAMES - 1) / CPPF_FRAMES, c.n_clips), dim3(64), 0, c.stream,
+                       c.segs, c.max_seg, c.hdr, c.cepstrogram, c.cap_frames, n_time, n_quef, 60.0, 330.0, c.cpp_frames, l.entries,
+                       l.count, l.cap, c.force_list & 2);
+    CPP_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(cpp_frame_kernel, dim3(2048), dim3(256), 0, c.stream, c.segs, c.max_seg, c.hdr, c.cepstrogram, c.cap_frames,
+                       n_time, n_quef, 60.0, 330.0, c.cpp_frames, l.entries, l.count, l.cap);
+    CPP_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int launch_reduce(const CppCall& c) {
+    hipLaunchKernelGGL(reduce_kernel, dim3(c.n_clips), dim3(256), 0, c.stream, c.segs, c.max_seg, c.hdr, c.cpp_frames, c.cap_frames,
+                       4.0, c.out);
+    CPP_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+#define CPP_TRY(call)                                                               \
+    do {                                                                            \
+        const int _rc = (call);                                                     \
+        if (_rc != RSAF_OK) return _rc;                                             \
+    } while (0)
+
+}  // namespace
+
 extern "C" {
 
 int rsaf_mshds_cpp_seg_doubles(void) { return SEG_DOUBLES; }
@@ -1013,105 +1098,17 @@ int rsaf_mshds_cpp(const float* wav, const void* clip_info, int n_clips, const d
                    int cap_frames, void* seg_table, int* hdr, double* resampled, double* cepstrogram, double* cpp_frames,
                    double* lowpassed, int64_t lp_origin, void* lp_work, int64_t cap_work, int lg_max, double* out,
                    rsaf_stream_t stream) {
-    RSAF_CHECK_ARG(n_clips >= 0 && n_clips <= 65535 && max_pulses >= 0, "bad clip/pulse count");
+    CppCall c{wav, (const ClipInfo*)clip_info, n_clips, pulses, max_pulses, n_pulses, window1000, (const double2*)twiddle1024,
+              max_seg, cap_res, cap_frames, (Seg*)seg_table, hdr, resampled, cepstrogram, cpp_frames, lowpassed, lp_origin,
+              (resample::c64*)lp_work, cap_work, lg_max, out, (hipStream_t)stream};
+    CPP_TRY(cpp_plan(c));
     if (n_clips == 0) return RSAF_OK;
-    RSAF_CHECK_ARG(wav && clip_info && pulses && n_pulses && window1000 && twiddle1024 && seg_table && hdr && resampled &&
-                   cepstrogram && cpp_frames && lowpassed && lp_work && out, "NULL pointer");
-    RSAF_CHECK_ARG(max_seg >= 1 && cap_res >= 1 && cap_frames >= 1 && cap_frames <= 65535 * 32 && cap_work >= 1024 &&
-                   lg_max >= 11 && lg_max <= resample::LP_LG_MAX, "bad capacities");
-    hipStream_t s = (hipStream_t)stream;
-    const ClipInfo* ci = (const ClipInfo*)clip_info;
-    Seg* segs = (Seg*)seg_table;
-    {
-        ProfScope prof("mshds_cpp_segments", s, 0.0, 0.0);
-        hipLaunchKernelGGL(segments_kernel, dim3(n_clips), dim3(64), 0, s, ci, pulses, max_pulses, n_pulses, 0.02, 0.1, 60.0,
-                           segs, max_seg, cap_res, cap_frames, cap_work, lg_max, hdr);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    {
-        ProfScope prof("mshds_cpp_resample", s, 0.0, 0.0);
-        resample::LpTables T;
-        const int rc = resample::lp_tables((int64_t)1 << lg_max, &T);
-        if (rc != RSAF_OK) return rc;
-        T.lg_max = lg_max;
-        auto lds_for = [](int lg_a, int lg_b) {
-            size_t lds = 0;
-            for (int lg = lg_a; lg <= lg_b; ++lg) {
-                const resample::LpGeom g = resample::lp_geom(lg);
-                lds = std::max(lds, std::max(((size_t)g.C << g.log1), ((size_t)2 << g.log2)) * sizeof(resample::c64));
-            }
-            return lds;
-        };
-        constexpr int LG_LDS = 14;                                           // 2^13 complex numbers = 128 KB of LDS
-        resample::c64* wk = (resample::c64*)lp_work;
-        {
-            const int lg_hi = std::min(LG_LDS, lg_max);
-            const size_t lds = ((size_t)1 << (lg_hi - 1)) * sizeof(resample::c64);
-            if (lds > 48 * 1024)
-                RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(seg_lowpass_lds_kernel, dim3(32, n_clips), dim3(1024), lds, s, wav, ci, segs, max_seg, hdr, lowpassed,
-                               lp_origin, lg_hi, T);
-        }
-        if (lg_max > LG_LDS) {
-            const int lg_lo = LG_LDS + 1, lg_hi = lg_max;
-            const size_t lds = lds_for(lg_lo, lg_hi);
-            if (lds > 48 * 1024) {
-                RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                RSAF_CHECK_HIP(hipFuncSetAttribute((const void*)seg_lowpass_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            }
-            const dim3 grid(64, n_clips);                                    // workgroups that walk the items of a clip
-            hipLaunchKernelGGL(seg_lowpass_kernel<0>, grid, dim3(256), lds, s, wav, ci, segs, max_seg, hdr, wk, cap_work, lowpassed, lp_origin, lg_lo, lg_hi, T);
-            hipLaunchKernelGGL(seg_lowpass_kernel<1>, grid, dim3(256), lds, s, wav, ci, segs, max_seg, hdr, wk, cap_work, lowpassed, lp_origin, lg_lo, lg_hi, T);
-            hipLaunchKernelGGL(seg_lowpass_kernel<2>, grid, dim3(256), lds, s, wav, ci, segs, max_seg, hdr, wk, cap_work, lowpassed, lp_origin, lg_lo, lg_hi, T);
-        }
-        const char* pe = getenv("RSAF_CPP_POLYPHASE");
-        hipLaunchKernelGGL(resample_kernel, dim3((cap_res + 255) / 256, n_clips), dim3(256), 0, s, (const double*)lowpassed, lp_origin,
-                           ci, segs, max_seg, hdr, cap_res, resampled, (pe && pe[0] == '0') ? 0 : 1);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    int force_list = 0;
-    // RSAF_CPP_WAVE: "0" = both per-frame kernels in their workgroup form, "c" = only the cepstrum by one wave per frame
-    // (bit 0: cepstrum through the list, bit 1: smoothed-CPP frames through the list)
-    { const char* e = getenv("RSAF_CPP_WAVE"); force_list = !e ? 0 : (e[0] == '0' ? 3 : (e[0] == 'c' ? 2 : 0)); }
-    {
-        ProfScope prof("mshds_cpp_cepstrum", s, 0.0, 0.0);
-        // frames with the full 1024-point transform: one wave each; the others are listed in lp_work (free once the intervals
-        // are resampled; the counter is its last slot) and taken by the workgroup kernel
-        const int64_t lp_doubles = (int64_t)n_clips * cap_work * 2;
-        int* list = reinterpret_cast<int*>(lp_work);
-        int* list_count = list + 2 * (lp_doubles - 1);
-        const int list_cap = (int)std::min<int64_t>(lp_doubles - 1, 0x7fffffff);
-        // every frame of every clip may be listed at most once: the list holds them all, nothing can be dropped
-        RSAF_CHECK_ARG((int64_t)n_clips * cap_frames <= list_cap, "frame list smaller than the frame count");
-        RSAF_CHECK_HIP(hipMemsetAsync(list_count, 0, sizeof(int), s));
-        const double pre = exp(-2.0 * PI * 50.0 * DXO);
-        hipLaunchKernelGGL(cepstrum_wave_kernel, dim3((cap_frames + CEP_FRAMES - 1) / CEP_FRAMES, n_clips), dim3(64), 0, s, segs,
-                           max_seg, hdr, resampled, cap_res, cap_frames, window1000, (const double2*)twiddle1024, pre, cepstrogram,
-                           list, list_count, list_cap, force_list & 1);
-        RSAF_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(cepstrum_kernel, dim3(2048), dim3(256), 0, s, segs, max_seg, hdr, resampled, cap_res, cap_frames,
-                           window1000, (const double2*)twiddle1024, pre, cepstrogram, list, list_count, list_cap);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    {
-        ProfScope prof("mshds_cpp_frames", s, 0.0, 0.0);
-        const int64_t lp_doubles = (int64_t)n_clips * cap_work * 2;
-        int* list = reinterpret_cast<int*>(lp_work);
-        int* list_count = list + 2 * (lp_doubles - 1);
-        const int list_cap = (int)std::min<int64_t>(lp_doubles - 1, 0x7fffffff);
-        RSAF_CHECK_HIP(hipMemsetAsync(list_count, 0, sizeof(int), s));
-        hipLaunchKernelGGL(cpp_frame_wave_kernel, dim3((cap_frames + CPPF_FRAMES - 1) / CPPF_FRAMES, n_clips), dim3(64), 0, s, segs,
-                           max_seg, hdr, cepstrogram, cap_frames, (int)floor(0.01 / DT), (int)floor(0.001 / DQ), 60.0, 330.0,
-                           cpp_frames, list, list_count, list_cap, force_list & 2);
-        RSAF_CHECK_HIP(hipGetLastError());
-        hipLaunchKernelGGL(cpp_frame_kernel, dim3(2048), dim3(256), 0, s, segs, max_seg, hdr, cepstrogram, cap_frames,
-                           (int)floor(0.01 / DT), (int)floor(0.001 / DQ), 60.0, 330.0, cpp_frames, list, list_count, list_cap);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(reduce_kernel, dim3(n_clips), dim3(256), 0, s, segs, max_seg, hdr, cpp_frames, cap_frames, 4.0, out);
-    RSAF_CHECK_HIP(hipGetLastError());
-    return RSAF_OK;
+    hipStream_t s = c.stream;
+    { ProfScope prof("mshds_cpp_segments", s, 0.0, 0.0); CPP_TRY(launch_segments(c)); }
+    { ProfScope prof("mshds_cpp_resample", s, 0.0, 0.0); CPP_TRY(launch_lowpass(c)); CPP_TRY(launch_resample(c)); }
+    { ProfScope prof("mshds_cpp_cepstrum", s, 0.0, 0.0); CPP_TRY(launch_cepstra(c)); }
+    { ProfScope prof("mshds_cpp_frames", s, 0.0, 0.0); CPP_TRY(launch_frames(c)); }
+    return launch_reduce(c);
 }
 
 }  // extern "C"

@@ -12,6 +12,7 @@ the kernels reproduce those cases (too-short clips, no voiced frames, no periods
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -38,6 +39,15 @@ BUILT_COLUMNS = [0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 1
 CLIP_INFO = np.dtype([("sample_off", "<i8"), ("frame_off", "<i8"), ("t1", "<f8"),
                       ("n_samples", "<i4"), ("n_frames", "<i4"), ("x1", "<f8"), ("xmax", "<f8")])
 assert CLIP_INFO.itemsize == 48
+# the cepstral-peak-prominence chain's buffers as csrc/mshds_cpp_layout.h lays them out: the rows of the segment table
+# (struct Seg, 15 doubles in this order), the four ints of the per-clip header (struct ClipHdr), the doubles of a cepstrogram row
+CPP_SEG_FIELDS = ("ix1", "m_in", "m_out", "res_off", "frame_off", "nf", "x1_seg", "x1o", "window", "t1", "nx", "nfft",
+                  "work_off", "item_off", "lg")
+CPP_SEG = {name: i for i, name in enumerate(CPP_SEG_FIELDS)}
+CPP_HDR_FIELDS = ("n_seg", "fail", "total_frames", "total_resampled")
+CPP_HDR = {name: i for i, name in enumerate(CPP_HDR_FIELDS)}
+CPP_HDR_INTS = len(CPP_HDR_FIELDS)        # 4
+CPP_NQ_MAX = 513                          # NQ_MAX: quefrency bins of the 1024-point transform
 RESAMPLE_INFO = np.dtype([("sample_off", "<i8"), ("out_off", "<i8"), ("pos0", "<f8"), ("x1o", "<f8"),
                           ("n_in", "<i4"), ("n_out", "<i4"), ("table", "<i4"), ("pad", "<i4")])
 assert RESAMPLE_INFO.itemsize == 48
@@ -237,6 +247,35 @@ class _PitchGeom:
         return win, wr[:self.brent_ixmax + 1].copy()
 
 
+def _gaussian_window(n: int):
+    """Praat's Gaussian analysis window of ``n`` samples: exp(-48 d^2 / (n + 1)^2) about the centre, brought to zero at the
+    edges (Sound_to_Formant, Sound_to_PowerCepstrogram; csrc/mshds_cpp_layout.h ``gauss_window``)."""
+    i = np.arange(1, n + 1)
+    imid, edge = 0.5 * (n + 1), math.exp(-12.0)
+    return (np.exp(-48.0 * (i - imid) ** 2 / (n + 1) ** 2) - edge) / (1.0 - edge)
+
+
+_CppCaps = collections.namedtuple("_CppCaps", "max_seg cap_res cap_frames cap_work lg_max chunk")
+
+
+def _cpp_caps(max_len: int, chunk_limit: int) -> _CppCaps:
+    """Capacities of the ``rsaf_mshds_cpp`` calls of a batch whose longest clip has ``max_len`` samples, per clip: rows of
+    the segment table, resampled samples, frames, complex numbers of the low-pass work buffer; the longest low-pass
+    transform (log2); clips per call."""
+    dur = max_len * DX
+    max_seg = int(dur / 0.02) + 2
+    cap_res = int(dur * 10000.0) + max_seg + 16
+    cap_frames = int(dur / 0.002) + max_seg
+    # Sound_resample of every extracted part: transforms of the first power of two >= part + 2000 samples, i.e. fewer
+    # than part + 2000 complex numbers each
+    cap_work = int(max_len) + 2000 * max_seg
+    # (a voiced interval longer than the transform's limit - 69 min of unbroken voicing - fails that clip alone: NaN)
+    lg_max = min(26, max(11, int(max_len + 2000 - 1).bit_length()))
+    # clips per launch group: bound the cepstrogram workspace (cap_frames x 513 doubles per clip) to ~3 GB
+    chunk = max(1, min(chunk_limit, int(3.0e9 // (cap_frames * CPP_NQ_MAX * 8))))
+    return _CppCaps(max_seg, cap_res, cap_frames, cap_work, lg_max, chunk)
+
+
 def lowpass_eligible(lengths):
     """Per clip: does Praat's whole-sound FFT low-pass (the first step of To Formant (burg)) fit the device transform?"""
     cap = int(_lib.load().rsaf_praat_lowpass_max_samples())
@@ -408,7 +447,7 @@ class MshdsEngine:
 
         def build():
             i = np.arange(1, nsamp + 1)
-            phase = (i - 0.5 * (nsamp + 1)) / nsamp
+            phase = (i - 0.5 * (nsamp + 1)) / nsamp         # the spectrogram's window divides by n, not n + 1: not _gaussian_window
             edge = math.exp(-12.0)
             win = (np.exp(-48.0 * phase * phase) - edge) / (1.0 - edge)
             k = np.arange(nfft)
@@ -499,11 +538,7 @@ class MshdsEngine:
         dt_window = 0.05
         nsw = int(math.floor(dt_window / dxo))
 
-        def build():
-            i = np.arange(1, nsw + 1)
-            imid, edge = 0.5 * (nsw + 1), math.exp(-12.0)
-            return ((np.exp(-48.0 * (i - imid) ** 2 / (nsw + 1) ** 2) - edge) / (1.0 - edge),)
-        (win,) = self._table(("formant", nsw), build)
+        (win,) = self._table(("formant", nsw), lambda: (_gaussian_window(nsw),))
         ci = np.zeros(n, dtype=CLIP_INFO)
         foff = 0
         for i in range(n):
@@ -584,37 +619,22 @@ class MshdsEngine:
                                                        ceiling=ceiling, voicing_threshold=0.3, stream=stream, dom=dom)   # :270
         pulses, npul, max_pulses = self.pulses(wav, lengths, p, stream)                                  # :271
 
-        def build_win():
-            i = np.arange(1, 1001)
-            imid, edge = 0.5 * 1001, math.exp(-12.0)
-            return ((np.exp(-48.0 * (i - imid) ** 2 / 1001 ** 2) - edge) / (1.0 - edge),)
-
         def build_tw():
             k = np.arange(512)
             return (np.stack([np.cos(2.0 * np.pi * k / 1024.0), -np.sin(2.0 * np.pi * k / 1024.0)], axis=1).reshape(-1),)
-        (win,) = self._table(("cpp_window", 1000), build_win)
+        (win,) = self._table(("cpp_window", 1000), lambda: (_gaussian_window(1000),))
         (tw,) = self._table(("cpp_twiddle", 1024), build_tw)
-        dur = max(lengths) * DX
-        max_seg = int(dur / 0.02) + 2
-        cap_res = int(dur * 10000.0) + max_seg + 16
-        cap_frames = int(dur / 0.002) + max_seg
-        # Sound_resample of every extracted part: transforms of the first power of two >= part + 2000 samples, i.e. fewer
-        # than part + 2000 complex numbers each
-        cap_work = int(max(lengths)) + 2000 * max_seg
-        # (a voiced interval longer than the transform's limit - 69 min of unbroken voicing - fails that clip alone: NaN)
-        lg_max = min(26, max(11, int(max(lengths) + 2000 - 1).bit_length()))
+        max_seg, cap_res, cap_frames, cap_work, lg_max, chunk = _cpp_caps(max(lengths), self.CPP_CHUNK)
         segd = int(lib.rsaf_mshds_cpp_seg_doubles())
         ci_all = p["ci"]
-        # clips per launch group: bound the cepstrogram workspace (cap_frames x 513 doubles per clip) to ~3 GB
-        chunk = max(1, min(self.CPP_CHUNK, int(3.0e9 // (cap_frames * 513 * 8))))
         for c0 in range(0, n, chunk):
             c1 = min(n, c0 + chunk)
             m = c1 - c0
             ci_d = _dev(ci_all[c0:c1], dev)
             segs = torch.empty(m * max_seg * segd, dtype=torch.float64, device=dev)
-            hdr = torch.zeros(m * 4, dtype=torch.int32, device=dev)
+            hdr = torch.zeros(m * CPP_HDR_INTS, dtype=torch.int32, device=dev)
             res = torch.empty(m * cap_res, dtype=torch.float64, device=dev)
-            ceps = torch.empty(m * cap_frames * 513, dtype=torch.float64, device=dev)
+            ceps = torch.empty(m * cap_frames * CPP_NQ_MAX, dtype=torch.float64, device=dev)
             cppf = torch.empty(m * cap_frames, dtype=torch.float64, device=dev)
             lp_origin = int(min(int(r["sample_off"]) for r in ci_all[c0:c1]))
             lp_end = int(max(int(r["sample_off"]) + int(r["n_samples"]) for r in ci_all[c0:c1]))

@@ -5,7 +5,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 from oracle import mshds_oracle as mo
-from robust_speech_analysis_framework_amd import synth
+from robust_speech_analysis_framework_amd import mshds, synth
 
 TOL = 1e-4
 
@@ -305,7 +305,7 @@ def test_cpp_voiced_intervals_cepstrogram_and_cpps(eng):
         pul = mo.point_process_cc(x, p)
         iv = [(float(f"{a:.6f}"), float(f"{b:.6f}")) for a, b in mo.vuv_intervals(pul, 0.0, len(x) * mo.DX)]
         iv = [(a, b) for a, b in iv if a < b]
-        assert hdr[i, 0] == len(iv) and hdr[i, 1] == 0                               # interval count is exact
+        assert hdr[i, mshds.CPP_HDR["n_seg"]] == len(iv) and hdr[i, mshds.CPP_HDR["fail"]] == 0   # interval count is exact
         ref_vals = []
         for k, (tmin, tmax) in enumerate(iv):
             ix1 = int(np.ceil((tmin - 0.5 * mo.DX) / mo.DX))
@@ -314,15 +314,15 @@ def test_cpp_voiced_intervals_cepstrogram_and_cpps(eng):
             a, b = max(ix1, 0), min(ix2, len(x) - 1)
             seg[a - ix1:b - ix1 + 1] = x[a:b + 1]
             x1_seg = 0.5 * mo.DX + ix1 * mo.DX - tmin
-            S = segs[i, k]
-            assert int(S[0]) == ix1 and int(S[1]) == len(seg)                         # integers exact
+            S = {name: segs[i, k, j] for name, j in mshds.CPP_SEG.items()}
+            assert int(S["ix1"]) == ix1 and int(S["m_in"]) == len(seg)                         # integers exact
             y, x1o, _ = mo.resample_part(seg, x1_seg, tmax - tmin, mo.CPP_FS, mo.CPP_DEPTH)
-            assert int(S[2]) == len(y) and abs(S[7] - x1o) < 1e-15
-            r0 = int(S[3])
+            assert int(S["m_out"]) == len(y) and abs(S["x1o"] - x1o) < 1e-15
+            r0 = int(S["res_off"])
             assert np.abs(res[i, r0:r0 + len(y)] - y).max() < 1e-9 * max(1.0, np.abs(y).max())
             z = mo.power_cepstrogram(seg, x1_seg, tmax - tmin)
-            f0, nf = int(S[4]), int(S[5])
-            assert nf == z.shape[1] and int(S[11]) // 2 + 1 == z.shape[0]
+            f0, nf = int(S["frame_off"]), int(S["nf"])
+            assert nf == z.shape[1] and int(S["nfft"]) // 2 + 1 == z.shape[0]
             g = ceps[i, f0:f0 + nf, :z.shape[0]].T
             assert np.abs(g - z).max() <= 1e-7 * np.abs(z).max()
             v = mo.cpps(z)
@@ -583,7 +583,7 @@ def test_one_wave_cpps_kernels_agree_with_the_workgroup_kernels(eng, monkeypatch
         for i in range(len(clips)):
             c = ceps[i, :hdr[i, 2]].copy()
             for k in range(hdr[i, 0]):                            # a short interval's frames hold nfft / 2 + 1 bins: the rest of
-                f0, nf, nfft = int(segs[i, k, 4]), int(segs[i, k, 5]), int(segs[i, k, 11])   # the row is never written
+                f0, nf, nfft = (int(segs[i, k, mshds.CPP_SEG[name]]) for name in ("frame_off", "nf", "nfft"))   # the row is never written
                 c[f0:f0 + nf, nfft // 2 + 1:] = 0.0
             rows.append(c)
         out[mode] = (got, [cppf[i, :hdr[i, 2]].copy() for i in range(len(clips))], rows)
