@@ -791,6 +791,37 @@ int rsaf_rows_segment_mean_f32(const float* rows, int64_t ld, int64_t plane_floa
 int rsaf_gather_rows_f32(const float* src, int64_t ld_src, const int64_t* src_row, int64_t n_rows, int width, float* dst,
                          int64_t ld_dst, rsaf_stream_t stream);
 
+/* ---- Device-resident training data: the padded batches of K loader steps in ONE launch --------------------------------
+ * The sequences of a data set live back to back in one float32 arena [arena_rows][width] on the device; a batch is B
+ * members, member b being the row_count[b] frames from arena row row_start[b] on (both arrays on the device).
+ *   out[b][t] = arena[row_start[b] + t]  for t < min(row_count[b], T),  zeros for every other t
+ * (collate_fn's pad_sequence(batch_first = True, padding_value = 0), src/dl_cv_strategies.py:81-84, T the longest
+ * member).  The kernel writes the zeros itself: no memset, no index array.  A member of 0 (or fewer) frames is a
+ * block of zeros.  An arena row outside [0, arena_rows) is never read: it gives a zero row.  With the four label
+ * fields, label_out[b] = label_src[label_index[b]], and -1 where label_index[b] is outside [0, label_count) (never read).
+ * 16-byte loads and stores where width % 4 == 0 and `arena` and `out` are 16-byte aligned, dwords otherwise; element
+ * offsets are 64-bit.  The items travel by value in the kernel arguments; each has its own B and T.
+ * Checks, all before the launch, rsaf_last_error() naming the item: 1 <= K <= RSAF_CNNLSTM_GROUP_MAX, width >= 1,
+ * B >= 1, T >= 1, B * T * width < 2^40, no NULL among arena, row_start, row_count and out, the four label fields
+ * given together or not at all, no two `out` / `label_out` ranges of the call overlapping; and the call fits one grid
+ * (fewer than 2^31 workgroups of 256 float4 or float elements over all items).
+ * `frames`: the frames the item copies, sum of min(row_count[b], T), as the host knows them; it only sizes the bytes
+ * of the profiling family "train_collate" (floats read + written); negative: counted as B * T. */
+typedef struct {
+    const float* arena;            /* device [arena_rows][width] */
+    int64_t arena_rows;
+    const int64_t* row_start;      /* device [B] */
+    const int32_t* row_count;      /* device [B] */
+    int B, T;
+    float* out;                    /* device [B][T][width], written in full */
+    const int64_t* label_src;      /* device [label_count], or NULL with the other three */
+    int64_t label_count;
+    const int64_t* label_index;    /* device [B] */
+    int64_t* label_out;            /* device [B] */
+    int64_t frames;
+} rsaf_collate_item;
+int rsaf_collate_pad_group(const rsaf_collate_item* items_host, int K, int width, rsaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,12 @@ class Arch(C.Structure):
     _fields_ = [("channels", _I), ("hidden", _I), ("act", _I)]
 
 
+class CollateItem(C.Structure):
+    """``rsaf_collate_item``: one padded batch of a group collate (``frames``: what the host knows the item copies)."""
+    _fields_ = [("arena", _P), ("arena_rows", _L), ("row_start", _P), ("row_count", _P), ("B", _I), ("T", _I), ("out", _P),
+                ("label_src", _P), ("label_count", _L), ("label_index", _P), ("label_out", _P), ("frames", _L)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -169,6 +175,7 @@ SIGNATURES = {
     "rsaf_segment_mean_std": (_I, [_P, _L, _P, _P, _I, _I, _P, _P]),
     "rsaf_rows_segment_mean_f32": (_I, [_P, _L, _L, _I, _P, _I, _I, _P, _P]),
     "rsaf_gather_rows_f32": (_I, [_P, _L, _P, _L, _I, _P, _L, _P]),
+    "rsaf_collate_pad_group": (_I, [C.POINTER(CollateItem), _I, _I, _P]),
     "rsaf_w2v2_frames": (_I, [_I]),
     "rsaf_w2v2_weight_floats": (_L, [_I] * 7),
     "rsaf_w2v2_weight_offsets": (_I, [_I] * 7 + [C.POINTER(_L), _I, C.POINTER(_I)]),

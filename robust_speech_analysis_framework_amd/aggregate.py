@@ -78,15 +78,14 @@ def aggregate_clip_features(clip_features_df, metadata_df):
     return final
 
 
-def aggregate_interview_sequences(clip_sequences, interview_metadata_df):
-    """Drop-in for ``src/utils.py:64-104``: participant id -> the participant's clip sequences stacked in
-    metadata order; clips without a sequence are skipped, participants without any are absent."""
+def _stack_interview_clips(clip_sequences, interview_metadata_df):
+    """The arithmetic of ``aggregate_interview_sequences``: ``(stacked float32 [rows, width] on the device, {participant id:
+    (first row, end row)})`` in group order; ``(None, {})`` when no participant has a sequence."""
     import torch
     groups = interview_metadata_df.groupby("unique_participant_id")["filename"].apply(list)             # :83
-    print("\nAggregating interview clips into single sequences per participant...")
     names = [f for f in clip_sequences]
     if not names:
-        return {}
+        return None, {}
     width = int(np.asarray(clip_sequences[names[0]]).shape[1])
     start, total = {}, 0
     for f in names:
@@ -103,11 +102,22 @@ def aggregate_interview_sequences(clip_sequences, interview_metadata_df):
         if len(src_row) > a:                                                                              # :95
             spans[pid] = (a, len(src_row))
     if not spans:
-        return {}
+        return None, {}
     _lib.load()
     _lib.require_gpu()
     src = torch.from_numpy(np.ascontiguousarray(flat)).cuda()
-    out = gather_rows(src, np.asarray(src_row, dtype=np.int64))
+    return gather_rows(src, np.asarray(src_row, dtype=np.int64)), spans
+
+
+def aggregate_interview_sequences(clip_sequences, interview_metadata_df):
+    """Drop-in for ``src/utils.py:64-104``: participant id -> the participant's clip sequences stacked in
+    metadata order; clips without a sequence are skipped, participants without any are absent.
+    (``device_data.DeviceSequenceStore.from_interview_clips`` keeps the same stacks on the device.)"""
+    import torch
+    print("\nAggregating interview clips into single sequences per participant...")
+    out, spans = _stack_interview_clips(clip_sequences, interview_metadata_df)
+    if not spans:
+        return {}
     torch.cuda.synchronize()
     host = out.cpu().numpy()
     return {pid: host[a:b].copy() for pid, (a, b) in spans.items()}

@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from .cnnlstm_fused import _class_weights, _fused_step_applies, _loss_list, ce_loss_group, cnnlstm_train_step_group
 from .cnnlstm_train import cnnlstm_train_group, train_group_max
+from .device_data import BatchPlan, batches_to_device, check_loader_devices, epoch_iterator
 
 
 class CNNLSTMGroup(nn.Module):
@@ -75,10 +76,16 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     replica by replica within a step, in another order than K sequential trainings draw them.
 
     ``mixed=True``: the replicas may differ in architecture (``cnnlstm_train_group``): several trials of a hyper-parameter
-    search, each with its folds, in one lock-step training."""
+    search, each with its folds, in one lock-step training.
+
+    Any loader may be a ``device_data.DeviceBatchLoader`` (sequences resident on the device) in place of a ``DataLoader``,
+    in any mix: the batches that such loaders contribute to a group step are assembled on the device by one
+    ``rsaf_collate_pad_group`` launch (per ``train_group_max()`` of them), in the ``DataLoader``'s order and with
+    ``collate_fn``'s bits, so the results are the same.  ``DataLoader`` entries are padded on the host and copied as before."""
     models, optimizers, loaders = list(models), list(optimizers), list(loaders)
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
+    check_loader_devices(loaders, device, "train_replicas_lockstep")
     histories = [[] for _ in models]
     loss_fns = _loss_list(loss_fn, len(models))
     fused = _fused_step_applies(optimizers, models, loss_fns)     # decided once for the call: no replica changes path mid-epoch
@@ -86,15 +93,15 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     for _ in range(epochs):
         for m in models:
             m.train()
-        its = [iter(ld) for ld in loaders]
+        its = [epoch_iterator(ld) for ld in loaders]
         total, count = [0.0] * len(models), [0] * len(models)
         while True:
             batches = [next(it, None) for it in its]
             live = [k for k, b in enumerate(batches) if b is not None]
             if not live:
                 break
-            xs = [batches[k][0].to(device) for k in live]
-            labs = [batches[k][1].to(device) for k in live]
+            xs, labs = zip(*batches_to_device([batches[k] for k in live], device))
+            xs, labs = list(xs), list(labs)
             if fused:
                 step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs, mixed=mixed,
                                                        class_weights=weights and [weights[k] for k in live])[0]
@@ -115,23 +122,33 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     return histories
 
 
+def _eval_pairs(tagged):
+    """``tagged``: iterable of ``(tag, model, loader)`` -> the ``(tag, model, seq, lab)`` of ``_grouped_eval_batches``, loader by
+    loader; a ``DeviceBatchLoader`` gives its batches as plans."""
+    for tag, model, ld in tagged:
+        for b in epoch_iterator(ld):
+            yield (tag, model, b, None) if isinstance(b, BatchPlan) else (tag, model, b[0], b[1])
+
+
 def _grouped_eval_batches(pairs, device, mixed=False):
     """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models (``mixed``: of architectures too) -> yields ``(tag, logits, lab on the device)``
     in the same order, the forwards pooled into group calls of up to ``train_group_max()`` batches.  The batches stay as
     collated: zero padding is not masked (``src/dl_cv_strategies.py:81-84``), so regrouping sequences would change the
-    results."""
+    results.  ``seq`` may be a ``BatchPlan`` of a device loader (``lab`` is then ignored): the plans of a group call are
+    assembled by one ``rsaf_collate_pad_group`` launch."""
     from .cnnlstm import cnnlstm_forward_group
     gmax = train_group_max()
     pend = []
 
     def flush():
-        outs = cnnlstm_forward_group([p[1] for p in pend], [p[2] for p in pend], mixed=mixed)
-        res = [(p[0], o, p[3]) for p, o in zip(pend, outs)]
+        data = batches_to_device([p[2] for p in pend], device)
+        outs = cnnlstm_forward_group([p[1] for p in pend], [x for x, _ in data], mixed=mixed)
+        res = [(p[0], o, lab) for p, o, (_, lab) in zip(pend, outs, data)]
         pend.clear()
         return res
 
     for tag, model, seq, lab in pairs:
-        pend.append((tag, model, seq.to(device), lab.to(device)))
+        pend.append((tag, model, seq if isinstance(seq, BatchPlan) else (seq, lab)))
         if len(pend) == gmax:
             yield from flush()
     if pend:
@@ -142,16 +159,18 @@ def eval_replicas_lockstep(models, loaders, device, mixed=False):
     """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) for K models over K loaders: all (model, batch) pairs are
     pooled into group calls.  Returns K triples ``(labels, preds, probs)`` of NumPy arrays in loader order, equal to
     what the reference's loop returns model by model; the results of a replica come to the host in one copy each.
-    ``mixed=True``: the models may differ in architecture (``cnnlstm_forward_group``)."""
+    ``mixed=True``: the models may differ in architecture (``cnnlstm_forward_group``).  Loaders may be
+    ``DeviceBatchLoader``s in any mix with ``DataLoader``s; their batches are assembled on the device, one launch per group call."""
     from .cnnlstm import eval_outputs
     models, loaders = list(models), list(loaders)
     if len(models) != len(loaders):
         raise ValueError(f"{len(models)} models but {len(loaders)} loaders")
+    check_loader_devices(loaders, device, "eval_replicas_lockstep")
     for m in models:
         m.eval()
     parts = [([], [], []) for _ in models]
     with torch.no_grad():
-        pairs = ((k, m, seq, lab) for k, (m, ld) in enumerate(zip(models, loaders)) for seq, lab in ld)
+        pairs = _eval_pairs((k, m, ld) for k, (m, ld) in enumerate(zip(models, loaders)))
         for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
             prob, pred = eval_outputs(out)
             for lst, v in zip(parts[k], (lab, pred, prob)):
@@ -180,13 +199,16 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
     stopping as the reference does them.  ``loss_fn``: one loss or a sequence of K, as in ``train_replicas_lockstep``; the
     validation losses of a replica are those of its own loss (its class weights).  A replica that stopped early sits out of the later epochs.  Returns
     ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded.  ``mixed=True``: the
-    replicas may differ in architecture, in the training pass and in the validation pass alike."""
+    replicas may differ in architecture, in the training pass and in the validation pass alike.  Training and validation
+    loaders may be ``DeviceBatchLoader``s in any mix with ``DataLoader``s, as in the two loops above."""
     models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
     train_loaders, val_loaders = list(train_loaders), list(val_loaders)
     K = len(models)
     if not (K == len(optimizers) == len(schedulers) == len(train_loaders) == len(val_loaders)):
         raise ValueError(f"{K} models, {len(optimizers)} optimizers, {len(schedulers)} schedulers, {len(train_loaders)} training "
                          f"loaders and {len(val_loaders)} validation loaders")
+    check_loader_devices(train_loaders, device, "train_eval_replicas_lockstep (train_loaders)")
+    check_loader_devices(val_loaders, device, "train_eval_replicas_lockstep (val_loaders)")
     train_hist, val_hist = [[] for _ in models], [[] for _ in models]
     loss_fns = _loss_list(loss_fn, K)
     best_val_loss = [float("inf")] * K
@@ -206,7 +228,7 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], [loss_fns[k] for k in running])
         weights = _class_weights(loss_fns) if fused else None
         with torch.no_grad():
-            pairs = ((k, models[k], seq, lab) for k in running for seq, lab in val_loaders[k])
+            pairs = _eval_pairs((k, models[k], val_loaders[k]) for k in running)
             for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
                 tags.append(k)
                 outs.append(out)

@@ -8,13 +8,16 @@
 //   rsaf_gather_rows_f32  : row gather with zero fill: np.vstack of a participant's clip sequences
 //                           (src/utils.py:96) and the right-zero-padded batch of collate_fn
 //                           (src/dl_cv_strategies.py:81-84) are both one launch.
-// Both are HBM-bound streaming kernels (every input element is read once or twice, coalesced along the row).
+//   rsaf_collate_pad_group : the padded batches of K DataLoader steps (collate_fn, src/dl_cv_strategies.py:81-84) out of
+//                           sequences that live back to back in one device arena, ONE launch for all K: no index
+//                           array, no memset, the zeros of the padding written by the same kernel.
+// All are HBM-bound streaming kernels (every input element is read once or twice, coalesced along the row).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
-#include "rsaf_common.h"
+#include "cnnlstm_host.h"       // TRY, fail, check_group_args (the group entries' checks); rsaf_common.h
 
 namespace rsaf {
 namespace aggregate {
@@ -84,6 +87,83 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restric
     }
 }
 
+
+// ---- rsaf_collate_pad_group -------------------------------------------------------------------------------------------
+// A member's slice out[b] is T * width contiguous floats, and so are the frames it copies (arena rows row_start[b] ..
+// + n): a member is one contiguous copy followed by one contiguous run of zeros, and a workgroup takes COLLATE_CHUNK
+// consecutive elements (float4 or float) of one member.  Nothing is divided per element: the rows that exist in the
+// arena become an element range [lo, hi) once per workgroup.
+// Elements per lane, all loaded before the first store.  8 and 1 were both measured in this kernel with tools/lockstep_feed_bench.py
+// (profiles/r24/lockstep_feed.txt and lockstep_feed_one_per_lane.txt): the launch of a K = 16 group step moves 5.7-5.8 TB/s
+// (read + written) with 8 and 4.7-4.8 with 1, one 4 x 20 000 x 768 batch takes 0.090 against 0.094 ms.  A stand-alone copy
+// of the loop (tools/micro/collate_variants.hip) ranks them the other way round, so that ranking was not adopted.
+constexpr int COLLATE_PER_THREAD = 8;
+constexpr int COLLATE_CHUNK = 256 * COLLATE_PER_THREAD;       // elements of one workgroup: 32 KB of float4, 8 KB of float
+
+struct CollateItem {
+    const float* arena;
+    const long long* row_start;
+    const int* row_count;
+    float* out;
+    const long long* label_src;
+    const long long* label_index;
+    long long* label_out;
+    long long arena_rows, label_count;
+    unsigned first_block;          // of this item in the grid
+    unsigned blocks_per_member;    // ceil(T * row elements / COLLATE_CHUNK)
+    int B, T, vec4;
+};
+struct CollateGroup {
+    CollateItem item[RSAF_CNNLSTM_GROUP_MAX];
+    int K, width;
+};
+static_assert(sizeof(CollateGroup) <= 3584, "the descriptors travel by value in the kernel arguments");
+
+template <typename V>
+__device__ __forceinline__ void collate_chunk(const V* __restrict__ src, V* __restrict__ dst, int64_t e0, int64_t lo, int64_t hi,
+                                              int64_t end) {
+    V v[COLLATE_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < COLLATE_PER_THREAD; ++j) {
+        const int64_t e = e0 + j * 256;
+        v[j] = V{};
+        if (e >= lo && e < hi) v[j] = src[e];
+    }
+#pragma unroll
+    for (int j = 0; j < COLLATE_PER_THREAD; ++j) {
+        const int64_t e = e0 + j * 256;
+        if (e < end) dst[e] = v[j];
+    }
+}
+
+// grid: the workgroups of all items back to back (item k from first_block on), blocks_per_member per member
+__global__ __launch_bounds__(256) void collate_pad_group_kernel(const CollateGroup g) {
+    int k = 0;
+    while (k + 1 < g.K && blockIdx.x >= g.item[k + 1].first_block) ++k;
+    const CollateItem& it = g.item[k];
+    const unsigned blk = blockIdx.x - it.first_block;
+    const unsigned b = blk / it.blocks_per_member, chunk = blk - b * it.blocks_per_member;
+    if (blk == 0 && it.label_out) {
+        for (int i = threadIdx.x; i < it.B; i += 256) {
+            const long long j = it.label_index[i];
+            it.label_out[i] = (j >= 0 && j < it.label_count) ? it.label_src[j] : -1LL;
+        }
+    }
+    const int64_t start = it.row_start[b];
+    const int64_t n = min(max(it.row_count[b], 0), it.T);
+    // the frames t of the member whose arena row start + t exists: [t_lo, t_hi), empty when none does
+    const int64_t t_lo = start < 0 ? (start < -n ? n : -start) : 0;
+    const int64_t t_hi = start >= it.arena_rows ? t_lo : max(min(n, it.arena_rows - start), t_lo);
+    const int64_t w = it.vec4 ? g.width / 4 : g.width;                    // elements of a row
+    const int64_t end = (int64_t)it.T * w, lo = t_lo * w, hi = t_hi * w;
+    const int64_t e0 = (int64_t)chunk * COLLATE_CHUNK + threadIdx.x;
+    // src is formed from the member's first row only where one of its rows exists, and read only at elements of [lo, hi)
+    const float* src = it.arena + (t_hi > t_lo ? start : 0) * g.width;
+    float* dst = it.out + (int64_t)b * it.T * g.width;
+    if (it.vec4) collate_chunk(reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), e0, lo, hi, end);
+    else collate_chunk(src, dst, e0, lo, hi, end);
+}
+
 }  // namespace aggregate
 }  // namespace rsaf
 
@@ -131,6 +211,60 @@ int rsaf_gather_rows_f32(const float* src, int64_t ld_src, const int64_t* src_ro
     ProfScope prof("gather_rows", s, 0.0, 8.0 * (double)n_rows * width);
     hipLaunchKernelGGL(aggregate::gather_rows_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, s, src, ld_src, src_row,
                        n_rows, width, dst, ld_dst, vec4);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_collate_pad_group(const rsaf_collate_item* items_host, int K, int width, rsaf_stream_t stream) {
+    using namespace rsaf::cnnlstm;
+    static_assert(sizeof(rsaf_collate_item) == 88, "rsaf_collate_item is part of the ABI (CollateItem of _lib.py)");
+    TRY(check_group_args(K, items_host, __func__));
+    if (!(width >= 1)) return fail(RSAF_ERR_ARG, __func__, -1, "width must be >= 1");
+    aggregate::CollateGroup g{};
+    g.K = K;
+    g.width = width;
+    struct Range { const char* p; int64_t bytes; int item; const char* what; } wrote[RSAF_CNNLSTM_GROUP_MAX * 2];
+    int n_wrote = 0;
+    int64_t blocks = 0;
+    double floats = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const rsaf_collate_item& it = items_host[k];
+        if (!(it.B >= 1 && it.T >= 1)) return fail(RSAF_ERR_ARG, __func__, k, "B and T must be >= 1");
+        const int64_t out_floats = (int64_t)it.B * it.T * width;         // < 2^31 * 2^31 * 2^31 overflows: test the factors
+        if (!((int64_t)it.B * it.T < (1LL << 40) && out_floats < (1LL << 40) && out_floats > 0))
+            return fail(RSAF_ERR_ARG, __func__, k, "B * T * width must be < 2^40");
+        if (!(it.arena && it.row_start && it.row_count && it.out)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
+        if (!(it.arena_rows >= 0)) return fail(RSAF_ERR_ARG, __func__, k, "arena_rows must be >= 0");
+        const int n_label = (it.label_src != nullptr) + (it.label_index != nullptr) + (it.label_out != nullptr);
+        if (!(n_label == 0 || n_label == 3) || (n_label == 0 && it.label_count != 0) || it.label_count < 0)
+            return fail(RSAF_ERR_ARG, __func__, k, "label_src, label_count, label_index and label_out go together: all or none");
+        const Range mine[2] = {{reinterpret_cast<const char*>(it.out), out_floats * 4, k, "out"},
+                               {reinterpret_cast<const char*>(it.label_out), (int64_t)it.B * 8, k, "label_out"}};
+        for (const Range& m : mine) {
+            if (!m.p) continue;
+            for (int i = 0; i < n_wrote; ++i)
+                if (m.p < wrote[i].p + wrote[i].bytes && wrote[i].p < m.p + m.bytes)
+                    return fail(RSAF_ERR_ARG, __func__, k, std::string("`") + m.what + "` overlaps `" + wrote[i].what + "` of item " +
+                                                               std::to_string(wrote[i].item));
+            wrote[n_wrote++] = m;
+        }
+        const int vec4 = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(it.arena) | reinterpret_cast<uintptr_t>(it.out)) & 15) == 0;
+        const int64_t member = (int64_t)it.T * (vec4 ? width / 4 : width);
+        const int64_t per_member = (member + aggregate::COLLATE_CHUNK - 1) / aggregate::COLLATE_CHUNK;
+        if (!(per_member <= 0x7fffffffLL && blocks + per_member * it.B <= 0x7fffffffLL))
+            return fail(RSAF_ERR_ARG, __func__, k, "too many elements for one launch");
+        g.item[k] = aggregate::CollateItem{it.arena, reinterpret_cast<const long long*>(it.row_start), it.row_count, it.out,
+                                           reinterpret_cast<const long long*>(it.label_src),
+                                           reinterpret_cast<const long long*>(it.label_index),
+                                           reinterpret_cast<long long*>(it.label_out), it.arena_rows, it.label_count,
+                                           (unsigned)blocks, (unsigned)per_member, it.B, it.T, vec4};
+        blocks += per_member * it.B;
+        const int64_t frames = it.frames >= 0 && it.frames <= (int64_t)it.B * it.T ? it.frames : (int64_t)it.B * it.T;
+        floats += (double)out_floats + (double)frames * width;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_collate", s, 0.0, 4.0 * floats);
+    hipLaunchKernelGGL(aggregate::collate_pad_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }
