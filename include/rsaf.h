@@ -822,6 +822,71 @@ typedef struct {
 } rsaf_collate_item;
 int rsaf_collate_pad_group(const rsaf_collate_item* items_host, int K, int width, rsaf_stream_t stream);
 
+/* ---- Augmentations inside the collate launch, from a counter-based generator -----------------------------------------
+ * rsaf_collate_augment_group is rsaf_collate_pad_group with a pipeline of up to RSAF_AUGMENT_MAX augmentation ops per
+ * item, applied in order to every member BEFORE it is padded (the reference's SequenceDataset applies `transform` per
+ * item, src/dl_cv_strategies.py:19-62, and collate_fn pads afterwards): the padding stays +0.0 under every pipeline.
+ * Every augmented value is a pure function of (seed, epoch, sample, op, element): no generator state lives on the
+ * device, and a member gets the same bits in any batch, at any T, in any group and on either store path.  No op changes
+ * the number of frames.
+ *
+ * The generator is the Philox4x32-10 of the dropout masks (above).  key = (seed & 0xffffffff, seed >> 32).  Member b is
+ * sequence sample_id[b] (its index in the store, < 2^32).  Op number s (0-based) of the pipeline uses two streams:
+ *   parameter block: counter = (0, 0x100 + 2 s, sample_id, epoch)            -> words w0 .. w3
+ *   element blocks : counter = (j, 0x100 + 2 s + 1, sample_id, epoch), j = e >> 2, for the flat index e = t * width + d of
+ *                    the element in the member's own [frames][width] layout (so e does not depend on the batch)
+ * The op fires iff `always` != 0 or w0 < fire_threshold; the host sets always = (p >= 1) and fire_threshold =
+ * floor(p * 2^32) otherwise.  u(w) = (w >> 8) * 2^-24.  What a firing op does, by `kind`:
+ *   0 Scale          x <- x * f, f = (float)(a + (b - a) * u(w1)): difference, product and sum in double, each rounded,
+ *                    not fused; one rounding to float; the product with x in float
+ *   1 GaussianNoise  x <- fmaf(amp, z[e], x), amp formed like f from w1.  The element block j with words (A, B, C, D)
+ *                    gives four normals by Box-Muller in float: u1 = ((A >> 8) + 1) * 2^-24 (in (0, 1]),
+ *                    u2 = (B >> 8) * 2^-24, r = sqrt(-2 ln u1), z[4j] = r cos(2 pi u2), z[4j+1] = r sin(2 pi u2); the pair
+ *                    (C, D) gives z[4j+2] and z[4j+3] in the same way
+ *   2 TimeMask       n = the member's own number of frames (row_count[b], not T): lo = floor(n * a), hi = floor(n * b) in
+ *                    double, len = lo + (((uint64) w1 * (hi - lo + 1)) >> 32), start = ((uint64) w2 * (n - len + 1)) >> 32;
+ *                    frames [start, start + len) become +0.0
+ *   3 FeatureMask    the same with n = width: columns [start, start + len) of every frame become +0.0
+ * Everything but z is integer or single-rounded arithmetic and is the same bits in any restatement; z comes from the
+ * accurate logf, sqrtf and sincospif (no fast intrinsics) and is within 2^-17 of the exact value.
+ *
+ * `ops` is the op table on the device (the kernel reads it through uniform loads), `ops_host` the same n_ops entries in
+ * host memory: the entry checks those and never reads device memory.  An item with n_ops = 0 is a plain collate item
+ * (ops, ops_host and sample_id may be NULL) and gets the bits of rsaf_collate_pad_group.
+ * Checks, all before the launch, rsaf_last_error() naming the item and, where there is one, the op: everything
+ * rsaf_collate_pad_group checks; 0 <= n_ops <= RSAF_AUGMENT_MAX; with n_ops > 0: ops, ops_host and sample_id not NULL,
+ * every kind known, a and b finite, epoch < 2^32 and T * width < 2^34 (element blocks are counted in 32 bits).
+ * Profiling family: "train_collate_augment", bytes as for "train_collate". */
+#define RSAF_AUGMENT_MAX 8
+typedef struct {
+    int kind;                      /* 0 Scale, 1 GaussianNoise, 2 TimeMask, 3 FeatureMask */
+    uint32_t fire_threshold;       /* floor(p * 2^32) */
+    int always;                    /* p >= 1 */
+    double a, b;                   /* min and max of the factor, the amplitude or the band part */
+} rsaf_augment_op;
+typedef struct {
+    /* the fields of rsaf_collate_item, in its order */
+    const float* arena;
+    int64_t arena_rows;
+    const int64_t* row_start;
+    const int32_t* row_count;
+    int B, T;
+    float* out;
+    const int64_t* label_src;
+    int64_t label_count;
+    const int64_t* label_index;
+    int64_t* label_out;
+    int64_t frames;
+    /* the pipeline */
+    const rsaf_augment_op* ops;       /* device [n_ops] */
+    const rsaf_augment_op* ops_host;  /* host [n_ops], the same values */
+    int n_ops;
+    uint64_t seed;
+    uint64_t epoch;                /* < 2^32 */
+    const int64_t* sample_id;      /* device [B]: the members' sequence indices in the store */
+} rsaf_collate_augment_item;
+int rsaf_collate_augment_group(const rsaf_collate_augment_item* items_host, int K, int width, rsaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -95,6 +95,17 @@ class CollateItem(C.Structure):
                 ("label_src", _P), ("label_count", _L), ("label_index", _P), ("label_out", _P), ("frames", _L)]
 
 
+class AugmentOp(C.Structure):
+    """``rsaf_augment_op``: one op of an augmentation pipeline (``kind``: 0 Scale, 1 GaussianNoise, 2 TimeMask, 3 FeatureMask)."""
+    _fields_ = [("kind", _I), ("fire_threshold", C.c_uint32), ("always", _I), ("a", C.c_double), ("b", C.c_double)]
+
+
+class CollateAugmentItem(C.Structure):
+    """``rsaf_collate_augment_item``: ``rsaf_collate_item`` plus the pipeline of its members (``n_ops`` 0: a plain item)."""
+    _fields_ = CollateItem._fields_ + [("ops", _P), ("ops_host", _P), ("n_ops", _I), ("seed", C.c_uint64), ("epoch", C.c_uint64),
+                                       ("sample_id", _P)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -176,6 +187,7 @@ SIGNATURES = {
     "rsaf_rows_segment_mean_f32": (_I, [_P, _L, _L, _I, _P, _I, _I, _P, _P]),
     "rsaf_gather_rows_f32": (_I, [_P, _L, _P, _L, _I, _P, _L, _P]),
     "rsaf_collate_pad_group": (_I, [C.POINTER(CollateItem), _I, _I, _P]),
+    "rsaf_collate_augment_group": (_I, [C.POINTER(CollateAugmentItem), _I, _I, _P]),
     "rsaf_w2v2_frames": (_I, [_I]),
     "rsaf_w2v2_weight_floats": (_L, [_I] * 7),
     "rsaf_w2v2_weight_offsets": (_I, [_I] * 7 + [C.POINTER(_L), _I, C.POINTER(_I)]),

@@ -386,5 +386,6 @@ from .cnnlstm_train import (DropoutStream, Segment, _pack_train_blob, _train_seg
 from .cnnlstm_fused import FusedAdam, _adam_order, ce_loss_group, cnnlstm_train_step_group  # noqa: E402,F401
 from .cnnlstm_loops import (CNNLSTMGroup, eval_model_grouped, eval_replicas_lockstep,  # noqa: E402,F401
                             train_eval_replicas_lockstep, train_replicas_lockstep)
+from .augment import AugmentStream, Compose, FeatureMask, GaussianNoise, Scale, TimeMask  # noqa: E402,F401
 from .device_data import (DeviceBatchLoader, DeviceSequenceDataset, DeviceSequenceStore,  # noqa: E402,F401
                           batch_indices, collate_batches)

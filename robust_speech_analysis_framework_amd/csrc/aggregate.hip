@@ -11,12 +11,19 @@
 //   rsaf_collate_pad_group : the padded batches of K DataLoader steps (collate_fn, src/dl_cv_strategies.py:81-84) out of
 //                           sequences that live back to back in one device arena, ONE launch for all K: no index
 //                           array, no memset, the zeros of the padding written by the same kernel.
-// All are HBM-bound streaming kernels (every input element is read once or twice, coalesced along the row).
+//   rsaf_collate_augment_group : the same launch with each member's augmentation pipeline (the reference's `transform=` of
+//                           SequenceDataset, src/dl_cv_strategies.py:19-62) applied between the loads and the stores,
+//                           every value a pure function of (seed, epoch, sample, op, element) (augment_rng.h).
+// All but the last are HBM-bound streaming kernels (every input element is read once or twice, coalesced along the row);
+// a member that draws Gaussian noise pays a Philox block and two Box-Muller pairs per four elements.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <cstring>
 
+#include "augment_rng.h"
 #include "cnnlstm_host.h"       // TRY, fail, check_group_args (the group entries' checks); rsaf_common.h
 
 namespace rsaf {
@@ -164,6 +171,201 @@ __global__ __launch_bounds__(256) void collate_pad_group_kernel(const CollateGro
     else collate_chunk(src, dst, e0, lo, hi, end);
 }
 
+// ---- rsaf_collate_augment_group ---------------------------------------------------------------------------------------
+// The same chunk walk with the member's augmentation pipeline between the loads and the stores (the mapping: include/rsaf.h,
+// coded in augment_rng.h).  The op loop is the outer one: an op's table entry (uniform loads) and parameter block are the
+// same for the whole workgroup, which then applies the op to the elements it holds in registers, and only to those of
+// [lo, hi): the padding is never touched.  A workgroup whose member fires no op falls through to the stores, a plain copy.
+struct AugmentItem {
+    CollateItem c;
+    const rsaf_augment_op* ops;
+    const long long* sample_id;
+    unsigned long long seed;
+    unsigned epoch;
+    int n_ops;
+};
+struct AugmentGroup {
+    AugmentItem item[RSAF_CNNLSTM_GROUP_MAX];
+    int K, width;
+};
+static_assert(sizeof(AugmentGroup) <= 3584, "the descriptors travel by value in the kernel arguments");
+
+// N floats per element: 4 (float4 path) or 1 (dword path).  `w`: elements of a row; e0, lo, hi, end in elements; `own_n`:
+// the member's own frames (what TimeMask divides).  An element's flat float index in the member is N * e on either path.
+template <int N>
+__device__ __forceinline__ void augment_chunk(const AugmentItem& it, int width, const float* __restrict__ src, float* __restrict__ dst,
+                                              int64_t e0, int64_t lo, int64_t hi, int64_t end, int64_t own_n, uint32_t sample) {
+    constexpr int P = COLLATE_PER_THREAD;
+    const int64_t w = width / N;
+    float x[P][N];
+    bool in[P];
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int64_t e = e0 + j * 256;
+        in[j] = e >= lo && e < hi;
+        if constexpr (N == 4) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (in[j]) v = reinterpret_cast<const float4*>(src)[e];
+            x[j][0] = v.x; x[j][1] = v.y; x[j][2] = v.z; x[j][3] = v.w;
+        } else {
+            x[j][0] = in[j] ? src[e] : 0.0f;
+        }
+    }
+    // the op table is not written while the kernel runs: read through the constant address space, its uniform loads are scalar
+    // on both store paths
+    typedef const rsaf_augment_op __attribute__((address_space(4))) ConstOp;
+    const ConstOp* table = (const ConstOp*)it.ops;
+    for (int s = 0; s < it.n_ops; ++s) {
+        rsaf_augment_op op;
+        op.kind = table[s].kind;
+        op.fire_threshold = table[s].fire_threshold;
+        op.always = table[s].always;
+        op.a = table[s].a;
+        op.b = table[s].b;
+        uint32_t pw[4];
+        rng::augment_param_block(it.seed, it.epoch, sample, s, pw);
+        if (!rng::augment_fires(op.always, op.fire_threshold, pw[0])) continue;
+        if (op.kind == rng::AUGMENT_SCALE) {
+            const float f = rng::augment_uniform(op.a, op.b, pw[1]);
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+                if (in[j]) {
+#pragma unroll
+                    for (int c = 0; c < N; ++c) x[j][c] *= f;
+                }
+        } else if (op.kind == rng::AUGMENT_GAUSSIAN_NOISE) {
+            const float amp = rng::augment_uniform(op.a, op.b, pw[1]);
+#pragma unroll
+            for (int j = 0; j < P; ++j)
+                if (in[j]) {
+                    const uint64_t flat = (uint64_t)(e0 + j * 256) * N;        // < 2^34 (entry check)
+                    uint32_t ew[4];
+                    rng::augment_element_block(it.seed, it.epoch, sample, s, (uint32_t)(flat >> 2), ew);
+                    if constexpr (N == 4) {
+                        float z[4];
+                        rng::augment_normal_pair(ew[0], ew[1], &z[0], &z[1]);
+                        rng::augment_normal_pair(ew[2], ew[3], &z[2], &z[3]);
+#pragma unroll
+                        for (int c = 0; c < 4; ++c) x[j][c] = fmaf(amp, z[c], x[j][c]);
+                    } else {
+                        x[j][0] = fmaf(amp, rng::augment_normal_of(ew, (unsigned)(flat & 3)), x[j][0]);
+                    }
+                }
+        } else if (op.kind == rng::AUGMENT_TIME_MASK) {
+            int64_t start, len;
+            rng::augment_span(own_n, op.a, op.b, pw[1], pw[2], &start, &len);
+            const int64_t m_lo = start * w, m_hi = (start + len) * w;
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+                const int64_t e = e0 + j * 256;
+                if (e >= m_lo && e < m_hi) {
+#pragma unroll
+                    for (int c = 0; c < N; ++c) x[j][c] = 0.0f;
+                }
+            }
+        } else if (op.kind == rng::AUGMENT_FEATURE_MASK) {
+            int64_t start, len;
+            rng::augment_span(width, op.a, op.b, pw[1], pw[2], &start, &len);
+            // the column of the lane's first element, then one step of 256 elements at a time: no division per element
+            const uint32_t uw = (uint32_t)w, step = 256u % uw;
+            uint32_t col = (uint32_t)((uint64_t)e0 % uw);
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+#pragma unroll
+                for (int c = 0; c < N; ++c) {
+                    const int64_t d = (int64_t)col * N + c;
+                    if (d >= start && d < start + len) x[j][c] = 0.0f;      // +0.0 in the padding as well
+                }
+                col += step;
+                if (col >= uw) col -= uw;
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+        const int64_t e = e0 + j * 256;
+        if (e < end) {
+            if constexpr (N == 4) reinterpret_cast<float4*>(dst)[e] = make_float4(x[j][0], x[j][1], x[j][2], x[j][3]);
+            else dst[e] = x[j][0];
+        }
+    }
+}
+
+// grid and member geometry: those of collate_pad_group_kernel
+__global__ __launch_bounds__(256) void collate_augment_group_kernel(const AugmentGroup g) {
+    int k = 0;
+    while (k + 1 < g.K && blockIdx.x >= g.item[k + 1].c.first_block) ++k;
+    const AugmentItem& ai = g.item[k];
+    const CollateItem& it = ai.c;
+    const unsigned blk = blockIdx.x - it.first_block;
+    const unsigned b = blk / it.blocks_per_member, chunk = blk - b * it.blocks_per_member;
+    const int64_t start = it.row_start[b];
+    const int64_t own_n = max(it.row_count[b], 0);
+    const int64_t n = min(own_n, (int64_t)it.T);
+    const uint32_t sample = ai.n_ops > 0 ? (uint32_t)ai.sample_id[b] : 0u;
+    const int64_t t_lo = start < 0 ? (start < -n ? n : -start) : 0;
+    const int64_t t_hi = start >= it.arena_rows ? t_lo : max(min(n, it.arena_rows - start), t_lo);
+    const int64_t w = it.vec4 ? g.width / 4 : g.width;
+    const int64_t end = (int64_t)it.T * w, lo = t_lo * w, hi = t_hi * w;
+    const int64_t e0 = (int64_t)chunk * COLLATE_CHUNK + threadIdx.x;
+    const float* src = it.arena + (t_hi > t_lo ? start : 0) * g.width;
+    float* dst = it.out + (int64_t)b * it.T * g.width;
+    if (it.vec4) augment_chunk<4>(ai, g.width, src, dst, e0, lo, hi, end, own_n, sample);
+    else augment_chunk<1>(ai, g.width, src, dst, e0, lo, hi, end, own_n, sample);
+    // the labels last: no store stands between the kernel's entry and the uniform loads above
+    if (blk == 0 && it.label_out) {
+        for (int i = threadIdx.x; i < it.B; i += 256) {
+            const long long j = it.label_index[i];
+            it.label_out[i] = (j >= 0 && j < it.label_count) ? it.label_src[j] : -1LL;
+        }
+    }
+}
+
+// ---- what both collate entries check and size, item by item, before their launch ----------------------------------------
+struct CollatePlan {
+    struct Range { const char* p; int64_t bytes; int item; const char* what; };
+    Range wrote[RSAF_CNNLSTM_GROUP_MAX * 2];
+    int n_wrote = 0;
+    int64_t blocks = 0;
+    double floats = 0.0;          // read + written, for the profiling family
+
+    int add(const rsaf_collate_item& it, int k, int width, const char* who, CollateItem* out) {
+        using namespace rsaf::cnnlstm;
+        if (!(it.B >= 1 && it.T >= 1)) return fail(RSAF_ERR_ARG, who, k, "B and T must be >= 1");
+        const int64_t out_floats = (int64_t)it.B * it.T * width;         // < 2^31 * 2^31 * 2^31 overflows: test the factors
+        if (!((int64_t)it.B * it.T < (1LL << 40) && out_floats < (1LL << 40) && out_floats > 0))
+            return fail(RSAF_ERR_ARG, who, k, "B * T * width must be < 2^40");
+        if (!(it.arena && it.row_start && it.row_count && it.out)) return fail(RSAF_ERR_ARG, who, k, "NULL pointer");
+        if (!(it.arena_rows >= 0)) return fail(RSAF_ERR_ARG, who, k, "arena_rows must be >= 0");
+        const int n_label = (it.label_src != nullptr) + (it.label_index != nullptr) + (it.label_out != nullptr);
+        if (!(n_label == 0 || n_label == 3) || (n_label == 0 && it.label_count != 0) || it.label_count < 0)
+            return fail(RSAF_ERR_ARG, who, k, "label_src, label_count, label_index and label_out go together: all or none");
+        const Range mine[2] = {{reinterpret_cast<const char*>(it.out), out_floats * 4, k, "out"},
+                               {reinterpret_cast<const char*>(it.label_out), (int64_t)it.B * 8, k, "label_out"}};
+        for (const Range& m : mine) {
+            if (!m.p) continue;
+            for (int i = 0; i < n_wrote; ++i)
+                if (m.p < wrote[i].p + wrote[i].bytes && wrote[i].p < m.p + m.bytes)
+                    return fail(RSAF_ERR_ARG, who, k, std::string("`") + m.what + "` overlaps `" + wrote[i].what + "` of item " +
+                                                          std::to_string(wrote[i].item));
+            wrote[n_wrote++] = m;
+        }
+        const int vec4 = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(it.arena) | reinterpret_cast<uintptr_t>(it.out)) & 15) == 0;
+        const int64_t member = (int64_t)it.T * (vec4 ? width / 4 : width);
+        const int64_t per_member = (member + COLLATE_CHUNK - 1) / COLLATE_CHUNK;
+        if (!(per_member <= 0x7fffffffLL && blocks + per_member * it.B <= 0x7fffffffLL))
+            return fail(RSAF_ERR_ARG, who, k, "too many elements for one launch");
+        *out = CollateItem{it.arena, reinterpret_cast<const long long*>(it.row_start), it.row_count, it.out,
+                           reinterpret_cast<const long long*>(it.label_src), reinterpret_cast<const long long*>(it.label_index),
+                           reinterpret_cast<long long*>(it.label_out), it.arena_rows, it.label_count,
+                           (unsigned)blocks, (unsigned)per_member, it.B, it.T, vec4};
+        blocks += per_member * it.B;
+        const int64_t frames = it.frames >= 0 && it.frames <= (int64_t)it.B * it.T ? it.frames : (int64_t)it.B * it.T;
+        floats += (double)out_floats + (double)frames * width;
+        return RSAF_OK;
+    }
+};
+
 }  // namespace aggregate
 }  // namespace rsaf
 
@@ -223,48 +425,54 @@ int rsaf_collate_pad_group(const rsaf_collate_item* items_host, int K, int width
     aggregate::CollateGroup g{};
     g.K = K;
     g.width = width;
-    struct Range { const char* p; int64_t bytes; int item; const char* what; } wrote[RSAF_CNNLSTM_GROUP_MAX * 2];
-    int n_wrote = 0;
-    int64_t blocks = 0;
-    double floats = 0.0;
+    aggregate::CollatePlan plan;
+    for (int k = 0; k < K; ++k) TRY(plan.add(items_host[k], k, width, __func__, &g.item[k]));
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof("train_collate", s, 0.0, 4.0 * plan.floats);
+    hipLaunchKernelGGL(aggregate::collate_pad_group_kernel, dim3((unsigned)plan.blocks), dim3(256), 0, s, g);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
+int rsaf_collate_augment_group(const rsaf_collate_augment_item* items_host, int K, int width, rsaf_stream_t stream) {
+    using namespace rsaf::cnnlstm;
+    static_assert(sizeof(rsaf_augment_op) == 32, "rsaf_augment_op is part of the ABI (AugmentOp of _lib.py)");
+    static_assert(sizeof(rsaf_collate_augment_item) == 136 && offsetof(rsaf_collate_augment_item, ops) == sizeof(rsaf_collate_item),
+                  "rsaf_collate_augment_item is part of the ABI (CollateAugmentItem of _lib.py) and opens with rsaf_collate_item");
+    TRY(check_group_args(K, items_host, __func__));
+    if (!(width >= 1)) return fail(RSAF_ERR_ARG, __func__, -1, "width must be >= 1");
+    aggregate::AugmentGroup g{};
+    g.K = K;
+    g.width = width;
+    aggregate::CollatePlan plan;
     for (int k = 0; k < K; ++k) {
-        const rsaf_collate_item& it = items_host[k];
-        if (!(it.B >= 1 && it.T >= 1)) return fail(RSAF_ERR_ARG, __func__, k, "B and T must be >= 1");
-        const int64_t out_floats = (int64_t)it.B * it.T * width;         // < 2^31 * 2^31 * 2^31 overflows: test the factors
-        if (!((int64_t)it.B * it.T < (1LL << 40) && out_floats < (1LL << 40) && out_floats > 0))
-            return fail(RSAF_ERR_ARG, __func__, k, "B * T * width must be < 2^40");
-        if (!(it.arena && it.row_start && it.row_count && it.out)) return fail(RSAF_ERR_ARG, __func__, k, "NULL pointer");
-        if (!(it.arena_rows >= 0)) return fail(RSAF_ERR_ARG, __func__, k, "arena_rows must be >= 0");
-        const int n_label = (it.label_src != nullptr) + (it.label_index != nullptr) + (it.label_out != nullptr);
-        if (!(n_label == 0 || n_label == 3) || (n_label == 0 && it.label_count != 0) || it.label_count < 0)
-            return fail(RSAF_ERR_ARG, __func__, k, "label_src, label_count, label_index and label_out go together: all or none");
-        const Range mine[2] = {{reinterpret_cast<const char*>(it.out), out_floats * 4, k, "out"},
-                               {reinterpret_cast<const char*>(it.label_out), (int64_t)it.B * 8, k, "label_out"}};
-        for (const Range& m : mine) {
-            if (!m.p) continue;
-            for (int i = 0; i < n_wrote; ++i)
-                if (m.p < wrote[i].p + wrote[i].bytes && wrote[i].p < m.p + m.bytes)
-                    return fail(RSAF_ERR_ARG, __func__, k, std::string("`") + m.what + "` overlaps `" + wrote[i].what + "` of item " +
-                                                               std::to_string(wrote[i].item));
-            wrote[n_wrote++] = m;
+        const rsaf_collate_augment_item& it = items_host[k];
+        rsaf_collate_item batch;
+        std::memcpy(&batch, &it, sizeof batch);
+        TRY(plan.add(batch, k, width, __func__, &g.item[k].c));
+        if (!(it.n_ops >= 0 && it.n_ops <= RSAF_AUGMENT_MAX)) return fail(RSAF_ERR_ARG, __func__, k, "n_ops must be in [0, 8] (RSAF_AUGMENT_MAX)");
+        if (it.n_ops > 0) {
+            if (!(it.ops && it.ops_host && it.sample_id))
+                return fail(RSAF_ERR_ARG, __func__, k, "ops, ops_host and sample_id must not be NULL when n_ops > 0");
+            for (int s = 0; s < it.n_ops; ++s) {
+                const rsaf_augment_op& op = it.ops_host[s];
+                if (!(op.kind >= 0 && op.kind < rng::AUGMENT_KINDS))
+                    return fail(RSAF_ERR_ARG, __func__, k, "op " + std::to_string(s) + ": unknown kind " + std::to_string(op.kind));
+                if (!(std::isfinite(op.a) && std::isfinite(op.b)))
+                    return fail(RSAF_ERR_ARG, __func__, k, "op " + std::to_string(s) + ": a and b must be finite");
+            }
+            if (!(it.epoch < (1ULL << 32))) return fail(RSAF_ERR_ARG, __func__, k, "epoch must be < 2^32");
+            if (!((int64_t)it.T * width < (1LL << 34))) return fail(RSAF_ERR_ARG, __func__, k, "T * width must be < 2^34 with n_ops > 0");
         }
-        const int vec4 = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(it.arena) | reinterpret_cast<uintptr_t>(it.out)) & 15) == 0;
-        const int64_t member = (int64_t)it.T * (vec4 ? width / 4 : width);
-        const int64_t per_member = (member + aggregate::COLLATE_CHUNK - 1) / aggregate::COLLATE_CHUNK;
-        if (!(per_member <= 0x7fffffffLL && blocks + per_member * it.B <= 0x7fffffffLL))
-            return fail(RSAF_ERR_ARG, __func__, k, "too many elements for one launch");
-        g.item[k] = aggregate::CollateItem{it.arena, reinterpret_cast<const long long*>(it.row_start), it.row_count, it.out,
-                                           reinterpret_cast<const long long*>(it.label_src),
-                                           reinterpret_cast<const long long*>(it.label_index),
-                                           reinterpret_cast<long long*>(it.label_out), it.arena_rows, it.label_count,
-                                           (unsigned)blocks, (unsigned)per_member, it.B, it.T, vec4};
-        blocks += per_member * it.B;
-        const int64_t frames = it.frames >= 0 && it.frames <= (int64_t)it.B * it.T ? it.frames : (int64_t)it.B * it.T;
-        floats += (double)out_floats + (double)frames * width;
+        g.item[k].ops = it.n_ops > 0 ? it.ops : nullptr;
+        g.item[k].sample_id = it.n_ops > 0 ? reinterpret_cast<const long long*>(it.sample_id) : nullptr;
+        g.item[k].seed = it.seed;
+        g.item[k].epoch = (unsigned)it.epoch;
+        g.item[k].n_ops = it.n_ops;
     }
     hipStream_t s = (hipStream_t)stream;
-    ProfScope prof("train_collate", s, 0.0, 4.0 * floats);
-    hipLaunchKernelGGL(aggregate::collate_pad_group_kernel, dim3((unsigned)blocks), dim3(256), 0, s, g);
+    ProfScope prof("train_collate_augment", s, 0.0, 4.0 * plan.floats);
+    hipLaunchKernelGGL(aggregate::collate_augment_group_kernel, dim3((unsigned)plan.blocks), dim3(256), 0, s, g);
     RSAF_CHECK_HIP(hipGetLastError());
     return RSAF_OK;
 }

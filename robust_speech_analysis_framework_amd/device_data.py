@@ -1,6 +1,6 @@
 """Device-resident training data for the lock-step loops: the sequences of a data set uploaded once, every batch assembled
 on the device in ``DataLoader``'s order and with ``collate_fn``'s bits, the K batches of a group step in one launch
-(``rsaf_collate_pad_group``).
+(``rsaf_collate_pad_group``; ``rsaf_collate_augment_group`` where a data set has a ``transform``, see ``augment``).
 
 The reference feeds a model through ``DataLoader(SequenceDataset(X[idx], y[idx]), batch_size, shuffle, collate_fn)``
 (``src/dl_cv_strategies.py:19-84,234-235``): every batch is padded on the CPU and uploaded again, per fold, per epoch and
@@ -18,10 +18,13 @@ module.
 """
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import _lib
+from .augment import AugmentStream, as_compose
 
 _STAGE_BYTES = 64 << 20             # pinned staging of an upload: two buffers of this size, however large the data set
 
@@ -175,11 +178,13 @@ class DeviceSequenceDataset:
 
     ``labels``: one integer label per sequence of the STORE (``y_data``); ``indices``: the sequences of this view in
     order (``None``: all of them).  ``subset(idx)`` is the view of ``idx`` within this one, as ``X[idx]`` of an ``X`` that
-    is already a subset.  ``dataset[i]`` is ``(device view [T, D], device int64 label)``.  There is no ``transform``
-    argument: augmentations run on host arrays before the upload, or not at all (``SequenceDataset`` applies them per
-    item on the CPU, which is what this class is there to avoid)."""
+    is already a subset.  ``dataset[i]`` is ``(device view [T, D], device int64 label)``, the sequence as stored.
+    ``transform`` (a ``Compose`` or one op of ``augment``) with ``augment_stream`` (an ``AugmentStream``) is the
+    counterpart of ``SequenceDataset``'s ``transform``: it is applied to every member of every batch a ``DeviceBatchLoader``
+    assembles, inside the collate launch, a new draw per epoch of the stream; the two go together, and views made by
+    ``subset`` share both.  A host callable is refused: those stay with the ``DataLoader`` path."""
 
-    def __init__(self, store, labels, indices=None):
+    def __init__(self, store, labels, indices=None, transform=None, augment_stream=None):
         if not isinstance(store, DeviceSequenceStore):
             raise TypeError(f"DeviceSequenceDataset: store is a {type(store).__name__}, not a DeviceSequenceStore")
         if torch.is_tensor(labels):
@@ -204,9 +209,19 @@ class DeviceSequenceDataset:
         if idx.size and (idx.min() < -len(store) or idx.max() >= len(store)):
             raise IndexError(f"DeviceSequenceDataset: index outside a store of {len(store)} sequences")
         self.indices = np.where(idx < 0, idx + len(store), idx)
+        if (transform is None) != (augment_stream is None):
+            raise ValueError("DeviceSequenceDataset: transform and augment_stream go together: "
+                             f"{'augment_stream' if transform is not None else 'transform'} is missing")
+        if transform is not None:
+            transform = as_compose(transform, "DeviceSequenceDataset")
+            if not isinstance(augment_stream, AugmentStream):
+                raise TypeError(f"DeviceSequenceDataset: augment_stream is a {type(augment_stream).__name__}, not an AugmentStream")
+            if len(store) > 2 ** 32:
+                raise ValueError("DeviceSequenceDataset: a transform numbers the sequences of the store in 32 bits")
+        self.transform, self.augment_stream = transform, augment_stream
 
     def subset(self, idx):
-        return DeviceSequenceDataset(self.store, self.labels, self.indices[np.asarray(idx)])
+        return DeviceSequenceDataset(self.store, self.labels, self.indices[np.asarray(idx)], self.transform, self.augment_stream)
 
     def __len__(self):
         return int(self.indices.size)
@@ -218,12 +233,14 @@ class DeviceSequenceDataset:
 
 class BatchPlan:
     """One batch of an epoch, not yet assembled: where its members' rows, counts and label indices stand in the
-    epoch's device arrays, and the host-side sizes (``B``, ``T`` = its longest member, ``frames`` = what it copies)."""
-    __slots__ = ("dataset", "row_start", "row_count", "label_index", "first", "B", "T", "frames")
+    epoch's device arrays, and the host-side sizes (``B``, ``T`` = its longest member, ``frames`` = what it copies).
+    ``epoch``: the epoch of the data set's ``AugmentStream`` that this batch is drawn at (``None``: no transform);
+    ``label_index`` holds the members' store indices, which are also their sample ids."""
+    __slots__ = ("dataset", "row_start", "row_count", "label_index", "first", "B", "T", "frames", "epoch")
 
-    def __init__(self, dataset, row_start, row_count, label_index, first, B, T, frames):
+    def __init__(self, dataset, row_start, row_count, label_index, first, B, T, frames, epoch=None):
         self.dataset, self.row_start, self.row_count, self.label_index = dataset, row_start, row_count, label_index
-        self.first, self.B, self.T, self.frames = first, B, T, frames
+        self.first, self.B, self.T, self.frames, self.epoch = first, B, T, frames, epoch
 
 
 class _EpochPlans:
@@ -242,6 +259,7 @@ class _EpochPlans:
         ld = self.loader
         ds, store = ld.dataset, ld.dataset.store
         batches = _draw_batches(len(ds), ld.batch_size, ld.shuffle, ld.generator, ld.drop_last)
+        epoch = ds.augment_stream.take_epoch() if ds.transform is not None else None
         plans = []
         if batches:
             order = ds.indices[np.concatenate([np.asarray(b, dtype=np.int64) for b in batches])]    # store indices, epoch order
@@ -254,7 +272,7 @@ class _EpochPlans:
             first = 0
             for b in batches:
                 ln = lengths[first:first + len(b)]
-                plans.append(BatchPlan(ds, row_start, row_count, order_device, first, len(b), int(ln.max()), int(ln.sum())))
+                plans.append(BatchPlan(ds, row_start, row_count, order_device, first, len(b), int(ln.max()), int(ln.sum()), epoch))
                 first += len(b)
         self.plans = iter(plans)
 
@@ -270,7 +288,9 @@ class DeviceBatchLoader:
     ``(x [B, T, D] float32 right-zero-padded to the longest member, labels [B] int64)`` on the device, equal bit for bit to
     what ``collate_fn`` builds.  Every ``iter()`` uploads the epoch's order once (pinned, non-blocking), derives the
     members' arena rows, frame counts and label indices on the device, and takes each batch's T from the lengths the
-    host keeps.  ``plans()`` gives the epoch's batches without assembling them, for ``collate_batches``."""
+    host keeps.  ``plans()`` gives the epoch's batches without assembling them, for ``collate_batches``.  Where the
+    data set has a ``transform``, every epoch takes the next epoch number of its ``AugmentStream`` at the point where it
+    draws its order (the first batch asked for)."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, drop_last=False):
         if not isinstance(dataset, DeviceSequenceDataset):
@@ -295,7 +315,10 @@ class DeviceBatchLoader:
 
 def collate_batches(plans):
     """``[(x, labels)]`` of the planned batches, assembled by one ``rsaf_collate_pad_group`` launch per
-    ``train_group_max()`` plans of one store width (lists longer than that are split like every other group call)."""
+    ``train_group_max()`` plans of one store width (lists longer than that are split like every other group call).  Where
+    any plan of a width comes from a data set with a ``transform``, all plans of that width go through
+    ``rsaf_collate_augment_group`` instead, the plain ones with ``n_ops = 0``: still one launch, so the training and the
+    validation batches of a step may share a call."""
     from .cnnlstm_train import _launch_chunked
     plans = list(plans)
     for k, p in enumerate(plans):
@@ -326,7 +349,22 @@ def collate_batches(plans):
                 it.label_index = p.label_index.data_ptr() + 8 * p.first
                 it.label_out, it.frames = outs[k][1].data_ptr(), p.frames
 
-            _launch_chunked("rsaf_collate_pad_group", _lib.CollateItem, members, fill, width)
+            if all(plans[k].epoch is None for k in members):
+                _launch_chunked("rsaf_collate_pad_group", _lib.CollateItem, members, fill, width)
+                continue
+
+            def fill_augmented(it, k, j):
+                fill(it, k, j)
+                p = plans[k]
+                if p.epoch is None:
+                    it.n_ops = 0
+                    return
+                tf = p.dataset.transform
+                it.ops, it.ops_host, it.n_ops = tf.table(device).data_ptr(), C.addressof(tf.table_host), len(tf)
+                it.seed, it.epoch = p.dataset.augment_stream.seed, p.epoch
+                it.sample_id = p.label_index.data_ptr() + 8 * p.first
+
+            _launch_chunked("rsaf_collate_augment_group", _lib.CollateAugmentItem, members, fill_augmented, width)
     return outs
 
 
