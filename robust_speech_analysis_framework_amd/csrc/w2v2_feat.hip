@@ -1,6 +1,7 @@
 // Wav2Vec2 forward, first stage: window tables, per-window normalisation, the seven feature-encoder convolutions (group-norm
 // and layer-norm mode) and the feature projection; the kernels, then the Forward phases that launch them.
 #include "w2v2_forward.h"
+#include "gn_stats.h"
 
 namespace rsaf {
 namespace w2v2 {
@@ -136,7 +137,7 @@ __global__ __launch_bounds__(256) void conv0_kernel(const float* __restrict__ xn
             if (APPLY) {
                 gv[k] = fmaf(y, a[k], b[k]);
             } else {
-                s[k] += y; q[k] += y * y; mx[k] = fmaxf(mx[k], fabsf(y));
+                gn::slab_add(y, s[k], q[k], mx[k]);
             }
         }
         if (APPLY) {                                        // GELU two channels per packed instruction (gemm_f16x3.h)
@@ -331,11 +332,15 @@ __global__ __launch_bounds__(256) void conv_ln_gelu_kernel(const float* __restri
     }
 }
 
-// GroupNorm coefficients per (window, channel) and the window's bound: |GELU(a y + b)| <= |a| max|y| + |b|
+// GroupNorm coefficients per (window, channel) and the window's bound: |GELU(a y + b)| <= |a| max|y| + |b|.  The moments come
+// from the slabs' float sums where those suffice (gn_stats.h); a channel whose mean outweighs its spread is summed again here,
+// in double, over its recomputed conv0 outputs (the FMA order of conv0_kernel: the y the apply pass will see).
+// xn, len: the windows' samples and their stride; cb: the conv bias or NULL
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restrict__ part, const float* __restrict__ g,
                                                           const float* __restrict__ be, float* __restrict__ ab,
                                                           unsigned* __restrict__ amax, int n, int C, int slabs,
-                                                          const int* __restrict__ T0w) {
+                                                          const int* __restrict__ T0w, const float* __restrict__ xn, int len,
+                                                          const float* __restrict__ w0, const float* __restrict__ cb) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= (int64_t)n * C) return;
     const int chunk = (int)(i / C), c = (int)(i % C);
@@ -347,12 +352,25 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* __restric
         q += (double)part[(((int64_t)chunk * slabs + sl) * 3 + 1) * C + c];
         mx = fmaxf(mx, part[(((int64_t)chunk * slabs + sl) * 3 + 2) * C + c]);
     }
-    const double mean = s / T0;
-    double var = q / T0 - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + 1e-5);
-    const double a = (double)g[c] * rstd;
-    const float af = (float)a, bf = (float)((double)be[c] - mean * a);
+    gn::Moments m = gn::moments_of_sums(s, q, T0);
+    if (!gn::sums_suffice(m)) {
+        const float* __restrict__ x = xn + (int64_t)chunk * len;
+        float wr[10];
+#pragma unroll
+        for (int j = 0; j < 10; ++j) wr[j] = w0[c * 10 + j];
+        const float bi = cb ? cb[c] : 0.f;
+        gn::Sums64 acc;
+        for (int t = 0; t < T0; ++t) {
+            float y = 0.f;
+#pragma unroll
+            for (int j = 0; j < 10; ++j) y = fmaf(wr[j], x[5 * t + j], y);
+            if (cb) y += bi;
+            acc.add(y);
+        }
+        m = gn::moments_of_sums(acc.s, acc.q, T0);
+    }
+    float af, bf;
+    gn::coefficients(m, g[c], be[c], af, bf);
     ab[((int64_t)chunk * 2 + 0) * C + c] = af;
     ab[((int64_t)chunk * 2 + 1) * C + c] = bf;
     atomicMax(amax + chunk, __float_as_uint((fabsf(af) * mx + fabsf(bf)) * 1.000001f));
@@ -509,7 +527,7 @@ int Forward::convs_group_norm(int g0, int g, const int* Tg) {
                                   nullptr, T[0], STAT_SLAB, slabs_g, s));
     const int64_t tot = (int64_t)g * C;
     hipLaunchKernelGGL(gn_finalize_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, ws + W.part,
-                       Wt + L.gng, Wt + L.gnb, ws + W.ab, camax, g, C, slabs_g, Tw + g0);
+                       Wt + L.gng, Wt + L.gnb, ws + W.ab, camax, g, C, slabs_g, Tw + g0, ws + W.xn, R.maxlen, Wt + L.conv0, cbias);
     RSAF_CHECK_HIP(hipGetLastError());
     RSAF_TRY(launch_scale_from_bound(camax, g, nullptr, 1.0f, nullptr, cscale, s));
     const int slab = 128;
