@@ -479,6 +479,77 @@ int rsaf_cnnlstm_train_backward_group_mixed(const rsaf_cnnlstm_train_item* items
 int rsaf_cnnlstm_forward_group_mixed(const rsaf_cnnlstm_forward_item* items_host, const rsaf_cnnlstm_arch* arch_host,
                                      int K, int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream);
 
+/* ---- Input gradient of the training step ----------------------------------------------------------------------
+ * What `loss.backward()` leaves in `x.grad` when a trainable module sits in front of the classifier (a mix of encoder
+ * layers, a projection, a perturbation of the embeddings).  The entries below are rsaf_cnnlstm_train_backward,
+ * _backward_group and _backward_group_mixed with three more operands; the plain entries keep their code and their bits.
+ *   dx [B][T][input_dim] float32, written (not accumulated) in every row: zero-padded frames and the odd last frame
+ *   carry gradient too, since nothing is masked.  With dy_c1 / dy_sc the gradients at the outputs of res_block1.conv1
+ *   and of the shortcut convolution (behind their BatchNorm backward) and dz1 the gradient at the block's sum:
+ *     dx[b,t,:] = sum_tap dy_c1[b, t-tap+1, :] . W1[:, :, tap] + dy_sc[b,t,:] . Wsc     (input_dim != channels)
+ *     dx        = (the convolution term) + dz1                                          (identity shortcut)
+ *   dx_scratch: rsaf_cnnlstm_train_dx_scratch_floats(input_dim, channels) floats (host only; -1 for bad dims), the
+ *   tap-flipped weights of the data-gradient GEMM.  `scratch` and `saved` keep the sizes of the plain entries.
+ * dx == NULL (an item, or the single entry): that replica wants none and runs exactly the launches of the plain entry;
+ * dx_scratch is then not read.  With dx, three launches are added per replica (two with the identity shortcut): the 1x1
+ * data-gradient GEMM of the shortcut, the flip of W1 and the k = 3 data-gradient GEMM whose epilogue adds the shortcut
+ * term.  The parameter gradients are the same bits with and without dx, and the recurrences of a group stay one launch
+ * per layer and pass.  Checks on top of those of the plain entries, all before the first launch, rsaf_last_error()
+ * naming the item: dx needs dx_scratch (RSAF_ERR_ARG); a short dx_scratch is RSAF_ERR_WORKSPACE; dx and dx_scratch
+ * share no float with each other, with x, saved, scratch or grads of their item, or with saved, scratch, grads, dx or
+ * dx_scratch of another item (RSAF_ERR_ARG). */
+int64_t rsaf_cnnlstm_train_dx_scratch_floats(int input_dim, int channels);
+int rsaf_cnnlstm_train_backward_dx(const float* x, int B, int T, int input_dim, int channels, int hidden,
+                                   int num_classes, int lstm_layers, int act, const float* params,
+                                   const float* mask_block1, const float* mask_block2,
+                                   const float* const* mask_lstm_host, const float* mask_fc, float* saved,
+                                   int64_t saved_floats, float* scratch, int64_t scratch_floats,
+                                   const float* dlogits, float* grads, float* dx, float* dx_scratch,
+                                   int64_t dx_scratch_floats, rsaf_stream_t stream);
+typedef struct {
+    const float* x;
+    int B, T;
+    const float* params;
+    const float* mask_block1;
+    const float* mask_block2;
+    const float* const* mask_lstm_host;
+    const float* mask_fc;
+    float* saved;
+    int64_t saved_floats;
+    float* scratch;
+    int64_t scratch_floats;
+    float* logits;                 /* not read: the item is a backward item */
+    float* bn_stats_out;           /* not read */
+    const float* dlogits;
+    float* grads;
+    float* dx;                     /* [B][T][input_dim], or NULL: no input gradient for this replica */
+    float* dx_scratch;             /* rsaf_cnnlstm_train_dx_scratch_floats floats; not read when dx is NULL */
+    int64_t dx_scratch_floats;
+} rsaf_cnnlstm_train_dx_item;
+int rsaf_cnnlstm_train_backward_group_dx(const rsaf_cnnlstm_train_dx_item* items_host, int K, int input_dim, int channels,
+                                         int hidden, int num_classes, int lstm_layers, int act, rsaf_stream_t stream);
+int rsaf_cnnlstm_train_backward_group_mixed_dx(const rsaf_cnnlstm_train_dx_item* items_host,
+                                               const rsaf_cnnlstm_arch* arch_host, int K, int input_dim,
+                                               int num_classes, int lstm_layers, rsaf_stream_t stream);
+
+/* ---- Learned mix of encoder layers ---------------------------------------------------------------------------
+ * x[b,t,:] = sum_l p[l] h[b,l,t,:] over the L hidden-state layers of a padded batch h [B][L][T][D] (what
+ * rsaf_w2v2_forward_ragged_hidden returns per file, stacked), p [L] device floats: the softmax of the learned weights,
+ * which with its Jacobian stays with the caller (two tiny ops on [L]).  1 <= L <= RSAF_LAYER_MIX_MAX, D % 4 == 0,
+ * B * T * D < 2^40; h, x and dx 16-byte aligned.
+ * rsaf_layer_mix_forward: one launch; every workgroup walks its chunks of (b, t, d) once (float4, grid stride) and loops
+ * over l, so x is written once and h read once.
+ * rsaf_layer_mix_backward: dp_out[l] = sum_{b,t,d} h[b,l,t,d] dx[b,t,d].  The (b, t, d) range is cut into parts whose
+ * number depends on the shape alone (csrc/layer_mix_layout.h); a part reads dx once for all L layers, accumulates its L
+ * sums in double and writes them to `partials` ([parts][L] doubles, rsaf_layer_mix_partials(B, L, T, D) of them: host
+ * only, -1 for bad dims); a second launch adds the parts in ascending order.  No atomics: the same bits on every call.
+ * A short `partials` (partials_count, in doubles) is RSAF_ERR_WORKSPACE. */
+#define RSAF_LAYER_MIX_MAX 32
+int rsaf_layer_mix_forward(const float* h, int B, int L, int T, int D, const float* p, float* x, rsaf_stream_t stream);
+int64_t rsaf_layer_mix_partials(int B, int L, int T, int D);
+int rsaf_layer_mix_backward(const float* h, const float* dx, int B, int L, int T, int D, double* partials,
+                            int64_t partials_count, float* dp_out, rsaf_stream_t stream);
+
 /* ---- Wav2Vec2 frame embeddings for a batch of equal-length chunks -----------------------------------
  * Replaces, per chunk, `processor(chunk).input_values` + `Wav2Vec2Model(...)(input_values)
  * .last_hidden_state` (src/foundation_model_extractor.py:113-116; third-party transformers

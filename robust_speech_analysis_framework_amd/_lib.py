@@ -35,6 +35,12 @@ class TrainItem(C.Structure):
                 ("scratch_floats", _L), ("logits", _P), ("bn_stats_out", _P), ("dlogits", _P), ("grads", _P)]
 
 
+class TrainDxItem(C.Structure):
+    """``rsaf_cnnlstm_train_dx_item``: a backward item of ``rsaf_cnnlstm_train_item`` plus where the gradient of its input goes
+    (``dx`` NULL: none wanted) and the scratch of that part."""
+    _fields_ = TrainItem._fields_ + [("dx", _P), ("dx_scratch", _P), ("dx_scratch_floats", _L)]
+
+
 class ForwardItem(C.Structure):
     """``rsaf_cnnlstm_forward_item``: one eval-mode forward of a group call."""
     _fields_ = [("x", _P), ("B", _I), ("T", _I), ("weights", _P), ("workspace", _P), ("workspace_bytes", _L), ("logits", _P)]
@@ -156,6 +162,14 @@ SIGNATURES = {
     "rsaf_cnnlstm_train_forward_group_mixed": (_I, [C.POINTER(TrainItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
     "rsaf_cnnlstm_train_backward_group_mixed": (_I, [C.POINTER(TrainItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
     "rsaf_cnnlstm_forward_group_mixed": (_I, [C.POINTER(ForwardItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_train_dx_scratch_floats": (_L, [_I, _I]),
+    "rsaf_cnnlstm_train_backward_dx": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _P, _P, _L,
+                                            _P]),
+    "rsaf_cnnlstm_train_backward_group_dx": (_I, [C.POINTER(TrainDxItem), _I, _I, _I, _I, _I, _I, _I, _P]),
+    "rsaf_cnnlstm_train_backward_group_mixed_dx": (_I, [C.POINTER(TrainDxItem), C.POINTER(Arch), _I, _I, _I, _I, _P]),
+    "rsaf_layer_mix_forward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
+    "rsaf_layer_mix_partials": (_L, [_I, _I, _I, _I]),
+    "rsaf_layer_mix_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _L, _P, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),
     "rsaf_mshds_intensity": (_I, [_P, _P, _I, _I, _P, _I, C.c_double, _I, _P, _P, _P]),

@@ -244,6 +244,7 @@ class CNNLSTM(nn.Module):
         self._packed_key = None
         self._workspace = None
         self._train_scratch = None
+        self._train_dx_scratch = None       # scratch of the input gradient of the training step (cnnlstm_train._Replica.want_dx)
         self.forced_masks = None            # tests: explicit dropout masks for the next training-mode forward
         self.dropout_stream = None          # a DropoutStream: masks from the counter-based generator instead of torch's RNG
 
@@ -256,6 +257,9 @@ class CNNLSTM(nn.Module):
         return self._packed
 
     def forward(self, x):
+        """Training mode: the training step on the autograd graph of the parameters and of ``x`` (``x.grad`` after
+        ``loss.backward()`` when ``x`` requires a gradient, so a trainable module in front of the classifier learns).
+        Eval mode: the inference forward, under ``no_grad`` and with no graph, for the input as for the parameters."""
         if not x.is_cuda:
             raise _lib.RsafError("CNNLSTM.forward needs a HIP (cuda) tensor: there is no CPU fallback")
         x = x.to(torch.float32)
@@ -265,7 +269,7 @@ class CNNLSTM(nn.Module):
                 # nn.BatchNorm1d in training mode (res_block2 sees B * (T // 2) values per channel)
                 raise ValueError("Expected more than 1 value per channel when training")
             x = x.contiguous()
-            return _train_step([self], [x.detach()], [_masks_for(self, x)], single=True)[0]
+            return _train_step([self], [x], [_masks_for(self, x)], single=True)[0]
         blob = self.packed_weights(x.device)
         with torch.no_grad():
             logits, self._workspace = cnnlstm_forward_packed(x, blob, self.dims, self.activation_name,

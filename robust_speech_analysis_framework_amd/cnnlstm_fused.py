@@ -473,8 +473,8 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=F
     """One whole training step of K independent ``CNNLSTM`` replicas, ``optimizers[k]`` the ``FusedAdam`` of ``models[k]``:
     group forward in training mode, ``nn.CrossEntropyLoss()`` (defaults) of ``labels[k]``, group backward, Adam and the
     BatchNorm running statistics -> ``(losses [K] on the device, [logits_k])``.  No autograd graph is built and ``.grad``
-    is not touched; the packing of the parameter blobs, the loss, the optimizer and the running statistics are one launch
-    each for the group.  A parameter with ``requires_grad = False`` keeps its value and its moments.
+    is not touched (an input that requires a gradient is a ``ValueError``: ``cnnlstm_train_group`` returns it); the packing of
+    the parameter blobs, the loss, the optimizer and the running statistics are one launch each for the group.  A parameter with ``requires_grad = False`` keeps its value and its moments.
 
     Arguments are checked as ``cnnlstm_train_group`` checks them; ``masks`` as there (``forced_masks`` and
     ``dropout_stream`` are honoured, and masks from torch's RNG are drawn replica by replica in the same order, so with
@@ -490,7 +490,7 @@ def cnnlstm_train_step_group(models, optimizers, xs, labels, masks=None, mixed=F
     of Adam (``FusedAdam``); norm and scale stay on the device (``last_grad_norm``, ``last_grad_scale``).  Both are per
     replica: the results of a replica do not depend on what the others of the group use."""
     optimizers, labels = list(optimizers), list(labels)
-    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group", mixed)
+    models, xs, mks = _check_train_group(models, xs, masks, "cnnlstm_train_step_group", mixed, graph=False)
     if not (len(optimizers) == len(labels) == len(models)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(labels)} label tensors")
     for k, (m, opt) in enumerate(zip(models, optimizers)):

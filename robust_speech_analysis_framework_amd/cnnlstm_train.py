@@ -369,12 +369,27 @@ class _Replica:
         self.logits = logits if logits is not None else new(B, d["num_classes"])
         self.stats = stats if stats is not None else new(5, 3, d["channels"])
         self.segs = self.params = self.dlogits = self.grads = None
+        self.dx = self.dx_scratch = None                  # backward: the gradient of ``x`` and its scratch, where one is wanted
 
     def backward_scratch(self):
         """The scratch is the model's cached buffer, shared with its later forwards.  Once the model has replaced it (a
         later forward needed a larger one, or one on another device), the backward takes a buffer of its own."""
         if self.scratch is not self.model._train_scratch:
             self.scratch = torch.empty_like(self.scratch)
+
+    def want_dx(self):
+        """The backward is to return the gradient of ``x`` as well: takes ``dx`` and the model's cached ``dx_scratch``
+        (``rsaf_cnnlstm_train_dx_scratch_floats``; kept while it is large enough, like the training scratch)."""
+        m, d = self.model, self.model.dims
+        n = int(_lib.load().rsaf_cnnlstm_train_dx_scratch_floats(d["input_dim"], d["channels"]))
+        if m._train_dx_scratch is None or m._train_dx_scratch.numel() < n or m._train_dx_scratch.device != self.x.device:
+            m._train_dx_scratch = torch.empty(n, dtype=torch.float32, device=self.x.device)
+        self.dx, self.dx_scratch = _new_dx(self.x), m._train_dx_scratch
+
+
+def _new_dx(x):
+    """Where the gradient of ``x`` [B, T, D] is written (every row; the kernels do not accumulate)."""
+    return torch.empty_like(x)
 
 
 def _fill_train_item(backward):
@@ -387,6 +402,8 @@ def _fill_train_item(backward):
         it.scratch, it.scratch_floats = r.scratch.data_ptr(), r.scratch.numel()
         if backward:
             it.dlogits, it.grads = r.dlogits.data_ptr(), r.grads.data_ptr()
+            if r.dx is not None:                       # only an ``rsaf_cnnlstm_train_dx_item`` has these (``_launch_group``)
+                it.dx, it.dx_scratch, it.dx_scratch_floats = r.dx.data_ptr(), r.dx_scratch.data_ptr(), r.dx_scratch.numel()
         else:
             it.logits, it.bn_stats_out = r.logits.data_ptr(), r.stats.data_ptr()
     return fill
@@ -394,16 +411,20 @@ def _fill_train_item(backward):
 
 def _launch_group(reps, backward, mixed=False):
     """``rsaf_cnnlstm_train_{forward,backward}_group`` over the replicas ``reps`` of one architecture; ``mixed``: the
-    ``_group_mixed`` entries over replicas of any mix of architectures."""
+    ``_group_mixed`` entries over replicas of any mix of architectures.  A backward in which a replica wants the gradient of
+    its input goes through the ``_dx`` entries (the others of the group leave ``dx`` NULL); one in which none does is the
+    call it has always been."""
     if not reps:
         return
     d = reps[0].model.dims
     entry = f"rsaf_cnnlstm_train_{'backward' if backward else 'forward'}_group"
+    dx = backward and any(r.dx is not None for r in reps)
+    item_type, suffix = (_lib.TrainDxItem, "_dx") if dx else (_lib.TrainItem, "")
     if mixed:
-        _launch_chunked(entry + "_mixed", _lib.TrainItem, reps, _fill_train_item(backward),
+        _launch_chunked(entry + "_mixed" + suffix, item_type, reps, _fill_train_item(backward),
                         *[d[f] for f in _SHARED_DIMS], arch=lambda r: _arch(r.model))
     else:
-        _launch_chunked(entry, _lib.TrainItem, reps, _fill_train_item(backward), *_dims5(d),
+        _launch_chunked(entry + suffix, item_type, reps, _fill_train_item(backward), *_dims5(d),
                         _ACT_CODE[reps[0].model.activation_name])
 
 
@@ -411,13 +432,15 @@ def _launch_single(r, backward):
     """``rsaf_cnnlstm_train_{forward,backward}`` of one replica: the path of ``model(x)``.  It runs ``lstm_rec4_kernel`` /
     ``lstm_bwd4_kernel`` where the group entries run their ``_group`` twins, and it is what the group paths are
     compared with bit for bit, so a group of one does not replace it."""
-    entry = f"rsaf_cnnlstm_train_{'backward' if backward else 'forward'}"
+    dx = backward and r.dx is not None
+    entry = f"rsaf_cnnlstm_train_{'backward' if backward else 'forward'}{'_dx' if dx else ''}"
     mk, m = r.masks, r.model
     out = (r.dlogits, r.grads) if backward else (r.logits, r.stats)
+    tail = (_lib.ptr(r.dx), _lib.ptr(r.dx_scratch), r.dx_scratch.numel()) if dx else ()
     _lib.check(getattr(_lib.load(), entry)(
         _lib.ptr(r.x), r.B, r.T, *_dims5(m.dims), _ACT_CODE[m.activation_name], _lib.ptr(r.blob), _lib.optr(mk["res_block1"]),
         _lib.optr(mk["res_block2"]), r.lstm_ptrs, _lib.optr(mk["fc"]), _lib.ptr(r.saved), r.saved.numel(), _lib.ptr(r.scratch),
-        r.scratch.numel(), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.stream_ptr(None)), entry)
+        r.scratch.numel(), _lib.ptr(out[0]), _lib.ptr(out[1]), *tail, _lib.stream_ptr(None)), entry)
 
 
 def _launch(reps, backward, path):
@@ -432,12 +455,16 @@ def _launch(reps, backward, path):
 # ---- autograd function ------------------------------------------------------------------------------------------------------
 class _TrainStep(torch.autograd.Function):
     """(logits_0, ..., logits_K-1) of K replicas in training mode; backward fills the parameter gradients of every
-    replica whose output received a gradient (none for the inputs).  ``path``: "single" is the one replica of
-    ``model(x)``, which goes through the single entries; "group" / "mixed" as ``_launch`` takes it."""
+    replica whose output received a gradient, and returns the gradient of every input that requires one (float32
+    [B, T, D], zero-padded frames included: nothing is masked).  A backward in which no input requires a gradient runs
+    the launches it ran before inputs could.  ``tensors``: the K inputs (float32, contiguous), then the parameters.
+    Double backward is not supported.  ``path``: "single" is the one replica of ``model(x)``, which goes through the single
+    entries; "group" / "mixed" as ``_launch`` takes it."""
 
     @staticmethod
-    def forward(ctx, models, xs, masks, segments, path, *params):
+    def forward(ctx, models, masks, segments, path, K, *tensors):
         ctx.set_materialize_grads(False)          # an output outside the loss arrives as None, not as zeros
+        xs = tensors[:K]
         reps = []
         for model, x, mk, sg in zip(models, xs, masks, segments):
             r = _Replica(model, x, mk, _pack_train_blob(model, x.device, sg)[1])
@@ -450,38 +477,45 @@ class _TrainStep(torch.autograd.Function):
         return tuple(r.logits for r in reps)
 
     @staticmethod
+    @torch.autograd.function.once_differentiable
     def backward(ctx, *dlogits):
         if ctx.reps is None:
             raise RuntimeError(f"CNNLSTM {'' if ctx.path == 'single' else 'group '}training step: backward can run once per forward "
                                "(the saved activations are consumed)")
         live = []
-        for r, dl in zip(ctx.reps, dlogits):
+        for k, (r, dl) in enumerate(zip(ctx.reps, dlogits)):
             if dl is None:
                 continue
             r.backward_scratch()
             r.dlogits = dl.to(torch.float32).contiguous()
             r.grads = torch.zeros_like(r.blob)
+            if ctx.needs_input_grad[5 + k]:
+                r.want_dx()
             live.append(r)
         _launch(live, True, ctx.path)
         out = []
         for r, dl in zip(ctx.reps, dlogits):
             out += [None] * len(r.params) if dl is None else _unpack_grads(r.segs, r.params, r.grads)
+        dxs = [r.dx for r in ctx.reps]            # None: no gradient asked for, or the output stayed out of the loss
         ctx.reps = None
-        return (None, None, None, None, None, *out)
+        return (None, None, None, None, None, *dxs, *out)
 
 
 def _train_step(models, xs, masks, single=False, mixed=False):
-    """Training-mode forward of checked replicas -> tuple of logits on the autograd graph of their parameters."""
+    """Training-mode forward of checked replicas -> tuple of logits on the autograd graph of their parameters and of the
+    inputs ``xs`` (float32, contiguous) that require a gradient."""
     segments = [_train_segments(m) for m in models]
     path = "single" if single else "mixed" if mixed else "group"
-    return _TrainStep.apply(models, xs, masks, segments, path, *[p for sg in segments for p in _blob_params(sg[0])])
+    return _TrainStep.apply(models, masks, segments, path, len(xs), *xs, *[p for sg in segments for p in _blob_params(sg[0])])
 
 
 # ---- group step ---------------------------------------------------------------------------------------------------------------
-def _check_train_group(models, xs, masks, who, mixed=False):
+def _check_train_group(models, xs, masks, who, mixed=False, graph=True):
     """Argument checks of a group training step; returns (models, float32 contiguous inputs, one mask set per replica:
     ``masks[k]``, else the model's ``forced_masks``, else from its ``dropout_stream`` (the replicas that come this far in
-    one launch), else drawn from torch's device RNG, replica by replica)."""
+    one launch), else drawn from torch's device RNG, replica by replica).
+    ``graph``: the inputs stay on their autograd graph; ``graph=False`` (the fused step, which builds none) refuses an input
+    that requires a gradient instead of dropping it."""
     models, xs = list(models), list(xs)
     if not models:
         raise ValueError(f"{who} needs at least one replica")
@@ -508,7 +542,12 @@ def _check_train_group(models, xs, masks, who, mixed=False):
             raise ValueError(f"replica {k}: Expected more than 1 value per channel when training")
 
     _check_group(models, xs, who, check_model, check_input, mixed)
-    xs = [x.detach().to(torch.float32).contiguous() for x in xs]
+    if not graph:
+        for k, x in enumerate(xs):
+            if x.requires_grad:
+                raise ValueError(f"replica {k}: the input requires a gradient, and {who} builds no autograd graph: "
+                                 "use cnnlstm_train_group, whose backward returns it")
+    xs = [(x if graph else x.detach()).to(torch.float32).contiguous() for x in xs]
     mks, streamed = [], []
     for k, (m, x) in enumerate(zip(models, xs)):
         mk = masks[k] if masks is not None else None
@@ -530,6 +569,8 @@ def cnnlstm_train_group(models, xs, masks=None, mixed=False):
     once: the replicas share nothing, so each model's ``.grad`` is the gradient of its own loss, and an output that
     stays out of the loss leaves its model without gradients.  Logits, gradients and BatchNorm buffers are those of K
     separate ``model(x)`` steps, bit for bit; the LSTM recurrences of all replicas run in one launch per layer and pass.
+    An input that requires a gradient receives it (``xs[k].grad`` after ``backward()``, as from ``model(x)``); a group may
+    mix such inputs with inputs that do not.
 
     ``masks[k]``: dropout keep masks in the format of ``draw_masks``; ``None`` (for the list or an entry) uses the
     model's ``forced_masks`` if set, else its ``dropout_stream`` if set (``draw_masks_group``: the masks of all such

@@ -240,6 +240,11 @@ inline WLayout make_wlayout(const Dims& d, int B, int T) {
     return W;
 }
 
+// ---- training: scratch of the input gradient (floats), apart from WLayout so that a step without one keeps its sizes -------
+// the tap-flipped transposed weights of res_block1.conv1 [D][3][C]: WLayout::wflip holds [C][3][C] only.  The shortcut term
+// of the input gradient [B*T][D] needs no room of its own: it waits in WLayout::t2 ([Nmax >= 3D][kp >= B*T]).
+inline int64_t dx_scratch_floats(const Dims& d) { return pad4((int64_t)d.D * 3 * d.C); }
+
 // ---- LDS of the recurrence kernels (cnnlstm_lstm.hip), in floats ----------------------------------------------------------
 // forward, 16 rows: h double-buffered [2][16][H + 4]
 constexpr int rec_ldh(int H) { return H + 4; }

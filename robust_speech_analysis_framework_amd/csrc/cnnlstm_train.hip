@@ -194,6 +194,34 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// The same for a BatchNorm over exactly two rows (B T' = 2 in block 2: one sequence of four or five frames).  There xhat is
+// +s in one row and -s in the other, so dy_a = -dy_b = g*rstd * (dz_a - dz_b)/2 * (1 - s^2), and 1 - s^2 = eps/(var + eps)
+// = eps*rstd^2 is 1e-5 to 1e-3 at ordinary variances: the general form above leaves it to the cancellation in
+// dz - mean(dz) - xhat*mean(dz*xhat), which keeps 2^-24 of the operands and so loses the whole factor in float32 (gradients
+// 2e-4 to 4e-4 of their largest magnitude off float64, the project's bar being 1e-4).  Here the factor is formed directly.
+// One thread per channel reads both rows before it writes either (dy may alias dout).
+template <int PRE>
+__global__ __launch_bounds__(256) void bn_bwd_pair_kernel(const float* __restrict__ dout, const float* __restrict__ mask,
+                                                          const float* __restrict__ y, const float* __restrict__ stat,
+                                                          const float* __restrict__ g, const float* __restrict__ be, float eps,
+                                                          float* __restrict__ dy, int act, int C) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float rstd = stat[2 * C + c];
+    float dz[2];
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        dz[r] = dout[r * C + c];
+        if (PRE) {
+            if (mask) dz[r] *= mask[r * C + c];
+            dz[r] *= act_df(g[c] * ((y[r * C + c] - stat[c]) * rstd) + be[c], act);
+        }
+    }
+    const float d = g[c] * rstd * (0.5f * (dz[0] - dz[1])) * (eps * rstd * rstd);
+    dy[c] = d;
+    dy[C + c] = -d;
+}
+
 __global__ __launch_bounds__(256) void mul_kernel(const float4* __restrict__ a, const float4* __restrict__ m,
                                                   float4* __restrict__ out, int64_t n4) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
@@ -487,7 +515,12 @@ static int bn_backward(const Ctx& c, const float* dout, const float* mask, bool 
     {
         ProfScope prof("train_elementwise", c.s, 0.0, (double)rows * C * 12);
         const int64_t n = rows * C;
-        if (pre)
+        if (rows == 2) {                                 // the two-row closed form (bn_bwd_pair_kernel); eps: that of bn_stats
+            if (pre)
+                hipLaunchKernelGGL((bn_bwd_pair_kernel<1>), dim3((C + 255) / 256), dim3(256), 0, c.s, dout, mask, y, stat, g, be, 1e-5f, dy, c.d.act, C);
+            else
+                hipLaunchKernelGGL((bn_bwd_pair_kernel<0>), dim3((C + 255) / 256), dim3(256), 0, c.s, dout, mask, y, stat, g, be, 1e-5f, dy, c.d.act, C);
+        } else if (pre)
             hipLaunchKernelGGL((bn_bwd_apply_kernel<1>), dim3(ew_blocks(n)), dim3(256), 0, c.s, dout, mask, y, stat, g, be, sums, dy, c.d.act, n, C);
         else
             hipLaunchKernelGGL((bn_bwd_apply_kernel<0>), dim3(ew_blocks(n)), dim3(256), 0, c.s, dout, mask, y, stat, g, be, sums, dy, c.d.act, n, C);
@@ -530,20 +563,26 @@ static int wgrad(const Ctx& c, const float* dy, int64_t ld_dy, int M, const floa
 }
 
 // data gradient of a k=3/pad=1 convolution: dx[B][T][Cin] from dy[B][T][Cout] and w[Cout][3][Cin]
+static int flip_taps(const Ctx& c, const float* w, float* wf, int Cout, int Cin) {
+    const int64_t n = (int64_t)Cout * 3 * Cin;
+    ProfScope prof("train_elementwise", c.s, 0.0, (double)n * 8);
+    hipLaunchKernelGGL(flip_taps_kernel, dim3(ew_blocks(n)), dim3(256), 0, c.s, w, wf, Cout, Cin);
+    RSAF_CHECK_HIP(hipGetLastError());
+    return RSAF_OK;
+}
+
 static int conv3_dgrad(const Ctx& c, const float* dy, const float* w, float* dx, int B, int T, int Cin, int Cout) {
     float* wf = c.ws + c.W.wflip;
-    {
-        const int64_t n = (int64_t)Cout * 3 * Cin;
-        ProfScope prof("train_elementwise", c.s, 0.0, (double)n * 8);
-        hipLaunchKernelGGL(flip_taps_kernel, dim3(ew_blocks(n)), dim3(256), 0, c.s, w, wf, Cout, Cin);
-        RSAF_CHECK_HIP(hipGetLastError());
-    }
+    TRY(flip_taps(c, w, wf, Cout, Cin));
     return conv3(dy, wf, nullptr, nullptr, 0, 0, dx, B, T, Cout, Cin, ACT_NONE, c.s, "train_dgrad_gemm");
 }
 
 // ---- one replica's step, cut at its recurrences into phases -----------------------------------------------------------
 // forward:  fwd_cnn (+ layer-0 input projection) | per layer: recurrence | fwd_after_rec (dropout + next input projection)
 //           | fwd_head;   backward:  bwd_head | per layer: BPTT recurrence | bwd_after_rec | bwd_blocks.
+// bwd_blocks ends with the gradient of the step's input where a replica asks for one (Replica::dx; the _dx entries): the 1x1
+// data gradient of the shortcut, the flip of W1 and the k = 3 data-gradient GEMM with N = D, whose epilogue adds the two terms.
+// A replica without dx runs the launches of the plain entries, in their order.
 // The single entries run the phases of their one replica with the one-recurrence launchers; the group entries run every
 // phase for all replicas and one grouped recurrence launch in between.
 struct Replica {
@@ -555,6 +594,8 @@ struct Replica {
     const float* lin;               // forward: input of the next LSTM layer, `in` features wide
     int in;
     float *dcur, *dnext;            // backward: gradient w.r.t. the output of the current layer | the free buffer
+    float* dx;                      // backward: where the gradient w.r.t. x goes [B][T][D], or NULL: none wanted
+    float* dx_scratch;              //           tap-flipped transposed res_block1.conv1 weights [D][3][C] (dx_scratch_floats)
 };
 
 // argument checks of one replica (idx < 0: the single entries, whose messages carry no item)
@@ -575,6 +616,56 @@ static int check_item(const Dims& d, const rsaf_cnnlstm_train_item& it, bool bac
                                                                            : "saved/scratch buffer too small for this item's architecture");
     r->c = Ctx{d, s, it.scratch, r->WL};
     r->lin = nullptr; r->in = 0; r->dcur = r->dnext = nullptr;
+    r->dx = r->dx_scratch = nullptr;
+    return RSAF_OK;
+}
+
+// the input-gradient part of a backward item, after check_item: its own scratch, and no float of dx or dx_scratch inside
+// anything else the item reads or writes
+static int check_item_dx(const rsaf_cnnlstm_train_dx_item& it, const char* who, int idx, Replica* r) {
+    if (!it.dx) return RSAF_OK;
+    const Dims& d = r->c.d;
+    const int64_t n_dx = (int64_t)it.B * it.T * d.D, n_scr = dx_scratch_floats(d);
+    if (!it.dx_scratch) return fail(RSAF_ERR_ARG, who, idx, "dx without dx_scratch");
+    if (it.dx_scratch_floats < n_scr) return fail(RSAF_ERR_WORKSPACE, who, idx, "dx_scratch too small (rsaf_cnnlstm_train_dx_scratch_floats)");
+    struct { const char* name; const float* p; int64_t n; } other[] = {
+        {"x", it.x, n_dx}, {"saved", it.saved, r->S.total}, {"scratch", it.scratch, r->WL.total}, {"grads", it.grads, r->L.total}};
+    for (const auto& o : other) {
+        if (overlap(it.dx, n_dx, o.p, o.n)) return fail(RSAF_ERR_ARG, who, idx, std::string("`dx` overlaps `") + o.name + "`");
+        if (overlap(it.dx_scratch, n_scr, o.p, o.n)) return fail(RSAF_ERR_ARG, who, idx, std::string("`dx_scratch` overlaps `") + o.name + "`");
+    }
+    if (overlap(it.dx, n_dx, it.dx_scratch, n_scr)) return fail(RSAF_ERR_ARG, who, idx, "`dx` overlaps `dx_scratch`");
+    r->dx = it.dx;
+    r->dx_scratch = it.dx_scratch;
+    return RSAF_OK;
+}
+
+static rsaf_cnnlstm_train_item base_item(const rsaf_cnnlstm_train_dx_item& it) {
+    return rsaf_cnnlstm_train_item{it.x, it.B, it.T, it.params, it.mask_block1, it.mask_block2, it.mask_lstm_host, it.mask_fc, it.saved,
+                                   it.saved_floats, it.scratch, it.scratch_floats, it.logits, it.bn_stats_out, it.dlogits, it.grads};
+}
+
+// dx and dx_scratch of item k against everything item j writes, and the other way round (after check_item_dx of both)
+static int check_overlaps_dx(int K, const char* who, const Replica* reps) {
+    auto ranges = [](const Replica& r, const float* (&p)[5], int64_t (&n)[5]) {
+        p[0] = r.it.saved; n[0] = r.S.total; p[1] = r.it.scratch; n[1] = r.WL.total; p[2] = r.it.grads; n[2] = r.L.total;
+        p[3] = r.dx; n[3] = r.dx ? (int64_t)r.it.B * r.it.T * r.c.d.D : 0;
+        p[4] = r.dx_scratch; n[4] = r.dx ? dx_scratch_floats(r.c.d) : 0;
+    };
+    static const char* const names[5] = {"saved", "scratch", "grads", "dx", "dx_scratch"};
+    for (int k = 1; k < K; ++k)
+        for (int j = 0; j < k; ++j) {
+            const float *pa[5], *pb[5];
+            int64_t na[5], nb[5];
+            ranges(reps[j], pa, na);
+            ranges(reps[k], pb, nb);
+            for (int a = 0; a < 5; ++a)
+                for (int b = 0; b < 5; ++b) {
+                    if ((a < 3 && b < 3) || !na[a] || !nb[b]) continue;       // the pairs without dx: check_overlaps
+                    if (overlap(pa[a], na[a], pb[b], nb[b]))
+                        return fail(RSAF_ERR_ARG, who, k, std::string("its `") + names[b] + "` overlaps `" + names[a] + "` of item " + std::to_string(j));
+                }
+        }
     return RSAF_OK;
 }
 
@@ -612,6 +703,18 @@ static int check_group_mixed(const rsaf_cnnlstm_train_item* items, const rsaf_cn
         TRY(check_item(d, items[k], backward, s, who, k, &reps[k], RSAF_ERR_ARG));
     }
     return check_overlaps(items, K, backward, who, reps);
+}
+
+// the backward groups with input gradients: the checks of the plain entries on the plain part of every item, then the dx part
+static int check_group_dx(const Dims* d, const rsaf_cnnlstm_train_dx_item* items, const rsaf_cnnlstm_arch* arch, int K, int input_dim,
+                          int num_classes, int lstm_layers, hipStream_t s, const char* who, Replica* reps) {
+    TRY(check_group_args(K, items, who));
+    rsaf_cnnlstm_train_item base[RSAF_CNNLSTM_GROUP_MAX];
+    for (int k = 0; k < K; ++k) base[k] = base_item(items[k]);
+    if (d) TRY(check_group(*d, base, K, true, s, who, reps));
+    else TRY(check_group_mixed(base, arch, K, input_dim, num_classes, lstm_layers, true, s, who, reps));
+    for (int k = 0; k < K; ++k) TRY(check_item_dx(items[k], who, k, &reps[k]));
+    return check_overlaps_dx(K, who, reps);
 }
 
 static int fwd_inproj(Replica& r, const PLayout& L, int l) {
@@ -873,9 +976,25 @@ static int bwd_blocks(Replica& r, const PLayout& L) {
     TRY(bn_backward(c, dz1, nullptr, false, saved + S.y2, stat(2), P + L.c2.g, P + L.c2.be, rows, G + L.c2.g, G + L.c2.be, dy2));
     TRY(colsum(c, dy2, C, rows, C, G + L.c2.b));
     TRY(wgrad(c, dy2, C, C, saved + S.a1d, C, C, 3, 0, B, T, G + L.c2.w));
+    // input gradient, shortcut term: dz1 itself for the identity (bufC is not written again), else dy_sc . Wsc while dy1 still
+    // holds dy_sc.  It waits in t2, which is free between two weight gradients and holds [Nmax >= 3D][kp >= rows] floats.
+    const float* dx_sc = dz1;
+    if (r.dx && D != C) {
+        float* sc_term = c.ws + c.W.t2;                              // [rows][D]
+        GemmParams p = gemm_params_plain(dy1, P + L.sc.w, sc_term, (int)rows, D, C, C, D, D);
+        p.b_kn = 1;                                                  // Wsc [C][D] read as [K][N]
+        TRY(launch_gemm_f32(p, s, "train_dgrad_gemm"));
+        dx_sc = sc_term;
+    }
     TRY(conv3_dgrad(c, dy2, P + L.c2.w, dy1, B, T, C, C));           // dy1 now holds d(a1d)
     TRY(bn_backward(c, dy1, r.it.mask_block1, true, saved + S.y1, stat(0), P + L.c1.g, P + L.c1.be, rows, G + L.c1.g, G + L.c1.be, dy2));
     TRY(colsum(c, dy2, C, rows, C, G + L.c1.b));
+    if (r.dx) {
+        // dx = dgrad of conv1 (the k = 3 data-gradient GEMM with N = D, flipped weights [D][3][C] in dx_scratch) + the shortcut
+        // term as the epilogue's residual; ahead of the last weight gradient, which takes t2 back
+        TRY(flip_taps(c, P + L.c1.w, r.dx_scratch, C, D));
+        TRY(conv3(dy2, r.dx_scratch, nullptr, dx_sc, D, (int64_t)T * D, r.dx, B, T, C, D, ACT_NONE, s, "train_dgrad_gemm"));
+    }
     TRY(wgrad(c, dy2, C, C, x, D, D, 3, 0, B, T, G + L.c1.w));
     return RSAF_OK;
 }
@@ -987,6 +1106,27 @@ int rsaf_cnnlstm_train_backward(const float* x, int B, int T, int input_dim, int
     return run_backward(&r, 1, SINGLE);
 }
 
+int64_t rsaf_cnnlstm_train_dx_scratch_floats(int input_dim, int channels) {
+    Dims d{input_dim, channels, 64, 2, 1, ACT_SILU};
+    if (check_dims(d) != RSAF_OK) return -1;
+    return dx_scratch_floats(d);
+}
+
+int rsaf_cnnlstm_train_backward_dx(const float* x, int B, int T, int input_dim, int channels, int hidden, int num_classes,
+                                   int lstm_layers, int act, const float* params, const float* mask_block1,
+                                   const float* mask_block2, const float* const* mask_lstm_host, const float* mask_fc, float* saved,
+                                   int64_t saved_floats, float* scratch, int64_t scratch_floats, const float* dlogits, float* grads,
+                                   float* dx, float* dx_scratch, int64_t dx_scratch_floats, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
+    TRY(check_dims(d));
+    const rsaf_cnnlstm_train_dx_item it{x, B, T, params, mask_block1, mask_block2, mask_lstm_host, mask_fc, saved, saved_floats,
+                                        scratch, scratch_floats, nullptr, nullptr, dlogits, grads, dx, dx_scratch, dx_scratch_floats};
+    Replica r;
+    TRY(check_item(d, base_item(it), true, (hipStream_t)stream, __func__, -1, &r));
+    TRY(check_item_dx(it, __func__, -1, &r));
+    return run_backward(&r, 1, SINGLE);
+}
+
 int rsaf_cnnlstm_train_group_max(void) { return RSAF_CNNLSTM_GROUP_MAX; }
 
 int rsaf_cnnlstm_train_forward_group(const rsaf_cnnlstm_train_item* items_host, int K, int input_dim, int channels, int hidden,
@@ -1005,6 +1145,14 @@ int rsaf_cnnlstm_train_backward_group(const rsaf_cnnlstm_train_item* items_host,
     return run_backward(reps, K, GROUPED);
 }
 
+int rsaf_cnnlstm_train_backward_group_dx(const rsaf_cnnlstm_train_dx_item* items_host, int K, int input_dim, int channels, int hidden,
+                                         int num_classes, int lstm_layers, int act, rsaf_stream_t stream) {
+    Dims d{input_dim, channels, hidden, num_classes, lstm_layers, act};
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group_dx(&d, items_host, nullptr, K, input_dim, num_classes, lstm_layers, (hipStream_t)stream, __func__, reps));
+    return run_backward(reps, K, GROUPED);
+}
+
 int rsaf_cnnlstm_train_forward_group_mixed(const rsaf_cnnlstm_train_item* items_host, const rsaf_cnnlstm_arch* arch_host, int K,
                                            int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
     Replica reps[RSAF_CNNLSTM_GROUP_MAX];
@@ -1016,6 +1164,13 @@ int rsaf_cnnlstm_train_backward_group_mixed(const rsaf_cnnlstm_train_item* items
                                             int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
     Replica reps[RSAF_CNNLSTM_GROUP_MAX];
     TRY(check_group_mixed(items_host, arch_host, K, input_dim, num_classes, lstm_layers, true, (hipStream_t)stream, __func__, reps));
+    return run_backward(reps, K, MIXED);
+}
+
+int rsaf_cnnlstm_train_backward_group_mixed_dx(const rsaf_cnnlstm_train_dx_item* items_host, const rsaf_cnnlstm_arch* arch_host, int K,
+                                               int input_dim, int num_classes, int lstm_layers, rsaf_stream_t stream) {
+    Replica reps[RSAF_CNNLSTM_GROUP_MAX];
+    TRY(check_group_dx(nullptr, items_host, arch_host, K, input_dim, num_classes, lstm_layers, (hipStream_t)stream, __func__, reps));
     return run_backward(reps, K, MIXED);
 }
 
