@@ -583,7 +583,9 @@ int rsaf_w2v2_forward(const float* wav, const int64_t* chunk_start, int n_chunks
  * T_i = rsaf_w2v2_frames(chunk_len[i]) frames, written to rows out_row_start[i] .. +T_i (or packed, window after window,
  * when out_row_start is NULL).  chunk_len_host: the same lengths on the host (launch geometry); they must be
  * NON-INCREASING.  Every window is normalised, GroupNorm-ed, zero-padded (positional conv) and attended over its own
- * frames only: the values are those of the per-window call.                                                          */
+ * frames only: the values are those of the per-window call.  That holds for window lengths of any mix: where the lengths
+ * of a call span frame counts at which the forward changes kernels (256 and 512 frames), the call is run as consecutive
+ * sub-calls, one per run of windows that share their kernels, in the same workspace and on the same stream.           */
 int64_t rsaf_w2v2_workspace_bytes_ragged(const int* chunk_len_host, int n_chunks, int conv_dim, int hidden, int layers,
                                          int heads, int intermediate, int pos_kernel, int pos_groups);
 int rsaf_w2v2_forward_ragged(const float* wav, const int64_t* chunk_start, const int* chunk_len,

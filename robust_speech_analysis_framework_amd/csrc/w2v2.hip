@@ -128,6 +128,35 @@ static int make_cfg(Cfg& c, int conv_dim, int hidden, int layers, int heads, int
     return arg_error("check_cfg", check_cfg(c));
 }
 
+// A ragged call.  Windows of one regime (w2v2_layout.h: window_regime): one forward, as ever.  Windows that span regimes: one
+// forward per regime run on that run's sub-list, one after the other in the caller's workspace on the caller's stream, so
+// every window takes the kernels, and returns the bits, of a call of its own.  The tables advance by the run's first
+// window; packed output (out_row_start NULL) and its taps advance by the rows already written.
+static int forward_runs(const float* wav, const int64_t* chunk_start, const int* len_dev, const int* len_host, const Rag& R, const Cfg& c,
+                        const float* weights, void* workspace, int64_t workspace_bytes, float* out, const int64_t* out_row_start,
+                        hipStream_t s, float* const* taps = nullptr) {
+    const std::vector<std::pair<int, int>> runs = regime_runs(c, R);
+    if (runs.size() == 1)
+        return forward_impl(wav, chunk_start, len_dev, R, c, weights, workspace, workspace_bytes, out, out_row_start, s, taps);
+    RSAF_CHECK_ARG(wav && chunk_start && weights && workspace && out, "NULL pointer");
+    if (workspace_bytes < make_ws(c, R).total * (int64_t)sizeof(float)) {      // the size published for the call covers every run
+        set_error("rsaf_w2v2_forward: workspace too small");
+        return RSAF_ERR_WORKSPACE;
+    }
+    std::vector<float*> run_taps((size_t)c.L + 1, nullptr);
+    for (const auto& run : runs) {
+        const int b = run.first;
+        Rag Rr;
+        RSAF_TRY(arg_error("make_rag", make_rag(len_host + b, run.second - b, 0, Rr)));
+        const int64_t skip = out_row_start ? 0 : R.row0[b] * (int64_t)c.Hd;
+        if (taps)
+            for (int k = 0; k <= c.L; ++k) run_taps[k] = taps[k] ? taps[k] + skip : nullptr;
+        RSAF_TRY(forward_impl(wav, chunk_start + b, len_dev + b, Rr, c, weights, workspace, workspace_bytes, out + skip,
+                              out_row_start ? out_row_start + b : nullptr, s, taps ? run_taps.data() : nullptr));
+    }
+    return RSAF_OK;
+}
+
 }  // namespace w2v2
 }  // namespace rsaf
 
@@ -245,7 +274,8 @@ int rsaf_w2v2_forward_ragged_ex(const float* wav, const int64_t* chunk_start, co
     RSAF_CHECK_ARG(chunk_len && chunk_len_host, "NULL length table");
     Rag R;
     RSAF_TRY(arg_error("make_rag", make_rag(chunk_len_host, n_chunks, 0, R)));
-    return forward_impl(wav, chunk_start, chunk_len, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream);
+    return forward_runs(wav, chunk_start, chunk_len, chunk_len_host, R, c, weights, workspace, workspace_bytes, out, out_row_start,
+                        (hipStream_t)stream);
 }
 
 int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start, const int* chunk_len, const int* chunk_len_host,
@@ -276,8 +306,8 @@ int rsaf_w2v2_forward_ragged_hidden(const float* wav, const int64_t* chunk_start
     RSAF_CHECK_ARG(hidden_plane_floats >= R.rows * (int64_t)hidden, "hidden_plane_floats smaller than the call's frames");
     std::vector<float*> taps((size_t)layers + 1, nullptr);
     for (int j = 0; j < n_hidden; ++j) taps[hidden_index_host[j]] = hidden_out + (int64_t)j * hidden_plane_floats;
-    return forward_impl(wav, chunk_start, chunk_len, R, c, weights, workspace, workspace_bytes, out, out_row_start, (hipStream_t)stream,
-                        taps.data());
+    return forward_runs(wav, chunk_start, chunk_len, chunk_len_host, R, c, weights, workspace, workspace_bytes, out, out_row_start,
+                        (hipStream_t)stream, taps.data());
 }
 
 }  // extern "C"

@@ -112,6 +112,9 @@ struct Forward {
     const int* T;
     const int64_t rows;
     const float scale;
+    // regime: what the frame-count predicates pick at the longest window (w2v2_layout.h); the entry points hand Forward windows
+    // of one regime only.
+    const Regime regime;
     // fused: attention on the fp16 matrix pipe, q / k / v as plane pairs.  relpos (REL_POS_BIAS): the gates come from the fp32
     // rows the q/k/v projection reads: x (post-LN), or LN1(h), which the stable-layer-norm LayerNorms then also write in fp32
     // into the att buffer (free until the attention writes it)
@@ -136,7 +139,7 @@ struct Forward {
     Forward(const Cfg& c_, const Rag& R_, const Workspace& W_, const float* weights, void* workspace, hipStream_t s_)
         : c(c_), R(R_), L(make_layout(c_)), W(W_), Wt(weights), ws(static_cast<float*>(workspace)), s(s_), n(R_.n), C(c_.C), Hd(c_.Hd),
           Tt(R_.Tmax[6]), G(conv_group(R_.n)), hd(c_.Hd / c_.NH), T(R_.Tmax), rows(R_.rows), scale(1.0f / sqrtf((float)hd)),
-          fused(fused_attention(c_, Tt)), relpos(c_.flags & F_REL_POS_BIAS), pre_ln(c_.flags & F_PRE_LN),
+          regime(window_regime(c_, Tt)), fused(regime.fused), relpos(c_.flags & F_REL_POS_BIAS), pre_ln(c_.flags & F_PRE_LN),
           layer_norm(c_.flags & F_LAYER_FEAT_NORM), conv_bias(c_.flags & F_CONV_BIAS),
           Tw(reinterpret_cast<int*>(ws + W.t_Tw)), row0(reinterpret_cast<int64_t*>(ws + W.t_row0)),
           ztab(reinterpret_cast<int64_t*>(ws + W.t_ztab)), rowwin(reinterpret_cast<int*>(ws + W.t_rowwin)),

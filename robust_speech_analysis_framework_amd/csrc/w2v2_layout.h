@@ -317,6 +317,32 @@ inline bool posconv_resident(const Cfg& c, int Tt) {
     return cg <= 64 && Tt <= PC_ROWS && (c.PK * (cg / 16)) % (4 * split) == 0 && PosconvLds::make(cg, c.PK, split).bytes() <= 160 * 1024;
 }
 
+// The regime of a window of Tt frames: what the three frame-count predicates pick for it, stated once for Forward (which
+// reads it at the call's longest window) and for the ragged entry points (which read it per window).  Two windows of one
+// regime run the same kernels in the same summation order whichever call they share; a call whose windows span several
+// regimes is run as one sub-call per regime run (regime_runs), so a window's values never depend on its neighbours.
+// posconv: 0 where the frame count picks nothing (the positional stack, group widths off the f16x3 path) or the batched
+// GEMM, else the row split of posconv_f16x3_kernel.
+struct Regime {
+    bool fused;
+    int posconv;
+    bool operator==(const Regime& o) const { return fused == o.fused && posconv == o.posconv; }
+    bool operator!=(const Regime& o) const { return !(*this == o); }
+};
+inline Regime window_regime(const Cfg& c, int Tt) {
+    const bool lds = c.pos_depth() == 0 && posconv_on_f16x3(c) && posconv_resident(c, Tt);
+    return Regime{fused_attention(c, Tt), lds ? posconv_split(Tt) : 0};
+}
+// [begin, end) of the maximal runs of consecutive windows of one regime (lengths are non-increasing: a regime's windows are contiguous)
+inline std::vector<std::pair<int, int>> regime_runs(const Cfg& c, const Rag& R) {
+    std::vector<std::pair<int, int>> runs;
+    for (int w = 0; w < R.n; ++w) {
+        if (w == 0 || window_regime(c, R.T6[w]) != window_regime(c, R.T6[w - 1])) runs.emplace_back(w, w + 1);
+        else runs.back().second = w + 1;
+    }
+    return runs;
+}
+
 // posstack_conv_kernel<NT>: the row tile's image [plane][NT panels][rows_alloc][16], PK - 1 halo rows included
 struct PosstackLds {
     int nt, rows_alloc;

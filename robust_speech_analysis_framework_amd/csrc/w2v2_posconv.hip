@@ -427,7 +427,7 @@ int Forward::positional_conv() {
     if (posconv_on_f16x3(c)) {
         RSAF_TRY(posconv_regroup_planes());
         const bool pc_off = [] { const char* e = getenv("RSAF_W2V2_POSCONV_GEMM"); return e && e[0] == '1'; }();   // per call: the tests toggle it
-        RSAF_TRY((!pc_off && posconv_resident(c, Tt)) ? posconv_lds() : posconv_batched_gemm());
+        RSAF_TRY((!pc_off && regime.posconv) ? posconv_lds() : posconv_batched_gemm());
     } else {                                                 // group widths that are no multiple of 16 (test geometries)
         RSAF_TRY(conv_runs_fp32(x, Wt + L.posw, Wt + L.posb, ACT_GELU, "w2v2_posconv_gemm", "w2v2_regroup"));
     }
@@ -538,7 +538,7 @@ int Forward::posconv_lds() {
     const int cg = Hd / c.PG;
     ProfScope prof("w2v2_posconv_gemm", s, 2.0 * (double)rows * cg * (double)c.PK * cg * c.PG, 0.0);
     return with_nt(cg / 16, [&](auto nt) {
-        return posconv_split(Tt) == 2 ? posconv_lds_launch<decltype(nt)::value, 2>() : posconv_lds_launch<decltype(nt)::value, 1>();
+        return regime.posconv == 2 ? posconv_lds_launch<decltype(nt)::value, 2>() : posconv_lds_launch<decltype(nt)::value, 1>();
     });
 }
 // grouped conv as a two-level batched GEMM on the f16x3 kernel's 256 x 64 tile: batch (window, group), M = T_w rows,

@@ -7,6 +7,7 @@
 // of every window group fit their buffers; (4) Rag equals a recomputation made here; (5) the LDS layouts request what the
 // formulas of the kernels' first form gave, stay within 160 KiB where their kernel runs, and their arrays are inside the
 // request, disjoint and 16-byte aligned; (6) the predicates take the recorded values.
+// With the argument `regimes`: the regime runs of ragged calls instead (see regimes_main).
 // Prints "ok <row>" per row; exit status 1 on the first failure.
 #include <algorithm>
 #include <cstdio>
@@ -240,7 +241,93 @@ static void check_lds(const Cfg& c, int Tt, const Want& want) {
     (void)Tt;
 }
 
-int main() {
+// ---- regime runs of a ragged call (`w2v2_layout_replay regimes`) -------------------------------------------------------------
+// A call whose windows span regimes is run as one sub-call per regime run in the caller's workspace.  Over every
+// non-increasing list of one to four windows with frame counts either side of 256, 512 and 513, at head widths 64 and 16,
+// with and without POS_CONV_STACK: the runs partition the list in order, each run is uniform under the predicates that pick
+// a path at its geometry (fused_attention always; posconv_resident, and posconv_split where resident, on the f16x3
+// positional path without a stack), neighbouring runs differ in one of them, and a run's workspace is no larger than the call's.
+struct PathPick { int fused, resident, split; };
+static PathPick path_pick(const Cfg& c, int Tt) {
+    const bool lds_path = c.pos_depth() == 0 && posconv_on_f16x3(c);
+    const bool res = lds_path && posconv_resident(c, Tt);
+    return {fused_attention(c, Tt), res, res ? posconv_split(Tt) : 0};
+}
+static bool same_pick(const PathPick& a, const PathPick& b) { return a.fused == b.fused && a.resident == b.resident && a.split == b.split; }
+
+static int64_t check_regime_runs(const Cfg& c, const std::vector<int>& frames) {
+    std::vector<int> len;
+    for (int T : frames) len.push_back(400 + 320 * (T - 1));
+    Rag R;
+    if (const char* msg = make_rag(len.data(), (int)len.size(), 0, R)) fail(std::string("make_rag: ") + msg);
+    for (size_t w = 0; w < frames.size(); ++w) expect(R.T6[w], frames[w], "frames of a window");
+    const std::vector<std::pair<int, int>> runs = regime_runs(c, R);
+    const int64_t call_total = make_ws(c, R).total;
+    int next = 0;
+    for (size_t r = 0; r < runs.size(); ++r) {
+        expect(runs[r].first, next, "a run begins where the last one ended");
+        if (runs[r].second <= runs[r].first) fail("an empty run");
+        next = runs[r].second;
+        const PathPick first = path_pick(c, R.T6[runs[r].first]);
+        for (int w = runs[r].first; w < runs[r].second; ++w)
+            if (!same_pick(path_pick(c, R.T6[w]), first)) fail("a run mixes paths at T = " + std::to_string(R.T6[w]));
+        if (r > 0 && same_pick(path_pick(c, R.T6[runs[r - 1].first]), first)) fail("two neighbouring runs take the same paths");
+        const Regime g = window_regime(c, R.T6[runs[r].first]);
+        expect(g.fused, first.fused, "Regime.fused");
+        expect(g.posconv, first.split, "Regime.posconv");
+        Rag Rr;
+        if (const char* msg = make_rag(len.data() + runs[r].first, runs[r].second - runs[r].first, 0, Rr)) fail(std::string("make_rag(run): ") + msg);
+        expect(Rr.rows, R.row0[runs[r].second] - R.row0[runs[r].first], "rows of a run");
+        const int64_t run_total = make_ws(c, Rr).total;
+        if (run_total > call_total)
+            fail("a run needs " + std::to_string(run_total) + " floats of workspace, the call has " + std::to_string(call_total));
+    }
+    expect(next, R.n, "the runs end at the last window");
+    return (int64_t)runs.size();
+}
+
+static int regimes_main() {
+    const int stack = F_LAYER_FEAT_NORM | F_POS_CONV_STACK | (5 << RSAF_W2V2_POS_DEPTH_SHIFT);
+    struct Row { const char* name; Cfg c; int max_runs; };
+    const Row rows[] = {
+        {"hd64-cg16", {32, 128, 1, 2, 128, 16, 8, 1e-5f, 0}, 3},              // tests/test_w2v2_long_windows_gpu.py, main geometry
+        {"hd64-cg16-wavlm", {32, 128, 1, 2, 128, 16, 8, 1e-5f, F_REL_POS_BIAS}, 3},
+        {"hd64-base", {512, 768, 12, 12, 3072, 128, 16, 1e-5f, 0}, 3},
+        {"hd64-large-stable", {512, 1024, 24, 16, 4096, 128, 16, 1e-5f, 7}, 2},   // group width 64: 512 rows and 127 taps exceed the LDS
+        {"hd16-cg8", {32, 64, 2, 4, 128, 16, 8, 1e-5f, 0}, 1},                // no regimes: exact-fp32 convolution, three launches
+        {"hd16-cg16", {32, 64, 2, 4, 128, 16, 4, 1e-5f, F_REL_POS_BIAS}, 3},   // the positional kernel alone has regimes
+        {"hd64-stack", {512, 768, 12, 12, 3072, 19, 16, 1e-5f, stack}, 2},     // the stack picks nothing by T; the attention does
+        {"hd16-stack", {32, 64, 2, 4, 128, 19, 4, 1e-5f, stack}, 1}};
+    const int F[] = {1025, 514, 513, 512, 511, 499, 258, 257, 256, 255, 249, 120, 2};   // descending
+    const int nF = (int)(sizeof(F) / sizeof(F[0]));
+    for (const Row& row : rows) {
+        g_row = std::string("regimes ") + row.name;
+        if (const char* msg = check_cfg(row.c)) fail(std::string("check_cfg: ") + msg);
+        int64_t lists = 0, most = 0;
+        for (int a = 0; a < nF; ++a)
+            for (int b = a; b <= nF; ++b)
+                for (int d = (b < nF ? b : nF); d <= nF; ++d)
+                    for (int e = (d < nF ? d : nF); e <= nF; ++e) {
+                        std::vector<int> frames = {F[a]};
+                        for (int i : {b, d, e}) if (i < nF) frames.push_back(F[i]);
+                        most = std::max(most, check_regime_runs(row.c, frames));
+                        ++lists;
+                    }
+        expect(most, row.max_runs, "most runs of a list");
+        // the list of the GPU test: 1025, 513 | 512, 499, 257 | 256 .. 2 at the main geometry
+        if (check_regime_runs(row.c, {1025, 513, 512, 499, 257, 256, 249, 120, 33, 2}) != row.max_runs) fail("runs of the ten-window list");
+        // many equal windows and a tail: the feature encoder's group buffers and the score buffer are sized by the call
+        std::vector<int> many(600, 499);
+        many.insert(many.end(), 40, 249);
+        many.push_back(2);
+        check_regime_runs(row.c, many);
+        std::printf("ok %s (%lld lists)\n", g_row.c_str(), (long long)lists);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "regimes") return regimes_main();
     const std::vector<WinSet> sets = window_sets();
     const int n_geoms = (int)(sizeof(GEOMS) / sizeof(GEOMS[0]));
     for (int gi = 0; gi < n_geoms; ++gi)

@@ -183,6 +183,8 @@ def test_hubert_base_geometry_matches_transformers(rsaf_lib):
 
 
 def test_wavlm_ragged_call_returns_the_bits_of_the_per_length_calls(rsaf_lib, wavlm_base):
+    """Windows of at most 249 frames at the base geometry; tests/test_w2v2_long_windows_gpu.py mixes windows either side of
+    256 and 512 frames, where the forward changes kernels."""
     import torch
     cfg, sd, eng = wavlm_base
     clip = synth.synth_clip(313, 7.0)

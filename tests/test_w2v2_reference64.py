@@ -71,6 +71,24 @@ def test_float32_baseline_is_the_same_code_in_float32():
             assert np.abs(a - b).max() <= 1e-4 * np.abs(b).max()
 
 
+def test_index_order_attention_products_change_nothing_in_float64():
+    """chain=True (tests/test_w2v2_long_windows_gpu.py takes its second float32 baseline from it) at T = 257, the first
+    window of the three-launch attention: in float64 the index-order products equal torch's own to 1e-12 of each state's
+    maximum, and in float32 they stay within float32's reach of the reference."""
+    import torch
+    T = 257
+    cfg, sd = R.conditioned_weights("a-group")
+    wav = R.waveform("control", 400 + 320 * (T - 1))
+    h64, c64 = R.forward64(sd, cfg, wav), R.forward64(sd, cfg, wav, chain=True)
+    c32 = R.forward64(sd, cfg, wav, dtype=torch.float32, chain=True)
+    assert len(h64) == len(c64) == len(c32) == cfg.num_hidden_layers + 1
+    for a, b, c in zip(h64, c64, c32):
+        assert a.shape == b.shape == c.shape == (T, cfg.hidden_size) and b.dtype == np.float64 and c.dtype == np.float32
+        assert np.abs(b - a).max() <= 1e-12 * np.abs(a).max()
+        assert np.abs(c - a).max() <= 1e-4 * np.abs(a).max()
+    assert np.array_equal(h64[0], c64[0])                         # hidden state 0 lies before any attention
+
+
 def test_hard_kinds_are_hard_and_the_control_is_not():
     """The conditions the GPU matrix asserts before its first launch, here without a GPU: mean^2 / var of conv0's float64
     output, worst channel."""

@@ -1,7 +1,7 @@
 """Wav2Vec2Model.forward in eval mode restated in plain torch operations, in float64 (the reference of the GPU tests) or, from
 the same code, in float32 (the baseline: what float32 arithmetic itself loses on an input).  A plain module, shared by
-tests/test_w2v2_attention_gpu.py and tests/test_w2v2_conditioning_gpu.py; tests/test_w2v2_reference64.py holds it to
-transformers' own model cast to float64.
+tests/test_w2v2_attention_gpu.py, tests/test_w2v2_conditioning_gpu.py and tests/test_w2v2_long_windows_gpu.py;
+tests/test_w2v2_reference64.py holds it to transformers' own model cast to float64.
 
 Covered: the group-norm and the layer-norm feature encoder, conv biases, the post-LN and the stable-layer-norm encoder and
 the preprocessor's do_normalize switch (model_type "wav2vec2"; HuBERT-base and WavLM-base differ from it in the encoder, and
@@ -43,12 +43,34 @@ def mean2_over_var(y):
     return float((y.mean(axis=1) ** 2 / (y.var(axis=1) + 1e-5)).max())
 
 
-def forward64(sd, cfg, wav, dtype=None):
+def _chain_scores(q, k):
+    """q k^T [.., T, T] accumulated one index of the head width at a time, in index order, in the tensors' dtype"""
+    import torch
+    s = torch.zeros(q.shape[:-1] + (k.shape[-2],), dtype=q.dtype)
+    for d in range(q.shape[-1]):
+        s = s + q[..., :, d:d + 1] * k[..., :, d].unsqueeze(-2)
+    return s
+
+
+def _chain_context(p, v):
+    """p v [.., T, hd] accumulated one key at a time, in key order, in the tensors' dtype"""
+    import torch
+    o = torch.zeros(p.shape[:-1] + (v.shape[-1],), dtype=p.dtype)
+    for j in range(p.shape[-1]):
+        o = o + p[..., :, j:j + 1] * v[..., j:j + 1, :]
+    return o
+
+
+def forward64(sd, cfg, wav, dtype=None, chain=False):
     """Wav2Vec2Model.forward in eval mode on one window, every operation in `dtype` (torch.float64 by default; the window's
     normalisation included): the list of hidden states, each [T, hidden], as transformers' output_hidden_states=True gives
     them.  Index 0 is the encoder's input after the positional convolution (post-LN encoder: and after the encoder LayerNorm;
     stable layer norm: before it, and the last state is the only one that passed it); index num_hidden_layers is the last
-    hidden state."""
+    hidden state.
+
+    chain: the two attention products q k^T and P v are accumulated one index at a time, in index order (a loop over the
+    head width, a loop over the keys), each step rounded to `dtype`: an order a float32 FMA chain may take, where torch's
+    own product blocks the sum.  Everything else is unchanged; in float64 the switch changes nothing beyond 1e-12."""
     import torch
     import torch.nn.functional as F
     dtype = dtype or torch.float64
@@ -91,7 +113,10 @@ def forward64(sd, cfg, wav, dtype=None):
             a = F.layer_norm(x, (D,), t[p + "layer_norm.weight"], t[p + "layer_norm.bias"], eps) if stable else x
             q, k, vv = (F.linear(a, t[p + f"attention.{n}_proj.weight"], t[p + f"attention.{n}_proj.bias"])
                         .view(B, T, nh, hd).transpose(1, 2) for n in "qkv")
-            a = torch.softmax((q @ k.transpose(-1, -2)) * hd ** -0.5, dim=-1) @ vv
+            if chain:
+                a = _chain_context(torch.softmax(_chain_scores(q, k) * hd ** -0.5, dim=-1), vv)
+            else:
+                a = torch.softmax((q @ k.transpose(-1, -2)) * hd ** -0.5, dim=-1) @ vv
             a = F.linear(a.transpose(1, 2).reshape(B, T, D), t[p + "attention.out_proj.weight"], t[p + "attention.out_proj.bias"])
             x = x + a
             if not stable:
@@ -106,6 +131,21 @@ def forward64(sd, cfg, wav, dtype=None):
         if stable:
             hidden[-1] = F.layer_norm(x, (x.shape[-1],), t["encoder.layer_norm.weight"], t["encoder.layer_norm.bias"], eps)
     return [h[0].numpy() for h in hidden]
+
+
+def wavlm64(sd, cfg, wav, dtype=None):
+    """transformers' WavLMModel of the config with the weights `sd` (built as _hf_model of tests/test_w2v2_families_gpu.py
+    builds it), cast to `dtype` (torch.float64 by default: the reference of the position-bias cases; torch.float32: their
+    baseline) and fed window_input(cfg, wav, dtype): the list of hidden states, each [T, hidden]."""
+    import torch
+    from test_w2v2_families_gpu import _hf_model
+    dtype = dtype or torch.float64
+    assert cfg.model_type == "wavlm"
+    m = _hf_model(cfg, sd).to(dtype)
+    with torch.no_grad():
+        hs = m(window_input(cfg, wav, dtype)[None], output_hidden_states=True).hidden_states
+    assert len(hs) == cfg.num_hidden_layers + 1
+    return [h[0].numpy() for h in hs]
 
 
 # ---- the conditioning matrix (tests/test_w2v2_conditioning_gpu.py; the CPU test uses its configurations and two kinds) ----
