@@ -960,6 +960,101 @@ typedef struct {
 } rsaf_collate_augment_item;
 int rsaf_collate_augment_group(const rsaf_collate_augment_item* items_host, int K, int width, rsaf_stream_t stream);
 
+/* ---- The layer mix inside the collate launch: resident layer stacks ----------------------------------------------------
+ * A store of layer stacks keeps sequence i, [L][T_i][width] as rsaf_w2v2_forward_ragged_hidden returns it per file, as
+ * L * T_i consecutive arena rows, layer-major: frame t of layer l is arena row row_start + l * T_i + t, row_start the
+ * first row of the block.  width % 4 == 0; arena, out and dx 16-byte aligned.  The padded stack [B][L][T][width] of a
+ * batch, L + 1 times the size of the batch the classifier reads, never exists.
+ *
+ * rsaf_collate_mix_group: ONE launch for K <= RSAF_CNNLSTM_GROUP_MAX items of one width, each with its own B, T, L and p:
+ *   out[b][t][:] = sum_l p[l] arena[row_start[b] + l * T_b + t][:]   for t < min(T_b, T),  T_b = row_count[b]
+ *   +0.0 everywhere else, written by the kernel (no memset, no index array)
+ * A member whose block [row_start[b], row_start[b] + L * T_b) does not lie wholly inside [0, arena_rows) is never read and
+ * comes out as zeros; a member of 0 (or fewer) frames is a block of zeros.  Per position: a = p[0] v_0, then a += p[l] v_l,
+ * float32, l ascending (the one inline function of csrc/layer_mix_layout.h that rsaf_layer_mix_forward calls too), so the
+ * batch has the bits of rsaf_layer_mix_forward on the zero-padded stack.  The labels are those of rsaf_collate_item.
+ * Grid: the workgroups of all items back to back, each one chunk of consecutive float4 of one member's `out`; the loads
+ * of four layers are issued before their adds.
+ * Checks, all before the launch, rsaf_last_error() naming the item: everything rsaf_collate_pad_group checks,
+ * 1 <= L <= RSAF_LAYER_MIX_MAX, width a positive multiple of 4, p not NULL, arena and out 16-byte aligned,
+ * B * T * width < 2^40.  Profiling family "train_collate_mix", bytes 4 * (L * frames * width + B * T * width).
+ *
+ * rsaf_collate_mix_backward_group: dp_out[l] = sum over the frames that exist of arena[...] . dx[b][t][:], for K items in
+ * TWO launches: one over the parts of all items, one final sum with one wave per (item, l).  Partition and summation
+ * order are those of rsaf_layer_mix_backward for the padded shape (B, L, T, width) (csrc/layer_mix_layout.h); a position
+ * whose frame does not exist is skipped, neither the arena nor dx is read there.  A product of two floats is exact in
+ * double and a skipped term is an exact +-0 added to a sum that starts at +0.0, so dp_out has the bits of
+ * rsaf_layer_mix_backward on the zero-padded stack.  No atomics: the same bits on every call, at any K.  `partials`:
+ * 8-byte aligned scratch of at least rsaf_layer_mix_partials(B, L, T, width) doubles, RSAF_ERR_WORKSPACE when shorter.
+ * Checks as above (dx, partials and dp_out for out; no labels); no two `partials` / `dp_out` ranges of a call overlap.
+ * Profiling family "train_collate_mix_backward", bytes 4 * ((L + 1) * frames * width). */
+typedef struct {
+    const float* arena;            /* device [arena_rows][width] */
+    int64_t arena_rows;
+    const int64_t* row_start;      /* device [B]: first arena row of the member's block */
+    const int32_t* row_count;      /* device [B]: the member's frames T_b */
+    int B, T, L;
+    const float* p;                /* device [L] */
+    float* out;                    /* device [B][T][width], written in full */
+    const int64_t* label_src;      /* the four label fields of rsaf_collate_item: all or none */
+    int64_t label_count;
+    const int64_t* label_index;
+    int64_t* label_out;
+    int64_t frames;                /* sum of min(T_b, T), as the host knows it; negative: counted as B * T */
+} rsaf_collate_mix_item;
+int rsaf_collate_mix_group(const rsaf_collate_mix_item* items_host, int K, int width, rsaf_stream_t stream);
+typedef struct {
+    const float* arena;
+    int64_t arena_rows;
+    const int64_t* row_start;
+    const int32_t* row_count;
+    int B, T, L;
+    const float* dx;               /* device [B][T][width] */
+    double* partials;              /* scratch, partials_count doubles */
+    int64_t partials_count;
+    float* dp_out;                 /* device [L] */
+    int64_t frames;
+} rsaf_collate_mix_backward_item;
+int rsaf_collate_mix_backward_group(const rsaf_collate_mix_backward_item* items_host, int K, int width, rsaf_stream_t stream);
+
+/* rsaf_layer_mix_adam_group: the step of the L mix weights of K items in ONE launch, one wave per item.
+ * mode RSAF_LAYER_MIX_FROM_DP: the gradient is the softmax Jacobian applied to dp in double,
+ *     dw_l = p_l (dp_l - sum_j p_j dp_j), the sum by the xor butterfly over the lanes, dw_l rounded to float once
+ *     (written to dw_out where that is not NULL);
+ * mode RSAF_LAYER_MIX_FROM_DW: the gradient is dw as given (the `.grad` of the weights).
+ * Then the published Adam update of rsaf_cnnlstm_adam_group (the same arithmetic: moments and update in double from the
+ * float operands, each rounded to float once; bias-corrected, eps outside the square root, no weight decay) on w,
+ * exp_avg, exp_avg_sq (device [L] each) with the item's lr, betas, eps and 1-based step, and
+ *     p_next_l = (float)(exp(w_l - max_j w_j) / sum_j exp(w_j - max_j w_j))      of the NEW w, in double, rounded once.
+ * mode RSAF_LAYER_MIX_SOFTMAX_ONLY: p_next from w as it stands; nothing else is read or written.
+ * L = 1 gives dw = 0 exactly and leaves w bit for bit.  Checks before the launch: 1 <= K <= RSAF_CNNLSTM_GROUP_MAX,
+ * 1 <= L <= RSAF_LAYER_MIX_MAX, a known mode, the pointers the mode reads or writes, and for the two stepping modes
+ * step >= 1, 0 <= beta < 1, eps >= 0, lr >= 0.  Profiling family "layer_mix_adam".
+ *
+ * Launch census of a group step of K <= RSAF_CNNLSTM_GROUP_MAX replicas with a learned mix each (cnnlstm_mix_train_step_group),
+ * on top of the launches of the fused step above (packing, dropout masks, forward, loss, backward through the _dx entries, Adam,
+ * running statistics), whatever K: 1 x rsaf_collate_mix_group (it replaces the step's rsaf_collate_pad_group), 2 launches of
+ * rsaf_collate_mix_backward_group, 1 x rsaf_layer_mix_adam_group, which leaves the p of the next step; a softmax-only launch of
+ * the same entry only where weights were changed from outside since the last step.  No launch reads or writes a [B][L][T][width]
+ * tensor. */
+#define RSAF_LAYER_MIX_FROM_DP 0
+#define RSAF_LAYER_MIX_FROM_DW 1
+#define RSAF_LAYER_MIX_SOFTMAX_ONLY 2
+typedef struct {
+    int L, mode;
+    const float* p;                /* device [L], FROM_DP */
+    const float* dp;               /* device [L], FROM_DP */
+    const float* dw;               /* device [L], FROM_DW */
+    float* dw_out;                 /* device [L] or NULL, FROM_DP */
+    float* w;                      /* device [L] */
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* p_next;                 /* device [L] */
+    double lr, beta1, beta2, eps;
+    int64_t step;
+} rsaf_layer_mix_adam_item;
+int rsaf_layer_mix_adam_group(const rsaf_layer_mix_adam_item* items_host, int K, rsaf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,29 @@ class CollateAugmentItem(C.Structure):
                                        ("sample_id", _P)]
 
 
+class CollateMixItem(C.Structure):
+    """``rsaf_collate_mix_item``: one mixed, padded batch out of resident layer stacks (``row_start``: first arena row of a
+    member's block of ``L * row_count`` rows)."""
+    _fields_ = [("arena", _P), ("arena_rows", _L), ("row_start", _P), ("row_count", _P), ("B", _I), ("T", _I), ("L", _I), ("p", _P),
+                ("out", _P), ("label_src", _P), ("label_count", _L), ("label_index", _P), ("label_out", _P), ("frames", _L)]
+
+
+class CollateMixBackwardItem(C.Structure):
+    """``rsaf_collate_mix_backward_item``: dL/dp of one such batch from the resident stacks and the step's ``dx``."""
+    _fields_ = [("arena", _P), ("arena_rows", _L), ("row_start", _P), ("row_count", _P), ("B", _I), ("T", _I), ("L", _I), ("dx", _P),
+                ("partials", _P), ("partials_count", _L), ("dp_out", _P), ("frames", _L)]
+
+
+LAYER_MIX_FROM_DP, LAYER_MIX_FROM_DW, LAYER_MIX_SOFTMAX_ONLY = 0, 1, 2
+
+
+class LayerMixAdamItem(C.Structure):
+    """``rsaf_layer_mix_adam_item``: the step of one mix's weights (``mode``: from ``p`` and ``dp``, from ``dw``, softmax only)."""
+    _fields_ = [("L", _I), ("mode", _I), ("p", _P), ("dp", _P), ("dw", _P), ("dw_out", _P), ("w", _P), ("exp_avg", _P),
+                ("exp_avg_sq", _P), ("p_next", _P), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("step", _L)]
+
+
 # symbol -> (restype, argtypes); must list every function declared in include/rsaf.h
 SIGNATURES = {
     "rsaf_abi_version": (_I, []),
@@ -170,6 +193,9 @@ SIGNATURES = {
     "rsaf_layer_mix_forward": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "rsaf_layer_mix_partials": (_L, [_I, _I, _I, _I]),
     "rsaf_layer_mix_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _L, _P, _P]),
+    "rsaf_collate_mix_group": (_I, [C.POINTER(CollateMixItem), _I, _I, _P]),
+    "rsaf_collate_mix_backward_group": (_I, [C.POINTER(CollateMixBackwardItem), _I, _I, _P]),
+    "rsaf_layer_mix_adam_group": (_I, [C.POINTER(LayerMixAdamItem), _I, _P]),
     "rsaf_mshds_frameout_doubles": (_I, []),
     "rsaf_mshds_clip_peak": (_I, [_P, _P, _I, _P, _P]),
     "rsaf_mshds_intensity": (_I, [_P, _P, _I, _I, _P, _I, C.c_double, _I, _P, _P, _P]),

@@ -393,3 +393,4 @@ from .cnnlstm_loops import (CNNLSTMGroup, eval_model_grouped, eval_replicas_lock
 from .augment import AugmentStream, Compose, FeatureMask, GaussianNoise, Scale, TimeMask  # noqa: E402,F401
 from .device_data import (DeviceBatchLoader, DeviceSequenceDataset, DeviceSequenceStore,  # noqa: E402,F401
                           batch_indices, collate_batches)
+from .layer_mix_train import cnnlstm_mix_train_step_group, collate_mix_batches  # noqa: E402,F401

@@ -66,10 +66,19 @@ class FusedAdam(torch.optim.Optimizer):
     clips nothing and still reports the norm.  ``step()`` does NOT modify ``.grad``: the scale is applied where Adam reads
     the gradient.  ``last_grad_norm`` and ``last_grad_scale`` are device scalars of the last clipped step (``None`` before
     it); reading them is the caller's sync, the step itself makes none.  The option is an attribute of the optimizer,
-    not an entry of ``param_groups``, which keep ``torch.optim.Adam``'s keys."""
+    not an entry of ``param_groups``, which keep ``torch.optim.Adam``'s keys.
+
+    ``layer_mix``: a ``LayerMix`` in front of the model, learned with it.  The optimizer then owns ``layer_mix.weights`` as a
+    second param group with the learning rate ``layer_mix_lr`` (``None``: the classifier's ``lr``) and the same betas and eps:
+    the format of ``torch.optim.Adam([{"params": model.parameters()}, {"params": [layer_mix.weights], "lr": ...}])``, which
+    state dicts follow in both directions and whose two groups the schedulers scale.  ``step()`` updates the weights from
+    ``weights.grad`` by one ``rsaf_layer_mix_adam_group`` launch (its ``dw`` mode), which also leaves the softmax of the new
+    weights on the device (``mix_p()``); ``cnnlstm_mix_train_step_group`` feeds the same kernel ``dL/dp``.
+    ``max_grad_norm`` keeps clipping over the classifier's parameters only, as ``clip_grad_norm_(model.parameters(), ...)``
+    says: the mix weights are not part of the norm and are not clipped.  Without ``layer_mix`` nothing changes."""
 
     def __init__(self, model, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, maximize=False,
-                 max_grad_norm=None):
+                 max_grad_norm=None, layer_mix=None, layer_mix_lr=None):
         from .cnnlstm import CNNLSTM
         if not isinstance(model, CNNLSTM):
             raise ValueError(f"FusedAdam: model must be a CNNLSTM, got {type(model).__name__}")
@@ -93,7 +102,24 @@ class FusedAdam(torch.optim.Optimizer):
             raise ValueError("FusedAdam: the parameters must be float32")
         # the keys of torch.optim.Adam's own param_groups, so that state dicts load in both directions
         defaults = dict(torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).defaults)
-        super().__init__(params, defaults)
+        if layer_mix is None:
+            if layer_mix_lr is not None:
+                raise ValueError("FusedAdam: layer_mix_lr without a layer_mix")
+            super().__init__(params, defaults)
+        else:
+            from .layer_mix import LayerMix
+            if not isinstance(layer_mix, LayerMix):
+                raise ValueError(f"FusedAdam: layer_mix must be a LayerMix, got {type(layer_mix).__name__}")
+            w = layer_mix.weights
+            if w.device != params[0].device or w.dtype != torch.float32 or not w.is_contiguous():
+                raise ValueError(f"FusedAdam: layer_mix.weights must be contiguous float32 on the model's device {params[0].device}, "
+                                 f"got {w.dtype} on {w.device}")
+            if layer_mix_lr is not None and not 0.0 <= layer_mix_lr:
+                raise ValueError(f"FusedAdam: invalid learning rate of the layer mix: {layer_mix_lr}")
+            super().__init__([{"params": params}, {"params": [w], "lr": lr if layer_mix_lr is None else layer_mix_lr}], defaults)
+        self.layer_mix = layer_mix
+        self._mix_p = self._mix_p_key = None    # softmax of the mix weights, cached against their version
+        self.last_mix_dp = None                 # dL/dp of the last fused mix step, on the device
         self.model = model
         self._order = _adam_order(model)
         self._steps = None                  # step count per parameter of _order (host mirror of state[p]['step']), None = unknown
@@ -123,6 +149,50 @@ class FusedAdam(torch.optim.Optimizer):
         if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
             raise ValueError("FusedAdam: weight_decay, amsgrad and maximize are not supported")
         return float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+    # -- the layer mix: a second param group of one parameter ----------------------------------------------------------------
+    def _mix_hyper(self):
+        g = self.param_groups[1]
+        if g.get("weight_decay", 0) != 0 or g.get("amsgrad", False) or g.get("maximize", False):
+            raise ValueError("FusedAdam: weight_decay, amsgrad and maximize are not supported")
+        return float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"])
+
+    def _mix_state(self):
+        """The moments of the mix weights, created as ``torch.optim.Adam`` creates them, float32 and contiguous."""
+        w = self.layer_mix.weights
+        st = self.state[w]
+        if "exp_avg" not in st:
+            st["step"] = torch.tensor(0.0, dtype=torch.float32)
+            st["exp_avg"] = torch.zeros_like(w, memory_format=torch.contiguous_format)
+            st["exp_avg_sq"] = torch.zeros_like(w, memory_format=torch.contiguous_format)
+        if not torch.is_tensor(st["step"]):
+            st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+        for key in ("exp_avg", "exp_avg_sq"):
+            if st[key].dtype != torch.float32 or not st[key].is_contiguous() or st[key].device != w.device:
+                st[key] = st[key].to(w.device, torch.float32).contiguous()
+        return st
+
+    def _mix_p_buffer(self):
+        w = self.layer_mix.weights
+        if self._mix_p is None or self._mix_p.device != w.device:
+            self._mix_p, self._mix_p_key = torch.empty_like(w, requires_grad=False), None
+        return self._mix_p
+
+    def _mix_p_current(self):
+        """The cached softmax stands for the weights as they are (same storage, same version)."""
+        w = self.layer_mix.weights
+        return self._mix_p is not None and self._mix_p_key == (w.data_ptr(), w._version)
+
+    def _mix_p_written(self):
+        w = self.layer_mix.weights
+        self._mix_p_key = (w.data_ptr(), w._version)
+
+    @torch.no_grad()
+    def mix_p(self):
+        """``softmax(layer_mix.weights)`` as the step kernel leaves it (computed in double, rounded to float once), on the
+        device.  Cached against the version counter of the weights: after a step of this optimizer it is there already;
+        weights changed from outside (``load_state_dict``, ``copy_``) cost one softmax-only launch."""
+        return mix_p_group([self])[0]
 
     def _ensure_state(self, skip):
         """Moments of every parameter that is about to be updated (created as torch.optim.Adam creates them)."""
@@ -246,13 +316,17 @@ class FusedAdam(torch.optim.Optimizer):
             if g.is_sparse or not g.is_cuda:
                 raise _lib.RsafError("FusedAdam: gradients must be dense HIP (cuda) tensors")
             grads.append(g.to(torch.float32).contiguous())
-        if self._all_skipped(skip):
-            return loss
-        self._ensure_state(skip)
-        rows = self._rows() + [[g.data_ptr() if g is not None else 0 for g in grads]]
-        table = _pointer_table(rows, self._order[0].device)
-        _adam_group([(self, None, table, skip)])
-        self._written(self._live(skip))
+        if not self._all_skipped(skip):
+            self._ensure_state(skip)
+            rows = self._rows() + [[g.data_ptr() if g is not None else 0 for g in grads]]
+            table = _pointer_table(rows, self._order[0].device)
+            _adam_group([(self, None, table, skip)])
+            self._written(self._live(skip))
+        if self.layer_mix is not None and self.layer_mix.weights.grad is not None:        # as torch.optim.Adam: whatever has a .grad
+            g = self.layer_mix.weights.grad
+            if g.is_sparse or not g.is_cuda:
+                raise _lib.RsafError("FusedAdam: gradients must be dense HIP (cuda) tensors")
+            mix_adam_group([self], dws=[g.to(torch.float32).contiguous()])
         return loss
 
 
@@ -324,6 +398,66 @@ def _adam_group(entries):
                 _launch_chunked("rsaf_cnnlstm_adam_group", _lib.AdamItem, live, fill, *dims5)
     for opt, _, _, skip in entries:
         opt._stepped(skip)
+
+
+def _check_mix_owners(optimizers, who):
+    for k, opt in enumerate(optimizers):
+        if not isinstance(opt, FusedAdam) or opt.layer_mix is None:
+            raise ValueError(f"{who}: optimizers[{k}] is not a FusedAdam that owns a layer mix (FusedAdam(model, layer_mix=...))")
+
+
+@torch.no_grad()
+def mix_p_group(optimizers):
+    """``[opt.mix_p()]`` of the optimizers: the cached softmax of every mix's weights; those whose weights changed since it
+    was written (another version or storage) are brought up to date together by one softmax-only launch of
+    ``rsaf_layer_mix_adam_group`` per ``train_group_max()`` of them.  In steady state no launch at all."""
+    optimizers = list(optimizers)
+    _check_mix_owners(optimizers, "mix_p_group")
+    stale = [opt for opt in optimizers if not opt._mix_p_current()]
+
+    def fill(it, opt, _k):
+        w = opt.layer_mix.weights
+        it.L, it.mode = w.numel(), _lib.LAYER_MIX_SOFTMAX_ONLY
+        it.w, it.p_next = w.data_ptr(), opt._mix_p_buffer().data_ptr()
+
+    if stale:
+        _launch_chunked("rsaf_layer_mix_adam_group", _lib.LayerMixAdamItem, stale, fill)
+        for opt in stale:
+            opt._mix_p_written()
+    return [opt._mix_p for opt in optimizers]
+
+
+@torch.no_grad()
+def mix_adam_group(optimizers, ps=None, dps=None, dws=None, dw_outs=None):
+    """One Adam step of the mix weights of K optimizers in one ``rsaf_layer_mix_adam_group`` launch (per
+    ``train_group_max()`` of them).  Either ``ps`` and ``dps`` (float32 ``[L]`` device tensors: the kernel applies the softmax
+    Jacobian in double; ``dw_outs[k]``, where given, receives the gradient it formed) or ``dws`` (the gradient of the
+    weights as it is).  The launch leaves the softmax of the new weights in every optimizer's ``mix_p()`` buffer."""
+    optimizers = list(optimizers)
+    _check_mix_owners(optimizers, "mix_adam_group")
+    if (dws is None) == (ps is None or dps is None):
+        raise ValueError("mix_adam_group: give either ps and dps, or dws")
+    states = [opt._mix_state() for opt in optimizers]
+
+    def fill(it, k, _j):
+        opt, st = optimizers[k], states[k]
+        w = opt.layer_mix.weights
+        it.L = w.numel()
+        if dws is None:
+            it.mode, it.p, it.dp = _lib.LAYER_MIX_FROM_DP, ps[k].data_ptr(), dps[k].data_ptr()
+            it.dw_out = dw_outs[k].data_ptr() if dw_outs is not None and dw_outs[k] is not None else None
+        else:
+            it.mode, it.dw = _lib.LAYER_MIX_FROM_DW, dws[k].data_ptr()
+        it.w, it.exp_avg, it.exp_avg_sq = w.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        it.p_next = opt._mix_p_buffer().data_ptr()
+        it.lr, it.beta1, it.beta2, it.eps = opt._mix_hyper()
+        it.step = int(st["step"]) + 1
+
+    _launch_chunked("rsaf_layer_mix_adam_group", _lib.LayerMixAdamItem, list(range(len(optimizers))), fill)
+    torch._foreach_add_([st["step"] for st in states], 1)
+    for opt, st in zip(optimizers, states):
+        opt._written([opt.layer_mix.weights, st["exp_avg"], st["exp_avg_sq"]])
+        opt._mix_p_written()
 
 
 def _pack_group(optimizers):
@@ -434,10 +568,12 @@ def _bn_running_group(reps):
     return written
 
 
-def _train_step_chunk(models, optimizers, xs, labels, masks, weights, mixed=False):
+def _train_step_chunk(models, optimizers, xs, labels, masks, weights, mixed=False, with_dx=None):
     """The fused step of up to ``train_group_max()`` replicas -> (losses [K], [logits_k]).  The statistics and gradient
     blobs of the replicas are slices of one allocation each, of every replica's own size (in a mixed group the channel
-    count and the blob length differ; every size is a multiple of 4 floats, so the slices stay 16-byte aligned)."""
+    count and the blob length differ; every size is a multiple of 4 floats, so the slices stay 16-byte aligned).
+    ``with_dx``: a callable; the backward then returns the gradient of every input too (the ``_dx`` entries), and
+    ``with_dx([dx_k])`` runs between the backward and Adam (the fused mix step: dL/dp from the resident stacks)."""
     device = xs[0].device
     nc = models[0].dims["num_classes"]
     rows = [x.shape[0] for x in xs]
@@ -453,7 +589,11 @@ def _train_step_chunk(models, optimizers, xs, labels, masks, weights, mixed=Fals
     grads = torch.split(torch.zeros(sum(sizes), dtype=torch.float32, device=device), sizes)     # one zero fill for the group
     for k, r in enumerate(reps):
         r.dlogits, r.grads = dl[k], grads[k]
+        if with_dx is not None:
+            r.want_dx()
     _launch_group(reps, True, mixed)
+    if with_dx is not None:
+        with_dx([r.dx for r in reps])
     entries = []
     for k, opt in enumerate(optimizers):
         skip = opt._frozen()

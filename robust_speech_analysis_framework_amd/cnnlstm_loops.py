@@ -13,9 +13,50 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .cnnlstm_fused import _class_weights, _fused_step_applies, _loss_list, ce_loss_group, cnnlstm_train_step_group
+from .cnnlstm_fused import FusedAdam, _class_weights, _fused_step_applies, _loss_list, ce_loss_group, cnnlstm_train_step_group
 from .cnnlstm_train import cnnlstm_train_group, train_group_max
-from .device_data import BatchPlan, batches_to_device, check_loader_devices, epoch_iterator
+from .device_data import BatchPlan, DeviceBatchLoader, batches_to_device, check_loader_devices, epoch_iterator
+from .layer_mix import LayerMix
+from .layer_mix_train import cnnlstm_mix_train_step_group, collate_mix_batches
+
+
+def _check_mixes(loaders, mixes, who):
+    """``mixes`` of a lock-step loop as a list of K ``LayerMix`` or ``None``: a replica with a mix needs a
+    ``DeviceBatchLoader`` over a store of layer stacks of the mix's L, and such a loader needs a mix."""
+    K = len(loaders)
+    mixes = [None] * K if mixes is None else list(mixes)
+    if len(mixes) != K:
+        raise ValueError(f"{who}: {K} loaders but {len(mixes)} mixes")
+    for k, (ld, mix) in enumerate(zip(loaders, mixes)):
+        layers = ld.dataset.store.layers if isinstance(ld, DeviceBatchLoader) else None
+        if mix is None:
+            if layers is not None:
+                raise ValueError(f"{who}: loader {k} is a DeviceBatchLoader over a store of layer stacks (layers={layers}), "
+                                 f"but mixes[{k}] is None: such a loader needs a LayerMix({layers})")
+            continue
+        if not isinstance(mix, LayerMix):
+            raise TypeError(f"{who}: mixes[{k}] is a {type(mix).__name__}, not a LayerMix")
+        if layers is None:
+            raise ValueError(f"{who}: mixes[{k}] is a LayerMix, but loader {k} is not a DeviceBatchLoader over a store of layer "
+                             "stacks (DeviceSequenceStore(..., layers=L))")
+        if mix.num_layers != layers:
+            raise ValueError(f"{who}: mixes[{k}] has num_layers={mix.num_layers}, but the store of loader {k} has layers={layers}")
+    return mixes
+
+
+def _assemble(batches, mixes, device):
+    """``batches_to_device`` for batches of which some are plans over stores of layer stacks (``mixes[k]`` not ``None``):
+    those are mixed inside one collate-mix launch per group (``collate_mix_batches``), the others assembled as before."""
+    mixed_k = [k for k, m in enumerate(mixes) if m is not None]
+    if not mixed_k:
+        return batches_to_device(batches, device)
+    plain_k = [k for k, m in enumerate(mixes) if m is None]
+    out = [None] * len(batches)
+    for k, xb in zip(plain_k, batches_to_device([batches[k] for k in plain_k], device) if plain_k else []):
+        out[k] = xb
+    for k, xb in zip(mixed_k, collate_mix_batches([batches[k] for k in mixed_k], [mixes[k] for k in mixed_k])):
+        out[k] = xb
+    return out
 
 
 class CNNLSTMGroup(nn.Module):
@@ -53,7 +94,7 @@ class CNNLSTMGroup(nn.Module):
         return outs
 
 
-def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device, mixed=False):
+def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device, mixed=False, mixes=None):
     """The reference's inner training loop (``src/dl_cv_strategies.py:244-248``: ``zero_grad / model(seq) / loss /
     backward / step`` per batch, a fixed number of epochs) for K replicas over K loaders in lock step: step i of an
     epoch takes batch i of every loader through one group step.  Loaders may differ in length; a replica whose epoch
@@ -81,15 +122,47 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
     Any loader may be a ``device_data.DeviceBatchLoader`` (sequences resident on the device) in place of a ``DataLoader``,
     in any mix: the batches that such loaders contribute to a group step are assembled on the device by one
     ``rsaf_collate_pad_group`` launch (per ``train_group_max()`` of them), in the ``DataLoader``'s order and with
-    ``collate_fn``'s bits, so the results are the same.  ``DataLoader`` entries are padded on the host and copied as before."""
+    ``collate_fn``'s bits, so the results are the same.  ``DataLoader`` entries are padded on the host and copied as before.
+
+    ``mixes``: a sequence of K ``LayerMix`` or ``None`` entries (``None`` for the argument: no replica has one, and the loop is
+    what it was).  A replica with a mix learns it in front of its model; its loader must be a ``DeviceBatchLoader`` over a
+    store of layer stacks of the mix's L (``DeviceSequenceStore(..., layers=L)``), and such a loader needs a mix: both are
+    refused by name before the first step.  The mixed batches come straight out of the collate launch.  When the fused
+    step applies (above) and every mixed replica's optimizer owns its mix (``FusedAdam(model, layer_mix=mix)``), the mixed
+    replicas of a step take one ``cnnlstm_mix_train_step_group`` call and the others one ``cnnlstm_train_step_group``
+    call; otherwise the mixed replicas run the autograd loop over ``collate_mix_batches``, where ``optimizers[k].step()``
+    must be the one that updates the mix (a ``FusedAdam(layer_mix=...)`` or any optimizer over both parameter sets); a
+    ``FusedAdam`` that does not own its replica's mix would leave it where it started and is refused by name."""
     models, optimizers, loaders = list(models), list(optimizers), list(loaders)
     if not (len(models) == len(optimizers) == len(loaders)):
         raise ValueError(f"{len(models)} models, {len(optimizers)} optimizers and {len(loaders)} loaders")
     check_loader_devices(loaders, device, "train_replicas_lockstep")
+    mixes = _check_mixes(loaders, mixes, "train_replicas_lockstep")
+    for k, (opt, mix) in enumerate(zip(optimizers, mixes)):
+        if mix is not None and isinstance(opt, FusedAdam) and opt.layer_mix is not mix:      # its step() would never move the mix
+            raise ValueError(f"train_replicas_lockstep: optimizers[{k}] is a FusedAdam that does not own mixes[{k}], so the mix would "
+                             f"never be updated: build it as FusedAdam(models[{k}], layer_mix=mixes[{k}])")
     histories = [[] for _ in models]
     loss_fns = _loss_list(loss_fn, len(models))
     fused = _fused_step_applies(optimizers, models, loss_fns)     # decided once for the call: no replica changes path mid-epoch
     weights = _class_weights(loss_fns) if fused else None
+    # the mixed replicas take the fused mix step when the fused step applies and every one's optimizer owns its mix
+    fused_mix = fused and all(opt.layer_mix is mix for opt, mix in zip(optimizers, mixes) if mix is not None)
+
+    def autograd_step(ks, xs, labs):
+        for k in ks:
+            optimizers[k].zero_grad()
+        outs = cnnlstm_train_group([models[k] for k in ks], xs, mixed=mixed)
+        losses = [loss_fns[k](o, lab) for k, o, lab in zip(ks, outs, labs)]
+        torch.stack(losses).sum().backward()
+        for k in ks:
+            optimizers[k].step()
+        return torch.stack([ls.detach() for ls in losses])
+
+    def fused_step(ks, xs, labs):
+        return cnnlstm_train_step_group([models[k] for k in ks], [optimizers[k] for k in ks], xs, labs, mixed=mixed,
+                                        class_weights=weights and [weights[k] for k in ks])[0]
+
     for _ in range(epochs):
         for m in models:
             m.train()
@@ -100,20 +173,34 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
             live = [k for k, b in enumerate(batches) if b is not None]
             if not live:
                 break
-            xs, labs = zip(*batches_to_device([batches[k] for k in live], device))
-            xs, labs = list(xs), list(labs)
-            if fused:
-                step_losses = cnnlstm_train_step_group([models[k] for k in live], [optimizers[k] for k in live], xs, labs, mixed=mixed,
-                                                       class_weights=weights and [weights[k] for k in live])[0]
-            else:
-                for k in live:
-                    optimizers[k].zero_grad()
-                outs = cnnlstm_train_group([models[k] for k in live], xs, mixed=mixed)
-                losses = [loss_fns[k](o, lab) for k, o, lab in zip(live, outs, labs)]
-                torch.stack(losses).sum().backward()
-                for k in live:
-                    optimizers[k].step()
-                step_losses = torch.stack([ls.detach() for ls in losses])
+            with_mix = [k for k in live if mixes[k] is not None]
+            if not with_mix:
+                xs, labs = zip(*batches_to_device([batches[k] for k in live], device))
+                step_losses = (fused_step if fused else autograd_step)(live, list(xs), list(labs))
+            elif fused_mix:                     # each kind takes its own step function
+                plain = [k for k in live if mixes[k] is None]
+                parts = []
+                if plain:
+                    xs, labs = zip(*batches_to_device([batches[k] for k in plain], device))
+                    parts.append(fused_step(plain, list(xs), list(labs)))
+                parts.append(cnnlstm_mix_train_step_group(
+                    [models[k] for k in with_mix], [mixes[k] for k in with_mix], [optimizers[k] for k in with_mix],
+                    [batches[k] for k in with_mix], mixed=mixed, class_weights=weights and [weights[k] for k in with_mix])[0])
+                live = plain + with_mix
+                step_losses = torch.cat(parts)
+            else:                               # the autograd loop over collate_mix_batches
+                plain = [k for k in live if mixes[k] is None]
+                parts = []
+                if plain and fused:
+                    xs, labs = zip(*batches_to_device([batches[k] for k in plain], device))
+                    parts.append(fused_step(plain, list(xs), list(labs)))
+                    rest = with_mix
+                else:
+                    rest = list(live)
+                xs, labs = zip(*_assemble([batches[k] for k in rest], [mixes[k] for k in rest], device))
+                parts.append(autograd_step(rest, list(xs), list(labs)))
+                live = (plain if plain and fused else []) + rest
+                step_losses = torch.cat(parts)
             for k, v in zip(live, step_losses.tolist()):
                 total[k] += v
                 count[k] += 1
@@ -123,54 +210,59 @@ def train_replicas_lockstep(models, optimizers, loaders, loss_fn, epochs, device
 
 
 def _eval_pairs(tagged):
-    """``tagged``: iterable of ``(tag, model, loader)`` -> the ``(tag, model, seq, lab)`` of ``_grouped_eval_batches``, loader by
-    loader; a ``DeviceBatchLoader`` gives its batches as plans."""
-    for tag, model, ld in tagged:
+    """``tagged``: iterable of ``(tag, model, loader, mix)`` -> the ``(tag, model, seq, lab, mix)`` of ``_grouped_eval_batches``,
+    loader by loader; a ``DeviceBatchLoader`` gives its batches as plans."""
+    for tag, model, ld, mix in tagged:
         for b in epoch_iterator(ld):
-            yield (tag, model, b, None) if isinstance(b, BatchPlan) else (tag, model, b[0], b[1])
+            yield (tag, model, b, None, mix) if isinstance(b, BatchPlan) else (tag, model, b[0], b[1], mix)
 
 
 def _grouped_eval_batches(pairs, device, mixed=False):
-    """``pairs``: iterable of ``(tag, model, seq, lab)`` in any mix of models (``mixed``: of architectures too) -> yields ``(tag, logits, lab on the device)``
+    """``pairs``: iterable of ``(tag, model, seq, lab, mix)`` in any mix of models (``mixed``: of architectures too) -> yields ``(tag, logits, lab on the device)``
     in the same order, the forwards pooled into group calls of up to ``train_group_max()`` batches.  The batches stay as
     collated: zero padding is not masked (``src/dl_cv_strategies.py:81-84``), so regrouping sequences would change the
     results.  ``seq`` may be a ``BatchPlan`` of a device loader (``lab`` is then ignored): the plans of a group call are
-    assembled by one ``rsaf_collate_pad_group`` launch."""
+    assembled by one ``rsaf_collate_pad_group`` launch; those over stores of layer stacks (``mix`` not ``None``) are mixed by
+    one ``rsaf_collate_mix_group`` launch per group call, the forward launch alone."""
     from .cnnlstm import cnnlstm_forward_group
     gmax = train_group_max()
     pend = []
 
     def flush():
-        data = batches_to_device([p[2] for p in pend], device)
+        data = _assemble([p[2] for p in pend], [p[3] for p in pend], device)
         outs = cnnlstm_forward_group([p[1] for p in pend], [x for x, _ in data], mixed=mixed)
         res = [(p[0], o, lab) for p, o, (_, lab) in zip(pend, outs, data)]
         pend.clear()
         return res
 
-    for tag, model, seq, lab in pairs:
-        pend.append((tag, model, seq if isinstance(seq, BatchPlan) else (seq, lab)))
+    for tag, model, seq, lab, mix in pairs:
+        pend.append((tag, model, seq if isinstance(seq, BatchPlan) else (seq, lab), mix))
         if len(pend) == gmax:
             yield from flush()
     if pend:
         yield from flush()
 
 
-def eval_replicas_lockstep(models, loaders, device, mixed=False):
+def eval_replicas_lockstep(models, loaders, device, mixed=False, mixes=None):
     """``_eval_model`` (``src/dl_cv_strategies.py:183-194``) for K models over K loaders: all (model, batch) pairs are
     pooled into group calls.  Returns K triples ``(labels, preds, probs)`` of NumPy arrays in loader order, equal to
     what the reference's loop returns model by model; the results of a replica come to the host in one copy each.
     ``mixed=True``: the models may differ in architecture (``cnnlstm_forward_group``).  Loaders may be
-    ``DeviceBatchLoader``s in any mix with ``DataLoader``s; their batches are assembled on the device, one launch per group call."""
+    ``DeviceBatchLoader``s in any mix with ``DataLoader``s; their batches are assembled on the device, one launch per group call.
+    ``mixes``: as in ``train_replicas_lockstep``; the batches of a replica with a mix are mixed inside the collate launch with
+    ``p = softmax(weights)`` as ``LayerMix.forward`` forms it (the forward launch alone, one per group call), so the logits are
+    those of the model on ``mix(h)`` of the zero-padded stack."""
     from .cnnlstm import eval_outputs
     models, loaders = list(models), list(loaders)
     if len(models) != len(loaders):
         raise ValueError(f"{len(models)} models but {len(loaders)} loaders")
     check_loader_devices(loaders, device, "eval_replicas_lockstep")
+    mixes = _check_mixes(loaders, mixes, "eval_replicas_lockstep")
     for m in models:
         m.eval()
     parts = [([], [], []) for _ in models]
     with torch.no_grad():
-        pairs = _eval_pairs((k, m, ld) for k, (m, ld) in enumerate(zip(models, loaders)))
+        pairs = _eval_pairs((k, m, ld, mix) for k, (m, ld, mix) in enumerate(zip(models, loaders, mixes)))
         for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
             prob, pred = eval_outputs(out)
             for lst, v in zip(parts[k], (lab, pred, prob)):
@@ -191,7 +283,7 @@ def eval_model_grouped(model, data_loader, device):
 
 
 def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, val_loaders, loss_fn, epochs, patience, device,
-                                 mixed=False):
+                                 mixed=False, mixes=None):
     """``_train_eval_loop`` (``src/dl_cv_strategies.py:112-165``) for K replicas: per epoch the training pass of
     ``train_replicas_lockstep`` over the replicas still running, then the validation pass of all of them in group calls
     (``val_loss`` accumulated batch by batch in loader order; the losses of a pass come to the host in one copy), then per
@@ -200,7 +292,9 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
     validation losses of a replica are those of its own loss (its class weights).  A replica that stopped early sits out of the later epochs.  Returns
     ``[(model, train_loss_history, val_loss_history)]``, every model with its best weights loaded.  ``mixed=True``: the
     replicas may differ in architecture, in the training pass and in the validation pass alike.  Training and validation
-    loaders may be ``DeviceBatchLoader``s in any mix with ``DataLoader``s, as in the two loops above."""
+    loaders may be ``DeviceBatchLoader``s in any mix with ``DataLoader``s, as in the two loops above.  ``mixes``: as in
+    ``train_replicas_lockstep``, for the training and the validation loaders alike; the ``state_dict`` of a replica's mix is
+    checkpointed and restored together with the model's, so best weights mean the best mix too."""
     models, optimizers, schedulers = list(models), list(optimizers), list(schedulers)
     train_loaders, val_loaders = list(train_loaders), list(val_loaders)
     K = len(models)
@@ -209,17 +303,21 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
                          f"loaders and {len(val_loaders)} validation loaders")
     check_loader_devices(train_loaders, device, "train_eval_replicas_lockstep (train_loaders)")
     check_loader_devices(val_loaders, device, "train_eval_replicas_lockstep (val_loaders)")
+    mixes = _check_mixes(train_loaders, mixes, "train_eval_replicas_lockstep (train_loaders)")
+    _check_mixes(val_loaders, mixes, "train_eval_replicas_lockstep (val_loaders)")
     train_hist, val_hist = [[] for _ in models], [[] for _ in models]
     loss_fns = _loss_list(loss_fn, K)
     best_val_loss = [float("inf")] * K
     epochs_no_improve = [0] * K
     best_model_weights = [None] * K
+    best_mix_weights = [None] * K
     running = list(range(K))
     for _ in range(epochs):
         if not running:
             break
         hist = train_replicas_lockstep([models[k] for k in running], [optimizers[k] for k in running],
-                                       [train_loaders[k] for k in running], [loss_fns[k] for k in running], 1, device, mixed=mixed)
+                                       [train_loaders[k] for k in running], [loss_fns[k] for k in running], 1, device, mixed=mixed,
+                                       mixes=[mixes[k] for k in running])
         for k, h in zip(running, hist):
             train_hist[k].append(h[0])
         for k in running:
@@ -228,7 +326,7 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
         fused = _fused_step_applies([optimizers[k] for k in running], [models[k] for k in running], [loss_fns[k] for k in running])
         weights = _class_weights(loss_fns) if fused else None
         with torch.no_grad():
-            pairs = _eval_pairs((k, models[k], val_loaders[k]) for k in running)
+            pairs = _eval_pairs((k, models[k], val_loaders[k], mixes[k]) for k in running)
             for k, out, lab in _grouped_eval_batches(pairs, device, mixed):
                 tags.append(k)
                 outs.append(out)
@@ -252,6 +350,8 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
             if avg_val_loss < best_val_loss[k]:
                 best_val_loss[k] = avg_val_loss
                 best_model_weights[k] = copy.deepcopy(models[k].state_dict())
+                if mixes[k] is not None:
+                    best_mix_weights[k] = copy.deepcopy(mixes[k].state_dict())
                 epochs_no_improve[k] = 0
             else:
                 epochs_no_improve[k] += 1
@@ -261,4 +361,6 @@ def train_eval_replicas_lockstep(models, optimizers, schedulers, train_loaders, 
     for k in range(K):
         if best_model_weights[k]:
             models[k].load_state_dict(best_model_weights[k])
+        if best_mix_weights[k]:
+            mixes[k].load_state_dict(best_mix_weights[k])
     return [(models[k], train_hist[k], val_hist[k]) for k in range(K)]

@@ -323,9 +323,7 @@ __global__ __launch_bounds__(256) void collate_augment_group_kernel(const Augmen
 
 // ---- what both collate entries check and size, item by item, before their launch ----------------------------------------
 struct CollatePlan {
-    struct Range { const char* p; int64_t bytes; int item; const char* what; };
-    Range wrote[RSAF_CNNLSTM_GROUP_MAX * 2];
-    int n_wrote = 0;
+    rsaf::cnnlstm::WrittenRanges wrote;
     int64_t blocks = 0;
     double floats = 0.0;          // read + written, for the profiling family
 
@@ -340,16 +338,8 @@ struct CollatePlan {
         const int n_label = (it.label_src != nullptr) + (it.label_index != nullptr) + (it.label_out != nullptr);
         if (!(n_label == 0 || n_label == 3) || (n_label == 0 && it.label_count != 0) || it.label_count < 0)
             return fail(RSAF_ERR_ARG, who, k, "label_src, label_count, label_index and label_out go together: all or none");
-        const Range mine[2] = {{reinterpret_cast<const char*>(it.out), out_floats * 4, k, "out"},
-                               {reinterpret_cast<const char*>(it.label_out), (int64_t)it.B * 8, k, "label_out"}};
-        for (const Range& m : mine) {
-            if (!m.p) continue;
-            for (int i = 0; i < n_wrote; ++i)
-                if (m.p < wrote[i].p + wrote[i].bytes && wrote[i].p < m.p + m.bytes)
-                    return fail(RSAF_ERR_ARG, who, k, std::string("`") + m.what + "` overlaps `" + wrote[i].what + "` of item " +
-                                                          std::to_string(wrote[i].item));
-            wrote[n_wrote++] = m;
-        }
+        TRY(wrote.add(it.out, out_floats * 4, k, "out", who));
+        TRY(wrote.add(it.label_out, (int64_t)it.B * 8, k, "label_out", who));
         const int vec4 = width % 4 == 0 && ((reinterpret_cast<uintptr_t>(it.arena) | reinterpret_cast<uintptr_t>(it.out)) & 15) == 0;
         const int64_t member = (int64_t)it.T * (vec4 ? width / 4 : width);
         const int64_t per_member = (member + COLLATE_CHUNK - 1) / COLLATE_CHUNK;

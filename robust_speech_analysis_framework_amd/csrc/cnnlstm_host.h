@@ -31,6 +31,22 @@ inline int check_group_args(int K, const void* items_host, const char* who, cons
     return RSAF_OK;
 }
 
+// the byte ranges that the items of one group call write, two per item at most: no two may overlap (NULL: nothing written)
+struct WrittenRanges {
+    struct Range { const char* p; int64_t bytes; int item; const char* what; };
+    Range r[RSAF_CNNLSTM_GROUP_MAX * 2];
+    int n = 0;
+    int add(const void* q, int64_t bytes, int k, const char* what, const char* who) {
+        const char* p = reinterpret_cast<const char*>(q);
+        if (!p) return RSAF_OK;
+        for (int i = 0; i < n; ++i)
+            if (p < r[i].p + r[i].bytes && r[i].p < p + bytes)
+                return fail(RSAF_ERR_ARG, who, k, std::string("`") + what + "` overlaps `" + r[i].what + "` of item " + std::to_string(r[i].item));
+        r[n++] = Range{p, bytes, k, what};
+        return RSAF_OK;
+    }
+};
+
 // [a, a + na) and [b, b + nb) share a float
 inline bool overlap(const float* a, int64_t na, const float* b, int64_t nb) { return a < b + nb && b < a + na; }
 

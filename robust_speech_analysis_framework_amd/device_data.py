@@ -13,6 +13,10 @@ per trial, although all of them draw from one ``sequences_dict``.  Here
 * ``collate_batches`` assembles any number of planned batches (``DeviceBatchLoader.plans()``) in one launch per
   ``train_group_max()`` of them, which is how the lock-step loops of ``cnnlstm_loops`` consume such loaders.
 
+A store may hold layer stacks instead (``DeviceSequenceStore(..., layers=L)``: every sequence ``[L, T_i, D]``, the hidden
+states of L encoder layers) for a learned ``LayerMix``: its plans carry the blocks' first rows, ``layer_mix_train`` mixes the
+layers inside the collate launch, and the loader iterated on its own yields the zero-padded stack ``[B, L, T, D]``.
+
 There is no CPU fallback: the store refuses a device that is not a HIP device.  ``cnnlstm`` re-exports the names of this
 module.
 """
@@ -25,6 +29,7 @@ import torch
 
 from . import _lib
 from .augment import AugmentStream, as_compose
+from .layer_mix import LAYER_MIX_MAX
 
 _STAGE_BYTES = 64 << 20             # pinned staging of an upload: two buffers of this size, however large the data set
 
@@ -74,31 +79,51 @@ class DeviceSequenceStore:
     ``src/dl_cv_strategies.py:300``; values are cast to float32 as ``torch.FloatTensor(seq.copy())`` casts them
     (``SequenceDataset.__getitem__``).  The upload goes through two pinned staging buffers of bounded size, so no second
     full copy of the data is made on the host.  ``frame_off`` (host, int64 ``[n + 1]``) and ``frame_off_device`` give the
-    arena rows of sequence i as ``frame_off[i] .. frame_off[i + 1]``."""
+    arena rows of sequence i as ``frame_off[i] .. frame_off[i + 1]``.
 
-    def __init__(self, sequences, device="cuda"):
+    ``layers=L`` (1 <= L <= 32, ``RSAF_LAYER_MIX_MAX``): a store of layer stacks for a learned ``LayerMix``.  Every sequence
+    is ``[L, T_i, D]`` with D a multiple of 4, what ``extract_wav2vec2_sequences(output_layers=[...])`` returns per file, and
+    its block is uploaded as it lies in memory: ``L * T_i`` arena rows, layer-major, the arena row of (i, l, t) being
+    ``L * frame_off[i] + l * T_i + t``.  ``frame_off`` and ``lengths`` stay in frames; ``layers`` is L (``None`` for a plain
+    store) and ``sequence(i)`` the ``[L, T_i, D]`` view.  ``collate_mix_batches`` mixes the layers inside the collate launch;
+    a ``DeviceBatchLoader`` iterated on its own yields the zero-padded stack ``[B, L, T, D]``."""
+
+    layers = None                       # a plain store, unless ``_adopt`` says otherwise
+
+    def __init__(self, sequences, device="cuda", layers=None):
         device = _hip_device(device, "DeviceSequenceStore")
         seqs = [s if torch.is_tensor(s) else np.asarray(s) for s in sequences]
         if not seqs:
             raise ValueError("DeviceSequenceStore: no sequences")
+        if layers is not None:
+            if isinstance(layers, bool) or not isinstance(layers, (int, np.integer)) or not 1 <= layers <= LAYER_MIX_MAX:
+                raise ValueError(f"DeviceSequenceStore: layers must be an integer in [1, {LAYER_MIX_MAX}] (or None: a plain store), "
+                                 f"got {layers!r}")
+            layers = int(layers)
         for i, s in enumerate(seqs):
-            if s.ndim != 2:
+            if layers is None and s.ndim != 2:
                 raise ValueError(f"DeviceSequenceStore: sequence {i} has shape {tuple(s.shape)}, expected [T, D]")
-        width = int(seqs[0].shape[1])
+            if layers is not None and (s.ndim != 3 or int(s.shape[0]) != layers):
+                raise ValueError(f"DeviceSequenceStore: sequence {i} has shape {tuple(s.shape)}, expected [{layers}, T, D] (layers={layers})")
+        width = int(seqs[0].shape[-1])
         for i, s in enumerate(seqs):
-            if int(s.shape[1]) != width:
-                raise ValueError(f"DeviceSequenceStore: sequence {i} has width {int(s.shape[1])}, sequence 0 has {width}: "
+            if int(s.shape[-1]) != width:
+                raise ValueError(f"DeviceSequenceStore: sequence {i} has width {int(s.shape[-1])}, sequence 0 has {width}: "
                                  "one store holds sequences of one width")
         if width < 1:
             raise ValueError("DeviceSequenceStore: sequences of width 0")
+        if layers is not None and width % 4:
+            raise ValueError(f"DeviceSequenceStore: a store of layer stacks needs a width that is a multiple of 4, got {width}")
         _lib.load()
         _lib.require_gpu()
-        lengths = np.array([int(s.shape[0]) for s in seqs], dtype=np.int64)
-        self._adopt(torch.empty((int(lengths.sum()), width), dtype=torch.float32, device=_resolved(device)), lengths)
-        self._upload(seqs)
+        lengths = np.array([int(s.shape[-2]) for s in seqs], dtype=np.int64)
+        rows = int(lengths.sum()) * (layers or 1)
+        self._adopt(torch.empty((rows, width), dtype=torch.float32, device=_resolved(device)), lengths, layers)
+        self._upload([s.reshape(-1, width) for s in seqs] if layers is not None else seqs)
 
-    def _adopt(self, arena, lengths):
+    def _adopt(self, arena, lengths, layers=None):
         self.arena = arena
+        self.layers = layers
         self.device = arena.device
         self.width = int(arena.shape[1])
         self.lengths = np.asarray(lengths, dtype=np.int64)
@@ -165,11 +190,14 @@ class DeviceSequenceStore:
         return int(self.arena.numel()) * 4
 
     def sequence(self, i):
-        """Sequence i as a device view ``[T_i, D]`` of the arena."""
+        """Sequence i as a device view ``[T_i, D]`` of the arena (``[L, T_i, D]`` in a store of layer stacks)."""
         i = int(i)
         if not -len(self) <= i < len(self):
             raise IndexError(f"sequence {i} of {len(self)}")
         i %= len(self)
+        if self.layers is not None:
+            L = self.layers
+            return self.arena[L * int(self.frame_off[i]):L * int(self.frame_off[i + 1])].view(L, -1, self.width)
         return self.arena[int(self.frame_off[i]):int(self.frame_off[i + 1])]
 
 
@@ -212,6 +240,9 @@ class DeviceSequenceDataset:
         if (transform is None) != (augment_stream is None):
             raise ValueError("DeviceSequenceDataset: transform and augment_stream go together: "
                              f"{'augment_stream' if transform is not None else 'transform'} is missing")
+        if transform is not None and store.layers is not None:
+            raise ValueError("DeviceSequenceDataset: transform is not supported over a store of layer stacks "
+                             f"(layers={store.layers}): augmentations apply to plain [T, D] sequences")
         if transform is not None:
             transform = as_compose(transform, "DeviceSequenceDataset")
             if not isinstance(augment_stream, AugmentStream):
@@ -235,12 +266,14 @@ class BatchPlan:
     """One batch of an epoch, not yet assembled: where its members' rows, counts and label indices stand in the
     epoch's device arrays, and the host-side sizes (``B``, ``T`` = its longest member, ``frames`` = what it copies).
     ``epoch``: the epoch of the data set's ``AugmentStream`` that this batch is drawn at (``None``: no transform);
-    ``label_index`` holds the members' store indices, which are also their sample ids."""
-    __slots__ = ("dataset", "row_start", "row_count", "label_index", "first", "B", "T", "frames", "epoch")
+    ``label_index`` holds the members' store indices, which are also their sample ids.  Over a store of layer stacks
+    ``row_start`` holds the first arena row of every member's block (``layers * frame_off``) and ``layers`` is the store's L;
+    ``row_count`` and ``frames`` stay in frames."""
+    __slots__ = ("dataset", "row_start", "row_count", "label_index", "first", "B", "T", "frames", "epoch", "layers")
 
-    def __init__(self, dataset, row_start, row_count, label_index, first, B, T, frames, epoch=None):
+    def __init__(self, dataset, row_start, row_count, label_index, first, B, T, frames, epoch=None, layers=None):
         self.dataset, self.row_start, self.row_count, self.label_index = dataset, row_start, row_count, label_index
-        self.first, self.B, self.T, self.frames, self.epoch = first, B, T, frames, epoch
+        self.first, self.B, self.T, self.frames, self.epoch, self.layers = first, B, T, frames, epoch, layers
 
 
 class _EpochPlans:
@@ -268,11 +301,13 @@ class _EpochPlans:
                 order_device = staged.to(store.device, non_blocking=True)
                 row_start = store.frame_off_device[order_device]
                 row_count = (store.frame_off_device[order_device + 1] - row_start).to(torch.int32)
+                if store.layers is not None:
+                    row_start = row_start * store.layers                        # first arena row of the member's block
             lengths = store.lengths[order]
             first = 0
             for b in batches:
                 ln = lengths[first:first + len(b)]
-                plans.append(BatchPlan(ds, row_start, row_count, order_device, first, len(b), int(ln.max()), int(ln.sum()), epoch))
+                plans.append(BatchPlan(ds, row_start, row_count, order_device, first, len(b), int(ln.max()), int(ln.sum()), epoch, store.layers))
                 first += len(b)
         self.plans = iter(plans)
 
@@ -313,17 +348,42 @@ class DeviceBatchLoader:
             yield collate_batches([plan])[0]
 
 
+def _layer_members(plan):
+    """The B * L (member, layer) pairs of a plan over a store of layer stacks as a plain plan of B * L members: pair
+    (b, l) is the ``row_count[b]`` frames from arena row ``row_start[b] + l * row_count[b]`` on; no labels."""
+    L, sl = plan.layers, slice(plan.first, plan.first + plan.B)
+    count = plan.row_count[sl].to(torch.int64)
+    layer = torch.arange(L, dtype=torch.int64, device=count.device)
+    start = (plan.row_start[sl, None] + layer[None, :] * count[:, None]).reshape(-1).contiguous()
+    count = count[:, None].expand(-1, L).reshape(-1).to(torch.int32).contiguous()
+    return BatchPlan(plan.dataset, start, count, None, 0, plan.B * L, plan.T, plan.frames * L)
+
+
 def collate_batches(plans):
     """``[(x, labels)]`` of the planned batches, assembled by one ``rsaf_collate_pad_group`` launch per
     ``train_group_max()`` plans of one store width (lists longer than that are split like every other group call).  Where
     any plan of a width comes from a data set with a ``transform``, all plans of that width go through
     ``rsaf_collate_augment_group`` instead, the plain ones with ``n_ops = 0``: still one launch, so the training and the
-    validation batches of a step may share a call."""
+    validation batches of a step may share a call.
+
+    A plan over a store of layer stacks gives ``(h [B, L, T, D], labels)``, the zero-padded stack, through the same launch:
+    its B * L (member, layer) pairs are the members, their rows derived on the device.  That is the input of
+    ``LayerMix.forward``; ``collate_mix_batches`` returns the mixed batch without building it."""
     from .cnnlstm_train import _launch_chunked
     plans = list(plans)
     for k, p in enumerate(plans):
         if not isinstance(p, BatchPlan):
             raise TypeError(f"collate_batches: entry {k} is a {type(p).__name__}, not a BatchPlan")
+    stacked = [k for k, p in enumerate(plans) if p.layers is not None]
+    if stacked:
+        flat = list(plans)
+        for k in stacked:
+            flat[k] = _layer_members(plans[k])
+        outs = collate_batches(flat)
+        for k in stacked:
+            p = plans[k]
+            outs[k] = (outs[k][0].view(p.B, p.layers, p.T, p.dataset.store.width), p.dataset.labels[p.label_index[p.first:p.first + p.B]])
+        return outs
     outs = [None] * len(plans)
     groups = {}
     for k, p in enumerate(plans):
@@ -335,7 +395,7 @@ def collate_batches(plans):
                 p = plans[k]
                 outs[k] = (torch.empty((p.B, p.T, width), dtype=torch.float32, device=device),
                            torch.empty((p.B,), dtype=torch.int64, device=device))
-                if p.T == 0:                # members of no frames only: pad_sequence's [B, 0, D]; nothing to launch
+                if p.T == 0 and p.label_index is not None:      # members of no frames only: pad_sequence's [B, 0, D]; nothing to launch
                     outs[k][1].copy_(p.dataset.labels[p.label_index[p.first:p.first + p.B]])
             members = [k for k in members if plans[k].T > 0]
 
@@ -345,9 +405,12 @@ def collate_batches(plans):
                 it.row_start = p.row_start.data_ptr() + 8 * p.first
                 it.row_count = p.row_count.data_ptr() + 4 * p.first
                 it.B, it.T, it.out = p.B, p.T, outs[k][0].data_ptr()
+                it.frames = p.frames
+                if p.label_index is None:                       # the (member, layer) pairs of a stack: labels by the caller
+                    return
                 it.label_src, it.label_count = p.dataset.labels.data_ptr(), int(p.dataset.labels.numel())
                 it.label_index = p.label_index.data_ptr() + 8 * p.first
-                it.label_out, it.frames = outs[k][1].data_ptr(), p.frames
+                it.label_out = outs[k][1].data_ptr()
 
             if all(plans[k].epoch is None for k in members):
                 _launch_chunked("rsaf_collate_pad_group", _lib.CollateItem, members, fill, width)
