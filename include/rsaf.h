@@ -108,7 +108,8 @@ int rsaf_smile_functionals(const double* lld, const int64_t* frame_off, int n_cl
  * a_pad_k > 0: k=3/pad=1 convolution over a channels-last sequence read in place (A points one
  * row before the sequence, lda = Cin, K = 3*Cin, a_pad_k = Cin).  act: 0 none, 1 GELU(erf), 2 SiLU.
  * Requirements: A, B 16-byte aligned; lda, ldb, A/B strides multiples of 4; K % 4 == 0 (b_kn = 0)
- * or N % 4 == 0 (b_kn = 1); nz <= 65535. */
+ * or N % 4 == 0 (b_kn = 1); nz <= 65535.  Only the logical operand elements reach a result: the padding
+ * between K and lda (ldb) and past N in a row of B, R or C may hold anything, NaN included, and is not written. */
 int rsaf_gemm_f32(const float* A, const float* B, float* C, const float* bias, const float* R,
                   int M, int N, int K, int64_t lda, int64_t ldb, int64_t ldc, int64_t ldr,
                   int nz, int nz2, const int64_t* strides8_host, int a_pad_k, int act, float alpha,

@@ -155,9 +155,17 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_kernel(const GemmParams p) {
         const int kok = gk < p.K;                                                               \
         _Pragma("unroll") for (int i = 0; i < A_IT; ++i) {                                      \
             const int hit = (alo[i] & (gk < p.a_pad_k)) | (ahi[i] & (gk >= p.K - p.a_pad_k));   \
-            const int ok = kok & arow_ok[i] & (hit ^ 1);                                        \
+            const int rok = arow_ok[i] & (hit ^ 1);                                             \
             float4 v = ra[i];                                                                   \
-            v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f; \
+            if constexpr (BKN) {                                                                \
+                /* B[K,N] allows K % 4 != 0: the float4 that straddles K keeps only k < K (what lies between K \
+                   and lda may be NaN, and the zeroed rows of B would not remove it) */         \
+                v.x = (rok & (gk < p.K)) ? v.x : 0.f; v.y = (rok & (gk + 1 < p.K)) ? v.y : 0.f; \
+                v.z = (rok & (gk + 2 < p.K)) ? v.z : 0.f; v.w = (rok & (gk + 3 < p.K)) ? v.w : 0.f; \
+            } else {                                                                            \
+                const int ok = kok & rok;                                                       \
+                v.x = ok ? v.x : 0.f; v.y = ok ? v.y : 0.f; v.z = ok ? v.z : 0.f; v.w = ok ? v.w : 0.f; \
+            }                                                                                   \
             *reinterpret_cast<float4*>(&As[(r0 + 32 * i) * LDS_K + c4 * 4]) = v;                \
         }                                                                                       \
         _Pragma("unroll") for (int i = 0; i < B_IT; ++i) {                                      \

@@ -85,7 +85,7 @@ def test_two_level_batch_attention_shapes(rsaf_lib):
     assert (got[..., T:] == 0).all()                     # pad columns untouched
     # O = P V, B operand [K,N] (N contiguous), K = 249 is not a multiple of 4
     P = torch.softmax(S[..., :T], dim=-1)
-    Pp = torch.zeros_like(S)
+    Pp = torch.full_like(S, float("nan"))                # pad columns K .. lda-1 are workspace: they may hold anything
     Pp[..., :T] = P
     O = torch.zeros((nc, T, D), dtype=torch.float32, device="cuda")
     ops.gemm_f32(Pp, dq, O, T, hd, T, Tp, 3 * D, D, nz=nc * nh, nz2=nh,
