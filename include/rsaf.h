@@ -128,8 +128,10 @@ int rsaf_gemm_f32(const float* A, const float* B, float* C, const float* bias, c
  *   rsaf_gemm_f16x3: C (fp32, row stride ldc) and / or C_planes (the next GEMM's A, scaled by c_scale[m * c_scale_stride],
  *     which must keep |x| * c_scale below 65504), either may be NULL; a_scale[m * a_scale_stride], b_scale[n]: the scales
  *     the planes were built with; amax_out (may be NULL): atomicMax of the bit pattern of max |x| over everything
- *     written (zero it first).  Supported: {act 0, C} {act 0, C, R} {act 0, C_planes} {act 0, C, C_planes} {act 1 or 2, C}
- *     {act 1, C_planes}.  K % 16 == 0, N % 16 == 0.                                                                */
+ *     written (zero it first).  Supported, ten combinations: {act 0, C} {act 0, C, R} {act 0, C_planes}
+ *     {act 0, C, C_planes} {act 1, C} {act 2, C} {act 1, C, R} {act 2, C, R} {act 1, C_planes} {act 2, C_planes}; anything
+ *     else (a residual without C, an activation with both outputs, no output) is an argument error.
+ *     K % 16 == 0, N % 16 == 0.                                                                                    */
 int rsaf_f16x2_row_scales(const float* src, int64_t rows, int K, int64_t ld, float* scale, float* norm2,
                           rsaf_stream_t stream);
 int rsaf_split_f16x2(const float* src, int64_t rows, int K, int64_t ld, const float* scale, int scale_stride,
