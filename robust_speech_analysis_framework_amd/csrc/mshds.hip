@@ -2,8 +2,8 @@
 //
 // Replaces these parselmouth/Praat calls of src/mshds_extractor.py: _speechrate (:11-125), _extract_intensity (:185-205),
 // the mean of _extract_harmonicity (:207-225) and _extract_Spectral_Moments (:340-376).  The pitch analysis they read
-// lives in mshds_pitch.hip, formants, pulses and Ltas in mshds_voice.hip, the cepstral part in mshds_cpp.hip, what the
-// files share in mshds_common.h.
+// lives in mshds_pitch.hip, formants, pulses and Ltas in mshds_formant.hip, mshds_pulses.hip and mshds_ltas.hip, the
+// cepstral part in mshds_cpp.hip, what the files share in mshds_common.h.
 // Algorithms: Praat's intensity (Kaiser-weighted mean square), Gaussian-window spectrogram + spectral moments gated by
 // pitch definedness, the harmonics-to-noise mean over a cc pitch track, de Jong & Wempe syllable nuclei.  Semantics =
 // oracle/mshds_oracle.py (parity unpinned: Praat itself is not available).  Praat computes in double, so do these

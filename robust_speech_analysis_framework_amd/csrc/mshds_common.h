@@ -1,6 +1,6 @@
-// What more than one MSHDS translation unit uses (mshds.hip, mshds_pitch.hip, mshds_voice.hip, mshds_cpp.hip): the
-// clip table rows, Praat's sample-index rounding, the wave / lane-group helpers of the sinc interpolation, and Brent's
-// search for a maximum (pitch candidates, syllable nuclei).
+// What more than one MSHDS translation unit uses (mshds.hip, mshds_pitch.hip, mshds_formant.hip, mshds_pulses.hip,
+// mshds_ltas.hip, mshds_cpp.hip): the clip table rows, Praat's sample-index rounding, the wave / lane-group helpers of the
+// sinc interpolation, and Brent's search for a maximum (pitch candidates, syllable nuclei).
 // Every MSHDS .hip includes this header before any code of its own: the three headers below are compiled with FMA
 // contraction on, everything after the pragma (the rest of this header and the including file) with it off.
 #pragma once
@@ -72,6 +72,14 @@ __device__ __forceinline__ double fast_rcp(double d) {
     r = r * (2.0 - d * r);
     r = r * (2.0 - d * r);
     return r;
+}
+
+// LDS that the lanes of ONE wave wrote becomes visible to its other lanes (a wave's LDS operations complete in order: this
+// orders the compiler's accesses and keeps the wave's lanes together)
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {      // l must be wave-uniform

@@ -1,5 +1,5 @@
 // Praat's whole-sound FFT low-pass (Sound_resample, anti-aliasing branch) for gfx950: device code shared by the resampler in
-// front of the extractors (resample.hip), the 10 kHz resampling of To Formant (burg) (mshds_voice.hip) and the per-interval one of To
+// front of the extractors (resample.hip), the 10 kHz resampling of To Formant (burg) (mshds_formant.hip) and the per-interval one of To
 // PowerCepstrogram (mshds_cpp.hip).
 #pragma once
 #include <hip/hip_runtime.h>

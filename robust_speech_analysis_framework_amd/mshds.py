@@ -2,11 +2,11 @@
 
 The reference runs ~10 Praat analyses per file through parselmouth, one file at a time, with Python
 loops per pulse / per frame (``src/mshds_extractor.py:11-376``).  Here the analyses of a whole batch
-run as float64 HIP kernels (``csrc/mshds.hip``, ``csrc/mshds_voice.hip``); the host only builds the frame grids (Praat's
+run as float64 HIP kernels (``csrc/mshds*.hip``); the host only builds the frame grids (Praat's
 ``Sampled_shortTermAnalysis`` arithmetic), the window tables, and routes each clip to the
 speaker-adapted pitch range that ``_pitch_values`` chooses (``:127-162``).
 
-All 25 columns are computed on the device (``csrc/mshds.hip``, ``mshds_voice.hip``, ``mshds_cpp.hip``); there is no CPU
+All 25 columns are computed on the device (``csrc/mshds*.hip``); there is no CPU
 fallback.  A helper that fails in the reference gives NaN for its columns there (``except: return nan``);
 the kernels reproduce those cases (too-short clips, no voiced frames, no periods) as NaN as well.
 """
@@ -48,9 +48,13 @@ CPP_HDR_FIELDS = ("n_seg", "fail", "total_frames", "total_resampled")
 CPP_HDR = {name: i for i, name in enumerate(CPP_HDR_FIELDS)}
 CPP_HDR_INTS = len(CPP_HDR_FIELDS)        # 4
 CPP_NQ_MAX = 513                          # NQ_MAX: quefrency bins of the 1024-point transform
+# struct ResampleInfo and struct FormantFrame of csrc/mshds_voice_layout.h (tests/test_voice_layout_host.py holds the offsets
+# to the header's)
 RESAMPLE_INFO = np.dtype([("sample_off", "<i8"), ("out_off", "<i8"), ("pos0", "<f8"), ("x1o", "<f8"),
                           ("n_in", "<i4"), ("n_out", "<i4"), ("table", "<i4"), ("pad", "<i4")])
 assert RESAMPLE_INFO.itemsize == 48
+FORMANT_FRAME = np.dtype([("f", "<f8", (5,)), ("b", "<f8", (5,))])
+FORMANT_FRAME_DOUBLES = FORMANT_FRAME.itemsize // 8     # 10
 LP_SIG = np.dtype([("in_off", "<i8"), ("out_off", "<i8"), ("work_off", "<i8"), ("n", "<i4"), ("lg", "<i4")])
 assert LP_SIG.itemsize == 32
 RS_DEPTH = 500
@@ -82,14 +86,14 @@ def resample10k_tables(pos0: float, depth: int = RS_DEPTH):
     return np.stack(rows), bs
 
 
-def short_term_frames(n_samples: int, window_duration: float, time_step: float, x1: float = 0.5 * DX):
-    """Praat Sampled_shortTermAnalysis of a sound of ``n_samples`` samples whose first sample lies at ``x1``:
-    (frames, time of first frame); integer-exact contract.  The physical duration is nx * dx (not the domain)."""
-    duration = n_samples * DX
+def short_term_frames(n_samples: int, window_duration: float, time_step: float, x1: float = 0.5 * DX, dx: float = DX):
+    """Praat Sampled_shortTermAnalysis of a sound of ``n_samples`` samples of period ``dx`` whose first sample lies at
+    ``x1``: (frames, time of first frame); integer-exact contract.  The physical duration is nx * dx (not the domain)."""
+    duration = n_samples * dx
     if window_duration > duration:
         return 0, 0.0
     nf = int(math.floor((duration - window_duration) / time_step)) + 1
-    mid = x1 - 0.5 * DX + 0.5 * duration
+    mid = x1 - 0.5 * dx + 0.5 * duration
     t1 = mid - 0.5 * nf * time_step + 0.5 * time_step
     return nf, t1
 
@@ -476,7 +480,6 @@ class MshdsEngine:
     def formants(self, wav, sample_offs, lengths, gpeak, floor, ceiling, frame_shift=0.005, stream=None, dom=None):
         """``_measureFormants`` (:303-338) -> float64 [n, 8] (mean/SD of F1, B1, F2, B2 at the pulses)."""
         import torch
-        lib = _lib.load()
         n = len(lengths)
         dev = self.device
         dom = dom if dom is not None else SoundDomain(lengths)
@@ -492,8 +495,24 @@ class MshdsEngine:
                                     stream, dom.sub(ids))
                 out[_dev(np.asarray(ids, dtype=np.int64), dev)] = sub
             return out
-        dxo = 1.0 / RS_RATE
-        ratio = RS_RATE / FS
+        if n == 0:
+            return torch.full((0, 8), float("nan"), dtype=torch.float64, device=dev)
+        ri, ri_d, y10 = self._resample10k(wav, sample_offs, lengths, dom, stream)
+        ci, ci_d, frames = self._formant_frames(ri, ri_d, y10, dom, frame_shift, stream)
+        out, p, pulses, npul, max_pulses = self._formant_stats_at_pulses(wav, sample_offs, lengths, gpeak, floor, ceiling,
+                                                                         frame_shift, frames, ci_d, stream, dom)
+        self._last_formants = {"frames": frames, "ci": ci, "pulses": pulses, "n_pulses": npul, "max_pulses": max_pulses,
+                               "y10": y10, "ri": ri, "pitch": p}
+        return out
+
+    def _resample10k(self, wav, sample_offs, lengths, dom, stream):
+        """Sound_resample(10000, 500) of every clip (n >= 1): the plan (one ``RESAMPLE_INFO`` row per clip, one weight table
+        per distinct position of the 10 kHz grid), the whole-sound FFT low-pass (16 kHz -> 10 kHz goes down), then the sinc
+        interpolation -> (plan, plan on the device, the 10 kHz samples of all clips)."""
+        import torch
+        lib = _lib.load()
+        n = len(lengths)
+        dev = self.device
         ri = np.zeros(n, dtype=RESAMPLE_INFO)
         lps = np.zeros(n, dtype=LP_SIG)
         tabs, bases, key_to_table = [], [], {}
@@ -514,18 +533,14 @@ class MshdsEngine:
             lps[i] = (int(so), int(so), work_off, int(nn), lg)
             out_off += m
             work_off += 1 << (lg - 1)
-        max_out = int(ri["n_out"].max()) if n else 0
+        max_out = int(ri["n_out"].max())
         y10 = torch.empty(max(out_off, 1), dtype=torch.float64, device=dev)
-        out = torch.full((max(n, 1), 8), float("nan"), dtype=torch.float64, device=dev)
-        if n == 0:
-            return out[:0]
         ri_d = _dev(ri, dev)
         wstride = int(lib.rsaf_mshds_resample10k_table_stride(RS_DEPTH))   # rows zero-padded for the kernel's tap blocks
         tab = np.zeros((len(tabs), 5, wstride))
         tab[:, :, :2 * RS_DEPTH + 1] = np.stack(tabs)
         tab_d = _dev(tab.reshape(-1), dev)
         base_d = _dev(np.asarray(bases, dtype=np.int32).reshape(-1), dev)
-        # Sound_resample(10000, 500): whole-sound FFT low-pass (16 kHz -> 10 kHz goes down), then sinc interpolation
         lp = torch.empty(int(wav.numel()), dtype=torch.float64, device=dev)
         work = torch.empty(2 * work_off, dtype=torch.float64, device=dev)
         _lib.check(lib.rsaf_praat_lowpass_batch(_lib.ptr(wav), _lib.ptr(_dev(lps, dev)), n, int(lps["lg"].max()), RS_RATE * DX,
@@ -533,40 +548,45 @@ class MshdsEngine:
                    "rsaf_praat_lowpass_batch")
         _lib.check(lib.rsaf_mshds_resample10k(_lib.ptr(lp), _lib.ptr(ri_d), n, max_out, _lib.ptr(tab_d), wstride, _lib.ptr(base_d),
                                               RS_DEPTH, _lib.ptr(y10), _lib.stream_ptr(stream)), "rsaf_mshds_resample10k")
-        del work
-        # Formant (burg): 5 ms, 5 formants, 5 kHz, 25 ms half-window, pre-emphasis from 50 Hz  (:319)
+        return ri, ri_d, y10
+
+    def _formant_frames(self, ri, ri_d, y10, dom, frame_shift, stream):
+        """Formant (burg): 5 formants, 5 kHz, 25 ms half-window, pre-emphasis from 50 Hz (:319) on the 10 kHz clips of
+        ``_resample10k`` -> (frame grid as ``CLIP_INFO`` rows, the grid on the device, frames as rows of ``FORMANT_FRAME``)."""
+        import torch
+        n = len(ri)
+        dxo = 1.0 / RS_RATE
         dt_window = 0.05
         nsw = int(math.floor(dt_window / dxo))
-
         (win,) = self._table(("formant", nsw), lambda: (_gaussian_window(nsw),))
         ci = np.zeros(n, dtype=CLIP_INFO)
         foff = 0
         for i in range(n):
             m, x1o = int(ri[i]["n_out"]), float(ri[i]["x1o"])
-            duration = m * dxo
-            if dt_window > duration:
-                nf, t1 = 0, 0.0
-            else:
-                nf = int(math.floor((duration - dt_window) / frame_shift)) + 1
-                t1 = x1o - 0.5 * dxo + 0.5 * duration - 0.5 * nf * frame_shift + 0.5 * frame_shift
+            nf, t1 = short_term_frames(m, dt_window, frame_shift, x1o, dxo)
             ci[i] = (int(ri[i]["out_off"]), foff, t1, m, nf, x1o, dom.xmax[i])
             foff += nf
         mxf = int(ci["n_frames"].max())
-        frames = torch.empty(max(foff, 1) * 10, dtype=torch.float64, device=dev)
-        ci_d = _dev(ci, dev)
-        _lib.check(lib.rsaf_mshds_formants(_lib.ptr(y10), _lib.ptr(ri_d), _lib.ptr(ci_d), n, mxf, _lib.ptr(win), nsw,
-                                           frame_shift, dxo, math.exp(-2.0 * math.pi * 50.0 * dxo), _lib.ptr(frames),
-                                           _lib.stream_ptr(stream)), "rsaf_mshds_formants")
-        # To Pitch (cc) with parselmouth's defaults (:320) and the pulses (:321)
+        frames = torch.empty(max(foff, 1) * FORMANT_FRAME_DOUBLES, dtype=torch.float64, device=self.device)
+        ci_d = _dev(ci, self.device)
+        _lib.check(_lib.load().rsaf_mshds_formants(_lib.ptr(y10), _lib.ptr(ri_d), _lib.ptr(ci_d), n, mxf, _lib.ptr(win), nsw,
+                                                   frame_shift, dxo, math.exp(-2.0 * math.pi * 50.0 * dxo), _lib.ptr(frames),
+                                                   _lib.stream_ptr(stream)), "rsaf_mshds_formants")
+        return ci, ci_d, frames
+
+    def _formant_stats_at_pulses(self, wav, sample_offs, lengths, gpeak, floor, ceiling, frame_shift, frames, ci_d, stream, dom):
+        """To Pitch (cc) with parselmouth's defaults (:320), the pulses (:321), and mean / SD of F1, B1, F2, B2 of
+        ``frames`` at the pulses (:326-336) -> (float64 [n, 8], pitch, pulses, n_pulses, max_pulses)."""
+        import torch
+        n = len(lengths)
+        out = torch.full((n, 8), float("nan"), dtype=torch.float64, device=self.device)
         p = self.pitch(wav, sample_offs, lengths, gpeak, time_step=frame_shift, floor=floor, ceiling=ceiling,
                        periods=1.0, is_cc=True, refine_depth=70, stream=stream, dom=dom)
         pulses, npul, max_pulses = self.pulses(wav, lengths, p, stream)
-        _lib.check(lib.rsaf_mshds_formant_stats(_lib.ptr(frames), _lib.ptr(ci_d), n, frame_shift, _lib.ptr(pulses),
-                                                max_pulses, _lib.ptr(npul), _lib.ptr(out), _lib.stream_ptr(stream)),
+        _lib.check(_lib.load().rsaf_mshds_formant_stats(_lib.ptr(frames), _lib.ptr(ci_d), n, frame_shift, _lib.ptr(pulses),
+                                                        max_pulses, _lib.ptr(npul), _lib.ptr(out), _lib.stream_ptr(stream)),
                    "rsaf_mshds_formant_stats")
-        self._last_formants = {"frames": frames, "ci": ci, "pulses": pulses, "n_pulses": npul, "max_pulses": max_pulses,
-                               "y10": y10, "ri": ri, "pitch": p}
-        return out[:n]
+        return out, p, pulses, npul, max_pulses
 
     def pulses(self, wav, lengths, pitch, stream=None):
         """Sound & Pitch: To PointProcess (cc): pulse times per clip in ascending order -> (pulses, n_pulses, max_pulses)."""
